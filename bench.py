@@ -19,7 +19,11 @@ the one GPU, N=8: 1.25M each); the seed index is replicated per GPU.
   --scaling weak --reads-per-gpu 1000000      configs[1] per rank
   --read-len >= 500                           single-end long reads (configs[3]: `--scaling weak --reads-per-gpu 100000 --read-len 10000`)
 
-The ONE JSON line (rank 0) carries, next to the contract keys:
+A plain run sets up, warms up, times the `--steps` steps of `value` and prints the ONE JSON line (rank 0) with the contract
+keys (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step) and the workload's
+`config`.  `--dump-outputs DIR` then writes what the last timed step computed, as float64 .npy files (dump_outputs below);
+the inputs are the same from run to run, so two builds can be compared output for output.
+Everything else takes runs of its own and comes with `--full` only; its line carries, next to the contract keys:
   value_host_to_host     the PCIe-inclusive figure (inputs from pinned host memory), never `value`
   value_device_resident  one batch at a time, outputs left in HBM: the run the per-kernel timings come from
   pcie                   measured H2D / D2H GB/s of this box (pinned, 256 MB) and the PCIe-bound reads/s that follows
@@ -31,6 +35,8 @@ The ONE JSON line (rank 0) carries, next to the contract keys:
   real_reads             the repository's real example reads x8 through the same step
   cpu_baseline           the CPU path on the host cores, timed around bare C calls (no Python in the timed spans)
   checks.oracle          the GPU's results on the CPU baseline's sample against what the CPU path computed (same run)
+
+  equals_device_resident_run, checks   every batch of `value` against the one-batch-at-a-time run; sanity of its records
 
 Launched for N>1 as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -201,6 +207,74 @@ def oracle_checks(pmx, gpu, cpu, node_id, paired):
     return out
 
 
+def simulate_pairs_8d(synth, genome, n_pairs, first_pair, read_len, seed):
+    """synth.simulate_paired_reads_8d in stretches of 500k pairs on up to 8 threads (numpy lets go of the GIL for the bulk of
+    the work).  The stream is counter-based, so the reads are byte for byte those of one call; a plain run's set-up counts
+    against its time outside the steps, and one call takes ~17 s for 10M reads."""
+    from concurrent.futures import ThreadPoolExecutor
+    stretch = 500000
+    concat = np.empty(2 * n_pairs * read_len, np.uint8)
+    n_cpu, quota = usable_cpus()
+    threads = max(1, min(8, n_cpu, int(quota) if quota else n_cpu))
+
+    def one(lo):
+        n = min(stretch, n_pairs - lo)
+        part, _ = synth.simulate_paired_reads_8d(genome, n, first_pair=first_pair + lo, read_len=read_len, seed=seed)
+        concat[2 * lo * read_len:2 * (lo + n) * read_len] = part
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(one, range(0, n_pairs, stretch)))
+    return concat, np.arange(2 * n_pairs + 1, dtype=np.int64) * read_len
+
+
+REC_FIELDS = ("rs", "re", "qs", "qe", "mapq", "rev", "proper_frag", "mapped", "n_cigar", "flags", "score")
+DUMP_RECORDS = 131072          # records in a dump: a fixed, seeded sample when the batch has more
+DUMP_BYTES = 64 << 20
+
+
+def cigar_ops(r_, arena):
+    """every CIGAR operation in record order (the arena is bump-allocated: its layout differs from run to run)"""
+    k = r_["n_cigar"].astype(np.int64)
+    tot = int(k.sum())
+    if tot == 0:
+        return np.zeros(0, np.uint32)
+    first = np.cumsum(k) - k
+    idx = np.repeat(r_["cigar_off"].astype(np.int64) - first, k) + np.arange(tot, dtype=np.int64)
+    return np.asarray(arena).view(np.uint32)[idx]
+
+
+def dump_outputs(path, recs, arena, result, node_scores):
+    """--dump-outputs: what the last timed step handed its caller, as float64 arrays (every value is an integer below 2^53
+    or a double, so nothing is rounded), DUMP_BYTES at most:
+      records.npy       [k, 11] the fields REC_FIELDS of k records (cigar_off is left out: an arena offset, not a result)
+      record_index.npy  [k] the reads they belong to: every read up to DUMP_RECORDS, else a sorted sample drawn with seed
+                        12345, cut short where the records and their CIGARs would pass DUMP_BYTES (long reads)
+      cigar_ops.npy     the CIGAR operations (length << 4 | op) of those records, in record order
+      placement.npy     [5, 2] best score and best node index per metric (TSV order)
+      ties.npy          [t, 2] (metric, node index) of every tied node
+      node_scores.npy   [nodes, 5] every node's score per metric"""
+    os.makedirs(path, exist_ok=True)
+    n = len(recs)
+    if n > DUMP_RECORDS:
+        idx = np.sort(np.random.default_rng(12345).choice(n, DUMP_RECORDS, replace=False))
+    else:
+        idx = np.arange(n)
+    sample = recs[idx]
+    ties = [(m, int(t)) for m, tied in enumerate(result.tied_indices) for t in tied]
+    fixed = 8 * (node_scores.size + 2 * len(ties) + 10) + 4096          # (+ the .npy headers)
+    cost = np.cumsum(8 * (len(REC_FIELDS) + 1 + sample["n_cigar"].astype(np.int64)))
+    keep = int(np.searchsorted(cost, DUMP_BYTES - fixed, side="right"))
+    idx, sample = idx[:keep], sample[:keep]
+    arrays = {"records": np.stack([sample[f].astype(np.float64) for f in REC_FIELDS], axis=1).reshape(len(sample), len(REC_FIELDS)),
+              "record_index": idx.astype(np.float64),
+              "cigar_ops": cigar_ops(sample, arena).astype(np.float64),
+              "placement": np.array([result.best_score, result.best_index], np.float64).T.reshape(-1, 2),
+              "ties": np.array(ties, np.float64).reshape(-1, 2),
+              "node_scores": np.asarray(node_scores, np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    return sum(a.nbytes for a in arrays.values())
+
+
 class Sequencer:
     """Collectives issued from several host threads must reach the process group in ONE order on every rank.  The batches
     are numbered; batch i has a histogram exchange H_i and a result gather G_i; with P pipelines the order is H_0 .. H_{P-1},
@@ -265,6 +339,11 @@ def main():
     ap.add_argument("--gather", choices=["sharded", "rccl"], default="sharded",
                     help="N>1: how the records reach the host -- sharded: every rank downloads its own part over its own PCIe link into "
                          "one shared-memory result set (pmx_dist_plan_alignments); rccl: everything to rank 0 over RCCL, then one download")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond `value`: the PCIe-inclusive and one-batch-at-a-time figures, PCIe and HBM "
+                         "copy rates, per-stage rooflines, real reads, the DP service, the CPU baseline and the same-run parity check against it "
+                         "(the --no-* switches apply to this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float64, 64 MB at most)")
     args = ap.parse_args()
 
     import torch
@@ -329,7 +408,7 @@ def main():
         del lst, cb
     else:
         first_pair = (lo // 2) if args.scaling == "strong" else rank * (my_reads // 2)
-        concat, off = synth.simulate_paired_reads_8d(src, my_reads // 2, first_pair=first_pair, read_len=args.read_len, seed=42)
+        concat, off = simulate_pairs_8d(synth, src, my_reads // 2, first_pair, args.read_len, 42)
     n_reads = len(off) - 1
     max_len = int(np.max(np.diff(off))) if n_reads else 0
     mean_len = int(off[-1] // max(n_reads, 1))
@@ -380,7 +459,7 @@ def main():
         out["duplex_each_GBps"] = reps * nbytes / (time.perf_counter() - t0) / 1e9
         return out
 
-    pcie = measure_pcie()
+    pcie = measure_pcie() if args.full else None
 
     def measure_copy_ceiling(nbytes=1 << 30, reps=5):
         """what this box's HBM sustains for the simplest streaming kernel there is: a device-to-device copy of 1 GB
@@ -399,7 +478,7 @@ def main():
         del a, b
         return 2.0 * nbytes / (ms * 1e-3) / 1e9
 
-    copy_ceiling = measure_copy_ceiling() if rank == 0 else None
+    copy_ceiling = measure_copy_ceiling() if args.full and rank == 0 else None
 
     # ------------------------------------------------------------------------------------------------------ pipelines
     h_concat = torch.from_numpy(concat).pin_memory()
@@ -706,7 +785,7 @@ def main():
     for pp in pipes:
         pp.alloc_outputs()
     h2h = None
-    if not args.no_host_to_host:
+    if args.full and not args.no_host_to_host:
         run_batches(max(args.warmup, 2 * len(pipes)))   # (untimed; two steps per pipeline: the second sizes what the first one's counts asked for)
         sync_all()
         t0 = time.perf_counter()
@@ -736,6 +815,92 @@ def main():
     h2h_recs = [None if pp.out_recs is None else pp.out_recs.numpy().view(pmx.REC_DTYPE).reshape(-1) for pp in pipes]
     h2h_nw = [pp.nw for pp in pipes]
     h2h_nodes = [None if pp.res is None else int(pp.res.best_index[4]) for pp in pipes]
+
+    def headline():
+        """the contract keys and the workload of `value` (rank 0): all of a plain run's line, the first keys of the full one"""
+        ms_per_step = elapsed / args.steps * 1e3
+        value = total_reads * args.steps / elapsed
+        return {
+            "metric": "reads placed+aligned/sec, %gM×%dbp vs 20k-genome PanMAN, 1/2/4/8 MI355X" % (total_reads / 1e6, args.read_len),
+            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "u8/i8 DP + u64 hash + f64 score", "data": "synthetic",
+            "config": {"workload": ("%gM x %dbp synthetic %s reads %s vs SARS-CoV-2 20k PanMAN (39,999 nodes), place+align, inputs resident in HBM -> records in pinned host memory (%s%s)"
+                                    % ((total_reads if args.scaling == "strong" else n_reads) / 1e6, args.read_len,
+                                       "paired" if paired else "single-end long (2% sub, 1.5% ins, 1.5% del)",
+                                       "in total, read-sharded over the ranks" if args.scaling == "strong" else "per GPU",
+                                       "configs[3]" if long_reads else ("configs[2]" if args.scaling == "strong" and args.total_reads == 10000000 else
+                                                                        ("configs[1]" if n_reads == 1000000 else "custom size")),
+                                       "" if world == 1 else "; seed index replicated, RCCL histogram all-gather + record/CIGAR gather")),
+                       "reads_per_gpu": n_reads, "total_reads": total_reads, "read_len": args.read_len,
+                       "warmup_steps_run": max(args.warmup, 2 * len(pipes)),
+                       "source_node": pm.node_id(src_node),
+                       "generator": ("SURVEY 8d: leaf number splitmix64(42) mod 20000 of the tree, one splitmix64(42) stream, 35 draws per pair "
+                                     "(start, insert ~ N(300,30) in [150,600], 0.2 % i.i.d. substitutions as geometric gaps), FR, no indels / N"
+                                     if not long_reads else "numpy PCG64 seed 43 + rank: 2 % sub, 1.5 % ins, 1.5 % del"),
+                       "batches_in_flight": len(pipes), "h2d_chunks": n_chunks,
+                       "index": "k=19,s=8,l=3,closed syncmers,flank-mask 250",
+                       "aligner_preset": ("k=21,w=11,a=2,b=8,q=12,e=2,q2=24,e2=1 (src/mm_align.c:140-166)" if not long_reads else
+                                          "map-hifi / map-ont branch of setup_minimap2 (src/mm_align.c:167-180)")},
+            "value_is": "inputs (ASCII bases + offsets of the batch) resident in HBM when the timed region starts -> pack -> seed -> score -> "
+                        "genome -> reference index -> align -> records + CIGAR arena in pinned host memory; %d batch(es) in flight" % len(pipes),
+        }
+
+    def close_and_print(out):
+        """close the pipelines, free the shared result set, leave the process group; rank 0 prints the line"""
+        nonlocal h2h_recs, saved_stdout_fd
+        for pp in pipes:
+            pp.close()
+        if shm_keep:
+            torch.cuda.synchronize()
+            for pp in pipes:
+                pp.out_recs = pp.out_cig = None
+            h2h_recs = None
+            if dist_on:
+                dist.barrier()
+            for segs, arrs in shm_keep:
+                for a_ in arrs:
+                    torch.cuda.cudart().cudaHostUnregister(a_.ctypes.data)
+            for segs, arrs in shm_keep:
+                del arrs
+                for sg in segs:
+                    try:
+                        sg.close()
+                    except BufferError:
+                        pass          # (a view is still alive somewhere: the mapping goes with the process)
+                    if rank == 0:
+                        sg.unlink()
+            shm_keep.clear()
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        if out is None and saved_stdout_fd is not None:   # other ranks: whatever is still buffered goes to stderr too
+            try:
+                import ctypes
+                ctypes.CDLL(None).fflush(None)
+            except Exception:
+                pass
+        if out is not None:
+            # the C buffers (the banner) are flushed to where descriptor 1 points now -- stderr -- before it is restored
+            try:
+                import ctypes
+                ctypes.CDLL(None).fflush(None)
+            except Exception:
+                pass
+            sys.stdout.flush()
+            if saved_stdout_fd is not None:
+                os.dup2(saved_stdout_fd, 1)
+                os.close(saved_stdout_fd)
+                saved_stdout_fd = None
+            print(json.dumps(out), flush=True)
+
+    if args.dump_outputs and rank == 0:
+        last = pipes[(args.steps - 1) % len(pipes)]           # (pipeline p takes the batches p, p + P, p + 2P, ...)
+        dump_outputs(args.dump_outputs, last.out_recs.numpy().view(pmx.REC_DTYPE).reshape(-1), last.out_cig[:last.nw].numpy(),
+                     last.res, last.placer.node_outputs()[0])
+    if not args.full:
+        close_and_print(headline() if rank == 0 else None)
+        return
 
     # ---------------------------------------------------------------- value_device_resident (one batch at a time, no PCIe)
     kernel_ms = {"align": [], "align_dom": [], "align_cseeds": [], "seed": [], "score": [], "pack": []}
@@ -775,16 +940,6 @@ def main():
     mean_cigar = float(np.mean(recs["n_cigar"]))
     same_as_resident = None
     gather_ok = None
-
-    def cigar_ops(r_, arena):
-        """every CIGAR operation in record order (the arena is bump-allocated: its layout differs from run to run)"""
-        k = r_["n_cigar"].astype(np.int64)
-        tot = int(k.sum())
-        if tot == 0:
-            return np.zeros(0, np.uint32)
-        first = np.cumsum(k) - k
-        idx = np.repeat(r_["cigar_off"].astype(np.int64) - first, k) + np.arange(tot, dtype=np.int64)
-        return np.asarray(arena).view(np.uint32)[idx]
 
     if rank == 0:
         same_as_resident = True
@@ -918,38 +1073,15 @@ def main():
                                "results equal ksw_extd2_sse of the reference (tests/test_dp_service_gpu.py)")
 
     if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        value = total_reads * args.steps / elapsed
+        out = headline()
+        value = out["value"]
         # bytes one step moves over PCIe (per rank; rank 0 downloads the gathered records of every rank)
         up_bytes = int(concat.size) + 8 * (n_reads + 1)
         down_bytes = 32 * n_out + 4 * max(h2h_nw)
         t_pcie = max(up_bytes / (pcie["h2d_GBps"] * 1e9), down_bytes / (pcie["d2h_GBps"] * 1e9))
         pcie.update(h2d_bytes_per_step=up_bytes, d2h_bytes_per_step=down_bytes, bound_reads_per_s=total_reads / t_pcie,
                     note="pinned host memory, 256 MB copies; bound = total reads / max(H2D time, D2H time) of one step at these rates (rank 0)")
-        out = {
-            "metric": "reads placed+aligned/sec, %gM×%dbp vs 20k-genome PanMAN, 1/2/4/8 MI355X" % (total_reads / 1e6, args.read_len),
-            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "u8/i8 DP + u64 hash + f64 score", "data": "synthetic",
-            "config": {"workload": ("%gM x %dbp synthetic %s reads %s vs SARS-CoV-2 20k PanMAN (39,999 nodes), place+align, inputs resident in HBM -> records in pinned host memory (%s%s)"
-                                    % ((total_reads if args.scaling == "strong" else n_reads) / 1e6, args.read_len,
-                                       "paired" if paired else "single-end long (2% sub, 1.5% ins, 1.5% del)",
-                                       "in total, read-sharded over the ranks" if args.scaling == "strong" else "per GPU",
-                                       "configs[3]" if long_reads else ("configs[2]" if args.scaling == "strong" and args.total_reads == 10000000 else
-                                                                        ("configs[1]" if n_reads == 1000000 else "custom size")),
-                                       "" if world == 1 else "; seed index replicated, RCCL histogram all-gather + record/CIGAR gather")),
-                       "reads_per_gpu": n_reads, "total_reads": total_reads, "read_len": args.read_len,
-                       "warmup_steps_run": max(args.warmup, 2 * len(pipes)),
-                       "source_node": pm.node_id(src_node),
-                       "generator": ("SURVEY 8d: leaf number splitmix64(42) mod 20000 of the tree, one splitmix64(42) stream, 35 draws per pair "
-                                     "(start, insert ~ N(300,30) in [150,600], 0.2 % i.i.d. substitutions as geometric gaps), FR, no indels / N"
-                                     if not long_reads else "numpy PCG64 seed 43 + rank: 2 % sub, 1.5 % ins, 1.5 % del"),
-                       "batches_in_flight": len(pipes), "h2d_chunks": n_chunks,
-                       "index": "k=19,s=8,l=3,closed syncmers,flank-mask 250",
-                       "aligner_preset": ("k=21,w=11,a=2,b=8,q=12,e=2,q2=24,e2=1 (src/mm_align.c:140-166)" if not long_reads else
-                                          "map-hifi / map-ont branch of setup_minimap2 (src/mm_align.c:167-180)")},
-            "value_is": "inputs (ASCII bases + offsets of the batch) resident in HBM when the timed region starts -> pack -> seed -> score -> "
-                        "genome -> reference index -> align -> records + CIGAR arena in pinned host memory; %d batch(es) in flight" % len(pipes),
+        out.update({
             "equals_device_resident_run": same_as_resident,
             "value_host_to_host": None if h2h is None else h2h["value"],
             "host_to_host": None if h2h is None else dict(h2h, note="the same step fed from pinned host memory (H2D of the bases + offsets, double-buffered, "
@@ -958,7 +1090,7 @@ def main():
             "device_resident": None if resident is None else dict(resident, note="one batch at a time, outputs left in HBM: the run the kernel timings come from"),
             "pcie": pcie,
             "host_to_host_over_min_of_value_and_pcie_bound": None if h2h is None else h2h["value"] / min(value, pcie["bound_reads_per_s"]),
-        }
+        })
         if resident is not None:
             align_ms = float(np.mean(kernel_ms["align"]))
             dom_ms = float(np.mean(kernel_ms["align_dom"]))
@@ -1123,50 +1255,7 @@ def main():
             out["cpu_baseline"] = None
     else:
         out = None
-    for pp in pipes:
-        pp.close()
-    if shm_keep:
-        torch.cuda.synchronize()
-        for pp in pipes:
-            pp.out_recs = pp.out_cig = None
-        h2h_recs = None
-        if dist_on:
-            dist.barrier()
-        for segs, arrs in shm_keep:
-            for a_ in arrs:
-                torch.cuda.cudart().cudaHostUnregister(a_.ctypes.data)
-        for segs, arrs in shm_keep:
-            del arrs
-            for sg in segs:
-                try:
-                    sg.close()
-                except BufferError:
-                    pass          # (a view is still alive somewhere: the mapping goes with the process)
-                if rank == 0:
-                    sg.unlink()
-        shm_keep.clear()
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
-    if out is None and saved_stdout_fd is not None:   # other ranks: whatever is still buffered goes to stderr too
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-    if out is not None:
-        # the C buffers (the banner) are flushed to where descriptor 1 points now -- stderr -- before it is restored
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        sys.stdout.flush()
-        if saved_stdout_fd is not None:
-            os.dup2(saved_stdout_fd, 1)
-            os.close(saved_stdout_fd)
-            saved_stdout_fd = None
-        print(json.dumps(out), flush=True)
+    close_and_print(out)
 
 
 if __name__ == "__main__":

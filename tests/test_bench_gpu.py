@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -18,7 +19,7 @@ def _line(out):
 
 
 def test_bench_single_rank_line():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--total-reads", "400000", "--cpu-sample", "20000"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--total-reads", "400000", "--cpu-sample", "20000"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -49,7 +50,7 @@ def test_bench_single_rank_line():
 def test_bench_two_ranks_functional():
     env = dict(os.environ, PMX_BENCH_TEST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29531", "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "2", "--scaling", "weak", "--reads-per-gpu", "100000",
+                        "--master-port", "29531", "bench.py", "--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--scaling", "weak", "--reads-per-gpu", "100000",
                         "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = _line(r.stdout)
@@ -63,7 +64,7 @@ def test_bench_exchange_path_on_rccl_one_rank():
     """the N>1 code path -- RCCL process group, histogram all-gather + device merge, record / CIGAR gather, barriers, max over
     ranks -- in a one-rank group on the real backend (PMX_BENCH_FORCE_DIST; a box of the pool has one GPU)"""
     env = dict(os.environ, PMX_BENCH_FORCE_DIST="1")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--total-reads", "100000", "--no-cpu-baseline", "--no-real-reads"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--total-reads", "100000", "--no-cpu-baseline", "--no-real-reads"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1, r.stdout[:600]   # ONE JSON line (RCCL's banner goes to stderr)
@@ -79,7 +80,7 @@ def test_bench_strong_scaling_two_ranks():
     its own part into the node's shared result set (pmx_dist_plan_alignments + pmx_dist_fetch_shard_async)"""
     env = dict(os.environ, PMX_BENCH_TEST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--scaling", "strong",
+                        "--master-port", "29533", "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--scaling", "strong",
                         "--total-reads", "200000", "--no-cpu-baseline", "--gather", "rccl"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = _line(r.stdout)
@@ -96,3 +97,36 @@ def test_two_rank_gather_equals_single_rank():
     assert d["n_records"] == d["n_expected"] == 40000
     assert d["fields_equal"] and d["cigars_equal"] and d["flagged"] == 0
     assert d["rank1_base_nonzero"] and d["rank1_has_cigars"] and d["multi_op_cigars"] > 1000
+
+
+def test_bench_plain_run_and_dump(tmp_path, sars):
+    """a plain run (no --full) times the steps of `value` only, prints the contract keys, and --dump-outputs writes what its
+    last step computed: the same arrays from two runs with the same arguments"""
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / ("dump%d" % run)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--total-reads", "200000",
+                            "--dump-outputs", str(d_out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1, r.stdout[:600]
+        d = _line(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "reads/s" and d["higher_is_better"] is True
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 200000) < 1.0          # reads of one step / its time
+        for k in ("cpu_baseline", "pcie", "roofline", "real_reads", "value_device_resident", "checks"):
+            assert k not in d, k
+        files = sorted(os.listdir(d_out))
+        assert files == ["cigar_ops.npy", "node_scores.npy", "placement.npy", "record_index.npy", "records.npy", "ties.npy"], files
+        arrs = {f[:-4]: np.load(d_out / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(os.path.getsize(d_out / f) for f in files) <= 64 << 20
+        recs, idx = arrs["records"], arrs["record_index"]
+        assert recs.shape == (131072, 11) and len(idx) == 131072 and np.all(np.diff(idx) > 0) and idx[-1] < 200000
+        assert len(arrs["cigar_ops"]) == int(recs[:, 8].sum())
+        assert np.mean(recs[:, 7]) > 0.99 and not np.any(recs[:, 9].astype(np.int64) & 3)       # mapped; no overflow / unsupported
+        assert sars.node_id(int(arrs["placement"][4, 1])) == d["config"]["source_node"]
+        assert arrs["node_scores"].shape == (sars.num_nodes, 5)
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

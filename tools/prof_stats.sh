@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_$tag
 rm -rf $O && mkdir -p $O
 cd $R
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -- python3 bench.py "$@" > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -- python3 bench.py --full "$@" > $O/bench.json 2> $O/bench.err
 find $O/t -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 rm -rf $O/t
 python3 - "$O/kernel_stats.csv" <<'P'

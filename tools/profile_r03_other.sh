@@ -8,7 +8,7 @@ rm -rf $O && mkdir -p $O
 cd $R
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rr_stats -- python3 tools/real_reads.py > $O/real_reads.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d $O/rr_sq -- python3 tools/real_reads.py > $O/real_reads_sq.log 2>&1
-LR="bench.py --scaling weak --reads-per-gpu 8000 --read-len 10000 --steps 2 --warmup 1 --no-cpu-baseline --pipelines 1"
+LR="bench.py --full --scaling weak --reads-per-gpu 8000 --read-len 10000 --steps 2 --warmup 1 --no-cpu-baseline --pipelines 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/lr_stats -- python3 $LR > $O/long_reads.json 2> $O/long_reads.log
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --kernel-trace --output-format csv -d $O/lr_sq -- python3 $LR > $O/long_reads_sq.json 2> $O/long_reads_sq.log
 find $O/rr_stats -name "*kernel_stats.csv" -exec cp {} $O/real_reads_kernel_stats.csv \;

@@ -6,8 +6,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_r04_pmc
 rm -rf $O && mkdir -p $O
 cd $R
-ARGS="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-real-reads --no-host-to-host --pipelines 1"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-real-reads --no-host-to-host > $O/stats_bench.json 2> $O/stats.log
+ARGS="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-real-reads --no-host-to-host --pipelines 1"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-real-reads --no-host-to-host > $O/stats_bench.json 2> $O/stats.log
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 $ARGS > $O/fetch.log 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 $ARGS > $O/write.log 2>&1
 timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_BUSY_CYCLES SQ_WAVES --kernel-trace --output-format csv -d $O/sq -- python3 $ARGS > $O/sq.log 2>&1

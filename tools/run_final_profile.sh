@@ -1,6 +1,6 @@
 #!/bin/bash
 # End-of-round record on a GPU box (from the repo root): PMC passes + kernel statistics (tools/profile_r04_pmc.sh,
-# tools/prof_stats.sh), the driver's bench command and the 1.25M-read line (tools/run_final_bench.sh), the GPU suite.
+# tools/prof_stats.sh), the driver's bench command and the 1.25M-read line (tools/run_final_bench.sh, into out/), the GPU suite.
 # Outputs under gpurun_out/; copy what is to be kept into profiles/rNN/.
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 bash tools/profile_r04_pmc.sh > gpurun_out/pmc_r04.log 2>&1
