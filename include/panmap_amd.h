@@ -476,7 +476,7 @@ int pmx_meta_candidates(const pmx_meta *m, uint32_t *dfs_index, int64_t cap);   
 int pmx_meta_overlap_coefficients(const pmx_meta *m, double *oc, int64_t cap);         /* per node */
 int pmx_meta_read_info(const pmx_meta *m, int64_t *n_seedmers, int64_t *multiplicity, int64_t cap);
 int pmx_meta_read_seedmers(const pmx_meta *m, int64_t *offsets, uint64_t *hash, uint8_t *rev, int64_t cap_seedmers);
-int pmx_meta_scores(pmx_ctx *ctx, pmx_meta *m, uint16_t *scores, int64_t cap);         /* [reads][candidates] */
+int pmx_meta_scores(pmx_ctx *ctx, pmx_meta *m, uint16_t *scores, int64_t cap);         /* [reads][candidates]; see pmx_meta_row_range */
 /* the estimated haplotypes, by proportion (descending): representative node, proportion, the candidates merged into it */
 int64_t pmx_meta_num_haplotypes(const pmx_meta *m);
 int pmx_meta_haplotype(const pmx_meta *m, int64_t i, uint32_t *node, double *prop, int64_t *n_members, uint32_t *members,
@@ -486,6 +486,13 @@ int pmx_meta_em_info(const pmx_meta *m, int32_t *rounds, int32_t *iterations, do
  * greater than T (src/mgsr.cpp:1593-1594, 1833-1834).  pmx_read_dust = mgsr::getDust (src/mgsr.cpp:1505-1568; host, no
  * device): Prinseq-scaled score over base triplets in a sliding window of `window` triplets (the reference uses 64). */
 int pmx_meta_set_dust(pmx_meta *m, double threshold);
+/* --meta --gpus N: call after pmx_meta_create, before pmx_meta_set_reads (`d` on the same context, kept alive by the caller).
+ * From then on set_reads, score and em are COLLECTIVE: every rank calls them in the same order, set_reads with its own shard of
+ * the raw reads.  The merged reads, overlap coefficients, candidates, haplotypes and em_info are then those of one rank over the
+ * whole sample, bit for bit, on every rank.  pmx_meta_scores returns only this rank's rows: merged reads [first, first + count)
+ * (pmx_meta_row_range; without a dist: 0 and num_reads). */
+int pmx_meta_attach_dist(pmx_meta *m, pmx_dist *d);
+int pmx_meta_row_range(const pmx_meta *m, int64_t *first, int64_t *count);
 double pmx_read_dust(const char *seq, int64_t len, int32_t window);
 
 /* The library's tuning / testing / diagnostic switches are environment variables PMX_<NAME>, all of them listed with their

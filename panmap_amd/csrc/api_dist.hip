@@ -225,6 +225,18 @@ struct pmx_dist {
     }
 };
 
+namespace pmx {
+pmx_ctx* dist_ctx(const pmx_dist* d) { return d->ctx; }
+void dist_all_gather(pmx_dist* d, const void* d_mine, size_t bytes, void* d_all) {
+    PMX_HIP(hipSetDevice(d->ctx->device));
+    d->tp->all_gather(d->ctx->stream, d_mine, bytes, d_all);
+}
+std::vector<int64_t> dist_exchange_counts(pmx_dist* d, const int64_t* mine, int k) {
+    PMX_HIP(hipSetDevice(d->ctx->device));
+    return d->exchange_counts(mine, k);
+}
+}  // namespace pmx
+
 extern "C" {
 
 int pmx_dist_unique_id(char id[PMX_DIST_ID_BYTES]) {

@@ -46,6 +46,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "api_internal.hpp"
 #include "device/dev_util.hpp"
 #include "host/index_build.hpp"
 #include "host/seed_host.hpp"
@@ -64,6 +65,10 @@ int fail(int code, const std::string& msg) {
     }                                                                  \
     catch (const HipError& e) { return fail(PMX_ERR_DEVICE, e.msg); }  \
     catch (const std::exception& e) { return fail(PMX_ERR_DEVICE, e.what()); }
+
+// the EM's two fixed-order reductions: reads per partial column sum (k_meta_colsum) and values per block sum (k_meta_sum_blocks)
+constexpr int64_t kColsumChunk = 256;
+constexpr int64_t kSumBlock = 1024;
 
 // index of `key` in the ascending array keys[0..n), or -1
 __device__ __forceinline__ int64_t find_sorted(const uint64_t* __restrict__ keys, int64_t n, uint64_t key) {
@@ -169,6 +174,25 @@ __global__ void k_meta_column_digest(const uint16_t* __restrict__ score, int64_t
     }
 }
 
+// --gpus N, pass A of the EM rows: each read's best score over the candidates and whether the --discard rule of pmx_meta_em
+// keeps it (the same integer arithmetic as the host loop of the one-rank path, which downloads the whole matrix instead).
+// A wave per read; the maximum is order-free.
+__global__ void k_meta_row_keep(const uint16_t* __restrict__ score, int64_t n_reads, int n_cand, const int64_t* __restrict__ read_off,
+                                double discard, uint8_t* __restrict__ keep) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        const uint16_t* srow = score + (size_t)r * (size_t)n_cand;
+        int mx = 0;
+        for (int c = lane; c < n_cand; c += 64) mx = max(mx, (int)srow[c]);
+        for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+        if (lane == 0) {
+            const int64_t n_seed = read_off[r + 1] - read_off[r];
+            keep[r] = (mx == 0 || mx < (int)((double)n_seed * discard)) ? 0 : 1;
+        }
+    }
+}
+
 // EM pass 1: denom[j] = 1 / sum_i P(j, i) * props[i] over the kept columns, in column order (lanes stride the columns, a fixed
 // butterfly adds the lanes); llh[j] = weight[j] * log(denom[j]).  A wave per read.
 __global__ void k_meta_denoms(const uint16_t* __restrict__ score, int n_cand, const int* __restrict__ cols, int n_cols, const double* __restrict__ props,
@@ -265,7 +289,7 @@ __global__ void k_meta_sum_blocks(const double* __restrict__ v, int64_t n, doubl
     if (done && *done) return;
     const int lane = threadIdx.x & 63;
     const int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t lo = b * 1024, hi = lo + 1024 < n ? lo + 1024 : n;
+    const int64_t lo = b * kSumBlock, hi = lo + kSumBlock < n ? lo + kSumBlock : n;
     if (lo >= n) return;
     double acc = 0.0;
     for (int64_t i = lo + lane; i < hi; i += 64) acc += v[i];
@@ -410,7 +434,107 @@ struct pmx_meta {
     double llh = 0.0;
     double dust_threshold = 100.0;          // --dust: 100 = no filter
     int64_t n_dust_dropped = 0;
+    int64_t longest = 0;                    // seedmers of the longest merged read
+    // --gpus N (pmx_meta_attach_dist): `score` holds merged reads [row_first, row_first + row_count) only (pass A), score_em
+    // the EM rows this rank owns (pass B)
+    pmx_dist* dist = nullptr;
+    bool reads_set = false;
+    int64_t row_first = 0, row_count = 0;
+    DevBuf<uint16_t> score_em;
 };
+
+namespace {
+// the order of merged reads: lexicographic on the hash list, then on the orientation list (the order the vector comparisons gave)
+int cmp_lists(const uint64_t* xh, const uint8_t* xv, int64_t xn, const uint64_t* yh, const uint8_t* yv, int64_t yn) {
+    const int64_t nmin = std::min(xn, yn);
+    for (int64_t i = 0; i < nmin; ++i)
+        if (xh[i] != yh[i]) return xh[i] < yh[i] ? -1 : 1;
+    if (xn != yn) return xn < yn ? -1 : 1;
+    const int c = memcmp(xv, yv, (size_t)xn);
+    return c < 0 ? -1 : c > 0 ? 1 : 0;
+}
+
+// --gpus N: every rank's merged run (sorted, distinct lists with multiplicities) to every rank -- the counts first, then one
+// max-padded all-gather of the bytes -- and a k-way merge into the whole sample's run, multiplicities added.  Equal to what
+// one rank makes of all the reads: a sort of the union with equal lists merged.
+void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int k) {
+    pmx_ctx* ctx = m->ctx;
+    const int world = (int)(counts.size() / (size_t)k);
+    auto run_bytes = [](int64_t nr, int64_t ns) { return (size_t)(16 * nr + 8 * ns + ((ns + 7) & ~(int64_t)7)); };
+    size_t mx = 8;
+    for (int r = 0; r < world; ++r) mx = std::max(mx, run_bytes(counts[(size_t)r * k + 3], counts[(size_t)r * k + 4]));
+    // this rank's run: lengths, multiplicities (int64), hashes (uint64), orientations (bytes)
+    const int64_t nr = m->n_reads, ns = m->n_seedmers;
+    std::vector<char> mine(mx, 0);
+    for (int64_t i = 0; i < nr; ++i) {
+        const int64_t len = m->h_read_off[(size_t)i + 1] - m->h_read_off[(size_t)i];
+        memcpy(mine.data() + 8 * i, &len, 8);
+    }
+    if (nr > 0) memcpy(mine.data() + 8 * nr, m->h_mult.data(), 8 * (size_t)nr);
+    if (ns > 0) {
+        memcpy(mine.data() + 16 * nr, m->h_seed_hash.data(), 8 * (size_t)ns);
+        memcpy(mine.data() + 16 * nr + 8 * ns, m->h_seed_rev.data(), (size_t)ns);
+    }
+    DevBuf<char> d_mine, d_all;
+    d_mine.alloc(mx);
+    d_all.alloc(mx * (size_t)world);
+    std::vector<char> all(mx * (size_t)world);
+    PMX_HIP(hipMemcpyAsync(d_mine.p, mine.data(), mx, hipMemcpyHostToDevice, ctx->stream));
+    dist_all_gather(m->dist, d_mine.p, mx, d_all.p);
+    PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    struct Run { const int64_t *len, *mult; const uint64_t* h; const uint8_t* v; int64_t n, i, at; };
+    std::vector<Run> runs;
+    for (int r = 0; r < world; ++r) {
+        const char* b = all.data() + (size_t)r * mx;
+        const int64_t rn = counts[(size_t)r * k + 3], rs = counts[(size_t)r * k + 4];
+        runs.push_back(Run{(const int64_t*)b, (const int64_t*)(b + 8 * rn), (const uint64_t*)(b + 16 * rn), (const uint8_t*)(b + 16 * rn + 8 * rs), rn, 0, 0});
+    }
+    auto cmp_heads = [](const Run& x, const Run& y) {
+        return cmp_lists(x.h + x.at, x.v + x.at, x.len[x.i], y.h + y.at, y.v + y.at, y.len[y.i]);
+    };
+    m->h_read_off.assign(1, 0);
+    m->h_seed_hash.clear(); m->h_seed_rev.clear(); m->h_mult.clear();
+    for (;;) {
+        int lo = -1;
+        for (int r = 0; r < world; ++r)
+            if (runs[r].i < runs[r].n && (lo < 0 || cmp_heads(runs[r], runs[lo]) < 0)) lo = r;
+        if (lo < 0) break;
+        const Run head = runs[lo];
+        const int64_t len = head.len[head.i];
+        m->h_seed_hash.insert(m->h_seed_hash.end(), head.h + head.at, head.h + head.at + len);
+        m->h_seed_rev.insert(m->h_seed_rev.end(), head.v + head.at, head.v + head.at + len);
+        m->h_read_off.push_back((int64_t)m->h_seed_hash.size());
+        int64_t mult = 0;
+        for (int r = lo; r < world; ++r) {   // (a run holds a list once; the ranks below `lo` hold greater heads)
+            Run& x = runs[r];
+            if (x.i < x.n && (r == lo || cmp_heads(x, head) == 0)) {
+                mult += x.mult[x.i];
+                x.at += x.len[x.i];
+                ++x.i;
+            }
+        }
+        m->h_mult.push_back(mult);
+    }
+    m->n_reads = (int64_t)m->h_mult.size();
+    m->n_seedmers = (int64_t)m->h_seed_hash.size();
+}
+
+// scores of merged reads [first, first + count) against the candidates (the masks of pmx_meta_score) into out[count][n_cand]
+void score_rows(pmx_ctx* ctx, pmx_meta* m, int64_t first, int64_t count, uint16_t* out) {
+    if (count <= 0) return;
+    const int n_cand = (int)m->cand.size(), words = (n_cand + 63) / 64;
+    const int64_t threads = count * (int64_t)words;
+    const dim3 grid(grid_for(threads, 256, ctx->n_cu * 16)), block(256);
+    if (m->longest < 128)
+        hipLaunchKernelGGL(k_meta_scores<7>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count, m->mask_fwd.p,
+                           m->mask_rev.p, words, n_cand, out);
+    else
+        hipLaunchKernelGGL(k_meta_scores<16>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count, m->mask_fwd.p,
+                           m->mask_rev.p, words, n_cand, out);
+    PMX_HIP(hipGetLastError());
+}
+}  // namespace
 
 extern "C" {
 
@@ -440,12 +564,15 @@ int pmx_meta_create(pmx_ctx* ctx, const pmx_index* idx_std, const pmx_index* idx
         for (uint64_t q = O->offsets[v]; q < O->offsets[v + 1]; ++q) node[q] = (uint32_t)v;
     m->ch_key.alloc((size_t)c); m->ch_pc.alloc((size_t)c); m->ch_cc.alloc((size_t)c); m->ch_node.alloc((size_t)c); m->subtree_end.alloc((size_t)n);
     if (c > 0) {
-        PMX_HIP(hipMemcpy(m->ch_key.p, O->hash.data(), sizeof(uint64_t) * (size_t)c, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(m->ch_pc.p, O->parent_count.data(), sizeof(int16_t) * (size_t)c, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(m->ch_cc.p, O->child_count.data(), sizeof(int16_t) * (size_t)c, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(m->ch_node.p, node.data(), sizeof(uint32_t) * (size_t)c, hipMemcpyHostToDevice));
+        PMX_HIP(hipMemcpyAsync(m->ch_key.p, O->hash.data(), sizeof(uint64_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->ch_pc.p, O->parent_count.data(), sizeof(int16_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->ch_cc.p, O->child_count.data(), sizeof(int16_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->ch_node.p, node.data(), sizeof(uint32_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
     }
-    PMX_HIP(hipMemcpy(m->subtree_end.p, end.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
+    // (copies on the context's stream: synchronous null-stream copies against its blocking CU-masked queue are a suspect of
+    //  the unexplained stalls)
+    PMX_HIP(hipMemcpyAsync(m->subtree_end.p, end.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
     const int rc = pmx_place_create(ctx, idx_std, &m->placer);
     if (rc != PMX_OK) return rc;
     *out = m.release();
@@ -458,6 +585,21 @@ void pmx_meta_free(pmx_ctx* ctx, pmx_meta* m) {
     if (ctx) (void)hipSetDevice(ctx->device);
     if (m->placer) pmx_place_free(ctx, m->placer);
     delete m;
+}
+
+int pmx_meta_attach_dist(pmx_meta* m, pmx_dist* d) {
+    if (!m || !d) return PMX_ERR_ARG;
+    if (dist_ctx(d) != m->ctx) return fail(PMX_ERR_ARG, "pmx_meta_attach_dist: the dist must be made on the meta's context");
+    if (m->reads_set) return fail(PMX_ERR_ARG, "pmx_meta_attach_dist: attach before pmx_meta_set_reads");
+    m->dist = d;
+    return PMX_OK;
+}
+
+int pmx_meta_row_range(const pmx_meta* m, int64_t* first, int64_t* count) {
+    if (!m) return PMX_ERR_ARG;
+    if (first) *first = m->row_first;
+    if (count) *count = m->row_count;
+    return PMX_OK;
 }
 
 // Step 1 + 2: the reads' seedmer lists (host threads), merged by list; the overlap coefficient of every node (place stage).
@@ -579,12 +721,7 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     // (lexicographic on the hash list, then on the orientation list: the order the vector comparisons gave)
     auto cmp3 = [&](int64_t a, int64_t b) {
         const View x = view(a), y = view(b);
-        const int64_t nmin = std::min(x.n, y.n);
-        for (int64_t i = 0; i < nmin; ++i)
-            if (x.h[i] != y.h[i]) return x.h[i] < y.h[i] ? -1 : 1;
-        if (x.n != y.n) return x.n < y.n ? -1 : 1;
-        const int c = memcmp(x.v, y.v, (size_t)x.n);
-        return c < 0 ? -1 : c > 0 ? 1 : 0;
+        return cmp_lists(x.h, x.v, x.n, y.h, y.v, y.n);
     };
     auto less = [&](int64_t a, int64_t b) { return cmp3(a, b) < 0; };
     std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { const int c = cmp3(a, b); return c < 0 || (c == 0 && a < b); });
@@ -602,6 +739,15 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     }
     m->n_reads = (int64_t)m->h_mult.size();
     m->n_seedmers = (int64_t)m->h_seed_hash.size();
+    // --gpus N: the ranks' runs become the whole sample's; the raw, DUST-dropped and kept read counts are summed
+    int64_t n_kept_all = n_reads;
+    if (m->dist) {
+        const int64_t mine[5] = {n_raw, n_dusty, n_reads, m->n_reads, m->n_seedmers};
+        const std::vector<int64_t> counts = dist_exchange_counts(m->dist, mine, 5);
+        m->n_raw_reads = m->n_dust_dropped = n_kept_all = 0;
+        for (size_t r = 0; r < counts.size() / 5; ++r) { m->n_raw_reads += counts[5 * r]; m->n_dust_dropped += counts[5 * r + 1]; n_kept_all += counts[5 * r + 2]; }
+        merge_runs_over_ranks(m, counts, 5);
+    }
     m->h_uniq = m->h_seed_hash;
     std::sort(m->h_uniq.begin(), m->h_uniq.end());
     m->h_uniq.erase(std::unique(m->h_uniq.begin(), m->h_uniq.end()), m->h_uniq.end());
@@ -612,15 +758,18 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     m->d_seed_uid.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
     m->d_seed_rev.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
     m->d_uniq.ensure(std::max<size_t>(m->h_uniq.size(), 1));
-    PMX_HIP(hipMemcpy(m->d_read_off.p, m->h_read_off.data(), sizeof(int64_t) * ((size_t)m->n_reads + 1), hipMemcpyHostToDevice));
+    PMX_HIP(hipMemcpyAsync(m->d_read_off.p, m->h_read_off.data(), sizeof(int64_t) * ((size_t)m->n_reads + 1), hipMemcpyHostToDevice, ctx->stream));
     if (m->n_seedmers > 0) {
-        PMX_HIP(hipMemcpy(m->d_seed_uid.p, uid.data(), sizeof(uint32_t) * (size_t)m->n_seedmers, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(m->d_seed_rev.p, m->h_seed_rev.data(), (size_t)m->n_seedmers, hipMemcpyHostToDevice));
-        PMX_HIP(hipMemcpy(m->d_uniq.p, m->h_uniq.data(), sizeof(uint64_t) * m->h_uniq.size(), hipMemcpyHostToDevice));
+        PMX_HIP(hipMemcpyAsync(m->d_seed_uid.p, uid.data(), sizeof(uint32_t) * (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->d_seed_rev.p, m->h_seed_rev.data(), (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->d_uniq.p, m->h_uniq.data(), sizeof(uint64_t) * m->h_uniq.size(), hipMemcpyHostToDevice, ctx->stream));
     }
+    PMX_HIP(hipStreamSynchronize(ctx->stream));   // (uid goes out of scope)
     // overlap coefficients through the place stage: seed the reads on the device, score the tree with every read seed kept
+    // (--gpus N: each rank seeds its kept reads, the histograms are merged, and every rank scores the tree with the whole
+    //  sample's kept-read count -- the coefficients, and so the candidates, are the same on every rank)
     m->oc.assign((size_t)m->n_nodes, 0.0);
-    if (n_reads > 0) {
+    if (n_kept_all > 0) {
         pmx_readset* rs = nullptr;
         int rc = pmx_readset_upload(ctx, concat, offsets, n_reads, &rs);
         if (rc != PMX_OK) return rc;
@@ -631,7 +780,8 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
         rc = pmx_readset_pack(ctx, rs);
         if (rc == PMX_OK) rc = pmx_place_reset(ctx, m->placer);
         if (rc == PMX_OK) rc = pmx_place_add_reads(ctx, m->placer, rs, &pp);
-        if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_reads, &res);
+        if (rc == PMX_OK && m->dist) rc = pmx_dist_merge_histograms(m->dist, m->placer);
+        if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept_all, &res);
         pmx_readset_free(ctx, rs);
         if (rc != PMX_OK) return rc;
         std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
@@ -642,6 +792,9 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     }
     m->cand.clear();
     m->groups.clear();
+    m->row_first = 0;
+    m->row_count = m->dist ? 0 : m->n_reads;
+    m->reads_set = true;
     return PMX_OK;
     PMX_CATCH
 }
@@ -676,6 +829,14 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
     const int n_cand = (int)m->cand.size(), words = (n_cand + 63) / 64;
     m->groups.clear();
     m->h_max_score.assign((size_t)m->n_reads, 0);
+    // this rank's rows: all merged reads, or (--gpus N, pass A) a balanced contiguous slice of them
+    m->row_first = 0;
+    m->row_count = m->n_reads;
+    if (m->dist) {
+        const int64_t rank = pmx_dist_rank(m->dist), world = pmx_dist_world(m->dist);
+        m->row_first = m->n_reads * rank / world;
+        m->row_count = m->n_reads * (rank + 1) / world - m->row_first;
+    }
     if (n_cand == 0 || m->n_reads == 0) return PMX_OK;
     m->d_cand.ensure((size_t)n_cand);
     PMX_HIP(hipMemcpyAsync(m->d_cand.p, m->cand.data(), sizeof(uint32_t) * (size_t)n_cand, hipMemcpyHostToDevice, ctx->stream));
@@ -688,19 +849,12 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
         hipLaunchKernelGGL(k_meta_mask_events, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, m->ch_key.p, m->ch_pc.p,
                            m->ch_cc.p, m->ch_node.p, m->n_changes, m->subtree_end.p, m->d_uniq.p, (int64_t)m->h_uniq.size(), m->d_cand.p, n_cand, words,
                            m->mask_fwd.p, m->mask_rev.p);
-    m->score.ensure((size_t)m->n_reads * (size_t)n_cand);
+    m->score.ensure((size_t)m->row_count * (size_t)n_cand);
     int64_t longest = 0;
     for (int64_t r = 0; r < m->n_reads; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
     if (longest >= 65535) return fail(PMX_ERR_UNSUPPORTED, "a read with 65,535 seedmers or more (16-bit scores)");
-    const int64_t threads = m->n_reads * (int64_t)words;
-    const dim3 grid(grid_for(threads, 256, ctx->n_cu * 16)), block(256);
-    if (longest < 128)
-        hipLaunchKernelGGL(k_meta_scores<7>, grid, block, 0, ctx->stream, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p, m->n_reads, m->mask_fwd.p,
-                           m->mask_rev.p, words, n_cand, m->score.p);
-    else
-        hipLaunchKernelGGL(k_meta_scores<16>, grid, block, 0, ctx->stream, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p, m->n_reads, m->mask_fwd.p,
-                           m->mask_rev.p, words, n_cand, m->score.p);
-    PMX_HIP(hipGetLastError());
+    m->longest = longest;
+    score_rows(ctx, m, m->row_first, m->row_count, m->score.p);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
     PMX_CATCH
@@ -737,11 +891,14 @@ int pmx_meta_read_seedmers(const pmx_meta* m, int64_t* offsets, uint64_t* hash, 
 }
 int pmx_meta_scores(pmx_ctx* ctx, pmx_meta* m, uint16_t* out, int64_t cap) {
     if (!ctx || !m || !out) return PMX_ERR_ARG;
-    const int64_t n = m->n_reads * (int64_t)m->cand.size();
+    const int64_t n = m->row_count * (int64_t)m->cand.size();
     if (cap < n) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    if (n > 0) PMX_HIP(hipMemcpy(out, m->score.p, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost));
+    if (n > 0) {
+        PMX_HIP(hipMemcpyAsync(out, m->score.p, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        PMX_HIP(hipStreamSynchronize(ctx->stream));
+    }
     return PMX_OK;
     PMX_CATCH
 }
@@ -759,34 +916,71 @@ int pmx_meta_em(pmx_ctx* ctx, pmx_meta* m, const pmx_meta_params* mp) {
     m->llh = 0.0;
     if (n_cand == 0 || n_reads == 0) return PMX_OK;
     // ---- columns: one per distinct score column (digest; members = the other candidates of that column)
-    DevBuf<uint64_t> d_dig;
-    d_dig.alloc(2 * (size_t)n_cand);
-    hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, n_reads, n_cand, d_dig.p);
-    std::vector<uint64_t> dig(2 * (size_t)n_cand);
-    PMX_HIP(hipMemcpyAsync(dig.data(), d_dig.p, sizeof(uint64_t) * dig.size(), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
-    std::map<std::pair<uint64_t, uint64_t>, int> first_of;
     std::vector<int> col_cand;                       // column -> candidate position of its representative
     std::vector<std::vector<uint32_t>> col_members;
-    for (int c = 0; c < n_cand; ++c) {
-        const auto key = std::make_pair(dig[2 * (size_t)c], dig[2 * (size_t)c + 1]);
-        auto it = first_of.find(key);
-        if (it == first_of.end()) { first_of.emplace(key, (int)col_cand.size()); col_cand.push_back(c); col_members.emplace_back(); }
-        else col_members[(size_t)it->second].push_back(m->cand[(size_t)c]);
-    }
-    // ---- rows: the reads that score somewhere (the others carry no weight, src/mgsr.cpp:8170-8173)
-    std::vector<uint16_t> h_score((size_t)n_reads * (size_t)n_cand);
-    PMX_HIP(hipMemcpy(h_score.data(), m->score.p, sizeof(uint16_t) * h_score.size(), hipMemcpyDeviceToHost));
     std::vector<int64_t> rows;
-    for (int64_t r = 0; r < n_reads; ++r) {
-        int mx = 0;
-        for (int c = 0; c < n_cand; ++c) mx = std::max<int>(mx, h_score[(size_t)r * (size_t)n_cand + (size_t)c]);
-        m->h_max_score[(size_t)r] = mx;
-        const int64_t n_seed = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
-        // --discard (src/main.cpp:1229-1240): the threshold is TRUNCATED to an integer there,
-        // `maxScore < static_cast<int>(seedmers * discard)`, so a read with int(n * d) <= max < n * d stays in the EM
-        if (mx == 0 || mx < (int)((double)n_seed * mp->discard)) continue;
-        rows.push_back(r);
+    DevBuf<uint64_t> d_dig;
+    d_dig.alloc(2 * (size_t)n_cand);
+    if (!m->dist) {
+        hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, n_reads, n_cand, d_dig.p);
+        std::vector<uint64_t> dig(2 * (size_t)n_cand);
+        PMX_HIP(hipMemcpyAsync(dig.data(), d_dig.p, sizeof(uint64_t) * dig.size(), hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipStreamSynchronize(st));
+        std::map<std::pair<uint64_t, uint64_t>, int> first_of;
+        for (int c = 0; c < n_cand; ++c) {
+            const auto key = std::make_pair(dig[2 * (size_t)c], dig[2 * (size_t)c + 1]);
+            auto it = first_of.find(key);
+            if (it == first_of.end()) { first_of.emplace(key, (int)col_cand.size()); col_cand.push_back(c); col_members.emplace_back(); }
+            else col_members[(size_t)it->second].push_back(m->cand[(size_t)c]);
+        }
+        // ---- rows: the reads that score somewhere (the others carry no weight, src/mgsr.cpp:8170-8173)
+        std::vector<uint16_t> h_score((size_t)n_reads * (size_t)n_cand);
+        PMX_HIP(hipMemcpyAsync(h_score.data(), m->score.p, sizeof(uint16_t) * h_score.size(), hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipStreamSynchronize(st));
+        for (int64_t r = 0; r < n_reads; ++r) {
+            int mx = 0;
+            for (int c = 0; c < n_cand; ++c) mx = std::max<int>(mx, h_score[(size_t)r * (size_t)n_cand + (size_t)c]);
+            m->h_max_score[(size_t)r] = mx;
+            const int64_t n_seed = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
+            // --discard (src/main.cpp:1229-1240): the threshold is TRUNCATED to an integer there,
+            // `maxScore < static_cast<int>(seedmers * discard)`, so a read with int(n * d) <= max < n * d stays in the EM
+            if (mx == 0 || mx < (int)((double)n_seed * mp->discard)) continue;
+            rows.push_back(r);
+        }
+    } else {
+        // --gpus N, pass A: the column digests of this rank's slice and its reads' --discard flags (k_meta_row_keep), one
+        // all-gather of both.  Two columns are equal iff they are equal on every slice: the key of a column is its digests in
+        // rank order, so the groups (and their order: by first candidate) are the one-rank groups.
+        const int world = pmx_dist_world(m->dist);
+        const int64_t max_slice = (n_reads + world - 1) / world;
+        const size_t dig_bytes = sizeof(uint64_t) * 2 * (size_t)n_cand, part_bytes = dig_bytes + (((size_t)max_slice + 7) & ~(size_t)7);
+        DevBuf<char> d_mine, d_all;
+        d_mine.alloc(part_bytes);
+        d_all.alloc(part_bytes * (size_t)world);
+        PMX_HIP(hipMemsetAsync(d_mine.p, 0, part_bytes, st));
+        hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, m->row_count, n_cand, (uint64_t*)d_mine.p);
+        if (m->row_count > 0)
+            hipLaunchKernelGGL(k_meta_row_keep, dim3(grid_for(m->row_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->score.p, m->row_count, n_cand,
+                               m->d_read_off.p + m->row_first, mp->discard, (uint8_t*)(d_mine.p + dig_bytes));
+        PMX_HIP(hipGetLastError());
+        dist_all_gather(m->dist, d_mine.p, part_bytes, d_all.p);
+        std::vector<char> all(part_bytes * (size_t)world);
+        PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipStreamSynchronize(st));
+        std::map<std::vector<uint64_t>, int> first_of;
+        std::vector<uint64_t> key(2 * (size_t)world);
+        for (int c = 0; c < n_cand; ++c) {
+            for (int r = 0; r < world; ++r) memcpy(&key[2 * (size_t)r], all.data() + (size_t)r * part_bytes + 2 * sizeof(uint64_t) * (size_t)c, 2 * sizeof(uint64_t));
+            auto it = first_of.find(key);
+            if (it == first_of.end()) { first_of.emplace(key, (int)col_cand.size()); col_cand.push_back(c); col_members.emplace_back(); }
+            else col_members[(size_t)it->second].push_back(m->cand[(size_t)c]);
+        }
+        for (int r = 0; r < world; ++r) {
+            const int64_t f = n_reads * r / world, n = n_reads * (r + 1) / world - f;
+            const uint8_t* keep = (const uint8_t*)(all.data() + (size_t)r * part_bytes + dig_bytes);
+            for (int64_t i = 0; i < n; ++i)
+                if (keep[i]) rows.push_back(f + i);
+        }
     }
     const int64_t n_rows = (int64_t)rows.size();
     if (n_rows == 0) return PMX_OK;
@@ -805,36 +999,69 @@ int pmx_meta_em(pmx_ctx* ctx, pmx_meta* m, const pmx_meta_params* mp) {
         }
         tab_off[(size_t)j] = it->second;
         weight[(size_t)j] = (double)m->h_mult[(size_t)r];
-        total_weight += weight[(size_t)j];
+        total_weight += weight[(size_t)j];   // (integers: exact in any order)
     }
     const double inv_total = 1.0 / total_weight;
+    const int64_t chunk = kColsumChunk;   // reads per partial column sum (2,048: 2,200 waves for 3,000 columns x 90k reads, each a serial walk: 373 us per pass)
+    const int n_chunks = (int)((n_rows + chunk - 1) / chunk);
+    const int64_t n_bsum = (n_rows + kSumBlock - 1) / kSumBlock;
+    // ---- this rank's EM rows: all of them, or (--gpus N, pass B) a contiguous range whose bounds are multiples of both
+    // reduction widths -- the rank's chunk partials and block sums are then whole global ones, at global positions
+    // rank * per / width of the all-gathered arrays, and the one-rank fold and store kernels add them in the one-rank order
+    int64_t e_first = 0, e_count = n_rows, per = n_rows;
+    const uint16_t* score_p = m->score.p;
+    std::vector<int64_t> loc_rows(rows);
+    if (m->dist) {
+        const int world = pmx_dist_world(m->dist), rank = pmx_dist_rank(m->dist);
+        const int64_t align = std::lcm(kColsumChunk, kSumBlock);
+        per = ((n_rows + world - 1) / world + align - 1) / align * align;
+        e_first = std::min<int64_t>(n_rows, per * rank);
+        e_count = std::min<int64_t>(n_rows, e_first + per) - e_first;
+        // pass B: the merged reads of the range, scored again into a matrix of their own
+        const int64_t r_lo = e_count > 0 ? rows[(size_t)e_first] : 0, r_hi = e_count > 0 ? rows[(size_t)(e_first + e_count - 1)] + 1 : 0;
+        m->score_em.ensure((size_t)std::max<int64_t>(r_hi - r_lo, 1) * (size_t)n_cand);
+        score_rows(ctx, m, r_lo, r_hi - r_lo, m->score_em.p);
+        score_p = m->score_em.p;
+        loc_rows.assign((size_t)e_count, 0);
+        for (int64_t j = 0; j < e_count; ++j) loc_rows[(size_t)j] = rows[(size_t)(e_first + j)] - r_lo;
+    }
+    const int loc_chunks = (int)((e_count + chunk - 1) / chunk);
+    const int64_t loc_bsum = (e_count + kSumBlock - 1) / kSumBlock;
+    const int64_t slot_chunks = (per + chunk - 1) / chunk, slot_bsum = (per + kSumBlock - 1) / kSumBlock;   // per rank in the gathers
     DevBuf<int64_t> d_rows;
     DevBuf<uint32_t> d_tab_off;
-    DevBuf<double> d_tab, d_weight, d_denom, d_llh, d_props, d_out, d_part, d_bsum;
+    DevBuf<double> d_tab, d_weight, d_denom, d_llh, d_props, d_out, d_part, d_bsum, d_gpart, d_gbsum;
     DevBuf<int> d_cols;
-    d_rows.alloc((size_t)n_rows); d_tab_off.alloc((size_t)n_rows); d_tab.alloc(tab.size()); d_weight.alloc((size_t)n_rows);
-    d_denom.alloc((size_t)n_rows); d_llh.alloc((size_t)n_rows);
-    PMX_HIP(hipMemcpy(d_rows.p, rows.data(), sizeof(int64_t) * (size_t)n_rows, hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(d_tab_off.p, tab_off.data(), sizeof(uint32_t) * (size_t)n_rows, hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    PMX_HIP(hipMemcpy(d_weight.p, weight.data(), sizeof(double) * (size_t)n_rows, hipMemcpyHostToDevice));
-    const int64_t chunk = 256;   // reads per partial column sum (2,048: 2,200 waves for 3,000 columns x 90k reads, each a serial walk: 373 us per pass)
-    const int n_chunks = (int)((n_rows + chunk - 1) / chunk);
-    const int64_t n_bsum = (n_rows + 1023) / 1024;
-    d_bsum.alloc((size_t)n_bsum);
-    std::vector<double> h_bsum((size_t)n_bsum);
+    d_rows.alloc((size_t)e_count); d_tab_off.alloc((size_t)e_count); d_tab.alloc(tab.size()); d_weight.alloc((size_t)e_count);
+    d_denom.alloc((size_t)e_count); d_llh.alloc((size_t)e_count);
+    if (e_count > 0) {
+        PMX_HIP(hipMemcpyAsync(d_rows.p, loc_rows.data(), sizeof(int64_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_tab_off.p, tab_off.data() + e_first, sizeof(uint32_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_weight.p, weight.data() + e_first, sizeof(double) * (size_t)e_count, hipMemcpyHostToDevice, st));
+    }
+    PMX_HIP(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    d_bsum.alloc((size_t)slot_bsum);
+    const int world = m->dist ? pmx_dist_world(m->dist) : 1;
+    if (m->dist) d_gbsum.alloc((size_t)slot_bsum * (size_t)world);
+    const double* bsum_all = m->dist ? d_gbsum.p : d_bsum.p;
 
     std::vector<int> cols = col_cand;       // current columns (candidate positions)
     std::vector<std::vector<uint32_t>> members = col_members;
     std::vector<double> props;
     for (int round = 0; round < std::max(1, mp->em_max_rounds); ++round) {
         const int n_cols = (int)cols.size();
-        d_cols.ensure((size_t)n_cols); d_props.ensure((size_t)n_cols); d_out.ensure((size_t)n_cols); d_part.ensure((size_t)n_chunks * (size_t)n_cols);
-        PMX_HIP(hipMemcpy(d_cols.p, cols.data(), sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice));
+        d_cols.ensure((size_t)n_cols); d_props.ensure((size_t)n_cols); d_out.ensure((size_t)n_cols); d_part.ensure((size_t)slot_chunks * (size_t)n_cols);
+        if (m->dist) d_gpart.ensure((size_t)slot_chunks * (size_t)n_cols * (size_t)world);
+        const double* part_all = m->dist ? d_gpart.p : d_part.p;
+        PMX_HIP(hipMemcpyAsync(d_cols.p, cols.data(), sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st));
         // The whole SQUAREM loop stays on the device: the proportion vectors never leave it, the small vector arithmetic runs in
         // single-block kernels with the host loop's own order of operations, and the host only looks at the convergence flag
         // every 16 iterations (launches queued past convergence return at once).  Per iteration: 6 passes over the score
-        // matrix (4 x k_meta_denoms, 2 x k_meta_colsum) and 13 small launches; before, 4 host round trips.
+        // matrix (4 x k_meta_denoms, 2 x k_meta_colsum) and 13 small launches; before, 4 host round trips.  --gpus N: the
+        // passes run over the rank's rows, and 4 all-gathers per iteration (chunk partials x 2, block sums x 2) bring every
+        // rank the global arrays; the single-block kernels then run replicated on identical inputs, so the convergence flag
+        // and the iteration count agree on every rank and every rank issues the same sequence of collectives (queued past
+        // convergence too).
         DevBuf<double> d_p0, d_p1, d_p2, d_sq;
         DevBuf<EmCtl> d_ctl;
         d_p0.alloc((size_t)n_cols); d_p1.alloc((size_t)n_cols); d_p2.alloc((size_t)n_cols); d_sq.alloc((size_t)n_cols);
@@ -856,20 +1083,26 @@ int pmx_meta_em(pmx_ctx* ctx, pmx_meta* m, const pmx_meta_params* mp) {
             PMX_HIP(hipFuncSetAttribute((const void*)k_em_extrapolate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
         }
         auto denoms = [&](const double* pr) {
-            hipLaunchKernelGGL(k_meta_denoms, dim3(grid_for(n_rows * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->score.p, n_cand, d_cols.p, n_cols, pr,
-                               d_rows.p, n_rows, d_tab_off.p, d_tab.p, d_weight.p, d_denom.p, d_llh.p, d_done);
+            hipLaunchKernelGGL(k_meta_denoms, dim3(grid_for(e_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, score_p, n_cand, d_cols.p, n_cols, pr,
+                               d_rows.p, e_count, d_tab_off.p, d_tab.p, d_weight.p, d_denom.p, d_llh.p, d_done);
         };
         auto em_step = [&](const double* from, double* to) {   // updateProps (src/mgsr.cpp:4341-4372) + normalizeProps
-            denoms(from);
-            hipLaunchKernelGGL(k_meta_colsum, dim3((n_cols + 63) / 64, n_chunks), dim3(64), 0, st, m->score.p, n_cand, d_cols.p, n_cols, from, d_rows.p,
-                               n_rows, chunk, d_tab_off.p, d_tab.p, d_weight.p, d_denom.p, d_part.p, d_done);
-            hipLaunchKernelGGL(k_meta_fold, dim3((n_cols + 63) / 64), dim3(64), 0, st, d_part.p, n_chunks, n_cols, inv_total, d_out.p, d_done);
+            if (e_count > 0) {
+                denoms(from);
+                hipLaunchKernelGGL(k_meta_colsum, dim3((n_cols + 63) / 64, loc_chunks), dim3(64), 0, st, score_p, n_cand, d_cols.p, n_cols, from, d_rows.p,
+                                   e_count, chunk, d_tab_off.p, d_tab.p, d_weight.p, d_denom.p, d_part.p, d_done);
+            }
+            if (m->dist) dist_all_gather(m->dist, d_part.p, sizeof(double) * (size_t)slot_chunks * (size_t)n_cols, d_gpart.p);
+            hipLaunchKernelGGL(k_meta_fold, dim3((n_cols + 63) / 64), dim3(64), 0, st, part_all, n_chunks, n_cols, inv_total, d_out.p, d_done);
             hipLaunchKernelGGL(k_em_normalize, dim3(1), dim3(256), em_work ? 0 : sizeof(double) * (size_t)n_cols, st, d_out.p, to, n_cols, d_ctl.p, em_work);
         };
         auto log_likelihood = [&](const double* pr, int which) {                          // getExp (:4385-4388)
-            denoms(pr);
-            hipLaunchKernelGGL(k_meta_sum_blocks, dim3((unsigned)((n_bsum + 3) / 4)), dim3(256), 0, st, d_llh.p, n_rows, d_bsum.p, d_done);
-            hipLaunchKernelGGL(k_em_store_llh, dim3(1), dim3(64), 0, st, d_bsum.p, n_bsum, d_ctl.p, which);
+            if (e_count > 0) {
+                denoms(pr);
+                hipLaunchKernelGGL(k_meta_sum_blocks, dim3((unsigned)((loc_bsum + 3) / 4)), dim3(256), 0, st, d_llh.p, e_count, d_bsum.p, d_done);
+            }
+            if (m->dist) dist_all_gather(m->dist, d_bsum.p, sizeof(double) * (size_t)slot_bsum, d_gbsum.p);
+            hipLaunchKernelGGL(k_em_store_llh, dim3(1), dim3(64), 0, st, bsum_all, n_bsum, d_ctl.p, which);
         };
         const int look_every = 16;
         for (int iter = 0; iter < mp->em_max_iterations;) {                               // runSquareEM (:4394-4443)

@@ -4,8 +4,8 @@
 //           seeding parameters, src/main.cpp:371-396; -f rebuilds; -i loads a given file; --index-out names the output)
 //   place   reads -> `<prefix>.placement.tsv` (src/placement.cpp:1952-2003)
 //   align   placed genome -> `<prefix>.ref.fa` (+ .fai), reads aligned to it -> `<prefix>.bam` (+ .bai)
-// `--stop index|place|align` ends after that stage.  The later stages of the reference (genotype, consensus), --meta,
-// the bwa backend and HPC seeds are outside this library: asking for them is an error, not a silent
+// `--stop index|place|align` ends after that stage.  --meta -> `<prefix>.mgsr.abundance.out`.  The later stages of the
+// reference (genotype, consensus), the bwa backend and HPC seeds are outside this library: asking for them is an error, not a silent
 // no-op (a `--stop` beyond align stops after align with a note).  Output prefix: -o, else derived from reads1 as the
 // reference derives it.  Exit code 130 on SIGINT.
 #include <signal.h>
@@ -526,15 +526,96 @@ std::string run_sample(const Config& c, int stop, pmx_panman*& pm, pmx_index* id
     return node_id;
 }
 
+// ------------------------------------------------------------------------------------------------ --gpus N
+// One process per GPU, forked before any GPU call: what the caller holds in memory (the indexes, the PanMAN, the reads) every
+// rank inherits, and each rank opens its own device.  The ranks meet through RCCL (pmx_dist_*); the communicator's id travels
+// through a file in a private directory.  The parent only waits.
+struct Ranks {
+    int rank = 0, world = 1;
+    std::string meet_dir;
+};
+
+// -> true in a rank (rk filled in), false in the parent once the ranks have ended (*code = the run's exit code)
+bool fork_ranks(int n, Ranks& rk, int* code) {
+    if (n <= 1) return true;
+    char tmpl[] = "/tmp/panmap_ranks_XXXXXX";
+    if (!mkdtemp(tmpl)) die("cannot create a rendezvous directory under /tmp");
+    rk.meet_dir = tmpl;
+    fflush(stdout); fflush(stderr);
+    std::vector<pid_t> kids;
+    for (int r = 0; r < n; ++r) {
+        const pid_t pid = fork();
+        if (pid < 0) die("fork failed");
+        if (pid == 0) { rk.rank = r; rk.world = n; return true; }
+        kids.push_back(pid);
+    }
+    // Wait for whichever rank ends first.  A rank that fails (no such device, unreadable reads, any die() between two
+    // collectives) leaves the others blocked in ncclCommInitRank / a collective for ever: the first failure ends the
+    // run -- the remaining children (and only they) get SIGTERM, are reaped, and its code is returned.
+    int worst = 0;
+    size_t left = kids.size();
+    while (left > 0) {
+        int st = 0;
+        const pid_t k = waitpid(-1, &st, 0);
+        if (k < 0) {
+            if (errno == EINTR) continue;
+            worst = worst ? worst : 1;
+            break;
+        }
+        auto it = std::find(kids.begin(), kids.end(), k);
+        if (it == kids.end()) continue;
+        *it = -1;
+        --left;
+        const int code = WIFEXITED(st) ? WEXITSTATUS(st) : 128 + (WIFSIGNALED(st) ? WTERMSIG(st) : 0);
+        if (code && !worst) {
+            worst = code;
+            for (pid_t o : kids) if (o > 0) kill(o, SIGTERM);
+        }
+    }
+    unlink((rk.meet_dir + "/uid.tmp").c_str());
+    unlink((rk.meet_dir + "/uid").c_str());
+    rmdir(rk.meet_dir.c_str());
+    *code = worst;
+    return false;
+}
+
+int rank_device(const Ranks& rk) {
+    int dev = 0;
+    if (const char* e = getenv("PMX_DEVICE")) dev = atoi(e);
+    if (rk.world > 1 && !getenv("PMX_DIST_SAME_DEVICE")) dev += rk.rank;   // (PMX_DIST_SAME_DEVICE: functional test on a one-GPU box)
+    return dev;
+}
+
+// the rendezvous: rank 0 makes the communicator id and publishes it in the directory, every rank joins (NULL for one rank)
+pmx_dist* join_ranks(pmx_ctx* ctx, const Ranks& rk) {
+    if (rk.world <= 1) return nullptr;
+    char uid[PMX_DIST_ID_BYTES];
+    const std::string uid_path = rk.meet_dir + "/uid";
+    if (rk.rank == 0) {
+        check(pmx_dist_unique_id(uid), "creating the communicator id");
+        FILE* f = fopen((uid_path + ".tmp").c_str(), "wb");
+        if (!f || fwrite(uid, 1, sizeof(uid), f) != sizeof(uid)) die("cannot write the communicator id");
+        fclose(f);
+        if (rename((uid_path + ".tmp").c_str(), uid_path.c_str()) != 0) die("cannot publish the communicator id");
+    } else {
+        FILE* f = nullptr;
+        for (int tries = 0; tries < 600000 && !(f = fopen(uid_path.c_str(), "rb")); ++tries) usleep(500);
+        if (!f || fread(uid, 1, sizeof(uid), f) != sizeof(uid)) die("rank 0 never published the communicator id");
+        fclose(f);
+    }
+    pmx_dist* dist = nullptr;
+    check(pmx_dist_init(ctx, uid, rk.rank, rk.world, &dist), "joining the ranks (RCCL)");
+    return dist;
+}
+
 // --meta (runDeconvolution, src/main.cpp:1192-1313): reads of a mixed sample -> `<prefix>.mgsr.abundance.out`, one line per
 // estimated haplotype: node id (+ the nodes merged into it, comma-joined) <TAB> proportion with five decimals, by proportion.
 // The two indexes of the tree (the place stage's and its oriented form, without flank mask) are built in memory.
-int run_meta(const Config& c) {
+int run_meta(Config c) {
     if (c.reads1.empty()) die("--meta needs reads");
     if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
     if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
     if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
-    if (c.gpus > 1) die("--meta runs on one GPU in this build");
     pmx_panman* pm = nullptr;
     check(pmx_panman_open(c.panman.c_str(), &pm), "opening the PanMAN");
     pmx_index *idx = nullptr, *oidx = nullptr;
@@ -564,14 +645,27 @@ int run_meta(const Config& c) {
         concat.append(s2, (size_t)o2[n2]);
         for (int64_t i = 1; i <= n2; ++i) off.push_back(base + o2[i]);
     }
-    int dev = 0;
-    if (const char* e = getenv("PMX_DEVICE")) dev = atoi(e);
+    // --gpus N: one rank per GPU, each with a contiguous shard of the reads above (R1 then R2); every rank ends with the whole
+    // sample's result (pmx_meta_attach_dist), rank 0 writes it
+    Ranks rk;
+    int code = 0;
+    if (!fork_ranks(c.gpus, rk, &code)) {
+        pmx_fastx_free(f1);
+        if (f2) pmx_fastx_free(f2);
+        pmx_index_close(idx); pmx_index_close(oidx);
+        pmx_panman_close(pm);
+        return code;
+    }
+    if (rk.rank > 0) c.quiet = true;
+    const int64_t n_all = (int64_t)off.size() - 1, lo = n_all * rk.rank / rk.world, hi = n_all * (rk.rank + 1) / rk.world;
     pmx_ctx* ctx = nullptr;
-    check(pmx_ctx_create(dev, &ctx), "opening the GPU");
+    check(pmx_ctx_create(rank_device(rk), &ctx), "opening the GPU");
+    pmx_dist* dist = join_ranks(ctx, rk);
     pmx_meta* m = nullptr;
     check(pmx_meta_create(ctx, idx, oidx, &m), "uploading the indexes");
+    if (dist) check(pmx_meta_attach_dist(m, dist), "attaching the ranks");
     check(pmx_meta_set_dust(m, c.dust), "--dust");
-    check(pmx_meta_set_reads(ctx, m, concat.data(), off.data(), (int64_t)off.size() - 1), "seeding the reads");
+    check(pmx_meta_set_reads(ctx, m, concat.data(), off.data() + lo, hi - lo), "seeding the reads");
     check(pmx_meta_score(ctx, m, c.top_oc, nullptr, 0), "scoring the reads against the candidate nodes");
     say(c, "meta", std::to_string(pmx_meta_num_reads(m)) + " distinct reads x " + std::to_string(pmx_meta_num_candidates(m)) + " candidate nodes");
     pmx_meta_params mp;
@@ -579,6 +673,17 @@ int run_meta(const Config& c) {
     mp.error_rate = 0.005; mp.em_convergence = c.em_convergence; mp.em_delta_threshold = c.em_delta; mp.prop_threshold = 0.005; mp.discard = c.discard;
     mp.em_max_iterations = c.em_max_iterations; mp.em_max_rounds = c.em_max_rounds;
     check(pmx_meta_em(ctx, m, &mp), "estimating the abundances");
+    if (rk.rank > 0) {
+        pmx_meta_free(ctx, m);
+        (void)pmx_dist_barrier(dist);
+        pmx_dist_free(dist);
+        pmx_ctx_destroy(ctx);
+        pmx_fastx_free(f1);
+        if (f2) pmx_fastx_free(f2);
+        pmx_index_close(idx); pmx_index_close(oidx);
+        pmx_panman_close(pm);
+        return 0;
+    }
     const std::string path = c.output + ".mgsr.abundance.out";
     FILE* f = fopen(path.c_str(), "w");
     if (!f) die("cannot write " + path);
@@ -598,6 +703,7 @@ int run_meta(const Config& c) {
     fclose(f);
     say(c, "meta", path + " (" + std::to_string(n_h) + " haplotypes)");
     pmx_meta_free(ctx, m);
+    if (dist) { (void)pmx_dist_barrier(dist); pmx_dist_free(dist); }
     pmx_ctx_destroy(ctx);
     pmx_fastx_free(f1);
     if (f2) pmx_fastx_free(f2);
@@ -638,83 +744,25 @@ int real_main(int argc, char** argv) {
     if (stop == 0 || (c.reads1.empty() && c.batch.empty())) return 0;
 
     // ------------------------------------------------------------------------------------------------ --gpus N
-    // One process per GPU, forked HERE: the index (and the PanMAN, when it was opened) is in memory and nothing has touched
-    // a GPU yet, so every rank inherits them and opens its own device.  The ranks meet through RCCL (pmx_dist_*); the
-    // communicator's id travels through a file in a private directory.  The parent only waits.
-    int rank = 0, world = 1;
-    std::string meet_dir;
+    // forked HERE: the index (and the PanMAN, when it was opened) is in memory and nothing has touched a GPU yet
+    Ranks rk;
     if (c.gpus > 1) {
         if (!c.batch.empty()) die("--gpus shards ONE sample over the GPUs; run --batch per GPU instead");
-        char tmpl[] = "/tmp/panmap_ranks_XXXXXX";
-        if (!mkdtemp(tmpl)) die("cannot create a rendezvous directory under /tmp");
-        meet_dir = tmpl;
-        fflush(stdout); fflush(stderr);
-        std::vector<pid_t> kids;
-        bool child = false;
-        for (int r = 0; r < c.gpus; ++r) {
-            const pid_t pid = fork();
-            if (pid < 0) die("fork failed");
-            if (pid == 0) { child = true; rank = r; world = c.gpus; break; }
-            kids.push_back(pid);
-        }
-        if (!child) {
-            // Wait for whichever rank ends first.  A rank that fails (no such device, unreadable reads, any die() between two
-            // collectives) leaves the others blocked in ncclCommInitRank / a collective for ever: the first failure ends the
-            // run -- the remaining children (and only they) get SIGTERM, are reaped, and its code is returned.
-            int worst = 0;
-            size_t left = kids.size();
-            while (left > 0) {
-                int st = 0;
-                const pid_t k = waitpid(-1, &st, 0);
-                if (k < 0) {
-                    if (errno == EINTR) continue;
-                    worst = worst ? worst : 1;
-                    break;
-                }
-                auto it = std::find(kids.begin(), kids.end(), k);
-                if (it == kids.end()) continue;
-                *it = -1;
-                --left;
-                const int code = WIFEXITED(st) ? WEXITSTATUS(st) : 128 + (WIFSIGNALED(st) ? WTERMSIG(st) : 0);
-                if (code && !worst) {
-                    worst = code;
-                    for (pid_t o : kids) if (o > 0) kill(o, SIGTERM);
-                }
-            }
-            unlink((meet_dir + "/uid.tmp").c_str());
-            unlink((meet_dir + "/uid").c_str());
-            rmdir(meet_dir.c_str());
+        int code = 0;
+        if (!fork_ranks(c.gpus, rk, &code)) {
             pmx_index_close(idx);
             if (pm) pmx_panman_close(pm);
-            return worst;
+            return code;
         }
-        if (rank > 0) c.quiet = true;
+        if (rk.rank > 0) c.quiet = true;
     }
+    const int rank = rk.rank;
 
     // ------------------------------------------------------------------------------------------------ samples
     pmx_ctx* ctx = nullptr;
-    int dev = 0;
-    if (const char* e = getenv("PMX_DEVICE")) dev = atoi(e);
-    if (world > 1 && !getenv("PMX_DIST_SAME_DEVICE")) dev += rank;   // (PMX_DIST_SAME_DEVICE: functional test on a one-GPU box)
+    const int dev = rank_device(rk);
     check(pmx_ctx_create(dev, &ctx), "opening the GPU");
-    pmx_dist* dist = nullptr;
-    if (world > 1) {
-        char uid[PMX_DIST_ID_BYTES];
-        const std::string uid_path = meet_dir + "/uid";
-        if (rank == 0) {
-            check(pmx_dist_unique_id(uid), "creating the communicator id");
-            FILE* f = fopen((uid_path + ".tmp").c_str(), "wb");
-            if (!f || fwrite(uid, 1, sizeof(uid), f) != sizeof(uid)) die("cannot write the communicator id");
-            fclose(f);
-            if (rename((uid_path + ".tmp").c_str(), uid_path.c_str()) != 0) die("cannot publish the communicator id");
-        } else {
-            FILE* f = nullptr;
-            for (int tries = 0; tries < 600000 && !(f = fopen(uid_path.c_str(), "rb")); ++tries) usleep(500);
-            if (!f || fread(uid, 1, sizeof(uid), f) != sizeof(uid)) die("rank 0 never published the communicator id");
-            fclose(f);
-        }
-        check(pmx_dist_init(ctx, uid, rank, world, &dist), "joining the ranks (RCCL)");
-    }
+    pmx_dist* dist = join_ranks(ctx, rk);
     pmx_place* pl = nullptr;
     check(pmx_place_create(ctx, idx, &pl), "uploading the index");
     int rc = 0;

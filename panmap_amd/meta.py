@@ -27,6 +27,19 @@ class Meta:
         oidx = Index.build(pm, k=k, s=s, t=t, l=l, open_syncmer=open_syncmer, flank_mask=flank_mask, mode=ORIENTED)
         return cls(ctx, idx, oidx)
 
+    def attach_dist(self, dist):
+        """--gpus N: `dist` (a Dist on this Meta's context) makes set_reads / score / em collective -- every rank calls them in
+        the same order, set_reads with its own shard of the reads -- and every rank ends with the whole sample's result.
+        Call before set_reads; keep `dist` alive as long as this Meta."""
+        check(lib.pmx_meta_attach_dist(self._h, dist._h), "pmx_meta_attach_dist")
+        self._dist = dist
+
+    def row_range(self):
+        """(first, count): the merged reads whose rows scores() returns (all of them without a dist)"""
+        first, count = C.c_int64(0), C.c_int64(0)
+        check(lib.pmx_meta_row_range(self._h, C.byref(first), C.byref(count)), "pmx_meta_row_range")
+        return int(first.value), int(count.value)
+
     def set_reads(self, reads=None, concat=None, offsets=None):
         if reads is not None:
             cb, offsets = concat_reads(reads)
@@ -81,7 +94,8 @@ class Meta:
         return off, h[:tot], rev[:tot]
 
     def scores(self) -> np.ndarray:
-        n, c = self.n_reads, int(lib.pmx_meta_num_candidates(self._h))
+        """[rows][candidates] for the merged reads of row_range()"""
+        n, c = self.row_range()[1], int(lib.pmx_meta_num_candidates(self._h))
         out = np.zeros((n, c), np.uint16)
         check(lib.pmx_meta_scores(self.ctx._h, self._h, out.ctypes.data, out.size), "pmx_meta_scores")
         return out
