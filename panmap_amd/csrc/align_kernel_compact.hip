@@ -170,7 +170,8 @@ __device__ __forceinline__ void align_compact_body(const AlignArgs& A) {
         unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (PRESEEDED) {
             // two-kernel form: the pairs' seeds wait in the hand-over words; a wave copies seed i of its 64 pairs with
-            // one contiguous load per word, four seeds requested together
+            // one contiguous load per word, four seeds requested together.  Only the first MT::kCap: a pair with more bails in
+            // compact_chain_pair and the second form loads all of them again from the hand-over words.
             int n_s = 0, n_s0 = 0;
             if (it < A.n_items) {
                 item = compact_item(A, it, rd, amb);
@@ -183,11 +184,12 @@ __device__ __forceinline__ void align_compact_body(const AlignArgs& A) {
             CSeedOutT<PT> so;
             so.q = nullptr; so.st = nullptr;
             so.out = (c_g32*)(A.cseeds + (size_t)it * CSeedOutT<PT>::kPairWords);
-            for (int i0 = 0; __ballot(i0 < n_s) != 0ULL; i0 += 4) {
+            const int n_load = n_s < MT::kCap ? n_s : MT::kCap;
+            for (int i0 = 0; __ballot(i0 < n_load) != 0ULL; i0 += 4) {
                 uint32_t x[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0};
-                if (i0 < n_s) so.get4(i0, x, y);
+                if (i0 < n_load) so.get4(i0, x, y);
 #pragma unroll
-                for (int b = 0; b < 4; ++b) if (i0 + b < n_s) m.setSeed(i0 + b, x[b], y[b]);
+                for (int b = 0; b < 4; ++b) if (i0 + b < n_load) m.setSeed(i0 + b, x[b], y[b]);
             }
             if (item >= 0 && rc == PMX_C_DONE) {
                 rc = compact_chain_pair(m, A.opt, A.ri, rd, n_s, n_s0, res, tab, pacc, A.edits != nullptr, A.prof != nullptr);

@@ -71,6 +71,9 @@ struct pmx_aligner {
     int64_t last_retry = 0, last_tpp_retry = 0;
     DevBuf<unsigned long long> prof;
     DevBuf<unsigned long long> stats;   // AlignArgs::stats
+    DevBuf<unsigned long long> dd_count;   // distinct-pair map counters (align_readset_once)
+    DevBuf<uint32_t> dd_list;           // representatives in launch order
+    DevBuf<char> dd_tmp;
     DevBuf<int32_t> edits;              // AlignArgs::edits while pmx_align_score_reads runs
     bool want_edits = false;
     pmx_align_stats last_stats;
@@ -156,6 +159,130 @@ __global__ void k_pair_keys(const uint32_t* __restrict__ read_key, int64_t n_pai
 }
 __global__ void k_halve(const uint32_t* __restrict__ in, int64_t n, uint32_t* out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = in[i] >> 1;
+}
+
+// Distinct-pair map (readset_pair_map): a pair's content is its two 64-byte read records (bases, ambiguity words, length),
+// 128 bytes side by side; what the align stage computes for a pair depends on them alone (the regions' hash: on the
+// lengths).  Pairs are sorted by a 32-bit hash of the content (stable: equal keys keep input order), a pair whose content
+// differs from its predecessor's starts a group, and every pair takes the first of its group as representative.  Equality
+// is tested byte for byte, so a hash collision only costs a missed merge.
+__global__ void k_pair_hashes(const uint8_t* __restrict__ recs, int64_t n_pairs, uint32_t* key, uint32_t* idx) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pairs; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint4* p = reinterpret_cast<const uint4*>(recs + (size_t)i * 128);
+        uint64_t h = 0x9e3779b97f4a7c15ULL;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint4 v = p[k];
+            h = mix64(h ^ ((uint64_t)v.y << 32 | v.x));
+            h = mix64(h ^ ((uint64_t)v.w << 32 | v.z));
+        }
+        key[i] = (uint32_t)(h >> 32) ^ (uint32_t)h;
+        idx[i] = (uint32_t)i;
+    }
+}
+__device__ __forceinline__ bool pair_recs_equal(const uint8_t* __restrict__ recs, uint32_t a, uint32_t b) {
+    const uint4* x = reinterpret_cast<const uint4*>(recs + (size_t)a * 128);
+    const uint4* y = reinterpret_cast<const uint4*>(recs + (size_t)b * 128);
+    bool eq = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint4 u = x[k], v = y[k];
+        eq = eq && u.x == v.x && u.y == v.y && u.z == v.z && u.w == v.w;
+    }
+    return eq;
+}
+// sorted position p -> p when it starts a group, else 0 (an inclusive max-scan then gives every position its group's start)
+__global__ void k_pair_group_starts(const uint8_t* __restrict__ recs, const uint32_t* __restrict__ key, const uint32_t* __restrict__ idx, int64_t n,
+                                    uint32_t* start) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const bool first = p == 0 || key[p] != key[p - 1] || !pair_recs_equal(recs, idx[p], idx[p - 1]);
+        start[p] = first ? (uint32_t)p : 0u;
+    }
+}
+// rep[pair] = the group's first pair; mult[rep] = pairs of the group (written by its last position; only reps get one)
+__global__ void k_pair_reps(const uint32_t* __restrict__ idx, const uint32_t* __restrict__ gs, int64_t n, uint32_t* rep, uint32_t* mult) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t g = gs[p], r = idx[g];
+        rep[idx[p]] = r;
+        if (p == n - 1 || gs[p + 1] != g) mult[r] = (uint32_t)(p - g + 1);
+    }
+}
+struct IsPairRep {
+    const uint32_t* rep;
+    __host__ __device__ bool operator()(const uint32_t& i) const { return rep[i] == i; }
+};
+// the copies a list of representatives stands for: out += sum(mult[list[i]] - 1) over the first *n_list entries
+__global__ void k_pair_dup_count(const uint32_t* __restrict__ list, const unsigned long long* __restrict__ n_list, const uint32_t* __restrict__ mult,
+                                 unsigned long long* out) {
+    const int64_t n = (int64_t)*n_list;
+    unsigned long long sum = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) sum += mult[list[i]] - 1u;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(out, sum);
+}
+// Fan-out, after every tier: each copy takes its representative's two records, edit counts and CIGAR words.  A copy claims
+// arena words of its own, so records never share words and an arena overflow is counted and flagged as it would have been
+// had the copy been aligned itself.  The words are claimed with one atomic per wave and PMX_FANOUT_ROUNDS x 64 pairs (one
+// per 64 pairs, as compact_emit claims them, put 78k atomics on one address per 10M reads: 0.9 ms for the kernel): a lane
+// counts the words of its pairs first, then copies.  A copy whose representative overflowed the arena cannot know how many
+// words it needs (the record's n_cigar is 0 then): counted in unknown[0], the host redoes the call without the map.
+#define PMX_FANOUT_ROUNDS 16
+__global__ void __launch_bounds__(256) k_pair_fanout(const uint32_t* __restrict__ rep, int64_t n_pairs, AlnRecord* records, int32_t* edits, uint32_t* cigars,
+                                                     uint64_t cigar_cap, unsigned long long* cigar_used, unsigned long long* unknown) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int64_t span = 64 * PMX_FANOUT_ROUNDS;
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / 64;
+    for (int64_t c0 = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / 64) * span; c0 < n_pairs; c0 += n_waves * span) {
+        uint32_t mine = 0, lost = 0;
+        for (int j = 0; j < PMX_FANOUT_ROUNDS; ++j) {
+            const int64_t d = c0 + j * 64 + lane;
+            if (d >= n_pairs) break;
+            const uint32_t r = rep[d];
+            if (r == (uint32_t)d) continue;
+            for (int s = 0; s < 2; ++s) {
+                const AlnRecord& x = records[2 * (size_t)r + s];
+                if (x.flags & PMX_REC_HAS_ALN) {
+                    mine += x.n_cigar;
+                    if ((x.flags & PMX_REC_OVERFLOW) && x.n_cigar == 0) ++lost;
+                }
+            }
+        }
+        uint32_t incl = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t v = __shfl_up(incl, o);
+            if (lane >= o) incl += v;
+        }
+        const uint32_t wave_total = __shfl(incl, 63);
+        unsigned long long wave_base = 0;
+        if (wave_total) {
+            if (lane == 0) wave_base = atomicAdd(cigar_used, (unsigned long long)wave_total);
+            wave_base = __shfl(wave_base, 0);
+        }
+        if (lost) atomicAdd(unknown, (unsigned long long)lost);
+        uint64_t coff = wave_base + (incl - mine);
+        for (int j = 0; j < PMX_FANOUT_ROUNDS; ++j) {
+            const int64_t d = c0 + j * 64 + lane;
+            if (d >= n_pairs) break;
+            const uint32_t r = rep[d];
+            if (r == (uint32_t)d) continue;
+            for (int s = 0; s < 2; ++s) {
+                AlnRecord rec = records[2 * (size_t)r + s];
+                if (rec.flags & PMX_REC_HAS_ALN) {
+                    const uint32_t src = rec.cigar_off, nw = rec.n_cigar;
+                    rec.cigar_off = (uint32_t)coff;
+                    if (coff + nw <= cigar_cap) {
+                        for (uint32_t k = 0; k < nw; ++k) cigars[coff + k] = cigars[src + k];
+                    } else {
+                        rec.flags |= PMX_REC_OVERFLOW;
+                        rec.n_cigar = 0;
+                    }
+                    coff += nw;
+                }
+                records[2 * (size_t)d + s] = rec;
+                if (edits) edits[2 * (size_t)d + s] = edits[2 * (size_t)r + s];
+            }
+        }
+    }
 }
 
 namespace {
@@ -325,9 +452,35 @@ const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStrea
     hipLaunchKernelGGL(k_pair_keys, dim3((unsigned)std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, st, rs->loc_key.p, n_items,
                        rs->pp_key.p, rs->pp_idx.p);
     PMX_HIP(rocprim::radix_sort_pairs(rs->pp_tmp.p, bytes, rs->pp_key.p, rs->pp_key2.p, rs->pp_idx.p, rs->pp_idx2.p, (size_t)n_items, 0, 64, st));
+    // (the map, too, depends on the reads alone; below a million pairs the align stage seldom wants it -- PMX_ALIGN_DEDUP_DEPTH
+    //  -- and makes it itself when it does)
+    if (side && n_items >= ((int64_t)1 << 20) && !pmx::opt_str(pmx::O_ALIGN_NO_DEDUP)) readset_pair_map(ctx, rs, st);
     if (side) { PMX_HIP(hipEventRecord(rs->pair_ev, side)); rs->pair_ev_pending = true; }
     rs->has_pair_order = true;
     return rs->pp_idx2.p;
+}
+
+// Distinct-pair map of a packed, paired read set with read records (k_pair_hashes .. k_pair_reps): rs->pd_rep[pair] = its
+// representative, rs->pd_mult[rep] = the pairs it stands for.  Enqueued on `st` (the side stream of the pair order, or the
+// context's stream).  10M reads: one 128-byte line per pair read twice, a 32-bit four-pass sort, ~0.55 ms.
+void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st) {
+    const int64_t n = rs->n / 2;
+    if (rs->has_pair_map || n < 1 || !rs->has_recs) return;
+    rs->pd_key.ensure((size_t)n); rs->pd_key2.ensure((size_t)n); rs->pd_idx.ensure((size_t)n); rs->pd_idx2.ensure((size_t)n);
+    rs->pd_gs.ensure((size_t)n); rs->pd_rep.ensure((size_t)n); rs->pd_mult.ensure((size_t)n);
+    size_t sort_bytes = 0, scan_bytes = 0;
+    PMX_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, rs->pd_key.p, rs->pd_key2.p, rs->pd_idx.p, rs->pd_idx2.p, (size_t)n, 0, 32, st));
+    PMX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, rs->pd_key.p, rs->pd_gs.p, (size_t)n, rocprim::maximum<uint32_t>(), st));
+    rs->pd_tmp.ensure(std::max(sort_bytes, scan_bytes));
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 8);
+    hipLaunchKernelGGL(k_pair_hashes, dim3(grid), dim3(256), 0, st, rs->recs.p, n, rs->pd_key.p, rs->pd_idx.p);
+    PMX_HIP(rocprim::radix_sort_pairs(rs->pd_tmp.p, sort_bytes, rs->pd_key.p, rs->pd_key2.p, rs->pd_idx.p, rs->pd_idx2.p, (size_t)n, 0, 32, st));
+    // (the unsorted keys are spent: their buffer takes the group starts before the scan)
+    hipLaunchKernelGGL(k_pair_group_starts, dim3(grid), dim3(256), 0, st, rs->recs.p, rs->pd_key2.p, rs->pd_idx2.p, n, rs->pd_key.p);
+    PMX_HIP(rocprim::inclusive_scan(rs->pd_tmp.p, scan_bytes, rs->pd_key.p, rs->pd_gs.p, (size_t)n, rocprim::maximum<uint32_t>(), st));
+    hipLaunchKernelGGL(k_pair_reps, dim3(grid), dim3(256), 0, st, rs->pd_idx2.p, rs->pd_gs.p, n, rs->pd_rep.p, rs->pd_mult.p);
+    PMX_HIP(hipGetLastError());
+    rs->has_pair_map = true;
 }
 }  // namespace pmx
 extern "C" {
@@ -347,7 +500,7 @@ int pmx_readset_order_pairs(pmx_ctx* ctx, pmx_readset* rs) {
     PMX_CATCH
 }
 
-static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int paired, int revcomp_mate2, uint64_t cigar_cap) {
+static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int paired, int revcomp_mate2, uint64_t cigar_cap, bool allow_dedup) {
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     const int64_t n_items = paired ? rs->n / 2 : rs->n;   // an odd trailing read is ignored (src/mm_align.c:372)
@@ -364,6 +517,8 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
     // (the counters are read back after every call, an empty read set's too: a rank whose shard holds no read)
     al->stats.ensure(4);
     PMX_HIP(hipMemsetAsync(al->stats.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    al->dd_count.ensure(4);   // distinct-pair map: [0] representatives, [1] copies of an arena-overflowed representative, [2] copies of bails
+    PMX_HIP(hipMemsetAsync(al->dd_count.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
     if (n_items <= 0) {
         al->last_dp_slots = 0; al->last_compact = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
         memset(&al->last_stats, 0, sizeof(al->last_stats));
@@ -827,8 +982,40 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
             A.mv_handover = nullptr; A.mv_stride = 0; A.mv_slots = 0;
             run_wave_tiers(n_t1, t1_list);
             };   // run_tail
+            const uint32_t* dd_rep = nullptr;   // distinct-pair map in use: pair -> representative
             if (use_compact) {
                 al->bail_list.ensure((size_t)n_items);
+                // Distinct pairs (readset_pair_map): the compact tier and the tail run one representative of every set of equal
+                // pairs, in launch order, and k_pair_fanout hands the copies their results at the end (10M bench reads: 18 % of
+                // the pairs are copies).  PMX_ALIGN_NO_DEDUP: every pair.
+                int64_t n_launch = n_items;
+                const uint32_t* dd_mult = nullptr;
+                // Copies are many only at depth: the bench workload at 10M reads (167 pairs per reference base) has 18 %, at
+                // 1.25M reads (21 per base) a few percent, which do not repay the map's launches and its host round trip --
+                // measured 6.6 -> 6.9 ms per step there.  Below PMX_ALIGN_DEDUP_DEPTH pairs per reference base (default 64)
+                // every pair runs itself.
+                double dedup_depth = 64.0;
+                if (const char* e = pmx::opt_str(pmx::O_ALIGN_DEDUP_DEPTH)) dedup_depth = atof(e);
+                if (allow_dedup && A.recs && !pmx::opt_str(pmx::O_ALIGN_NO_DEDUP) && (double)n_items >= dedup_depth * (double)al->ri.len) {
+                    if (rs->pair_ev_pending) { PMX_HIP(hipStreamWaitEvent(ctx->stream, rs->pair_ev, 0)); rs->pair_ev_pending = false; }
+                    readset_pair_map(ctx, rs, ctx->stream);   // (made beside the place stage with the pair order when the host asked for that)
+                    al->dd_list.ensure((size_t)n_items);
+                    const IsPairRep is_rep{rs->pd_rep.p};
+                    const rocprim::counting_iterator<uint32_t> every(0u);
+                    size_t bytes = 0;
+                    if (order) PMX_HIP(rocprim::select(nullptr, bytes, order, al->dd_list.p, al->dd_count.p, (size_t)n_items, is_rep, ctx->stream));
+                    else PMX_HIP(rocprim::select(nullptr, bytes, every, al->dd_list.p, al->dd_count.p, (size_t)n_items, is_rep, ctx->stream));
+                    al->dd_tmp.ensure(bytes);
+                    if (order) PMX_HIP(rocprim::select(al->dd_tmp.p, bytes, order, al->dd_list.p, al->dd_count.p, (size_t)n_items, is_rep, ctx->stream));
+                    else PMX_HIP(rocprim::select(al->dd_tmp.p, bytes, every, al->dd_list.p, al->dd_count.p, (size_t)n_items, is_rep, ctx->stream));
+                    unsigned long long h_reps = 0;
+                    PMX_HIP(hipMemcpyAsync(&h_reps, al->dd_count.p, sizeof(h_reps), hipMemcpyDeviceToHost, ctx->stream));
+                    PMX_HIP(hipStreamSynchronize(ctx->stream));
+                    n_launch = (int64_t)h_reps;
+                    order = al->dd_list.p;
+                    dd_rep = rs->pd_rep.p;
+                    dd_mult = rs->pd_mult.p;
+                }
                 const bool pos16 = al->ri.len <= 32767 && !pmx::opt_str(pmx::O_ALIGN_COMPACT_POS32);
                 const bool c_fused = pmx::opt_str(pmx::O_ALIGN_COMPACT_FUSED) != nullptr;
                 auto c_kern = c_fused ? (pos16 ? k_align_compact16_fused : k_align_compact32_fused) : (pos16 ? k_align_compact16 : k_align_compact32);
@@ -840,9 +1027,9 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
                 // their worst lane costs, and with a resident grid striding over the positions (PMX_ALIGN_COMPACT_WAVES = waves
                 // per CU brings it back) the slowest stride set the kernel's end -- 10M reads: 17.05 -> 15.5 ms, and the seeds
                 // kernel below 4.77 -> 4.10 ms.  (The hardware keeps 160 KB / c_lds = seven waves per CU resident either way.)
-                int64_t c_grid = (n_items + 63) / 64;
+                int64_t c_grid = (n_launch + 63) / 64;
                 if (const char* e = pmx::opt_str(pmx::O_ALIGN_COMPACT_WAVES)) c_grid = std::min<int64_t>((int64_t)ctx->n_cu * std::max(atoi(e), 1), c_grid);
-                A.n_items = n_items;
+                A.n_items = n_launch;
                 A.pair_perm = order;
                 A.retry_list = al->bail_list.p;
                 A.retry_count = al->retry_count.p + 2;
@@ -851,7 +1038,7 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
                 // registers allow instead of seven waves per CU; the seeds cross in HBM (224 bytes per pair with 16-bit
                 // position words).  PMX_ALIGN_COMPACT_FUSED keeps everything in k_align_compact.
                 if (!c_fused) {
-                    const size_t blocks = (size_t)((n_items + 63) / 64);
+                    const size_t blocks = (size_t)((n_launch + 63) / 64);
                     al->cseeds.ensure(blocks * (size_t)PMX_C_CAP * (pos16 ? 1 : 2) * 64);
                     al->cseed_n.ensure(blocks * 64);
                     A.cseeds = al->cseeds.p;
@@ -860,7 +1047,7 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
                     // takes 7.5 / 6.0 / 4.8 ms per 5M pairs, one workgroup per 64 pairs 4.1; the register budget of five waves per
                     // SIMD spills and gains 1 %, of six loses)
                     auto s_kern = pos16 ? k_compact_seeds16 : k_compact_seeds32;
-                    int64_t s_grid = (n_items + 63) / 64;
+                    int64_t s_grid = (n_launch + 63) / 64;
                     if (const char* e = pmx::opt_str(pmx::O_ALIGN_CSEED_WAVES)) s_grid = std::min<int64_t>((int64_t)ctx->n_cu * std::max(atoi(e), 1), s_grid);
                     timer_begin(ctx, "align_cseeds");
                     hipLaunchKernelGGL(s_kern, dim3((unsigned)s_grid), dim3(64), ((size_t)PMX_C_SEEDQ * 2 + 8) * 64 * sizeof(uint32_t),   // queues + eight staging words per lane
@@ -913,7 +1100,7 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
                 timer_end(ctx, "align_dom", 1);
                 if (c_multi) {
                     // (the list's length stays on the device: a resident grid -- seven waves per CU by the LDS -- strides over it)
-                    const int64_t m_grid = std::min<int64_t>((n_items + 63) / 64, (int64_t)ctx->n_cu * 7);
+                    const int64_t m_grid = std::min<int64_t>((n_launch + 63) / 64, (int64_t)ctx->n_cu * 7);
                     al->multi_ws.ensure((size_t)m_grid * PMX_CM_WS_WORDS * 64);
                     A.multi_ws = al->multi_ws.p;
                     timer_begin(ctx, "align_cmulti");
@@ -947,12 +1134,21 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
                     for (int k = 0; k < 8; ++k) fprintf(stderr, " %s=%.0f", cn[k], (double)h[k] / waves);
                     fprintf(stderr, "\n");
                 }
+                unsigned long long h_dups = 0;
+                if (dd_mult) {   // the copies of the pairs handed to the general tiers (compact_tier_items counts pairs, copies too)
+                    const unsigned dgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_launch + 255) / 256, (int64_t)ctx->n_cu * 8));
+                    hipLaunchKernelGGL(k_pair_dup_count, dim3(dgrid), dim3(256), 0, ctx->stream, al->bail_list.p, al->retry_count.p + 2, dd_mult, al->dd_count.p + 2);
+                    if (n_early > 0)
+                        hipLaunchKernelGGL(k_pair_dup_count, dim3(dgrid), dim3(256), 0, ctx->stream, al->early_list.p, al->multi_count.p + 2, dd_mult, al->dd_count.p + 2);
+                    PMX_HIP(hipGetLastError());
+                    PMX_HIP(hipMemcpyAsync(&h_dups, al->dd_count.p + 2, sizeof(h_dups), hipMemcpyDeviceToHost, ctx->stream));
+                }
                 unsigned long long h_bail = 0;
                 PMX_HIP(hipMemcpyAsync(&h_bail, al->retry_count.p + 2, sizeof(h_bail), hipMemcpyDeviceToHost, ctx->stream));
                 PMX_HIP(hipStreamSynchronize(ctx->stream));
                 n_t0 = (int64_t)h_bail;
                 order = al->bail_list.p;
-                al->last_compact = n_items - n_t0 - n_early;
+                al->last_compact = n_items - n_t0 - n_early - (int64_t)h_dups;
                 A.retry_list = al->retry_list2.p;
                 A.retry_count = al->retry_count.p;
             }
@@ -964,6 +1160,11 @@ static int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* 
                     PMX_HIP(hipEventSynchronize(ctx->tail_done));
                 }
                 run_tail(al->bail_list.p, n_t0);
+                if (dd_rep) {   // every tier is through: the copies take their representatives' results
+                    hipLaunchKernelGGL(k_pair_fanout, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_items + 256 * PMX_FANOUT_ROUNDS - 1) / (256 * PMX_FANOUT_ROUNDS), (int64_t)ctx->n_cu * 8))), dim3(256), 0,
+                                       ctx->stream, dd_rep, n_items, al->records.p, A.edits, al->cigars.p, (uint64_t)al->cigar_cap, al->cigar_used.p, al->dd_count.p + 1);
+                    PMX_HIP(hipGetLastError());
+                }
             }
         }
     } else {
@@ -1041,13 +1242,15 @@ int pmx_align_readset(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int 
     if (!al->opt.is_sr_like) cap = std::max<uint64_t>(cap, (uint64_t)rs->total / 8 + (uint64_t)rs->n * 16);
     if (al->cigar_words_per_kbase > 0.0) cap = std::max<uint64_t>(cap, (uint64_t)(al->cigar_words_per_kbase * 1.25 * (double)rs->total / 1000.0) + 4096);
     if (const char* e = pmx::opt_str(pmx::O_ALIGN_CIGAR_CAP)) cap = (uint64_t)std::max<long long>(atoll(e), 16);   // tests: force the redo
+    bool dedup = true;
     for (int attempt = 0;; ++attempt) {
-        const int rc = align_readset_once(ctx, al, rs, paired, revcomp_mate2, cap);
+        const int rc = align_readset_once(ctx, al, rs, paired, revcomp_mate2, cap, dedup);
         if (rc != PMX_OK) return rc;
-        unsigned long long used = 0, st[4] = {0, 0, 0, 0};
+        unsigned long long used = 0, st[4] = {0, 0, 0, 0}, dd[2] = {0, 0};
         PMX_TRY
         PMX_HIP(hipMemcpyAsync(&used, al->cigar_used.p, sizeof(used), hipMemcpyDeviceToHost, ctx->stream));
         PMX_HIP(hipMemcpyAsync(st, al->stats.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(dd, al->dd_count.p, sizeof(dd), hipMemcpyDeviceToHost, ctx->stream));
         PMX_HIP(hipStreamSynchronize(ctx->stream));
         PMX_CATCH
         al->last_cigar_used = used;
@@ -1062,6 +1265,9 @@ int pmx_align_readset(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int 
         if (used <= cap) return PMX_OK;
         if (attempt >= 2) return fail(PMX_ERR_CAPACITY, "CIGAR arena overflow persists after resizing");
         cap = used + 64;
+        // copies of a representative that overflowed the arena could not count their words (k_pair_fanout): `used` falls short
+        // by those, and the redo aligns every pair itself (its count is then exact for the last attempt)
+        if (dd[1] > 0) dedup = false;
     }
 }
 

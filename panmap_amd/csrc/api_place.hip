@@ -397,6 +397,7 @@ int pmx_readset_rewrap_device(pmx_ctx* ctx, pmx_readset* rs, const void* d_conca
     rs->packed = false;
     rs->has_order = false;
     rs->has_pair_order = false;
+    rs->has_pair_map = false;
     rs->packed_ranges.clear();
     rs->ordered_ranges.clear();
     rs->has_qual = false;
@@ -468,6 +469,7 @@ int pmx_readset_pack(pmx_ctx* ctx, pmx_readset* rs) {
     rs->packed = true;
     rs->has_order = false;   // (the buffer behind a wrapped read set may hold new reads)
     rs->has_pair_order = false;
+    rs->has_pair_map = false;
     rs->packed_ranges.clear();
     rs->packed_ranges.add(0, rs->n);
     rs->ordered_ranges.clear();
@@ -493,6 +495,7 @@ int pmx_readset_pack_range(pmx_ctx* ctx, pmx_readset* rs, int64_t r0, int64_t r1
     if (rs->packed) {   // re-packing part of a packed set: the order of those reads may have changed
         rs->has_order = false;
         rs->has_pair_order = false;
+        rs->has_pair_map = false;
         rs->ordered_ranges.clear();
     }
     rs->packed_ranges.add(r0, r1);

@@ -67,6 +67,11 @@ struct pmx_readset {
     mutable bool has_pair_order = false;
     mutable hipEvent_t pair_ev = nullptr;     // recorded behind the sort when it ran on a side stream
     mutable bool pair_ev_pending = false;
+    // distinct-pair map of the align stage (api_align.hip readset_pair_map), made with the pair order: pairs whose two read
+    // records are equal byte for byte share a representative (the first of them in input order), which alone is aligned
+    mutable pmx::DevBuf<uint32_t> pd_key, pd_key2, pd_idx, pd_idx2, pd_gs, pd_rep, pd_mult;
+    mutable pmx::DevBuf<char> pd_tmp;
+    mutable bool has_pair_map = false;
     ~pmx_readset() { if (pair_ev) (void)hipEventDestroy(pair_ev); }
     // streaming (pmx_readset_pack_range / pmx_place_add_reads_range): the ranges packed so far (`packed` once they cover the
     // set) and the ranges whose slice of loc_perm holds their reads in locality order (`has_order` once they cover the set:
@@ -83,4 +88,5 @@ const uint32_t* readset_locality_order(pmx_ctx* ctx, const pmx_readset* rs);
 // the same for the reads [r0, r1) alone: their slice of the permutation (absolute read indices), sorted by locality key
 const uint32_t* readset_locality_order_range(pmx_ctx* ctx, const pmx_readset* rs, int64_t r0, int64_t r1);
 const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t side);   // api_align.hip
+void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st);                  // api_align.hip
 }
