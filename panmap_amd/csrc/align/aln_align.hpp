@@ -255,6 +255,16 @@ PMX_HDN int test_zdrop(Work& W, const Opt& o, Ptr<const uint8_t> qseq, Ptr<const
     return ds.worst > o.zdrop ? 1 : 0;
 }
 
+// Whether mm_test_zdrop (test_zdrop) of a gap fill of qlen query bases can be skipped: a fill answered by a DP shortcut
+// (W.last_dp_shortcut) is gap-free, so its largest drop is at most the sum of its negative steps (mismatches, ambiguous
+// bases), which is at most a*qlen - score.  Once that is <= zdrop and <= zdrop_inv, test_zdrop returns 0 without looking.
+// (A fill over an N run can drop by far more than any mismatch count suggests: sc_ambi per N, however many.)
+PMX_HD bool fill_zdrop_skip(const Work& W, const Opt& o, int qlen, const Ez& ez) {
+    if (!W.last_dp_shortcut) return false;
+    const int64_t deficit = (int64_t)o.a * qlen - ez.score;
+    return deficit <= o.zdrop && deficit <= o.zdrop_inv;
+}
+
 // How far a gap of `gap` bases that starts at `at` can slide to the left over `room` aligned bases: one step for every base
 // before the gap that equals the base `gap` positions later (the alignment stays the same alignment).
 template <class SEQ>
@@ -730,9 +740,7 @@ PMX_HDN void align1(Work& W, const Opt& o, const RefIndex& ri, int qlen, const P
                 align_pair(W, o, qe - qs, qseq, re - rs, tseq, bw1, -1, o.zdrop, PMX_EZ_APPROX_MAX, ez);   // first pass: approximate Z-drop
                 W.skip_shortcut = 0;
             }
-            // a gap fill answered by shortcut (2) is gap-free with at most three mismatches (d(a+b) <= a + 2*gmin): its
-            // largest score drop is below 4(a+b) <= zdrop, so mm_test_zdrop returns 0 without looking
-            const bool tz_skip = W.last_dp_shortcut && 4 * (o.a + o.b) <= o.zdrop && 4 * (o.a + o.b) <= o.zdrop_inv;
+            const bool tz_skip = fill_zdrop_skip(W, o, qe - qs, ez);
             if (!tz_skip && decided) ref_getseq(ri, rs, re, tseq);   // the shortcut read the reference directly
             const int zdrop_code = tz_skip ? 0 : test_zdrop(W, o, qseq, tseq, ez.n_cigar, cig_tmp);
             if (zdrop_code != 0) align_pair(W, o, qe - qs, qseq, re - rs, tseq, bw1, -1, zdrop_code == 2 ? o.zdrop_inv : o.zdrop, 0, ez);

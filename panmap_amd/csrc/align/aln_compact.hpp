@@ -538,7 +538,7 @@ PMX_HD int c_align1(const CList<MT>& al, const Opt& o, const RefIndex& ri, const
         if (d > 0) { pm = qs - 1 - c_first(D.mm, qs0, qs); pf = qs - 1 - c_last(D.mm, qs0, qs); }
         CQryFn qf{rd, rev, qs - 1, -1};
         CRefFn tf{ri, rs - 1, -1};
-        if (!ksw_shortcut_ext_decide(ql, tl, d, pf, pm, qf, tf, a, b, (int8_t)o.q, (int8_t)o.e, (int8_t)o.q2, (int8_t)o.e2, zdrop, o.end_bonus, ez, &cig0))
+        if (!ksw_shortcut_ext_decide(ql, tl, d, pf, pm, 0, qf, tf, a, b, o.sc_ambi, (int8_t)o.q, (int8_t)o.e, (int8_t)o.q2, (int8_t)o.e2, zdrop, o.end_bonus, ez, &cig0))
             return PMX_C_BAIL;
         if (ez.n_cigar > 0) { r.has_p = 1; m_total += (int32_t)(cig0 >> 4); r.dp_score += (int32_t)ez.max; }
         rs1 = rs - (ez.reach_end ? ez.mqe_t + 1 : ez.max_t + 1);
@@ -554,7 +554,7 @@ PMX_HD int c_align1(const CList<MT>& al, const Opt& o, const RefIndex& ri, const
         const int ql = qe - qs, tl = re - rs;
         if (!ksw_shortcut_applicable(ql, tl, a, b, gmin, bw_long) || !ksw_shortcut_is_fill(ql, tl, PMX_EZ_APPROX_MAX)) return PMX_C_BAIL;
         const int d = c_count(D.mm, qs, qe);
-        if (!ksw_shortcut_fill_decide(ql, d, 0, a, b, gmin, PMX_EZ_APPROX_MAX, ez, &cig0)) return PMX_C_BAIL;
+        if (!ksw_shortcut_fill_decide(ql, d, 0, 0, 0, a, b, o.sc_ambi, gmin, o.e < o.e2 ? o.e : o.e2, PMX_EZ_APPROX_MAX, ez, &cig0)) return PMX_C_BAIL;
         // (the fill is gap-free with at most three mismatches: mm_test_zdrop cannot fire, see align1)
         if (!(4 * (o.a + o.b) <= o.zdrop && 4 * (o.a + o.b) <= o.zdrop_inv)) return PMX_C_BAIL;
         r.has_p = 1;
@@ -571,7 +571,7 @@ PMX_HD int c_align1(const CList<MT>& al, const Opt& o, const RefIndex& ri, const
         if (d > 0) { pf = c_first(D.mm, qe, qe0) - qe; pm = c_last(D.mm, qe, qe0) - qe; }
         CQryFn qf{rd, rev, qe, 1};
         CRefFn tf{ri, re, 1};
-        if (!ksw_shortcut_ext_decide(ql, tl, d, pf, pm, qf, tf, a, b, (int8_t)o.q, (int8_t)o.e, (int8_t)o.q2, (int8_t)o.e2, o.zdrop, o.end_bonus, ez, &cig0))
+        if (!ksw_shortcut_ext_decide(ql, tl, d, pf, pm, 0, qf, tf, a, b, o.sc_ambi, (int8_t)o.q, (int8_t)o.e, (int8_t)o.q2, (int8_t)o.e2, o.zdrop, o.end_bonus, ez, &cig0))
             return PMX_C_BAIL;
         if (ez.n_cigar > 0) { r.has_p = 1; m_total += (int32_t)(cig0 >> 4); r.dp_score += (int32_t)ez.max; }
         re1 = re + (ez.reach_end ? ez.mqe_t + 1 : ez.max_t + 1);

@@ -769,17 +769,79 @@ PMX_HD int count_diff(Ptr<const uint8_t> a, Ptr<const uint8_t> b, int n) {
 //  (2) global alignment in the approximate-max first pass of two equal-length sequences without
 //      ambiguous bases whose Hamming distance d satisfies d*(a+b) <= a + 2*min(q+e,q2+e2) (strictly less when
 //      gaps are right-aligned): no gapped alignment scores more than the gap-free one for any prefix pair on the
-//      main diagonal, so the traceback is all-diagonal -> score = len*a - d*(a+b), CIGAR = len M.
+//      main diagonal, so the traceback is all-diagonal -> score = len*a - d*(a+b), CIGAR = len M;
+//  (1d), (2) with ambiguous bases: an N (score -sc_ambi against anything) on the query, the target or both, mixed with
+//      real mismatches, under the bounds stated at ksw_shortcut_ext_amb / ksw_shortcut_fill_decide (an N on both
+//      sides, as on an N run of the reference that the read carries too, costs those bounds nothing).  Such a fill
+//      may hold any number of N, so its running score can drop by more than zdrop: align1 skips mm_test_zdrop of an
+//      answered fill only when fill_zdrop_skip bounds the drop (aln_align.hpp).
 // Everything else runs the DP.
 // QF / TF: callables returning the query / target base at position i (so the bases can come from the work
 // arena, straight from the reference in global memory, or be read back to front for a left extension)
 // The decisions of the shortcuts, separated from how the mismatch statistics were obtained (a per-base scan here, a
 // packed XOR in the compact tier, aln_compact.hpp): both tiers answer from the SAME code.
-// Extension (EXTZ_ONLY): d = positions i < qlen where the bases differ or one is ambiguous, pf / pm = the smallest /
-// largest such position.  cig0 receives the single CIGAR operation when ez.n_cigar == 1.
+// (1d) of ksw_shortcut_ext_decide: a diagonal whose defects include ambiguous bases (score -c on either side, c = sc_ambi,
+// 0 <= c <= emin = min(e, e2) < gmin).  Bounds, for any path from the origin to (i, j):
+//   per query base, an aligned base scores at most ub(i) = a (real) or -c (N); per target base, at most ubT(j) likewise;
+//   a gap of L bases costs >= (gmin - emin) + L*emin, and a base in a gap gives up its ub: a real one a + emin >= 0
+//   more than the bound, an N one emin - c >= 0.  Hence, with U_i / UT_j the prefix sums of ub / ubT:
+//   (A) j > i (>= j-i deletions):    H(i,j) <= U_i - (gmin - emin) - (j-i)*emin
+//   (B) i > j (>= i-j insertions):   H(i,j) <= UT_j - (gmin - emin) - (i-j)*emin
+//   (C) a gapped path back onto the diagonal has >= 2 gaps: <= U_m - 2*gmin + c (and <= UT_m - 2*gmin + c).
+// The diagonal H_d(m) = U_m - Dq_m = UT_m - Dt_m, where the query-side deficit Dq counts a+b per real mismatch and a+c per
+// base ambiguous on the target only, Dt likewise a+b and a+c per base ambiguous on the query only (an N on both sides, the
+// usual case on an N run, costs neither).  With Dq <= gmin and Dt < gmin - emin over the query:
+//   every cell off the diagonal is <= H_d(min(i,j)) (A, B), so the running max is the first maximum of H_d (from 0);
+//   row qlen-1: H(qlen-1,t) < H_d(qlen-1) for t < qlen-1 (B: the diagonal loses at most emin per N or real match after t,
+//   b - emin < a+b per real mismatch) and <= for t > qlen-1 (A), so mqe = H_d(qlen-1) at t = qlen-1; column qlen-1 when
+//   tlen == qlen likewise by (A) if also Dq < gmin - emin; (C) and gmin > c: every diagonal cell is reached diagonally
+//   with a strict margin (either tie rule), the traceback is all-diagonal; z-drop: each anti-diagonal holds a cell within
+//   gmin (inside) or q2 + L*e2 (past the query end, where the allowance is >= L*e2) of the diagonal's value, so it cannot
+//   fire while the diagonal's largest drop from its running max + max(gmin, q2) <= zdrop.
 template <class QF, class TF>
-PMX_HD bool ksw_shortcut_ext_decide(int qlen, int tlen, int d, int pf, int pm, QF& qf, TF& tf, int a, int b, int8_t q, int8_t e, int8_t q2,
-                                    int8_t e2, int zdrop, int end_bonus, Ez& ez, uint32_t* cig0) {
+PMX_HD bool ksw_shortcut_ext_amb(int qlen, int tlen, QF& qf, TF& tf, int a, int b, int c, int8_t q, int8_t e, int8_t q2, int8_t e2, int zdrop,
+                                 int end_bonus, Ez& ez, uint32_t* cig0) {
+    const int g1 = q + e, g2 = q2 + e2;
+    const int gmin = g1 < g2 ? g1 : g2, emin = e < e2 ? e : e2;
+    if (c < 0 || c > emin || c >= gmin) return false;
+    const int lim_q = tlen == qlen ? gmin - emin - 1 : gmin, lim_t = gmin - emin - 1;
+    int dq = 0, dt = 0, h = 0, hmax = 0, mpos = -1, drop = 0;
+    for (int i = 0; i < qlen; ++i) {
+        const uint32_t x = qf(i), y = tf(i);
+        int s = a;
+        if (x > 3 || y > 3) {
+            s = -c;
+            if (x <= 3) dq += a + c;
+            else if (y <= 3) dt += a + c;
+        } else if (x != y) {
+            s = -b;
+            dq += a + b;
+            dt += a + b;
+        }
+        if (dq > lim_q || dt > lim_t) return false;
+        h += s;
+        if (h > hmax) { hmax = h; mpos = i; }
+        if (hmax - h > drop) drop = hmax - h;
+    }
+    if (drop + (gmin > q2 ? gmin : q2) > zdrop) return false;
+    ez_reset(ez);
+    ez.max = (uint32_t)hmax;
+    ez.max_t = ez.max_q = mpos;
+    ez.mqe = h;
+    ez.mqe_t = qlen - 1;
+    if (tlen == qlen) { ez.mte = h; ez.mte_q = qlen - 1; }
+    ez.reach_end = ez.mqe + end_bonus > (int)ez.max ? 1 : 0;
+    const int len = ez.reach_end ? qlen : ez.max_q + 1;
+    if (len > 0) { *cig0 = (uint32_t)len << 4; ez.n_cigar = 1; }
+    return true;
+}
+
+// Extension (EXTZ_ONLY): d = positions i < qlen where the bases differ or one is ambiguous, pf / pm = the smallest /
+// largest such position, amb = how many of them hold an ambiguous base (c = sc_ambi: used only when amb > 0).  cig0
+// receives the single CIGAR operation when ez.n_cigar == 1.
+template <class QF, class TF>
+PMX_HD bool ksw_shortcut_ext_decide(int qlen, int tlen, int d, int pf, int pm, int amb, QF& qf, TF& tf, int a, int b, int c, int8_t q, int8_t e,
+                                    int8_t q2, int8_t e2, int zdrop, int end_bonus, Ez& ez, uint32_t* cig0) {
     const int g1 = q + e, g2 = q2 + e2;
     const int gmin = g1 < g2 ? g1 : g2, gmax = g1 > g2 ? g1 : g2;
     if (d == 0) {
@@ -855,6 +917,7 @@ PMX_HD bool ksw_shortcut_ext_decide(int qlen, int tlen, int d, int pf, int pm, Q
             return true;
         }
     }
+    if (amb > 0) return ksw_shortcut_ext_amb(qlen, tlen, qf, tf, a, b, c, q, e, q2, e2, zdrop, end_bonus, ez, cig0);
     return false;
 }
 // pre-conditions shared by every shortcut, and the ones of the extension / gap-fill class
@@ -867,15 +930,26 @@ PMX_HD bool ksw_shortcut_is_ext(int qlen, int tlen, int a, int b, int gmax, int 
 PMX_HD bool ksw_shortcut_is_fill(int qlen, int tlen, int flag) {
     return !(flag & PMX_EZ_EXTZ_ONLY) && (flag & PMX_EZ_APPROX_MAX) && !(flag & PMX_EZ_APPROX_DROP) && qlen == tlen;
 }
-// Gap fill in the approximate-max first pass: d differing positions (an ambiguous query base counts), amb ambiguous ones
-PMX_HD bool ksw_shortcut_fill_decide(int qlen, int d, int amb, int a, int b, int gmin, int flag, Ez& ez, uint32_t* cig0) {
-    // gap-free = a*n - d(a+b); any gapped global path has >= 2 gaps and <= n-1 pairs: <= a(n-1) - 2*gmin.  With
-    // left-aligned gaps (no RIGHT flag) a tie is harmless: the traceback takes a gap only when it is strictly
-    // better (`d = a > z ? 1 : 0`), and the score is the same.
+// Gap fill in the approximate-max first pass: d real mismatches, nq / nt positions where only the query / only the target
+// base is ambiguous, nb positions where both are (c = sc_ambi, emin = min(e, e2): used only when one of those is > 0)
+PMX_HD bool ksw_shortcut_fill_decide(int qlen, int d, int nq, int nt, int nb, int a, int b, int c, int gmin, int emin, int flag, Ez& ez,
+                                     uint32_t* cig0) {
+    // Without ambiguous bases: gap-free = a*n - d(a+b); any gapped global path has >= 2 gaps and <= n-1 pairs:
+    // <= a(n-1) - 2*gmin.  In general (bounds (C) of ksw_shortcut_ext_amb, 0 <= c <= emin): a gapped path back onto the
+    // diagonal at any prefix m scores <= U_m - Mq with Mq = 2*gmin + a, or 2*gmin - c once the query holds an N (an N
+    // in a gap gives up only emin - c), and <= UT_m - Mt likewise with the target's N; the gap-free path scores
+    // U_m - Dq_m = UT_m - Dt_m (the deficits of ksw_shortcut_ext_amb), both growing with m.  So Dq <= Mq or Dt <= Mt
+    // over the whole fill keeps every prefix pair on the main diagonal gap-free.  With left-aligned gaps (no RIGHT
+    // flag) a tie is harmless: the traceback takes a gap only when it is strictly better (`d = a > z ? 1 : 0`), and
+    // the score is the same.
     const bool right = (flag & PMX_EZ_RIGHT) != 0;
-    if (amb == 0 && (right ? d * (a + b) < a + 2 * gmin : d * (a + b) <= a + 2 * gmin)) {
+    const int ab = a + b, ac = a + c;
+    if (nq + nt + nb > 0 && (c < 0 || c > emin)) return false;
+    const int dq = d * ab + nt * ac, mq = 2 * gmin + (nq + nb > 0 ? -c : a);
+    const int dt = d * ab + nq * ac, mt = 2 * gmin + (nt + nb > 0 ? -c : a);
+    if (right ? (dq < mq || dt < mt) : (dq <= mq || dt <= mt)) {
         ez_reset(ez);
-        ez.score = qlen * a - d * (a + b);
+        ez.score = qlen * a - d * ab - (nq + nt + nb) * ac;
         *cig0 = (uint32_t)qlen << 4;
         ez.n_cigar = 1;
         return true;
@@ -889,32 +963,45 @@ PMX_HD bool ksw_shortcut_f(Work& W, int qlen, QF& qf, int tlen, TF& tf, const in
     PMX_LDS(&W);
     Ptr<uint32_t> cig_tmp = W.cig_tmp; PMX_LDS(cig_tmp);
     const int a = mat[0], b = -mat[1];
+    // the score of an ambiguous base (code 4) against anything; a matrix that is not of that shape gets no closed form
+    // for ambiguous bases (c < 0 declines them)
+    bool amb_uniform = true;
+    for (int k = 0; k < 5; ++k) amb_uniform = amb_uniform && mat[k * 5 + 4] == mat[4] && mat[20 + k] == mat[4];
+    const int c = amb_uniform ? -mat[4] : -1;
     const int g1 = q + e, g2 = q2 + e2;
     const int gmin = g1 < g2 ? g1 : g2, gmax = g1 > g2 ? g1 : g2;
     if (!ksw_shortcut_applicable(qlen, tlen, a, b, gmin, w)) return false;
     uint32_t cig0 = 0;
     bool done = false;
     if (ksw_shortcut_is_ext(qlen, tlen, a, b, gmax, zdrop, flag)) {
-        // d = differing or ambiguous positions among the first qlen; pf / pm: smallest / largest such position
-        int d = 0, pm = -1, pf = INT32_MAX;
+        // d = differing or ambiguous positions among the first qlen; pf / pm: smallest / largest such position; amb: how
+        // many of them hold an ambiguous base
+        int d = 0, pm = -1, pf = INT32_MAX, amb = 0;
         for (int i = lane_id(); i < qlen; i += PMX_W) {
             const uint32_t cq = qf(i), ct = tf(i);
             if (cq != ct || cq > 3 || ct > 3) { ++d; pm = i; pf = i < pf ? i : pf; }
-        }
-        d = wave_sum_i32(d);
-        if (d > 0 && d <= 2) { pm = wave_max_i32(pm); pf = -wave_max_i32(-pf); }
-        done = ksw_shortcut_ext_decide(qlen, tlen, d, pf, pm, qf, tf, a, b, q, e, q2, e2, zdrop, end_bonus, ez, &cig0);
-    } else if (ksw_shortcut_is_fill(qlen, tlen, flag)) {
-        // differing positions, and ambiguous bases (any of those forces the DP)
-        int d = 0, amb = 0;
-        for (int i = lane_id(); i < qlen; i += PMX_W) {
-            const uint32_t cq = qf(i), ct = tf(i);
-            d += (cq != ct || cq > 3) ? 1 : 0;
             amb += (cq > 3 || ct > 3) ? 1 : 0;
         }
         d = wave_sum_i32(d);
         amb = wave_sum_i32(amb);
-        done = ksw_shortcut_fill_decide(qlen, d, amb, a, b, gmin, flag, ez, &cig0);
+        if (d > 0 && d <= 2) { pm = wave_max_i32(pm); pf = -wave_max_i32(-pf); }
+        done = ksw_shortcut_ext_decide(qlen, tlen, d, pf, pm, amb, qf, tf, a, b, c, q, e, q2, e2, zdrop, end_bonus, ez, &cig0);
+    } else if (ksw_shortcut_is_fill(qlen, tlen, flag)) {
+        // real mismatches, and positions ambiguous on the query only / on the target only / on both
+        int d = 0, nq = 0, nt = 0, nb = 0;
+        for (int i = lane_id(); i < qlen; i += PMX_W) {
+            const uint32_t cq = qf(i), ct = tf(i);
+            d += (cq != ct && cq <= 3 && ct <= 3) ? 1 : 0;
+            nq += (cq > 3 && ct <= 3) ? 1 : 0;
+            nt += (cq <= 3 && ct > 3) ? 1 : 0;
+            nb += (cq > 3 && ct > 3) ? 1 : 0;
+        }
+        d = wave_sum_i32(d);
+        nq = wave_sum_i32(nq);
+        nt = wave_sum_i32(nt);
+        nb = wave_sum_i32(nb);
+        const int emin = e < e2 ? e : e2;
+        done = ksw_shortcut_fill_decide(qlen, d, nq, nt, nb, a, b, c, gmin, emin, flag, ez, &cig0);
     }
     if (done) {
         if (ez.n_cigar > 0) cig_tmp[0] = cig0;
