@@ -495,6 +495,100 @@ int pmx_meta_attach_dist(pmx_meta *m, pmx_dist *d);
 int pmx_meta_row_range(const pmx_meta *m, int64_t *first, int64_t *count);
 double pmx_read_dust(const char *seq, int64_t len, int32_t window);
 
+/* ------------------------------------------------------------------------------------------
+ * GENOTYPE + CONSENSUS stages (runGenotyping / runConsensus, src/main.cpp:1828-1900).  The reference forks
+ * `bcftools mpileup -Ou -B`, `bcftools call --ploidy 1 -m -A`, filters the calls (src/genotyping.cpp:167-279) and forks
+ * `bcftools consensus` (src/conversion.cpp:83-255).  Here: a device pileup into integer tables, the htslib error model and
+ * the reference's filter restated over those tables, and the two writers.  Substitutions only; DESIGN.md section 7 names
+ * what is left out (INDEL records, BAQ, the rank-test annotations, the allele pruning of `call -m`).
+ *
+ * pmx_pileup_* replace createMplpBcf (src/conversion.cpp:83-128).  Tables per 0-based reference position:
+ *   hist[pos][q 0..63][strand 0 fwd / 1 rev][base A C G T N]  (PMX_PILEUP_HIST uint32 counters per position): the bases
+ *     bcf_call_glfgen hands to errmod_cal, q as it caps it (src/3rdparty/bcftools/bam2bcf.c:425-461);
+ *   aux[pos][0..3]: raw depth (INFO/DP), sum of the capped mapping qualities of those bases (MQ = sum / bases), bases of
+ *     MQ-0 reads, reads covering the position with a deletion.
+ * Reads enter as the BAM of the align stage shows them: the filters of mplp_func (bcftools/mpileup.c:196-299: orphans of
+ * paired data are skipped), the depth cap of bam_plp_push in BAM order (htslib-1.20/sam.c:6097-6151) and the
+ * reconciliation of overlapping mates (sam.c:5824-6003) are applied.  names_concat / name_offsets (n_reads + 1; names as
+ * in the FASTQ, a trailing /1 or /2 is dropped) feed the read-name hash that picks the mate an overlap keeps; NULL = the
+ * reads are called r0, r1, ... by read index.
+ * ------------------------------------------------------------------------------------------ */
+#define PMX_PILEUP_HIST 640
+#define PMX_PILEUP_AUX 4
+typedef struct {
+    int32_t max_depth;    /* 250 (mpileup.c:1367); 0 = no cap */
+    int32_t min_baseq;    /* 1   (mpileup.c:1363) */
+    int32_t max_baseq;    /* 60  (mpileup.c:1364) */
+    int32_t delta_baseq;  /* 30  (mpileup.c:1365) */
+    int32_t cap_mapq;     /* 60  (bca->capQ, bam2bcf.c:49) */
+    int32_t reserved[3];
+} pmx_pileup_params;
+void pmx_pileup_default_params(pmx_pileup_params *pp);
+typedef struct pmx_pileup pmx_pileup;
+int pmx_pileup_create(pmx_ctx *ctx, pmx_pileup **out);
+void pmx_pileup_free(pmx_ctx *ctx, pmx_pileup *pu);
+/* [hot] the pileup of the results the aligner's last pmx_align_readset left on the device, over the same read set
+ * (qualities as attached with pmx_readset_set_qualities; without them every base is 'I'); ref_len = the aligner's genome */
+int pmx_pileup_run(pmx_ctx *ctx, pmx_pileup *pu, pmx_aligner *al, const pmx_readset *rs, int64_t ref_len, int paired,
+                   int revcomp_mate2, const char *names_concat, const int64_t *name_offsets, const pmx_pileup_params *pp);
+/* the same from host arrays (records + CIGAR arena as pmx_align_fetch / pmx_dist_fetch_gathered return them, reads and
+ * qualities concatenated with n_records + 1 offsets): what rank 0 of a --gpus N run holds for the whole sample */
+int pmx_pileup_run_records(pmx_ctx *ctx, pmx_pileup *pu, const pmx_aln_record *records, int64_t n_records,
+                           const uint32_t *cigar_arena, int64_t n_words, const char *concat, const char *qual_concat,
+                           const int64_t *offsets, int64_t ref_len, int paired, int revcomp_mate2, const char *names_concat,
+                           const int64_t *name_offsets, const pmx_pileup_params *pp);
+/* hist: ref_len * PMX_PILEUP_HIST, aux: ref_len * PMX_PILEUP_AUX (either may be NULL) */
+int pmx_pileup_fetch(pmx_ctx *ctx, pmx_pileup *pu, uint32_t *hist, uint32_t *aux);
+/* per read of the last run: bit 0 = in the pileup, bit 1 = its overlap with its mate was reconciled, bit 2 = it is the
+ * second mate in BAM order, bit 3 = it keeps the quality of agreeing bases; rank = its place in the BAM (0xffffffff: not
+ * written).  Either may be NULL. */
+int pmx_pileup_read_info(const pmx_pileup *pu, uint8_t *flags, uint32_t *bam_rank, int64_t cap);
+/* algorithmic HBM bytes of the last run's two kernels (inputs read once + tables written once) */
+int64_t pmx_pileup_bytes(const pmx_pileup *pu);
+
+/* pmx_genotype_* replace createVcfWithMutationMatrices / createConsensus (src/conversion.cpp:130-255) and
+ * genotyping::applyMutationSpectrum / passesConsensusGate (src/genotyping.cpp:167-279).  Host; positions are few. */
+/* IndexBuilder::computeSubstitutionSpectrum (src/index_single_mode.cpp:1408-1558): counts[from * 4 + to] of the
+ * substitutions on the tree's branches, the number of branches, and the genome length the rates are normalised with: the
+ * median of ten leaf genomes, here the leaves evenly spaced in DFS order (the reference walks a hash map) */
+int pmx_genotype_spectrum_counts(const pmx_panman *pm, int64_t counts[16], int64_t *n_branches, int64_t *genome_len);
+/* the rates for genome length L turned to phred as loadSubstMatrixFromIndex does (src/main.cpp:290-311); returns 1 when
+ * the tree shows no substitution at all (the reference then runs without a spectrum), 0 otherwise */
+int pmx_genotype_spectrum_phred(const int64_t counts[16], int64_t n_branches, int64_t genome_len, double phred[16]);
+/* one site from its hist[pos] (PMX_PILEUP_HIST counters): errmod_cal (htslib-1.20/errmod.c:143-208) + bcf_call_combine
+ * (bam2bcf.c:955-1115).  ref_base: the reference letter.  alleles[0..n_alleles): A C G T N = 0..4, reference first, then
+ * the alternatives seen by falling quality sum (the unseen allele is not listed); pl[k] = the likelihood of the homozygote
+ * of allele k as mpileup scales it (minimum over ALL its genotypes subtracted, not renormalised); ad[k], adf/adr, dp4. */
+typedef struct {
+    int32_t n_alleles;
+    int32_t alleles[5];
+    int32_t pl[5];
+    int32_t ad[5];
+    int32_t dp4[4];
+    int32_t n_bases;      /* bases in the model (sum of hist) */
+    int32_t reserved[3];
+} pmx_site_call;
+int pmx_genotype_site(const uint32_t *hist, char ref_base, pmx_site_call *out);
+/* applyMutationSpectrum (src/genotyping.cpp:200-279) on one raw VCF line; phred = NULL: the plain branch of
+ * createVcfWithMutationMatrices (src/conversion.cpp:163-178).  Writes the line to keep ("" = dropped) and returns its
+ * length, or a negative error (a line the reference throws on). */
+int64_t pmx_genotype_filter_line(const char *line, const double *phred16, int min_depth, double min_qual, char *out, int64_t cap);
+typedef struct pmx_genotyper pmx_genotyper;
+/* calls of a whole genome from the pileup tables: every position where an alternative base has a non-zero quality sum
+ * becomes a raw line, goes through pmx_genotype_filter_line, and a line that stays is written with REF and the called
+ * allele alone.  Returns the number of records, or a negative error. */
+int64_t pmx_genotype_call(const uint32_t *hist, const uint32_t *aux, const char *reference, int64_t ref_len, const char *chrom,
+                          const double *phred16, int min_depth, double min_qual, pmx_genotyper **out);
+int64_t pmx_genotype_num_records(const pmx_genotyper *g);
+const char *pmx_genotype_record(const pmx_genotyper *g, int64_t i);   /* the VCF line without its newline */
+void pmx_genotype_free(pmx_genotyper *g);
+/* `<prefix>.vcf`: header (fileformat, contig, the INFO / FORMAT fields written, #CHROM ... sample_name) + the records */
+int pmx_genotype_write_vcf(const pmx_genotyper *g, const char *path, const char *chrom, int64_t ref_len, const char *sample_name);
+/* `bcftools consensus -f ref.fa vcf` for substitution records + the header rename of createConsensus
+ * (src/conversion.cpp:186-255): the first sequence of ref_fa with every record's ALT in place of its REF, `>header`,
+ * 60 bases per line */
+int pmx_genotype_write_consensus(const char *vcf_path, const char *ref_fa_path, const char *out_path, const char *header);
+
 /* The library's tuning / testing / diagnostic switches are environment variables PMX_<NAME>, all of them listed with their
  * class and meaning in ONE table (csrc/device/pmx_options.hpp).  The environment is read once, at the first use;
  * pmx_options_reload reads it again (a test that changes a switch inside one process), pmx_options_describe writes the

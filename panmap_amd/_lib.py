@@ -220,6 +220,24 @@ SIGNATURES = {
     "pmx_dist_rank_counts": (_i32, [_vp, _vp, _vp]),
     "pmx_dist_fetch_gathered": (_i32, [_vp, _vp, _i64, _vp, _i64]),
     "pmx_dist_fetch_gathered_async": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "pmx_pileup_default_params": (None, [_vp]),
+    "pmx_pileup_create": (_i32, [_vp, _PP]),
+    "pmx_pileup_free": (None, [_vp, _vp]),
+    "pmx_pileup_run": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "pmx_pileup_run_records": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "pmx_pileup_fetch": (_i32, [_vp, _vp, _vp, _vp]),
+    "pmx_pileup_read_info": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_pileup_bytes": (_i64, [_vp]),
+    "pmx_genotype_spectrum_counts": (_i32, [_vp, _vp, _vp, _vp]),
+    "pmx_genotype_spectrum_phred": (_i32, [_vp, _i64, _i64, _vp]),
+    "pmx_genotype_site": (_i32, [_vp, C.c_char, _vp]),
+    "pmx_genotype_filter_line": (_i64, [_cp, _vp, _i32, C.c_double, _vp, _i64]),
+    "pmx_genotype_call": (_i64, [_vp, _vp, _cp, _i64, _cp, _vp, _i32, C.c_double, _PP]),
+    "pmx_genotype_num_records": (_i64, [_vp]),
+    "pmx_genotype_record": (_cp, [_vp, _i64]),
+    "pmx_genotype_free": (None, [_vp]),
+    "pmx_genotype_write_vcf": (_i32, [_vp, _cp, _cp, _i64, _cp]),
+    "pmx_genotype_write_consensus": (_i32, [_cp, _cp, _cp, _cp]),
 }
 
 class MetaParams(C.Structure):

@@ -29,6 +29,10 @@ struct pmx_index {
     pmx::LiteIndex ix;
 };
 
+namespace pmx {
+const Panman& panman_of(const pmx_panman* pm) { return pm->pm; }   // host/genotype.cpp walks the tree for its spectrum
+}
+
 extern "C" {
 
 const char* pmx_last_error(void) { return pmx::g_last_error.c_str(); }

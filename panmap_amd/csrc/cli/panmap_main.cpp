@@ -4,10 +4,11 @@
 //           seeding parameters, src/main.cpp:371-396; -f rebuilds; -i loads a given file; --index-out names the output)
 //   place   reads -> `<prefix>.placement.tsv` (src/placement.cpp:1952-2003)
 //   align   placed genome -> `<prefix>.ref.fa` (+ .fai), reads aligned to it -> `<prefix>.bam` (+ .bai)
-// `--stop index|place|align` ends after that stage.  --meta -> `<prefix>.mgsr.abundance.out`.  The later stages of the
-// reference (genotype, consensus), the bwa backend and HPC seeds are outside this library: asking for them is an error, not a silent
-// no-op (a `--stop` beyond align stops after align with a note).  Output prefix: -o, else derived from reads1 as the
-// reference derives it.  Exit code 130 on SIGINT.
+//   genotype   device pileup of the alignments -> substitution calls -> `<prefix>.vcf` (runGenotyping, src/main.cpp:1828-1875)
+//   consensus  the placed genome with the calls applied -> `<prefix>.consensus.fa` (runConsensus, src/main.cpp:1877-1900)
+// `--stop index|place|align|genotype|consensus` ends after that stage (default: consensus).  --meta ->
+// `<prefix>.mgsr.abundance.out`.  The bwa backend, HPC seeds and BAQ are outside this library: asking for them is an error,
+// not a silent no-op.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -47,6 +48,8 @@ struct Config {
     bool refine = false;   // src/main.cpp:186-190, 2002-2011
     double refine_top_pct = 0.01;
     int refine_max_top_n = 150, refine_neighbor_radius = 2, refine_max_neighbor_n = 150;
+    int min_depth = 1;       // --min-depth / --min-qual: the consensus gate (src/genotyping.cpp:167-174, 272)
+    double min_qual = 30.0;
 };
 
 void on_sigint(int) { _exit(130); }
@@ -66,7 +69,8 @@ void usage() {
     fputs("Usage: panmap <panman> [reads1.fq[.gz]] [reads2.fq[.gz]] [options]\n"
           "  -o, --output PREFIX        output prefix (default: derived from reads1)\n"
           "  -t, --threads N            accepted (the GPU owns the parallelism)\n"
-          "      --stop STAGE           index|place|align (later stages are not part of this build)\n"
+          "      --stop STAGE           index|place|align|genotype|consensus (default consensus)\n"
+          "      --min-depth N          high-quality bases a call needs (default 1)     --min-qual F   lowest QUAL kept (default 30)\n"
           "      --batch FILE           one sample per line: reads1 [reads2] [prefix]; the index stays resident\n"
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
@@ -133,9 +137,12 @@ Config parse(int argc, char** argv) {
         else if (a == "--em-maximum-rounds") c.em_max_rounds = atoi(v().c_str());
         else if (a == "--discard") c.discard = atof(v().c_str());
         else if (a == "--dust") c.dust = atof(v().c_str());
+        else if (a == "--min-depth") c.min_depth = atoi(v().c_str());
+        else if (a == "--min-qual") c.min_qual = atof(v().c_str());
+        else if (a == "--baq") die("--baq (base alignment quality) is not implemented in this build; the pileup runs as `mpileup -B` does");
         else if (a == "--filter-and-assign" || a == "--impute" || a == "--extent-guard" || a == "--reference-node" ||
                  a == "--dump-sequence" || a == "--dump-all-scores")
-            die("option " + a + " belongs to a part of panmap this build does not implement (index / place / align only)");
+            die("option " + a + " belongs to a part of panmap this build does not implement (index / place / align / genotype / consensus only)");
         else if (a.size() > 1 && a[0] == '-') die("unknown option " + a + " (see --help)");
         else pos.push_back(a);
     }
@@ -523,6 +530,51 @@ std::string run_sample(const Config& c, int stop, pmx_panman*& pm, pmx_index* id
                         results.data(), paired), "writing the BAM");
     say(c, "align", bam + " (" + std::to_string(n_mapped) + " of " + std::to_string(n_items) + (paired ? " pairs" : " reads") + " mapped" +
                     (n_withheld ? ", " + std::to_string(n_withheld) + " invalid records withheld" : "") + ")");
+    if (stop < 3) return node_id;
+
+    // ------------------------------------------------------------------------------------------------ genotype
+    // One rank: the pileup runs over what the align stage left on the device.  --gpus N: rank 0 holds the gathered records
+    // and the whole sample's reads on the host and uploads them.  Same tables either way.
+    std::string names_concat;
+    std::vector<int64_t> name_off((size_t)n_reads + 1, 0);
+    for (int64_t r = 0; r < n_reads; ++r) { names_concat += name_s[(size_t)r]; name_off[(size_t)r + 1] = (int64_t)names_concat.size(); }
+    names_concat.push_back('\0');
+    struct PileupGuard { pmx_ctx* ctx; pmx_pileup* pu = nullptr; pmx_genotyper* gt = nullptr; ~PileupGuard() { if (gt) pmx_genotype_free(gt); if (pu) pmx_pileup_free(ctx, pu); } } pg{ctx};
+    check(pmx_pileup_create(ctx, &pg.pu), "creating the pileup");
+    if (dist) {
+        check(pmx_pileup_run_records(ctx, pg.pu, recs.data(), n_reads, arena.data(), (int64_t)arena.size(), concat.data(), quals.data(), off.data(),
+                                     (int64_t)genome.size(), paired ? 1 : 0, paired ? 1 : 0, names_concat.data(), name_off.data(), nullptr), "pileup");
+    } else {
+        check(pmx_readset_set_qualities(ctx, rs, quals.data()), "attaching the qualities");
+        check(pmx_pileup_run(ctx, pg.pu, al, rs, (int64_t)genome.size(), paired ? 1 : 0, paired ? 1 : 0, names_concat.data(), name_off.data(), nullptr), "pileup");
+    }
+    std::vector<uint32_t> hist(genome.size() * PMX_PILEUP_HIST), aux(genome.size() * PMX_PILEUP_AUX);
+    check(pmx_pileup_fetch(ctx, pg.pu, hist.data(), aux.data()), "fetching the pileup tables");
+    // the substitution spectrum of the tree (the reference keeps it in the index; here it is counted from the PanMAN)
+    static bool have_spectrum = false, spectrum_empty = false;
+    static double phred[16];
+    if (!have_spectrum) {
+        int64_t counts[16], n_branches = 0, genome_len = 0;
+        check(pmx_genotype_spectrum_counts(pm, counts, &n_branches, &genome_len), "counting the substitution spectrum");
+        const int rc = pmx_genotype_spectrum_phred(counts, n_branches, genome_len, phred);
+        if (rc < 0) die("substitution spectrum");
+        spectrum_empty = rc == 1;
+        have_spectrum = true;
+    }
+    const int64_t n_calls = pmx_genotype_call(hist.data(), aux.data(), genome.data(), (int64_t)genome.size(), node_id.c_str(), spectrum_empty ? nullptr : phred,
+                                              c.min_depth, c.min_qual, &pg.gt);
+    if (n_calls < 0) die(std::string("calling variants: ") + pmx_last_error());
+    const std::string vcf = c.output + ".vcf";
+    check(pmx_genotype_write_vcf(pg.gt, vcf.c_str(), node_id.c_str(), (int64_t)genome.size(), bam.c_str()), "writing the VCF");
+    say(c, "call", vcf + " (" + std::to_string(n_calls) + " variants)");
+    if (stop < 4) return node_id;
+
+    // ------------------------------------------------------------------------------------------------ consensus
+    std::string sample = c.output.substr(c.output.find_last_of("/\\") + 1);   // src/main.cpp:1889-1892
+    if (sample.empty()) sample = "sample";
+    const std::string cons = c.output + ".consensus.fa";
+    check(pmx_genotype_write_consensus(vcf.c_str(), (c.output + ".ref.fa").c_str(), cons.c_str(), (sample + "_consensus ref=" + node_id).c_str()), "writing the consensus");
+    say(c, "consensus", cons);
     return node_id;
 }
 
@@ -719,7 +771,7 @@ int real_main(int argc, char** argv) {
     if (c.t < 0 || c.t > c.k - c.s) die("Invalid syncmer offset=" + std::to_string(c.t) + " (must be in 0..k-s = 0.." + std::to_string(c.k - c.s) + ")");
     if (c.hpc) die("--hpc (homopolymer-compressed seeds) is not implemented in this build");
     if (c.aligner != "minimap2") die("aligner '" + c.aligner + "' is not implemented in this build (minimap2 only)");
-    int stop = c.stop == "index" ? 0 : c.stop == "place" ? 1 : c.stop == "align" ? 2 : (c.stop == "genotype" || c.stop == "consensus") ? 3 : -1;
+    int stop = c.stop == "index" ? 0 : c.stop == "place" ? 1 : c.stop == "align" ? 2 : c.stop == "genotype" ? 3 : c.stop == "consensus" ? 4 : -1;
     if (stop < 0) die("--stop expects index|place|align|genotype|consensus");
     if (c.index.empty()) c.index = c.index_out.empty() ? c.panman + ".idx" : c.index_out;
     else if (!exists(c.index)) die("index file not found: " + c.index + " (--index expects a pre-built index; use --index-out to build at a custom path)");
@@ -756,7 +808,6 @@ int real_main(int argc, char** argv) {
         }
         if (rk.rank > 0) c.quiet = true;
     }
-    const int rank = rk.rank;
 
     // ------------------------------------------------------------------------------------------------ samples
     pmx_ctx* ctx = nullptr;
@@ -795,7 +846,6 @@ int real_main(int argc, char** argv) {
         fprintf(stderr, "Batch complete: %d placed, %d failed\n", ok, failed);
         rc = failed ? 1 : 0;
     }
-    if (stop > 2 && rank == 0) fprintf(stderr, "panmap: note: stages after align (genotype, consensus) are not part of this build; stopped after align.\n");
     if (dist) { (void)pmx_dist_barrier(dist); pmx_dist_free(dist); }
     pmx_place_free(ctx, pl);
     pmx_ctx_destroy(ctx);

@@ -248,6 +248,15 @@ void parallel_for(size_t n, size_t grain, F&& body) {   // body(begin, end) over
 
 }  // namespace
 
+// the reference sorts (pos, record) pairs with std::sort on pos only (src/conversion.cpp:499): records of one position
+// stand in whatever order that sort leaves them in, so every consumer of the BAM order goes through this one call
+std::vector<std::pair<int32_t, size_t>> bam_record_order(const std::vector<int32_t>& sort_pos) {
+    std::vector<std::pair<int32_t, size_t>> order(sort_pos.size());
+    for (size_t i = 0; i < sort_pos.size(); ++i) order[i] = {sort_pos[i], i};
+    std::sort(order.begin(), order.end(), [](const std::pair<int32_t, size_t>& a, const std::pair<int32_t, size_t>& b) { return a.first < b.first; });
+    return order;
+}
+
 int write_bam(const std::string& bam_path, const std::string& ref_name, int64_t ref_len, const std::vector<std::string>& seqs,
               const std::vector<std::string>& quals, const std::vector<std::string>& names, const align_pair_result_t* results, int64_t n_results,
               bool paired, bool write_index) {
@@ -277,10 +286,9 @@ int write_bam(const std::string& bam_path, const std::string& ref_name, int64_t 
         if (used[k])
             for (size_t q = 0; q < per; ++q) recs.push_back(std::move(slots[k * per + q]));
     slots.clear();
-    // the reference sorts (pos, record) pairs with std::sort on pos only (src/conversion.cpp:499)
-    std::vector<std::pair<int32_t, size_t>> order(recs.size());
-    for (size_t i = 0; i < recs.size(); ++i) order[i] = {recs[i].sort_pos, i};
-    std::sort(order.begin(), order.end(), [](const std::pair<int32_t, size_t>& a, const std::pair<int32_t, size_t>& b) { return a.first < b.first; });
+    std::vector<int32_t> sort_pos(recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) sort_pos[i] = recs[i].sort_pos;
+    const std::vector<std::pair<int32_t, size_t>> order = bam_record_order(sort_pos);
 
     const std::string text = "@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:" + ref_name + "\tLN:" + std::to_string(ref_len) + "\n";
     std::string hdr("BAM\1", 4);

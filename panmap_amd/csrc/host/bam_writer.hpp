@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "panmap_amd.h"
@@ -15,5 +16,10 @@ namespace pmx {
 int write_bam(const std::string& bam_path, const std::string& ref_name, int64_t ref_len, const std::vector<std::string>& seqs,
               const std::vector<std::string>& quals, const std::vector<std::string>& names, const align_pair_result_t* results, int64_t n_results,
               bool paired, bool write_index);
+
+// The order write_bam puts its records in: `sort_pos` holds read_align_t::pos of every record it writes, in input order
+// (both mates of every mapped pair); returns (pos, input index) in file order.  The genotype stage's depth cap admits reads
+// in this order.
+std::vector<std::pair<int32_t, size_t>> bam_record_order(const std::vector<int32_t>& sort_pos);
 
 }  // namespace pmx

@@ -1,0 +1,542 @@
+// Calls, filter and writers of the genotype / consensus stages (host; C ABI pmx_genotype_*, include/panmap_amd.h).
+//
+// The reference forks `bcftools call --ploidy 1 -m -A` on the output of `bcftools mpileup`, filters the lines with
+// genotyping::applyMutationSpectrum / passesConsensusGate and forks `bcftools consensus`
+// (src/conversion.cpp:130-255, src/genotyping.cpp:167-279).  Restated here as functions of the pileup tables:
+//   * the htslib error model: errmod_cal with cal_coef's tables (src/3rdparty/samtools/htslib-1.20/errmod.c:51-208);
+//   * allele order, PL and DP4 of a site: bcf_call_combine (src/3rdparty/bcftools/bam2bcf.c:955-1115); MQ as mcall.c:1659;
+//   * the substitution spectrum of the tree (src/index_single_mode.cpp:1408-1558) as phred (src/main.cpp:290-311);
+//   * the filter, line by line as the reference applies it.
+// Not restated: INDEL records, BAQ, the rank-test annotations, the QUAL and the allele pruning of
+// `call -m` (a site is a candidate when an alternative base has a non-zero quality sum).
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <sstream>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../api_internal.hpp"
+#include "panman.hpp"
+
+namespace pmx {
+const Panman& panman_of(const pmx_panman* pm);   // api_host.cpp
+}
+
+namespace {
+
+constexpr int NQ = 64, NB = 5, HIST = NQ * 2 * NB;
+
+// ------------------------------------------------------------------------------------------------ error model
+// cal_coef (errmod.c:66-112) with depcorr = 1 - CALL_DEFTHETA = 0.17 and eta = 0.03 (bam2bcf.c:47-54, errmod.c:123):
+//   fk[n]         = 0.83^n * 0.97 + 0.03
+//   beta[q][n][k] : phred of "k-th error among n bases of quality q" from the binomial tail, by the reference's recurrence
+//   lhet[n][k]    = log C(n, k) - n log 2
+// The reference fills 64 x 256 x 256 doubles up front; a site touches a few (q, n) rows, made here when first asked for.
+double log_binom(int n, int k) { return k <= 0 || k > n ? 0.0 : lgamma(n + 1.0) - lgamma(k + 1.0) - lgamma(n - k + 1.0); }
+
+double fk_of(int n) { return n == 0 ? 1.0 : pow(1.0 - 0.17, n) * (1.0 - 0.03) + 0.03; }
+
+const std::vector<double>& beta_row(int q, int n) {
+    static std::mutex mu;
+    static std::map<int, std::vector<double>> rows;
+    std::lock_guard<std::mutex> g(mu);
+    std::vector<double>& row = rows[q << 8 | n];
+    if (!row.empty()) return row;
+    row.assign((size_t)n + 1, 0.0);
+    const double e = pow(10.0, -q / 10.0), le = log(e), le1 = log(1.0 - e);
+    double sum1 = log_binom(n, n) + n * le, sum = 0;
+    row[(size_t)n] = HUGE_VAL;
+    for (int k = n - 1; k >= 0; --k, sum1 = sum) {
+        sum = sum1 + log1p(exp(log_binom(n, k) + k * le + (n - k) * le1 - sum1));
+        row[(size_t)k] = -10.0 / M_LN10 * (sum1 - sum);
+    }
+    return row;
+}
+
+// More than 255 bases: errmod_cal shuffles them with a shared random generator and keeps 255 (errmod.c:156-159), which
+// is no function of the site.  Here each (quality, strand, base) class keeps its share of 255, largest remainders first
+// (ties: the higher class code) -- the expectation of that draw.
+void thin_to_255(std::vector<std::pair<int, int64_t>>& classes, int64_t n) {
+    std::vector<std::pair<int64_t, int>> rem;
+    int64_t kept = 0;
+    for (size_t i = 0; i < classes.size(); ++i) {
+        const int64_t c = classes[i].second, share = c * 255 / n;
+        rem.emplace_back(-(c * 255 % n), -(int)i);
+        classes[i].second = share;
+        kept += share;
+    }
+    std::sort(rem.begin(), rem.end());
+    for (size_t j = 0; kept < 255 && j < rem.size(); ++j, ++kept) ++classes[(size_t)(-rem[j].second)].second;
+}
+
+// errmod_cal (errmod.c:143-208) for m = 5 over the classes of hist[pos]; q[25] as floats, like the reference's
+int64_t error_model(const uint32_t* hist, float q[25]) {
+    for (int i = 0; i < 25; ++i) q[i] = 0.f;
+    // the sort key of bca->bases is quality << 5 | strand << 4 | base (bam2bcf.c:461): ascending class codes
+    std::vector<std::pair<int, int64_t>> classes;
+    int64_t n_all = 0;
+    for (int ql = 0; ql < NQ; ++ql)
+        for (int s = 0; s < 2; ++s)
+            for (int b = 0; b < NB; ++b) {
+                const uint32_t c = hist[(ql * 2 + s) * NB + b];
+                if (c) { classes.emplace_back(ql << 5 | s << 4 | b, (int64_t)c); n_all += c; }
+            }
+    if (n_all == 0) return 0;
+    int n = (int)std::min<int64_t>(n_all, 255);
+    if (n_all > 255) thin_to_255(classes, n_all);
+    double fsum[NB] = {0}, bsum[NB] = {0};
+    int c[NB] = {0}, w[32] = {0};
+    for (size_t ci = classes.size(); ci-- > 0;) {   // from the highest quality down, as the sorted array is read
+        const int code = classes[ci].first, qual = std::min(std::max(code >> 5, 4), 63), bs = code & 0x1f, base = code & 0xf;
+        const std::vector<double>& beta = beta_row(qual, n);
+        for (int64_t t = 0; t < classes[ci].second; ++t) {
+            const double f = fk_of(w[bs]);
+            fsum[base] += f;
+            bsum[base] += f * beta[(size_t)c[base]];
+            ++c[base];
+            ++w[bs];
+        }
+    }
+    for (int j = 0; j < NB; ++j) {
+        float tmp1 = 0.f;
+        int tmp2 = 0;
+        for (int k = 0; k < NB; ++k) {
+            if (k == j) continue;
+            tmp1 = (float)(tmp1 + bsum[k]);
+            tmp2 += c[k];
+        }
+        if (tmp2) q[j * NB + j] = tmp1;
+        for (int k = j + 1; k < NB; ++k) {
+            const int cjk = c[j] + c[k];
+            tmp1 = 0.f;
+            tmp2 = 0;
+            for (int i = 0; i < NB; ++i) {
+                if (i == j || i == k) continue;
+                tmp1 = (float)(tmp1 + bsum[i]);
+                tmp2 += c[i];
+            }
+            const double lhet = log_binom(cjk, c[k]) - M_LN2 * cjk;
+            q[j * NB + k] = q[k * NB + j] = tmp2 ? (float)(-4.343 * lhet + tmp1) : (float)(-4.343 * lhet);
+        }
+        for (int k = 0; k < NB; ++k)
+            if (q[j * NB + k] < 0.0f) q[j * NB + k] = 0.0f;
+    }
+    return n_all;
+}
+
+int base_index(char c) {   // seq_nt16_int of the letter: A C G T -> 0..3, everything else 4
+    switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return 4; }
+}
+
+// bcf_call_combine for one sample (bam2bcf.c:955-1115)
+void site_call(const uint32_t* hist, char ref_base, pmx_site_call* out) {
+    memset(out, 0, sizeof(*out));
+    float p[25];
+    out->n_bases = (int32_t)std::min<int64_t>(error_model(hist, p), INT32_MAX);
+    const int ref4 = base_index(ref_base);
+    // QS: sum of the capped qualities per base (bam2bcf.c:465-467); AD: bases per allele; DP4 from anno[0..3] (:476)
+    int64_t qs[4] = {0, 0, 0, 0}, ad[NB] = {0}, dp4[4] = {0, 0, 0, 0};
+    for (int ql = 0; ql < NQ; ++ql)
+        for (int s = 0; s < 2; ++s)
+            for (int b = 0; b < NB; ++b) {
+                const int64_t c = hist[(ql * 2 + s) * NB + b];
+                if (!c) continue;
+                if (b < 4) qs[b] += c * ql;
+                ad[b] += c;
+                dp4[((ref4 < 4 && b == ref4) ? 0 : 2) + s] += c;
+            }
+    for (int i = 0; i < 4; ++i) out->dp4[i] = (int32_t)dp4[i];
+    float qsum[5] = {0, 0, 0, 0, 0}, sum = 0;
+    for (int j = 0; j < 4; ++j) sum += (float)qs[j];
+    if (sum != 0)
+        for (int j = 0; j < 4; ++j) qsum[j] += (float)qs[j] / sum;
+    int ord[4] = {0, 1, 2, 3};   // ascending by qsum (insertion sort, strict <: equal sums keep their order)
+    for (int i = 1; i < 4; ++i)
+        for (int j = i; j > 0 && qsum[ord[j]] < qsum[ord[j - 1]]; --j) std::swap(ord[j], ord[j - 1]);
+    int a[5] = {-1, -1, -1, -1, -1}, n_al = 1, i = 3, unseen = -1;
+    a[0] = ref4;
+    for (; i >= 0; --i) {
+        if (ord[i] == ref4) continue;
+        if (qsum[ord[i]] == 0) break;
+        a[n_al++] = ord[i];
+    }
+    const int n_seen = n_al;
+    if (((ref4 < 4 && n_al < 4) || (ref4 == 4 && n_al < 5)) && i >= 0) { unseen = n_al; a[n_al++] = ord[i]; }
+    (void)unseen;
+    // PL: the genotypes of a[] in VCF order, minimum subtracted, + .499 truncated, at most 255 (bam2bcf.c:1020-1046)
+    float mn = 3.4e38f;
+    for (int x = 0; x < n_al; ++x)
+        for (int y = 0; y <= x; ++y) mn = std::min(mn, p[a[y] * NB + a[x]]);
+    out->n_alleles = n_seen;
+    for (int k = 0; k < n_seen; ++k) {
+        int y = (int)(p[a[k] * NB + a[k]] - mn + .499);
+        out->pl[k] = y > 255 ? 255 : y;
+        out->alleles[k] = a[k];
+        out->ad[k] = (int32_t)ad[a[k]];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ filter
+std::vector<std::string> split(const std::string& s, char sep) {   // std::getline semantics: no trailing empty field
+    std::vector<std::string> out;
+    std::istringstream ss(s);
+    std::string f;
+    while (std::getline(ss, f, sep)) out.push_back(f);
+    return out;
+}
+
+int nuc_index(char c) {   // getIndexFromNucleotide (src/genotyping.cpp:112-125)
+    switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '*': return 4; default: return 5; }
+}
+
+// passesConsensusGate (src/genotyping.cpp:167-174)
+bool passes_gate(int called, const std::vector<int>& ad, int min_depth) {
+    if (called <= 0) return false;
+    if (ad.empty() || called >= (int)ad.size()) return true;
+    long total = 0;
+    for (int x : ad) total += x;
+    if (total < min_depth) return false;
+    return (long)ad[(size_t)called] * 2 > total;
+}
+
+// the sample-field form (src/genotyping.cpp:176-198)
+bool passes_gate(const std::string& sample, int min_depth) {
+    const std::vector<std::string> parts = split(sample, ':');
+    if (parts.size() < 3) return true;
+    int gt = 0;
+    try { gt = std::stoi(parts[0]); } catch (...) { return true; }
+    std::vector<int> ad;
+    for (const std::string& x : split(parts[2], ','))
+        try { ad.push_back(std::stoi(x)); } catch (...) {}
+    return passes_gate(gt, ad, min_depth);
+}
+
+std::string fixed4(double v) {
+    char buf[64];
+    snprintf(buf, sizeof(buf), "%.4f", v);
+    return buf;
+}
+
+// applyMutationSpectrum (src/genotyping.cpp:200-279); *called receives the allele index of a kept call
+std::string apply_spectrum(const std::string& line, const double* sm, int min_depth, double min_qual, int* called) {
+    const std::vector<std::string> f = split(line, '\t');
+    if (f.size() < 10 || f[0] == "#CHROM") return line;
+    if (f.size() != 10) throw std::runtime_error("Couldn't parse VCF. Unrecognized number of fields.");
+    if (f[4] == ".") return "";
+    if (f[7].substr(0, 2) != "DP" || f[3].empty() || nuc_index(f[3][0]) > 3) return (!f[9].empty() && f[9][0] == '0') ? "" : line;
+    if (f[3].size() > 1) throw std::runtime_error("Error: reference allele parsing error.");
+    const int ref = nuc_index(f[3][0]);
+    std::vector<char> alts;
+    for (const std::string& x : split(f[4], ',')) alts.push_back(x.empty() ? '.' : x[0]);
+    const std::vector<std::string> sf = split(f[9], ':');
+    if (sf.size() != 3) throw std::runtime_error("Couldn't parse VCF. Unrecognized sample format.");
+    std::vector<double> pls;
+    for (const std::string& x : split(sf[1], ',')) pls.push_back(std::stod(x));
+    std::vector<int> ads;
+    for (const std::string& x : split(sf[2], ',')) ads.push_back(std::stoi(x));
+    std::vector<double> gls;
+    if (alts.size() + 1 == pls.size()) gls = pls;
+    else
+        for (size_t i = 0; i < pls.size(); i += 2) {
+            gls.push_back(pls[i]);
+            if (gls.size() == alts.size() + 1) break;
+        }
+    if (gls.empty()) throw std::runtime_error("Couldn't parse VCF. No likelihoods.");
+    gls[0] += sm[ref * 4 + ref];
+    for (size_t i = 1; i < gls.size(); ++i) {
+        const int alt = nuc_index(alts[i - 1]);
+        if (alt <= 3) gls[i] += sm[ref * 4 + alt];   // a '*' ALT keeps its likelihood
+    }
+    const double mn = *std::min_element(gls.begin(), gls.end());
+    int best = 0;
+    for (size_t i = 0; i < gls.size(); ++i) {
+        gls[i] -= mn;
+        if (gls[i] == 0) best = (int)i;
+    }
+    if (best == 0) return "";
+    if (!passes_gate(best, ads, min_depth)) return "";
+    const double qual = gls[0];
+    if (qual < min_qual) return "";
+    if (called) *called = best;
+    return f[0] + "\t" + f[1] + "\t" + f[2] + "\t" + f[3] + "\t" + f[4] + "\t" + fixed4(qual) + "\t" + f[6] + "\t" + f[7] + "\t" + f[8] + "\t" +
+           std::to_string(best) + ":" + sf[1] + ":" + sf[2];
+}
+
+// the branch of createVcfWithMutationMatrices without a spectrum (src/conversion.cpp:163-178)
+std::string plain_filter(const std::string& line, int min_depth, double min_qual) {
+    if (line.empty()) return "";
+    if (line[0] == '#') return line;
+    const std::vector<std::string> f = split(line, '\t');
+    const bool qual_ok = f.size() >= 6 && (f[5] == "." || std::stod(f[5]) >= min_qual);
+    if (f.size() >= 10 && f[4] != "." && !f[9].empty() && f[9][0] != '0' && qual_ok && passes_gate(f[9], min_depth)) return line;
+    return "";
+}
+
+std::string join_ints(const int32_t* v, int n) {
+    std::string s;
+    for (int i = 0; i < n; ++i) { if (i) s += ","; s += std::to_string(v[i]); }
+    return s;
+}
+
+}  // namespace
+
+struct pmx_genotyper {
+    std::vector<std::string> records;
+};
+
+extern "C" {
+
+int pmx_genotype_spectrum_counts(const pmx_panman* pmh, int64_t counts[16], int64_t* n_branches, int64_t* genome_len) {
+    if (!pmh || !counts) return PMX_ERR_ARG;
+    try {
+        const pmx::Panman& pm = pmx::panman_of(pmh);
+        for (int i = 0; i < 16; ++i) counts[i] = 0;
+        int64_t branches = 0;
+        // the DFS of computeSubstitutionSpectrum (src/index_single_mode.cpp:1418-1477): block mutations switch blocks on and
+        // off at every node; nucleotide mutations are applied (and counted) at every node but the root, so a child of the
+        // root compares against the block consensus; a substitution counts when its block exists and both letters are A C G T
+        std::string cols = pm.consensus_cols;
+        std::vector<uint8_t> exists((size_t)pm.n_blocks, 0);
+        struct Frame { int32_t node; size_t child; std::vector<std::pair<uint32_t, char>> col_undo; std::vector<std::pair<int32_t, uint8_t>> blk_undo; };
+        std::vector<Frame> stack;
+        auto enter = [&](int32_t ni) {
+            stack.emplace_back();
+            Frame& fr = stack.back();
+            fr.node = ni;
+            fr.child = 0;
+            const pmx::PanmanNode& nd = pm.nodes[(size_t)ni];
+            for (const pmx::BlockMut& bm : nd.block_muts) {
+                if (bm.block < 0 || bm.block >= pm.n_blocks) continue;
+                fr.blk_undo.emplace_back(bm.block, exists[(size_t)bm.block]);
+                if (bm.insertion) exists[(size_t)bm.block] = 1;
+                else if (!bm.inversion) exists[(size_t)bm.block] = 0;
+            }
+            if (ni == 0) return;
+            ++branches;
+            for (const pmx::NucMut& nm : nd.nuc_muts) {
+                const int type = nm.type & 0x7;
+                const bool is_sub = type == 0 || type == 3;   // NS, NSNPS
+                if (nm.block < 0 || nm.block >= pm.n_blocks) continue;
+                for (int i = 0; i < nm.len; ++i) {
+                    const int32_t pos = nm.gap < 0 ? nm.pos + i : nm.pos, gap = nm.gap < 0 ? -1 : nm.gap + i;
+                    if (pos < 0 || pos >= pm.block_len[(size_t)nm.block]) continue;
+                    const int64_t c = pm.column(nm.block, pos, gap);
+                    if (c < 0) continue;
+                    const char old = cols[(size_t)c], nw = pmx::nuc_from_code((int)((nm.nucs >> (4 * (5 - i))) & 0xf));
+                    fr.col_undo.emplace_back((uint32_t)c, old);
+                    cols[(size_t)c] = nw;
+                    if (is_sub && exists[(size_t)nm.block]) {
+                        const int oi = base_index(old), ni2 = base_index(nw);
+                        if (oi < 4 && ni2 < 4 && oi != ni2) ++counts[oi * 4 + ni2];
+                    }
+                }
+            }
+        };
+        if (!pm.nodes.empty()) enter(0);
+        while (!stack.empty()) {
+            Frame& fr = stack.back();
+            const pmx::PanmanNode& nd = pm.nodes[(size_t)fr.node];
+            if (fr.child < nd.children.size()) { const int32_t ch = nd.children[fr.child++]; enter(ch); continue; }
+            for (size_t i = fr.col_undo.size(); i-- > 0;) cols[fr.col_undo[i].first] = fr.col_undo[i].second;
+            for (size_t i = fr.blk_undo.size(); i-- > 0;) exists[(size_t)fr.blk_undo[i].first] = fr.blk_undo[i].second;
+            stack.pop_back();
+        }
+        if (n_branches) *n_branches = branches;
+        if (genome_len) {
+            // the median of ten leaf genomes (:1479-1502).  The reference takes its leaves from a hash map's iteration
+            // order; here: the leaves in DFS order, every (leaves / 10)-th
+            std::vector<int32_t> leaves;
+            for (size_t i = 0; i < pm.nodes.size(); ++i)
+                if (pm.nodes[i].children.empty()) leaves.push_back((int32_t)i);
+            std::vector<int64_t> lengths;
+            const size_t want = std::min<size_t>(10, leaves.size()), step = std::max<size_t>(1, want ? leaves.size() / want : 1);
+            const pmx::PanmanState root = pmx::root_state_of(pm);
+            for (size_t i = 0; i < leaves.size() && lengths.size() < want; i += step) lengths.push_back((int64_t)pmx::node_genome(pm, leaves[i], &root).size());
+            std::sort(lengths.begin(), lengths.end());
+            *genome_len = lengths.empty() ? 0 : lengths[lengths.size() / 2];
+        }
+        return PMX_OK;
+    } catch (const std::exception& e) {
+        pmx::set_error(e.what());
+        return PMX_ERR_FORMAT;
+    }
+}
+
+int pmx_genotype_spectrum_phred(const int64_t counts[16], int64_t n_branches, int64_t genome_len, double phred[16]) {
+    if (!counts || !phred) return PMX_ERR_ARG;
+    double rate[16];
+    if (n_branches > 0 && genome_len > 0) {   // src/index_single_mode.cpp:1506-1538: every base is a quarter of the genome
+        const int64_t base_count = genome_len / 4;
+        for (int from = 0; from < 4; ++from)
+            for (int to = 0; to < 4; ++to) {
+                if (from == to) {
+                    double off = 0;
+                    for (int j = 0; j < 4; ++j)
+                        if (j != from && base_count > 0) off += (double)counts[from * 4 + j] / (double)(n_branches * base_count);
+                    rate[from * 4 + to] = 1.0 - off;
+                } else rate[from * 4 + to] = base_count > 0 ? (double)counts[from * 4 + to] / (double)(n_branches * base_count) : 0.0;
+            }
+    } else
+        for (int i = 0; i < 16; ++i) rate[i] = (i / 4 == i % 4) ? 1.0 : 0.0;
+    bool any = false;   // loadSubstMatrixFromIndex (src/main.cpp:290-311)
+    for (int i = 0; i < 16; ++i)
+        if (i / 4 != i % 4 && rate[i] > 0) any = true;
+    for (int i = 0; i < 16; ++i) phred[i] = rate[i] > 0 ? -10.0 * log10(rate[i]) : 100.0;
+    return any ? 0 : 1;
+}
+
+int pmx_genotype_site(const uint32_t* hist, char ref_base, pmx_site_call* out) {
+    if (!hist || !out) return PMX_ERR_ARG;
+    try {
+        site_call(hist, ref_base, out);
+        return PMX_OK;
+    } catch (const std::exception& e) {
+        pmx::set_error(e.what());
+        return PMX_ERR_ARG;
+    }
+}
+
+int64_t pmx_genotype_filter_line(const char* line, const double* phred16, int min_depth, double min_qual, char* out, int64_t cap) {
+    if (!line) return PMX_ERR_ARG;
+    try {
+        const std::string r = phred16 ? apply_spectrum(line, phred16, min_depth, min_qual, nullptr) : plain_filter(line, min_depth, min_qual);
+        if (out && cap > 0) {
+            const size_t n = std::min<size_t>(r.size(), (size_t)cap - 1);
+            memcpy(out, r.data(), n);
+            out[n] = '\0';
+        }
+        return (int64_t)r.size();
+    } catch (const std::exception& e) {
+        pmx::set_error(e.what());
+        return PMX_ERR_FORMAT;
+    }
+}
+
+int64_t pmx_genotype_call(const uint32_t* hist, const uint32_t* aux, const char* reference, int64_t ref_len, const char* chrom, const double* phred16,
+                          int min_depth, double min_qual, pmx_genotyper** out) {
+    if (!hist || !aux || !reference || !chrom || !out || ref_len < 0) return PMX_ERR_ARG;
+    try {
+        std::unique_ptr<pmx_genotyper> g(new pmx_genotyper());
+        for (int64_t pos = 0; pos < ref_len; ++pos) {
+            const uint32_t* h = hist + pos * HIST;
+            // candidate: an alternative base with a non-zero quality sum (every counted base has quality >= 4)
+            const int ref4 = base_index(reference[pos]);
+            bool cand = false;
+            for (int c = 0; c < HIST && !cand; ++c)
+                if (h[c] && c % NB < 4 && c % NB != ref4) cand = true;
+            if (!cand) continue;
+            pmx_site_call sc;
+            site_call(h, reference[pos], &sc);
+            if (sc.n_alleles < 2) continue;
+            const uint32_t* ax = aux + pos * 4;
+            const int64_t depth = (int64_t)sc.dp4[0] + sc.dp4[1] + sc.dp4[2] + sc.dp4[3];
+            const int mq = depth > 0 ? (int)((float)ax[1] / (float)depth) : 0;   // mcall.c:1659
+            std::string alt;
+            for (int k = 1; k < sc.n_alleles; ++k) { if (k > 1) alt += ","; alt += "ACGTN"[sc.alleles[k]]; }
+            int raw_gt = 0;   // the most likely haploid genotype of the raw line (lowest index on ties)
+            for (int k = 1; k < sc.n_alleles; ++k)
+                if (sc.pl[k] < sc.pl[raw_gt]) raw_gt = k;
+            const std::string ref_s(1, (char)toupper((unsigned char)reference[pos]));
+            const std::string info = "DP=" + std::to_string(ax[0]) + ";AC=1;AN=1;DP4=" + join_ints(sc.dp4, 4) + ";MQ=" + std::to_string(mq);
+            const std::string head = std::string(chrom) + "\t" + std::to_string(pos + 1) + "\t.\t" + ref_s + "\t";
+            const std::string raw = head + alt + "\t.\t.\t" + info + "\tGT:PL:AD\t" + std::to_string(raw_gt) + ":" + join_ints(sc.pl, sc.n_alleles) + ":" +
+                                    join_ints(sc.ad, sc.n_alleles);
+            int called = raw_gt;
+            const std::string kept = phred16 ? apply_spectrum(raw, phred16, min_depth, min_qual, &called) : plain_filter(raw, min_depth, min_qual);
+            if (kept.empty()) continue;
+            if (called <= 0 || called >= sc.n_alleles) { g->records.push_back(kept); continue; }   // (a line the filter passed through untouched)
+            // the written record: REF and the called allele alone
+            const std::vector<std::string> f = split(kept, '\t');
+            const int32_t pl2[2] = {sc.pl[0], sc.pl[called]}, ad2[2] = {sc.ad[0], sc.ad[called]};
+            g->records.push_back(head + std::string(1, "ACGTN"[sc.alleles[called]]) + "\t" + f[5] + "\t.\t" + info + "\tGT:PL:AD\t1:" + join_ints(pl2, 2) + ":" +
+                                 join_ints(ad2, 2));
+        }
+        const int64_t n = (int64_t)g->records.size();
+        *out = g.release();
+        return n;
+    } catch (const std::exception& e) {
+        pmx::set_error(e.what());
+        return PMX_ERR_FORMAT;
+    }
+}
+
+int64_t pmx_genotype_num_records(const pmx_genotyper* g) { return g ? (int64_t)g->records.size() : 0; }
+const char* pmx_genotype_record(const pmx_genotyper* g, int64_t i) {
+    return g && i >= 0 && i < (int64_t)g->records.size() ? g->records[(size_t)i].c_str() : nullptr;
+}
+void pmx_genotype_free(pmx_genotyper* g) { delete g; }
+
+int pmx_genotype_write_vcf(const pmx_genotyper* g, const char* path, const char* chrom, int64_t ref_len, const char* sample_name) {
+    if (!g || !path || !chrom || !sample_name) return PMX_ERR_ARG;
+    FILE* f = fopen(path, "w");
+    if (!f) { pmx::set_error(std::string("cannot write ") + path); return PMX_ERR_IO; }
+    fprintf(f, "##fileformat=VCFv4.2\n##contig=<ID=%s,length=%lld>\n", chrom, (long long)ref_len);
+    fputs("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Raw read depth\">\n"
+          "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Allele count in genotypes for each ALT allele, in the same order as listed\">\n"
+          "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"Total number of alleles in called genotypes\">\n"
+          "##INFO=<ID=DP4,Number=4,Type=Integer,Description=\"Number of high-quality ref-forward , ref-reverse, alt-forward and alt-reverse bases\">\n"
+          "##INFO=<ID=MQ,Number=1,Type=Integer,Description=\"Average mapping quality\">\n"
+          "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+          "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"List of Phred-scaled genotype likelihoods\">\n"
+          "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Allelic depths (high-quality bases)\">\n", f);
+    fprintf(f, "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n", sample_name);
+    for (const std::string& r : g->records) fprintf(f, "%s\n", r.c_str());
+    const bool ok = !ferror(f);
+    if (fclose(f) != 0 || !ok) { pmx::set_error(std::string("write failed: ") + path); return PMX_ERR_IO; }
+    return PMX_OK;
+}
+
+int pmx_genotype_write_consensus(const char* vcf_path, const char* ref_fa_path, const char* out_path, const char* header) {
+    if (!vcf_path || !ref_fa_path || !out_path || !header) return PMX_ERR_ARG;
+    try {
+        std::ifstream fa(ref_fa_path);
+        if (!fa) { pmx::set_error(std::string("cannot read ") + ref_fa_path); return PMX_ERR_IO; }
+        std::string line, name, seq;
+        bool first = false;
+        while (std::getline(fa, line)) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (!line.empty() && line[0] == '>') {
+                if (first) break;   // the first sequence
+                first = true;
+                name = line.substr(1, line.find_first_of(" \t", 1) - 1);
+            } else if (first) seq += line;
+        }
+        std::ifstream vcf(vcf_path);
+        if (!vcf) { pmx::set_error(std::string("cannot read ") + vcf_path); return PMX_ERR_IO; }
+        while (std::getline(vcf, line)) {
+            if (line.empty() || line[0] == '#') continue;
+            const std::vector<std::string> f = split(line, '\t');
+            if (f.size() < 5 || f[0] != name || f[4] == ".") continue;
+            const long long pos = std::stoll(f[1]);
+            const std::string alt = f[4].substr(0, f[4].find(','));
+            if (f[3].size() != 1 || alt.size() != 1 || alt == "*") throw std::runtime_error("consensus: only substitution records are applied (" + f[0] + ":" + f[1] + ")");
+            if (pos < 1 || pos > (long long)seq.size()) throw std::runtime_error("consensus: position outside the reference (" + f[0] + ":" + f[1] + ")");
+            if (toupper((unsigned char)seq[(size_t)pos - 1]) != toupper((unsigned char)f[3][0]))
+                throw std::runtime_error("consensus: REF of " + f[0] + ":" + f[1] + " is not the reference base");
+            seq[(size_t)pos - 1] = alt[0];
+        }
+        FILE* o = fopen(out_path, "w");
+        if (!o) { pmx::set_error(std::string("cannot write ") + out_path); return PMX_ERR_IO; }
+        fprintf(o, ">%s\n", header);
+        for (size_t i = 0; i < seq.size(); i += 60) {
+            fwrite(seq.data() + i, 1, std::min<size_t>(60, seq.size() - i), o);
+            fputc('\n', o);
+        }
+        const bool ok = !ferror(o);
+        if (fclose(o) != 0 || !ok) { pmx::set_error(std::string("write failed: ") + out_path); return PMX_ERR_IO; }
+        return PMX_OK;
+    } catch (const std::exception& e) {
+        pmx::set_error(e.what());
+        return PMX_ERR_FORMAT;
+    }
+}
+
+}  // extern "C"
