@@ -1,4 +1,4 @@
-// Launch interface of the grouped DP service (align_kernel_dpg.hip), shared with api_align.hip.
+// Launch interface of the grouped DP service (align_kernel_dpg.hip), shared with align_stage.hip and api_align.hip.
 #pragma once
 #include <stdint.h>
 

@@ -37,7 +37,6 @@
     X(ALIGN_NO_COMPACT, "ab", "align: skip the compact tier (every pair through the general tiers)")                                           \
     X(ALIGN_COMPACT_FUSED, "ab", "align: compact tier as one kernel (sketch + probes inside k_align_compact)")                                 \
     X(ALIGN_COMPACT_POS32, "test", "align: compact tier with 32-bit position words whatever the reference length")                             \
-    X(ALIGN_EARLY_TAIL, "ab", "align: the pairs the compact tier's seeds kernel gave up on run on a second stream beside the chain kernels")   \
     X(ALIGN_NO_DEDUP, "ab", "align: every pair through the compact tier and the tail, no distinct-pair map (copies are not fanned out)")       \
     X(ALIGN_DEDUP_DEPTH, "tune", "align: distinct-pair map from this many pairs per reference base (default 64; 0 = always)")                  \
     X(ALIGN_NO_MULTI, "ab", "align: compact tier without its second form (several regions per mate): every bail to the thread-per-pair tier")  \

@@ -58,7 +58,7 @@ struct pmx_readset {
     mutable pmx::DevBuf<uint32_t> loc_key, loc_key2, loc_idx, loc_perm;
     mutable pmx::DevBuf<char> loc_tmp;
     mutable bool has_order = false;
-    // pair order of the align stage (pairs by both mates' locality keys: api_align.hip), made ahead of time on a side stream
+    // pair order of the align stage (pairs by both mates' locality keys: align_pairs.hip), made ahead of time on a side stream
     // by pmx_readset_order_pairs -- it depends on the reads alone, so it can run beside the place stage's scoring instead of
     // between the placement and the first align kernel -- or by the aligner itself when nobody asked
     mutable pmx::DevBuf<uint64_t> pp_key, pp_key2;
@@ -67,7 +67,7 @@ struct pmx_readset {
     mutable bool has_pair_order = false;
     mutable hipEvent_t pair_ev = nullptr;     // recorded behind the sort when it ran on a side stream
     mutable bool pair_ev_pending = false;
-    // distinct-pair map of the align stage (api_align.hip readset_pair_map), made with the pair order: pairs whose two read
+    // distinct-pair map of the align stage (align_pairs.hip readset_pair_map), made with the pair order: pairs whose two read
     // records are equal byte for byte share a representative (the first of them in input order), which alone is aligned
     mutable pmx::DevBuf<uint32_t> pd_key, pd_key2, pd_idx, pd_idx2, pd_gs, pd_rep, pd_mult;
     mutable pmx::DevBuf<char> pd_tmp;
@@ -87,6 +87,6 @@ namespace pmx {
 const uint32_t* readset_locality_order(pmx_ctx* ctx, const pmx_readset* rs);
 // the same for the reads [r0, r1) alone: their slice of the permutation (absolute read indices), sorted by locality key
 const uint32_t* readset_locality_order_range(pmx_ctx* ctx, const pmx_readset* rs, int64_t r0, int64_t r1);
-const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t side);   // api_align.hip
-void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st);                  // api_align.hip
+const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t side);   // align_pairs.hip
+void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st);                  // align_pairs.hip
 }

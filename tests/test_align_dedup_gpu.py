@@ -1,4 +1,4 @@
-"""GPU parity of the align stage's distinct-pair map (api_align.hip readset_pair_map / k_pair_fanout): the compact tier and
+"""GPU parity of the align stage's distinct-pair map (align_pairs.hip readset_pair_map / k_pair_fanout): the compact tier and
 the tail run one representative of every set of pairs with equal read records, and the copies take its results.  Every
 case here is aligned with the map and without it (PMX_ALIGN_NO_DEDUP) and must come out equal by content: each record's
 fields but its arena offset, and its CIGAR operations.  With the map, no two records may share arena words."""

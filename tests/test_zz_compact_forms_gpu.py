@@ -30,8 +30,6 @@ FORMS = {
     "pos32": {"PMX_ALIGN_COMPACT_POS32": "1"},
     "pos32_fused": {"PMX_ALIGN_COMPACT_POS32": "1", "PMX_ALIGN_COMPACT_FUSED": "1"},
     "resident_grids": {"PMX_ALIGN_COMPACT_WAVES": "7", "PMX_ALIGN_CSEED_WAVES": "16"},
-    # the general tiers of the pairs the seeds kernel gave up on, on the context's second stream beside the chain kernels
-    "early_tail": {"PMX_ALIGN_EARLY_TAIL": "1"},
 }
 
 
