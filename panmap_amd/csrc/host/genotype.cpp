@@ -7,8 +7,9 @@
 //   * allele order, PL and DP4 of a site: bcf_call_combine (src/3rdparty/bcftools/bam2bcf.c:955-1115); MQ as mcall.c:1659;
 //   * the substitution spectrum of the tree (src/index_single_mode.cpp:1408-1558) as phred (src/main.cpp:290-311);
 //   * the filter, line by line as the reference applies it.
-// Not restated: INDEL records, BAQ, the rank-test annotations, the QUAL and the allele pruning of
-// `call -m` (a site is a candidate when an alternative base has a non-zero quality sum).
+// Not restated: INDEL records, BAQ, the rank-test annotations and the QUAL of `call -m`.  A site is a
+// candidate when an alternative base has a non-zero quality sum, and its record lists every such base, as `call -m -A`
+// does (pinned to the reference's programs by tests/test_pileup_reference.py).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -445,19 +446,21 @@ int64_t pmx_genotype_call(const uint32_t* hist, const uint32_t* aux, const char*
             for (int k = 1; k < sc.n_alleles; ++k)
                 if (sc.pl[k] < sc.pl[raw_gt]) raw_gt = k;
             const std::string ref_s(1, (char)toupper((unsigned char)reference[pos]));
-            const std::string info = "DP=" + std::to_string(ax[0]) + ";AC=1;AN=1;DP4=" + join_ints(sc.dp4, 4) + ";MQ=" + std::to_string(mq);
+            // AC: one count per alternative, 1 at the raw line's genotype (the haploid genotype of `call --ploidy 1`)
+            auto info_of = [&](int gt) {
+                std::string ac;
+                for (int k = 1; k < sc.n_alleles; ++k) { if (k > 1) ac += ","; ac += k == gt ? "1" : "0"; }
+                return "DP=" + std::to_string(ax[0]) + ";AC=" + ac + ";AN=1;DP4=" + join_ints(sc.dp4, 4) + ";MQ=" + std::to_string(mq);
+            };
             const std::string head = std::string(chrom) + "\t" + std::to_string(pos + 1) + "\t.\t" + ref_s + "\t";
-            const std::string raw = head + alt + "\t.\t.\t" + info + "\tGT:PL:AD\t" + std::to_string(raw_gt) + ":" + join_ints(sc.pl, sc.n_alleles) + ":" +
-                                    join_ints(sc.ad, sc.n_alleles);
+            const std::string raw = head + alt + "\t.\t.\t" + info_of(raw_gt) + "\tGT:PL:AD\t" + std::to_string(raw_gt) + ":" + join_ints(sc.pl, sc.n_alleles) +
+                                    ":" + join_ints(sc.ad, sc.n_alleles);
             int called = raw_gt;
             const std::string kept = phred16 ? apply_spectrum(raw, phred16, min_depth, min_qual, &called) : plain_filter(raw, min_depth, min_qual);
             if (kept.empty()) continue;
-            if (called <= 0 || called >= sc.n_alleles) { g->records.push_back(kept); continue; }   // (a line the filter passed through untouched)
-            // the written record: REF and the called allele alone
-            const std::vector<std::string> f = split(kept, '\t');
-            const int32_t pl2[2] = {sc.pl[0], sc.pl[called]}, ad2[2] = {sc.ad[0], sc.ad[called]};
-            g->records.push_back(head + std::string(1, "ACGTN"[sc.alleles[called]]) + "\t" + f[5] + "\t.\t" + info + "\tGT:PL:AD\t1:" + join_ints(pl2, 2) + ":" +
-                                 join_ints(ad2, 2));
+            // the written record is the line the reference's filter leaves: every alternative `call -m -A` keeps, one PL and
+            // one AD per allele, GT the filter's allele, INFO passed through as it stood (src/genotyping.cpp:274-277)
+            g->records.push_back(kept);
         }
         const int64_t n = (int64_t)g->records.size();
         *out = g.release();
@@ -516,7 +519,19 @@ int pmx_genotype_write_consensus(const char* vcf_path, const char* ref_fa_path, 
             const std::vector<std::string> f = split(line, '\t');
             if (f.size() < 5 || f[0] != name || f[4] == ".") continue;
             const long long pos = std::stoll(f[1]);
-            const std::string alt = f[4].substr(0, f[4].find(','));
+            // `bcftools consensus -f ref -o out vcf` on a file with a sample column applies the allele the sample's GT names
+            // (consensus.c:231-259: every sample is taken, iupac_GTs; :606-622: ialt = iupac_set_allele); a record whose
+            // GT names the reference changes nothing, and a file without a sample column gets its first alternative
+            size_t which = 1;
+            if (f.size() >= 10) {
+                const std::string gt = f[9].substr(0, f[9].find(':'));
+                if (gt.empty() || gt.find_first_not_of("0123456789") != std::string::npos) continue;   // a missing genotype sets nothing
+                which = (size_t)std::stoul(gt);
+                if (which == 0) continue;
+            }
+            const std::vector<std::string> alts = split(f[4], ',');
+            if (which > alts.size()) throw std::runtime_error("consensus: too few alternatives (" + f[0] + ":" + f[1] + ")");
+            const std::string alt = alts[which - 1];
             if (f[3].size() != 1 || alt.size() != 1 || alt == "*") throw std::runtime_error("consensus: only substitution records are applied (" + f[0] + ":" + f[1] + ")");
             if (pos < 1 || pos > (long long)seq.size()) throw std::runtime_error("consensus: position outside the reference (" + f[0] + ":" + f[1] + ")");
             if (toupper((unsigned char)seq[(size_t)pos - 1]) != toupper((unsigned char)f[3][0]))

@@ -32,7 +32,9 @@ struct ReadView {
     uint32_t c5, c3;
     int len;
     int64_t off;
-    int flipseq;        // BAM query index i is base len-1-i of the uploaded read, complemented
+    int m2rc;           // a mate 2 the pipeline reverse-complements before it aligns (seeding::reverseComplement)
+    int rev;            // placed on the other strand of what was aligned
+    int flipseq;        // m2rc ^ rev: BAM query index i is base len-1-i of the uploaded read
     int rs;
     __device__ uint32_t op(int k) const {
         if (c5) { if (k == 0) return c5 << 4 | CIG_S; --k; }
@@ -51,16 +53,31 @@ __device__ ReadView view_of(const PileupArgs& a, int64_t r) {
     v.c5 = c5 > 0 ? (uint32_t)c5 : 0;
     v.c3 = c3 > 0 ? (uint32_t)c3 : 0;
     v.n_ops = rec.n_cigar + (v.c5 ? 1 : 0) + (v.c3 ? 1 : 0);
-    v.flipseq = ((a.revcomp_mate2 && (r & 1)) ? 1 : 0) ^ (rec.rev ? 1 : 0);
+    v.m2rc = (a.revcomp_mate2 && (r & 1)) ? 1 : 0;
+    v.rev = rec.rev ? 1 : 0;
+    v.flipseq = v.m2rc ^ v.rev;
     v.rs = rec.rs;
     return v;
 }
 
-// htslib's 4-bit code of BAM query base i (1 2 4 8 = A C G T; every other letter counts as N = 15)
+// htslib's seq_nt16_table: "=ACMGRSVTWYHKDBN", either case, every other byte N = 15 (the letters' codes as nibbles A..P, Q..Z)
+__device__ int nt16_of(uint8_t c) {
+    const uint32_t l = (uint32_t)(c | 0x20) - 'a';   // 0..25 for a letter of either case
+    if (l >= 26u) return c == '=' ? 0 : 15;
+    const uint64_t tab = l < 16u ? 0xFFF3FCFFB4FFD2E1ull : 0xFAF97F865Full;
+    return (int)((tab >> (4u * (l & 15u))) & 0xfu);
+}
+
+// The 4-bit code the BAM record holds for query base i.  seeding::reverseComplement (src/seeding.cpp:271-284) complements
+// the upper-case A C G T of a mate 2 and leaves every other byte; build_bam_from_result (src/conversion.cpp:288-388) keeps
+// the letters of a read placed as aligned -- ambiguity codes included, R is not N -- and, for a read placed on the other
+// strand, complements A C G T of either case and writes N for everything else.  tweak_overlap_quality compares these codes.
 __device__ int base16(const PileupArgs& a, const ReadView& v, int i) {
-    const uint8_t c = a.ascii[v.off + (v.flipseq ? v.len - 1 - i : i)] & 0xdf;
-    int code = c == 'A' ? 1 : c == 'C' ? 2 : c == 'G' ? 4 : c == 'T' ? 8 : 15;
-    if (v.flipseq && code != 15) code = code == 1 ? 8 : code == 2 ? 4 : code == 4 ? 2 : 1;
+    const uint8_t c = a.ascii[v.off + (v.flipseq ? v.len - 1 - i : i)];
+    int code = nt16_of(c);
+    const bool acgt = code != 0 && (code & (code - 1)) == 0;                     // 1 2 4 8; their complement is the code's bits reversed
+    if (v.m2rc && acgt && c < 'a') code = (int)(__brev((unsigned)code) >> 28);     // upper case only
+    if (v.rev) code = acgt ? (int)(__brev((unsigned)code) >> 28) : 15;
     return code;
 }
 

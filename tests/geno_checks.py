@@ -6,6 +6,7 @@ bcf_call_combine (bam2bcf.c:955-1115) with loops and math.lgamma.  Shares no tab
 The BAM order of the records is an input (`rank`: place of every read in the BAM, 0xffffffff = not written): the reference
 sorts with an unstable sort on the position alone, so the order of equal positions is a property of the file.
 """
+import functools
 import heapq
 import math
 
@@ -38,8 +39,20 @@ _CODE = np.full(256, 15, np.uint8)
 for _c, _v in zip(b"ACGT", (1, 2, 4, 8)):
     _CODE[_c] = _v
     _CODE[_c + 32] = _v
-_COMP16 = np.arange(16, dtype=np.uint8)
-_COMP16[[1, 2, 4, 8]] = [8, 4, 2, 1]
+# what the BAM holds for a letter (build_bam_from_result, src/conversion.cpp:288-388; htslib's seq_nt16_table): a read placed as
+# given keeps every code of "=ACMGRSVTWYHKDBN", either case; a read placed on the other strand has A C G T of either case
+# complemented and N for every other letter.  A mate 2 the pipeline reverse-complements first (seeding::reverseComplement,
+# src/seeding.cpp:271-284) has only its upper-case A C G T complemented by that step.  ('=' in a read is not modelled.)
+_NT16 = np.full(256, 15, np.uint8)
+for _v, _c in enumerate(b"=ACMGRSVTWYHKDBN"):
+    _NT16[_c] = _v
+    if _c != ord("="):
+        _NT16[_c + 32] = _v
+_NT16_OTHER_STRAND = np.full(256, 15, np.uint8)
+for _c, _v in zip(b"ACGT", (8, 4, 2, 1)):
+    _NT16_OTHER_STRAND[_c] = _NT16_OTHER_STRAND[_c + 32] = _v
+_RC_UPPER = np.arange(256, dtype=np.uint8)
+_RC_UPPER[list(b"ACGT")] = list(b"TGCA")
 _B4 = np.full(16, 4, np.int64)
 _B4[[1, 2, 4, 8]] = [0, 1, 2, 3]
 
@@ -56,13 +69,15 @@ class Read:
         c3 = qs if self.rev else self.len - qe
         ops = [(int(x) & 0xf, int(x) >> 4) for x in cig[int(rec["cigar_off"]):int(rec["cigar_off"]) + int(rec["n_cigar"])]]
         self.cigar = ([(S, c5)] if c5 > 0 else []) + ops + ([(S, c3)] if c3 > 0 else [])
-        flip = bool(revcomp_mate2 and (r & 1)) != bool(self.rev)
-        code = _CODE[concat[lo:hi]]
+        m2 = bool(revcomp_mate2 and (r & 1))
+        flip = m2 != bool(self.rev)
+        given = _RC_UPPER[concat[lo:hi][::-1]] if m2 else concat[lo:hi]
+        code = _NT16_OTHER_STRAND[given[::-1]] if self.rev else _NT16[given]
         q = np.full(self.len, ord("I"), np.int64) if quals is None else quals[lo:hi].astype(np.int64)
         q[q == 0] = ord("I")
         q = np.maximum(q - 33, 0)
         if flip:
-            code, q = _COMP16[code[::-1]], q[::-1]
+            q = q[::-1]
         self.code, self.q = code.copy(), q.copy()
         self.strand = (0 if self.rev else 1) if (paired and (r & 1)) else (1 if self.rev else 0)
         self.late_idx, self.late_q = -1, 0
@@ -130,8 +145,12 @@ class _Walk:
         return self.ci > 0 and self.c[self.ci - 1][0] == D
 
 
-def reconcile(a: Read, b: Read, a_keeps: bool):
-    """tweak_overlap_quality (sam.c:5824-5963): a came first in the BAM"""
+def reconcile(a: Read, b: Read, a_keeps: bool, seen=None):
+    """tweak_overlap_quality (sam.c:5824-5963): a came first in the BAM.  `seen`: a dict that counts the branches taken
+    (for the preconditions of the crafted fixtures)"""
+    def note(what):
+        if seen is not None:
+            seen[what] = seen.get(what, 0) + 1
     amul, bmul = (1, 0) if a_keeps else (0, 1)
     iref = b.rs
     wa = _Walk(a, iref - a.rs)
@@ -152,6 +171,7 @@ def reconcile(a: Read, b: Read, a_keeps: bool):
         iref = max(iref, wa.iref + a.rs, wb.iref + b.rs) + 1
         if wa.iref + a.rs != wb.iref + b.rs:
             if wa.iref + a.rs < wb.iref + b.rs and wb.prev_is_del():
+                note("deletion in b")
                 while True:
                     if wa.iseq >= a.len:
                         return
@@ -161,6 +181,7 @@ def reconcile(a: Read, b: Read, a_keeps: bool):
                     if not wa.iref + a.rs < wb.iref + b.rs:
                         break
             elif wa.prev_is_del():
+                note("deletion in a")
                 while True:
                     if wb.iseq >= b.len:
                         return
@@ -170,18 +191,23 @@ def reconcile(a: Read, b: Read, a_keeps: bool):
                     if not wb.iref + b.rs < wa.iref + a.rs:
                         break
             else:
+                note("unequal positions skipped")
                 continue
         if wa.iseq >= a.len or wb.iseq >= b.len:
             return
         qa, qb = int(a.q[wa.iseq]), int(b.q[wb.iseq])
         if a.code[wa.iseq] == b.code[wb.iseq]:
+            note("agree, a keeps" if a_keeps else "agree, b keeps")
             s = min(qa + qb, 200)
             a.q[wa.iseq], b.q[wb.iseq] = amul * s, bmul * s
         elif qa > qb:
+            note("differ, a better")
             a.q[wa.iseq], b.q[wb.iseq] = qa * 4 // 5, 0
         elif qa < qb:
+            note("differ, b better")
             b.q[wb.iseq], a.q[wa.iseq] = qb * 4 // 5, 0
         else:
+            note("differ, equal quality")
             a.q[wa.iseq], b.q[wb.iseq] = amul * (qa * 4 // 5), bmul * (qb * 4 // 5)
 
 
@@ -237,7 +263,7 @@ def pileup_tables(recs, cig, concat, offsets, ref_len, paired, revcomp_mate2, ra
         adm_start.append(rs)
     adm_start = np.asarray(adm_start, np.int64)
     reads = {r: Read(r, recs[r], cig, concat, offsets, quals, paired, revcomp_mate2) for r in adm_order}
-    n_reconciled = 0
+    n_reconciled, late_reads, branches = 0, [], {}
     if paired:
         for u in range(0, n - 1, 2):
             if not (admitted[u] and admitted[u + 1]):
@@ -261,7 +287,7 @@ def pileup_tables(recs, cig, concat, offsets, ref_len, paired, revcomp_mate2, ra
                 elif op in (D, N):
                     x += ln
             neighbour = int(a.q[q_last + 1]) if q_last >= 0 and q_last + 1 < a.len else None
-            reconcile(a, b, name_keeps_first(qname))
+            reconcile(a, b, name_keeps_first(qname), branches)
             n_reconciled += 1
             if neighbour is not None:
                 # the position is piled up when the first admitted read that starts behind it is pushed (sam.c:6034); the
@@ -270,6 +296,7 @@ def pileup_tables(recs, cig, concat, offsets, ref_len, paired, revcomp_mate2, ra
                 first = adm_order[j] if j < len(adm_order) else -1
                 if first != rb:
                     a.late_idx, a.late_q = q_last, neighbour
+                    late_reads.append(ra)
     hist = np.zeros((ref_len, 64, 2, 5), np.uint32)
     aux = np.zeros((ref_len, 4), np.uint32)
     for r in adm_order:
@@ -306,7 +333,8 @@ def pileup_tables(recs, cig, concat, offsets, ref_len, paired, revcomp_mate2, ra
                 x += ln
             elif op == N:
                 x += ln
-    return hist, aux, dict(admitted=admitted, refused_by_cap=refused, reconciled_pairs=n_reconciled)
+    return hist, aux, dict(admitted=admitted, refused_by_cap=refused, reconciled_pairs=n_reconciled, late_neighbours=len(late_reads), late_reads=late_reads,
+                           branches=branches)
 
 
 # ------------------------------------------------------------------------------------------------ error model
@@ -314,8 +342,9 @@ def _lbinom(n, k):
     return 0.0 if k <= 0 or k > n else math.lgamma(n + 1) - math.lgamma(k + 1) - math.lgamma(n - k + 1)
 
 
+@functools.lru_cache(maxsize=None)
 def _beta_row(q, n):
-    """cal_coef (errmod.c:86-99) for one (quality, depth)"""
+    """cal_coef (errmod.c:86-99) for one (quality, depth); the row is read, never written"""
     e = 10.0 ** (-q / 10.0)
     le, le1 = math.log(e), math.log(1.0 - e)
     row = [0.0] * (n + 1)

@@ -172,16 +172,8 @@ def test_checker_reproduces_the_golden_line_from_the_reference_aligner(pmx, orac
     of the BAM written from them: DP, AD, DP4, MQ and PL of the golden line at position 24152."""
     if not os.path.isdir(os.path.join(ROOT, "oracle", "_ref")):
         pytest.skip("oracle/_ref (compiled reference aligner) is absent")
-    import test_bam as tb
-    g = b"".join(l.strip() for l in open(os.path.join(GOLDEN, "isolate.ref.fa"), "rb") if not l.startswith(b">"))
-    seqs, quals, names = pmx.read_fastq_paired(os.path.join(GOLDEN, "isolate_R1.fastq.gz"), os.path.join(GOLDEN, "isolate_R2.fastq.gz"))
-    want = oracle.ref_align_reads_direct(g, seqs, True, 8)
-    bam = str(tmp_path / "isolate.bam")
-    pmx.write_bam(bam, "node_7618", len(g), seqs, quals, names, want, True)
-    rank = gc.rank_from_bam(tb.parse_bam(bam)[2], names, True)
-    recs, cig = gc.results_to_records(want, True)
-    concat, off = pmx.concat_reads(seqs)
-    hist, aux, info = gc.pileup_tables(recs, cig, concat, off, len(g), True, False, rank, quals=b"".join(quals), names=names)
+    import pileup_golden as pg
+    g, hist, aux, info = pg.demo_checker_tables(pmx, oracle, str(tmp_path))
     p = 24152 - 1
     site = gc.site(hist[p], g[p:p + 1])
     mq = int(np.float32(aux[p, 1]) / np.float32(hist[p].sum()))
