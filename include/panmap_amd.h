@@ -358,6 +358,48 @@ int pmx_align_scoring(const pmx_aligner *al, int32_t out[9]);
 int pmx_align_dp_batch(pmx_ctx *ctx, pmx_aligner *al, const uint8_t *seqs, const int64_t *q_off, const int64_t *t_off, int64_t n,
                        const int32_t *w, const int32_t *zdrop, const int32_t *end_bonus, const int32_t *flag, pmx_dp_result *out,
                        int reps, double *kernel_ms);
+/* One chosen DP implementation of the align tiers on a caller's requests (the entry point of their parity tests against the
+ * reference's ksw_extd2_sse / ksw_ll_i16; inputs as pmx_align_dp_batch takes them):
+ *   SERVE            the wave DP service as a service round launches it: everything else (class 2), then the register-resident
+ *                    kernel for sides <= 192 (class 1).  Requests are posted in 480-byte entries ((qlen + 15 & ~15) + tlen <= 480)
+ *                    and results hold up to 20 CIGAR operations.
+ *   SERVE_ONE_CLASS  the same service with one class: every request through ksw_extd2 of the all-LDS unit.
+ *   WAVE_LONG        one request per wave on the layout of the long-read launch (dp_fast LDS copy unless no_dp_fast).
+ *   WAVE_GENERAL     the same on the general layout of the wave tiers (no dp_fast: the anti-diagonal kernel on the layout's arrays).
+ *   SW_LL            sw_ll (ksw_ll_i16) on the long-read layout: score in .score, .qe / .te / .ok as it leaves them.
+ * max_read_len / n_segs: what the layouts are planned from, by the planners the stage itself uses.  no_rows_dp / no_dp_fast: the
+ * PMX_ALIGN_NO_ROWS_DP / PMX_ALIGN_NO_DP_FAST switches as arguments.  caps[0] receives the capacities planned (SERVE: class 2,
+ * caps[1] class 1) also when n == 0; a request beyond them comes back served = 0.  CIGARs go to cigar_arena (arena_cap words;
+ * n * caps[0].max_cigar always suffices) at out[i].cigar_off.  path_taken: PMX_DP_PATH_* of the implementation that ran. */
+#define PMX_DP_PROBE_SERVE 0
+#define PMX_DP_PROBE_SERVE_ONE_CLASS 1
+#define PMX_DP_PROBE_WAVE_LONG 2
+#define PMX_DP_PROBE_WAVE_GENERAL 3
+#define PMX_DP_PROBE_SW_LL 4
+#define PMX_DP_PATH_REG 0x100      /* ksw_extd2_reg, | NC (1..3), | TB_LDS */
+#define PMX_DP_PATH_ROWS 0x200     /* ksw_extd2_rows_t, | SW (4, 8, 12, 16), | EXACT */
+#define PMX_DP_PATH_DIAG 0x300     /* ksw_extd2_t, | FAST or | TB_LDS */
+#define PMX_DP_PATH_KIND 0x300
+#define PMX_DP_PATH_EXACT 0x20
+#define PMX_DP_PATH_FAST 0x40
+#define PMX_DP_PATH_TB_LDS 0x80
+#define PMX_DP_PATH_ALL_LDS 0x1000 /* dispatched by the all-LDS unit (SERVE_ONE_CLASS) */
+typedef struct {
+    int32_t served;
+    uint32_t max;
+    int32_t zdropped, max_q, max_t, mqe, mqe_t, mte, mte_q, score, n_cigar, reach_end;
+    int32_t path_taken;
+    int32_t ok, qe, te; /* SW_LL */
+    int64_t cigar_off;
+} pmx_dp_probe_result;
+typedef struct {
+    int32_t max_qlen, max_tlen, max_cigar, reserved;
+    int64_t tb_cap, tb_fast_cap;
+} pmx_dp_probe_caps;
+int pmx_align_dp_probe(pmx_ctx *ctx, pmx_aligner *al, int path, int max_read_len, int n_segs, int no_rows_dp, int no_dp_fast,
+                       const uint8_t *seqs, const int64_t *q_off, const int64_t *t_off, int64_t n, const int32_t *w,
+                       const int32_t *zdrop, const int32_t *end_bonus, const int32_t *flag, pmx_dp_probe_result *out,
+                       uint32_t *cigar_arena, int64_t arena_cap, pmx_dp_probe_caps caps[2]);
 int64_t pmx_align_num_records(const pmx_aligner *al);
 int64_t pmx_align_cigar_words(pmx_ctx *ctx, pmx_aligner *al);
 int pmx_align_fetch(pmx_ctx *ctx, pmx_aligner *al, pmx_aln_record *records, int64_t n_records, uint32_t *cigar_arena,

@@ -337,3 +337,19 @@ def ref_ksw_extd2(query, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag):
     if ez.cigar:
         C.CDLL(None).free(ez.cigar)
     return out
+
+
+def ref_ksw_ll(query, target, mat, gapo, gape):
+    """ksw_ll_qinit + ksw_ll_i16 of the compiled reference (src/3rdparty/minimap2/ksw2_ll_sse.c:37-158) on nt4 codes, as the Z-drop
+    test and the inversion probe call them (align.c:74-86, 835-885: 16-bit lanes, alphabet of 5).  -> (score, qe, te)"""
+    L = rlib()
+    L.ksw_ll_qinit.restype = C.c_void_p
+    L.ksw_ll_qinit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int8)]
+    L.ksw_ll_i16.restype = C.c_int
+    L.ksw_ll_i16.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    qb, tb = bytes(bytearray(query)), bytes(bytearray(target))
+    qp = L.ksw_ll_qinit(None, 2, len(qb), qb, 5, mat)
+    qe, te = C.c_int(-1), C.c_int(-1)
+    score = L.ksw_ll_i16(qp, len(tb), tb, gapo, gape, C.byref(qe), C.byref(te))
+    _libc.free(qp)      # (kmalloc of a NULL pool is malloc)
+    return int(score), int(qe.value), int(te.value)

@@ -712,6 +712,15 @@ def last_error() -> bytes:
 
 DP_RESULT_DTYPE = np.dtype([("served", "<i4"), ("max", "<u4"), ("zdropped", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), ("mqe", "<i4"), ("mqe_t", "<i4"),
                             ("mte", "<i4"), ("mte_q", "<i4"), ("score", "<i4"), ("n_cigar", "<i4"), ("reach_end", "<i4"), ("cigar", "<u4", (20,))])
+DP_PROBE_DTYPE = np.dtype([("served", "<i4"), ("max", "<u4"), ("zdropped", "<i4"), ("max_q", "<i4"), ("max_t", "<i4"), ("mqe", "<i4"), ("mqe_t", "<i4"),
+                           ("mte", "<i4"), ("mte_q", "<i4"), ("score", "<i4"), ("n_cigar", "<i4"), ("reach_end", "<i4"), ("path_taken", "<i4"),
+                           ("ok", "<i4"), ("qe", "<i4"), ("te", "<i4"), ("cigar_off", "<i8")])
+DP_PROBE_CAPS_DTYPE = np.dtype([("max_qlen", "<i4"), ("max_tlen", "<i4"), ("max_cigar", "<i4"), ("reserved", "<i4"), ("tb_cap", "<i8"),
+                                ("tb_fast_cap", "<i8")])
+DP_PROBE_PATHS = {"SERVE": 0, "SERVE_ONE_CLASS": 1, "WAVE_LONG": 2, "WAVE_GENERAL": 3, "SW_LL": 4}
+# path_taken (PMX_DP_PATH_* of include/panmap_amd.h)
+DP_PATH_REG, DP_PATH_ROWS, DP_PATH_DIAG, DP_PATH_KIND = 0x100, 0x200, 0x300, 0x300
+DP_PATH_EXACT, DP_PATH_FAST, DP_PATH_TB_LDS, DP_PATH_ALL_LDS = 0x20, 0x40, 0x80, 0x1000
 REC_DTYPE = np.dtype([("rs", "<i4"), ("re", "<i4"), ("qs", "<i4"), ("qe", "<i4"), ("mapq", "u1"), ("rev", "u1"),
                       ("proper_frag", "u1"), ("mapped", "u1"), ("n_cigar", "<u2"), ("flags", "<u2"), ("cigar_off", "<u4"),
                       ("score", "<i4")])
@@ -800,6 +809,35 @@ class Aligner:
         check(lib.pmx_align_dp_batch(self.ctx._h, self._h, seqs.ctypes.data, qs.ctypes.data, ts.ctypes.data, n, w_.ctypes.data, z_.ctypes.data,
                                      e_.ctypes.data, f_.ctypes.data, out.ctypes.data, int(reps), C.byref(ms)), "pmx_align_dp_batch")
         return out, float(ms.value)
+
+    def dp_probe(self, path, queries, targets, w, zdrop, end_bonus, flag, max_read_len: int, n_segs: int = 1, no_rows_dp: bool = False,
+                 no_dp_fast: bool = False):
+        """one chosen DP implementation of the align tiers on (query, target) pairs of nt4 codes (pmx_align_dp_probe); path: a key of
+        DP_PROBE_PATHS.  -> (structured array of DP_PROBE_DTYPE, CIGAR arena: request i's operations at [cigar_off, cigar_off + n_cigar),
+        capacities planned: two records of DP_PROBE_CAPS_DTYPE)"""
+        n = len(queries)
+        qa = [np.asarray(a, np.uint8) for a in queries]
+        ta = [np.asarray(b, np.uint8) for b in targets]
+        qs, ts = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+        if n:
+            qs[1:] = np.cumsum([len(a) for a in qa])
+            ts[1:] = np.cumsum([len(b) for b in ta])
+        ts += qs[-1]                                       # all queries first, then all targets
+        seqs = np.ascontiguousarray(np.concatenate(qa + ta)) if n else np.zeros(1, np.uint8)
+        code = DP_PROBE_PATHS[path]
+        caps = np.zeros(2, DP_PROBE_CAPS_DTYPE)
+        args = (self.ctx._h, self._h, code, int(max_read_len), int(n_segs), int(bool(no_rows_dp)), int(bool(no_dp_fast)))
+        check(lib.pmx_align_dp_probe(*args, None, None, None, 0, None, None, None, None, None, None, 0, caps.ctypes.data), "pmx_align_dp_probe")
+        out = np.zeros(n, DP_PROBE_DTYPE)
+        arena = np.zeros(max(n * int(caps["max_cigar"][0]), 1), np.uint32)
+
+        def arr(x):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.int32), (n,)))
+        w_, z_, e_, f_ = arr(w), arr(zdrop), arr(end_bonus), arr(flag)
+        if n:
+            check(lib.pmx_align_dp_probe(*args, seqs.ctypes.data, qs.ctypes.data, ts.ctypes.data, n, w_.ctypes.data, z_.ctypes.data, e_.ctypes.data,
+                                         f_.ctypes.data, out.ctypes.data, arena.ctypes.data, len(arena), caps.ctypes.data), "pmx_align_dp_probe")
+        return out, arena, caps
 
     def stats(self) -> dict:
         """work statistics of the last align_readset call (DP cells = q * min(t, 2w+1) per ksw2 call)"""

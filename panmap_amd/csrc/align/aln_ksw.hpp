@@ -379,7 +379,7 @@ PMX_HD void ksw_extd2(Work& W, int qlen, QP query, int tlen, TP target, const in
         const size_t area = (size_t)9 * (PMX_DP_FAST_TLEN + 32) + 64, main_b = ksw_rows_lds_main(qlen);
         if (main_b <= area &&
             ksw_extd2_rows(W, W.dp_fast, main_b, W.dp_fast + main_b, area - main_b, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez)) {
-            account(23);
+            account(23);   // (W.dp_path: set by ksw_extd2_rows)
             return;
         }
     }
@@ -387,11 +387,13 @@ PMX_HD void ksw_extd2(Work& W, int qlen, QP query, int tlen, TP target, const in
     auto account = [&](int) {};
 #endif
     if (W.dp_fast && W.caps.dp_fast_tlen == PMX_DP_FAST_TLEN && (tlen + 15) / 16 * 16 <= PMX_DP_FAST_TLEN && qlen <= PMX_DP_FAST_TLEN) {
+        W.dp_path = PMX_DPP_DIAG | PMX_DPP_FAST;
         if (flag & PMX_EZ_RIGHT) ksw_extd2_t<true, true>(W, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez);
         else ksw_extd2_t<true, false>(W, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez);
         account(26);
         return;
     }
+    W.dp_path = PMX_DPP_DIAG | (PMX_TB_IS_LDS((const uint8_t*)W.tb) ? PMX_DPP_TB_LDS : 0);
     if (flag & PMX_EZ_RIGHT) ksw_extd2_t<false, true>(W, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez);
     else ksw_extd2_t<false, false>(W, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez);
     account(29);
@@ -406,6 +408,9 @@ PMX_HD void ksw_extd2(Work& W, int qlen, QP query, int tlen, TP target, const in
             ksw_extd2_rows(W, (int8_t*)W.du, main_b, (int8_t*)W.H, arr_b, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez))
             return;
     }
+#endif
+#if defined(PMX_ALL_LDS)
+    W.dp_path = PMX_DPP_ALL_LDS | PMX_DPP_DIAG | (PMX_TB_IS_LDS((const uint8_t*)W.tb) ? PMX_DPP_TB_LDS : 0);
 #endif
     if (flag & PMX_EZ_RIGHT) ksw_extd2_t<false, true>(W, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez);
     else ksw_extd2_t<false, false>(W, qlen, query, tlen, target, mat, q, e, q2, e2, w, zdrop, end_bonus, flag, ez);

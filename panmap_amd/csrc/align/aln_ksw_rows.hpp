@@ -258,6 +258,11 @@ __device__ __forceinline__ bool ksw_extd2_rows(Work& W, int8_t* lds, size_t lds_
     if (ksw_rows_lds_main(qlen) > lds_bytes || ksw_rows_lds_arrays(qlen, tlen, exact) > arr_bytes) return false;
     const int sc_mch = mat[0], sc_mis = mat[1], sc_N = mat[24] == 0 ? -e2 : mat[24];
     const bool right = (flag & PMX_EZ_RIGHT) != 0;
+#if defined(PMX_ALL_LDS)
+    W.dp_path = PMX_DPP_ALL_LDS | PMX_DPP_ROWS | sw | (exact ? PMX_DPP_EXACT : 0);
+#else
+    W.dp_path = PMX_DPP_ROWS | sw | (exact ? PMX_DPP_EXACT : 0);
+#endif
 #define PMX_ROWS_CALL(SWV, R, X) ksw_extd2_rows_t<SWV, R, X>(W, lds, lds_arr, qlen, query, tlen, target, q, e, q2, e2, sc_mch, sc_mis, sc_N, zdrop, end_bonus, flag, ez)
 #define PMX_ROWS_SW(SWV)                                         \
     do {                                                         \

@@ -387,6 +387,16 @@ struct DpReq {   // 512 bytes
     uint8_t seq[PMX_DP_SEQ_BYTES];   // query, then target at ((qlen + 15) & ~15)
 };
 
+// Work::dp_path: which implementation of ksw_extd2 answered a DP call (== PMX_DP_PATH_* of include/panmap_amd.h)
+#define PMX_DPP_REG 0x100       // ksw_extd2_reg, | NC (1..3)
+#define PMX_DPP_ROWS 0x200      // ksw_extd2_rows_t, | SW (4, 8, 12, 16), | PMX_DPP_EXACT
+#define PMX_DPP_DIAG 0x300      // ksw_extd2_t, | PMX_DPP_FAST
+#define PMX_DPP_KIND 0x300
+#define PMX_DPP_EXACT 0x20      // rows: exact maximum replayed (else the approximate-maximum mode)
+#define PMX_DPP_FAST 0x40       // anti-diagonal kernel on the dp_fast LDS copy
+#define PMX_DPP_TB_LDS 0x80     // traceback matrix in LDS (else in the wave's slab)
+#define PMX_DPP_ALL_LDS 0x1000  // dispatched by the all-LDS unit (align_kernel_t1.hip)
+
 // Capacities of the per-wave work memory (chosen by the host from the read-length regime).
 struct Caps {
     int max_qlen;      // per segment
@@ -468,6 +478,7 @@ struct Work {
     int dp_post_end;        // calls [dp_n_cached, dp_post_end) were posted in this pass (contiguous: the next pass may rely on them)
     uint32_t status_pre;    // status when the first request of this pass was posted (what follows runs on neutral dummy results)
     int last_dp_shortcut;   // the last align_pair call was answered by ksw_shortcut
+    int dp_path;            // PMX_DPP_*: the implementation that ran the last DP call (set where the dispatchers branch; pmx_align_dp_probe reports it)
     int skip_shortcut;      // align1 already tried the shortcut on the reference bases directly
     // optional phase profile (diagnostic runs only: AlignArgs::prof != NULL)
     unsigned long long* prof;

@@ -81,12 +81,34 @@ struct AlignArgs {
     AlnRecord* records;
 };
 
+// pmx_align_dp_probe, wave paths (k_align_dp_probe in align_kernel.hip): one request per wave on a wave-per-read layout
+struct DpProbeOut {
+    Ez ez;
+    int32_t served, path, ok, qe, te;   // sw_ll: score in ez.score, ok / qe / te as it leaves them
+};
+struct DpProbeArgs {
+    const uint8_t* seqs;        // nt4 codes; request i: query seqs[q_off[i] .. q_off[i+1]), target seqs[t_off[i] .. t_off[i+1])
+    const int64_t* q_off;
+    const int64_t* t_off;
+    const int32_t *w, *zdrop, *end_bonus, *flag;
+    int64_t n;
+    DpProbeOut* out;
+    uint32_t* cigars;           // n * layout.caps.max_cigar words
+    int sw_ll;                  // 1 = sw_ll instead of ksw_extd2
+    int no_rows_dp;
+    Opt opt;
+    Layout layout;
+    uint8_t* slow_base;
+    size_t slow_stride;
+};
+
 __global__ void k_align_reads(AlignArgs A);
 __global__ void k_align_reads_w4(AlignArgs A);
 __global__ void k_align_reads_t1(AlignArgs A);
 __global__ void k_align_reads_t1_w4(AlignArgs A);
 __global__ void k_align_reads_tpp(AlignArgs A);
 __global__ void k_align_dp_serve(AlignArgs A);
+__global__ void k_align_dp_probe(DpProbeArgs A);
 __global__ void k_align_compact16(AlignArgs A);   // retry_list / retry_count = its bail list; reference <= 32,767 bases; seeds from cseeds
 __global__ void k_align_compact32(AlignArgs A);
 __global__ void k_align_compact16_fused(AlignArgs A);   // sketch and probes inside (PMX_ALIGN_COMPACT_FUSED)

@@ -59,6 +59,7 @@ __global__ void __launch_bounds__(64, 3) k_align_dp_serve(AlignArgs A) {
                            rq->w, rq->zdrop, rq->end_bonus, rq->flag, ez)
         if (A.dp_class == 1) {
             const bool tbl = tb_need <= A.layout.tb_fast_cap;
+            W.dp_path = PMX_DPP_REG | (tlen <= 64 ? 1 : tlen <= 128 ? 2 : 3) | (tbl ? PMX_DPP_TB_LDS : 0);
             if (tlen <= 64) { if (tbl) PMX_REG_DP(1, true); else PMX_REG_DP(1, false); }
             else if (tlen <= 128) { if (tbl) PMX_REG_DP(2, true); else PMX_REG_DP(2, false); }
             else { if (tbl) PMX_REG_DP(3, true); else PMX_REG_DP(3, false); }
@@ -73,6 +74,7 @@ __global__ void __launch_bounds__(64, 3) k_align_dp_serve(AlignArgs A) {
             const uint32_t* cg = W.cig_tmp; PMX_LDS(cg);
             dp_store_result(A, slot, rq, ez, cg, W.status);
             rq->call = 0xffffffffu;   // served
+            rq->flag = W.dp_path;     // (the entry keeps which kernel ran it: pmx_align_dp_probe reads it back)
             if (A.stats) {
                 atomicAdd(&A.stats[0], 1ULL);
                 atomicAdd(&A.stats[1], (unsigned long long)dp_cells(qlen, tlen, rq->w));

@@ -59,6 +59,43 @@ void dpg_launch(pmx_ctx* ctx, pmx_aligner* al, DpgArgs& DG, int64_t n_slots, con
     if (serve) hipLaunchKernelGGL(k_align_dp_group, dim3((unsigned)grid), dim3(64), PMX_DPG_LDS_BYTES, ctx->stream, DG);
     PMX_HIP(hipGetLastError());
 }
+
+// The wave DP service's layouts, LDS bytes, slab strides and resident grids
+DpServePlan plan_dp_serve(const pmx_ctx* ctx, int max_read_len, int n_segs, const Opt& o) {
+    DpServePlan P;
+    P.dp_layout = plan_layout_dp(max_read_len, n_segs, o);
+    P.dp_lds = PMX_ALIGN_WORK_BYTES + P.dp_layout.fast_bytes + 16;
+    P.dp_stride = (P.dp_layout.slow_bytes + 255) & ~(size_t)255;
+    P.dp_max_grid = (int64_t)ctx->n_cu * (int64_t)std::min<size_t>(16, (size_t)(160 * 1024) / P.dp_lds);
+    P.dps_layout = plan_layout_dp(max_read_len, n_segs, o, DpServePlan::kSmallQlen, DpServePlan::kSmallTlen);
+    P.dps_lds = PMX_ALIGN_WORK_BYTES + P.dps_layout.fast_bytes + 16;
+    P.dps_max_grid = (int64_t)ctx->n_cu * (int64_t)std::min<size_t>(16, (size_t)(160 * 1024) / P.dps_lds);
+    P.dps_stride = (P.dps_layout.slow_bytes + 255) & ~(size_t)255;
+    return P;
+}
+
+// k_align_dp_serve reads, beyond the base: dp_req_base / dp_res_base, layout, slow_base / slow_stride, n_items, worklist,
+// dp_class, dp_small_qlen / dp_small_tlen / dp_small_tb, and dp_left (null: it always looks at every entry).
+void launch_dp_serve(AlignArgs A, const DpServePlan& P, bool two_class, uint8_t* slow, uint8_t* slow2, hipStream_t stream) {
+    const int64_t n_dp = A.n_items;
+    A.dp_small_qlen = DpServePlan::kSmallQlen; A.dp_small_tlen = DpServePlan::kSmallTlen;
+    A.dp_small_tb = (uint32_t)P.dps_layout.tb_cap;
+    A.layout = P.dp_layout;
+    A.slow_stride = P.dp_stride;
+    A.slow_base = slow;
+    A.dp_class = two_class ? 2 : 0;
+    // (tier 0 runs for the short-read preset only; with max_gap of a long-read preset the arrays of this class exceed the LDS of a
+    //  CU and pmx_align_dp_probe is left with the small class)
+    if (P.dp_max_grid > 0)
+        hipLaunchKernelGGL(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(P.dp_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), P.dp_lds, stream, A);
+    if (two_class) {
+        A.layout = P.dps_layout;
+        A.slow_stride = P.dps_stride;
+        A.slow_base = slow2;
+        A.dp_class = 1;
+        hipLaunchKernelGGL(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(P.dps_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), P.dps_lds, stream, A);
+    }
+}
 }  // namespace pmx
 
 namespace {
@@ -105,6 +142,23 @@ struct AlignSwitches {
     }
 };
 
+}  // namespace
+
+namespace pmx {
+// general capacities (AlignStage::setup) / the first launch of the long reads (AlignStage::long_reads: small LDS budget, 8 MB of
+// traceback per wave, the dp_fast LDS copy of the DP arrays)
+Layout plan_general_layout(int max_read_len, int n_segs, const Opt& o) {
+    const AlignSwitches sw;
+    return plan_layout(max_read_len, n_segs, o, sw.lds_budget);
+}
+Layout plan_long_reads_layout(int max_read_len, int n_segs, const Opt& o, bool no_dp_fast) {
+    const AlignSwitches sw;
+    return plan_layout(max_read_len, n_segs, o, sw.lr_lds_budget, sw.tb_small, 1, no_dp_fast ? 0 : PMX_DP_FAST_TLEN);
+}
+}  // namespace pmx
+
+namespace {
+
 typedef void (*AlignKernel)(AlignArgs);
 
 // One call of the stage.  `base` holds what every launch of the call shares; a launch function copies it, sets the fields its
@@ -119,14 +173,14 @@ struct AlignStage {
     const int64_t n_items;      // an odd trailing read is ignored (src/mm_align.c:372)
     const int n_segs;
     const AlignKernel kern, kern_t1;
-    static constexpr int kSmallQlen = 192, kSmallTlen = 192;   // the wave service's small class (ksw_extd2_reg<3>: up to three target columns per lane)
     AlignArgs base{};           // reads, reference, options, outputs, stats / edits / prof, paired, revcomp_mate2, sk_no_lane_ring, no_rows_dp,
                                 // the first mv_epoch of the call, and (plan_tier0) the thread-per-pair arena; every other field zero
     Layout general, compact;    // wave tiers: general capacities; all-LDS layout (typical short-read pairs)
     // thread-per-pair tier and its DP service (plan_tier0)
-    Layout tpp_layout, dp_layout, dps_layout;   // dp / dps: the wave service's two classes (everything else / register DP)
-    size_t tpp_raw_stride = 0, tpp_lds_bytes = 0, dp_lds = 0, dp_stride = 0, dps_lds = 0, dps_stride = 0;
-    int64_t tpp_max_grid = 0, dp_max_grid = 0, dps_max_grid = 0;
+    Layout tpp_layout;
+    DpServePlan dpp;            // the wave service's two classes
+    size_t tpp_raw_stride = 0, tpp_lds_bytes = 0;
+    int64_t tpp_max_grid = 0;
     bool use_dp_service = false, use_compact = false, dpg_ok = false;
     DpgArgs dpg_base;           // scoring parameters of the grouped service (dpg_setup)
     // launch order (launch_order)
@@ -206,7 +260,7 @@ bool AlignStage::setup(int revcomp_mate2, uint64_t cigar_cap) {
     base.sk_no_lane_ring = sw.no_lane_ring ? 1 : 0;
     base.no_rows_dp = sw.no_rows_dp ? 1 : 0;
     base.mv_epoch = ++al->mv_epoch;
-    general = hooked(plan_layout((int)rs->max_len, n_segs, al->opt, sw.lds_budget));
+    general = hooked(plan_general_layout((int)rs->max_len, n_segs, al->opt));
     compact = hooked(plan_layout_compact((int)rs->max_len, n_segs, al->opt));
     return true;
 }
@@ -294,8 +348,7 @@ void AlignStage::long_reads() {
     // wave's HBM slab whatever the LDS budget, and the kernel is bound by the latency of those accesses: what counts is
     // resident waves (16 per CU: 32.4 k reads/s, 8 per CU: 21.1 k) and that the DPs -- nearly all a few hundred bases
     // wide -- run on a small LDS copy of their arrays (plan_layout dp_fast_tlen)
-    const int dp_fast = sw.no_dp_fast ? 0 : PMX_DP_FAST_TLEN;
-    const Layout g1 = hooked(plan_layout((int)rs->max_len, n_segs, al->opt, sw.lr_lds_budget, sw.tb_small, 1, dp_fast));
+    const Layout g1 = hooked(plan_long_reads_layout((int)rs->max_len, n_segs, al->opt, sw.no_dp_fast));
     al->retry_list.ensure((size_t)n_items);
     timer_begin(ctx, "align_dom");
     AlignArgs A = base;
@@ -328,14 +381,7 @@ void AlignStage::plan_tier0() {
     if (tpp_wave_stride > UINT32_MAX) throw std::runtime_error("thread-per-pair arena stride exceeds 32 bits");
     base.tpp.base = al->slab0.p;
     base.tpp.wave_stride = (uint32_t)tpp_wave_stride;
-    dp_layout = plan_layout_dp((int)rs->max_len, n_segs, al->opt);
-    dp_lds = PMX_ALIGN_WORK_BYTES + dp_layout.fast_bytes + 16;
-    dp_stride = (dp_layout.slow_bytes + 255) & ~(size_t)255;
-    dp_max_grid = (int64_t)ctx->n_cu * (int64_t)std::min<size_t>(16, (size_t)(160 * 1024) / dp_lds);
-    dps_layout = plan_layout_dp((int)rs->max_len, n_segs, al->opt, kSmallQlen, kSmallTlen);
-    dps_lds = PMX_ALIGN_WORK_BYTES + dps_layout.fast_bytes + 16;
-    dps_max_grid = (int64_t)ctx->n_cu * (int64_t)std::min<size_t>(16, (size_t)(160 * 1024) / dps_lds);
-    dps_stride = (dps_layout.slow_bytes + 255) & ~(size_t)255;
+    dpp = plan_dp_serve(ctx, (int)rs->max_len, n_segs, al->opt);
     dpg_ok = dpg_setup(al->opt, dpg_base) && !sw.no_dp_group;
     use_dp_service = !sw.no_dp_service;
     if (use_dp_service) {
@@ -345,8 +391,8 @@ void AlignStage::plan_tier0() {
         al->dp_slot_pairs.ensure((size_t)n_items);
         al->dp_list_a.ensure((size_t)n_items);
         al->dp_list_b.ensure((size_t)n_items);
-        al->slow.ensure(dp_stride * (size_t)dp_max_grid);
-        al->slow2.ensure(dps_stride * (size_t)dps_max_grid);
+        al->slow.ensure(dpp.dp_stride * (size_t)dpp.dp_max_grid);
+        al->slow2.ensure(dpp.dps_stride * (size_t)dpp.dps_max_grid);
         if (!sw.no_mv_handover)
             al->mv_handover.ensure((size_t)std::min<int64_t>(std::min<int64_t>(n_items, UINT32_MAX - 1), 131072) * ((size_t)tpp_layout.caps.max_mini + 1u));
     }
@@ -515,8 +561,6 @@ void AlignStage::launch_tpp(const AlignArgs& T, int round, int64_t n_work, const
 // One DP service round over the slots `cur` (nullptr: 0 .. n_dp-1): the grouped service, what it left, the wave service
 // for that (or nothing, or the left-overs refused), then the replay of the pairs, which lists the slots that post again
 // in `next`.
-// k_align_dp_serve reads, beyond the base: dp_req_base / dp_res_base, layout, slow_base / slow_stride, n_items, worklist,
-// dp_class, dp_small_qlen / dp_small_tlen / dp_small_tb, and dp_left (null: it always looks at every entry).
 void AlignStage::dp_round(const AlignArgs& T, int round, int64_t n_dp, const uint32_t* cur, uint32_t* next) {
     if (sw.dp_hist) print_dp_requests(round, n_dp);
     bool wave_service = true;
@@ -550,25 +594,11 @@ void AlignStage::dp_round(const AlignArgs& T, int round, int64_t n_dp, const uin
         }
     }
     if (wave_service) {
-        const bool two_class = !sw.dp_one_class;
         AlignArgs A = base;
         A.dp_req_base = al->dp_req.p; A.dp_res_base = al->dp_res.p;
         A.n_items = n_dp;
         A.worklist = cur;
-        A.dp_small_qlen = kSmallQlen; A.dp_small_tlen = kSmallTlen;
-        A.dp_small_tb = (uint32_t)dps_layout.tb_cap;
-        A.layout = dp_layout;
-        A.slow_stride = dp_stride;
-        A.slow_base = al->slow.p;
-        A.dp_class = two_class ? 2 : 0;
-        hipLaunchKernelGGL(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(dp_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), dp_lds, stream, A);
-        if (two_class) {
-            A.layout = dps_layout;
-            A.slow_stride = dps_stride;
-            A.slow_base = al->slow2.p;
-            A.dp_class = 1;
-            hipLaunchKernelGGL(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(dps_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), dps_lds, stream, A);
-        }
+        launch_dp_serve(A, dpp, !sw.dp_one_class, al->slow.p, al->slow2.p, stream);
     }
     PMX_HIP(hipGetLastError());
     if (dpg_ok && sw.dpg_shadow) compare_dpg_shadow(round, n_dp);
@@ -806,3 +836,150 @@ int pmx::align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs
     return PMX_OK;
     PMX_CATCH
 }
+
+// pmx_align_dp_probe (include/panmap_amd.h): a chosen DP path on the caller's requests
+namespace pmx {
+int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, int n_segs, int no_rows_dp, int no_dp_fast, const uint8_t* seqs,
+                   const int64_t* q_off, const int64_t* t_off, int64_t n, const int32_t* w, const int32_t* zdrop, const int32_t* end_bonus,
+                   const int32_t* flag, pmx_dp_probe_result* out, uint32_t* cigar_arena, int64_t arena_cap, pmx_dp_probe_caps* caps) {
+    const hipStream_t stream = ctx->stream;
+    const bool serve = path == PMX_DP_PROBE_SERVE || path == PMX_DP_PROBE_SERVE_ONE_CLASS;
+    memset(caps, 0, 2 * sizeof(*caps));
+    auto set_caps = [](pmx_dp_probe_caps& c, const Layout& L, int max_cigar) {
+        c.max_qlen = L.caps.max_qlen; c.max_tlen = L.caps.max_tlen; c.max_cigar = max_cigar;
+        c.tb_cap = (int64_t)L.tb_cap; c.tb_fast_cap = (int64_t)L.tb_fast_cap;
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        memset(&out[i], 0, sizeof(out[i]));
+        if (q_off[i + 1] < q_off[i] || t_off[i + 1] < t_off[i]) return fail(PMX_ERR_ARG, "pmx_align_dp_probe: descending offsets");
+    }
+    int64_t used = 0;
+    if (serve) {
+        const DpServePlan P = plan_dp_serve(ctx, max_read_len, n_segs, al->opt);
+        const bool class2_fits = P.dp_max_grid > 0;   // (else: its arrays exceed the LDS of a CU, nothing of that class can run: capacities 0)
+        if (class2_fits) set_caps(caps[0], P.dp_layout, std::min<int>(P.dp_layout.caps.max_cigar, PMX_DP_MAX_CIGAR));
+        else caps[0].max_cigar = PMX_DP_MAX_CIGAR;
+        set_caps(caps[1], P.dps_layout, std::min<int>(P.dps_layout.caps.max_cigar, PMX_DP_MAX_CIGAR));
+        if (n == 0) return PMX_OK;
+        if (n > (int64_t)(UINT32_MAX / PMX_DP_REQ_PER_PASS) - 1) return fail(PMX_ERR_CAPACITY, "pmx_align_dp_probe: too many requests");
+        if (P.dps_lds > 160 * 1024) return fail(PMX_ERR_CAPACITY, "pmx_align_dp_probe: reads too long for the LDS work arena");
+        const bool two_class = path == PMX_DP_PROBE_SERVE;
+        std::vector<DpReq> req((size_t)n * PMX_DP_REQ_PER_PASS);
+        for (int64_t i = 0; i < n; ++i) {
+            for (int j = 0; j < PMX_DP_REQ_PER_PASS; ++j) req[(size_t)i * PMX_DP_REQ_PER_PASS + j].call = 0xffffffffu;
+            DpReq& r = req[(size_t)i * PMX_DP_REQ_PER_PASS];
+            const int64_t ql = q_off[i + 1] - q_off[i], tl = t_off[i + 1] - t_off[i];
+            if (ql < 1 || tl < 1 || ((ql + 15) & ~(int64_t)15) + tl > PMX_DP_SEQ_BYTES) continue;   // cannot be posted
+            // the pairs that post requests hold reads of at most max_read_len bases: a query beyond the class's capacity (the
+            // off[] arrays are sized by it) is refused here
+            const bool small = two_class && ql <= DpServePlan::kSmallQlen && tl <= DpServePlan::kSmallTlen &&
+                               dp_request_tb_bytes((int)ql, (int)tl, w[i]) <= P.dps_layout.tb_cap;
+            if (!small && (!class2_fits || ql > P.dp_layout.caps.max_qlen)) continue;
+            r.qlen = (int32_t)ql; r.tlen = (int32_t)tl;
+            r.w = w[i]; r.zdrop = zdrop[i]; r.end_bonus = end_bonus[i]; r.flag = flag[i];
+            r.key = (uint32_t)i;
+            r.call = 0;
+            memset(r.seq, 0, sizeof(r.seq));
+            memcpy(r.seq, seqs + q_off[i], (size_t)ql);
+            memcpy(r.seq + ((ql + 15) & ~(int64_t)15), seqs + t_off[i], (size_t)tl);
+        }
+        DevBuf<uint8_t> d_req, slow, slow2;
+        DevBuf<DpRes> d_res;
+        d_req.alloc(req.size() * sizeof(DpReq));
+        d_res.alloc((size_t)n * PMX_DP_MAX_CALLS);
+        const int64_t g0 = std::min<int64_t>(P.dp_max_grid, n * PMX_DP_REQ_PER_PASS), g1 = std::min<int64_t>(P.dps_max_grid, n * PMX_DP_REQ_PER_PASS);
+        slow.alloc(P.dp_stride * (size_t)std::max<int64_t>(g0, 1));
+        slow2.alloc(P.dps_stride * (size_t)g1);
+        PMX_HIP(hipMemcpyAsync(d_req.p, req.data(), req.size() * sizeof(DpReq), hipMemcpyHostToDevice, stream));
+        PMX_HIP(hipMemsetAsync(d_res.p, 0xff, sizeof(DpRes) * (size_t)n * PMX_DP_MAX_CALLS, stream));
+        const size_t lds_max = std::max(class2_fits ? P.dp_lds : 0, P.dps_lds);
+        if (lds_max > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_align_dp_serve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        AlignArgs A{};
+        A.opt = al->opt;
+        A.no_rows_dp = no_rows_dp ? 1 : 0;
+        A.dp_req_base = d_req.p; A.dp_res_base = d_res.p;
+        A.n_items = n;
+        launch_dp_serve(A, P, two_class, slow.p, slow2.p, stream);
+        PMX_HIP(hipGetLastError());
+        std::vector<DpRes> res((size_t)n * PMX_DP_MAX_CALLS);
+        PMX_HIP(hipMemcpyAsync(res.data(), d_res.p, res.size() * sizeof(DpRes), hipMemcpyDeviceToHost, stream));
+        PMX_HIP(hipMemcpyAsync(req.data(), d_req.p, req.size() * sizeof(DpReq), hipMemcpyDeviceToHost, stream));   // (a served entry holds its PMX_DPP_* code)
+        PMX_HIP(hipStreamSynchronize(stream));
+        for (int64_t i = 0; i < n; ++i) {
+            const DpRes& R = res[(size_t)i * PMX_DP_MAX_CALLS];
+            const DpReq& r = req[(size_t)i * PMX_DP_REQ_PER_PASS];
+            pmx_dp_probe_result& o = out[i];
+            if (r.key == (uint32_t)i && r.call == 0xffffffffu && r.qlen > 0) o.path_taken = r.flag;   // ran (even when the result overflowed)
+            if (R.key != (uint32_t)i) continue;
+            if (R.ez.n_cigar < 0 || R.ez.n_cigar > PMX_DP_MAX_CIGAR) continue;
+            if (used + R.ez.n_cigar > arena_cap) return fail(PMX_ERR_CAPACITY, "pmx_align_dp_probe: CIGAR arena too small");
+            o.served = 1;
+            o.max = R.ez.max; o.zdropped = R.ez.zdropped; o.max_q = R.ez.max_q; o.max_t = R.ez.max_t; o.mqe = R.ez.mqe; o.mqe_t = R.ez.mqe_t;
+            o.mte = R.ez.mte; o.mte_q = R.ez.mte_q; o.score = R.ez.score; o.n_cigar = R.ez.n_cigar; o.reach_end = R.ez.reach_end;
+            o.cigar_off = used;
+            for (int k = 0; k < R.ez.n_cigar; ++k) cigar_arena[used + k] = R.cigar[k];
+            used += R.ez.n_cigar;
+        }
+        return PMX_OK;
+    }
+    const Layout L = path == PMX_DP_PROBE_WAVE_GENERAL ? plan_general_layout(max_read_len, n_segs, al->opt)
+                                                       : plan_long_reads_layout(max_read_len, n_segs, al->opt, no_dp_fast != 0);
+    set_caps(caps[0], L, L.caps.max_cigar);
+    if (n == 0) return PMX_OK;
+    const size_t lds_bytes = PMX_ALIGN_WORK_BYTES + L.fast_bytes + 16;
+    if (lds_bytes > 160 * 1024) return fail(PMX_ERR_CAPACITY, "pmx_align_dp_probe: reads too long for the LDS work arena");
+    if (lds_bytes > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_align_dp_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    const int64_t total = std::max<int64_t>(q_off[n], t_off[n]);
+    DpProbeArgs A{};
+    DevBuf<uint8_t> d_seqs, slab;
+    DevBuf<int64_t> d_off;
+    DevBuf<int32_t> d_par;
+    DevBuf<DpProbeOut> d_out;
+    DevBuf<uint32_t> d_cig;
+    const int64_t grid = std::min<int64_t>(n, 128);   // (a long-read slab is ~8 MB per wave and more with the full traceback)
+    A.slow_stride = (L.slow_bytes + 255) & ~(size_t)255;
+    d_seqs.alloc((size_t)total);
+    d_off.alloc((size_t)(2 * (n + 1)));
+    d_par.alloc((size_t)(4 * n));
+    d_out.alloc((size_t)n);
+    d_cig.alloc((size_t)n * (size_t)L.caps.max_cigar);
+    slab.alloc(A.slow_stride * (size_t)grid);
+    PMX_HIP(hipMemcpyAsync(d_seqs.p, seqs, (size_t)total, hipMemcpyHostToDevice, stream));
+    PMX_HIP(hipMemcpyAsync(d_off.p, q_off, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, stream));
+    PMX_HIP(hipMemcpyAsync(d_off.p + (n + 1), t_off, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, stream));
+    const int32_t* par[4] = {w, zdrop, end_bonus, flag};
+    for (int k = 0; k < 4; ++k) PMX_HIP(hipMemcpyAsync(d_par.p + (size_t)k * n, par[k], sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, stream));
+    PMX_HIP(hipMemsetAsync(d_out.p, 0, sizeof(DpProbeOut) * (size_t)n, stream));
+    A.seqs = d_seqs.p; A.q_off = d_off.p; A.t_off = d_off.p + (n + 1);
+    A.w = d_par.p; A.zdrop = d_par.p + n; A.end_bonus = d_par.p + 2 * n; A.flag = d_par.p + 3 * n;
+    A.n = n;
+    A.out = d_out.p; A.cigars = d_cig.p;
+    A.sw_ll = path == PMX_DP_PROBE_SW_LL ? 1 : 0;
+    A.no_rows_dp = no_rows_dp ? 1 : 0;
+    A.opt = al->opt;
+    A.layout = L;
+    A.slow_base = slab.p;
+    hipLaunchKernelGGL(k_align_dp_probe, dim3((unsigned)grid), dim3(64), lds_bytes, stream, A);
+    PMX_HIP(hipGetLastError());
+    std::vector<DpProbeOut> res((size_t)n);
+    std::vector<uint32_t> cig((size_t)n * (size_t)L.caps.max_cigar);
+    PMX_HIP(hipMemcpyAsync(res.data(), d_out.p, sizeof(DpProbeOut) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    PMX_HIP(hipMemcpyAsync(cig.data(), d_cig.p, sizeof(uint32_t) * cig.size(), hipMemcpyDeviceToHost, stream));
+    PMX_HIP(hipStreamSynchronize(stream));
+    for (int64_t i = 0; i < n; ++i) {
+        const DpProbeOut& R = res[(size_t)i];
+        pmx_dp_probe_result& o = out[i];
+        o.path_taken = R.path;
+        o.ok = R.ok; o.qe = R.qe; o.te = R.te;
+        if (!R.served) continue;
+        if (used + R.ez.n_cigar > arena_cap) return fail(PMX_ERR_CAPACITY, "pmx_align_dp_probe: CIGAR arena too small");
+        o.served = 1;
+        o.max = R.ez.max; o.zdropped = R.ez.zdropped; o.max_q = R.ez.max_q; o.max_t = R.ez.max_t; o.mqe = R.ez.mqe; o.mqe_t = R.ez.mqe_t;
+        o.mte = R.ez.mte; o.mte_q = R.ez.mte_q; o.score = R.ez.score; o.n_cigar = R.ez.n_cigar; o.reach_end = R.ez.reach_end;
+        o.cigar_off = used;
+        for (int k = 0; k < R.ez.n_cigar; ++k) cigar_arena[used + k] = cig[(size_t)i * (size_t)L.caps.max_cigar + k];
+        used += R.ez.n_cigar;
+    }
+    return PMX_OK;
+}
+}  // namespace pmx

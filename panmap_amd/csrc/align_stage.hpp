@@ -89,6 +89,26 @@ int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int
 bool dpg_setup(const aln::Opt& o, aln::DpgArgs& DG);
 void dpg_launch(pmx_ctx* ctx, pmx_aligner* al, aln::DpgArgs& DG, int64_t n_slots, const uint32_t* worklist, int waves_per_cu, bool serve);
 
+// align_stage.hip: the wave DP service (k_align_dp_serve), its two classes: everything else (dp) / register DP (dps).  One
+// planner and one launch function for AlignStage::dp_round and pmx_align_dp_probe.
+struct DpServePlan {
+    static constexpr int kSmallQlen = 192, kSmallTlen = 192;   // the small class (ksw_extd2_reg<3>: up to three target columns per lane)
+    aln::Layout dp_layout, dps_layout;
+    size_t dp_lds = 0, dp_stride = 0, dps_lds = 0, dps_stride = 0;
+    int64_t dp_max_grid = 0, dps_max_grid = 0;
+};
+DpServePlan plan_dp_serve(const pmx_ctx* ctx, int max_read_len, int n_segs, const aln::Opt& o);
+// A: the base arguments with dp_req_base / dp_res_base / n_items / worklist set; slow / slow2: the two classes' slabs
+// (dp_stride x grid, dps_stride x grid bytes).  two_class false: one launch with dp_class = 0.
+void launch_dp_serve(aln::AlignArgs A, const DpServePlan& P, bool two_class, uint8_t* slow, uint8_t* slow2, hipStream_t stream);
+// the layouts of the wave-per-read launches: AlignStage::setup's `general`, AlignStage::long_reads' first launch
+aln::Layout plan_general_layout(int max_read_len, int n_segs, const aln::Opt& o);
+aln::Layout plan_long_reads_layout(int max_read_len, int n_segs, const aln::Opt& o, bool no_dp_fast);
+// align_stage.hip: pmx_align_dp_probe behind its argument checks (include/panmap_amd.h)
+int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, int n_segs, int no_rows_dp, int no_dp_fast, const uint8_t* seqs,
+                   const int64_t* q_off, const int64_t* t_off, int64_t n, const int32_t* w, const int32_t* zdrop, const int32_t* end_bonus,
+                   const int32_t* flag, pmx_dp_probe_result* out, uint32_t* cigar_arena, int64_t arena_cap, pmx_dp_probe_caps* caps);
+
 // align_pairs.hip (readset_pair_order / readset_pair_map: readset.hpp)
 // pair order by mate 1's locality key alone: the even reads of the read order, halved -> al->pp_idx2
 const uint32_t* pair_order_mate1(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* read_order);

@@ -426,6 +426,24 @@ int pmx_align_dp_batch(pmx_ctx* ctx, pmx_aligner* al, const uint8_t* seqs, const
     PMX_CATCH
 }
 
+static_assert(PMX_DP_PATH_REG == PMX_DPP_REG && PMX_DP_PATH_ROWS == PMX_DPP_ROWS && PMX_DP_PATH_DIAG == PMX_DPP_DIAG && PMX_DP_PATH_KIND == PMX_DPP_KIND &&
+                  PMX_DP_PATH_EXACT == PMX_DPP_EXACT && PMX_DP_PATH_FAST == PMX_DPP_FAST && PMX_DP_PATH_TB_LDS == PMX_DPP_TB_LDS &&
+                  PMX_DP_PATH_ALL_LDS == PMX_DPP_ALL_LDS, "path codes of the public header");
+
+int pmx_align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, int n_segs, int no_rows_dp, int no_dp_fast, const uint8_t* seqs,
+                       const int64_t* q_off, const int64_t* t_off, int64_t n, const int32_t* w, const int32_t* zdrop, const int32_t* end_bonus,
+                       const int32_t* flag, pmx_dp_probe_result* out, uint32_t* cigar_arena, int64_t arena_cap, pmx_dp_probe_caps caps[2]) {
+    if (!ctx || !al || !caps || n < 0 || path < PMX_DP_PROBE_SERVE || path > PMX_DP_PROBE_SW_LL || max_read_len < 1 || max_read_len > (1 << 20) ||
+        n_segs < 1 || n_segs > 2 || arena_cap < 0)
+        return PMX_ERR_ARG;
+    if (n > 0 && (!seqs || !q_off || !t_off || !w || !zdrop || !end_bonus || !flag || !out || (arena_cap > 0 && !cigar_arena))) return PMX_ERR_ARG;
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    return align_dp_probe(ctx, al, path, max_read_len, n_segs, no_rows_dp, no_dp_fast, seqs, q_off, t_off, n, w, zdrop, end_bonus, flag, out, cigar_arena,
+                          arena_cap, caps);
+    PMX_CATCH
+}
+
 // The download of pmx_align_fetch on a stream of the caller's choice, without waiting for it: the copies start when the
 // results are complete (event on the context's stream) and the next pmx_align_readset on this aligner waits for them
 // before it overwrites the buffers.  The caller synchronises `stream` before it reads the host buffers (pinned memory, or
