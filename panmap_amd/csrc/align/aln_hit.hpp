@@ -93,7 +93,7 @@ PMX_HDN int gen_regs(Work& W, uint32_t hash, int qlen, int n_u, Ptr<const uint64
     PMX_LDS(&W); PMX_LDS(u); PMX_LDS(a); PMX_LDS(r);
     if (n_u == 0) return 0;
     if (n_u > W.caps.max_reg) { W.status |= PMX_ST_OVERFLOW; n_u = W.caps.max_reg; }
-    if (n_u > 64) { W.status |= PMX_ST_UNSUPPORTED; n_u = 64; }   // beyond the stable regime of the reference's sorter
+    if (n_u > 64) { W.status |= PMX_ST_UNSUPPORTED; PMX_UNSUPPORTED_AT(PMX_US_HIT_CHAINS); n_u = 64; }   // beyond the stable regime of the reference's sorter
     // order keys and anchor offsets, kept in the region slots' own `hash` / `as` / `cnt` / `score` fields until ranked:
     // the final records are written through a second pass so that nothing is overwritten before it is read
     Ptr<A128> key = W.aux128; PMX_LDS(key);   // x = order key, y = first anchor << 32 | anchors
@@ -365,7 +365,7 @@ PMX_HDN void hit_sort(Work& W, int* n_regs, Reg* r) {
     PMX_LDS(&W); PMX_LDS(r);
     const int n = *n_regs;
     if (n <= 1) return;
-    if (n > 64) { W.status |= PMX_ST_UNSUPPORTED; return; }
+    if (n > 64) { W.status |= PMX_ST_UNSUPPORTED; PMX_UNSUPPORTED_AT(PMX_US_HIT_REGS); return; }
     Reg* t = W.reg_tmp; PMX_LDS(t);
     auto listed = [&](int i) { return r[i].inv || r[i].cnt > 0; };
     auto key_of = [&](int i) { return (uint64_t)(int64_t)(r[i].has_p ? r[i].dp_max : r[i].score) << 32 | r[i].hash; };
@@ -479,6 +479,7 @@ PMX_HDN void set_mapq(const RefIndex& ri, int n_regs, Reg* regs, int min_chain_s
         const bool tables_ok = !(r.has_p && (r.dp_max < 0 || r.dp_max >= ri.n_logf)) && r.score >= 0 && r.score < ri.n_logf && r.n_sub + 1 < ri.n_logf;
         if (!tables_ok) {   // outside the host logf tables
             *status |= PMX_ST_UNSUPPORTED;
+            PMX_UNSUPPORTED_AT(PMX_US_MAPQ_LOGF);
             r.mapq = 0;
             continue;
         }

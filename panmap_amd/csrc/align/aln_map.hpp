@@ -66,7 +66,7 @@ PMX_HDN void pair_hits(Work& W, const RefIndex& ri, int max_gap_ref, int pe_bonu
         const Reg& r = reg_of(e);
         return (uint64_t)(uint32_t)r.rid << 32 | (uint32_t)(r.rs << 1) | (uint32_t)(mate_of(e) ^ r.rev);
     };
-    if (n_ends > 64) { W.status |= PMX_ST_UNSUPPORTED; return; }
+    if (n_ends > 64) { W.status |= PMX_ST_UNSUPPORTED; PMX_UNSUPPORTED_AT(PMX_US_PAIR_ENDS); return; }
     // a pair must reach the two best single scores minus the bonus
     int floor_dp = -pe_bonus;
     for (int m = 0; m < 2; ++m) {
@@ -160,7 +160,7 @@ PMX_HDN void pair_hits(Work& W, const RefIndex& ri, int max_gap_ref, int pe_bonu
         if (n_pairs > 1) {
             int close = 0;                // pairs within sub_diff of the best (the best included)
             for (int i = 0; i < n_pairs; ++i) close += hi_scores[i] + (uint64_t)sub_diff >= (uint64_t)best_hi;
-            if (close >= ri.n_logf) { W.status |= PMX_ST_UNSUPPORTED; close = ri.n_logf - 1; }
+            if (close >= ri.n_logf) { W.status |= PMX_ST_UNSUPPORTED; PMX_UNSUPPORTED_AT(PMX_US_PAIR_LOGF); close = ri.n_logf - 1; }
             const int by_margin = (int)(6.02f * (float)((best >> 32) - (second >> 32)) / match_sc - 4.343f * ri.logf_int[close]);
             pe_q = pe_q < by_margin ? pe_q : by_margin;
         }

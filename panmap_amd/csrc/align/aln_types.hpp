@@ -363,6 +363,16 @@ struct Ez {             // ksw_extz_t (ksw2.h:27-36)
 // status bits reported per record
 #define PMX_ST_OVERFLOW 0x1
 #define PMX_ST_UNSUPPORTED 0x2
+// the short-read sites that set it, numbered for the CPU unit-test build's per-site counters (nothing in the kernels)
+#ifndef PMX_UNSUPPORTED_AT
+#define PMX_UNSUPPORTED_AT(site) ((void)0)
+#endif
+#define PMX_US_PAIR_ENDS 0     // pairing: more than 64 regions of the two mates together
+#define PMX_US_PAIR_LOGF 1     // pairing: a count outside the logf table
+#define PMX_US_HIT_CHAINS 2    // more than 64 chains to sort
+#define PMX_US_HIT_REGS 3      // more than 64 regions of one mate
+#define PMX_US_MAPQ_LOGF 4     // mapping quality: a score outside the logf table
+#define PMX_US_SITES 5
 #define PMX_ST_NEED_WAVE 0x4   // thread-per-pair kernel: hand this pair to the wave-per-pair kernels
 #define PMX_ST_NEED_DP 0x8     // thread-per-pair kernel: a DP request was posted; re-run once it is served
 #define PMX_ST_ABORT (PMX_ST_NEED_WAVE | PMX_ST_NEED_DP)

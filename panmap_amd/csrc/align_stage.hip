@@ -232,7 +232,7 @@ bool AlignStage::setup(int revcomp_mate2, uint64_t cigar_cap) {
     PMX_HIP(hipMemsetAsync(al->stats.p, 0, 4 * sizeof(unsigned long long), stream));
     al->dd_count.ensure(4);   // distinct-pair map: [0] representatives, [1] copies of an arena-overflowed representative, [2] copies of bails
     PMX_HIP(hipMemsetAsync(al->dd_count.p, 0, 4 * sizeof(unsigned long long), stream));
-    al->last_dp_slots = 0; al->last_compact = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
+    al->last_dp_slots = 0; al->last_compact = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_huge = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
     memset(&al->last_stats, 0, sizeof(al->last_stats));
     if (n_items <= 0) return false;
     al->last_stats.n_items = n_items;
@@ -332,6 +332,7 @@ void AlignStage::wave_tiers(int64_t n_t1, const uint32_t* t1_list) {
         launch_wave(base, kern, general, n_retry, al->retry_list.p, al->retry_list2.p, al->slow2);
         int64_t n_huge = 0;
         read_counts(n_huge, unused, true);
+        al->last_huge += n_huge;
         if (n_huge > 0) {
             const Layout huge = hooked(plan_layout((int)rs->max_len, n_segs, al->opt, sw.lds_budget, 0, 16));
             launch_wave(base, kern, huge, n_huge, al->retry_list2.p, nullptr, al->slow2, 64);

@@ -51,7 +51,7 @@ struct pmx_aligner {
     int last_dp_rounds = 0;
     pmx::DevBuf<uint32_t> retry_list;
     pmx::DevBuf<unsigned long long> retry_count;
-    int64_t last_retry = 0, last_tpp_retry = 0;
+    int64_t last_retry = 0, last_tpp_retry = 0, last_huge = 0;
     pmx::DevBuf<unsigned long long> prof;
     pmx::DevBuf<unsigned long long> stats;   // AlignArgs::stats
     pmx::DevBuf<unsigned long long> dd_count;   // distinct-pair map counters (align_readset_once)

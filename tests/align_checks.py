@@ -160,6 +160,139 @@ def inverted_repeat_case(pmx, genome: bytes, n: int, seed: int, copy_div: float,
     return ref, reads
 
 
+_COMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def _revcomp(s: bytes) -> bytes:
+    return s.translate(_COMP)[::-1]
+
+
+def _substitute(rng, s: bytes, rate: float) -> bytes:
+    """every base with probability `rate` replaced by one of the three other bases"""
+    a = np.frombuffer(s, np.uint8).copy()
+    hit = np.nonzero(rng.random(len(a)) < rate)[0]
+    if len(hit):
+        code = np.zeros(256, np.uint8)
+        code[list(b"ACGT")] = range(4)
+        a[hit] = np.frombuffer(b"ACGT", np.uint8)[(code[a[hit]] + rng.integers(1, 4, len(hit))) % 4]
+    return a.tobytes()
+
+
+def repeat_reference(genome: bytes, seed=1, base_len=12000):
+    """-> (reference, families): a stretch of a repeat-free genome followed by repeat families, what short pairs need to
+    have several candidate loci per mate (mapq < 60, secondaries, pairing among candidates, improper pairs) and, for the
+    high-copy family, more anchors than one general layout of the wave tiers holds.  `families`: name -> list of [start, end)
+    intervals on the reference (one per copy; lowcx: the (AT)x100 run and the Ax80 run).  No product code; one generator."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+
+    def rand(n):
+        return np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, n)].tobytes()
+    base = genome[1000:1000 + base_len]
+    parts, families = [base], {}
+    pos = len(base)
+
+    def put(name, piece, is_copy=True):
+        nonlocal pos
+        if is_copy:
+            families.setdefault(name, []).append((pos, pos + len(piece)))
+        parts.append(piece)
+        pos += len(piece)
+    put("exact_dup", base[2000:2800])
+    put("", rand(300), False)
+    put("div_dup", _substitute(rng, base[4000:5000], 0.02))
+    put("", rand(300), False)
+    put("inv_dup", _substitute(rng, _revcomp(base[6000:6700]), 0.01))
+    put("", rand(300), False)
+    put("tandem", rand(60) * 15)
+    put("", rand(300), False)
+    unit = rand(400)
+    for j in range(3):                      # (the unit, then two copies 3 % off it; its own spacer: 250 random bases after each copy)
+        put("three_copies", unit if j == 0 else _substitute(rng, unit, 0.03))
+        put("", rand(250), False)
+    unit = rand(150)
+    for _ in range(HIGH_COPIES):            # (its own spacer: 40 random bases after each copy)
+        put("high_copy", _substitute(rng, unit, 0.01))
+        put("", rand(40), False)
+    put("lowcx", b"AT" * 100)
+    put("", rand(100), False)
+    put("lowcx", b"A" * 80)
+    put("", rand(200), False)
+    return b"".join(parts), families
+
+
+HIGH_COPIES = 30     # copies of the high_copy unit (see tests/test_align_repeats_gpu.py::test_high_copy_reaches_the_huge_layout)
+REPEAT_FAMILIES = ("exact_dup", "div_dup", "inv_dup", "tandem", "three_copies", "high_copy")   # (lowcx apart: the product withholds some of its pairs)
+
+
+def pairs_over(reference: bytes, n, seed, lo, hi, sub=0.005, read_len=150, insert=300, sd=30):
+    """n read pairs from fragments within [lo, hi) of the reference (fragment length normal(insert, sd), at least a read),
+    from either strand at random (the mates swap: read 1 is then the reverse-strand mate), `sub` substitutions per base;
+    returned in readFastqPaired orientation (mate 2 reverse-complemented), as flat [r1, r2, r1, r2, ...].  No product code."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lo, hi = max(0, lo), min(len(reference), hi)
+    assert hi - lo >= read_len
+    out = []
+    for _ in range(n):
+        flen = int(min(max(read_len, round(rng.normal(insert, sd))), hi - lo))
+        st = int(rng.integers(lo, hi - flen + 1))
+        frag = reference[st:st + flen]
+        left, right = frag[:read_len], frag[flen - read_len:]
+        r1, r2 = (_revcomp(right), _revcomp(left)) if rng.random() < 0.5 else (left, right)
+        out += [_substitute(rng, r1, sub), _substitute(rng, r2, sub)]
+    return out
+
+
+_repeat_cache = {}
+
+
+def _isolate_genome():
+    return b"".join(l.strip() for l in open(os.path.join(HERE, "golden", "isolate.ref.fa"), "rb") if not l.startswith(b">"))
+
+
+def repeat_variant(variant):
+    """'small': 12 kb base (24,830 bases: 16-bit position words in the compact tier); 'large': the whole genome as base
+    (about 41.5 kb: the 32-bit forms) -> (reference, families)"""
+    key = ("ref", variant)
+    if key not in _repeat_cache:
+        g = _isolate_genome()
+        _repeat_cache[key] = repeat_reference(g, 1, {"small": 12000, "large": len(g) - 1000}[variant])
+    return _repeat_cache[key]
+
+
+def repeat_reads(variant, name, n=None):
+    """the read sets of the repeat tests -> (reference, reads).  A family name: n pairs (default 300) over the family +- 250 bases
+    (short of lowcx);
+    'lowcx': 200 pairs over each of its two runs +- 250; 'mixed': 5/6 of n (default 1,800) over the appended families without
+    lowcx and 1/6 over the base."""
+    key = ("reads", variant, name, n)
+    if key not in _repeat_cache:
+        ref, fam = repeat_variant(variant)
+        if name == "mixed":
+            n = n or 1800
+            base_len = fam["exact_dup"][0][0]
+            reads = pairs_over(ref, n - n // 6, 11, base_len, fam["lowcx"][0][0]) + pairs_over(ref, n // 6, 12, 0, base_len)
+        elif name == "lowcx":
+            reads = []
+            for j, (s, e) in enumerate(fam["lowcx"]):
+                reads += pairs_over(ref, n or 200, 21 + j, s - 250, e + 250)
+        else:
+            # (+- 250 bases, but never into lowcx: a pair with a mate in the (AT)x100 run, 40 bases behind the last high_copy unit,
+            #  is a lowcx pair -- those are withheld by a stated limit and have their own, weaker test)
+            seed = 31 + REPEAT_FAMILIES.index(name)
+            reads = pairs_over(ref, n or 300, seed, fam[name][0][0] - 250, min(fam[name][-1][1] + 250, fam["lowcx"][0][0]))
+        _repeat_cache[key] = (ref, reads)
+    return _repeat_cache[key]
+
+
+def repeat_want(oracle, variant, name, n=None, paired=True):
+    """the reference aligner's records for repeat_reads(...), computed once per session and shared (never modified)"""
+    key = ("want", variant, name, n, paired)
+    if key not in _repeat_cache:
+        ref, reads = repeat_reads(variant, name, n)
+        _repeat_cache[key] = oracle.ref_align_reads_direct(ref, reads, paired, 8)
+    return _repeat_cache[key]
+
+
 def golden_cases(pmx):
     """(genome, {name: (reads, expected results)}) of tests/golden/align_golden.json.gz; the inputs are regenerated
     exactly as tests/golden/make_align_golden.py made them"""

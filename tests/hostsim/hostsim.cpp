@@ -11,7 +11,11 @@
 // posts a request instead of running a DP, the request is served by ksw_extd2, the pair is replayed.
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { const unsigned long long o = *p; *p += v; return o; }
 #endif
+// which of the numbered short-read sites set PMX_ST_UNSUPPORTED, and how often (printed by hs_align under `verbose`, read by hs_unsupported_counts)
+static long long pmx_us_cnt[8];
+#define PMX_UNSUPPORTED_AT(site) (++pmx_us_cnt[site])
 #include "align/aln_host.hpp"
+extern "C" void hs_unsupported_counts(long long* out, int reset) { for (int i = 0; i < PMX_US_SITES; ++i) { out[i] = pmx_us_cnt[i]; if (reset) pmx_us_cnt[i] = 0; } }
 #ifndef PMX_HOSTSIM_TPP
 // work counters of the compact tier (0: anchors, 1: anchor pairs the chain fill evaluated, 2: run skips, 3: pairs whose seeds the two-way merge ordered)
 static long long pmx_c_cnt[4];
@@ -53,7 +57,9 @@ extern "C" int hs_align(const char* ref, int64_t ref_len, int n_reads, const cha
 #else
     // long reads: like api_align.hip, DPs of up to PMX_DP_FAST_TLEN bases run on the small copy of the DP arrays (PMX_HS_DP_FAST overrides)
     const int dp_fast = getenv("PMX_HS_DP_FAST") ? atoi(getenv("PMX_HS_DP_FAST")) : (o.is_sr_like ? 0 : PMX_DP_FAST_TLEN);
-    Layout L = plan_layout(max_len, n_segs, o, (size_t)1 << 30, 0, 1, dp_fast);
+    // PMX_HS_ANCHOR_SCALE: the anchor_scale of the layout (1: the general layout of the wave tiers, 16: their last-resort one)
+    const int anchor_scale = getenv("PMX_HS_ANCHOR_SCALE") ? std::max(1, atoi(getenv("PMX_HS_ANCHOR_SCALE"))) : 1;
+    Layout L = plan_layout(max_len, n_segs, o, (size_t)1 << 30, 0, anchor_scale, dp_fast);
 #endif
     std::vector<uint8_t> fast(L.fast_bytes + 64), slow(L.slow_bytes + 64);
     Work W;
@@ -177,6 +183,9 @@ extern "C" int hs_align(const char* ref, int64_t ref_len, int n_reads, const cha
         }
     }
     *cig_used = used;
+    if (verbose)
+        fprintf(stderr, "hostsim: UNSUPPORTED set by: pair ends > 64: %lld, pair logf: %lld, chains > 64: %lld, regions > 64: %lld, mapq logf: %lld (counts since the last reset)\n",
+                pmx_us_cnt[PMX_US_PAIR_ENDS], pmx_us_cnt[PMX_US_PAIR_LOGF], pmx_us_cnt[PMX_US_HIT_CHAINS], pmx_us_cnt[PMX_US_HIT_REGS], pmx_us_cnt[PMX_US_MAPQ_LOGF]);
 #ifdef PMX_HOSTSIM_TPP
     if (verbose) fprintf(stderr, "hostsim tpp: %lld DP requests, %lld pairs to the wave tier of %d\n", (long long)n_requests, (long long)n_wave, n_items);
 #endif

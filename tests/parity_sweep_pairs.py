@@ -1,7 +1,11 @@
 """Randomized parity sweep (GPU box): read pairs of random shape -- read length, insert, error rates, indels / N, mate
 orientation, random nodes of both trees -- through the library against the compiled reference aligner (oracle/_ref).
 Not collected by pytest (minutes of GPU time); tests/test_align_gpu.py::test_varied_pair_shapes_exact keeps eight shapes.
-usage: python tests/parity_sweep_pairs.py [seed] [configs]"""
+With `repeats` as third argument the references are align_checks.repeat_reference over a random node's genome (duplications, an
+inverted copy, tandem and high-copy families; a random generator seed and base length) and the pairs align_checks.pairs_over
+of a random stretch of it short of the low-complexity runs (whose pairs the product withholds);
+tests/test_align_repeats_gpu.py keeps one such reference.
+usage: python tests/parity_sweep_pairs.py [seed] [configs] [repeats]"""
 import os, sys, numpy as np, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -13,6 +17,7 @@ pm = pmx.Panman(os.path.join(G, "sars_20000_twilight_dipper.panman"))
 rsv = pmx.Panman(os.path.join(G, "rsv_4K.panman"))
 ctx = pmx.Context(0)
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
+REPEATS = len(sys.argv) > 3 and sys.argv[3] == "repeats"
 al = None
 nbad = 0
 dump = []
@@ -28,9 +33,17 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 30):
     indel_every = int(rng.choice([0, 0, 0, 3, 9, 25]))
     as_seq = bool(rng.random() < 0.3)
     n = 8000
-    concat, off = pmx.simulate_paired_reads(g, n, read_len=read_len, seed=int(rng.integers(1, 1 << 30)), sub_rate=sub, mean_insert=max(mean_insert, float(read_len)), sd_insert=max(mean_insert / 8, 1.0))
-    reads = [bytes(concat[off[i]:off[i + 1]]) for i in range(len(off) - 1)]
-    if not as_seq:
+    if REPEATS:
+        if len(g) < 14000: continue
+        as_seq = False
+        g, fam = ac.repeat_reference(g, int(rng.integers(1, 1 << 30)), int(rng.choice([12000, len(g) - 1000])))
+        end = fam["lowcx"][0][0]
+        lo = int(rng.choice([0, fam["exact_dup"][0][0], fam["tandem"][0][0], fam["high_copy"][0][0] - 250]))
+        reads = ac.pairs_over(g, 2000, int(rng.integers(1, 1 << 30)), lo, end, sub=sub, read_len=read_len, insert=max(mean_insert, float(read_len)), sd=max(mean_insert / 8, 1.0))
+    else:
+        concat, off = pmx.simulate_paired_reads(g, n, read_len=read_len, seed=int(rng.integers(1, 1 << 30)), sub_rate=sub, mean_insert=max(mean_insert, float(read_len)), sd_insert=max(mean_insert / 8, 1.0))
+        reads = [bytes(concat[off[i]:off[i + 1]]) for i in range(len(off) - 1)]
+    if not as_seq and not REPEATS:
         reads = [r if i % 2 == 0 else pmx.reverse_complement(r) for i, r in enumerate(reads)]
     if indel_every:
         for i in range(0, len(reads), indel_every):
@@ -48,7 +61,7 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 30):
     bad = ac.compare_results(got, want)
     fl = sum(1 for x in got if x["flags"] & 3)
     st = al.stats()
-    print(it, tree is pm, node, len(g), read_len, mean_insert, sub, indel_every, as_seq, "bad", len(bad), "flagged", fl, "compact", st["compact_tier_items"], "mapped", sum(w["mapped"] for w in want), flush=True)
+    print(it, tree is pm, node, len(g), read_len, mean_insert, sub, indel_every, as_seq, "bad", len(bad), "flagged", fl, "compact", st["compact_tier_items"], "general", st["general_tier_items"], "huge", st["huge_tier_items"], "mapped", sum(w["mapped"] for w in want), flush=True)
     if bad:
         nbad += 1
         print("   first:", bad[:2])
@@ -56,7 +69,7 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 30):
         for b in bad:
             if b[0] in seen or len(seen) >= 4: continue
             seen.add(b[0])
-            dump.append(dict(tree="sars" if tree is pm else "rsv", node=node, mean=mean, pair=[reads[2 * b[0]].decode(), reads[2 * b[0] + 1].decode()], what=str(b), it=it))
+            dump.append(dict(tree="sars" if tree is pm else "rsv", node=node, reference=g.decode() if REPEATS else None, mean=mean, pair=[reads[2 * b[0]].decode(), reads[2 * b[0] + 1].decode()], what=str(b), it=it))
 print("configs with mismatches:", nbad, "time", time.time() - t0)
 import json
 json.dump(dump, open(os.path.join(ROOT, "gpurun_out", "sweep_bad.json"), "w"))
