@@ -210,6 +210,25 @@ int pmx_place_histogram_merge_device(pmx_ctx *ctx, pmx_place *pl, const void *d_
    down the tree (src/placement.cpp:242-345, 701-918) and the sequential best/tie rule (:355-401) */
 int pmx_place_score(pmx_ctx *ctx, pmx_place *pl, const pmx_place_params *pp, int64_t n_reads_total,
                     pmx_place_result *res);
+/* which path the last pmx_place_score of this object took (diagnostic: it changes no result).  A call that finds the
+   persistent launch starved (a wave gave up waiting for a flag: the grid was not resident, or a flag was withheld) is
+   redone with the level kernels and gives the same bits; `redone` is the only place where that shows. */
+enum {
+    PMX_SCORE_FORM_CHAINS = 0,       /* heavy-path chains, one persistent launch (the default) */
+    PMX_SCORE_FORM_TREE = 1,         /* flag per node, one persistent launch (PMX_PLACE_TREE_KERNEL) */
+    PMX_SCORE_FORM_LEVELS_GRAPH = 2, /* one launch per BFS level, replayed from a captured graph (PMX_PLACE_LEVEL_KERNELS) */
+    PMX_SCORE_FORM_LEVELS = 3        /* the same as plain launches (+ PMX_PLACE_NO_GRAPH) */
+};
+typedef struct {
+    int32_t form;          /* PMX_SCORE_FORM_*; -1 before the first call */
+    int32_t redone;        /* 1: the level kernels ran again after the persistent launch reported a starved grid */
+    int64_t n_chains;      /* heavy-path decomposition of pmx_place_create */
+    int64_t max_chain_len; /* nodes of its longest chain */
+    int64_t n_levels;      /* BFS levels of the tree */
+    int64_t grid_waves;    /* workgroups of the persistent launch x 4 waves; 0 for the level forms */
+    int64_t reserved[4];
+} pmx_score_info;
+int pmx_place_score_info(const pmx_place *pl, pmx_score_info *out);
 /* tied DFS indices of metric m (ascending), after pmx_place_score */
 int pmx_place_tied(const pmx_place *pl, int metric, uint32_t *out, int64_t cap);
 /* optional per-node outputs (host copies): scores [n_nodes][5] double, metrics [n_nodes][5] double,

@@ -65,6 +65,12 @@ class PlaceResult(C.Structure):
                 ("weighted_containment_den", C.c_double)]
 
 
+class ScoreInfo(C.Structure):
+    """pmx_score_info"""
+    _fields_ = [("form", C.c_int32), ("redone", C.c_int32), ("n_chains", C.c_int64), ("max_chain_len", C.c_int64),
+                ("n_levels", C.c_int64), ("grid_waves", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class ReadAlign(C.Structure):
     _fields_ = [("pos", C.c_int32), ("rs", C.c_int32), ("re", C.c_int32), ("qs", C.c_int32), ("qe", C.c_int32),
                 ("mapq", C.c_uint8), ("rev", C.c_uint8), ("proper_frag", C.c_uint8),
@@ -151,6 +157,7 @@ SIGNATURES = {
     "pmx_align_dp_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(C.c_double)]),
     "pmx_align_dp_probe": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "pmx_place_score": (_i32, [_vp, _vp, C.POINTER(PlaceParams), _i64, C.POINTER(PlaceResult)]),
+    "pmx_place_score_info": (_i32, [_vp, C.POINTER(ScoreInfo)]),
     "pmx_place_tied": (_i32, [_vp, _i32, _vp, _i64]),
     "pmx_place_node_outputs": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "pmx_place_kept_seeds": (_i64, [_vp, _vp, _vp, _vp, _i64]),

@@ -549,6 +549,16 @@ class Placer:
                                res.n_kept_seeds, res.total_seed_freq, res.min_support, res.log_read_magnitude,
                                res.log_containment_den, res.weighted_containment_den)
 
+    SCORE_FORMS = ("chains", "tree", "levels_graph", "levels")
+
+    def score_info(self) -> dict:
+        """which path the last score() took: form (one of SCORE_FORMS, None before the first call), redone (the level
+        kernels ran again after a starved persistent launch), and the sizes of the decomposition"""
+        si = _lib.ScoreInfo()
+        check(lib.pmx_place_score_info(self._h, C.byref(si)), "pmx_place_score_info")
+        return dict(form=self.SCORE_FORMS[si.form] if 0 <= si.form < len(self.SCORE_FORMS) else None, redone=int(si.redone),
+                    n_chains=int(si.n_chains), max_chain_len=int(si.max_chain_len), n_levels=int(si.n_levels), grid_waves=int(si.grid_waves))
+
     def node_outputs(self):
         n = self.n_nodes
         sc, me, ct = np.zeros((n, 5)), np.zeros((n, 5)), np.zeros((n, 2), np.int64)

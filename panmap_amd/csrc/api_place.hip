@@ -70,7 +70,10 @@ struct pmx_place {
     DevBuf<double> metrics5, scores5, scores_bfs, terms;
     DevBuf<uint32_t> chain_off, chain_nodes;   // heavy-path chains (k_score_chains), heads in BFS order
     DevBuf<uint64_t> chain_beg, chain_end;
-    int64_t n_chains = 0;
+    int64_t n_chains = 0, max_chain_len = 0;
+    // which path the last pmx_place_score took (pmx_place_score_info); form -1: no call yet
+    int32_t last_form = -1, last_redone = 0;
+    int64_t last_grid_waves = 0;
     DevBuf<uint32_t> tree_done;            // k_score_tree: epoch of the call that last finished each node; [n_nodes] = status word
     uint32_t tree_epoch = 0;
     DevBuf<uint64_t> dd_h1, dd_h2, dd_h1s, dd_key;   // --dedup scratch
@@ -581,6 +584,7 @@ int pmx_place_create(pmx_ctx* ctx, const pmx_index* idx, pmx_place** out) {
         if ((int64_t)h_chain_nodes.size() != n) throw std::runtime_error("chain decomposition does not cover the tree");
     }
     pl->n_chains = (int64_t)h_chain_off.size() - 1;
+    for (int64_t c = 0; c < pl->n_chains; ++c) pl->max_chain_len = std::max<int64_t>(pl->max_chain_len, (int64_t)h_chain_off[c + 1] - h_chain_off[c]);
     pl->chain_off.alloc(h_chain_off.size()); pl->chain_nodes.alloc((size_t)n); pl->chain_beg.alloc((size_t)n); pl->chain_end.alloc((size_t)n);
     PMX_HIP(hipMemcpyAsync(pl->chain_off.p, h_chain_off.data(), sizeof(uint32_t) * h_chain_off.size(), hipMemcpyHostToDevice, ctx->stream));
     PMX_HIP(hipMemcpyAsync(pl->chain_nodes.p, h_chain_nodes.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -1143,6 +1147,8 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
     };
     const void* sig[3] = {(const void*)t_mag, (const void*)pl->metrics5.p, (const void*)pl->term_meta.p};
     bool tree_kernel = false;
+    pl->last_redone = 0;
+    pl->last_grid_waves = 0;
     if (!pmx::opt_str(pmx::O_PLACE_LEVEL_KERNELS)) {
         // one persistent launch, parent -> child through per-node flags (k_score_tree); one workgroup per CU so that
         // every wave is resident
@@ -1157,11 +1163,15 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
         }
         if (pmx::opt_str(pmx::O_PLACE_TREE_KERNEL)) {   // per-node flags in BFS order (kept for comparison)
             const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_nodes + 3) / 4));
+            pl->last_form = PMX_SCORE_FORM_TREE;
+            pl->last_grid_waves = (int64_t)grid * 4;
             hipLaunchKernelGGL(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, t_mag, t_raw,
                                t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
                                pl->tree_done.p + pl->n_nodes);
         } else {
             const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_chains + 3) / 4));
+            pl->last_form = PMX_SCORE_FORM_CHAINS;
+            pl->last_grid_waves = (int64_t)grid * 4;
             hipLaunchKernelGGL(k_score_chains, dim3(grid), dim3(256), 0, st, pl->chain_off.p, pl->n_chains, pl->chain_nodes.p, pl->chain_beg.p,
                                pl->chain_end.p, pl->parent.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p,
                                pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
@@ -1171,8 +1181,11 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
             const uint32_t one = 1;
             PMX_HIP(hipMemcpyAsync(pl->tree_done.p + pl->n_nodes, &one, sizeof(one), hipMemcpyHostToDevice, st));
         }
-    } else if (pmx::opt_str(pmx::O_PLACE_NO_GRAPH)) launch_levels();
-    else {
+    } else if (pmx::opt_str(pmx::O_PLACE_NO_GRAPH)) {
+        pl->last_form = PMX_SCORE_FORM_LEVELS;
+        launch_levels();
+    } else {
+        pl->last_form = PMX_SCORE_FORM_LEVELS_GRAPH;
         if (!pl->level_graph_exec || pl->level_graph_sig[0] != sig[0] || pl->level_graph_sig[1] != sig[1] || pl->level_graph_sig[2] != sig[2]) {
             if (pl->level_graph_exec) { (void)hipGraphExecDestroy(pl->level_graph_exec); pl->level_graph_exec = nullptr; }
             hipGraph_t graph = nullptr;
@@ -1206,6 +1219,7 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
         PMX_HIP(hipMemsetAsync(pl->tree_done.p + pl->n_nodes, 0, sizeof(uint32_t), st));
         tree_kernel = false;
         tree_status = 0;
+        pl->last_redone = 1;
         launch_levels();
         PMX_HIP(hipGetLastError());
         finish();
@@ -1281,6 +1295,18 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
     res->weighted_containment_den = h_scal[2];
     return PMX_OK;
     PMX_CATCH
+}
+
+int pmx_place_score_info(const pmx_place* pl, pmx_score_info* out) {
+    if (!pl || !out) return PMX_ERR_ARG;
+    std::memset(out, 0, sizeof(*out));
+    out->form = pl->last_form;
+    out->redone = pl->last_redone;
+    out->n_chains = pl->n_chains;
+    out->max_chain_len = pl->max_chain_len;
+    out->n_levels = (int64_t)pl->level_off.size() - 1;
+    out->grid_waves = pl->last_grid_waves;
+    return PMX_OK;
 }
 
 int pmx_place_tied(const pmx_place* pl, int metric, uint32_t* out, int64_t cap) {

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from place_tree_checks import assert_place_matches
 
 pytestmark = pytest.mark.gpu
 
@@ -25,25 +26,7 @@ def _check_place(pmx, oracle, ctx, index, reads, params=None, k=19, s=8, l=3, op
     res = placer.score(params, len(reads))
     want = oracle.place(reads, index.arrays(), k, s, l, open_syncmer, t, params.trimStart, params.trimEnd, params.seedMaskFraction,
                         params.minReadSupport, params.forceLeaf, params.dedupReads, quals, params.minSeedQuality)
-    hh, hc = placer.histogram()
-    assert np.array_equal(hh, want["hist_hash"]), "seed set differs"
-    assert np.array_equal(hc, want["hist_count"]), "seed counts differ"
-    kh, kl = placer.kept_seeds()
-    assert np.array_equal(kh, want["kept_hash"])
-    assert np.array_equal(kl.view(np.uint64), want["kept_log"].view(np.uint64)), "log1p(count) not bit-equal"
-    st = want["state"]
-    assert res.min_support == st.min_support and res.readUniqueSeedCount == st.n_kept
-    assert res.totalReadSeedFrequency == st.total_freq and res.n_unique_seeds == st.n_unique_in
-    assert np.float64(res.readMagnitude).view(np.uint64) == np.float64(st.log_magnitude).view(np.uint64)
-    assert np.float64(res.logContainmentDenominator).view(np.uint64) == np.float64(st.log_cont_den).view(np.uint64)
-    assert np.float64(res.weightedContainmentDenominator).view(np.uint64) == np.float64(want["wc_den"]).view(np.uint64)
-    sc, met, cts = placer.node_outputs()
-    assert np.array_equal(cts, want["counts"])
-    assert np.array_equal(met.view(np.uint64), want["metrics"].view(np.uint64)), "node accumulators not bit-equal"
-    assert np.array_equal(sc.view(np.uint64), want["scores"].view(np.uint64)), "node scores not bit-equal"
-    for m in range(5):
-        assert res.best_score[m] == want["best"][m] and res.best_index[m] == want["best_idx"][m]
-        assert np.array_equal(res.tied_indices[m], want["ties"][m])
+    assert_place_matches(placer, res, want)
     placer.close()
     return res
 
