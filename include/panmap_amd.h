@@ -562,7 +562,8 @@ double pmx_read_dust(const char *seq, int64_t len, int32_t window);
  * `bcftools mpileup -Ou -B`, `bcftools call --ploidy 1 -m -A`, filters the calls (src/genotyping.cpp:167-279) and forks
  * `bcftools consensus` (src/conversion.cpp:83-255).  Here: a device pileup into integer tables, the htslib error model and
  * the reference's filter restated over those tables, and the two writers.  Substitutions only; DESIGN.md section 7 names
- * what is left out (INDEL records, BAQ, the rank-test annotations, the allele pruning of `call -m`).
+ * what is left out (INDEL records, BAQ, the allele pruning of `call -m`); mpileup's bias annotations are written on request
+ * (pmx_pileup_bias + pmx_genotype_annotate).
  *
  * pmx_pileup_* replace createMplpBcf (src/conversion.cpp:83-128).  Tables per 0-based reference position:
  *   hist[pos][q 0..63][strand 0 fwd / 1 rev][base A C G T N]  (PMX_PILEUP_HIST uint32 counters per position): the bases
@@ -607,6 +608,27 @@ int pmx_pileup_fetch(pmx_ctx *ctx, pmx_pileup *pu, uint32_t *hist, uint32_t *aux
 int pmx_pileup_read_info(const pmx_pileup *pu, uint8_t *flags, uint32_t *bam_rank, int64_t cap);
 /* algorithmic HBM bytes of the last run's two kernels (inputs read once + tables written once) */
 int64_t pmx_pileup_bytes(const pmx_pileup *pu);
+/* [hot] the bias pass: for every listed site, the histograms mpileup's rank tests read (bam2bcf.c:488-527) over exactly the
+ * bases the last pmx_pileup_run / pmx_pileup_run_records counted in hist.  PMX_PILEUP_BIAS uint32 counters per site:
+ *   [PMX_PLB_POS][is_alt][100]  position in the aligned part of the read, scaled to 0..99 (get_position, bam2bcf.c:144-193)
+ *   [PMX_PLB_SCL][is_alt][100]  15 * length of the nearest soft clip / (distance to it + 1), at most 99
+ *   [PMX_PLB_MQ ][is_alt][60]   mapping quality (255 -> 20, cap_mapq, at most 59)
+ *   [PMX_PLB_BQ ][is_alt][60]   base quality after the neighbour rule and max_baseq, at most 59
+ *   [PMX_PLB_MQS][strand][60]   mapping quality by strand of the written record (0 forward, 1 reverse)
+ * is_alt = 0 when the reference letter is A C G T (either case) and the base equals it, 1 otherwise.  positions: 0-based,
+ * strictly ascending, inside [0, ref_len); ref_bases: one letter per site; out: n_sites * PMX_PILEUP_BIAS.  The state of the
+ * last run is read on the device: after pmx_pileup_run the aligner's results and the read set must still be those of that
+ * run.  n_sites == 0 does nothing; a call before a run, an unsorted list or a position outside the reference is an error
+ * and launches nothing. */
+#define PMX_PLB_NPOS 100
+#define PMX_PLB_NQUAL 60
+#define PMX_PLB_POS 0
+#define PMX_PLB_SCL 200
+#define PMX_PLB_MQ 400
+#define PMX_PLB_BQ 520
+#define PMX_PLB_MQS 640
+#define PMX_PILEUP_BIAS 760
+int pmx_pileup_bias(pmx_ctx *ctx, pmx_pileup *pu, const int32_t *positions, const char *ref_bases, int64_t n_sites, uint32_t *out);
 
 /* pmx_genotype_* replace createVcfWithMutationMatrices / createConsensus (src/conversion.cpp:130-255) and
  * genotyping::applyMutationSpectrum / passesConsensusGate (src/genotyping.cpp:167-279).  Host; positions are few. */
@@ -631,6 +653,22 @@ typedef struct {
     int32_t reserved[3];
 } pmx_site_call;
 int pmx_genotype_site(const uint32_t *hist, char ref_base, pmx_site_call *out);
+/* the annotations `bcftools mpileup` adds to a record with an alternative, from one site's hist, aux and bias rows:
+ * calc_vdb (bam2bcf.c:596-657), calc_mwu_biasZ with do_Z = 1 (:813-864, called as :1152-1160), calc_SegBias for one
+ * sample (:891-927) and MQ0F (:1314), each as the float the reference stores.  Bit k of `present` is set when value[k] is
+ * written to the record (a HUGE_VAL result is not, :1288-1309); MQ0F always is. */
+enum { PMX_TEST_VDB = 0, PMX_TEST_SGB, PMX_TEST_RPBZ, PMX_TEST_MQBZ, PMX_TEST_MQSBZ, PMX_TEST_BQBZ, PMX_TEST_SCBZ, PMX_TEST_MQ0F, PMX_N_TESTS };
+typedef struct {
+    float value[PMX_N_TESTS];
+    uint32_t present;
+    uint32_t reserved[3];
+} pmx_site_tests;
+int pmx_genotype_site_tests(const uint32_t *hist_row, const uint32_t *aux_row, const uint32_t *bias_row, char ref_base, pmx_site_tests *out);
+/* the INFO name of test k ("VDB", "SGB", ...; NULL outside 0..PMX_N_TESTS-1), in the order a record lists them */
+const char *pmx_genotype_test_name(int k);
+/* a float as htslib's kputd prints it into a VCF (kstring.c:38-140): six significant digits, trailing zeros dropped, %g
+ * outside [0.0001, 999999].  Returns the length needed (without the NUL). */
+int64_t pmx_genotype_format_float(double v, char *out, int64_t cap);
 /* applyMutationSpectrum (src/genotyping.cpp:200-279) on one raw VCF line; phred = NULL: the plain branch of
  * createVcfWithMutationMatrices (src/conversion.cpp:163-178).  Writes the line to keep ("" = dropped) and returns its
  * length, or a negative error (a line the reference throws on). */
@@ -643,6 +681,12 @@ int64_t pmx_genotype_call(const uint32_t *hist, const uint32_t *aux, const char 
                           const double *phred16, int min_depth, double min_qual, pmx_genotyper **out);
 int64_t pmx_genotype_num_records(const pmx_genotyper *g);
 const char *pmx_genotype_record(const pmx_genotyper *g, int64_t i);   /* the VCF line without its newline */
+/* 0-based reference position of record i (-1: no such record) */
+int64_t pmx_genotype_record_pos(const pmx_genotyper *g, int64_t i);
+/* rewrites the INFO of the records at `positions` (0-based, ascending; bias: n_sites * PMX_PILEUP_BIAS from
+ * pmx_pileup_bias at the same positions) as DP;VDB;SGB;RPBZ;MQBZ;MQSBZ;BQBZ;SCBZ;MQ0F;AC;AN;DP4;MQ, absent tests left out.
+ * A position without a record is an error.  pmx_genotype_write_vcf then also writes the eight ##INFO lines. */
+int pmx_genotype_annotate(pmx_genotyper *g, const int32_t *positions, const uint32_t *bias, int64_t n_sites);
 void pmx_genotype_free(pmx_genotyper *g);
 /* `<prefix>.vcf`: header (fileformat, contig, the INFO / FORMAT fields written, #CHROM ... sample_name) + the records */
 int pmx_genotype_write_vcf(const pmx_genotyper *g, const char *path, const char *chrom, int64_t ref_len, const char *sample_name);

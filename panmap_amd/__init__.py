@@ -13,5 +13,5 @@ from .api import reload_options, describe_options  # noqa: F401
 from .api import Dist, score_reads_vs_reference, last_error, refine_top_candidates, refine_candidates, refine_placement, format_refined_tsv  # noqa: F401
 from ._lib import RefineParams  # noqa: F401
 from .synth import simulate_paired_reads, simulate_long_reads  # noqa: F401
-from .genotype import Pileup, Genotyper, PileupParams, spectrum_counts, spectrum_phred, site_call, filter_line, write_consensus  # noqa: F401
+from .genotype import Pileup, Genotyper, PileupParams, spectrum_counts, spectrum_phred, site_call, site_tests, format_float, filter_line, write_consensus  # noqa: F401
 from .synth import simulate_paired_reads_8d  # noqa: F401

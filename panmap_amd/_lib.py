@@ -236,6 +236,7 @@ SIGNATURES = {
     "pmx_pileup_fetch": (_i32, [_vp, _vp, _vp, _vp]),
     "pmx_pileup_read_info": (_i32, [_vp, _vp, _vp, _i64]),
     "pmx_pileup_bytes": (_i64, [_vp]),
+    "pmx_pileup_bias": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "pmx_genotype_spectrum_counts": (_i32, [_vp, _vp, _vp, _vp]),
     "pmx_genotype_spectrum_phred": (_i32, [_vp, _i64, _i64, _vp]),
     "pmx_genotype_site": (_i32, [_vp, C.c_char, _vp]),
@@ -244,6 +245,11 @@ SIGNATURES = {
     "pmx_genotype_num_records": (_i64, [_vp]),
     "pmx_genotype_record": (_cp, [_vp, _i64]),
     "pmx_genotype_free": (None, [_vp]),
+    "pmx_genotype_record_pos": (_i64, [_vp, _i64]),
+    "pmx_genotype_site_tests": (_i32, [_vp, _vp, _vp, C.c_char, _vp]),
+    "pmx_genotype_test_name": (_cp, [_i32]),
+    "pmx_genotype_format_float": (_i64, [C.c_double, _vp, _i64]),
+    "pmx_genotype_annotate": (_i32, [_vp, _vp, _vp, _i64]),
     "pmx_genotype_write_vcf": (_i32, [_vp, _cp, _cp, _i64, _cp]),
     "pmx_genotype_write_consensus": (_i32, [_cp, _cp, _cp, _cp]),
 }

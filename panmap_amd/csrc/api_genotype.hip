@@ -12,6 +12,8 @@
 //     list's tail sentinel, so it is dropped when max_depth or more pushed reads end at or behind its start;
 //   * overlap_push (sam.c:5969-6003): mates are reconciled when both were pushed and both are proper.
 // O(records + genome length), one pass; its product is one byte and one rank per read.
+//
+// pmx_pileup_bias runs k_pileup_bias over the device state the last run left (kept in the handle until the next run).
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -39,6 +41,13 @@ struct pmx_pileup {
     DevBuf<int64_t> off;
     std::vector<uint8_t> h_rinfo;
     std::vector<uint32_t> h_rank;
+    // pmx_pileup_bias: the arguments of the last run (its sorted starts, admit flags, reconciled qualities and late_* stay
+    // in the buffers above until the next run) and the pass's own buffers
+    PileupArgs last;
+    bool have_run = false;
+    DevBuf<int32_t> b_sites;
+    DevBuf<uint8_t> b_ref;
+    DevBuf<uint32_t> b_out;
 };
 
 namespace {
@@ -147,6 +156,7 @@ int run_core(pmx_ctx* ctx, pmx_pileup* pu, const pmx_aln_record* h_recs, int64_t
     if (paired && (n & 1)) return fail(PMX_ERR_ARG, "pileup: a paired read set has an even number of reads");
     if (pp.max_depth < 0 || pp.min_baseq < 0 || pp.delta_baseq < 0 || pp.cap_mapq < 0 || pp.cap_mapq > 63)
         return fail(PMX_ERR_ARG, "pileup: parameters out of range");
+    pu->have_run = false;
     Sweep sw;
     sweep(h_recs, n, n_words, h_off, ref_len, paired != 0, pp.max_depth, names, name_off, sw);
     const int64_t total = h_off[n] - h_off[0];
@@ -193,6 +203,8 @@ int run_core(pmx_ctx* ctx, pmx_pileup* pu, const pmx_aln_record* h_recs, int64_t
     PMX_HIP(hipStreamSynchronize(st));
     pu->h_rinfo.swap(sw.rinfo);
     pu->h_rank.swap(sw.rank);
+    pu->last = a;
+    pu->have_run = true;
     // bases + qualities read, reconciled qualities written and read back, records + CIGARs, the sweep's arrays, the tables
     pu->bytes = 4 * total + n * (int64_t)(sizeof(pmx_aln_record) + 8 + 1 + 4 + 5) + 4 * n_words + 8 * (int64_t)sw.s_rs.size() +
                 ref_len * (int64_t)(4 * PLP_CELLS + 4);
@@ -277,6 +289,38 @@ int pmx_pileup_fetch(pmx_ctx* ctx, pmx_pileup* pu, uint32_t* hist, uint32_t* aux
     if (hist) PMX_HIP(hipMemcpyAsync(hist, pu->hist.p, sizeof(uint32_t) * (size_t)pu->ref_len * PLP_HIST, hipMemcpyDeviceToHost, ctx->stream));
     if (aux) PMX_HIP(hipMemcpyAsync(aux, pu->aux.p, sizeof(uint32_t) * (size_t)pu->ref_len * PLP_AUX, hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return PMX_OK;
+    PMX_CATCH
+}
+
+int pmx_pileup_bias(pmx_ctx* ctx, pmx_pileup* pu, const int32_t* positions, const char* ref_bases, int64_t n_sites, uint32_t* out) {
+    if (!ctx || !pu || n_sites < 0) return PMX_ERR_ARG;
+    if (n_sites == 0) return PMX_OK;
+    if (!positions || !ref_bases || !out) return PMX_ERR_ARG;
+    if (!pu->have_run) return fail(PMX_ERR_ARG, "pileup bias: nothing has been run");
+    for (int64_t i = 0; i < n_sites; ++i) {
+        if (positions[i] < 0 || positions[i] >= pu->ref_len)
+            return fail(PMX_ERR_ARG, "pileup bias: position " + std::to_string(positions[i]) + " is outside the reference (length " + std::to_string(pu->ref_len) + ")");
+        if (i > 0 && positions[i] <= positions[i - 1])
+            return fail(PMX_ERR_ARG, "pileup bias: positions must be strictly ascending (entry " + std::to_string(i) + ")");
+    }
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    pu->b_sites.ensure((size_t)n_sites);
+    pu->b_ref.ensure((size_t)n_sites);
+    pu->b_out.ensure((size_t)n_sites * PLB_CELLS);
+    hipStream_t st = ctx->stream;
+    PMX_HIP(hipMemcpyAsync(pu->b_sites.p, positions, sizeof(int32_t) * (size_t)n_sites, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(pu->b_ref.p, ref_bases, (size_t)n_sites, hipMemcpyHostToDevice, st));
+    PileupBiasArgs b;
+    b.run = pu->last;
+    b.sites = pu->b_sites.p; b.ref_bases = pu->b_ref.p; b.n_sites = n_sites; b.out = pu->b_out.p;
+    timer_begin(ctx, "pileup_bias");
+    hipLaunchKernelGGL(k_pileup_bias, dim3((unsigned)std::min<int64_t>(n_sites, (int64_t)ctx->n_cu * 16)), dim3(256), 0, st, b);
+    timer_end(ctx, "pileup_bias", 1);
+    PMX_HIP(hipGetLastError());
+    PMX_HIP(hipMemcpyAsync(out, pu->b_out.p, sizeof(uint32_t) * (size_t)n_sites * PLB_CELLS, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
     return PMX_OK;
     PMX_CATCH
 }

@@ -50,6 +50,7 @@ struct Config {
     int refine_max_top_n = 150, refine_neighbor_radius = 2, refine_max_neighbor_n = 150;
     int min_depth = 1;       // --min-depth / --min-qual: the consensus gate (src/genotyping.cpp:167-174, 272)
     double min_qual = 30.0;
+    bool annotate_vcf = false;   // --annotate-vcf: mpileup's bias annotations in the INFO of the written records
 };
 
 void on_sigint(int) { _exit(130); }
@@ -71,6 +72,7 @@ void usage() {
           "  -t, --threads N            accepted (the GPU owns the parallelism)\n"
           "      --stop STAGE           index|place|align|genotype|consensus (default consensus)\n"
           "      --min-depth N          high-quality bases a call needs (default 1)     --min-qual F   lowest QUAL kept (default 30)\n"
+          "      --annotate-vcf         add VDB, SGB, RPBZ, MQBZ, MQSBZ, BQBZ, SCBZ and MQ0F to the INFO of the VCF records\n"
           "      --batch FILE           one sample per line: reads1 [reads2] [prefix]; the index stays resident\n"
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
@@ -139,6 +141,7 @@ Config parse(int argc, char** argv) {
         else if (a == "--dust") c.dust = atof(v().c_str());
         else if (a == "--min-depth") c.min_depth = atoi(v().c_str());
         else if (a == "--min-qual") c.min_qual = atof(v().c_str());
+        else if (a == "--annotate-vcf") c.annotate_vcf = true;
         else if (a == "--baq") die("--baq (base alignment quality) is not implemented in this build; the pileup runs as `mpileup -B` does");
         else if (a == "--filter-and-assign" || a == "--impute" || a == "--extent-guard" || a == "--reference-node" ||
                  a == "--dump-sequence" || a == "--dump-all-scores")
@@ -564,6 +567,18 @@ std::string run_sample(const Config& c, int stop, pmx_panman*& pm, pmx_index* id
     const int64_t n_calls = pmx_genotype_call(hist.data(), aux.data(), genome.data(), (int64_t)genome.size(), node_id.c_str(), spectrum_empty ? nullptr : phred,
                                               c.min_depth, c.min_qual, &pg.gt);
     if (n_calls < 0) die(std::string("calling variants: ") + pmx_last_error());
+    if (c.annotate_vcf && n_calls > 0) {
+        // the written records' sites go through the bias pass of the pileup that is still on the device
+        std::vector<int32_t> sites((size_t)n_calls);
+        std::string letters((size_t)n_calls, 'N');
+        for (int64_t i = 0; i < n_calls; ++i) {
+            sites[(size_t)i] = (int32_t)pmx_genotype_record_pos(pg.gt, i);
+            letters[(size_t)i] = genome[(size_t)sites[(size_t)i]];
+        }
+        std::vector<uint32_t> bias((size_t)n_calls * PMX_PILEUP_BIAS);
+        check(pmx_pileup_bias(ctx, pg.pu, sites.data(), letters.data(), n_calls, bias.data()), "pileup bias pass");
+        check(pmx_genotype_annotate(pg.gt, sites.data(), bias.data(), n_calls), "annotating the records");
+    }
     const std::string vcf = c.output + ".vcf";
     check(pmx_genotype_write_vcf(pg.gt, vcf.c_str(), node_id.c_str(), (int64_t)genome.size(), bam.c_str()), "writing the VCF");
     say(c, "call", vcf + " (" + std::to_string(n_calls) + " variants)");

@@ -7,7 +7,9 @@
 //   * allele order, PL and DP4 of a site: bcf_call_combine (src/3rdparty/bcftools/bam2bcf.c:955-1115); MQ as mcall.c:1659;
 //   * the substitution spectrum of the tree (src/index_single_mode.cpp:1408-1558) as phred (src/main.cpp:290-311);
 //   * the filter, line by line as the reference applies it.
-// Not restated: INDEL records, BAQ, the rank-test annotations and the QUAL of `call -m`.  A site is a
+//   * on request (pmx_genotype_annotate), the bias annotations of bcf_call_combine -- VDB, SGB, the five Mann-Whitney
+//     Z scores, MQ0F -- from the histograms of the device's bias pass (bam2bcf.c:596-657, 813-927, 1152-1173).
+// Not restated: INDEL records, BAQ and the QUAL of `call -m`.  A site is a
 // candidate when an alternative base has a non-zero quality sum, and its record lists every such base, as `call -m -A`
 // does (pinned to the reference's programs by tests/test_pileup_reference.py).
 #include <algorithm>
@@ -281,6 +283,150 @@ std::string plain_filter(const std::string& line, int min_depth, double min_qual
     return "";
 }
 
+// ------------------------------------------------------------------------------------------------ bias annotations
+// kf_erfc (htslib-1.20/kfunc.c:58-84): the complementary error function by the rational approximation of Hart et al.,
+// with a continued fraction in the tail.  Not libm's erfc: VDB values are printed to six digits down to 1e-37.
+double kf_erfc(double x) {
+    static const double p[7] = {220.2068679123761, 221.2135961699311, 112.0792914978709, 33.912866078383, 6.37396220353165, .7003830644436881,
+                                .03526249659989109};
+    static const double q[8] = {440.4137358247522, 793.8265125199484, 637.3336333788311, 296.5642487796737, 86.78073220294608, 16.06417757920695,
+                                1.755667163182642, .08838834764831844};
+    const double z = fabs(x) * M_SQRT2;
+    if (z > 37.) return x > 0. ? 0. : 2.;
+    const double expntl = exp(z * z * -.5);
+    double r;
+    if (z < 10. / M_SQRT2) {
+        double num = p[6], den = q[7];
+        for (int i = 5; i >= 0; --i) num = num * z + p[i];
+        for (int i = 6; i >= 0; --i) den = den * z + q[i];
+        r = expntl * num / den;
+    } else r = expntl / 2.506628274631001 / (z + 1. / (z + 2. / (z + 3. / (z + 4. / (z + .65)))));
+    return x > 0. ? 2. * r : 2. * (1. - r);
+}
+
+// calc_vdb (bam2bcf.c:596-657) over the alt bases' scaled positions: float accumulators, the truncation of the mean
+// distance and the integer division of the depth-2 branch as the reference has them.  HUGE_VAL below two bases.
+double calc_vdb(const uint32_t* pos, int npos) {
+    static const float param[15][3] = {{3, 0.079, 18},   {4, 0.09, 19.8},  {5, 0.1, 20.5},   {6, 0.11, 21.5},  {7, 0.125, 21.6},
+                                       {8, 0.135, 22},   {9, 0.14, 22.2},  {10, 0.153, 22.3}, {15, 0.19, 22.8}, {20, 0.22, 23.2},
+                                       {30, 0.26, 23.4}, {40, 0.29, 23.5}, {50, 0.35, 23.65}, {100, 0.5, 23.7}, {200, 0.7, 23.7}};
+    const int readlen = 100, nparam = 15;
+    int dp = 0;
+    float mean_pos = 0, mean_diff = 0;
+    for (int i = 0; i < npos; ++i) {
+        if (!pos[i]) continue;
+        dp += (int)pos[i];
+        mean_pos += (int)pos[i] * i;
+    }
+    if (dp < 2) return HUGE_VAL;
+    mean_pos /= dp;
+    for (int i = 0; i < npos; ++i) {
+        if (!pos[i]) continue;
+        mean_diff += (int)pos[i] * fabs((double)(i - mean_pos));   // float difference, double product, stored back into the float
+    }
+    mean_diff /= dp;
+    const int ipos = (int)mean_diff;
+    if (dp == 2) return (2 * readlen - 2 * (ipos + 1) - 1) * (ipos + 1) / (readlen - 1) / (readlen * 0.5);
+    int i = nparam;
+    if (dp < 200)
+        for (i = 0; i < nparam; ++i)
+            if (param[i][0] >= dp) break;
+    float pshift, pscale;
+    if (i == nparam) { pscale = param[nparam - 1][1]; pshift = param[nparam - 1][2]; }
+    else if (i > 0 && param[i][0] != dp) {
+        pscale = (param[i - 1][1] + param[i][1]) * 0.5;
+        pshift = (param[i - 1][2] + param[i][2]) * 0.5;
+    } else { pscale = param[i][1]; pshift = param[i][2]; }
+    return 0.5 * kf_erfc(-(mean_diff - pshift) * pscale);
+}
+
+// calc_mwu_biasZ with do_Z = 1 (bam2bcf.c:813-864): the Mann-Whitney U of a against b as a Z score with the correction for
+// ties; HUGE_VAL when either side is empty, 0 when the variance vanishes
+double mwu_z(const uint32_t* a, const uint32_t* b, int n) {
+    bool b_empty = true;
+    for (int i = 0; i < n && b_empty; ++i) b_empty = b[i] == 0;
+    int64_t t = 0, e = 0, l = 0, na = 0, nb = 0;
+    for (int i = n - 1; i >= 0; --i) {
+        const int64_t ai = a[i], bi = b_empty ? 0 : b[i];
+        e += ai * bi;
+        l += ai * nb;
+        na += ai;
+        nb += bi;
+        const int64_t pi = ai + bi;
+        t += (pi * pi - 1) * pi;
+    }
+    if (!na || !nb) return HUGE_VAL;
+    const double U = l + e * 0.5, m = na * nb / 2.0;
+    const double var2 = (na * nb) / 12.0 * ((na + nb + 1) - t / (double)((na + nb) * (na + nb - 1)));
+    if (var2 <= 0) return 0;
+    return (U - m) / sqrt(var2);
+}
+
+// calc_SegBias for one sample (bam2bcf.c:891-927): nref / nr = the reference / other bases of the site
+double seg_bias(int nref, int nr) {
+    if (!nr) return HUGE_VAL;
+    const int n = 1, avg_dp = (nref + nr) / n;
+    double M = floor((double)nr / avg_dp + 0.5);
+    if (M > n) M = n;
+    else if (M == 0) M = 1;
+    const double f = M / 2. / n, p = (double)nr / n, q = (double)nr / M, log2 = log(2.0);
+    const double x = log(2 * (1 - f)), y = log(f) + nr * log2 - q;
+    double tmp = x > y ? log(1 + exp(y - x)) + x : log(1 + exp(x - y)) + y;
+    tmp += log(f) + nr * log(q / p) - q + p;
+    return tmp;
+}
+
+void site_tests(const uint32_t* hist, const uint32_t* aux, const uint32_t* bias, char ref_base, pmx_site_tests* out) {
+    memset(out, 0, sizeof(*out));
+    const int ref4 = base_index(ref_base);
+    int64_t nref = 0, nr = 0;
+    for (int c = 0; c < HIST; ++c) (ref4 < 4 && c % NB == ref4 ? nref : nr) += hist[c];
+    const uint32_t *pos = bias + PMX_PLB_POS, *scl = bias + PMX_PLB_SCL, *mq = bias + PMX_PLB_MQ, *bq = bias + PMX_PLB_BQ, *mqs = bias + PMX_PLB_MQS;
+    const int NP = PMX_PLB_NPOS, NQL = PMX_PLB_NQUAL;
+    double v[PMX_N_TESTS];
+    v[PMX_TEST_VDB] = calc_vdb(pos + NP, NP);
+    v[PMX_TEST_SGB] = seg_bias((int)nref, (int)nr);
+    v[PMX_TEST_RPBZ] = mwu_z(pos, pos + NP, NP);
+    v[PMX_TEST_MQBZ] = mwu_z(mq, mq + NQL, NQL);
+    v[PMX_TEST_MQSBZ] = mwu_z(mqs, mqs + NQL, NQL);
+    v[PMX_TEST_BQBZ] = mwu_z(bq, bq + NQL, NQL);
+    v[PMX_TEST_SCBZ] = mwu_z(scl, scl + NP, NP);
+    for (int k = 0; k < PMX_TEST_MQ0F; ++k) {
+        out->value[k] = (float)v[k];                       // the fields of bcf_call_t are floats (bam2bcf.h:178-180)
+        if (v[k] != HUGE_VAL) out->present |= 1u << k;     // bam2bcf.c:1288-1309
+    }
+    out->value[PMX_TEST_MQ0F] = aux[0] ? (float)aux[2] / (float)aux[0] : 0.f;   // bam2bcf.c:1314
+    out->present |= 1u << PMX_TEST_MQ0F;
+}
+
+const char* const TEST_NAMES[PMX_N_TESTS] = {"VDB", "SGB", "RPBZ", "MQBZ", "MQSBZ", "BQBZ", "SCBZ", "MQ0F"};
+
+// htslib's kputd (kstring.c:38-140), the printer of every VCF float: outside [0.0001, 999999] printf's %g; inside, the
+// value scaled to a six-digit integer by rint, the decimal point put back, trailing zeros (and a bare point) dropped
+std::string format_float(double d) {
+    if (d == 0) return std::signbit(d) ? "-0" : "0";
+    std::string s;
+    if (d < 0) { s = "-"; d = -d; }
+    char buf[64];
+    if (!(d >= 0.0001 && d <= 999999)) {
+        snprintf(buf, sizeof(buf), "%g", d);
+        return s + buf;
+    }
+    static const double bound[9] = {0.001, 0.01, 0.1, 1, 10, 100, 1000, 10000, 100000};
+    static const double scale[10] = {1e9, 1e8, 1e7, 1e6, 1e5, 1e4, 1e3, 1e2, 1e1, 1};
+    int k = 0;
+    while (k < 9 && !(d < bound[k])) ++k;
+    const int decimals = 9 - k;
+    snprintf(buf, sizeof(buf), "%0*u", decimals + 1, (unsigned)(uint32_t)rint(d * scale[k]));
+    std::string digits = buf;
+    if (decimals) {
+        digits.insert(digits.size() - (size_t)decimals, ".");
+        digits.erase(digits.find_last_not_of('0') + 1);
+        if (digits.back() == '.') digits.pop_back();
+    }
+    return s + digits;
+}
+
 std::string join_ints(const int32_t* v, int n) {
     std::string s;
     for (int i = 0; i < n; ++i) { if (i) s += ","; s += std::to_string(v[i]); }
@@ -291,6 +437,11 @@ std::string join_ints(const int32_t* v, int n) {
 
 struct pmx_genotyper {
     std::vector<std::string> records;
+    // per record, for pmx_genotype_annotate: its 0-based position, reference letter and the site's hist / aux rows
+    std::vector<int64_t> pos;
+    std::vector<char> ref;
+    std::vector<uint32_t> rows;   // HIST + 4 per record
+    bool annotated = false;
 };
 
 extern "C" {
@@ -461,6 +612,10 @@ int64_t pmx_genotype_call(const uint32_t* hist, const uint32_t* aux, const char*
             // the written record is the line the reference's filter leaves: every alternative `call -m -A` keeps, one PL and
             // one AD per allele, GT the filter's allele, INFO passed through as it stood (src/genotyping.cpp:274-277)
             g->records.push_back(kept);
+            g->pos.push_back(pos);
+            g->ref.push_back(reference[pos]);
+            g->rows.insert(g->rows.end(), h, h + HIST);
+            g->rows.insert(g->rows.end(), ax, ax + 4);
         }
         const int64_t n = (int64_t)g->records.size();
         *out = g.release();
@@ -476,14 +631,77 @@ const char* pmx_genotype_record(const pmx_genotyper* g, int64_t i) {
     return g && i >= 0 && i < (int64_t)g->records.size() ? g->records[(size_t)i].c_str() : nullptr;
 }
 void pmx_genotype_free(pmx_genotyper* g) { delete g; }
+int64_t pmx_genotype_record_pos(const pmx_genotyper* g, int64_t i) { return g && i >= 0 && i < (int64_t)g->pos.size() ? g->pos[(size_t)i] : -1; }
+
+int pmx_genotype_site_tests(const uint32_t* hist_row, const uint32_t* aux_row, const uint32_t* bias_row, char ref_base, pmx_site_tests* out) {
+    if (!hist_row || !aux_row || !bias_row || !out) return PMX_ERR_ARG;
+    site_tests(hist_row, aux_row, bias_row, ref_base, out);
+    return PMX_OK;
+}
+
+const char* pmx_genotype_test_name(int k) { return k >= 0 && k < PMX_N_TESTS ? TEST_NAMES[k] : nullptr; }
+
+int64_t pmx_genotype_format_float(double v, char* out, int64_t cap) {
+    const std::string r = format_float(v);
+    if (out && cap > 0) {
+        const size_t n = std::min<size_t>(r.size(), (size_t)cap - 1);
+        memcpy(out, r.data(), n);
+        out[n] = '\0';
+    }
+    return (int64_t)r.size();
+}
+
+int pmx_genotype_annotate(pmx_genotyper* g, const int32_t* positions, const uint32_t* bias, int64_t n_sites) {
+    if (!g || n_sites < 0 || (n_sites > 0 && (!positions || !bias))) return PMX_ERR_ARG;
+    try {
+        size_t rec = 0;   // records and positions both ascend
+        for (int64_t s = 0; s < n_sites; ++s) {
+            if (s > 0 && positions[s] <= positions[s - 1]) throw std::runtime_error("annotate: positions must be strictly ascending");
+            while (rec < g->pos.size() && g->pos[rec] < positions[s]) ++rec;
+            if (rec == g->pos.size() || g->pos[rec] != positions[s]) throw std::runtime_error("annotate: no record at position " + std::to_string(positions[s]));
+            const uint32_t* row = g->rows.data() + rec * (HIST + 4);
+            pmx_site_tests t;
+            site_tests(row, row + HIST, bias + s * PMX_PILEUP_BIAS, g->ref[rec], &t);
+            std::vector<std::string> f = split(g->records[rec], '\t');
+            if (f.size() != 10) throw std::runtime_error("annotate: unexpected record");
+            // DP first, then the tests, then what the record held behind DP (AC;AN;DP4;MQ) -- the order of the reference's line
+            const size_t semi = f[7].find(';');
+            std::string info = f[7].substr(0, semi);
+            if (info.rfind("DP=", 0) != 0) throw std::runtime_error("annotate: unexpected record");
+            if (f[7].find(";MQ0F=") != std::string::npos)
+                throw std::runtime_error("annotate: record at position " + std::to_string(positions[s]) + " is annotated already");
+            for (int k = 0; k < PMX_N_TESTS; ++k)
+                if (t.present >> k & 1u) info += std::string(";") + TEST_NAMES[k] + "=" + format_float(t.value[k]);
+            if (semi != std::string::npos) info += f[7].substr(semi);
+            f[7] = info;
+            std::string line = f[0];
+            for (size_t i = 1; i < f.size(); ++i) line += "\t" + f[i];
+            g->records[rec] = line;
+        }
+        g->annotated = true;
+        return PMX_OK;
+    } catch (const std::exception& e) {
+        pmx::set_error(e.what());
+        return PMX_ERR_ARG;
+    }
+}
 
 int pmx_genotype_write_vcf(const pmx_genotyper* g, const char* path, const char* chrom, int64_t ref_len, const char* sample_name) {
     if (!g || !path || !chrom || !sample_name) return PMX_ERR_ARG;
     FILE* f = fopen(path, "w");
     if (!f) { pmx::set_error(std::string("cannot write ") + path); return PMX_ERR_IO; }
     fprintf(f, "##fileformat=VCFv4.2\n##contig=<ID=%s,length=%lld>\n", chrom, (long long)ref_len);
-    fputs("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Raw read depth\">\n"
-          "##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Allele count in genotypes for each ALT allele, in the same order as listed\">\n"
+    fputs("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Raw read depth\">\n", f);
+    if (g->annotated)   // the lines of `bcftools mpileup`, in its order
+        fputs("##INFO=<ID=VDB,Number=1,Type=Float,Description=\"Variant Distance Bias for filtering splice-site artefacts in RNA-seq data (bigger is better)\",Version=\"3\">\n"
+              "##INFO=<ID=RPBZ,Number=1,Type=Float,Description=\"Mann-Whitney U-z test of Read Position Bias (closer to 0 is better)\">\n"
+              "##INFO=<ID=MQBZ,Number=1,Type=Float,Description=\"Mann-Whitney U-z test of Mapping Quality Bias (closer to 0 is better)\">\n"
+              "##INFO=<ID=BQBZ,Number=1,Type=Float,Description=\"Mann-Whitney U-z test of Base Quality Bias (closer to 0 is better)\">\n"
+              "##INFO=<ID=MQSBZ,Number=1,Type=Float,Description=\"Mann-Whitney U-z test of Mapping Quality vs Strand Bias (closer to 0 is better)\">\n"
+              "##INFO=<ID=SCBZ,Number=1,Type=Float,Description=\"Mann-Whitney U-z test of Soft-Clip Length Bias (closer to 0 is better)\">\n"
+              "##INFO=<ID=SGB,Number=1,Type=Float,Description=\"Segregation based metric, http://samtools.github.io/bcftools/rd-SegBias.pdf\">\n"
+              "##INFO=<ID=MQ0F,Number=1,Type=Float,Description=\"Fraction of MQ0 reads (smaller is better)\">\n", f);
+    fputs("##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Allele count in genotypes for each ALT allele, in the same order as listed\">\n"
           "##INFO=<ID=AN,Number=1,Type=Integer,Description=\"Total number of alleles in called genotypes\">\n"
           "##INFO=<ID=DP4,Number=4,Type=Integer,Description=\"Number of high-quality ref-forward , ref-reverse, alt-forward and alt-reverse bases\">\n"
           "##INFO=<ID=MQ,Number=1,Type=Integer,Description=\"Average mapping quality\">\n"

@@ -46,7 +46,22 @@ struct PileupArgs {
     int32_t min_baseq, max_baseq, delta_baseq, cap_mapq;
 };
 
+// The bias pass (k_pileup_bias): the histograms the rank tests of bcf_call_combine read (bam2bcf.c:488-527), for a list of
+// sites, over the state a run left behind.  One site = PLB_CELLS counters, layout published as PMX_PLB_* (panmap_amd.h).
+constexpr int PLB_POS = PMX_PLB_POS, PLB_SCL = PMX_PLB_SCL, PLB_MQ = PMX_PLB_MQ, PLB_BQ = PMX_PLB_BQ, PLB_MQS = PMX_PLB_MQS;
+constexpr int PLB_NPOS = PMX_PLB_NPOS, PLB_NQUAL = PMX_PLB_NQUAL, PLB_CELLS = PMX_PILEUP_BIAS;
+static_assert(PLB_MQS + 2 * PLB_NQUAL == PLB_CELLS && PLB_SCL == 2 * PLB_NPOS && PLB_MQ == 4 * PLB_NPOS, "bias table layout");
+
+struct PileupBiasArgs {
+    PileupArgs run;           // the last run's arguments: its device state is read, nothing of it is written
+    const int32_t* sites;     // 0-based positions, strictly ascending, inside [0, ref_len)
+    const uint8_t* ref_bases; // the reference letter of every site
+    int64_t n_sites;
+    uint32_t* out;            // [n_sites][PLB_CELLS]
+};
+
 __global__ void k_pileup_quals(PileupArgs a);
 __global__ void k_pileup_window(PileupArgs a);
+__global__ void k_pileup_bias(PileupBiasArgs b);
 
 }  // namespace pmx

@@ -9,6 +9,10 @@
 // Two kernels:
 //   k_pileup_quals   one thread per read pair: the base qualities in BAM orientation, with htslib's reconciliation of
 //                    overlapping mates (tweak_overlap_quality, htslib-1.20/sam.c:5824-5963) applied;
+//   k_pileup_bias    a second pass for a list of sites (the records that get written): the histograms mpileup's rank tests
+//                    read -- position in the read, soft-clip length, mapping and base quality by ref/alt, mapping quality
+//                    by strand (bam2bcf.c:488-527) -- over exactly the bases the window kernel counted.  One block per
+//                    site, counters in LDS, plain stores; integers only.
 //   k_pileup_window  one block per window of PLP_WINDOW positions: the admitted reads that reach the window (a contiguous
 //                    run of the BAM order) are walked along their CIGARs, the counters accumulate in LDS, and the window is
 //                    written to global memory with plain stores -- a window has one owner, so there is no global atomic at
@@ -195,6 +199,45 @@ __device__ void reconcile(const PileupArgs& a, const ReadView& va, const ReadVie
     }
 }
 
+// The quality mpileup gives query base i of a read (bam2bcf.c:425-435): the lower of the base's reconciled quality and its
+// neighbours' + delta_baseq -- the right neighbour of base `late` as it stood before the reconciliation (k_pileup_quals) --
+// dropped (-1) below min_baseq, at most max_baseq.  This is `baseQ`; the window kernel goes on to cap it by the mapping
+// quality.  Both table kernels take a base's quality from here, so they count the same bases.
+__device__ inline int base_quality(const PileupArgs& a, const uint8_t* eq, int len, int i, int late, int late_q) {
+    int q = eq[i];
+    if (i > 0 && q > eq[i - 1] + a.delta_baseq) q = eq[i - 1] + a.delta_baseq;
+    if (i + 1 < len) {
+        const int qr = i == late ? late_q : eq[i + 1];
+        if (q > qr + a.delta_baseq) q = qr + a.delta_baseq;
+    }
+    if (q < a.min_baseq) return -1;
+    return q > a.max_baseq ? a.max_baseq : q;
+}
+
+// seq_nt16_int of the BAM code: A C G T -> 0..3, everything else 4
+__device__ inline int base4_of(int b16) { return b16 == 1 ? 0 : b16 == 2 ? 1 : b16 == 4 ? 2 : b16 == 8 ? 3 : 4; }
+
+// get_position (bam2bcf.c:144-193) and the two scalings of :493-498 for query base i of a read with soft clips c5 / c3:
+// epos = place in the aligned part scaled to 0..98, scl = 15 * nearest clip's length / (distance + 1), at most 99.  Where
+// both ends are clipped and the left clip is not the nearer one, the reference leaves the clip length unset (0).  Doubles,
+// in the reference's order of operations (the build does not contract).
+__device__ inline void read_position(int i, int len, int c5, int c3, int& epos, int& scl) {
+    const int pos = i + 1 - c5, aligned = len - c5 - c3;
+    epos = (int)((double)pos / (aligned + 1) * (PLB_NPOS - 1));
+    const int left = c5 ? i + 1 - c5 : -1, right = c3 ? len - c3 - i : -1;
+    int sc_len = 0, sc_dist = 0;
+    if (left >= 0) {
+        if (right < 0 || left < right) { sc_len = c5; sc_dist = left; }
+    } else if (right >= 0) { sc_len = c3; sc_dist = right; }
+    scl = 0;
+    if (sc_len) {
+        scl = (int)(15.0 * sc_len / (sc_dist + 1));
+        if (scl > PLB_NPOS - 1) scl = PLB_NPOS - 1;
+    }
+    epos = min(max(epos, 0), PLB_NPOS - 1);   // the reference asserts both ranges (:499-500); a counter never leaves its block
+    scl = max(scl, 0);
+}
+
 }  // namespace
 
 __global__ void k_pileup_quals(PileupArgs a) {
@@ -275,7 +318,7 @@ __global__ void __launch_bounds__(256) k_pileup_window(PileupArgs a) {
             int mapq = rec.mapq < 255 ? rec.mapq : 20;                               // DEF_MAPQ (bam2bcf.c:449)
             const bool mq0 = mapq == 0;
             if (mapq > a.cap_mapq) mapq = a.cap_mapq;
-            const int late = a.late_idx[r];
+            const int late = a.late_idx[r], late_q = a.late_q[r];
             int x = v.rs, y = 0;
             for (int ci = 0; ci < v.n_ops && x < w1; ++ci) {
                 const uint32_t c = v.op(ci);
@@ -286,20 +329,12 @@ __global__ void __launch_bounds__(256) k_pileup_window(PileupArgs a) {
                         if (i >= v.len) break;
                         uint32_t* cell = tab + (p - w0) * PLP_CELLS;
                         atomicAdd(cell + PLP_HIST + 0, 1u);   // ori_depth: every read that shows a base here (bam2bcf.c:298-308)
-                        // the lower of the base's quality and its neighbours' + delta (bam2bcf.c:425-432)
-                        int q = eq[i];
-                        if (i > 0 && q > eq[i - 1] + a.delta_baseq) q = eq[i - 1] + a.delta_baseq;
-                        if (i + 1 < v.len) {
-                            const int qr = i == late ? a.late_q[r] : eq[i + 1];
-                            if (q > qr + a.delta_baseq) q = qr + a.delta_baseq;
-                        }
-                        if (q < a.min_baseq) continue;
-                        if (q > a.max_baseq) q = a.max_baseq;
+                        int q = base_quality(a, eq, v.len, i, late, late_q);
+                        if (q < 0) continue;
                         if (q > mapq) q = mapq;               // bam2bcf.c:456-460
                         if (q > 63) q = 63;
                         if (q < 4) q = 4;
-                        const int b16 = base16(a, v, i);
-                        const int b = b16 == 1 ? 0 : b16 == 2 ? 1 : b16 == 4 ? 2 : b16 == 8 ? 3 : 4;   // seq_nt16_int
+                        const int b = base4_of(base16(a, v, i));
                         atomicAdd(cell + (q * 2 + strand) * PLP_NBASE + b, 1u);
                         atomicAdd(cell + PLP_HIST + 1, (uint32_t)mapq);
                         if (mq0) atomicAdd(cell + PLP_HIST + 2, 1u);
@@ -322,6 +357,69 @@ __global__ void __launch_bounds__(256) k_pileup_window(PileupArgs a) {
             const int p = i / PLP_AUX, c = i - p * PLP_AUX;
             a.aux[(int64_t)(w0 + p) * PLP_AUX + c] = tab[p * PLP_CELLS + PLP_HIST + c];
         }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256) k_pileup_bias(PileupBiasArgs b) {
+    __shared__ uint32_t tab[PLB_CELLS];
+    const PileupArgs& a = b.run;
+    for (int64_t s = blockIdx.x; s < b.n_sites; s += gridDim.x) {
+        const int p = b.sites[s];
+        for (int i = threadIdx.x; i < PLB_CELLS; i += blockDim.x) tab[i] = 0;
+        __syncthreads();
+        // is_diff of bam2bcf.c:438: a base is "ref" only against a reference letter A C G T
+        const int r16 = nt16_of(b.ref_bases[s]);
+        const int ref4 = base4_of(r16);
+        // the admitted reads that can reach the site: starts in [p - max_span, p] -- the window kernel's two searches
+        int64_t lo, hi;
+        {
+            const int from = p - a.max_span;
+            int64_t l = 0, h = a.n_sorted;
+            while (l < h) { const int64_t m = (l + h) >> 1; if (a.s_rs[m] < from) l = m + 1; else h = m; }
+            lo = l;
+            h = a.n_sorted;
+            while (l < h) { const int64_t m = (l + h) >> 1; if (a.s_rs[m] < p + 1) l = m + 1; else h = m; }
+            hi = l;
+        }
+        for (int64_t k = lo + threadIdx.x; k < hi; k += blockDim.x) {
+            const int64_t r = a.s_idx[k];
+            const pmx_aln_record& rec = a.recs[r];
+            if (rec.re <= p) continue;
+            const ReadView v = view_of(a, r);
+            // the query base on the site, if the read shows one there
+            int i = -1;
+            {
+                int x = v.rs, y = 0;
+                for (int ci = 0; ci < v.n_ops && x <= p; ++ci) {
+                    const uint32_t c = v.op(ci);
+                    const int op = (int)(c & 0xf), n = (int)(c >> 4);
+                    if (op == CIG_M || op == CIG_EQ || op == CIG_X) {
+                        if (p < x + n) { i = y + (p - x); break; }
+                        x += n; y += n;
+                    } else if (op == CIG_I || op == CIG_S) y += n;
+                    else if (op == CIG_D || op == CIG_N) x += n;
+                }
+            }
+            if (i < 0 || i >= v.len) continue;
+            int bq = base_quality(a, a.effq + v.off, v.len, i, a.late_idx[r], a.late_q[r]);
+            if (bq < 0) continue;
+            if (bq > PLB_NQUAL - 1) bq = PLB_NQUAL - 1;
+            int mq = rec.mapq < 255 ? rec.mapq : 20;
+            if (mq > a.cap_mapq) mq = a.cap_mapq;
+            if (mq > PLB_NQUAL - 1) mq = PLB_NQUAL - 1;
+            const int strand = (a.paired && (r & 1)) ? !rec.rev : (rec.rev != 0);
+            const int alt = (ref4 < 4 && base4_of(base16(a, v, i)) == ref4) ? 0 : 1;
+            int epos, scl;
+            read_position(i, v.len, (int)v.c5, (int)v.c3, epos, scl);
+            atomicAdd(tab + PLB_POS + alt * PLB_NPOS + epos, 1u);
+            atomicAdd(tab + PLB_SCL + alt * PLB_NPOS + scl, 1u);
+            atomicAdd(tab + PLB_MQ + alt * PLB_NQUAL + mq, 1u);
+            atomicAdd(tab + PLB_BQ + alt * PLB_NQUAL + bq, 1u);
+            atomicAdd(tab + PLB_MQS + strand * PLB_NQUAL + mq, 1u);
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < PLB_CELLS; i += blockDim.x) b.out[s * PLB_CELLS + i] = tab[i];
         __syncthreads();
     }
 }

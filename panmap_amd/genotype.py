@@ -11,6 +11,9 @@ from .api import Aligner, Context, Panman, ReadSet
 HIST = 640   # PMX_PILEUP_HIST: [q 0..63][strand][A C G T N]
 AUX = 4      # PMX_PILEUP_AUX: raw depth, sum of capped mapQ, bases of MQ-0 reads, deletions
 HIST_SHAPE = (64, 2, 5)
+BIAS = 760   # PMX_PILEUP_BIAS: pos [2][100], scl [2][100], mq [2][60], bq [2][60] by ref/alt, mqs [2][60] by strand
+BIAS_BLOCKS = dict(pos=(0, 100), scl=(200, 100), mq=(400, 60), bq=(520, 60), mqs=(640, 60))   # PMX_PLB_*: offset, bins
+TEST_KEYS = ("VDB", "SGB", "RPBZ", "MQBZ", "MQSBZ", "BQBZ", "SCBZ", "MQ0F")
 
 ADMITTED, RECONCILED, SECOND_MATE, KEEPS_AGREEING = 1, 2, 4, 8   # bits of Pileup.read_info()[0]
 
@@ -28,6 +31,11 @@ class SiteCall(C.Structure):
     """pmx_site_call"""
     _fields_ = [("n_alleles", C.c_int32), ("alleles", C.c_int32 * 5), ("pl", C.c_int32 * 5), ("ad", C.c_int32 * 5), ("dp4", C.c_int32 * 4),
                 ("n_bases", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class SiteTests(C.Structure):
+    """pmx_site_tests"""
+    _fields_ = [("value", C.c_float * 8), ("present", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 def _names(names):
@@ -79,6 +87,17 @@ class Pileup:
         check(lib.pmx_pileup_fetch(self.ctx._h, self._h, hist.ctypes.data, aux.ctypes.data), "pmx_pileup_fetch")
         return hist, aux
 
+    def bias(self, positions, ref_bases: bytes):
+        """the bias pass of the last run at the listed sites (0-based, strictly ascending; one reference letter each)
+        -> uint32 [n, 760], blocks as BIAS_BLOCKS"""
+        positions = np.ascontiguousarray(positions, np.int32)
+        ref_bases = bytes(ref_bases)
+        if positions.ndim != 1 or len(ref_bases) != len(positions):
+            raise ValueError("bias: one reference letter per position")
+        out = np.zeros((len(positions), BIAS), np.uint32)
+        check(lib.pmx_pileup_bias(self.ctx._h, self._h, positions.ctypes.data, ref_bases, len(positions), out.ctypes.data), "pmx_pileup_bias")
+        return out
+
     def read_info(self):
         """-> (flags uint8 per read: ADMITTED | RECONCILED | SECOND_MATE | KEEPS_AGREEING, rank in the BAM uint32 per read)"""
         flags = np.zeros(max(self.n_reads, 1), np.uint8)
@@ -128,6 +147,23 @@ def site_call(hist, ref_base: bytes) -> dict:
     return dict(alleles=list(sc.alleles[:n]), pl=list(sc.pl[:n]), ad=list(sc.ad[:n]), dp4=list(sc.dp4), n_bases=sc.n_bases)
 
 
+def format_float(v) -> str:
+    """a float as a VCF prints it (htslib's kputd)"""
+    buf = C.create_string_buffer(64)
+    lib.pmx_genotype_format_float(float(v), buf, len(buf))
+    return buf.value.decode()
+
+
+def site_tests(hist_row, aux_row, bias_row, ref_base: bytes) -> dict:
+    """mpileup's bias annotations of one site -> {key: value as the VCF prints it}, absent keys left out (TEST_KEYS order)"""
+    h = np.ascontiguousarray(np.asarray(hist_row, np.uint32).reshape(HIST))
+    a = np.ascontiguousarray(np.asarray(aux_row, np.uint32).reshape(AUX))
+    b = np.ascontiguousarray(np.asarray(bias_row, np.uint32).reshape(BIAS))
+    t = SiteTests()
+    check(lib.pmx_genotype_site_tests(h.ctypes.data, a.ctypes.data, b.ctypes.data, ref_base[:1], C.byref(t)), "pmx_genotype_site_tests")
+    return {lib.pmx_genotype_test_name(k).decode(): format_float(t.value[k]) for k in range(len(TEST_KEYS)) if t.present >> k & 1}
+
+
 def filter_line(line: str, phred=None, min_depth: int = 1, min_qual: float = 30.0) -> str:
     """applyMutationSpectrum on one VCF line (phred None: the branch without a spectrum); '' = dropped"""
     p = None if phred is None else np.ascontiguousarray(np.asarray(phred, np.float64).reshape(16))
@@ -154,6 +190,18 @@ class Genotyper:
 
     def records(self):
         return [lib.pmx_genotype_record(self._h, i).decode() for i in range(lib.pmx_genotype_num_records(self._h))]
+
+    def positions(self):
+        """0-based reference position of every record"""
+        return np.asarray([lib.pmx_genotype_record_pos(self._h, i) for i in range(lib.pmx_genotype_num_records(self._h))], np.int32)
+
+    def annotate(self, positions, bias):
+        """adds mpileup's bias annotations to the INFO of the records at `positions` (bias: Pileup.bias at those positions)"""
+        positions = np.ascontiguousarray(positions, np.int32)
+        bias = np.ascontiguousarray(bias, np.uint32)
+        if bias.size != len(positions) * BIAS:
+            raise ValueError("annotate: one bias row per position")
+        check(lib.pmx_genotype_annotate(self._h, positions.ctypes.data, bias.ctypes.data, len(positions)), "pmx_genotype_annotate")
 
     def write_vcf(self, path: str, sample_name: str):
         check(lib.pmx_genotype_write_vcf(self._h, path.encode(), self.chrom.encode(), self.ref_len, sample_name.encode()), "pmx_genotype_write_vcf")
