@@ -163,9 +163,6 @@ const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStrea
     }
     if (!readset_locality_order(ctx, rs) || n_items < 1) return nullptr;
     rs->pp_key.ensure((size_t)n_items); rs->pp_key2.ensure((size_t)n_items); rs->pp_idx.ensure((size_t)n_items); rs->pp_idx2.ensure((size_t)n_items + 1);
-    size_t bytes = 0;
-    PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, rs->pp_key.p, rs->pp_key2.p, rs->pp_idx.p, rs->pp_idx2.p, (size_t)n_items, 0, 64, ctx->stream));
-    rs->pp_tmp.ensure(bytes);
     hipStream_t st = ctx->stream;
     if (side) {
         if (!rs->pair_ev) PMX_HIP(hipEventCreateWithFlags(&rs->pair_ev, hipEventDisableTiming));
@@ -175,7 +172,7 @@ const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStrea
     }
     hipLaunchKernelGGL(k_pair_keys, dim3((unsigned)std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, st, rs->loc_key.p, n_items,
                        rs->pp_key.p, rs->pp_idx.p);
-    PMX_HIP(rocprim::radix_sort_pairs(rs->pp_tmp.p, bytes, rs->pp_key.p, rs->pp_key2.p, rs->pp_idx.p, rs->pp_idx2.p, (size_t)n_items, 0, 64, st));
+    PMX_ROCPRIM(rs->pp_tmp, radix_sort_pairs, rs->pp_key.p, rs->pp_key2.p, rs->pp_idx.p, rs->pp_idx2.p, (size_t)n_items, 0, 64, st);
     // (the map, too, depends on the reads alone; below a million pairs the align stage seldom wants it -- PMX_ALIGN_DEDUP_DEPTH
     //  -- and makes it itself when it does)
     if (side && n_items >= ((int64_t)1 << 20) && !pmx::opt_str(pmx::O_ALIGN_NO_DEDUP)) readset_pair_map(ctx, rs, st);
@@ -192,16 +189,13 @@ void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st) {
     if (rs->has_pair_map || n < 1 || !rs->has_recs) return;
     rs->pd_key.ensure((size_t)n); rs->pd_key2.ensure((size_t)n); rs->pd_idx.ensure((size_t)n); rs->pd_idx2.ensure((size_t)n);
     rs->pd_gs.ensure((size_t)n); rs->pd_rep.ensure((size_t)n); rs->pd_mult.ensure((size_t)n);
-    size_t sort_bytes = 0, scan_bytes = 0;
-    PMX_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, rs->pd_key.p, rs->pd_key2.p, rs->pd_idx.p, rs->pd_idx2.p, (size_t)n, 0, 32, st));
-    PMX_HIP(rocprim::inclusive_scan(nullptr, scan_bytes, rs->pd_key.p, rs->pd_gs.p, (size_t)n, rocprim::maximum<uint32_t>(), st));
-    rs->pd_tmp.ensure(std::max(sort_bytes, scan_bytes));
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 8);
     hipLaunchKernelGGL(k_pair_hashes, dim3(grid), dim3(256), 0, st, rs->recs.p, n, rs->pd_key.p, rs->pd_idx.p);
-    PMX_HIP(rocprim::radix_sort_pairs(rs->pd_tmp.p, sort_bytes, rs->pd_key.p, rs->pd_key2.p, rs->pd_idx.p, rs->pd_idx2.p, (size_t)n, 0, 32, st));
+    PMX_ROCPRIM(rs->pd_tmp, radix_sort_pairs, rs->pd_key.p, rs->pd_key2.p, rs->pd_idx.p, rs->pd_idx2.p, (size_t)n, 0, 32, st);
     // (the unsorted keys are spent: their buffer takes the group starts before the scan)
     hipLaunchKernelGGL(k_pair_group_starts, dim3(grid), dim3(256), 0, st, rs->recs.p, rs->pd_key2.p, rs->pd_idx2.p, n, rs->pd_key.p);
-    PMX_HIP(rocprim::inclusive_scan(rs->pd_tmp.p, scan_bytes, rs->pd_key.p, rs->pd_gs.p, (size_t)n, rocprim::maximum<uint32_t>(), st));
+    // (the sort and the scan share one temporary; the scan needs less of it, so it grows at the sort alone)
+    PMX_ROCPRIM(rs->pd_tmp, inclusive_scan, rs->pd_key.p, rs->pd_gs.p, (size_t)n, rocprim::maximum<uint32_t>(), st);
     hipLaunchKernelGGL(k_pair_reps, dim3(grid), dim3(256), 0, st, rs->pd_idx2.p, rs->pd_gs.p, n, rs->pd_rep.p, rs->pd_mult.p);
     PMX_HIP(hipGetLastError());
     rs->has_pair_map = true;
@@ -210,10 +204,7 @@ void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st) {
 const uint32_t* pair_order_mate1(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* read_order) {
     const int64_t n_items = rs->n / 2;
     al->pp_idx.ensure((size_t)rs->n); al->pp_idx2.ensure((size_t)n_items + 1);
-    size_t bytes = 0;
-    PMX_HIP(rocprim::select(nullptr, bytes, read_order, al->pp_idx.p, al->pp_idx2.p + n_items, (size_t)rs->n, IsEvenRead(), ctx->stream));
-    al->pp_tmp.ensure(bytes);
-    PMX_HIP(rocprim::select(al->pp_tmp.p, bytes, read_order, al->pp_idx.p, al->pp_idx2.p + n_items, (size_t)rs->n, IsEvenRead(), ctx->stream));
+    PMX_ROCPRIM(al->pp_tmp, select, read_order, al->pp_idx.p, al->pp_idx2.p + n_items, (size_t)rs->n, IsEvenRead(), ctx->stream);
     hipLaunchKernelGGL(k_halve, dim3((unsigned)std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
                        al->pp_idx.p, n_items, al->pp_idx2.p);
     return al->pp_idx2.p;
@@ -225,12 +216,8 @@ int64_t pair_select_reps(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, c
     al->dd_list.ensure((size_t)n_pairs);
     const IsPairRep is_rep{rs->pd_rep.p};
     const rocprim::counting_iterator<uint32_t> every(0u);
-    size_t bytes = 0;
-    if (order) PMX_HIP(rocprim::select(nullptr, bytes, order, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream));
-    else PMX_HIP(rocprim::select(nullptr, bytes, every, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream));
-    al->dd_tmp.ensure(bytes);
-    if (order) PMX_HIP(rocprim::select(al->dd_tmp.p, bytes, order, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream));
-    else PMX_HIP(rocprim::select(al->dd_tmp.p, bytes, every, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream));
+    if (order) PMX_ROCPRIM(al->dd_tmp, select, order, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream);
+    else PMX_ROCPRIM(al->dd_tmp, select, every, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream);
     unsigned long long h_reps = 0;
     PMX_HIP(hipMemcpyAsync(&h_reps, al->dd_count.p, sizeof(h_reps), hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));

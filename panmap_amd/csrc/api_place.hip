@@ -1,9 +1,13 @@
-// C ABI, device part 1: context, read sets, PLACE stage orchestration (see include/panmap_amd.h).
+// C ABI, device part 1: context, read sets, PLACE stage orchestration (see include/panmap_amd.h).  The seeding driver is
+// SeedStage (pmx_place_add_reads*), the scoring driver ScoreStage (pmx_place_score): one struct per call, one function per step.
 #include <hip/hip_runtime.h>
 #include <memory>
 
 #include <algorithm>
+#include <array>
+#include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <string.h>
 
@@ -94,11 +98,37 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+// Every switch the stage reads (device/pmx_options.hpp), parsed here and nowhere below.
+struct PlaceSwitches {
+    static bool on(OptId id) { return pmx::opt_str(id) != nullptr; }
+    const bool seed_safe_bound = on(O_SEED_SAFE_BOUND), seed_no_hint = on(O_SEED_NO_HINT);                                // table bound policy
+    const bool seed_generic = on(O_SEED_GENERIC), seed_no_sort = on(O_SEED_NO_SORT), seed_no_collapse = on(O_SEED_NO_COLLAPSE);   // kernel path
+    const bool level_kernels = on(O_PLACE_LEVEL_KERNELS), tree_kernel = on(O_PLACE_TREE_KERNEL), no_graph = on(O_PLACE_NO_GRAPH);   // scoring form
+    const bool test_starved = on(O_PLACE_TEST_STARVED);
+    const bool prof = on(O_PLACE_PROF);   // diagnostics
+    int64_t seed_chunk_mb = 0;    // 0: a third of the range, 64..512
+    int64_t seed_bound_div = 0;   // 0: an eighth of the safe bound, or the previous histogram's density
+    int seed_par = 0;             // 0: by the size of the range
+    int seed_batches = 1;
+    PlaceSwitches() {
+        if (const char* e = pmx::opt_str(pmx::O_SEED_CHUNK_MB)) seed_chunk_mb = std::max<int64_t>(1, atoll(e));
+        if (const char* e = pmx::opt_str(pmx::O_SEED_BOUND_DIV)) seed_bound_div = std::max<int64_t>(1, atoll(e));
+        if (const char* e = pmx::opt_str(pmx::O_SEED_PAR)) seed_par = std::max(1, std::min(4, atoi(e)));
+        if (const char* e = pmx::opt_str(pmx::O_SEED_BATCHES)) seed_batches = std::max(1, atoi(e));
+    }
+};
+
 #define PMX_TRY try {
 #define PMX_CATCH                                                      \
     }                                                                  \
     catch (const HipError& e) { return fail(PMX_ERR_DEVICE, e.msg); }  \
     catch (const std::exception& e) { return fail(PMX_ERR_DEVICE, e.what()); }
+
+// every slot of the seed table empty: the keys PMX_EMPTY_KEY, the counts zero
+void table_clear(pmx_ctx* ctx, pmx_place* pl) {
+    hipLaunchKernelGGL(k_fill_u64, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, PMX_EMPTY_KEY, pl->cap);
+    PMX_HIP(hipMemsetAsync(pl->vals.p, 0, pl->cap * sizeof(unsigned long long), ctx->stream));
+}
 
 // (the device memory stays at its high-water mark: a batch whose ranges want a small, then a large table would otherwise
 // free and allocate gigabytes per batch -- hipFree synchronises the device, and a fresh allocation of that size takes
@@ -107,8 +137,7 @@ void table_alloc(pmx_ctx* ctx, pmx_place* pl, uint64_t cap) {
     pl->keys.ensure(cap);
     pl->vals.ensure(cap);
     pl->cap = cap;
-    hipLaunchKernelGGL(k_fill_u64, dim3(grid_for((int64_t)cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, PMX_EMPTY_KEY, cap);
-    PMX_HIP(hipMemsetAsync(pl->vals.p, 0, cap * sizeof(unsigned long long), ctx->stream));
+    table_clear(ctx, pl);
 }
 
 uint64_t next_pow2(uint64_t x) {
@@ -124,10 +153,7 @@ void table_reserve(pmx_ctx* ctx, pmx_place* pl, uint64_t bound_new) {
         if (need0 < (1u << 16)) need0 = 1u << 16;
         pl->needs_clear = false;
         if (pl->cap < need0 || pl->cap > 4 * need0) table_alloc(ctx, pl, need0);   // (also shrinks: clearing and compacting scan every slot)
-        else {
-            hipLaunchKernelGGL(k_fill_u64, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, PMX_EMPTY_KEY, pl->cap);
-            PMX_HIP(hipMemsetAsync(pl->vals.p, 0, pl->cap * sizeof(unsigned long long), ctx->stream));
-        }
+        else table_clear(ctx, pl);
         return;
     }
     unsigned long long h_ctr[PMX_CTR_N];
@@ -177,12 +203,7 @@ void finalize_histogram(pmx_ctx* ctx, pmx_place* pl) {
         PMX_HIP(hipMemsetAsync(pl->counters.p + PMX_CTR_COMPACT, 0, sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(k_table_compact, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p,
                            pl->vals.p, pl->cap, pl->hist_hash_tmp.p, pl->hist_count_tmp.p, pl->counters.p + PMX_CTR_COMPACT);
-        size_t bytes = 0;
-        PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, pl->hist_hash_tmp.p, pl->hist_hash.p, pl->hist_count_tmp.p, pl->hist_count.p,
-                                          (size_t)n, 0, 64, ctx->stream));
-        pl->tmp.ensure(bytes);
-        PMX_HIP(rocprim::radix_sort_pairs(pl->tmp.p, bytes, pl->hist_hash_tmp.p, pl->hist_hash.p, pl->hist_count_tmp.p, pl->hist_count.p,
-                                          (size_t)n, 0, 64, ctx->stream));
+        PMX_ROCPRIM(pl->tmp, radix_sort_pairs, pl->hist_hash_tmp.p, pl->hist_hash.p, pl->hist_count_tmp.p, pl->hist_count.p, (size_t)n, 0, 64, ctx->stream);
     }
     pl->hist_sorted = true;
 }
@@ -212,6 +233,63 @@ struct Best {
     }
 };
 
+// The sequential best/tie rule in BFS visit order (src/placement.cpp:355-401), per metric: `scores` holds the five metrics'
+// node scores one after the other, each in visit order (h_order[j] = the node visited j-th); force_leaf skips the nodes
+// that have a child.  -> best score, its node and the sorted tie list per metric.
+// Every improvement of `best` resets the tie list to the improving node, so only the visit positions after the
+// LAST improvement can contribute ties: pass 1 replays just the scalar part of the rule (best, idx, position of
+// the last improvement), pass 2 runs the full rule from that position on.  Same result as one pass with the
+// vectors, without pushing and clearing tens of thousands of transient ties.
+std::array<Best, 5> best_and_ties(const double* scores, const std::vector<uint32_t>& h_order, const std::vector<uint8_t>& h_has_child, bool force_leaf) {
+    std::array<Best, 5> best;
+    const int64_t nn = (int64_t)h_order.size();
+    std::vector<uint8_t> flag((size_t)nn);
+    for (int m = 0; m < 5; ++m) {
+        const double* sc = scores + (size_t)m * (size_t)nn;   // this metric, in visit order
+        double b = 0.0, thr = 0.0 + std::max(0.0 * 0.0001, 1e-9);   // thr = best + tol, recomputed only when best moves
+        int64_t last = -1;
+        if (force_leaf) {
+            for (int64_t j = 0; j < nn; ++j) {
+                if (h_has_child[h_order[j]]) continue;
+                if (sc[j] > thr) { b = sc[j]; thr = b + std::max(b * 0.0001, 1e-9); last = j; }
+            }
+        } else {
+            for (int64_t j = 0; j < nn; ++j)
+                if (sc[j] > thr) { b = sc[j]; thr = b + std::max(b * 0.0001, 1e-9); last = j; }
+        }
+        if (last < 0) {   // never improved (all scores ~0): the plain rule, start to end
+            for (int64_t j = 0; j < nn; ++j) {
+                const uint32_t nd = h_order[j];
+                if (force_leaf && h_has_child[nd]) continue;
+                best[m].update(nd, sc[j]);
+            }
+        } else {
+            // after the last improvement `best` is fixed, so a later node ties iff score >= best - tol (and > 0); the
+            // rule's list, once sorted and de-duplicated, is {idx} + those nodes: flagged and read back in id order
+            best[m].best = b;
+            best[m].idx = h_order[last];
+            const double tol = std::max(b * 0.0001, 1e-9);
+            std::fill(flag.begin(), flag.end(), (uint8_t)0);
+            flag[best[m].idx] = 1;
+            for (int64_t j = last + 1; j < nn; ++j) {
+                if (!(sc[j] >= b - tol && sc[j] > 0)) continue;
+                const uint32_t nd = h_order[j];
+                if (force_leaf && h_has_child[nd]) continue;
+                flag[nd] = 1;
+            }
+            for (int64_t nd = 0; nd < nn; ++nd)
+                if (flag[(size_t)nd]) best[m].tied.push_back((uint32_t)nd);
+        }
+        std::vector<uint32_t>& t = best[m].tied;
+        if (!t.empty()) {
+            std::sort(t.begin(), t.end());
+            t.erase(std::unique(t.begin(), t.end()), t.end());
+            best[m].idx = t.front();
+        }
+    }
+    return best;
+}
+
 }  // namespace
 
 namespace pmx {
@@ -225,10 +303,7 @@ static void order_range(pmx_ctx* ctx, const pmx_readset* rs, int64_t r0, int64_t
     // (sorting on the key's top 20 bits alone -- three radix passes instead of four -- returned index arrays that were no
     //  permutation on this rocprim: measured, not understood; the full key it is)
     const unsigned lo_bit = 0u;
-    size_t bytes = 0;
-    PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, rs->loc_key.p + r0, rs->loc_key2.p + r0, rs->loc_idx.p + r0, rs->loc_perm.p + r0, (size_t)m, lo_bit, 32, ctx->stream));
-    rs->loc_tmp.ensure(bytes);
-    PMX_HIP(rocprim::radix_sort_pairs(rs->loc_tmp.p, bytes, rs->loc_key.p + r0, rs->loc_key2.p + r0, rs->loc_idx.p + r0, rs->loc_perm.p + r0, (size_t)m, lo_bit, 32, ctx->stream));
+    PMX_ROCPRIM(rs->loc_tmp, radix_sort_pairs, rs->loc_key.p + r0, rs->loc_key2.p + r0, rs->loc_idx.p + r0, rs->loc_perm.p + r0, (size_t)m, lo_bit, 32, ctx->stream);
 }
 
 const uint32_t* readset_locality_order(pmx_ctx* ctx, const pmx_readset* rs) {
@@ -411,10 +486,7 @@ int pmx_readset_rewrap_device(pmx_ctx* ctx, pmx_readset* rs, const void* d_conca
     PMX_HIP(hipMemsetAsync(rs->stats.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_read_word_counts, dim3(grid_for(n_reads + 1, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rs->off.p, n_reads, total_bytes,
                        rs->nw_tmp.p, rs->stats.p);
-    size_t bytes = 0;
-    PMX_HIP(rocprim::exclusive_scan(nullptr, bytes, rs->nw_tmp.p, rs->woff.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), ctx->stream));
-    rs->scan_tmp.ensure(bytes);
-    PMX_HIP(rocprim::exclusive_scan(rs->scan_tmp.p, bytes, rs->nw_tmp.p, rs->woff.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), ctx->stream));
+    PMX_ROCPRIM(rs->scan_tmp, exclusive_scan, rs->nw_tmp.p, rs->woff.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), ctx->stream);
     struct { int64_t n_words; unsigned long long st[2]; } h = {0, {0, 0}};
     PMX_HIP(hipMemcpyAsync(&h.n_words, rs->woff.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipMemcpyAsync(h.st, rs->stats.p, sizeof(h.st), hipMemcpyDeviceToHost, ctx->stream));
@@ -636,19 +708,213 @@ static void dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs) {
     pl->dd_idx.ensure((size_t)n); pl->dd_idx2.ensure((size_t)n); pl->dd_keep.ensure((size_t)n);
     if (n == 0) { pl->dd_for = rs; return; }
     hipLaunchKernelGGL(k_read_hashes, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p, n, pl->dd_h1.p, pl->dd_h2.p, pl->dd_idx.p);
-    size_t bytes = 0;
-    PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, pl->dd_h2.p, pl->dd_key.p, pl->dd_idx.p, pl->dd_idx2.p, (size_t)n, 0, 64, ctx->stream));
-    pl->tmp.ensure(bytes);
-    PMX_HIP(rocprim::radix_sort_pairs(pl->tmp.p, bytes, pl->dd_h2.p, pl->dd_key.p, pl->dd_idx.p, pl->dd_idx2.p, (size_t)n, 0, 64, ctx->stream));
+    PMX_ROCPRIM(pl->tmp, radix_sort_pairs, pl->dd_h2.p, pl->dd_key.p, pl->dd_idx.p, pl->dd_idx2.p, (size_t)n, 0, 64, ctx->stream);
     hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_idx2.p, n, pl->dd_key.p);
-    PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, pl->dd_key.p, pl->dd_h1s.p, pl->dd_idx2.p, pl->dd_idx.p, (size_t)n, 0, 64, ctx->stream));
-    pl->tmp.ensure(bytes);
-    PMX_HIP(rocprim::radix_sort_pairs(pl->tmp.p, bytes, pl->dd_key.p, pl->dd_h1s.p, pl->dd_idx2.p, pl->dd_idx.p, (size_t)n, 0, 64, ctx->stream));
+    PMX_ROCPRIM(pl->tmp, radix_sort_pairs, pl->dd_key.p, pl->dd_h1s.p, pl->dd_idx2.p, pl->dd_idx.p, (size_t)n, 0, 64, ctx->stream);
     hipLaunchKernelGGL(k_mark_first_of_run, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p, pl->dd_h1s.p, pl->dd_h2.p, pl->dd_idx.p, n,
                        pl->dd_keep.p);
     PMX_HIP(hipGetLastError());
     pl->dd_for = rs;
 }
+
+// ------------------------------------------------------------------------------------- seeding
+// The side streams of the seeding stage and their events, made on first use (they belong to the context: dev_util.hpp)
+static void ensure_seed_streams(pmx_ctx* ctx) {
+    if (ctx->seed_go) return;
+    PMX_HIP(hipEventCreateWithFlags(&ctx->seed_go, hipEventDisableTiming));
+    for (int j = 0; j < 3; ++j) {   // (own hardware queues: see create_dedicated_stream)
+        ctx->seed_streams[j] = create_dedicated_stream(ctx->n_cu);
+        PMX_HIP(hipEventCreateWithFlags(&ctx->seed_done[j], hipEventDisableTiming));
+    }
+}
+
+namespace {
+
+// One call of pmx_place_add_reads / _range: the plan (made by the constructor, constant afterwards), then one function per step.
+struct SeedStage {
+    pmx_ctx* const ctx;
+    pmx_place* const pl;
+    const pmx_readset* const rs;
+    const pmx_place_params* const pp;
+    const int64_t rr0, rr1;
+    const PlaceSwitches sw;
+    // plan
+    SeedParams sp;
+    int l = 1;                      // s-mers per seed, at least 1
+    bool quality_mode = false;      // src/placement.cpp:1386: no dedup in this branch
+    bool ks_path = false;           // the kernel specialised for the default parameters (same results, ~3x fewer instructions)
+    bool collapse = false;          // k_collapse_reads ahead of it
+    int fixed_len = 0;              // every read of the set has this many bases (total = n x max_len): word offsets follow from the read index
+    size_t lds = 0, lds_ks = 0;     // dynamic LDS of k_seed_histogram / k_seed_histogram_ks
+    int64_t chunk_reads_opt = 1, chunk_reads_safe = 1;
+    int64_t bound_div = 1;          // > 1: the first pass is optimistic
+    double bound_frac = 0;          // > 0: optimistic bound as a fraction of the safe one (takes the place of 1 / bound_div)
+    int n_par = 1;                  // chunks of a group in flight
+    // set by the steps
+    const uint8_t* keep = nullptr;  // --dedup mask (dedup_mask)
+    const uint32_t* perm = nullptr; // seeding order (seeding_order)
+
+    SeedStage(pmx_ctx* c, pmx_place* p, const pmx_readset* r, const pmx_place_params* q, int64_t r0, int64_t r1);
+    void dedup_mask();
+    void seeding_order();
+    void prepare_collapse();
+    void launch_chunk(int j, int64_t r0, int64_t r1, hipStream_t st);
+    void pass(bool optimistic);
+    unsigned long long failed_inserts();
+};
+
+SeedStage::SeedStage(pmx_ctx* c, pmx_place* p, const pmx_readset* r, const pmx_place_params* q, int64_t r0, int64_t r1)
+    : ctx(c), pl(p), rs(r), pp(q), rr0(r0), rr1(r1) {
+    sp.k = pl->params.k; sp.s = pl->params.s; sp.t = pl->params.t; sp.l = pl->params.l; sp.open = pl->params.open ? 1 : 0;
+    sp.trim_start = pp->trim_start; sp.trim_end = pp->trim_end;
+    const int w = sp.k - sp.s + 1;
+    l = sp.l < 1 ? 1 : sp.l;
+    lds = (size_t)(2 * w + l) * PMX_SEED_BLOCK * sizeof(uint64_t) +
+          (size_t)(PMX_SEED_BLOCK / 64) * (PMX_SEED_QCAP * sizeof(uint64_t) + 8);   // + the waves' seed queues and their counters
+    // the specialised kernel keeps its rings in registers: LDS = the waves' seed queues + the block cache (keys 8 B +
+    // counts 4 B + admission tags 2 B per entry)
+    lds_ks = (size_t)(PMX_SEED_BLOCK / 64) * PMX_SEED_QCAP_KS * sizeof(uint64_t) + (size_t)PMX_SEED_CACHE * 14 + 35 * sizeof(uint64_t) +   // + the base-hash tables
+             (size_t)(PMX_SEED_BLOCK / 64) * (64 * sizeof(uint32_t) + PMX_SEED_QCAP_KS);                                                   // + multiplicities, pushing lanes
+    quality_mode = pp->min_seed_quality > 0 && rs->has_qual;
+    ks_path = sp.k == 19 && sp.s == 8 && sp.t == 0 && (l == 3 || l == 1) && !quality_mode && !sw.seed_generic;
+    // Read collapse ahead of the seeding kernel (k_collapse_reads: src/placement.cpp:1550-1593 seeds every distinct read once,
+    // with its multiplicity): reads of up to 160 bases on the specialised kernel's path
+    collapse = ks_path && rs->max_len <= 160 && !sw.seed_no_collapse;
+    fixed_len = (rs->n > 0 && rs->total == rs->n * rs->max_len) ? (int)rs->max_len : 0;
+    // Reads go in chunks of <= ~64M bases, three at a time.  Before each group the table is grown (rehash) if the distinct
+    // keys seen so far plus one new key per base of the chunk would push the load factor past 0.7, so an
+    // insert can never fail, yet the table is sized by what the reads actually contain (a few million
+    // distinct seeds for a 1M-read sample) instead of by the one-key-per-base bound of the whole batch:
+    // a 16x smaller table to clear, probe and compact.
+    // (a group of three chunks = one table reservation: 1M x 150 bp is one group; 16 MB chunks measured 2.46 ms for the stage,
+    //  one group 2.09).  A large range is cut into as few groups as 512 MB chunks allow: 10M x 150 bp in 24 launches of 64 MB
+    //  took 10.8 ms, in 16 of 96 MB 9.6 ms, in 4 of 384 MB 9.05 ms -- a third of the range per chunk, between 64 and 512 MB
+    const int64_t max_len = std::max<int64_t>(rs->max_len, 1);
+    const int64_t chunk_mb = sw.seed_chunk_mb > 0 ? sw.seed_chunk_mb : std::min<int64_t>(512, std::max<int64_t>(64, (((rr1 - rr0) * max_len / 3) >> 20) + 1));
+    chunk_reads_opt = std::max<int64_t>(1, (chunk_mb << 20) / max_len);
+    // (with the safe bound -- one key per base of the group -- the groups stay three chunks of 64 MB: the table is grown by
+    //  what a group can add, and a 1.5 GB group would reserve a 68 GB table for a sample that overflowed the optimistic one)
+    chunk_reads_safe = std::max<int64_t>(1, (std::min<int64_t>(chunk_mb, 64) << 20) / max_len);
+    // Table sizing.  The safe bound on the distinct keys a chunk can add is one per base; real reads add one seed per
+    // 5-6 bases and most of those repeat.  When the table is empty at the start of the call the chunks are first run
+    // with an eighth of the safe bound (a smaller table to clear, probe and compact); an insert that finds no slot is
+    // counted (probe sequences are capped), and in that case the table is cleared and the call is redone with the safe
+    // bound.  Same histogram either way.
+    // Once a histogram has been finished its density (distinct seeds per read base) sizes the next optimistic table:
+    // twice that, at least 1/256 of the safe bound (1/64 until round 4: 2^25 slots at a load of 3.5 % for 10M reads; every table atomic missed the L2 and the compaction scanned 512 MB) -- batches of one run look alike, and a table 16x smaller is 16x
+    // cheaper to clear and to compact.
+    if (!pl->table_dirty && !sw.seed_safe_bound) {
+        bound_div = 8;
+        if (sw.seed_bound_div > 0) bound_div = sw.seed_bound_div;   // (tests force the redo with a large value)
+        else if (pl->keys_per_base > 0 && !sw.seed_no_hint) bound_frac = std::min(1.0 / 8, std::max(2 * pl->keys_per_base, 1.0 / 256));
+    }
+    // A launch of one chunk is latency-bound (every wave walks its 150 bases one after the other, a few waves per
+    // SIMD): the chunks of a group run concurrently on side streams, sharing the table (all they do is atomics).
+    // (round 4, after the read collapse: one chunk at a time is as fast -- 10M reads 4.8 ms either way, 1.25M 1.42 against
+    //  1.53 -- so ranges under 4M reads stay on the context's own stream: every side stream is a hardware queue, and a host that
+    //  keeps four batches of a small job in flight, bench.py up to 3M reads, ran into the queue limit with them: its
+    //  one-batch-at-a-time leg fell from 102 to 57-67 M reads/s)
+    n_par = sw.seed_par > 0 ? sw.seed_par : (rr1 - rr0 >= 4000000 ? 3 : 1);
+}
+
+// --dedup: every distinct read sequence of this read set counts once
+void SeedStage::dedup_mask() {
+    if (!pp->dedup_reads || quality_mode) return;
+    if (pl->dd_for != rs) dedup_local(ctx, pl, rs);   // (pmx_place_dedup_* may have prepared -- and thinned -- the mask already)
+    keep = pl->dd_keep.p;
+    pl->dd_for = nullptr;                               // one use: the next call starts over
+}
+
+// seeding order (default-parameter kernel): reads that start with the same 16 bases next to each other, so that a
+// block's (seed, count) cache sees its seeds many times (k_seed_histogram_ks)
+void SeedStage::seeding_order() {
+    if (!ks_path || sw.seed_no_sort) return;
+    const bool whole = rr0 == 0 && rr1 == rs->n;
+    perm = whole ? readset_locality_order(ctx, rs) : readset_locality_order_range(ctx, rs, rr0, rr1);
+}
+
+void SeedStage::prepare_collapse() {
+    if (!collapse) return;
+    if (!pl->collapse_attr_set) {
+        PMX_HIP(hipFuncSetAttribute((const void*)k_collapse_reads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PMX_DEDUP_LDS_BYTES));
+        pl->collapse_attr_set = true;
+    }
+    pl->t_count.ensure(4);
+}
+
+// The reads [r0, r1) as chunk j of their group, on `st`, in one of three forms:
+//   collapse + ks over tiles  k_collapse_reads writes the distinct reads of the chunk as tiles (t_words / t_amb / t_len / t_mult / t_count of
+//                             slot j); k_seed_histogram_ks then reads the tiles: woff, off, keep and perm are null, r_begin is 0
+//   ks over reads             k_seed_histogram_ks on the read set itself: t_len, t_mult and t_count are null
+//   generic                   k_seed_histogram: the three list outputs are null; qual is null and min_q 0 outside quality mode; it takes no perm
+void SeedStage::launch_chunk(int j, int64_t r0, int64_t r1, hipStream_t st) {
+    // batches of PMX_SEED_BLOCK reads per block of the specialised kernel, contiguous in the seeding order.  More than one
+    // saves cache flushes (memory-side atomics) but measured slower: 1.55 ms for the stage with 1, 1.59 / 1.84 / 1.86 / 3.14
+    // with 2 / 4 / 8 / 16 -- fewer, longer blocks fill the chip worse, and the atomics are not what bounds the kernel
+    // (the specialised kernel: one batch of reads per block whatever the chunk's size -- the dispatcher hands the blocks out;
+    //  a grid capped at what is resident made every block walk several batches, which measured slower, see above)
+    const dim3 grid(ks_path ? grid_for(r1 - r0, PMX_SEED_BLOCK * sw.seed_batches, 1 << 30) : grid_for(r1 - r0, PMX_SEED_BLOCK, ctx->n_cu * 16)), block(PMX_SEED_BLOCK);
+    const auto ks = l == 3 ? k_seed_histogram_ks<19, 8, 3> : k_seed_histogram_ks<19, 8, 1>;
+    if (ks_path && collapse) {
+        const int64_t n_c = r1 - r0, n_tiles = (n_c + 63) / 64;
+        pl->t_words[j].ensure((size_t)n_tiles * 5 * 64); pl->t_amb[j].ensure((size_t)n_tiles * 5 * 64);
+        pl->t_len[j].ensure((size_t)n_tiles * 64); pl->t_mult[j].ensure((size_t)n_tiles * 64);
+        PMX_HIP(hipMemsetAsync(pl->t_count.p + j, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_collapse_reads, dim3((unsigned)((n_c + PMX_DEDUP_BLOCK - 1) / PMX_DEDUP_BLOCK)), dim3(PMX_DEDUP_BLOCK), PMX_DEDUP_LDS_BYTES, st,
+                           rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, keep, perm, sp.k, fixed_len, rs->has_recs ? rs->recs.p : (const uint8_t*)nullptr, pl->t_words[j].p, pl->t_amb[j].p, pl->t_len[j].p,
+                           pl->t_mult[j].p, pl->t_count.p + j);
+        PMX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ks, grid, block, lds_ks, st, pl->t_words[j].p, pl->t_amb[j].p,
+                           (const int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, n_c, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p,
+                           (const uint8_t*)nullptr, (const uint32_t*)nullptr, pl->t_len[j].p, pl->t_mult[j].p, pl->t_count.p + j);
+    } else if (ks_path)
+        hipLaunchKernelGGL(ks, grid, block, lds_ks, st, rs->words.p, rs->amb.p,
+                           rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p, keep, perm,
+                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL(k_seed_histogram, grid, block, lds, st, rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p,
+                           pl->vals.p, pl->cap - 1, pl->counters.p, keep, quality_mode ? rs->qual.p : nullptr,
+                           quality_mode ? pp->min_seed_quality : 0, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr);
+    PMX_HIP(hipGetLastError());
+}
+
+// One pass over the range: groups of n_par chunks, one table reservation per group.  The bound on the distinct keys a group
+// can add is one per base (safe), or the plan's fraction of that (optimistic: inserts may then fail, see failed_inserts).
+// Chunk 0 of a group runs on the context's stream, the others on the side streams, behind the reservation (seed_go); the
+// context's stream waits for each of them.
+void SeedStage::pass(bool optimistic) {
+    const int64_t chunk_reads = optimistic ? chunk_reads_opt : chunk_reads_safe;
+    for (int64_t g0 = rr0; g0 < rr1; g0 += chunk_reads * n_par) {
+        const int64_t g1 = std::min<int64_t>(rr1, g0 + chunk_reads * n_par);
+        const double safe_bound = (double)(g1 - g0) * (double)rs->max_len;
+        const double bound = !optimistic ? safe_bound : bound_frac > 0 ? safe_bound * bound_frac : safe_bound / (double)bound_div;
+        table_reserve(ctx, pl, (uint64_t)bound + 1);
+        if (n_par > 1) PMX_HIP(hipEventRecord(ctx->seed_go, ctx->stream));
+        int j = 0;
+        for (int64_t r0 = g0; r0 < g1; r0 += chunk_reads, ++j) {
+            const int64_t r1 = std::min<int64_t>(g1, r0 + chunk_reads);
+            hipStream_t st = j == 0 ? ctx->stream : ctx->seed_streams[j - 1];
+            if (j > 0) PMX_HIP(hipStreamWaitEvent(st, ctx->seed_go, 0));
+            launch_chunk(j, r0, r1, st);
+            if (j > 0) {
+                PMX_HIP(hipEventRecord(ctx->seed_done[j - 1], st));
+                PMX_HIP(hipStreamWaitEvent(ctx->stream, ctx->seed_done[j - 1], 0));
+            }
+        }
+    }
+}
+
+// the inserts of an optimistic pass that found no slot (the counters read here serve finalize_histogram too)
+unsigned long long SeedStage::failed_inserts() {
+    PMX_HIP(hipMemcpyAsync(pl->h_ctr, pl->counters.p, sizeof(pl->h_ctr), hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    pl->h_ctr_valid = true;
+    const unsigned long long h_ovf = pl->h_ctr[PMX_CTR_OVERFLOW];
+    if (sw.prof) fprintf(stderr, "[pmx place] seeding with bound 1/%lld: table %llu slots, %llu failed inserts\n", (long long)bound_div, (unsigned long long)pl->cap, h_ovf);
+    return h_ovf;
+}
+
+}  // namespace
 
 static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, int64_t rr0, int64_t rr1, const pmx_place_params* pp) {
     if (!ctx || !pl || !rs || !pp || rr0 < 0 || rr1 < rr0 || rr1 > rs->n) return PMX_ERR_ARG;
@@ -658,146 +924,23 @@ static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, in
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     pl->h_ctr_valid = false;
-    SeedParams sp;
-    sp.k = pl->params.k; sp.s = pl->params.s; sp.t = pl->params.t; sp.l = pl->params.l; sp.open = pl->params.open ? 1 : 0;
-    sp.trim_start = pp->trim_start; sp.trim_end = pp->trim_end;
-    const int w = sp.k - sp.s + 1, l = sp.l < 1 ? 1 : sp.l;
-    const size_t lds = (size_t)(2 * w + l) * PMX_SEED_BLOCK * sizeof(uint64_t) +
-                       (size_t)(PMX_SEED_BLOCK / 64) * (PMX_SEED_QCAP * sizeof(uint64_t) + 8);   // + the waves' seed queues and their counters
-    if (lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
-    if (lds > 64 * 1024)
-        PMX_HIP(hipFuncSetAttribute((const void*)k_seed_histogram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    SeedStage S(ctx, pl, rs, pp, rr0, rr1);
+    if (S.lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
+    if (S.lds > 64 * 1024)
+        PMX_HIP(hipFuncSetAttribute((const void*)k_seed_histogram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds));
     if (rr1 > rr0) {
-        // Reads go in chunks of <= ~64M bases, three at a time.  Before each group the table is grown (rehash) if the distinct
-        // keys seen so far plus one new key per base of the chunk would push the load factor past 0.7, so an
-        // insert can never fail, yet the table is sized by what the reads actually contain (a few million
-        // distinct seeds for a 1M-read sample) instead of by the one-key-per-base bound of the whole batch:
-        // a 16x smaller table to clear, probe and compact.
-        const bool quality_mode = pp->min_seed_quality > 0 && rs->has_qual;   // src/placement.cpp:1386: no dedup in this branch
-        const uint8_t* keep = nullptr;
-        if (pp->dedup_reads && !quality_mode) {   // --dedup: every distinct read sequence of this read set counts once
-            if (pl->dd_for != rs) dedup_local(ctx, pl, rs);   // (pmx_place_dedup_* may have prepared -- and thinned -- the mask already)
-            keep = pl->dd_keep.p;
-            pl->dd_for = nullptr;                               // one use: the next call starts over
-        }
-        // (a group of three chunks = one table reservation: 1M x 150 bp is one group; 16 MB chunks measured 2.46 ms for the stage,
-        //  one group 2.09).  A large range is cut into as few groups as 512 MB chunks allow: 10M x 150 bp in 24 launches of 64 MB
-        //  took 10.8 ms, in 16 of 96 MB 9.6 ms, in 4 of 384 MB 9.05 ms -- a third of the range per chunk, between 64 and 512 MB
-        int64_t chunk_mb = std::min<int64_t>(512, std::max<int64_t>(64, (((rr1 - rr0) * std::max<int64_t>(rs->max_len, 1) / 3) >> 20) + 1));
-        if (const char* e = pmx::opt_str(pmx::O_SEED_CHUNK_MB)) chunk_mb = std::max<int64_t>(1, atoll(e));
-        const int64_t chunk_reads_opt = std::max<int64_t>(1, (chunk_mb << 20) / std::max<int64_t>(rs->max_len, 1));
-        // (with the safe bound -- one key per base of the group -- the groups stay three chunks of 64 MB: the table is grown by
-        //  what a group can add, and a 1.5 GB group would reserve a 68 GB table for a sample that overflowed the optimistic one)
-        const int64_t chunk_reads_safe = std::max<int64_t>(1, (std::min<int64_t>(chunk_mb, 64) << 20) / std::max<int64_t>(rs->max_len, 1));
-        // Table sizing.  The safe bound on the distinct keys a chunk can add is one per base; real reads add one seed per
-        // 5-6 bases and most of those repeat.  When the table is empty at the start of the call the chunks are first run
-        // with an eighth of the safe bound (a smaller table to clear, probe and compact); an insert that finds no slot is
-        // counted (probe sequences are capped), and in that case the table is cleared and the call is redone with the safe
-        // bound.  Same histogram either way.
-        // Once a histogram has been finished its density (distinct seeds per read base) sizes the next optimistic table:
-        // twice that, at least 1/256 of the safe bound (1/64 until round 4: 2^25 slots at a load of 3.5 % for 10M reads; every table atomic missed the L2 and the compaction scanned 512 MB) -- batches of one run look alike, and a table 16x smaller is 16x
-        // cheaper to clear and to compact.
-        int64_t bound_div = 1;
-        double bound_frac = 0;   // > 0: optimistic bound as a fraction of the safe one (takes the place of 1 / bound_div)
-        if (!pl->table_dirty && !pmx::opt_str(pmx::O_SEED_SAFE_BOUND)) {
-            bound_div = 8;
-            if (const char* e = pmx::opt_str(pmx::O_SEED_BOUND_DIV)) bound_div = std::max<int64_t>(1, atoll(e));   // (tests force the redo with a large value)
-            else if (pl->keys_per_base > 0 && !pmx::opt_str(pmx::O_SEED_NO_HINT)) bound_frac = std::min(1.0 / 8, std::max(2 * pl->keys_per_base, 1.0 / 256));
-        }
+        S.dedup_mask();
         timer_begin(ctx, "seed");
-        // seeding order (default-parameter kernel): reads that start with the same 16 bases next to each other, so that a
-        // block's (seed, count) cache sees its seeds many times (k_seed_histogram_ks)
-        const bool ks_path = sp.k == 19 && sp.s == 8 && sp.t == 0 && (l == 3 || l == 1) && !quality_mode && !pmx::opt_str(pmx::O_SEED_GENERIC);
-        const uint32_t* perm = ks_path && !pmx::opt_str(pmx::O_SEED_NO_SORT) ? (whole ? readset_locality_order(ctx, rs) : readset_locality_order_range(ctx, rs, rr0, rr1)) : nullptr;
-        // the specialised kernel keeps its rings in registers: LDS = the waves' seed queues + the block cache (keys 8 B +
-        // counts 4 B + admission tags 2 B per entry)
-        const size_t lds_ks = (size_t)(PMX_SEED_BLOCK / 64) * PMX_SEED_QCAP_KS * sizeof(uint64_t) + (size_t)PMX_SEED_CACHE * 14 + 35 * sizeof(uint64_t) +   // + the base-hash tables
-                              (size_t)(PMX_SEED_BLOCK / 64) * (64 * sizeof(uint32_t) + PMX_SEED_QCAP_KS);                                                   // + multiplicities, pushing lanes
-        // Read collapse ahead of the seeding kernel (k_collapse_reads: src/placement.cpp:1550-1593 seeds every distinct read once,
-        // with its multiplicity): reads of up to 160 bases on the specialised kernel's path
-        const bool collapse = ks_path && rs->max_len <= 160 && !pmx::opt_str(pmx::O_SEED_NO_COLLAPSE);
-        if (collapse && !pl->collapse_attr_set) {
-            PMX_HIP(hipFuncSetAttribute((const void*)k_collapse_reads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PMX_DEDUP_LDS_BYTES));
-            pl->collapse_attr_set = true;
-        }
-        if (collapse) pl->t_count.ensure(4);
-        // every read of the set has max_len bases (total = n x max_len): word offsets follow from the read index
-        const int fixed_len = (rs->n > 0 && rs->total == rs->n * rs->max_len) ? (int)rs->max_len : 0;
-        for (int attempt = 0; attempt < 2; ++attempt) {
-        // A launch of one chunk is latency-bound (every wave walks its 150 bases one after the other, a few waves per
-        // SIMD): the chunks of a group run concurrently on side streams, sharing the table (all they do is atomics).
-        // (round 4, after the read collapse: one chunk at a time is as fast -- 10M reads 4.8 ms either way, 1.25M 1.42 against
-        //  1.53 -- so ranges under 4M reads stay on the context's own stream: every side stream is a hardware queue, and a host that
-        //  keeps four batches of a small job in flight, bench.py up to 3M reads, ran into the queue limit with them: its
-        //  one-batch-at-a-time leg fell from 102 to 57-67 M reads/s)
-        int n_par = rr1 - rr0 >= 4000000 ? 3 : 1;
-        if (const char* e = pmx::opt_str(pmx::O_SEED_PAR)) n_par = std::max(1, std::min(4, atoi(e)));
-        if (n_par > 1 && !ctx->seed_go) {
-            PMX_HIP(hipEventCreateWithFlags(&ctx->seed_go, hipEventDisableTiming));
-            for (int j = 0; j < 3; ++j) {   // (own hardware queues: see create_dedicated_stream)
-                ctx->seed_streams[j] = create_dedicated_stream(ctx->n_cu);
-                PMX_HIP(hipEventCreateWithFlags(&ctx->seed_done[j], hipEventDisableTiming));
-            }
-        }
-        const int64_t chunk_reads = bound_div > 1 ? chunk_reads_opt : chunk_reads_safe;
-        for (int64_t g0 = rr0; g0 < rr1; g0 += chunk_reads * n_par) {
-            const int64_t g1 = std::min<int64_t>(rr1, g0 + chunk_reads * n_par);
-            const double safe_bound = (double)(g1 - g0) * (double)rs->max_len;
-            table_reserve(ctx, pl, (uint64_t)(bound_div > 1 && bound_frac > 0 ? safe_bound * bound_frac : safe_bound / (double)bound_div) + 1);
-            if (n_par > 1) PMX_HIP(hipEventRecord(ctx->seed_go, ctx->stream));
-            int j = 0;
-            for (int64_t r0 = g0; r0 < g1; r0 += chunk_reads, ++j) {
-            const int64_t r1 = std::min<int64_t>(g1, r0 + chunk_reads);
-            hipStream_t st = j == 0 ? ctx->stream : ctx->seed_streams[j - 1];
-            if (j > 0) PMX_HIP(hipStreamWaitEvent(st, ctx->seed_go, 0));
-            // batches of PMX_SEED_BLOCK reads per block of the specialised kernel, contiguous in the seeding order.  More than one
-            // saves cache flushes (memory-side atomics) but measured slower: 1.55 ms for the stage with 1, 1.59 / 1.84 / 1.86 / 3.14
-            // with 2 / 4 / 8 / 16 -- fewer, longer blocks fill the chip worse, and the atomics are not what bounds the kernel
-            int seed_batches = 1;
-            if (const char* e = pmx::opt_str(pmx::O_SEED_BATCHES)) seed_batches = std::max(1, atoi(e));
-            // (the specialised kernel: one batch of reads per block whatever the chunk's size -- the dispatcher hands the blocks out;
-            //  a grid capped at what is resident made every block walk several batches, which measured slower, see above)
-            const dim3 grid(ks_path ? grid_for(r1 - r0, PMX_SEED_BLOCK * seed_batches, 1 << 30) : grid_for(r1 - r0, PMX_SEED_BLOCK, ctx->n_cu * 16)), block(PMX_SEED_BLOCK);
-            // the default seeding parameters run the kernel specialised for them (same results, ~3x fewer instructions)
-            if (ks_path && collapse) {
-                const int64_t n_c = r1 - r0, n_tiles = (n_c + 63) / 64;
-                pl->t_words[j].ensure((size_t)n_tiles * 5 * 64); pl->t_amb[j].ensure((size_t)n_tiles * 5 * 64);
-                pl->t_len[j].ensure((size_t)n_tiles * 64); pl->t_mult[j].ensure((size_t)n_tiles * 64);
-                PMX_HIP(hipMemsetAsync(pl->t_count.p + j, 0, sizeof(unsigned long long), st));
-                hipLaunchKernelGGL(k_collapse_reads, dim3((unsigned)((n_c + PMX_DEDUP_BLOCK - 1) / PMX_DEDUP_BLOCK)), dim3(PMX_DEDUP_BLOCK), PMX_DEDUP_LDS_BYTES, st,
-                                   rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, keep, perm, sp.k, fixed_len, rs->has_recs ? rs->recs.p : (const uint8_t*)nullptr, pl->t_words[j].p, pl->t_amb[j].p, pl->t_len[j].p,
-                                   pl->t_mult[j].p, pl->t_count.p + j);
-                PMX_HIP(hipGetLastError());
-                hipLaunchKernelGGL((l == 3 ? k_seed_histogram_ks<19, 8, 3> : k_seed_histogram_ks<19, 8, 1>), grid, block, lds_ks, st, pl->t_words[j].p, pl->t_amb[j].p,
-                                   (const int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, n_c, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p,
-                                   (const uint8_t*)nullptr, (const uint32_t*)nullptr, pl->t_len[j].p, pl->t_mult[j].p, pl->t_count.p + j);
-            } else if (ks_path)
-                hipLaunchKernelGGL((l == 3 ? k_seed_histogram_ks<19, 8, 3> : k_seed_histogram_ks<19, 8, 1>), grid, block, lds_ks, st, rs->words.p, rs->amb.p,
-                                   rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p, keep, perm,
-                                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const unsigned long long*)nullptr);
-            else
-                hipLaunchKernelGGL(k_seed_histogram, grid, block, lds, st, rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p,
-                                   pl->vals.p, pl->cap - 1, pl->counters.p, keep, quality_mode ? rs->qual.p : nullptr,
-                                   quality_mode ? pp->min_seed_quality : 0, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr);
-            PMX_HIP(hipGetLastError());
-            if (j > 0) {
-                PMX_HIP(hipEventRecord(ctx->seed_done[j - 1], st));
-                PMX_HIP(hipStreamWaitEvent(ctx->stream, ctx->seed_done[j - 1], 0));
-            }
-            }
-        }
-        if (bound_div == 1) break;
-        PMX_HIP(hipMemcpyAsync(pl->h_ctr, pl->counters.p, sizeof(pl->h_ctr), hipMemcpyDeviceToHost, ctx->stream));   // (finalize_histogram reuses them)
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
-        pl->h_ctr_valid = true;
-        const unsigned long long h_ovf = pl->h_ctr[PMX_CTR_OVERFLOW];
-        if (pmx::opt_str(pmx::O_PLACE_PROF)) fprintf(stderr, "[pmx place] seeding with bound 1/%lld: table %llu slots, %llu failed inserts\n", (long long)bound_div, (unsigned long long)pl->cap, h_ovf);
-        if (h_ovf == 0) break;
-        // the optimistic table overflowed: start over with the safe bound
-        PMX_HIP(hipMemsetAsync(pl->counters.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
-        hipLaunchKernelGGL(k_fill_u64, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, PMX_EMPTY_KEY, pl->cap);
-        PMX_HIP(hipMemsetAsync(pl->vals.p, 0, pl->cap * sizeof(unsigned long long), ctx->stream));
-        bound_div = 1;
+        S.seeding_order();
+        S.prepare_collapse();
+        if (S.n_par > 1) ensure_seed_streams(ctx);
+        const bool optimistic = S.bound_div > 1;
+        S.pass(optimistic);
+        if (optimistic && S.failed_inserts() != 0) {
+            // the optimistic table overflowed: start over with the safe bound
+            PMX_HIP(hipMemsetAsync(pl->counters.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
+            table_clear(ctx, pl);
+            S.pass(false);
         }
         timer_end(ctx, "seed", 1);
     }
@@ -809,6 +952,16 @@ static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, in
     PMX_CATCH
 }
 
+// host count of the reads the --dedup mask keeps
+static int64_t dedup_mask_count(pmx_ctx* ctx, pmx_place* pl, int64_t n) {
+    std::vector<uint8_t> h((size_t)n);
+    if (n > 0) PMX_HIP(hipMemcpyAsync(h.data(), pl->dd_keep.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    int64_t kept = 0;
+    for (uint8_t v : h) kept += v;
+    return kept;
+}
+
 // --dedup over several ranks (pmx_dist_dedup_reads drives these): the local mask + the hash pairs of the kept reads, and
 // the removal of the reads whose pair another rank already keeps
 int64_t pmx_place_dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, void* d_h1, void* d_h2, int64_t cap) {
@@ -818,14 +971,7 @@ int64_t pmx_place_dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs
     dedup_local(ctx, pl, rs);
     pl->dd_count.ensure(1);
     PMX_HIP(hipMemsetAsync(pl->dd_count.p, 0, sizeof(unsigned long long), ctx->stream));
-    if (!d_h1 || !d_h2) {   // count only: a reduction of the mask through the same kernel into scratch is not worth a variant
-        unsigned long long kept = 0;
-        std::vector<uint8_t> h((size_t)rs->n);
-        if (rs->n > 0) PMX_HIP(hipMemcpyAsync(h.data(), pl->dd_keep.p, (size_t)rs->n, hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
-        for (uint8_t v : h) kept += v;
-        return (int64_t)kept;
-    }
+    if (!d_h1 || !d_h2) return dedup_mask_count(ctx, pl, rs->n);   // count only: a reduction of the mask through the same kernel into scratch is not worth a variant
     if (cap < rs->n) return fail(PMX_ERR_CAPACITY, "dedup export buffers must hold one pair per read");
     if (rs->n > 0)
         hipLaunchKernelGGL(k_kept_read_hashes, dim3(grid_for(rs->n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_h2.p, pl->dd_keep.p, rs->n,
@@ -843,12 +989,7 @@ int64_t pmx_place_dedup_local_count(pmx_ctx* ctx, pmx_place* pl, const pmx_reads
     if (pl->dd_for != rs) return fail(PMX_ERR_ARG, "pmx_place_dedup_local must run on this read set first");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    std::vector<uint8_t> h((size_t)rs->n);
-    if (rs->n > 0) PMX_HIP(hipMemcpyAsync(h.data(), pl->dd_keep.p, (size_t)rs->n, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    int64_t kept = 0;
-    for (uint8_t v : h) kept += v;
-    return kept;
+    return dedup_mask_count(ctx, pl, rs->n);
     PMX_CATCH
 }
 
@@ -860,10 +1001,7 @@ int pmx_place_dedup_drop_seen(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs
     PMX_HIP(hipSetDevice(ctx->device));
     DevBuf<uint64_t> s1, s2;
     s1.alloc((size_t)n_seen); s2.alloc((size_t)n_seen);
-    size_t bytes = 0;
-    PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, (uint64_t*)d_seen_h1, s1.p, (uint64_t*)d_seen_h2, s2.p, (size_t)n_seen, 0, 64, ctx->stream));
-    pl->tmp.ensure(bytes);
-    PMX_HIP(rocprim::radix_sort_pairs(pl->tmp.p, bytes, (uint64_t*)d_seen_h1, s1.p, (uint64_t*)d_seen_h2, s2.p, (size_t)n_seen, 0, 64, ctx->stream));
+    PMX_ROCPRIM(pl->tmp, radix_sort_pairs, (uint64_t*)d_seen_h1, s1.p, (uint64_t*)d_seen_h2, s2.p, (size_t)n_seen, 0, 64, ctx->stream);
     hipLaunchKernelGGL(k_drop_seen_reads, dim3(grid_for(rs->n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_h2.p, rs->n, s1.p, s2.p, n_seen,
                        pl->dd_keep.p);
     PMX_HIP(hipGetLastError());
@@ -1026,61 +1164,90 @@ int pmx_place_histogram_merge(pmx_ctx* ctx, pmx_place* pl, const uint64_t* hash,
     PMX_CATCH
 }
 
-int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int64_t n_reads_total, pmx_place_result* res) {
-    if (!ctx || !pl || !pp || !res) return PMX_ERR_ARG;
-    PMX_TRY
-    PMX_HIP(hipSetDevice(ctx->device));
-    std::memset(res, 0, sizeof(*res));
-    for (int m = 0; m < 5; ++m) res->best_index[m] = UINT32_MAX;
-    // PMX_PLACE_PROF=1: host wall time of the sections of this call (each mark synchronises the stream first)
-    const bool prof = pmx::opt_str(pmx::O_PLACE_PROF) != nullptr;
-    auto t_prev = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!prof) return;
-        (void)hipStreamSynchronize(ctx->stream);
+// ------------------------------------------------------------------------------------- scoring
+namespace {
+
+// PMX_PLACE_PROF=1: host wall time of the sections of a pmx_place_score call (each mark synchronises the stream first)
+struct SectionClock {
+    const bool on;
+    const hipStream_t st;
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+    void mark(const char* what) {
+        if (!on) return;
+        (void)hipStreamSynchronize(st);
         const auto t = std::chrono::steady_clock::now();
         fprintf(stderr, "[pmx place score] %s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
         t_prev = t;
-    };
-    finalize_histogram(ctx, pl);
-    mark("finalize_histogram (compact + sort)");
-    const int64_t n = pl->n_hist;
-    const int G = ctx->n_cu * 8;
-    hipStream_t st = ctx->stream;
-    res->n_reads = n_reads_total;
+    }
+};
 
-    // ---- read-side filters (src/placement.cpp:1703-1856)
+// One call of pmx_place_score behind finalize_histogram: one function per step, in the order of the declarations.
+struct ScoreStage {
+    pmx_ctx* const ctx;
+    pmx_place* const pl;
+    const pmx_place_params* const pp;
+    const hipStream_t st;
+    const int G;
+    const PlaceSwitches sw;
+    // read_filters
+    int64_t n_kept = 0, min_support = 0;
+    unsigned long long h_stats[4] = {0, 0, 0, 0};
+    // score_terms: the five term arrays, n_changes doubles each, in pl->terms
+    double *t_mag = nullptr, *t_raw = nullptr, *t_cos = nullptr, *t_wc = nullptr, *t_lc = nullptr;
+    bool persistent = false;      // the scoring form just launched leaves a status word (k_score_chains / k_score_tree)
+    // fetch (the node scores go to pl->h_scores)
+    double h_scal[3] = {0, 0, 0};
+    uint32_t tree_status = 0;     // != 0: a wave of the persistent launch gave up
+
+    ScoreStage(pmx_ctx* c, pmx_place* p, const pmx_place_params* q) : ctx(c), pl(p), pp(q), st(c->stream), G(c->n_cu * 8) {}
+    void read_filters();
+    void mask_top_fraction(int64_t n);
+    void sums_and_probe_table();
+    void score_terms();
+    void score_nodes();
+    void begin_persistent();
+    void launch_chains();
+    void launch_tree();
+    void launch_levels();
+    void launch_levels_graph();
+    void fetch();
+    void redo_by_levels();
+};
+
+// optional top-fraction mask (seed_mask_fraction): the most frequent seeds die too.  Leaves h_stats of the histogram
+// after the homopolymer erase.
+void ScoreStage::mask_top_fraction(int64_t n) {
+    // unique seeds after homopolymer erase
+    PMX_HIP(hipMemsetAsync(pl->stats.p, 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
+    PMX_HIP(hipMemcpyAsync(h_stats, pl->stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    const int64_t n_mask = (int64_t)(pp->seed_mask_fraction * (double)h_stats[3]);   // :1775
+    if (n_mask <= 0) return;
+    DevBuf<uint64_t> key, key2;
+    DevBuf<uint32_t> idx, idx2;
+    key.alloc(n); key2.alloc(n); idx.alloc(n); idx2.alloc(n);
+    hipLaunchKernelGGL(k_mask_keys, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, key.p, idx.p);
+    PMX_ROCPRIM(pl->tmp, radix_sort_pairs, key.p, key2.p, idx.p, idx2.p, (size_t)n, 0, 64, st);
+    const int64_t nm = std::min<int64_t>(n_mask, (int64_t)h_stats[3]);
+    hipLaunchKernelGGL(k_mask_apply, dim3(grid_for(nm, 256, G)), dim3(256), 0, st, idx2.p, nm, pl->dead.p);
+    PMX_HIP(hipStreamSynchronize(st));   // (the four local buffers go out of scope)
+}
+
+// read-side filters (src/placement.cpp:1703-1856): homopolymer mask, optional top-fraction mask, stats, keep scan and
+// scatter -> pl->kept_hash / kept_log; n_kept, min_support, h_stats
+void ScoreStage::read_filters() {
+    const int64_t n = pl->n_hist;
     pl->dead.ensure(n);
     pl->flag.ensure(n + 1);
     pl->pos.ensure(n + 1);
     pl->kept_hash.ensure(n);
     pl->kept_log.ensure(n);
-    int64_t n_kept = 0, min_support = pp->min_read_support;
-    unsigned long long h_stats[4] = {0, 0, 0, 0};
+    min_support = pp->min_read_support;
     if (n > 0) {
         hipLaunchKernelGGL(k_mark_homopolymer, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_hash.p, n, homopolymer_hash(0, pl->params.k),
                            homopolymer_hash(1, pl->params.k), homopolymer_hash(2, pl->params.k), homopolymer_hash(3, pl->params.k), pl->dead.p);
-        if (pp->seed_mask_fraction > 0.0) {
-            // unique seeds after homopolymer erase
-            PMX_HIP(hipMemsetAsync(pl->stats.p, 0, 4 * sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
-            PMX_HIP(hipMemcpyAsync(h_stats, pl->stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, st));
-            PMX_HIP(hipStreamSynchronize(st));
-            const int64_t n_mask = (int64_t)(pp->seed_mask_fraction * (double)h_stats[3]);   // :1775
-            if (n_mask > 0) {
-                DevBuf<uint64_t> key, key2;
-                DevBuf<uint32_t> idx, idx2;
-                key.alloc(n); key2.alloc(n); idx.alloc(n); idx2.alloc(n);
-                hipLaunchKernelGGL(k_mask_keys, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, key.p, idx.p);
-                size_t bytes = 0;
-                PMX_HIP(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, 0, 64, st));
-                pl->tmp.ensure(bytes);
-                PMX_HIP(rocprim::radix_sort_pairs(pl->tmp.p, bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, 0, 64, st));
-                const int64_t nm = std::min<int64_t>(n_mask, (int64_t)h_stats[3]);
-                hipLaunchKernelGGL(k_mask_apply, dim3(grid_for(nm, 256, G)), dim3(256), 0, st, idx2.p, nm, pl->dead.p);
-                PMX_HIP(hipStreamSynchronize(st));
-            }
-        }
+        if (pp->seed_mask_fraction > 0.0) mask_top_fraction(n);
         PMX_HIP(hipMemsetAsync(pl->stats.p, 0, 4 * sizeof(unsigned long long), st));
         hipLaunchKernelGGL(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
         PMX_HIP(hipMemcpyAsync(h_stats, pl->stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, st));
@@ -1090,10 +1257,7 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
             min_support = est > 3.0 ? 2 : 1;
         }
         hipLaunchKernelGGL(k_keep_flags, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, min_support, pl->flag.p);
-        size_t bytes = 0;
-        PMX_HIP(rocprim::exclusive_scan(nullptr, bytes, pl->flag.p, pl->pos.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
-        pl->tmp.ensure(bytes);
-        PMX_HIP(rocprim::exclusive_scan(pl->tmp.p, bytes, pl->flag.p, pl->pos.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
+        PMX_ROCPRIM(pl->tmp, exclusive_scan, pl->flag.p, pl->pos.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
         uint32_t last_pos = 0, last_flag = 0;
         PMX_HIP(hipMemcpyAsync(&last_pos, pl->pos.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         PMX_HIP(hipMemcpyAsync(&last_flag, pl->flag.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1103,15 +1267,15 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
                            pl->kept_hash.p, pl->kept_log.p);
     } else if (min_support < 0) min_support = 1;
     pl->n_kept = n_kept;
-    mark("read-side filters (homopolymer, stats, keep scan/scatter)");
-    // canonical-order sums (src/placement.cpp:957-984)
-    {
-        const int64_t nb = (n_kept + PMX_SUM_BLOCK - 1) / PMX_SUM_BLOCK;
-        pl->partial.ensure((size_t)(2 * nb + 2));
-        if (nb > 0) hipLaunchKernelGGL(k_block_sums, dim3((unsigned)std::min<int64_t>(nb, (int64_t)G * 4)), dim3(64), 0, st, pl->kept_log.p, n_kept, pl->partial.p);
-        hipLaunchKernelGGL(k_sequential_sums, dim3(1), dim3(64), 0, st, pl->partial.p, nb, pl->scalars.p);
-    }
-    // probe table for the kept seeds
+}
+
+// canonical-order sums (src/placement.cpp:957-984), the probe table for the kept seeds, the weighted-containment
+// denominator -> pl->scalars, pl->tkeys / tvals
+void ScoreStage::sums_and_probe_table() {
+    const int64_t nb = (n_kept + PMX_SUM_BLOCK - 1) / PMX_SUM_BLOCK;
+    pl->partial.ensure((size_t)(2 * nb + 2));
+    if (nb > 0) hipLaunchKernelGGL(k_block_sums, dim3((unsigned)std::min<int64_t>(nb, (int64_t)G * 4)), dim3(64), 0, st, pl->kept_log.p, n_kept, pl->partial.p);
+    hipLaunchKernelGGL(k_sequential_sums, dim3(1), dim3(64), 0, st, pl->partial.p, nb, pl->scalars.p);
     pl->tcap = next_pow2((uint64_t)std::max<int64_t>(n_kept, 1) * 2 + 64);
     pl->tkeys.ensure(pl->tcap);
     pl->tvals.ensure(pl->tcap);
@@ -1121,178 +1285,170 @@ int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int
                            pl->tvals.p, pl->tcap - 1);
     hipLaunchKernelGGL(k_wc_denominator, dim3(1), dim3(1024), 0, st, pl->ch_hash.p, pl->ch_child.p, pl->root_beg, pl->root_end, pl->tkeys.p, pl->tvals.p,
                        pl->tcap - 1, n_kept > 0 ? 1 : 0, pl->scalars.p + 2);
-    double h_scal[3] = {0, 0, 0};   // fetched with the scores below (the device reads the scalars itself)
-    mark("sums, probe table, denominators");
+}
 
-    // ---- node scoring, one launch per BFS level (src/placement.cpp:701-918)
-    const int n_levels = (int)pl->level_off.size() - 1;
-    timer_begin(ctx, "score");
+// the five terms of every change of the index (k_score_terms) -> pl->terms, pl->term_meta
+void ScoreStage::score_terms() {
     const int64_t n_ch = pl->n_changes;
     pl->terms.ensure((size_t)std::max<int64_t>(n_ch, 1) * 5);
     pl->term_meta.ensure((size_t)std::max<int64_t>(n_ch, 1));
-    double* t_mag = pl->terms.p;
-    double *t_raw = t_mag + n_ch, *t_cos = t_mag + 2 * n_ch, *t_wc = t_mag + 3 * n_ch, *t_lc = t_mag + 4 * n_ch;
+    t_mag = pl->terms.p;
+    t_raw = t_mag + n_ch; t_cos = t_mag + 2 * n_ch; t_wc = t_mag + 3 * n_ch; t_lc = t_mag + 4 * n_ch;
     if (n_ch > 0)
         hipLaunchKernelGGL(k_score_terms, dim3(grid_for(n_ch, 256, G)), dim3(256), 0, st, pl->ch_hash.p, pl->ch_par.p, pl->ch_child.p, n_ch,
                            pl->tkeys.p, pl->tvals.p, pl->tcap - 1, n_kept > 0 ? 1 : 0, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p);
-    // The level launches are a fixed, launch-bound chain (122 dependent launches for the SARS tree, none of
-    // whose arguments change between calls): captured once into a HIP graph and replayed.
-    auto launch_levels = [&]() {
-        for (int lv = 0; lv < n_levels; ++lv) {
-            const int64_t beg = pl->level_off[lv], cnt = pl->level_off[lv + 1] - beg;
-            if (cnt <= 0) continue;
-            hipLaunchKernelGGL(k_score_level, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, pl->level_nodes.p + beg, cnt, pl->parent.p,
-                               pl->offsets.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p);
-        }
-    };
+}
+
+// the per-node flags of the persistent kernels: a node is done when its flag holds the epoch of this call
+void ScoreStage::begin_persistent() {
+    if (!pl->tree_done.p) {
+        pl->tree_done.alloc((size_t)pl->n_nodes + 1);
+        PMX_HIP(hipMemsetAsync(pl->tree_done.p, 0, sizeof(uint32_t) * ((size_t)pl->n_nodes + 1), st));
+        pl->tree_epoch = 0;
+    }
+    if (++pl->tree_epoch == 0) {   // wrapped: start over
+        PMX_HIP(hipMemsetAsync(pl->tree_done.p, 0, sizeof(uint32_t) * ((size_t)pl->n_nodes + 1), st));
+        pl->tree_epoch = 1;
+    }
+}
+
+// heavy-path chains (the default): one persistent launch, parent -> child through per-node flags; one workgroup per CU so
+// that every wave is resident
+void ScoreStage::launch_chains() {
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_chains + 3) / 4));
+    pl->last_grid_waves = (int64_t)grid * 4;
+    hipLaunchKernelGGL(k_score_chains, dim3(grid), dim3(256), 0, st, pl->chain_off.p, pl->n_chains, pl->chain_nodes.p, pl->chain_beg.p,
+                       pl->chain_end.p, pl->parent.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p,
+                       pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
+}
+
+// per-node flags in BFS order (k_score_tree; kept for comparison), resident like the chains kernel
+void ScoreStage::launch_tree() {
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_nodes + 3) / 4));
+    pl->last_grid_waves = (int64_t)grid * 4;
+    hipLaunchKernelGGL(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, t_mag, t_raw,
+                       t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
+                       pl->tree_done.p + pl->n_nodes);
+}
+
+// one launch per BFS level (k_score_level); needs no co-residency
+void ScoreStage::launch_levels() {
+    const int n_levels = (int)pl->level_off.size() - 1;
+    for (int lv = 0; lv < n_levels; ++lv) {
+        const int64_t beg = pl->level_off[lv], cnt = pl->level_off[lv + 1] - beg;
+        if (cnt <= 0) continue;
+        hipLaunchKernelGGL(k_score_level, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, pl->level_nodes.p + beg, cnt, pl->parent.p,
+                           pl->offsets.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p);
+    }
+}
+
+// The level launches are a fixed, launch-bound chain (122 dependent launches for the SARS tree, none of
+// whose arguments change between calls): captured once into a HIP graph and replayed.
+void ScoreStage::launch_levels_graph() {
     const void* sig[3] = {(const void*)t_mag, (const void*)pl->metrics5.p, (const void*)pl->term_meta.p};
-    bool tree_kernel = false;
+    if (!pl->level_graph_exec || pl->level_graph_sig[0] != sig[0] || pl->level_graph_sig[1] != sig[1] || pl->level_graph_sig[2] != sig[2]) {
+        if (pl->level_graph_exec) { (void)hipGraphExecDestroy(pl->level_graph_exec); pl->level_graph_exec = nullptr; }
+        hipGraph_t graph = nullptr;
+        PMX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+        launch_levels();
+        PMX_HIP(hipStreamEndCapture(st, &graph));
+        PMX_HIP(hipGraphInstantiate(&pl->level_graph_exec, graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+        for (int q = 0; q < 3; ++q) pl->level_graph_sig[q] = sig[q];
+    }
+    PMX_HIP(hipGraphLaunch(pl->level_graph_exec, st));
+}
+
+// node scoring (src/placement.cpp:701-918) in the form the switches select; what pmx_place_score_info reports
+void ScoreStage::score_nodes() {
     pl->last_redone = 0;
     pl->last_grid_waves = 0;
-    if (!pmx::opt_str(pmx::O_PLACE_LEVEL_KERNELS)) {
-        // one persistent launch, parent -> child through per-node flags (k_score_tree); one workgroup per CU so that
-        // every wave is resident
-        if (!pl->tree_done.p) {
-            pl->tree_done.alloc((size_t)pl->n_nodes + 1);
-            PMX_HIP(hipMemsetAsync(pl->tree_done.p, 0, sizeof(uint32_t) * ((size_t)pl->n_nodes + 1), st));
-            pl->tree_epoch = 0;
-        }
-        if (++pl->tree_epoch == 0) {   // wrapped: start over
-            PMX_HIP(hipMemsetAsync(pl->tree_done.p, 0, sizeof(uint32_t) * ((size_t)pl->n_nodes + 1), st));
-            pl->tree_epoch = 1;
-        }
-        if (pmx::opt_str(pmx::O_PLACE_TREE_KERNEL)) {   // per-node flags in BFS order (kept for comparison)
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_nodes + 3) / 4));
-            pl->last_form = PMX_SCORE_FORM_TREE;
-            pl->last_grid_waves = (int64_t)grid * 4;
-            hipLaunchKernelGGL(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, t_mag, t_raw,
-                               t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
-                               pl->tree_done.p + pl->n_nodes);
-        } else {
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_chains + 3) / 4));
-            pl->last_form = PMX_SCORE_FORM_CHAINS;
-            pl->last_grid_waves = (int64_t)grid * 4;
-            hipLaunchKernelGGL(k_score_chains, dim3(grid), dim3(256), 0, st, pl->chain_off.p, pl->n_chains, pl->chain_nodes.p, pl->chain_beg.p,
-                               pl->chain_end.p, pl->parent.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p,
-                               pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
-        }
-        tree_kernel = true;
-        if (pmx::opt_str(pmx::O_PLACE_TEST_STARVED)) {   // tests: pretend a wave gave up, so that the level-kernel redo runs
+    persistent = !sw.level_kernels;
+    if (persistent) {
+        begin_persistent();
+        pl->last_form = sw.tree_kernel ? PMX_SCORE_FORM_TREE : PMX_SCORE_FORM_CHAINS;
+        if (sw.tree_kernel) launch_tree();
+        else launch_chains();
+        if (sw.test_starved) {   // tests: pretend a wave gave up, so that the level-kernel redo runs
             const uint32_t one = 1;
             PMX_HIP(hipMemcpyAsync(pl->tree_done.p + pl->n_nodes, &one, sizeof(one), hipMemcpyHostToDevice, st));
         }
-    } else if (pmx::opt_str(pmx::O_PLACE_NO_GRAPH)) {
+    } else if (sw.no_graph) {
         pl->last_form = PMX_SCORE_FORM_LEVELS;
         launch_levels();
     } else {
         pl->last_form = PMX_SCORE_FORM_LEVELS_GRAPH;
-        if (!pl->level_graph_exec || pl->level_graph_sig[0] != sig[0] || pl->level_graph_sig[1] != sig[1] || pl->level_graph_sig[2] != sig[2]) {
-            if (pl->level_graph_exec) { (void)hipGraphExecDestroy(pl->level_graph_exec); pl->level_graph_exec = nullptr; }
-            hipGraph_t graph = nullptr;
-            PMX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            launch_levels();
-            PMX_HIP(hipStreamEndCapture(st, &graph));
-            PMX_HIP(hipGraphInstantiate(&pl->level_graph_exec, graph, nullptr, nullptr, 0));
-            (void)hipGraphDestroy(graph);
-            for (int q = 0; q < 3; ++q) pl->level_graph_sig[q] = sig[q];
-        }
-        PMX_HIP(hipGraphLaunch(pl->level_graph_exec, st));
+        launch_levels_graph();
     }
-    timer_end(ctx, "score", 1);
-    uint32_t tree_status = 0;
-    auto finish = [&]() {   // node scores from the accumulators, everything the host needs back in one synchronisation
-        hipLaunchKernelGGL(k_score_getters, dim3(grid_for(pl->n_nodes, 256, G)), dim3(256), 0, st, pl->metrics5.p, pl->counts2.p, pl->n_nodes, pl->scalars.p,
-                           n_kept, pl->scores5.p, pl->level_nodes.p, pl->scores_bfs.p);
-        PMX_HIP(hipGetLastError());
-        pl->h_scores.resize(5 * (size_t)pl->n_nodes);
-        PMX_HIP(hipMemcpyAsync(pl->h_scores.data(), pl->scores_bfs.p, sizeof(double) * 5 * (size_t)pl->n_nodes, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(h_scal, pl->scalars.p, sizeof(h_scal), hipMemcpyDeviceToHost, st));
-        if (tree_kernel) PMX_HIP(hipMemcpyAsync(&tree_status, pl->tree_done.p + pl->n_nodes, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
-    };
-    finish();
-    mark("terms + tree scoring + getters + D2H of the scores");
-    if (tree_status != 0) {
-        // The persistent kernel is only correct while all of its workgroups are resident; a wave that polled 2^24 times
-        // without seeing its parent's flag gave up (the GPU is shared with another process, or with collectives in
-        // flight).  The level kernels need no co-residency and add the same terms in the same order: redo with them.
-        PMX_HIP(hipMemsetAsync(pl->tree_done.p + pl->n_nodes, 0, sizeof(uint32_t), st));
-        tree_kernel = false;
-        tree_status = 0;
-        pl->last_redone = 1;
-        launch_levels();
-        PMX_HIP(hipGetLastError());
-        finish();
-        mark("level-kernel redo after a starved persistent launch");
-    }
+}
 
-    // ---- sequential best/tie rule in BFS visit order (src/placement.cpp:355-401)
-    // Every improvement of `best` resets the tie list to the improving node, so only the visit positions after the
-    // LAST improvement can contribute ties: pass 1 replays just the scalar part of the rule (best, idx, position of
-    // the last improvement), pass 2 runs the full rule from that position on.  Same result as one pass with the
-    // vectors, without pushing and clearing tens of thousands of transient ties.
-    Best best[5];
-    {
-        const int64_t nn = pl->n_nodes;
-        std::vector<uint8_t> flag((size_t)nn);
-        for (int m = 0; m < 5; ++m) {
-            const double* sc = pl->h_scores.data() + (size_t)m * (size_t)nn;   // this metric, in visit order
-            double b = 0.0, thr = 0.0 + std::max(0.0 * 0.0001, 1e-9);   // thr = best + tol, recomputed only when best moves
-            int64_t last = -1;
-            if (pp->force_leaf) {
-                for (int64_t j = 0; j < nn; ++j) {
-                    if (pl->h_has_child[pl->h_order[j]]) continue;
-                    if (sc[j] > thr) { b = sc[j]; thr = b + std::max(b * 0.0001, 1e-9); last = j; }
-                }
-            } else {
-                for (int64_t j = 0; j < nn; ++j)
-                    if (sc[j] > thr) { b = sc[j]; thr = b + std::max(b * 0.0001, 1e-9); last = j; }
-            }
-            if (last < 0) {   // never improved (all scores ~0): the plain rule, start to end
-                for (int64_t j = 0; j < nn; ++j) {
-                    const uint32_t nd = pl->h_order[j];
-                    if (pp->force_leaf && pl->h_has_child[nd]) continue;
-                    best[m].update(nd, sc[j]);
-                }
-                continue;
-            }
-            // after the last improvement `best` is fixed, so a later node ties iff score >= best - tol (and > 0); the
-            // rule's list, once sorted and de-duplicated, is {idx} + those nodes: flagged and read back in id order
-            best[m].best = b;
-            best[m].idx = pl->h_order[last];
-            const double tol = std::max(b * 0.0001, 1e-9);
-            std::fill(flag.begin(), flag.end(), (uint8_t)0);
-            flag[best[m].idx] = 1;
-            for (int64_t j = last + 1; j < nn; ++j) {
-                if (!(sc[j] >= b - tol && sc[j] > 0)) continue;
-                const uint32_t nd = pl->h_order[j];
-                if (pp->force_leaf && pl->h_has_child[nd]) continue;
-                flag[nd] = 1;
-            }
-            for (int64_t nd = 0; nd < nn; ++nd)
-                if (flag[(size_t)nd]) best[m].tied.push_back((uint32_t)nd);
-        }
+// node scores from the accumulators, everything the host needs back in one synchronisation -> pl->h_scores, h_scal, tree_status
+void ScoreStage::fetch() {
+    hipLaunchKernelGGL(k_score_getters, dim3(grid_for(pl->n_nodes, 256, G)), dim3(256), 0, st, pl->metrics5.p, pl->counts2.p, pl->n_nodes, pl->scalars.p,
+                       n_kept, pl->scores5.p, pl->level_nodes.p, pl->scores_bfs.p);
+    PMX_HIP(hipGetLastError());
+    pl->h_scores.resize(5 * (size_t)pl->n_nodes);
+    PMX_HIP(hipMemcpyAsync(pl->h_scores.data(), pl->scores_bfs.p, sizeof(double) * 5 * (size_t)pl->n_nodes, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(h_scal, pl->scalars.p, sizeof(h_scal), hipMemcpyDeviceToHost, st));
+    tree_status = 0;
+    if (persistent) PMX_HIP(hipMemcpyAsync(&tree_status, pl->tree_done.p + pl->n_nodes, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+}
+
+// The persistent kernel is only correct while all of its workgroups are resident; a wave that polled 2^24 times
+// without seeing its parent's flag gave up (the GPU is shared with another process, or with collectives in
+// flight).  The level kernels need no co-residency and add the same terms in the same order: redo with them.
+void ScoreStage::redo_by_levels() {
+    PMX_HIP(hipMemsetAsync(pl->tree_done.p + pl->n_nodes, 0, sizeof(uint32_t), st));
+    persistent = false;
+    pl->last_redone = 1;
+    launch_levels();
+    PMX_HIP(hipGetLastError());
+    fetch();
+}
+
+}  // namespace
+
+int pmx_place_score(pmx_ctx* ctx, pmx_place* pl, const pmx_place_params* pp, int64_t n_reads_total, pmx_place_result* res) {
+    if (!ctx || !pl || !pp || !res) return PMX_ERR_ARG;
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    std::memset(res, 0, sizeof(*res));
+    for (int m = 0; m < 5; ++m) res->best_index[m] = UINT32_MAX;
+    ScoreStage S(ctx, pl, pp);
+    SectionClock clock{S.sw.prof, ctx->stream};
+    finalize_histogram(ctx, pl);
+    clock.mark("finalize_histogram (compact + sort)");
+    res->n_reads = n_reads_total;
+    S.read_filters();
+    clock.mark("read-side filters (homopolymer, stats, keep scan/scatter)");
+    S.sums_and_probe_table();
+    clock.mark("sums, probe table, denominators");
+    timer_begin(ctx, "score");
+    S.score_terms();
+    S.score_nodes();
+    timer_end(ctx, "score", 1);
+    S.fetch();
+    clock.mark("terms + tree scoring + getters + D2H of the scores");
+    if (S.tree_status != 0) {
+        S.redo_by_levels();
+        clock.mark("level-kernel redo after a starved persistent launch");
     }
+    const std::array<Best, 5> best = best_and_ties(pl->h_scores.data(), pl->h_order, pl->h_has_child, pp->force_leaf != 0);
     for (int m = 0; m < 5; ++m) {
-        std::vector<uint32_t>& t = best[m].tied;
-        if (!t.empty()) {
-            std::sort(t.begin(), t.end());
-            t.erase(std::unique(t.begin(), t.end()), t.end());
-            best[m].idx = t.front();
-        }
-        pl->tied[m] = t;
+        pl->tied[m] = best[m].tied;
         res->best_score[m] = best[m].best;
         res->best_index[m] = best[m].idx;
-        res->n_tied[m] = (int64_t)t.size();
+        res->n_tied[m] = (int64_t)best[m].tied.size();
     }
-    mark("best / tie rule on the host");
-    res->n_unique_seeds = (int64_t)h_stats[3];
-    res->n_kept_seeds = n_kept;
-    res->total_seed_freq = (int64_t)h_stats[2];
-    res->min_support = min_support;
-    res->log_read_magnitude = std::sqrt(h_scal[0]);
-    res->log_containment_den = h_scal[1];
-    res->weighted_containment_den = h_scal[2];
+    clock.mark("best / tie rule on the host");
+    res->n_unique_seeds = (int64_t)S.h_stats[3];
+    res->n_kept_seeds = S.n_kept;
+    res->total_seed_freq = (int64_t)S.h_stats[2];
+    res->min_support = S.min_support;
+    res->log_read_magnitude = std::sqrt(S.h_scal[0]);
+    res->log_containment_den = S.h_scal[1];
+    res->weighted_containment_den = S.h_scal[2];
     return PMX_OK;
     PMX_CATCH
 }

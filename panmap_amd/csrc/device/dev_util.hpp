@@ -60,6 +60,20 @@ struct DevBuf {
     }
 };
 
+// rocprim's two-call protocol: `call(storage, bytes)` with no storage reports the temporary bytes it needs, `tmp` grows to
+// them, the second call does the work.  PMX_ROCPRIM(tmp, algorithm, arguments...) binds everything behind rocprim's first
+// two parameters, written once: PMX_ROCPRIM(pl->tmp, radix_sort_pairs, keys_in, keys_out, vals_in, vals_out, n, 0, 64, stream).
+// (The macro is for translation units that include rocprim; this header does not.)
+template <class Call>
+inline void rocprim_two_calls(DevBuf<char>& tmp, Call call) {
+    size_t bytes = 0;
+    PMX_HIP(call((void*)nullptr, bytes));
+    tmp.ensure(bytes);
+    PMX_HIP(call((void*)tmp.p, bytes));
+}
+#define PMX_ROCPRIM(tmp, algorithm, ...) \
+    pmx::rocprim_two_calls(tmp, [&](void* storage_, size_t& bytes_) { return rocprim::algorithm(storage_, bytes_, __VA_ARGS__); })
+
 // A stream with a HARDWARE queue of its own.  HIP multiplexes ordinary streams onto a few hardware queues
 // (GPU_MAX_HW_QUEUES, 4 by default); streams that land on one queue execute strictly in submission order: kernels of two
 // contexts then never overlap, and a kernel queued behind the barrier packet of a long host-to-device copy of ANOTHER stream

@@ -133,11 +133,8 @@ bool build_ref_index_device(hipStream_t st, const char* reference, int64_t ref_l
     hipLaunchKernelGGL(k_ref_encode, dim3((unsigned)((n_words + 127) / 128)), dim3(128), 0, st, d.ascii.p, len, d.seq.p, d.pk.p, d.pk_amb.p, n_words);
     const int n_slices = (len + kSlice - 1) / kSlice;
     hipLaunchKernelGGL(k_ref_sketch, dim3((unsigned)((n_slices + 63) / 64)), dim3(64), 0, st, d.seq.p, len, o.w, o.k, d.keys.p, cap, d.ctr.p);
-    size_t bytes = 0;
     const unsigned end_bit = (unsigned)(2 * o.k + kPosBits);
-    PMX_HIP(rocprim::radix_sort_keys(nullptr, bytes, d.keys.p, d.keys2.p, (size_t)cap, 0, end_bit, st));
-    d.tmp.ensure(bytes);
-    PMX_HIP(rocprim::radix_sort_keys(d.tmp.p, bytes, d.keys.p, d.keys2.p, (size_t)cap, 0, end_bit, st));
+    PMX_ROCPRIM(d.tmp, radix_sort_keys, d.keys.p, d.keys2.p, (size_t)cap, 0, end_bit, st);
     // the unused tail of the key buffer is all ones: the largest value in the sorted bits, and no minimizer has every
     // position bit set (ref_index_device_supported), so the sentinels sort behind the minimizers and k_ref_runs skips them
     hipLaunchKernelGGL(k_ref_runs, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, d.keys2.p, (int64_t)cap, d.pos.p, d.ctr.p);
