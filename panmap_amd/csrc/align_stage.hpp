@@ -73,16 +73,6 @@ struct pmx_aligner {
 
 namespace pmx {
 
-inline int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-#define PMX_TRY try {
-#define PMX_CATCH                                                           \
-    }                                                                       \
-    catch (const pmx::HipError& e) { return pmx::fail(PMX_ERR_DEVICE, e.msg); } \
-    catch (const std::exception& e) { return pmx::fail(PMX_ERR_DEVICE, e.what()); }
-
 // align_stage.hip: one attempt of pmx_align_readset with a CIGAR arena of `cigar_cap` words (the caller redoes an overflow)
 int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int paired, int revcomp_mate2, uint64_t cigar_cap, bool allow_dedup);
 // align_stage.hip: the grouped DP service (align_kernel_dpg.hip), shared with pmx_align_dp_batch

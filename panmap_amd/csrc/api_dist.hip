@@ -33,16 +33,6 @@ int64_t pmx_place_histogram_entries(pmx_ctx* ctx, pmx_place* pl);
 extern "C" int64_t pmx_place_dedup_local_count(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs);
 
 namespace {
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-#define PMX_TRY try {
-#define PMX_CATCH                                                      \
-    }                                                                  \
-    catch (const HipError& e) { return fail(PMX_ERR_DEVICE, e.msg); }  \
-    catch (const std::exception& e) { return fail(PMX_ERR_DEVICE, e.what()); }
-
 struct RcclApi {
     void* handle = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;

@@ -52,17 +52,6 @@ struct pmx_pileup {
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define PMX_TRY try {
-#define PMX_CATCH                                                      \
-    }                                                                  \
-    catch (const HipError& e) { return fail(PMX_ERR_DEVICE, e.msg); }  \
-    catch (const std::exception& e) { return fail(PMX_ERR_DEVICE, e.what()); }
-
 // the name hash of tweak_overlap_quality (sam.c:5853): __ac_Wang_hash(__ac_X31_hash_string(qname)) & 1 (htslib/khash.h:399-449)
 bool first_mate_keeps(const std::string& qname) {
     uint32_t h = qname.empty() ? 0u : (uint32_t)(int)(signed char)qname[0];

@@ -56,19 +56,11 @@
 using namespace pmx;
 
 namespace {
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-#define PMX_TRY try {
-#define PMX_CATCH                                                      \
-    }                                                                  \
-    catch (const HipError& e) { return fail(PMX_ERR_DEVICE, e.msg); }  \
-    catch (const std::exception& e) { return fail(PMX_ERR_DEVICE, e.what()); }
-
 // the EM's two fixed-order reductions: reads per partial column sum (k_meta_colsum) and values per block sum (k_meta_sum_blocks)
 constexpr int64_t kColsumChunk = 256;
 constexpr int64_t kSumBlock = 1024;
+// reads per launch of the seeding kernel in list mode: bounds the list arrays (one slot per base)
+constexpr int64_t kListChunk = 2000000;
 
 // index of `key` in the ascending array keys[0..n), or -1
 __device__ __forceinline__ int64_t find_sorted(const uint64_t* __restrict__ keys, int64_t n, uint64_t key) {
@@ -427,7 +419,6 @@ struct pmx_meta {
     DevBuf<uint32_t> d_cand;
     DevBuf<unsigned long long> mask_fwd, mask_rev;
     DevBuf<uint16_t> score;                 // [n_reads][n_cand]
-    std::vector<int32_t> h_max_score;       // per read, over the candidates
     // result
     std::vector<pmx_meta_group> groups;     // sorted by proportion, descending
     int em_rounds = 0, em_iterations = 0;
@@ -534,6 +525,622 @@ void score_rows(pmx_ctx* ctx, pmx_meta* m, int64_t first, int64_t count, uint16_
                            m->mask_rev.p, words, n_cand, out);
     PMX_HIP(hipGetLastError());
 }
+
+// a read set made inside a step: released when the step ends, on every way out of it (the step's caller has set the device)
+using ReadSetGuard = std::unique_ptr<pmx_readset>;
+
+// One call of pmx_meta_set_reads: one function per step, in the order the entry point calls them.  A step that calls into the
+// read-set or place API returns that API's code; the others throw (HipError).
+struct MetaReads {
+    pmx_ctx* const ctx;
+    pmx_meta* const m;
+    // the sample: the caller's reads, after drop_dusty the kept ones (kept_concat / kept_off hold them when any read was dropped)
+    const char* concat;
+    const int64_t* offsets;
+    int64_t n_reads;
+    std::string kept_concat;
+    std::vector<int64_t> kept_off;
+    const int64_t n_raw;              // reads the caller passed
+    int64_t n_dusty = 0;              // of them, dropped by --dust
+    int64_t n_kept_all;               // kept reads of the whole sample (--gpus N: over all ranks)
+    // seedmer_lists: the flat seedmer lists of the kept reads, read r at [r_off[r], r_off[r + 1])
+    std::vector<int64_t> r_off;
+    std::vector<uint64_t> r_hash;
+    std::vector<uint8_t> r_rev;
+    // what the chunks of seedmer_lists share, for as long as that step runs: the launch plan and the device arrays
+    struct ListChunks {
+        SeedParams sp;
+        size_t lds = 0;                    // dynamic LDS of k_seed_histogram
+        DevBuf<uint64_t> d_lh, d_oh;       // hashes: per slot / gathered
+        DevBuf<uint8_t> d_lr, d_or;        // orientations: per slot / gathered
+        DevBuf<uint32_t> d_ln;             // seedmers per read
+        DevBuf<int64_t> d_ooff;            // offsets of the gathered lists
+        DevBuf<unsigned long long> d_ctr;  // the seeding kernel's counters (not read here)
+    };
+
+    MetaReads(pmx_ctx* c, pmx_meta* mm, const char* cc, const int64_t* off, int64_t n)
+        : ctx(c), m(mm), concat(cc), offsets(off), n_reads(n), n_raw(n), n_kept_all(n) {}
+    struct ListView { const uint64_t* h; const uint8_t* v; int64_t n; };
+    ListView list(int64_t r) const { return ListView{r_hash.data() + r_off[(size_t)r], r_rev.data() + r_off[(size_t)r], r_off[(size_t)r + 1] - r_off[(size_t)r]}; }
+    // (lexicographic on the hash list, then on the orientation list: the order the vector comparisons gave)
+    int cmp(int64_t a, int64_t b) const { const ListView x = list(a), y = list(b); return cmp_lists(x.h, x.v, x.n, y.h, y.v, y.n); }
+
+    void drop_dusty();
+    int seedmer_lists();
+    int seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc);
+    void merge_equal_lists();
+    void merge_over_ranks();
+    void upload_lists();
+    int overlap_coefficients();
+};
+
+// --dust.  Reads: the caller's reads, m->dust_threshold.  Leaves: concat / offsets / n_reads describe the kept reads only
+// (re-concatenated when any was dropped), n_dusty, n_kept_all.  Nothing below knows about DUST.
+void MetaReads::drop_dusty() {
+    const double dust_thr = m->dust_threshold;
+    if (!(dust_thr < 100.0)) return;
+    // src/mgsr.cpp:1593-1594: a read with a non-zero score above the threshold is left out
+    std::vector<uint8_t> dusty((size_t)n_reads, 0);
+    unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    if (n_reads < 4096) n_thr = 1;
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < n_thr; ++t)
+        pool.emplace_back([&, t]() {
+            for (int64_t r = (int64_t)t; r < n_reads; r += n_thr) {
+                const double d = pmx_read_dust(concat + offsets[r], offsets[r + 1] - offsets[r], 64);
+                if (d != 0 && d > dust_thr) dusty[(size_t)r] = 1;
+            }
+        });
+    for (auto& th : pool) th.join();
+    // the dusty reads leave the sample altogether (src/mgsr.cpp:1590-1597: they never enter seqToIndexVec), the overlap
+    // coefficients included: everything below sees the kept reads only
+    for (uint8_t d : dusty) n_dusty += d;
+    if (n_dusty == 0) return;
+    kept_off.push_back(0);
+    for (int64_t r = 0; r < n_reads; ++r) {
+        if (dusty[(size_t)r]) continue;
+        kept_concat.append(concat + offsets[r], (size_t)(offsets[r + 1] - offsets[r]));
+        kept_off.push_back((int64_t)kept_concat.size());
+    }
+    concat = kept_concat.data();
+    offsets = kept_off.data();
+    n_reads = n_kept_all = (int64_t)kept_off.size() - 1;
+}
+
+// The reads' seedmer lists ON THE DEVICE (round 4; src/mgsr.cpp:1774-2237): the reads are packed 2 bit/base like any read set
+// and the generic seeding kernel runs in its list mode (k_seed_histogram: same syncmers, same k-min-mers as the place stage,
+// orientation = R < F); a gather makes the lists contiguous.  Chunks of reads bound the list arrays (one slot per base).
+// Reads: concat / offsets / n_reads.  Leaves: r_off / r_hash / r_rev.
+int MetaReads::seedmer_lists() {
+    const SyncmerParams& p = m->params;
+    ListChunks lc;
+    SeedParams& sp = lc.sp;
+    sp.k = p.k; sp.s = p.s; sp.t = p.t; sp.l = p.l; sp.open = p.open ? 1 : 0; sp.trim_start = 0; sp.trim_end = 0;
+    const int w = sp.k - sp.s + 1;
+    const size_t lds = lc.lds = (size_t)(2 * w + p.l) * PMX_SEED_BLOCK * sizeof(uint64_t) + (size_t)(PMX_SEED_BLOCK / 64) * (PMX_SEED_QCAP * sizeof(uint64_t) + 8);
+    if (lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
+    if (lds > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_seed_histogram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    r_off.assign((size_t)n_reads + 1, 0);
+    lc.d_ctr.alloc(PMX_CTR_N);
+    PMX_HIP(hipMemsetAsync(lc.d_ctr.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
+    for (int64_t c0 = 0; c0 < n_reads; c0 += kListChunk) {
+        const int rc = seedmer_lists_chunk(lc, c0, std::min(n_reads, c0 + kListChunk) - c0);
+        if (rc != PMX_OK) return rc;
+    }
+    return PMX_OK;
+}
+
+// One chunk: upload and pack reads [c0, c0 + nc), the seeding kernel in list mode (entry e of read r in slot woff[r] * 32 + e,
+// the count in d_ln[r]), the counts to the host for the offsets, the gather, the lists to the host.
+// Leaves: r_off (c0, c0 + nc], r_hash / r_rev grown by the chunk's seedmers.
+int MetaReads::seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc) {
+    pmx_readset* rs = nullptr;
+    int rc = pmx_readset_upload(ctx, concat, offsets + c0, nc, &rs);
+    if (rc != PMX_OK) return rc;
+    const ReadSetGuard rs_guard(rs);
+    rc = pmx_readset_pack(ctx, rs);
+    if (rc != PMX_OK) return rc;
+    const size_t slots = (size_t)std::max<int64_t>(rs->n_words, 1) * 32;
+    lc.d_lh.ensure(slots); lc.d_lr.ensure(slots); lc.d_ln.ensure((size_t)nc);
+    PMX_HIP(hipMemsetAsync(lc.d_ln.p, 0, sizeof(uint32_t) * (size_t)nc, ctx->stream));
+    hipLaunchKernelGGL(k_seed_histogram, dim3(grid_for(nc, PMX_SEED_BLOCK, ctx->n_cu * 16)), dim3(PMX_SEED_BLOCK), lc.lds, ctx->stream, rs->words.p, rs->amb.p,
+                       rs->woff.p, rs->off.p, (int64_t)0, nc, lc.sp, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0, lc.d_ctr.p,
+                       (const uint8_t*)nullptr, (const uint8_t*)nullptr, 0, lc.d_lh.p, lc.d_lr.p, lc.d_ln.p);
+    PMX_HIP(hipGetLastError());
+    std::vector<uint32_t> h_n((size_t)nc);
+    PMX_HIP(hipMemcpyAsync(h_n.data(), lc.d_ln.p, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<int64_t> o_off((size_t)nc + 1, 0);
+    for (int64_t i = 0; i < nc; ++i) o_off[(size_t)i + 1] = o_off[(size_t)i] + (int64_t)h_n[(size_t)i];
+    const int64_t tot = o_off[(size_t)nc];
+    const size_t base = r_hash.size();
+    r_hash.resize(base + (size_t)tot);
+    r_rev.resize(base + (size_t)tot);
+    if (tot > 0) {
+        lc.d_ooff.ensure((size_t)nc + 1); lc.d_oh.ensure((size_t)tot); lc.d_or.ensure((size_t)tot);
+        PMX_HIP(hipMemcpyAsync(lc.d_ooff.p, o_off.data(), sizeof(int64_t) * ((size_t)nc + 1), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_meta_gather_lists, dim3(grid_for(nc * 8, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, lc.d_lh.p, lc.d_lr.p, rs->woff.p,
+                           lc.d_ooff.p, nc, lc.d_oh.p, lc.d_or.p);
+        PMX_HIP(hipGetLastError());
+        PMX_HIP(hipMemcpyAsync(r_hash.data() + base, lc.d_oh.p, sizeof(uint64_t) * (size_t)tot, hipMemcpyDeviceToHost, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(r_rev.data() + base, lc.d_or.p, (size_t)tot, hipMemcpyDeviceToHost, ctx->stream));
+        PMX_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    for (int64_t i = 0; i < nc; ++i) r_off[(size_t)(c0 + i) + 1] = (int64_t)base + o_off[(size_t)i + 1];
+    return PMX_OK;
+}
+
+// Reads with the same seedmer list (hash and orientation, in order) are one read with a multiplicity; a read without
+// seedmers scores 0 everywhere and carries no weight in the EM (src/mgsr.cpp:8170-8173): dropped here.
+// Reads: r_off / r_hash / r_rev.  Leaves: m->h_read_off / h_seed_hash / h_seed_rev / h_mult, sorted by cmp_lists, with
+// m->n_reads / n_seedmers, and this rank's raw and dropped counts.
+void MetaReads::merge_equal_lists() {
+    std::vector<int64_t> order;
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (r_off[(size_t)r + 1] > r_off[(size_t)r]) order.push_back(r);
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { const int c = cmp(a, b); return c < 0 || (c == 0 && a < b); });
+    m->n_raw_reads = n_raw;
+    m->n_dust_dropped = n_dusty;
+    m->h_read_off.assign(1, 0);
+    m->h_seed_hash.clear(); m->h_seed_rev.clear(); m->h_mult.clear();
+    for (size_t i = 0; i < order.size(); ++i) {
+        if (i > 0 && cmp(order[i - 1], order[i]) == 0) { ++m->h_mult.back(); continue; }
+        const ListView o = list(order[i]);
+        m->h_seed_hash.insert(m->h_seed_hash.end(), o.h, o.h + o.n);
+        m->h_seed_rev.insert(m->h_seed_rev.end(), o.v, o.v + o.n);
+        m->h_read_off.push_back((int64_t)m->h_seed_hash.size());
+        m->h_mult.push_back(1);
+    }
+    m->n_reads = (int64_t)m->h_mult.size();
+    m->n_seedmers = (int64_t)m->h_seed_hash.size();
+}
+
+// --gpus N: the ranks' runs become the whole sample's; the raw, DUST-dropped and kept read counts are summed.
+// Reads and leaves what merge_equal_lists left, now for the whole sample, on every rank.
+void MetaReads::merge_over_ranks() {
+    const int64_t mine[5] = {n_raw, n_dusty, n_reads, m->n_reads, m->n_seedmers};
+    const std::vector<int64_t> counts = dist_exchange_counts(m->dist, mine, 5);
+    m->n_raw_reads = m->n_dust_dropped = n_kept_all = 0;
+    for (size_t r = 0; r < counts.size() / 5; ++r) { m->n_raw_reads += counts[5 * r]; m->n_dust_dropped += counts[5 * r + 1]; n_kept_all += counts[5 * r + 2]; }
+    merge_runs_over_ranks(m, counts, 5);
+}
+
+// Reads: the merged lists in m->h_*.  Leaves: m->h_uniq (the distinct hashes, ascending) and, on the device, the offsets,
+// every seedmer as its index into h_uniq with its orientation, and h_uniq itself.
+void MetaReads::upload_lists() {
+    m->h_uniq = m->h_seed_hash;
+    std::sort(m->h_uniq.begin(), m->h_uniq.end());
+    m->h_uniq.erase(std::unique(m->h_uniq.begin(), m->h_uniq.end()), m->h_uniq.end());
+    std::vector<uint32_t> uid((size_t)m->n_seedmers);
+    for (int64_t i = 0; i < m->n_seedmers; ++i)
+        uid[(size_t)i] = (uint32_t)(std::lower_bound(m->h_uniq.begin(), m->h_uniq.end(), m->h_seed_hash[(size_t)i]) - m->h_uniq.begin());
+    m->d_read_off.ensure((size_t)m->n_reads + 1);
+    m->d_seed_uid.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
+    m->d_seed_rev.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
+    m->d_uniq.ensure(std::max<size_t>(m->h_uniq.size(), 1));
+    PMX_HIP(hipMemcpyAsync(m->d_read_off.p, m->h_read_off.data(), sizeof(int64_t) * ((size_t)m->n_reads + 1), hipMemcpyHostToDevice, ctx->stream));
+    if (m->n_seedmers > 0) {
+        PMX_HIP(hipMemcpyAsync(m->d_seed_uid.p, uid.data(), sizeof(uint32_t) * (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->d_seed_rev.p, m->h_seed_rev.data(), (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
+        PMX_HIP(hipMemcpyAsync(m->d_uniq.p, m->h_uniq.data(), sizeof(uint64_t) * m->h_uniq.size(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    PMX_HIP(hipStreamSynchronize(ctx->stream));   // (uid goes out of scope)
+}
+
+// Overlap coefficients through the place stage: seed the reads on the device, score the tree with every read seed kept
+// (--gpus N: each rank seeds its kept reads, the histograms are merged, and every rank scores the tree with the whole
+//  sample's kept-read count -- the coefficients, and so the candidates, are the same on every rank).
+// Reads: concat / offsets / n_reads, n_kept_all.  Leaves: m->oc.
+int MetaReads::overlap_coefficients() {
+    m->oc.assign((size_t)m->n_nodes, 0.0);
+    if (n_kept_all <= 0) return PMX_OK;
+    int rc;
+    {   // (the read set is released as soon as the tree is scored)
+        pmx_readset* rs = nullptr;
+        rc = pmx_readset_upload(ctx, concat, offsets, n_reads, &rs);
+        if (rc != PMX_OK) return rc;
+        const ReadSetGuard rs_guard(rs);
+        pmx_place_params pp;
+        memset(&pp, 0, sizeof(pp));
+        pp.min_read_support = 1;
+        pmx_place_result res;
+        rc = pmx_readset_pack(ctx, rs);
+        if (rc == PMX_OK) rc = pmx_place_reset(ctx, m->placer);
+        if (rc == PMX_OK) rc = pmx_place_add_reads(ctx, m->placer, rs, &pp);
+        if (rc == PMX_OK && m->dist) rc = pmx_dist_merge_histograms(m->dist, m->placer);
+        if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept_all, &res);
+    }
+    if (rc != PMX_OK) return rc;
+    std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
+    rc = pmx_place_node_outputs(ctx, m->placer, nullptr, nullptr, counts2.data());
+    if (rc != PMX_OK) return rc;
+    for (int64_t v = 0; v < m->n_nodes; ++v)
+        m->oc[(size_t)v] = counts2[2 * (size_t)v + 1] > 0 ? (double)counts2[2 * (size_t)v] / (double)counts2[2 * (size_t)v + 1] : 0.0;
+    return PMX_OK;
+}
+
+// ---- pmx_meta_score's steps
+
+// The candidates (no HIP): the nodes of the `top_oc` best distinct overlap coefficients, or exactly the nodes of the
+// override; ascending DFS indices, each once.  False: an override node out of range.
+bool select_candidates(const std::vector<double>& oc, int64_t n_nodes, int64_t top_oc, const uint32_t* cand_override, int64_t n_override,
+                       std::vector<uint32_t>& cand) {
+    cand.clear();
+    if (n_override > 0) {
+        cand.assign(cand_override, cand_override + n_override);
+        for (uint32_t v : cand)
+            if ((int64_t)v >= n_nodes) return false;
+    } else {
+        std::vector<uint32_t> by_oc((size_t)n_nodes);
+        std::iota(by_oc.begin(), by_oc.end(), 0u);
+        std::stable_sort(by_oc.begin(), by_oc.end(), [&](uint32_t a, uint32_t b) { return oc[a] > oc[b]; });
+        int64_t ranks = 0;
+        double cur = -1.0;
+        for (uint32_t v : by_oc) {
+            if (oc[v] != cur) {
+                cur = oc[v];
+                if (++ranks > top_oc) break;
+            }
+            cand.push_back(v);
+        }
+    }
+    std::sort(cand.begin(), cand.end());
+    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+    return true;
+}
+
+// this rank's rows of the score matrix: all merged reads, or (--gpus N, pass A) a balanced contiguous slice of them
+void own_row_slice(pmx_meta* m) {
+    m->row_first = 0;
+    m->row_count = m->n_reads;
+    if (m->dist) {
+        const int64_t rank = pmx_dist_rank(m->dist), world = pmx_dist_world(m->dist);
+        m->row_first = m->n_reads * rank / world;
+        m->row_count = m->n_reads * (rank + 1) / world - m->row_first;
+    }
+}
+
+// Reads: m->cand, the oriented index, m->d_uniq.  Leaves: m->d_cand and the two (seedmer x candidate) bit matrices,
+// enqueued on the context's stream.
+void build_masks(pmx_ctx* ctx, pmx_meta* m) {
+    const int n_cand = (int)m->cand.size(), words = (n_cand + 63) / 64;
+    m->d_cand.ensure((size_t)n_cand);
+    PMX_HIP(hipMemcpyAsync(m->d_cand.p, m->cand.data(), sizeof(uint32_t) * (size_t)n_cand, hipMemcpyHostToDevice, ctx->stream));
+    const size_t mask_words = m->h_uniq.size() * (size_t)words;
+    m->mask_fwd.ensure(std::max<size_t>(mask_words, 1));
+    m->mask_rev.ensure(std::max<size_t>(mask_words, 1));
+    PMX_HIP(hipMemsetAsync(m->mask_fwd.p, 0, sizeof(unsigned long long) * std::max<size_t>(mask_words, 1), ctx->stream));
+    PMX_HIP(hipMemsetAsync(m->mask_rev.p, 0, sizeof(unsigned long long) * std::max<size_t>(mask_words, 1), ctx->stream));
+    if (m->n_changes > 0)
+        hipLaunchKernelGGL(k_meta_mask_events, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, m->ch_key.p, m->ch_pc.p,
+                           m->ch_cc.p, m->ch_node.p, m->n_changes, m->subtree_end.p, m->d_uniq.p, (int64_t)m->h_uniq.size(), m->d_cand.p, n_cand, words,
+                           m->mask_fwd.p, m->mask_rev.p);
+}
+
+// ---- pmx_meta_em's steps
+
+// One call of pmx_meta_em, for a sample with candidates and reads: one function per step, in the order the entry point
+// calls them; what a step leaves is constant afterwards.
+struct EmStage {
+    pmx_ctx* const ctx;
+    pmx_meta* const m;
+    const pmx_meta_params* const mp;
+    const hipStream_t st;
+    const int n_cand;
+    const int64_t n_reads;
+    const int world;
+    // group_columns: one column per distinct score column
+    std::vector<int> col_cand;                         // column -> candidate position of its representative (the group's first)
+    std::vector<std::vector<uint32_t>> col_members;    // column -> the other candidates (DFS indices) with that score column
+    // kept_rows_*: the merged reads the EM runs on, ascending
+    DevBuf<uint64_t> d_dig;                            // the one-rank path's column digests (made on both paths)
+    std::vector<int64_t> rows;
+    int64_t n_rows = 0;
+    // likelihood_tables, per kept row j: P(read | node) with score s at tab[tab_off[j] + s], the read's multiplicity
+    std::vector<double> tab, weight;
+    std::vector<uint32_t> tab_off;
+    double inv_total = 0.0;                            // 1 / the sum of the weights
+    int n_chunks = 0;                                  // partial column sums (kColsumChunk rows each) over all kept rows
+    int64_t n_bsum = 0;                                // block sums (kSumBlock rows each) over all kept rows
+    // own_em_rows: kept rows [e_first, e_first + e_count) are this rank's, as rows loc_rows[] of the matrix score_p
+    int64_t e_first = 0, e_count = 0, per = 0;         // per: rows per rank in the gathers
+    const uint16_t* score_p = nullptr;
+    std::vector<int64_t> loc_rows;
+    int loc_chunks = 0;
+    int64_t loc_bsum = 0, slot_chunks = 0, slot_bsum = 0;   // this rank's partials and block sums; per rank in the gathers
+    // upload_rows: device buffers of the call (the per-column ones grow in EmRound)
+    DevBuf<int64_t> d_rows;
+    DevBuf<uint32_t> d_tab_off;
+    DevBuf<double> d_tab, d_weight, d_denom, d_llh, d_props, d_out, d_part, d_bsum, d_gpart, d_gbsum;
+    DevBuf<int> d_cols;
+    const double* bsum_all = nullptr;                  // the block sums of all rows: d_bsum, or (--gpus N) the gathered d_gbsum
+
+    EmStage(pmx_ctx* c, pmx_meta* mm, const pmx_meta_params* p)
+        : ctx(c), m(mm), mp(p), st(c->stream), n_cand((int)mm->cand.size()), n_reads(mm->n_reads), world(mm->dist ? pmx_dist_world(mm->dist) : 1) {
+        d_dig.alloc(2 * (size_t)n_cand);
+    }
+    void group_columns(const std::vector<uint64_t>& digests, int n_ranks);
+    void kept_rows_one_rank();
+    void kept_rows_dist();
+    void likelihood_tables();
+    void own_em_rows();
+    void upload_rows();
+    void publish_groups(const std::vector<int>& cols, const std::vector<std::vector<uint32_t>>& members, const std::vector<double>& props);
+};
+
+// Columns: one per distinct score column, in the order of their first candidates.  digests[2 * (r * n_cand + c)], + 1: the
+// 128-bit digest of candidate c's column over rank r's rows.  Two columns are equal iff they are equal on every rank's rows:
+// the key of a column is its digests in rank order (one rank: its one digest).  The map is only asked `find` and `emplace`,
+// never walked, so its ordering of the keys plays no part: a column joins the group of the first candidate with its key.
+// Leaves: col_cand / col_members.
+void EmStage::group_columns(const std::vector<uint64_t>& digests, int n_ranks) {
+    std::map<std::vector<uint64_t>, int> first_of;
+    std::vector<uint64_t> key(2 * (size_t)n_ranks);
+    for (int c = 0; c < n_cand; ++c) {
+        for (int r = 0; r < n_ranks; ++r) memcpy(&key[2 * (size_t)r], &digests[2 * ((size_t)r * (size_t)n_cand + (size_t)c)], 2 * sizeof(uint64_t));
+        auto it = first_of.find(key);
+        if (it == first_of.end()) { first_of.emplace(key, (int)col_cand.size()); col_cand.push_back(c); col_members.emplace_back(); }
+        else col_members[(size_t)it->second].push_back(m->cand[(size_t)c]);
+    }
+}
+
+// One rank: the column digests, then the whole score matrix to the host for the rows.
+// Reads: m->score.  Leaves: the columns and `rows`, the reads that score somewhere (the others carry no weight,
+// src/mgsr.cpp:8170-8173) and that --discard keeps.
+void EmStage::kept_rows_one_rank() {
+    hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, n_reads, n_cand, d_dig.p);
+    std::vector<uint64_t> dig(2 * (size_t)n_cand);
+    PMX_HIP(hipMemcpyAsync(dig.data(), d_dig.p, sizeof(uint64_t) * dig.size(), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    group_columns(dig, 1);
+    std::vector<uint16_t> h_score((size_t)n_reads * (size_t)n_cand);
+    PMX_HIP(hipMemcpyAsync(h_score.data(), m->score.p, sizeof(uint16_t) * h_score.size(), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    for (int64_t r = 0; r < n_reads; ++r) {
+        int mx = 0;
+        for (int c = 0; c < n_cand; ++c) mx = std::max<int>(mx, h_score[(size_t)r * (size_t)n_cand + (size_t)c]);
+        const int64_t n_seed = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
+        // --discard (src/main.cpp:1229-1240): the threshold is TRUNCATED to an integer there,
+        // `maxScore < static_cast<int>(seedmers * discard)`, so a read with int(n * d) <= max < n * d stays in the EM
+        if (mx == 0 || mx < (int)((double)n_seed * mp->discard)) continue;
+        rows.push_back(r);
+    }
+    n_rows = (int64_t)rows.size();
+}
+
+// --gpus N, pass A: the column digests of this rank's slice and its reads' --discard flags (k_meta_row_keep), one
+// all-gather of both.  The groups (and their order: by first candidate) are the one-rank groups, see group_columns.
+// Reads: m->score (this rank's slice).  Leaves: the columns and `rows`, the same on every rank.
+void EmStage::kept_rows_dist() {
+    const int64_t max_slice = (n_reads + world - 1) / world;
+    const size_t dig_bytes = sizeof(uint64_t) * 2 * (size_t)n_cand, part_bytes = dig_bytes + (((size_t)max_slice + 7) & ~(size_t)7);
+    DevBuf<char> d_mine, d_all;
+    d_mine.alloc(part_bytes);
+    d_all.alloc(part_bytes * (size_t)world);
+    PMX_HIP(hipMemsetAsync(d_mine.p, 0, part_bytes, st));
+    hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, m->row_count, n_cand, (uint64_t*)d_mine.p);
+    if (m->row_count > 0)
+        hipLaunchKernelGGL(k_meta_row_keep, dim3(grid_for(m->row_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->score.p, m->row_count, n_cand,
+                           m->d_read_off.p + m->row_first, mp->discard, (uint8_t*)(d_mine.p + dig_bytes));
+    PMX_HIP(hipGetLastError());
+    dist_all_gather(m->dist, d_mine.p, part_bytes, d_all.p);
+    std::vector<char> all(part_bytes * (size_t)world);
+    PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    std::vector<uint64_t> dig(2 * (size_t)n_cand * (size_t)world);
+    for (int r = 0; r < world; ++r) memcpy(&dig[2 * (size_t)n_cand * (size_t)r], all.data() + (size_t)r * part_bytes, dig_bytes);
+    group_columns(dig, world);
+    for (int r = 0; r < world; ++r) {
+        const int64_t f = n_reads * r / world, n = n_reads * (r + 1) / world - f;
+        const uint8_t* keep = (const uint8_t*)(all.data() + (size_t)r * part_bytes + dig_bytes);
+        for (int64_t i = 0; i < n; ++i)
+            if (keep[i]) rows.push_back(f + i);
+    }
+    n_rows = (int64_t)rows.size();
+}
+
+// P(read | node) = err^(n - s) * (1 - err)^s for the distinct n of the reads: tables computed with the host libm.
+// Reads: rows, the reads' lengths and multiplicities.  Leaves: tab / tab_off / weight / inv_total, n_chunks / n_bsum.
+void EmStage::likelihood_tables() {
+    std::map<int64_t, uint32_t> off_of_n;
+    tab_off.resize((size_t)n_rows);
+    weight.resize((size_t)n_rows);
+    double total_weight = 0.0;
+    for (int64_t j = 0; j < n_rows; ++j) {
+        const int64_t r = rows[(size_t)j], n_seed = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
+        auto it = off_of_n.find(n_seed);
+        if (it == off_of_n.end()) {
+            it = off_of_n.emplace(n_seed, (uint32_t)tab.size()).first;
+            for (int64_t s = 0; s <= n_seed; ++s) tab.push_back(std::pow(mp->error_rate, (double)(n_seed - s)) * std::pow(1.0 - mp->error_rate, (double)s));
+        }
+        tab_off[(size_t)j] = it->second;
+        weight[(size_t)j] = (double)m->h_mult[(size_t)r];
+        total_weight += weight[(size_t)j];   // (integers: exact in any order)
+    }
+    inv_total = 1.0 / total_weight;
+    // (kColsumChunk reads per partial column sum; with 2,048: 2,200 waves for 3,000 columns x 90k reads, each a serial walk: 373 us per pass)
+    n_chunks = (int)((n_rows + kColsumChunk - 1) / kColsumChunk);
+    n_bsum = (n_rows + kSumBlock - 1) / kSumBlock;
+}
+
+// This rank's EM rows: all of them, or (--gpus N, pass B) a contiguous range whose bounds are multiples of both
+// reduction widths -- the rank's chunk partials and block sums are then whole global ones, at global positions
+// rank * per / width of the all-gathered arrays, and the one-rank fold and store kernels add them in the one-rank order.
+// Reads: rows.  Leaves: e_first / e_count / per, score_p / loc_rows and the counts of partials and block sums.
+void EmStage::own_em_rows() {
+    e_first = 0; e_count = per = n_rows;
+    score_p = m->score.p;
+    loc_rows = rows;
+    if (m->dist) {
+        const int rank = pmx_dist_rank(m->dist);
+        const int64_t align = std::lcm(kColsumChunk, kSumBlock);
+        per = ((n_rows + world - 1) / world + align - 1) / align * align;
+        e_first = std::min<int64_t>(n_rows, per * rank);
+        e_count = std::min<int64_t>(n_rows, e_first + per) - e_first;
+        // pass B: the merged reads of the range, scored again into a matrix of their own
+        const int64_t r_lo = e_count > 0 ? rows[(size_t)e_first] : 0, r_hi = e_count > 0 ? rows[(size_t)(e_first + e_count - 1)] + 1 : 0;
+        m->score_em.ensure((size_t)std::max<int64_t>(r_hi - r_lo, 1) * (size_t)n_cand);
+        score_rows(ctx, m, r_lo, r_hi - r_lo, m->score_em.p);
+        score_p = m->score_em.p;
+        loc_rows.assign((size_t)e_count, 0);
+        for (int64_t j = 0; j < e_count; ++j) loc_rows[(size_t)j] = rows[(size_t)(e_first + j)] - r_lo;
+    }
+    loc_chunks = (int)((e_count + kColsumChunk - 1) / kColsumChunk);
+    loc_bsum = (e_count + kSumBlock - 1) / kSumBlock;
+    slot_chunks = (per + kColsumChunk - 1) / kColsumChunk;
+    slot_bsum = (per + kSumBlock - 1) / kSumBlock;
+}
+
+// Reads: loc_rows and this rank's range of tab_off / weight, tab.  Leaves: them on the device, with room for the
+// denominators, the log-likelihood terms and the block sums.
+void EmStage::upload_rows() {
+    d_rows.alloc((size_t)e_count); d_tab_off.alloc((size_t)e_count); d_tab.alloc(tab.size()); d_weight.alloc((size_t)e_count);
+    d_denom.alloc((size_t)e_count); d_llh.alloc((size_t)e_count);
+    if (e_count > 0) {
+        PMX_HIP(hipMemcpyAsync(d_rows.p, loc_rows.data(), sizeof(int64_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_tab_off.p, tab_off.data() + e_first, sizeof(uint32_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_weight.p, weight.data() + e_first, sizeof(double) * (size_t)e_count, hipMemcpyHostToDevice, st));
+    }
+    PMX_HIP(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    d_bsum.alloc((size_t)slot_bsum);
+    if (m->dist) d_gbsum.alloc((size_t)slot_bsum * (size_t)world);
+    bsum_all = m->dist ? d_gbsum.p : d_bsum.p;
+}
+
+// Reads: the columns the rounds left, with their proportions.  Leaves: m->groups, by proportion, descending.
+void EmStage::publish_groups(const std::vector<int>& cols, const std::vector<std::vector<uint32_t>>& members, const std::vector<double>& props) {
+    for (size_t i = 0; i < cols.size(); ++i) {
+        pmx_meta_group g;
+        g.node = m->cand[(size_t)cols[i]];
+        g.members = members[i];
+        g.prop = props[i];
+        m->groups.push_back(std::move(g));
+    }
+    std::stable_sort(m->groups.begin(), m->groups.end(), [](const pmx_meta_group& a, const pmx_meta_group& b) { return a.prop > b.prop; });
+}
+
+// One round of the EM over the columns `cols`: its device vectors, then the SQUAREM loop.
+// The whole SQUAREM loop stays on the device: the proportion vectors never leave it, the small vector arithmetic runs in
+// single-block kernels with the host loop's own order of operations, and the host only looks at the convergence flag
+// every 16 iterations (launches queued past convergence return at once).  Per iteration: 6 passes over the score
+// matrix (4 x k_meta_denoms, 2 x k_meta_colsum) and 13 small launches; before, 4 host round trips.  --gpus N: the
+// passes run over the rank's rows, and 4 all-gathers per iteration (chunk partials x 2, block sums x 2) bring every
+// rank the global arrays; the single-block kernels then run replicated on identical inputs, so the convergence flag
+// and the iteration count agree on every rank and every rank issues the same sequence of collectives (queued past
+// convergence too).
+struct EmRound {
+    EmStage* const S;
+    pmx_meta* const m;
+    const hipStream_t st;
+    const int n_cols;
+    DevBuf<double> d_p0, d_p1, d_p2, d_sq;
+    DevBuf<EmCtl> d_ctl;
+    DevBuf<double> d_em_work;
+    double* em_work = nullptr;           // the small kernels' scratch vector in global memory, when LDS cannot hold it
+    const double* part_all = nullptr;    // the chunk partials of all rows: d_part, or (--gpus N) the gathered d_gpart
+    const int* d_done = nullptr;
+    EmCtl h_ctl;                         // as of the last look; after run, the round's iterations and log-likelihood
+
+    EmRound(EmStage* stage, const std::vector<int>& cols);
+    void denoms(const double* pr);
+    void em_step(const double* from, double* to);
+    void log_likelihood(const double* pr, int which);
+    void run(std::vector<double>& props);
+};
+
+// Reads: the round's columns.  Leaves: them on the device, the control block zeroed, the LDS attribute of the small kernels.
+EmRound::EmRound(EmStage* stage, const std::vector<int>& cols) : S(stage), m(stage->m), st(stage->st), n_cols((int)cols.size()) {
+    S->d_cols.ensure((size_t)n_cols); S->d_props.ensure((size_t)n_cols); S->d_out.ensure((size_t)n_cols); S->d_part.ensure((size_t)S->slot_chunks * (size_t)n_cols);
+    if (m->dist) S->d_gpart.ensure((size_t)S->slot_chunks * (size_t)n_cols * (size_t)S->world);
+    part_all = m->dist ? S->d_gpart.p : S->d_part.p;
+    PMX_HIP(hipMemcpyAsync(S->d_cols.p, cols.data(), sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    d_p0.alloc((size_t)n_cols); d_p1.alloc((size_t)n_cols); d_p2.alloc((size_t)n_cols); d_sq.alloc((size_t)n_cols);
+    d_ctl.alloc(1);
+    memset(&h_ctl, 0, sizeof(h_ctl));
+    PMX_HIP(hipMemcpyAsync(d_ctl.p, &h_ctl, sizeof(h_ctl), hipMemcpyHostToDevice, st));
+    d_done = &d_ctl.p->done;
+    // the in-order sums of the small kernels read a copy of the vector in LDS (2 x n_cols doubles at most); beyond 160 KB a
+    // scratch vector in global memory stands in
+    const size_t em_lds = 2 * sizeof(double) * (size_t)n_cols;
+    if (em_lds > (size_t)160 * 1024) { d_em_work.alloc(2 * (size_t)n_cols); em_work = d_em_work.p; }
+    else if (em_lds > (size_t)64 * 1024) {
+        PMX_HIP(hipFuncSetAttribute((const void*)k_em_normalize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
+        PMX_HIP(hipFuncSetAttribute((const void*)k_em_extrapolate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
+    }
+}
+
+void EmRound::denoms(const double* pr) {
+    hipLaunchKernelGGL(k_meta_denoms, dim3(grid_for(S->e_count * 64, 256, S->ctx->n_cu * 8)), dim3(256), 0, st, S->score_p, S->n_cand, S->d_cols.p, n_cols, pr,
+                       S->d_rows.p, S->e_count, S->d_tab_off.p, S->d_tab.p, S->d_weight.p, S->d_denom.p, S->d_llh.p, d_done);
+}
+
+// updateProps (src/mgsr.cpp:4341-4372) + normalizeProps
+void EmRound::em_step(const double* from, double* to) {
+    if (S->e_count > 0) {
+        denoms(from);
+        hipLaunchKernelGGL(k_meta_colsum, dim3((n_cols + 63) / 64, S->loc_chunks), dim3(64), 0, st, S->score_p, S->n_cand, S->d_cols.p, n_cols, from, S->d_rows.p,
+                           S->e_count, kColsumChunk, S->d_tab_off.p, S->d_tab.p, S->d_weight.p, S->d_denom.p, S->d_part.p, d_done);
+    }
+    if (m->dist) dist_all_gather(m->dist, S->d_part.p, sizeof(double) * (size_t)S->slot_chunks * (size_t)n_cols, S->d_gpart.p);
+    hipLaunchKernelGGL(k_meta_fold, dim3((n_cols + 63) / 64), dim3(64), 0, st, part_all, S->n_chunks, n_cols, S->inv_total, S->d_out.p, d_done);
+    hipLaunchKernelGGL(k_em_normalize, dim3(1), dim3(256), em_work ? 0 : sizeof(double) * (size_t)n_cols, st, S->d_out.p, to, n_cols, d_ctl.p, em_work);
+}
+
+// getExp (src/mgsr.cpp:4385-4388)
+void EmRound::log_likelihood(const double* pr, int which) {
+    if (S->e_count > 0) {
+        denoms(pr);
+        hipLaunchKernelGGL(k_meta_sum_blocks, dim3((unsigned)((S->loc_bsum + 3) / 4)), dim3(256), 0, st, S->d_llh.p, S->e_count, S->d_bsum.p, d_done);
+    }
+    if (m->dist) dist_all_gather(m->dist, S->d_bsum.p, sizeof(double) * (size_t)S->slot_bsum, S->d_gbsum.p);
+    hipLaunchKernelGGL(k_em_store_llh, dim3(1), dim3(64), 0, st, S->bsum_all, S->n_bsum, d_ctl.p, which);
+}
+
+// runSquareEM (src/mgsr.cpp:4394-4443) from uniform proportions, in batches of 16 iterations between two looks at the convergence flag.
+// Leaves: props, h_ctl.
+void EmRound::run(std::vector<double>& props) {
+    const pmx_meta_params* mp = S->mp;
+    props.assign((size_t)n_cols, 1.0 / (double)n_cols);
+    PMX_HIP(hipMemcpyAsync(S->d_props.p, props.data(), sizeof(double) * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    const int look_every = 16;
+    for (int iter = 0; iter < mp->em_max_iterations;) {
+        const int batch = std::min(look_every, mp->em_max_iterations - iter);
+        for (int b = 0; b < batch; ++b) {
+            hipLaunchKernelGGL(k_em_copy, dim3(1), dim3(256), 0, st, S->d_props.p, d_p0.p, n_cols, d_ctl.p);
+            em_step(d_p0.p, d_p1.p);
+            em_step(d_p1.p, d_p2.p);
+            hipLaunchKernelGGL(k_em_extrapolate, dim3(1), dim3(256), em_work ? 0 : 2 * sizeof(double) * (size_t)n_cols, st, d_p0.p, d_p1.p, d_p2.p, d_sq.p, n_cols, d_ctl.p, em_work);
+            log_likelihood(d_p2.p, 0);
+            log_likelihood(d_sq.p, 1);
+            hipLaunchKernelGGL(k_em_choose, dim3(1), dim3(256), 0, st, d_p0.p, d_p2.p, d_sq.p, S->d_props.p, n_cols, d_ctl.p, mp->em_convergence,
+                               mp->em_delta_threshold);
+        }
+        PMX_HIP(hipGetLastError());
+        PMX_HIP(hipMemcpyAsync(&h_ctl, d_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipStreamSynchronize(st));
+        iter += batch;
+        if (h_ctl.done) break;
+    }
+    PMX_HIP(hipMemcpyAsync(props.data(), S->d_props.p, sizeof(double) * (size_t)n_cols, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+}
+
+// removeLowPropNodes (src/mgsr.cpp:4445-4490), called after EVERY round including the last allowed one (src/main.cpp:1263-1271):
+// when it removes anything the surviving nodes' proportions are reset to uniform, and if that was the last round
+// the uniform vector is what the abundance file reports -- mirrored, not "fixed".  (No HIP.)  True: a column was dropped.
+bool drop_low_proportions(std::vector<int>& cols, std::vector<std::vector<uint32_t>>& members, std::vector<double>& props, double prop_threshold) {
+    std::vector<int> keep;
+    for (int i = 0; i < (int)cols.size(); ++i)
+        if (props[(size_t)i] >= prop_threshold) keep.push_back(i);
+    if (keep.size() == cols.size()) return false;
+    std::vector<int> cols2;
+    std::vector<std::vector<uint32_t>> members2;
+    for (int i : keep) { cols2.push_back(cols[(size_t)i]); members2.push_back(members[(size_t)i]); }
+    cols.swap(cols2);
+    members.swap(members2);
+    props.assign(cols.size(), cols.empty() ? 0.0 : 1.0 / (double)cols.size());
+    return true;
+}
 }  // namespace
 
 extern "C" {
@@ -602,194 +1209,21 @@ int pmx_meta_row_range(const pmx_meta* m, int64_t* first, int64_t* count) {
     return PMX_OK;
 }
 
-// Step 1 + 2: the reads' seedmer lists (host threads), merged by list; the overlap coefficient of every node (place stage).
+// Step 1 + 2: the reads' seedmer lists (the seeding kernel in list mode), merged by list; the overlap coefficient of every
+// node (place stage).  The host only filters by DUST (integer state, a few operations per base) and merges equal lists.
 int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int64_t* offsets, int64_t n_reads) {
     if (!ctx || !m || !offsets || n_reads < 0 || (!concat && n_reads > 0)) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    const SyncmerParams p = m->params;
-    const int l = p.l;
-    // ---- the reads' seedmer lists ON THE DEVICE (round 4; src/mgsr.cpp:1774-2237): the reads are packed 2 bit/base like any
-    // read set and the generic seeding kernel runs in its list mode (k_seed_histogram: same syncmers, same k-min-mers as
-    // the place stage, orientation = R < F); a gather makes the lists contiguous.  Chunks of reads bound the list arrays
-    // (one slot per base).  The host only filters by DUST (integer state, a few operations per base) and merges equal lists.
-    const double dust_thr = m->dust_threshold;
-    std::vector<uint8_t> dusty(dust_thr < 100.0 ? (size_t)n_reads : 0, 0);
-    if (dust_thr < 100.0) {   // src/mgsr.cpp:1593-1594: a read with a non-zero score above the threshold is left out
-        unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        if (n_reads < 4096) n_thr = 1;
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < n_thr; ++t)
-            pool.emplace_back([&, t]() {
-                for (int64_t r = (int64_t)t; r < n_reads; r += n_thr) {
-                    const double d = pmx_read_dust(concat + offsets[r], offsets[r + 1] - offsets[r], 64);
-                    if (d != 0 && d > dust_thr) dusty[(size_t)r] = 1;
-                }
-            });
-        for (auto& th : pool) th.join();
-    }
-    // the dusty reads leave the sample altogether (src/mgsr.cpp:1590-1597: they never enter seqToIndexVec), the overlap
-    // coefficients included: everything below sees the kept reads only
-    const int64_t n_raw = n_reads;
-    int64_t n_dusty = 0;
-    for (uint8_t d : dusty) n_dusty += d;
-    std::string kept_concat;
-    std::vector<int64_t> kept_off;
-    if (n_dusty > 0) {
-        kept_off.push_back(0);
-        for (int64_t r = 0; r < n_reads; ++r) {
-            if (dusty[(size_t)r]) continue;
-            kept_concat.append(concat + offsets[r], (size_t)(offsets[r + 1] - offsets[r]));
-            kept_off.push_back((int64_t)kept_concat.size());
-        }
-        concat = kept_concat.data();
-        offsets = kept_off.data();
-        n_reads = (int64_t)kept_off.size() - 1;
-        dusty.clear();
-    }
-    std::vector<int64_t> r_off((size_t)n_reads + 1, 0);   // flat seedmer lists of the raw reads
-    std::vector<uint64_t> r_hash;
-    std::vector<uint8_t> r_rev;
-    {
-        SeedParams sp;
-        sp.k = p.k; sp.s = p.s; sp.t = p.t; sp.l = l; sp.open = p.open ? 1 : 0; sp.trim_start = 0; sp.trim_end = 0;
-        const int w = sp.k - sp.s + 1;
-        const size_t lds = (size_t)(2 * w + l) * PMX_SEED_BLOCK * sizeof(uint64_t) + (size_t)(PMX_SEED_BLOCK / 64) * (PMX_SEED_QCAP * sizeof(uint64_t) + 8);
-        if (lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
-        if (lds > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_seed_histogram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        DevBuf<uint64_t> d_lh, d_oh;
-        DevBuf<uint8_t> d_lr, d_or, d_keep;
-        DevBuf<uint32_t> d_ln;
-        DevBuf<int64_t> d_ooff;
-        DevBuf<unsigned long long> d_ctr;
-        d_ctr.alloc(PMX_CTR_N);
-        PMX_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
-        const int64_t chunk = 2000000;
-        for (int64_t c0 = 0; c0 < n_reads; c0 += chunk) {
-            const int64_t c1 = std::min(n_reads, c0 + chunk), nc = c1 - c0;
-            pmx_readset* rs = nullptr;
-            int rc = pmx_readset_upload(ctx, concat, offsets + c0, nc, &rs);
-            if (rc != PMX_OK) return rc;
-            std::unique_ptr<pmx_readset, void (*)(pmx_readset*)> rs_guard(rs, [](pmx_readset* x) { delete x; });
-            rc = pmx_readset_pack(ctx, rs);
-            if (rc != PMX_OK) return rc;
-            const size_t slots = (size_t)std::max<int64_t>(rs->n_words, 1) * 32;
-            d_lh.ensure(slots); d_lr.ensure(slots); d_ln.ensure((size_t)nc);
-            PMX_HIP(hipMemsetAsync(d_ln.p, 0, sizeof(uint32_t) * (size_t)nc, ctx->stream));
-            const uint8_t* keep = nullptr;
-            if (!dusty.empty()) {
-                std::vector<uint8_t> k8((size_t)nc);
-                for (int64_t i = 0; i < nc; ++i) k8[(size_t)i] = dusty[(size_t)(c0 + i)] ? 0 : 1;
-                d_keep.ensure((size_t)nc);
-                PMX_HIP(hipMemcpyAsync(d_keep.p, k8.data(), (size_t)nc, hipMemcpyHostToDevice, ctx->stream));
-                PMX_HIP(hipStreamSynchronize(ctx->stream));   // (k8 goes out of scope)
-                keep = d_keep.p;
-            }
-            hipLaunchKernelGGL(k_seed_histogram, dim3(grid_for(nc, PMX_SEED_BLOCK, ctx->n_cu * 16)), dim3(PMX_SEED_BLOCK), lds, ctx->stream, rs->words.p, rs->amb.p,
-                               rs->woff.p, rs->off.p, (int64_t)0, nc, sp, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0, d_ctr.p, keep,
-                               (const uint8_t*)nullptr, 0, d_lh.p, d_lr.p, d_ln.p);
-            PMX_HIP(hipGetLastError());
-            std::vector<uint32_t> h_n((size_t)nc);
-            PMX_HIP(hipMemcpyAsync(h_n.data(), d_ln.p, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
-            PMX_HIP(hipStreamSynchronize(ctx->stream));
-            std::vector<int64_t> o_off((size_t)nc + 1, 0);
-            for (int64_t i = 0; i < nc; ++i) o_off[(size_t)i + 1] = o_off[(size_t)i] + (int64_t)h_n[(size_t)i];
-            const int64_t tot = o_off[(size_t)nc];
-            const size_t base = r_hash.size();
-            r_hash.resize(base + (size_t)tot);
-            r_rev.resize(base + (size_t)tot);
-            if (tot > 0) {
-                d_ooff.ensure((size_t)nc + 1); d_oh.ensure((size_t)tot); d_or.ensure((size_t)tot);
-                PMX_HIP(hipMemcpyAsync(d_ooff.p, o_off.data(), sizeof(int64_t) * ((size_t)nc + 1), hipMemcpyHostToDevice, ctx->stream));
-                hipLaunchKernelGGL(k_meta_gather_lists, dim3(grid_for(nc * 8, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, d_lh.p, d_lr.p, rs->woff.p, d_ooff.p, nc,
-                                   d_oh.p, d_or.p);
-                PMX_HIP(hipGetLastError());
-                PMX_HIP(hipMemcpyAsync(r_hash.data() + base, d_oh.p, sizeof(uint64_t) * (size_t)tot, hipMemcpyDeviceToHost, ctx->stream));
-                PMX_HIP(hipMemcpyAsync(r_rev.data() + base, d_or.p, (size_t)tot, hipMemcpyDeviceToHost, ctx->stream));
-                PMX_HIP(hipStreamSynchronize(ctx->stream));
-            }
-            for (int64_t i = 0; i < nc; ++i) r_off[(size_t)(c0 + i) + 1] = (int64_t)base + o_off[(size_t)i + 1];
-        }
-    }
-    // reads with the same seedmer list (hash and orientation, in order) are one read with a multiplicity; a read without
-    // seedmers scores 0 everywhere and carries no weight in the EM (src/mgsr.cpp:8170-8173): dropped here
-    struct View { const uint64_t* h; const uint8_t* v; int64_t n; };
-    auto view = [&](int64_t r) { return View{r_hash.data() + r_off[(size_t)r], r_rev.data() + r_off[(size_t)r], r_off[(size_t)r + 1] - r_off[(size_t)r]}; };
-    std::vector<int64_t> order;
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (r_off[(size_t)r + 1] > r_off[(size_t)r]) order.push_back(r);
-    // (lexicographic on the hash list, then on the orientation list: the order the vector comparisons gave)
-    auto cmp3 = [&](int64_t a, int64_t b) {
-        const View x = view(a), y = view(b);
-        return cmp_lists(x.h, x.v, x.n, y.h, y.v, y.n);
-    };
-    auto less = [&](int64_t a, int64_t b) { return cmp3(a, b) < 0; };
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { const int c = cmp3(a, b); return c < 0 || (c == 0 && a < b); });
-    m->n_raw_reads = n_raw;
-    m->n_dust_dropped = n_dusty;
-    m->h_read_off.assign(1, 0);
-    m->h_seed_hash.clear(); m->h_seed_rev.clear(); m->h_mult.clear();
-    for (size_t i = 0; i < order.size(); ++i) {
-        const View o = view(order[i]);
-        if (i > 0 && cmp3(order[i - 1], order[i]) == 0) { ++m->h_mult.back(); continue; }
-        m->h_seed_hash.insert(m->h_seed_hash.end(), o.h, o.h + o.n);
-        m->h_seed_rev.insert(m->h_seed_rev.end(), o.v, o.v + o.n);
-        m->h_read_off.push_back((int64_t)m->h_seed_hash.size());
-        m->h_mult.push_back(1);
-    }
-    m->n_reads = (int64_t)m->h_mult.size();
-    m->n_seedmers = (int64_t)m->h_seed_hash.size();
-    // --gpus N: the ranks' runs become the whole sample's; the raw, DUST-dropped and kept read counts are summed
-    int64_t n_kept_all = n_reads;
-    if (m->dist) {
-        const int64_t mine[5] = {n_raw, n_dusty, n_reads, m->n_reads, m->n_seedmers};
-        const std::vector<int64_t> counts = dist_exchange_counts(m->dist, mine, 5);
-        m->n_raw_reads = m->n_dust_dropped = n_kept_all = 0;
-        for (size_t r = 0; r < counts.size() / 5; ++r) { m->n_raw_reads += counts[5 * r]; m->n_dust_dropped += counts[5 * r + 1]; n_kept_all += counts[5 * r + 2]; }
-        merge_runs_over_ranks(m, counts, 5);
-    }
-    m->h_uniq = m->h_seed_hash;
-    std::sort(m->h_uniq.begin(), m->h_uniq.end());
-    m->h_uniq.erase(std::unique(m->h_uniq.begin(), m->h_uniq.end()), m->h_uniq.end());
-    std::vector<uint32_t> uid((size_t)m->n_seedmers);
-    for (int64_t i = 0; i < m->n_seedmers; ++i)
-        uid[(size_t)i] = (uint32_t)(std::lower_bound(m->h_uniq.begin(), m->h_uniq.end(), m->h_seed_hash[(size_t)i]) - m->h_uniq.begin());
-    m->d_read_off.ensure((size_t)m->n_reads + 1);
-    m->d_seed_uid.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
-    m->d_seed_rev.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
-    m->d_uniq.ensure(std::max<size_t>(m->h_uniq.size(), 1));
-    PMX_HIP(hipMemcpyAsync(m->d_read_off.p, m->h_read_off.data(), sizeof(int64_t) * ((size_t)m->n_reads + 1), hipMemcpyHostToDevice, ctx->stream));
-    if (m->n_seedmers > 0) {
-        PMX_HIP(hipMemcpyAsync(m->d_seed_uid.p, uid.data(), sizeof(uint32_t) * (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->d_seed_rev.p, m->h_seed_rev.data(), (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->d_uniq.p, m->h_uniq.data(), sizeof(uint64_t) * m->h_uniq.size(), hipMemcpyHostToDevice, ctx->stream));
-    }
-    PMX_HIP(hipStreamSynchronize(ctx->stream));   // (uid goes out of scope)
-    // overlap coefficients through the place stage: seed the reads on the device, score the tree with every read seed kept
-    // (--gpus N: each rank seeds its kept reads, the histograms are merged, and every rank scores the tree with the whole
-    //  sample's kept-read count -- the coefficients, and so the candidates, are the same on every rank)
-    m->oc.assign((size_t)m->n_nodes, 0.0);
-    if (n_kept_all > 0) {
-        pmx_readset* rs = nullptr;
-        int rc = pmx_readset_upload(ctx, concat, offsets, n_reads, &rs);
-        if (rc != PMX_OK) return rc;
-        pmx_place_params pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.min_read_support = 1;
-        pmx_place_result res;
-        rc = pmx_readset_pack(ctx, rs);
-        if (rc == PMX_OK) rc = pmx_place_reset(ctx, m->placer);
-        if (rc == PMX_OK) rc = pmx_place_add_reads(ctx, m->placer, rs, &pp);
-        if (rc == PMX_OK && m->dist) rc = pmx_dist_merge_histograms(m->dist, m->placer);
-        if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept_all, &res);
-        pmx_readset_free(ctx, rs);
-        if (rc != PMX_OK) return rc;
-        std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
-        rc = pmx_place_node_outputs(ctx, m->placer, nullptr, nullptr, counts2.data());
-        if (rc != PMX_OK) return rc;
-        for (int64_t v = 0; v < m->n_nodes; ++v)
-            m->oc[(size_t)v] = counts2[2 * (size_t)v + 1] > 0 ? (double)counts2[2 * (size_t)v] / (double)counts2[2 * (size_t)v + 1] : 0.0;
-    }
+    MetaReads R(ctx, m, concat, offsets, n_reads);
+    R.drop_dusty();
+    int rc = R.seedmer_lists();
+    if (rc != PMX_OK) return rc;
+    R.merge_equal_lists();
+    if (m->dist) R.merge_over_ranks();
+    R.upload_lists();
+    rc = R.overlap_coefficients();
+    if (rc != PMX_OK) return rc;
     m->cand.clear();
     m->groups.clear();
     m->row_first = 0;
@@ -805,51 +1239,12 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
     if (!ctx || !m || (n_override > 0 && !cand_override)) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    m->cand.clear();
-    if (n_override > 0) {
-        m->cand.assign(cand_override, cand_override + n_override);
-        for (uint32_t v : m->cand)
-            if ((int64_t)v >= m->n_nodes) return fail(PMX_ERR_ARG, "candidate node out of range");
-    } else {
-        std::vector<uint32_t> by_oc((size_t)m->n_nodes);
-        std::iota(by_oc.begin(), by_oc.end(), 0u);
-        std::stable_sort(by_oc.begin(), by_oc.end(), [&](uint32_t a, uint32_t b) { return m->oc[a] > m->oc[b]; });
-        int64_t ranks = 0;
-        double cur = -1.0;
-        for (uint32_t v : by_oc) {
-            if (m->oc[v] != cur) {
-                cur = m->oc[v];
-                if (++ranks > top_oc) break;
-            }
-            m->cand.push_back(v);
-        }
-    }
-    std::sort(m->cand.begin(), m->cand.end());
-    m->cand.erase(std::unique(m->cand.begin(), m->cand.end()), m->cand.end());
-    const int n_cand = (int)m->cand.size(), words = (n_cand + 63) / 64;
+    if (!select_candidates(m->oc, m->n_nodes, top_oc, cand_override, n_override, m->cand)) return fail(PMX_ERR_ARG, "candidate node out of range");
     m->groups.clear();
-    m->h_max_score.assign((size_t)m->n_reads, 0);
-    // this rank's rows: all merged reads, or (--gpus N, pass A) a balanced contiguous slice of them
-    m->row_first = 0;
-    m->row_count = m->n_reads;
-    if (m->dist) {
-        const int64_t rank = pmx_dist_rank(m->dist), world = pmx_dist_world(m->dist);
-        m->row_first = m->n_reads * rank / world;
-        m->row_count = m->n_reads * (rank + 1) / world - m->row_first;
-    }
-    if (n_cand == 0 || m->n_reads == 0) return PMX_OK;
-    m->d_cand.ensure((size_t)n_cand);
-    PMX_HIP(hipMemcpyAsync(m->d_cand.p, m->cand.data(), sizeof(uint32_t) * (size_t)n_cand, hipMemcpyHostToDevice, ctx->stream));
-    const size_t mask_words = m->h_uniq.size() * (size_t)words;
-    m->mask_fwd.ensure(std::max<size_t>(mask_words, 1));
-    m->mask_rev.ensure(std::max<size_t>(mask_words, 1));
-    PMX_HIP(hipMemsetAsync(m->mask_fwd.p, 0, sizeof(unsigned long long) * std::max<size_t>(mask_words, 1), ctx->stream));
-    PMX_HIP(hipMemsetAsync(m->mask_rev.p, 0, sizeof(unsigned long long) * std::max<size_t>(mask_words, 1), ctx->stream));
-    if (m->n_changes > 0)
-        hipLaunchKernelGGL(k_meta_mask_events, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, m->ch_key.p, m->ch_pc.p,
-                           m->ch_cc.p, m->ch_node.p, m->n_changes, m->subtree_end.p, m->d_uniq.p, (int64_t)m->h_uniq.size(), m->d_cand.p, n_cand, words,
-                           m->mask_fwd.p, m->mask_rev.p);
-    m->score.ensure((size_t)m->row_count * (size_t)n_cand);
+    own_row_slice(m);
+    if (m->cand.empty() || m->n_reads == 0) return PMX_OK;
+    build_masks(ctx, m);
+    m->score.ensure((size_t)m->row_count * m->cand.size());
     int64_t longest = 0;
     for (int64_t r = 0; r < m->n_reads; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
     if (longest >= 65535) return fail(PMX_ERR_UNSUPPORTED, "a read with 65,535 seedmers or more (16-bit scores)");
@@ -908,250 +1303,29 @@ int pmx_meta_em(pmx_ctx* ctx, pmx_meta* m, const pmx_meta_params* mp) {
     if (!ctx || !m || !mp) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int n_cand = (int)m->cand.size();
-    const int64_t n_reads = m->n_reads;
     m->groups.clear();
     m->em_rounds = m->em_iterations = 0;
     m->llh = 0.0;
-    if (n_cand == 0 || n_reads == 0) return PMX_OK;
-    // ---- columns: one per distinct score column (digest; members = the other candidates of that column)
-    std::vector<int> col_cand;                       // column -> candidate position of its representative
-    std::vector<std::vector<uint32_t>> col_members;
-    std::vector<int64_t> rows;
-    DevBuf<uint64_t> d_dig;
-    d_dig.alloc(2 * (size_t)n_cand);
-    if (!m->dist) {
-        hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, n_reads, n_cand, d_dig.p);
-        std::vector<uint64_t> dig(2 * (size_t)n_cand);
-        PMX_HIP(hipMemcpyAsync(dig.data(), d_dig.p, sizeof(uint64_t) * dig.size(), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
-        std::map<std::pair<uint64_t, uint64_t>, int> first_of;
-        for (int c = 0; c < n_cand; ++c) {
-            const auto key = std::make_pair(dig[2 * (size_t)c], dig[2 * (size_t)c + 1]);
-            auto it = first_of.find(key);
-            if (it == first_of.end()) { first_of.emplace(key, (int)col_cand.size()); col_cand.push_back(c); col_members.emplace_back(); }
-            else col_members[(size_t)it->second].push_back(m->cand[(size_t)c]);
-        }
-        // ---- rows: the reads that score somewhere (the others carry no weight, src/mgsr.cpp:8170-8173)
-        std::vector<uint16_t> h_score((size_t)n_reads * (size_t)n_cand);
-        PMX_HIP(hipMemcpyAsync(h_score.data(), m->score.p, sizeof(uint16_t) * h_score.size(), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
-        for (int64_t r = 0; r < n_reads; ++r) {
-            int mx = 0;
-            for (int c = 0; c < n_cand; ++c) mx = std::max<int>(mx, h_score[(size_t)r * (size_t)n_cand + (size_t)c]);
-            m->h_max_score[(size_t)r] = mx;
-            const int64_t n_seed = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
-            // --discard (src/main.cpp:1229-1240): the threshold is TRUNCATED to an integer there,
-            // `maxScore < static_cast<int>(seedmers * discard)`, so a read with int(n * d) <= max < n * d stays in the EM
-            if (mx == 0 || mx < (int)((double)n_seed * mp->discard)) continue;
-            rows.push_back(r);
-        }
-    } else {
-        // --gpus N, pass A: the column digests of this rank's slice and its reads' --discard flags (k_meta_row_keep), one
-        // all-gather of both.  Two columns are equal iff they are equal on every slice: the key of a column is its digests in
-        // rank order, so the groups (and their order: by first candidate) are the one-rank groups.
-        const int world = pmx_dist_world(m->dist);
-        const int64_t max_slice = (n_reads + world - 1) / world;
-        const size_t dig_bytes = sizeof(uint64_t) * 2 * (size_t)n_cand, part_bytes = dig_bytes + (((size_t)max_slice + 7) & ~(size_t)7);
-        DevBuf<char> d_mine, d_all;
-        d_mine.alloc(part_bytes);
-        d_all.alloc(part_bytes * (size_t)world);
-        PMX_HIP(hipMemsetAsync(d_mine.p, 0, part_bytes, st));
-        hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, m->row_count, n_cand, (uint64_t*)d_mine.p);
-        if (m->row_count > 0)
-            hipLaunchKernelGGL(k_meta_row_keep, dim3(grid_for(m->row_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->score.p, m->row_count, n_cand,
-                               m->d_read_off.p + m->row_first, mp->discard, (uint8_t*)(d_mine.p + dig_bytes));
-        PMX_HIP(hipGetLastError());
-        dist_all_gather(m->dist, d_mine.p, part_bytes, d_all.p);
-        std::vector<char> all(part_bytes * (size_t)world);
-        PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
-        std::map<std::vector<uint64_t>, int> first_of;
-        std::vector<uint64_t> key(2 * (size_t)world);
-        for (int c = 0; c < n_cand; ++c) {
-            for (int r = 0; r < world; ++r) memcpy(&key[2 * (size_t)r], all.data() + (size_t)r * part_bytes + 2 * sizeof(uint64_t) * (size_t)c, 2 * sizeof(uint64_t));
-            auto it = first_of.find(key);
-            if (it == first_of.end()) { first_of.emplace(key, (int)col_cand.size()); col_cand.push_back(c); col_members.emplace_back(); }
-            else col_members[(size_t)it->second].push_back(m->cand[(size_t)c]);
-        }
-        for (int r = 0; r < world; ++r) {
-            const int64_t f = n_reads * r / world, n = n_reads * (r + 1) / world - f;
-            const uint8_t* keep = (const uint8_t*)(all.data() + (size_t)r * part_bytes + dig_bytes);
-            for (int64_t i = 0; i < n; ++i)
-                if (keep[i]) rows.push_back(f + i);
-        }
-    }
-    const int64_t n_rows = (int64_t)rows.size();
-    if (n_rows == 0) return PMX_OK;
-    // ---- P(read | node) = err^(n - s) * (1 - err)^s for the distinct n of the reads: tables computed with the host libm
-    std::map<int64_t, uint32_t> off_of_n;
-    std::vector<double> tab;
-    std::vector<uint32_t> tab_off((size_t)n_rows);
-    std::vector<double> weight((size_t)n_rows);
-    double total_weight = 0.0;
-    for (int64_t j = 0; j < n_rows; ++j) {
-        const int64_t r = rows[(size_t)j], n_seed = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
-        auto it = off_of_n.find(n_seed);
-        if (it == off_of_n.end()) {
-            it = off_of_n.emplace(n_seed, (uint32_t)tab.size()).first;
-            for (int64_t s = 0; s <= n_seed; ++s) tab.push_back(std::pow(mp->error_rate, (double)(n_seed - s)) * std::pow(1.0 - mp->error_rate, (double)s));
-        }
-        tab_off[(size_t)j] = it->second;
-        weight[(size_t)j] = (double)m->h_mult[(size_t)r];
-        total_weight += weight[(size_t)j];   // (integers: exact in any order)
-    }
-    const double inv_total = 1.0 / total_weight;
-    const int64_t chunk = kColsumChunk;   // reads per partial column sum (2,048: 2,200 waves for 3,000 columns x 90k reads, each a serial walk: 373 us per pass)
-    const int n_chunks = (int)((n_rows + chunk - 1) / chunk);
-    const int64_t n_bsum = (n_rows + kSumBlock - 1) / kSumBlock;
-    // ---- this rank's EM rows: all of them, or (--gpus N, pass B) a contiguous range whose bounds are multiples of both
-    // reduction widths -- the rank's chunk partials and block sums are then whole global ones, at global positions
-    // rank * per / width of the all-gathered arrays, and the one-rank fold and store kernels add them in the one-rank order
-    int64_t e_first = 0, e_count = n_rows, per = n_rows;
-    const uint16_t* score_p = m->score.p;
-    std::vector<int64_t> loc_rows(rows);
-    if (m->dist) {
-        const int world = pmx_dist_world(m->dist), rank = pmx_dist_rank(m->dist);
-        const int64_t align = std::lcm(kColsumChunk, kSumBlock);
-        per = ((n_rows + world - 1) / world + align - 1) / align * align;
-        e_first = std::min<int64_t>(n_rows, per * rank);
-        e_count = std::min<int64_t>(n_rows, e_first + per) - e_first;
-        // pass B: the merged reads of the range, scored again into a matrix of their own
-        const int64_t r_lo = e_count > 0 ? rows[(size_t)e_first] : 0, r_hi = e_count > 0 ? rows[(size_t)(e_first + e_count - 1)] + 1 : 0;
-        m->score_em.ensure((size_t)std::max<int64_t>(r_hi - r_lo, 1) * (size_t)n_cand);
-        score_rows(ctx, m, r_lo, r_hi - r_lo, m->score_em.p);
-        score_p = m->score_em.p;
-        loc_rows.assign((size_t)e_count, 0);
-        for (int64_t j = 0; j < e_count; ++j) loc_rows[(size_t)j] = rows[(size_t)(e_first + j)] - r_lo;
-    }
-    const int loc_chunks = (int)((e_count + chunk - 1) / chunk);
-    const int64_t loc_bsum = (e_count + kSumBlock - 1) / kSumBlock;
-    const int64_t slot_chunks = (per + chunk - 1) / chunk, slot_bsum = (per + kSumBlock - 1) / kSumBlock;   // per rank in the gathers
-    DevBuf<int64_t> d_rows;
-    DevBuf<uint32_t> d_tab_off;
-    DevBuf<double> d_tab, d_weight, d_denom, d_llh, d_props, d_out, d_part, d_bsum, d_gpart, d_gbsum;
-    DevBuf<int> d_cols;
-    d_rows.alloc((size_t)e_count); d_tab_off.alloc((size_t)e_count); d_tab.alloc(tab.size()); d_weight.alloc((size_t)e_count);
-    d_denom.alloc((size_t)e_count); d_llh.alloc((size_t)e_count);
-    if (e_count > 0) {
-        PMX_HIP(hipMemcpyAsync(d_rows.p, loc_rows.data(), sizeof(int64_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_tab_off.p, tab_off.data() + e_first, sizeof(uint32_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_weight.p, weight.data() + e_first, sizeof(double) * (size_t)e_count, hipMemcpyHostToDevice, st));
-    }
-    PMX_HIP(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
-    d_bsum.alloc((size_t)slot_bsum);
-    const int world = m->dist ? pmx_dist_world(m->dist) : 1;
-    if (m->dist) d_gbsum.alloc((size_t)slot_bsum * (size_t)world);
-    const double* bsum_all = m->dist ? d_gbsum.p : d_bsum.p;
-
-    std::vector<int> cols = col_cand;       // current columns (candidate positions)
-    std::vector<std::vector<uint32_t>> members = col_members;
+    if (m->cand.empty() || m->n_reads == 0) return PMX_OK;
+    EmStage S(ctx, m, mp);
+    if (m->dist) S.kept_rows_dist();
+    else S.kept_rows_one_rank();
+    if (S.n_rows == 0) return PMX_OK;
+    S.likelihood_tables();
+    S.own_em_rows();
+    S.upload_rows();
+    std::vector<int> cols = S.col_cand;       // current columns (candidate positions)
+    std::vector<std::vector<uint32_t>> members = S.col_members;
     std::vector<double> props;
     for (int round = 0; round < std::max(1, mp->em_max_rounds); ++round) {
-        const int n_cols = (int)cols.size();
-        d_cols.ensure((size_t)n_cols); d_props.ensure((size_t)n_cols); d_out.ensure((size_t)n_cols); d_part.ensure((size_t)slot_chunks * (size_t)n_cols);
-        if (m->dist) d_gpart.ensure((size_t)slot_chunks * (size_t)n_cols * (size_t)world);
-        const double* part_all = m->dist ? d_gpart.p : d_part.p;
-        PMX_HIP(hipMemcpyAsync(d_cols.p, cols.data(), sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st));
-        // The whole SQUAREM loop stays on the device: the proportion vectors never leave it, the small vector arithmetic runs in
-        // single-block kernels with the host loop's own order of operations, and the host only looks at the convergence flag
-        // every 16 iterations (launches queued past convergence return at once).  Per iteration: 6 passes over the score
-        // matrix (4 x k_meta_denoms, 2 x k_meta_colsum) and 13 small launches; before, 4 host round trips.  --gpus N: the
-        // passes run over the rank's rows, and 4 all-gathers per iteration (chunk partials x 2, block sums x 2) bring every
-        // rank the global arrays; the single-block kernels then run replicated on identical inputs, so the convergence flag
-        // and the iteration count agree on every rank and every rank issues the same sequence of collectives (queued past
-        // convergence too).
-        DevBuf<double> d_p0, d_p1, d_p2, d_sq;
-        DevBuf<EmCtl> d_ctl;
-        d_p0.alloc((size_t)n_cols); d_p1.alloc((size_t)n_cols); d_p2.alloc((size_t)n_cols); d_sq.alloc((size_t)n_cols);
-        d_ctl.alloc(1);
-        EmCtl h_ctl;
-        memset(&h_ctl, 0, sizeof(h_ctl));
-        PMX_HIP(hipMemcpyAsync(d_ctl.p, &h_ctl, sizeof(h_ctl), hipMemcpyHostToDevice, st));
-        props.assign((size_t)n_cols, 1.0 / (double)n_cols);
-        PMX_HIP(hipMemcpyAsync(d_props.p, props.data(), sizeof(double) * (size_t)n_cols, hipMemcpyHostToDevice, st));
-        const int* d_done = &d_ctl.p->done;
-        // the in-order sums of the small kernels read a copy of the vector in LDS (2 x n_cols doubles at most); beyond 160 KB a
-        // scratch vector in global memory stands in
-        DevBuf<double> d_em_work;
-        double* em_work = nullptr;
-        const size_t em_lds = 2 * sizeof(double) * (size_t)n_cols;
-        if (em_lds > (size_t)160 * 1024) { d_em_work.alloc(2 * (size_t)n_cols); em_work = d_em_work.p; }
-        else if (em_lds > (size_t)64 * 1024) {
-            PMX_HIP(hipFuncSetAttribute((const void*)k_em_normalize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
-            PMX_HIP(hipFuncSetAttribute((const void*)k_em_extrapolate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
-        }
-        auto denoms = [&](const double* pr) {
-            hipLaunchKernelGGL(k_meta_denoms, dim3(grid_for(e_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, score_p, n_cand, d_cols.p, n_cols, pr,
-                               d_rows.p, e_count, d_tab_off.p, d_tab.p, d_weight.p, d_denom.p, d_llh.p, d_done);
-        };
-        auto em_step = [&](const double* from, double* to) {   // updateProps (src/mgsr.cpp:4341-4372) + normalizeProps
-            if (e_count > 0) {
-                denoms(from);
-                hipLaunchKernelGGL(k_meta_colsum, dim3((n_cols + 63) / 64, loc_chunks), dim3(64), 0, st, score_p, n_cand, d_cols.p, n_cols, from, d_rows.p,
-                                   e_count, chunk, d_tab_off.p, d_tab.p, d_weight.p, d_denom.p, d_part.p, d_done);
-            }
-            if (m->dist) dist_all_gather(m->dist, d_part.p, sizeof(double) * (size_t)slot_chunks * (size_t)n_cols, d_gpart.p);
-            hipLaunchKernelGGL(k_meta_fold, dim3((n_cols + 63) / 64), dim3(64), 0, st, part_all, n_chunks, n_cols, inv_total, d_out.p, d_done);
-            hipLaunchKernelGGL(k_em_normalize, dim3(1), dim3(256), em_work ? 0 : sizeof(double) * (size_t)n_cols, st, d_out.p, to, n_cols, d_ctl.p, em_work);
-        };
-        auto log_likelihood = [&](const double* pr, int which) {                          // getExp (:4385-4388)
-            if (e_count > 0) {
-                denoms(pr);
-                hipLaunchKernelGGL(k_meta_sum_blocks, dim3((unsigned)((loc_bsum + 3) / 4)), dim3(256), 0, st, d_llh.p, e_count, d_bsum.p, d_done);
-            }
-            if (m->dist) dist_all_gather(m->dist, d_bsum.p, sizeof(double) * (size_t)slot_bsum, d_gbsum.p);
-            hipLaunchKernelGGL(k_em_store_llh, dim3(1), dim3(64), 0, st, bsum_all, n_bsum, d_ctl.p, which);
-        };
-        const int look_every = 16;
-        for (int iter = 0; iter < mp->em_max_iterations;) {                               // runSquareEM (:4394-4443)
-            const int batch = std::min(look_every, mp->em_max_iterations - iter);
-            for (int b = 0; b < batch; ++b) {
-                hipLaunchKernelGGL(k_em_copy, dim3(1), dim3(256), 0, st, d_props.p, d_p0.p, n_cols, d_ctl.p);
-                em_step(d_p0.p, d_p1.p);
-                em_step(d_p1.p, d_p2.p);
-                hipLaunchKernelGGL(k_em_extrapolate, dim3(1), dim3(256), em_work ? 0 : 2 * sizeof(double) * (size_t)n_cols, st, d_p0.p, d_p1.p, d_p2.p, d_sq.p, n_cols, d_ctl.p, em_work);
-                log_likelihood(d_p2.p, 0);
-                log_likelihood(d_sq.p, 1);
-                hipLaunchKernelGGL(k_em_choose, dim3(1), dim3(256), 0, st, d_p0.p, d_p2.p, d_sq.p, d_props.p, n_cols, d_ctl.p, mp->em_convergence,
-                                   mp->em_delta_threshold);
-            }
-            PMX_HIP(hipGetLastError());
-            PMX_HIP(hipMemcpyAsync(&h_ctl, d_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
-            PMX_HIP(hipStreamSynchronize(st));
-            iter += batch;
-            if (h_ctl.done) break;
-        }
-        PMX_HIP(hipMemcpyAsync(props.data(), d_props.p, sizeof(double) * (size_t)n_cols, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
-        m->em_iterations += h_ctl.iterations;
-        const double llh = h_ctl.llh;
-        m->llh = llh;
+        EmRound R(&S, cols);
+        R.run(props);
+        m->em_iterations += R.h_ctl.iterations;
+        m->llh = R.h_ctl.llh;
         ++m->em_rounds;
-        // removeLowPropNodes (:4445-4490), called after EVERY round including the last allowed one (src/main.cpp:1263-1271):
-        // when it removes anything the surviving nodes' proportions are reset to uniform, and if that was the last round
-        // the uniform vector is what the abundance file reports -- mirrored, not "fixed"
-        std::vector<int> keep;
-        for (int i = 0; i < n_cols; ++i)
-            if (props[(size_t)i] >= mp->prop_threshold) keep.push_back(i);
-        if ((int)keep.size() == n_cols) break;
-        std::vector<int> cols2;
-        std::vector<std::vector<uint32_t>> members2;
-        for (int i : keep) { cols2.push_back(cols[(size_t)i]); members2.push_back(members[(size_t)i]); }
-        cols.swap(cols2);
-        members.swap(members2);
-        props.assign(cols.size(), cols.empty() ? 0.0 : 1.0 / (double)cols.size());
-        if (cols.empty()) break;
+        if (!drop_low_proportions(cols, members, props, mp->prop_threshold) || cols.empty()) break;
     }
-    for (size_t i = 0; i < cols.size(); ++i) {
-        pmx_meta_group g;
-        g.node = m->cand[(size_t)cols[i]];
-        g.members = members[i];
-        g.prop = props[i];
-        m->groups.push_back(std::move(g));
-    }
-    std::stable_sort(m->groups.begin(), m->groups.end(), [](const pmx_meta_group& a, const pmx_meta_group& b) { return a.prop > b.prop; });
+    S.publish_groups(cols, members, props);
     return PMX_OK;
     PMX_CATCH
 }

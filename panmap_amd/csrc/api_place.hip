@@ -93,11 +93,6 @@ struct pmx_place {
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
 // Every switch the stage reads (device/pmx_options.hpp), parsed here and nowhere below.
 struct PlaceSwitches {
     static bool on(OptId id) { return pmx::opt_str(id) != nullptr; }
@@ -117,12 +112,6 @@ struct PlaceSwitches {
         if (const char* e = pmx::opt_str(pmx::O_SEED_BATCHES)) seed_batches = std::max(1, atoi(e));
     }
 };
-
-#define PMX_TRY try {
-#define PMX_CATCH                                                      \
-    }                                                                  \
-    catch (const HipError& e) { return fail(PMX_ERR_DEVICE, e.msg); }  \
-    catch (const std::exception& e) { return fail(PMX_ERR_DEVICE, e.what()); }
 
 // every slot of the seed table empty: the keys PMX_EMPTY_KEY, the counts zero
 void table_clear(pmx_ctx* ctx, pmx_place* pl) {

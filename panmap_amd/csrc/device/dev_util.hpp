@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <exception>
 #include <map>
 #include <string>
 #include <vector>
@@ -22,6 +23,18 @@ struct HipError {
         if (_e != hipSuccess)                                                                              \
             throw pmx::HipError{std::string(#expr) + ": " + hipGetErrorString(_e)};                        \
     } while (0)
+
+// the C ABI's way out of an entry point: the message for pmx_last_error, the code for the caller; PMX_TRY ... PMX_CATCH
+// around an entry point's body turn what it throws into PMX_ERR_DEVICE
+inline int fail(int code, const std::string& msg) {
+    set_error(msg);
+    return code;
+}
+#define PMX_TRY try {
+#define PMX_CATCH                                                               \
+    }                                                                           \
+    catch (const pmx::HipError& e) { return pmx::fail(PMX_ERR_DEVICE, e.msg); } \
+    catch (const std::exception& e) { return pmx::fail(PMX_ERR_DEVICE, e.what()); }
 
 template <class T>
 struct DevBuf {

@@ -234,3 +234,145 @@ def test_config5_sars_five_haplotypes(pmx):
     info = meta.em_info()
     assert 1 <= info["rounds"] <= 5 and info["iterations"] < 1000
     meta.close()
+
+
+# ---- the paths of pmx_meta_set_reads and pmx_meta_em that the tests above do not reach
+
+def _bits(x):
+    """doubles as their bit patterns"""
+    return np.atleast_1d(np.asarray(x, np.float64)).copy().view(np.uint64)
+
+
+def _mixture_reads():
+    a, b = _fasta(os.path.join(GOLDEN, "MZ515733.1.fa")), _fasta(os.path.join(GOLDEN, "rsv_4K.panman.random.node_1330.fa"))
+    return _tile(a, 700) + _tile(b, 300)
+
+
+def _run_outputs(meta, reads, dust):
+    """set_reads / score / em with --dust `dust` -> every output of the stage by name, doubles as bit patterns"""
+    meta.set_dust(dust)
+    try:
+        meta.set_reads(reads)
+    finally:
+        meta.set_dust(100.0)             # the module's Meta is shared
+    meta.score(top_oc=1000)
+    haps = meta.em()
+    off, h, rev = meta.read_seedmers()
+    ns, mult = meta.read_info()
+    info = meta.em_info()
+    return dict(read_seedmers=(off, h, rev), read_info=(ns, mult), overlap_coefficients=(_bits(meta.overlap_coefficients()),),
+                candidates=(meta.candidates(),), scores=(meta.scores(),),
+                haplotypes=[(n, int(_bits(p)[0]), m) for n, p, m in haps],
+                em_info=(info["rounds"], info["iterations"], int(_bits(info["log_likelihood"])[0])))
+
+
+def _assert_outputs_equal(got, want):
+    assert got.keys() == want.keys()
+    for name in want:
+        if name in ("haplotypes", "em_info"):
+            assert got[name] == want[name], name
+        else:
+            assert len(got[name]) == len(want[name]), name
+            for g, w in zip(got[name], want[name]):
+                assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), name
+
+
+@pytest.fixture(scope="module")
+def mixture_outputs(rsv_meta):
+    """the 70 / 30 sample without --dust: computed once, compared against by the tests below"""
+    return _run_outputs(rsv_meta[2], _mixture_reads(), 100.0)
+
+
+def test_dust_on_nothing_dropped(pmx, rsv_meta, mixture_outputs):
+    """--dust 20 on a sample none of whose reads it drops: every output equals the run without --dust, bit for bit"""
+    reads = _mixture_reads()
+    assert len(reads) == 1000 and max(pmx.read_dust(r) for r in reads) <= 20.0     # (the maximum is 11.56)
+    got = _run_outputs(rsv_meta[2], reads, 20.0)
+    assert len(got["haplotypes"]) == 2 and got["scores"][0].size > 0
+    _assert_outputs_equal(got, mixture_outputs)
+
+
+def test_dust_drops_reads_on_one_rank(pmx, rsv_meta, mixture_outputs):
+    """--dust 20 on the sample with 20 low-complexity reads spread through it: they leave the sample altogether, every
+    output equals the run of the 1,000 reads alone, bit for bit"""
+    reads = _mixture_reads()
+    low = [b"A" * 150, b"AC" * 75] * 10
+    mixed = []
+    for i, r in enumerate(reads):
+        if i % 50 == 7:
+            mixed.append(low[i // 50])
+        mixed.append(r)
+    assert len(mixed) == 1020 and mixed[0] not in low and mixed[-1] not in low
+    above = [r for r in mixed if pmx.read_dust(r) > 20.0]
+    assert sorted(above) == sorted(low)
+    got = _run_outputs(rsv_meta[2], mixed, 20.0)
+    _assert_outputs_equal(got, mixture_outputs)
+
+
+def test_nothing_to_do_and_state_reset(pmx, rsv_meta):
+    """no reads, and reads too short for a seedmer (18 bases, k = 19): no merged read, score() and em() return with nothing;
+    the next sample on the same Meta comes out as it does on a fresh one"""
+    pm, ctx, meta = rsv_meta
+    a = _fasta(os.path.join(GOLDEN, "MZ515733.1.fa"))
+    short = [a[20 * i:20 * i + 18].encode() for i in range(50)]
+    assert all(len(r) == 18 for r in short)
+    for reads in ([], short):
+        meta.set_reads(reads)
+        assert meta.n_reads == 0
+        meta.score(top_oc=1000)
+        assert meta.em() == [] and meta.haplotypes() == []
+        info = meta.em_info()
+        assert info["rounds"] == 0 and info["iterations"] == 0
+        if not reads:
+            oc = meta.overlap_coefficients()
+            assert oc.shape == (meta.index.info.n_nodes,) and not oc.any()
+    meta.set_reads(_mixture_reads())
+    meta.score(top_oc=1000)
+    text = pmx.format_abundance(meta.em(), meta.index.node_id)
+    lines = [l.split("\t") for l in text.splitlines()]
+    assert len(lines) == 2, text
+    got = {ids: float(p) for ids, p in lines}
+    assert 0.55 < got["MZ515733.1"] < 0.82 and 0.18 < got["node_1330"] < 0.45, text
+    assert 0.99 < sum(got.values()) < 1.01
+
+
+def test_equal_columns_grouped(pmx, rsv_meta):
+    """candidates with equal score columns are one haplotype: the lowest DFS index represents it, the others are its members.
+    Eight candidates, among them two (node, parent) pairs whose columns are equal; prop_threshold 0 keeps every column, so
+    every group is reported"""
+    from panmap_amd import _lib
+    pm, ctx, meta = rsv_meta
+    meta.set_reads(_mixture_reads())
+    meta.score(top_oc=1000)
+    cands, sc = meta.candidates(), meta.scores()
+    pos = {int(v): j for j, v in enumerate(cands)}
+    pairs, used_cols = [], set()
+    for j, v in enumerate(cands.tolist()):
+        p = pm.parent(v)
+        key = sc[:, j].tobytes()
+        if p in pos and sc[:, j].any() and key not in used_cols and np.array_equal(sc[:, j], sc[:, pos[p]]):
+            pairs.append((p, v))
+            used_cols.add(key)
+    assert len(pairs) >= 2                                   # (pairs of different columns)
+    chosen = [v for pr in pairs[:2] for v in pr]
+    for j, v in enumerate(cands.tolist()):                   # four more nodes, each with a column of its own
+        key = sc[:, j].tobytes()
+        if len(chosen) < 8 and key not in used_cols and sc[:, j].any():
+            chosen.append(v)
+            used_cols.add(key)
+    chosen = np.array(sorted(chosen), np.uint32)
+    assert len(chosen) == 8 and len(set(chosen.tolist())) == 8
+    meta.score(candidates=chosen)
+    assert np.array_equal(meta.candidates(), chosen)
+    haps = meta.em(_lib.MetaParams(prop_threshold=0.0))
+    sc8 = meta.scores()
+    cols = _merged_columns(sc8)
+    want = {}
+    for j in cols:
+        same = [int(chosen[i]) for i in range(8) if np.array_equal(sc8[:, i], sc8[:, j])]
+        assert same[0] == int(chosen[j]) == min(same)
+        want[same[0]] = same[1:]
+    assert len(cols) == 6 and sorted(len(m) for m in want.values()) == [0, 0, 0, 0, 1, 1]
+    assert {node: members for node, _, members in haps} == want and len(haps) == len(want)
+    for p, v in pairs[:2]:
+        assert want[p] == [v]
