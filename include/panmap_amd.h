@@ -78,6 +78,11 @@ int pmx_index_build_ex(const pmx_panman *pm, int k, int s, int t, int l, int ope
  * two orientations of one hash apart -- what the reference's MGSR index keeps as seedInfos[].isReverse
  * (src/mgsr.cpp:7225-7320 counts (forward, reverse) occurrences per hash).  Needs l >= 2. */
 #define PMX_INDEX_ORIENTED 0x100
+/* mode | PMX_INDEX_HPC: the index of the homopolymer-compressed genomes (--hpc).  Node n contributes the seeds of
+ * hpcCompress(genome(n)) (src/seeding.cpp:286-306); the hard flank mask is judged at the UNCOMPRESSED coordinate of a k-mer's
+ * first base (src/index_single_mode.cpp:878-883).  Always the from-scratch producer (mode 0 or 1; 2 and PMX_INDEX_ORIENTED
+ * are PMX_ERR_UNSUPPORTED).  Not pinned to the reference's incremental HPC producer: DESIGN.md sections 1 and 7. */
+#define PMX_INDEX_HPC 0x200
 #define PMX_ORIENT_XOR 0x9e3779b97f4a7c15ULL
 /* adopt caller-provided SoA arrays (copied): parent[n], offsets[n+1], hash/pc/cc[offsets[n]] */
 int pmx_index_from_arrays(const pmx_index_info *info, const uint32_t *parent, const uint64_t *offsets,
@@ -139,6 +144,18 @@ int pmx_readset_set_qualities(pmx_ctx *ctx, pmx_readset *rs, const char *qual_co
  * side stream of the context.  It depends on the reads alone, so made here it runs beside the place stage instead of between
  * the placement and the first align kernel; an aligner that finds none makes it itself.  Same results either way. */
 int pmx_readset_order_pairs(pmx_ctx *ctx, pmx_readset *rs);
+/* the HPC form of a read set (seeding::hpcCompress, src/seeding.cpp:286-306, applied as src/placement.cpp:1143-1165
+   applies it): *out == NULL makes a new read set, otherwise that object's buffers are reused (streaming).  The result owns
+   its bases / offsets (/ qualities, when src has them: first base of each run), is marked HPC, is NOT packed.  Base 0 of a
+   read is kept, base i > 0 iff toupper(seq[i]) != toupper(seq[i-1]); kept characters are copied as they are.  Only a placer
+   over an HPC index takes such a set (it also takes the plain set and compresses it itself); the align stage, pmx_readset_order_pairs
+   and pmx_pileup_run refuse it (PMX_ERR_ARG): they work on the uncompressed reads. */
+int pmx_readset_hpc_compress(pmx_ctx *ctx, const pmx_readset *src, pmx_readset **out);
+int pmx_readset_is_hpc(const pmx_readset *rs);
+int pmx_readset_has_qualities(const pmx_readset *rs);
+/* download a read set's ASCII bases, offsets (n+1, starting at 0) and, if present and qual != NULL, qualities:
+   returns the number of bases; copies only when cap suffices */
+int64_t pmx_readset_export(pmx_ctx *ctx, const pmx_readset *rs, char *concat, int64_t cap, int64_t *offsets, char *qual);
 void pmx_readset_free(pmx_ctx *ctx, pmx_readset *rs);
 int64_t pmx_readset_num_reads(const pmx_readset *rs);
 
@@ -175,7 +192,10 @@ typedef struct {
 
 typedef struct pmx_place pmx_place; /* device-resident index + working buffers for one sample */
 
-/* uploads the index SoA (replicated per GPU) and precomputes BFS levels */
+/* uploads the index SoA (replicated per GPU) and precomputes BFS levels.  Over an HPC index (pmx_index_info.hpc) the reads are
+   seeded in their HPC form: pmx_place_add_reads* take a read set marked HPC as it is (packed, like any set), or a plain one,
+   whose range they compress into a scratch set of the placer, pack and seed from (the caller's set is untouched).  A set marked
+   HPC with another index, and a plain set in the pmx_place_dedup_* calls of an HPC placer, are PMX_ERR_ARG. */
 int pmx_place_create(pmx_ctx *ctx, const pmx_index *idx, pmx_place **out);
 void pmx_place_free(pmx_ctx *ctx, pmx_place *pl);
 

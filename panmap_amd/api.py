@@ -16,6 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check
 
+INDEX_HPC = 0x200    # PMX_INDEX_HPC
 METRICS = ("log_raw", "log_cosine", "containment", "weighted_containment", "log_containment")
 
 
@@ -86,20 +87,22 @@ class Index:
         check(lib.pmx_index_get_info(self._h, C.byref(self.info)), "pmx_index_get_info")
 
     @classmethod
-    def build(cls, pm: Panman, k=19, s=8, t=0, l=3, open_syncmer=False, flank_mask=250, mode=0, max_nodes=-1) -> "Index":
-        """mode 0 = automatic, 1 = from-scratch re-seeding of every node, 2 = incremental DFS (see pmx_index_build_ex)"""
+    def build(cls, pm: Panman, k=19, s=8, t=0, l=3, open_syncmer=False, flank_mask=250, mode=0, max_nodes=-1, hpc=False) -> "Index":
+        """mode 0 = automatic, 1 = from-scratch re-seeding of every node, 2 = incremental DFS (see pmx_index_build_ex);
+        hpc: the index of the homopolymer-compressed genomes (PMX_INDEX_HPC; from scratch, so mode 2 is refused)"""
         h = C.c_void_p()
-        check(lib.pmx_index_build_ex(pm._h, k, s, t, l, int(open_syncmer), flank_mask, mode, max_nodes, C.byref(h)), "pmx_index_build_ex")
+        check(lib.pmx_index_build_ex(pm._h, k, s, t, l, int(open_syncmer), flank_mask, mode | (INDEX_HPC if hpc else 0), max_nodes, C.byref(h)),
+              "pmx_index_build_ex")
         return cls(h)
 
     @classmethod
-    def from_arrays(cls, k, s, t, l, open_syncmer, parent, offsets, hashes, parent_counts, child_counts, flank_mask=0):
+    def from_arrays(cls, k, s, t, l, open_syncmer, parent, offsets, hashes, parent_counts, child_counts, flank_mask=0, hpc=False):
         parent = np.ascontiguousarray(parent, np.uint32)
         offsets = np.ascontiguousarray(offsets, np.uint64)
         hashes = np.ascontiguousarray(hashes, np.uint64)
         pc = np.ascontiguousarray(parent_counts, np.int16)
         cc = np.ascontiguousarray(child_counts, np.int16)
-        info = _lib.IndexInfo(k, s, t, l, int(open_syncmer), 0, flank_mask, 0, len(parent), len(hashes))
+        info = _lib.IndexInfo(k, s, t, l, int(open_syncmer), int(bool(hpc)), flank_mask, 0, len(parent), len(hashes))
         h = C.c_void_p()
         check(lib.pmx_index_from_arrays(C.byref(info), parent.ctypes.data, offsets.ctypes.data, hashes.ctypes.data,
                                         pc.ctypes.data, cc.ctypes.data, C.byref(h)), "pmx_index_from_arrays")
@@ -124,6 +127,11 @@ class Index:
         if lib.pmx_index_read_header(os.fsencode(path), C.byref(info), C.byref(unc)) != 0:
             return None
         return dict(k=info.k, s=info.s, t=info.t, l=info.l, open=bool(info.open_syncmer), hpc=bool(info.hpc), uncompressed=bool(unc.value))
+
+    @property
+    def hpc(self) -> bool:
+        """the index holds the seeds of homopolymer-compressed genomes: a placer over it seeds the reads in their HPC form"""
+        return bool(self.info.hpc)
 
     def node_id(self, dfs_index: int) -> str:
         p = lib.pmx_index_node_id(self._h, int(dfs_index))
@@ -417,6 +425,40 @@ class ReadSet:
             raise ValueError("quality strings must have the lengths of the reads")
         buf = (C.c_char * max(len(qc), 1)).from_buffer_copy(qc if qc else b"\0")
         check(lib.pmx_readset_set_qualities(self.ctx._h, self._h, C.addressof(buf)), "pmx_readset_set_qualities")
+
+    def hpc_compress(self, pack: bool = True, out: Optional["ReadSet"] = None) -> "ReadSet":
+        """the homopolymer-compressed form of this read set, made on the device (pmx_readset_hpc_compress): what a placer over
+        an HPC index seeds from.  `out`: a read set returned by an earlier call, whose buffers are reused."""
+        if out is None:
+            out = ReadSet.__new__(ReadSet)
+            out.ctx = self.ctx
+            out._h = C.c_void_p()
+        check(lib.pmx_readset_hpc_compress(self.ctx._h, self._h, C.byref(out._h)), "pmx_readset_hpc_compress")
+        out._keep = None   # (only now: after a failed call a wrapped `out` still points at the buffers its keepalive holds)
+        out.n_reads = self.n_reads
+        out.total_bases = int(lib.pmx_readset_export(self.ctx._h, out._h, None, -1, None, None))
+        if pack:
+            out.pack()
+        return out
+
+    @property
+    def is_hpc(self) -> bool:
+        return bool(lib.pmx_readset_is_hpc(self._h))
+
+    def export(self):
+        """(concat, offsets, quals | None): the read set's ASCII bases, its n+1 offsets (starting at 0) and its qualities,
+        downloaded from the device"""
+        total = int(lib.pmx_readset_export(self.ctx._h, self._h, None, -1, None, None))
+        if total < 0:
+            raise _lib.PmxError(total, "pmx_readset_export")
+        has_qual = bool(lib.pmx_readset_has_qualities(self._h))
+        concat = np.zeros(max(total, 1), np.uint8)
+        qual = np.zeros(max(total, 1), np.uint8) if has_qual else None
+        off = np.zeros(self.n_reads + 1, np.int64)
+        got = int(lib.pmx_readset_export(self.ctx._h, self._h, concat.ctypes.data, total, off.ctypes.data, qual.ctypes.data if has_qual else None))
+        if got != total:
+            raise _lib.PmxError(got if got < 0 else -5, "pmx_readset_export")
+        return concat[:total].tobytes(), off, (qual[:total].tobytes() if has_qual else None)
 
     def close(self):
         if self._h:

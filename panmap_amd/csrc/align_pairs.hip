@@ -243,6 +243,7 @@ void pair_fanout(pmx_ctx* ctx, pmx_aligner* al, const uint32_t* rep, int64_t n_p
 // and the first align kernel (10M reads: ~1 ms).  Optional: an aligner that finds none makes it itself.
 int pmx_readset_order_pairs(pmx_ctx* ctx, pmx_readset* rs) {
     if (!ctx || !rs) return PMX_ERR_ARG;
+    if (rs->hpc) return fail(PMX_ERR_ARG, "the read set is homopolymer-compressed: the align stage's pair order is made of the uncompressed read set");
     if (!rs->packed) return fail(PMX_ERR_ARG, "read set is not packed");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));

@@ -171,6 +171,7 @@ void pmx_aligner_free(pmx_ctx* ctx, pmx_aligner* al) {
 // no record ever leaves this function with PMX_REC_OVERFLOW set because of the arena.
 int pmx_align_readset(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int paired, int revcomp_mate2) {
     if (!ctx || !al || !rs) return PMX_ERR_ARG;
+    if (rs->hpc) return fail(PMX_ERR_ARG, "the read set is homopolymer-compressed: the align stage works on the uncompressed reads, pass the read set it was compressed from");
     if (!rs->packed) return fail(PMX_ERR_ARG, "read set is not packed (call pmx_readset_pack first)");
     uint64_t cap = (uint64_t)std::max<int64_t>(rs->n * 16, 4096);
     // long reads: an operation every ~20 bases at 5 % errors; and whatever the previous call on this aligner needed per base

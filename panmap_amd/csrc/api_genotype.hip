@@ -224,6 +224,7 @@ void pmx_pileup_free(pmx_ctx* ctx, pmx_pileup* pu) {
 int pmx_pileup_run(pmx_ctx* ctx, pmx_pileup* pu, pmx_aligner* al, const pmx_readset* rs, int64_t ref_len, int paired, int revcomp_mate2,
                    const char* names_concat, const int64_t* name_offsets, const pmx_pileup_params* pp) {
     if (!ctx || !pu || !al || !rs) return PMX_ERR_ARG;
+    if (rs->hpc) return fail(PMX_ERR_ARG, "the read set is homopolymer-compressed: the pileup reads the bases the aligner saw, pass the uncompressed read set");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     const int64_t n = pmx_align_num_records(al);

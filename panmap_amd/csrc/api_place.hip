@@ -26,6 +26,8 @@ struct pmx_place {
     // index (device, replicated per GPU)
     int64_t n_nodes = 0, n_changes = 0;
     SyncmerParams params;
+    bool hpc = false;                      // the index was built over homopolymer-compressed genomes: reads are seeded in their HPC form
+    std::unique_ptr<pmx_readset> hpc_scratch;   // the HPC form of the plain read range of the current pmx_place_add_reads* call (buffers reused)
     DevBuf<uint32_t> parent;
     DevBuf<uint64_t> offsets, ch_hash;
     DevBuf<int16_t> ch_par, ch_child;
@@ -466,6 +468,7 @@ int pmx_readset_rewrap_device(pmx_ctx* ctx, pmx_readset* rs, const void* d_conca
     rs->packed_ranges.clear();
     rs->ordered_ranges.clear();
     rs->has_qual = false;
+    rs->hpc = false;
     rs->n = n_reads;
     rs->ascii.wrap((uint8_t*)d_concat, (size_t)total_bytes);
     rs->off.wrap((int64_t*)d_offsets, (size_t)n_reads + 1);
@@ -566,6 +569,106 @@ int pmx_readset_pack_range(pmx_ctx* ctx, pmx_readset* rs, int64_t r0, int64_t r1
     PMX_CATCH
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------------- homopolymer compression (hpc_kernels.hip)
+namespace {
+// a buffer pmx_readset_hpc_compress writes is the object's own, never one a caller wrapped
+template <class T>
+void own_ensure(DevBuf<T>& b, size_t count) {
+    if (!b.owned) b.release();
+    b.ensure(count);
+}
+
+// dst = the HPC form of the reads [r0, r1) of src: count (k_hpc_count), the byte and word offsets as two exclusive scans, write
+// (k_hpc_write), then the bookkeeping of the rewrap path from one 32-byte read-back.  No host pass over the reads.
+void hpc_compress_into(pmx_ctx* ctx, const pmx_readset* src, int64_t r0, int64_t r1, pmx_readset* dst) {
+    const int64_t m = r1 - r0;
+    dst->packed = false;
+    dst->has_order = false;
+    dst->has_pair_order = false;
+    dst->has_pair_map = false;
+    dst->packed_ranges.clear();
+    dst->ordered_ranges.clear();
+    dst->has_qual = false;
+    dst->hpc = true;
+    dst->n = m;
+    dst->off0 = 0;
+    own_ensure(dst->off, (size_t)m + 1);
+    // Sized by the bases of the WHOLE source set, also when [r0, r1) is a small range of it (pmx_place_add_reads_range): never
+    // too small -- the compressed reads are no longer than the source's -- and known on the host, so the count, the scans and
+    // the write are enqueued back to back and the call has one read-back, at its end.  The price is device memory: the scratch
+    // set of a placer that seeds a large batch range by range holds as many bytes as the batch.  Sizing by the range's own span
+    // would take a second read-back (off[r0], off[r1]) ahead of the kernels.
+    own_ensure(dst->ascii, (size_t)src->total + 32);
+    if (src->has_qual) dst->qual.ensure((size_t)src->total + 32);
+    dst->len_tmp.ensure((size_t)m + 1);
+    dst->nw_tmp.ensure((size_t)m + 1);
+    dst->woff.ensure((size_t)m + 1);
+    dst->stats.ensure(2);
+    PMX_HIP(hipMemsetAsync(dst->stats.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    const int grid = grid_for(m, 4, ctx->n_cu * 32);   // four waves per block, one read per wave and step
+    timer_begin(ctx, "hpc");
+    hipLaunchKernelGGL(k_hpc_count, dim3(grid), dim3(256), 0, ctx->stream, src->ascii.p, src->off.p + r0, m, dst->len_tmp.p, dst->nw_tmp.p, dst->stats.p);
+    PMX_HIP(hipGetLastError());
+    PMX_ROCPRIM(dst->scan_tmp, exclusive_scan, dst->len_tmp.p, dst->off.p, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), ctx->stream);
+    PMX_ROCPRIM(dst->scan_tmp, exclusive_scan, dst->nw_tmp.p, dst->woff.p, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), ctx->stream);
+    if (m > 0) {
+        hipLaunchKernelGGL(k_hpc_write, dim3(grid), dim3(256), 0, ctx->stream, src->ascii.p, src->off.p + r0, src->has_qual ? src->qual.p : (const uint8_t*)nullptr, m,
+                           dst->off.p, dst->ascii.p, src->has_qual ? dst->qual.p : (uint8_t*)nullptr);
+        PMX_HIP(hipGetLastError());
+    }
+    timer_end(ctx, "hpc", 1);
+    struct { int64_t total, n_words; unsigned long long st[2]; } h = {0, 0, {0, 0}};
+    PMX_HIP(hipMemcpyAsync(&h.total, dst->off.p + m, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(&h.n_words, dst->woff.p + m, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(h.st, dst->stats.p, sizeof(h.st), hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    dst->total = h.total;
+    dst->n_words = h.n_words;
+    dst->max_len = (int64_t)h.st[0];
+    dst->has_qual = src->has_qual;
+    dst->words.ensure((size_t)std::max<int64_t>(h.n_words, 1));
+    dst->amb.ensure((size_t)std::max<int64_t>(h.n_words, 1));
+    dst->has_recs = m > 0 && dst->max_len <= 160;
+    if (dst->has_recs) dst->recs.ensure((size_t)m * 64);
+}
+}  // namespace
+
+extern "C" {
+
+int pmx_readset_hpc_compress(pmx_ctx* ctx, const pmx_readset* src, pmx_readset** out) {
+    if (!ctx || !src || !out) return PMX_ERR_ARG;
+    if (*out == src) return fail(PMX_ERR_ARG, "pmx_readset_hpc_compress: the result cannot be the source read set");
+    if (src->hpc) return fail(PMX_ERR_ARG, "pmx_readset_hpc_compress: the read set is homopolymer-compressed already");
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    std::unique_ptr<pmx_readset> fresh;
+    pmx_readset* dst = *out;
+    if (!dst) { fresh.reset(new pmx_readset()); dst = fresh.get(); }
+    hpc_compress_into(ctx, src, 0, src->n, dst);
+    if (fresh) *out = fresh.release();
+    return PMX_OK;
+    PMX_CATCH
+}
+
+int pmx_readset_is_hpc(const pmx_readset* rs) { return rs && rs->hpc ? 1 : 0; }
+int pmx_readset_has_qualities(const pmx_readset* rs) { return rs && rs->has_qual ? 1 : 0; }
+
+int64_t pmx_readset_export(pmx_ctx* ctx, const pmx_readset* rs, char* concat, int64_t cap, int64_t* offsets, char* qual) {
+    if (!ctx || !rs) return PMX_ERR_ARG;
+    if (cap < rs->total || (rs->total > 0 && !concat) || !offsets) return rs->total;
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    if (rs->total > 0) PMX_HIP(hipMemcpyAsync(concat, rs->ascii.p + rs->off0, (size_t)rs->total, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipMemcpyAsync(offsets, rs->off.p, sizeof(int64_t) * ((size_t)rs->n + 1), hipMemcpyDeviceToHost, ctx->stream));
+    if (qual && rs->has_qual && rs->total > 0) PMX_HIP(hipMemcpyAsync(qual, rs->qual.p + rs->off0, (size_t)rs->total, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = rs->n; i >= 0; --i) offsets[i] -= offsets[0];
+    return rs->total;
+    PMX_CATCH
+}
+
 void pmx_readset_free(pmx_ctx* ctx, pmx_readset* rs) {
     if (ctx) (void)hipSetDevice(ctx->device);
     delete rs;
@@ -578,7 +681,6 @@ int pmx_place_create(pmx_ctx* ctx, const pmx_index* idx, pmx_place** out) {
     const LiteIndex* L = pmx_index_internal(idx);
     if (L->params.k > 32 || L->params.k < 1) return fail(PMX_ERR_UNSUPPORTED, "device seeding supports 1 <= k <= 32");
     if (L->params.l > 64) return fail(PMX_ERR_UNSUPPORTED, "device seeding supports l <= 64");
-    if (L->hpc) return fail(PMX_ERR_UNSUPPORTED, "HPC indexes are not supported on the device yet");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     pmx_place* pl = new pmx_place();
@@ -586,6 +688,7 @@ int pmx_place_create(pmx_ctx* ctx, const pmx_index* idx, pmx_place** out) {
     pl->n_nodes = n;
     pl->n_changes = m;
     pl->params = L->params;
+    pl->hpc = L->hpc;
     pl->parent.alloc(n); pl->offsets.alloc(n + 1); pl->ch_hash.alloc(m); pl->ch_par.alloc(m); pl->ch_child.alloc(m);
     PMX_HIP(hipMemcpyAsync(pl->parent.p, L->parent.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
     PMX_HIP(hipMemcpyAsync(pl->offsets.p, L->offsets.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
@@ -905,13 +1008,31 @@ unsigned long long SeedStage::failed_inserts() {
 
 }  // namespace
 
+// the messages of the calls that find a read set and an index of different kinds
+static const char* const kHpcSetPlainIndex = "the read set is homopolymer-compressed but the index is not an HPC index: pass the uncompressed read set";
+static const char* const kPlainSetHpcDedup = "the index is an HPC index and --dedup compares the compressed reads: compress first (pmx_readset_hpc_compress + pmx_readset_pack) and pass that read set to the dedup calls and to pmx_place_add_reads";
+
 static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, int64_t rr0, int64_t rr1, const pmx_place_params* pp) {
     if (!ctx || !pl || !rs || !pp || rr0 < 0 || rr1 < rr0 || rr1 > rs->n) return PMX_ERR_ARG;
     const bool whole = rr0 == 0 && rr1 == rs->n;
-    if (!rs->packed && !rs->packed_ranges.covers(rr0, rr1)) return fail(PMX_ERR_ARG, "read set is not packed (call pmx_readset_pack / pmx_readset_pack_range first)");
+    if (rs->hpc && !pl->hpc) return fail(PMX_ERR_ARG, kHpcSetPlainIndex);
+    const bool compress = pl->hpc && !rs->hpc;   // an HPC index sees compressed reads only (src/placement.cpp:1143-1165)
+    if (!compress && !rs->packed && !rs->packed_ranges.covers(rr0, rr1)) return fail(PMX_ERR_ARG, "read set is not packed (call pmx_readset_pack / pmx_readset_pack_range first)");
     if (!whole && pp->dedup_reads) return fail(PMX_ERR_UNSUPPORTED, "--dedup collapses duplicates over a whole read set: seed it with pmx_place_add_reads");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
+    if (compress) {
+        // the caller's set stays as it is: [rr0, rr1) is compressed into the placer's own scratch set (made again on every
+        // call: nothing to go stale), packed, and seeded from there with the derived set's numbers
+        if (!pl->hpc_scratch) pl->hpc_scratch.reset(new pmx_readset());
+        pl->dd_for = nullptr;
+        hpc_compress_into(ctx, rs, rr0, rr1, pl->hpc_scratch.get());
+        const int rc = pmx_readset_pack(ctx, pl->hpc_scratch.get());
+        if (rc != PMX_OK) return rc;
+        rs = pl->hpc_scratch.get();
+        rr0 = 0;
+        rr1 = rs->n;
+    }
     pl->h_ctr_valid = false;
     SeedStage S(ctx, pl, rs, pp, rr0, rr1);
     if (S.lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
@@ -955,6 +1076,8 @@ static int64_t dedup_mask_count(pmx_ctx* ctx, pmx_place* pl, int64_t n) {
 // the removal of the reads whose pair another rank already keeps
 int64_t pmx_place_dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, void* d_h1, void* d_h2, int64_t cap) {
     if (!ctx || !pl || !rs) return PMX_ERR_ARG;
+    if (rs->hpc && !pl->hpc) return fail(PMX_ERR_ARG, kHpcSetPlainIndex);
+    if (pl->hpc && !rs->hpc) return fail(PMX_ERR_ARG, kPlainSetHpcDedup);
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     dedup_local(ctx, pl, rs);
@@ -975,6 +1098,7 @@ int64_t pmx_place_dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs
 // reads the prepared mask still keeps (no recomputation)
 int64_t pmx_place_dedup_local_count(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs) {
     if (!ctx || !pl || !rs) return PMX_ERR_ARG;
+    if (pl->hpc && !rs->hpc) return fail(PMX_ERR_ARG, kPlainSetHpcDedup);
     if (pl->dd_for != rs) return fail(PMX_ERR_ARG, "pmx_place_dedup_local must run on this read set first");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
@@ -984,6 +1108,7 @@ int64_t pmx_place_dedup_local_count(pmx_ctx* ctx, pmx_place* pl, const pmx_reads
 
 int pmx_place_dedup_drop_seen(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, void* d_seen_h1, void* d_seen_h2, int64_t n_seen) {
     if (!ctx || !pl || !rs || n_seen < 0 || (n_seen > 0 && (!d_seen_h1 || !d_seen_h2))) return PMX_ERR_ARG;
+    if (pl->hpc && !rs->hpc) return fail(PMX_ERR_ARG, kPlainSetHpcDedup);
     if (pl->dd_for != rs) return fail(PMX_ERR_ARG, "pmx_place_dedup_local must run on this read set first");
     if (n_seen == 0 || rs->n == 0) return PMX_OK;
     PMX_TRY

@@ -82,6 +82,8 @@ void usage() {
           "  -i, --index PATH           load a pre-built index       --index-out PATH   write the built index here\n"
           "  -f, --reindex              force rebuild                --zstd-level N     (default 7)   --index-uncompressed\n"
           "  -k N  -s N  -l N  --offset N  --open-syncmer  --flank-mask N  --seed-mask-fraction F\n"
+          "      --hpc                  the index must be homopolymer-compressed (one given with -i or found at <panman>.idx is used as\n"
+          "                             it is, with or without this flag; this command line does not build one; not with --meta)\n"
           "      --dedup --trim-start N --trim-end N --min-seed-quality N --min-read-support N --force-leaf\n"
           "  -a, --aligner minimap2     -q, --quiet   -h, --help   -V, --version\n", stderr);
 }
@@ -238,8 +240,10 @@ void mkdirs(const std::string& dir) {   // fs::create_directories
     }
 }
 
-// cachedIndexUsable (src/main.cpp:371-396)
-bool cached_index_usable(const Config& c) {
+// cachedIndexUsable (src/main.cpp:371-396).  The index is authoritative about HPC, as in the reference (the place stage takes
+// `hpc` from the index, src/placement.cpp:1095-1101): an index whose header says hpc = 1 is usable when the other parameters
+// match, with or without --hpc on the command line -- it is never rebuilt over.  *is_hpc: what the header says.
+bool cached_index_usable(const Config& c, bool* is_hpc) {
     if (exists(c.panman) && mtime(c.index) < mtime(c.panman)) {
         fprintf(stderr, "panmap: cached index %s is older than %s; rebuilding.\n", c.index.c_str(), c.panman.c_str());
         return false;
@@ -250,12 +254,20 @@ bool cached_index_usable(const Config& c) {
         fprintf(stderr, "panmap: cached index %s has no readable param header (old format/corrupt); rebuilding.\n", c.index.c_str());
         return false;
     }
-    if (h.k != c.k || h.s != c.s || h.t != c.t || h.l != c.l || (h.hpc != 0) != c.hpc || (h.open_syncmer != 0) != c.open_syncmer) {
-        fprintf(stderr, "panmap: cached index %s was built with different seeding parameters (k/s/t/l/hpc/open-syncmer); rebuilding.\n", c.index.c_str());
+    if (h.k != c.k || h.s != c.s || h.t != c.t || h.l != c.l || (h.open_syncmer != 0) != c.open_syncmer) {
+        fprintf(stderr, "panmap: cached index %s was built with different seeding parameters (k/s/t/l/open-syncmer); rebuilding.\n", c.index.c_str());
         return false;
     }
+    *is_hpc = h.hpc != 0;
     return true;
 }
+
+// --hpc means "the index must be an HPC index"; this command line does not build one (that producer is not pinned to the
+// reference's: DESIGN.md section 7)
+const char* const kHpcNeedsIndex =
+    "--hpc needs a homopolymer-compressed index, and this command line does not build one.  Make it with the reference's "
+    "`panmap <panman> --hpc --stop index`, or with pmx_index_build_ex(..., mode | PMX_INDEX_HPC, ...) / Index.build(hpc=True) + "
+    "save, and name it with -i (or leave it at <panman>.idx)";
 
 char comp(char b) {   // seeding::reverseComplement (src/seeding.cpp:271-284): A/C/G/T only, everything else kept
     switch (b) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return b; }
@@ -267,10 +279,11 @@ char comp(char b) {   // seeding::reverseComplement (src/seeding.cpp:271-284): A
 struct SampleGuard {
     pmx_ctx* ctx;
     pmx_fastx *f1 = nullptr, *f2 = nullptr;
-    pmx_readset* rs = nullptr;
+    pmx_readset *rs = nullptr, *rs_hpc = nullptr;
     pmx_aligner* al = nullptr;
     ~SampleGuard() {
         if (al) pmx_aligner_free(ctx, al);
+        if (rs_hpc) pmx_readset_free(ctx, rs_hpc);
         if (rs) pmx_readset_free(ctx, rs);
         if (f1) pmx_fastx_free(f1);
         if (f2) pmx_fastx_free(f2);
@@ -329,8 +342,19 @@ std::string run_sample(const Config& c, int stop, pmx_panman*& pm, pmx_index* id
     if (c.min_seed_quality > 0) check(pmx_readset_set_qualities(ctx, rs, quals.data() + off[(size_t)lo]), "attaching the qualities");
     pmx_place_result res;
     check(pmx_place_reset(ctx, pl), "place reset");
-    if (dist && c.dedup && c.min_seed_quality <= 0) check(pmx_dist_dedup_reads(dist, pl, rs, nullptr), "collapsing duplicate reads over the ranks");
-    check(pmx_place_add_reads(ctx, pl, rs, &pp), "seeding the reads");
+    // An HPC index: the placer compresses the reads by itself (the raw reads go on to the align, genotype and consensus stages).
+    // Only the dedup over the ranks needs the compressed set in hand: its calls hash the read bytes and are matched to the
+    // seeding call by the read set, so the shard is compressed here and that set is given to both.
+    pmx_readset* seed_rs = rs;
+    pmx_index_info ii;
+    check(pmx_index_get_info(idx, &ii), "index info");
+    if (ii.hpc && dist && c.dedup && c.min_seed_quality <= 0) {
+        check(pmx_readset_hpc_compress(ctx, rs, &g.rs_hpc), "compressing the reads");
+        check(pmx_readset_pack(ctx, g.rs_hpc), "packing the compressed reads");
+        seed_rs = g.rs_hpc;
+    }
+    if (dist && c.dedup && c.min_seed_quality <= 0) check(pmx_dist_dedup_reads(dist, pl, seed_rs, nullptr), "collapsing duplicate reads over the ranks");
+    check(pmx_place_add_reads(ctx, pl, seed_rs, &pp), "seeding the reads");
     if (dist) check(pmx_dist_merge_histograms(dist, pl), "merging the ranks' seed histograms");
     check(pmx_place_score(ctx, pl, &pp, n_reads, &res), "scoring the tree");
     static const char* metric_names[5] = {"log_raw", "log_cosine", "containment", "weighted_containment", "log_containment"};
@@ -784,7 +808,6 @@ int real_main(int argc, char** argv) {
     Config c = parse(argc, argv);
     if (c.s <= 0 || c.s > c.k) die("Invalid syncmer s=" + std::to_string(c.s) + " (must be in 1..k, k=" + std::to_string(c.k) + ")");
     if (c.t < 0 || c.t > c.k - c.s) die("Invalid syncmer offset=" + std::to_string(c.t) + " (must be in 0..k-s = 0.." + std::to_string(c.k - c.s) + ")");
-    if (c.hpc) die("--hpc (homopolymer-compressed seeds) is not implemented in this build");
     if (c.aligner != "minimap2") die("aligner '" + c.aligner + "' is not implemented in this build (minimap2 only)");
     int stop = c.stop == "index" ? 0 : c.stop == "place" ? 1 : c.stop == "align" ? 2 : c.stop == "genotype" ? 3 : c.stop == "consensus" ? 4 : -1;
     if (stop < 0) die("--stop expects index|place|align|genotype|consensus");
@@ -794,15 +817,23 @@ int real_main(int argc, char** argv) {
     if (!c.batch.empty() && !c.reads1.empty()) die("--batch takes the read files from the batch file, not from the command line");
     if (c.gpus < 1) die("--gpus expects a positive number");
 
-    if (c.meta) return run_meta(c);
+    if (c.meta) {   // the reference's --meta has no HPC
+        pmx_index_info h;
+        if (c.hpc) die("--meta has no homopolymer-compressed form: drop --hpc");
+        if (exists(c.index) && pmx_index_read_header(c.index.c_str(), &h, nullptr) == PMX_OK && h.hpc) die("--meta cannot use the homopolymer-compressed index " + c.index);
+        return run_meta(c);
+    }
 
     // ------------------------------------------------------------------------------------------------ index
     pmx_panman* pm = nullptr;
     pmx_index* idx = nullptr;
-    if (exists(c.index) && !c.force_reindex && cached_index_usable(c)) {
+    bool idx_hpc = false;
+    if (exists(c.index) && !c.force_reindex && cached_index_usable(c, &idx_hpc)) {
+        if (c.hpc && !idx_hpc) die(std::string(kHpcNeedsIndex) + "; " + c.index + " is not one");
         check(pmx_index_load(c.index.c_str(), &idx), "loading the index");
-        say(c, "index", c.index + " (cached)");
+        say(c, "index", c.index + " (cached)" + (idx_hpc ? ", homopolymer-compressed" : ""));
     } else {
+        if (c.hpc) die(kHpcNeedsIndex);
         check(pmx_panman_open(c.panman.c_str(), &pm), "opening the PanMAN");
         check(pmx_index_build(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, c.flank_mask, &idx), "building the index");
         check(pmx_index_save(idx, c.index.c_str(), c.zstd_level, c.index_uncompressed ? 1 : 0), "writing the index");

@@ -284,28 +284,38 @@ bool has_inverted_blocks(const Panman& pm) {
 // back up), its seed multiset extracted as the reference's test helpers do (src/test/helpers/
 // seed_helpers.cpp: extractSeeds + k-min-mers) and diffed against the parent's.  O(genome) per node instead
 // of O(mutated columns); used for PanMANs with inverted blocks, which the incremental builder does not track,
-// and by tests/test_host_stage.py as an independent check of the incremental builder.
-void build_from_scratch(const Panman& pm, const SyncmerParams& p, int flank_mask, size_t max_nodes, LiteIndex& out) {
-    typedef std::vector<std::pair<uint64_t, int32_t>> Counts;
-    const size_t n = std::min(pm.nodes.size(), max_nodes);
-    PanmanState st;
-    st.init(pm);
-    std::vector<int32_t> stack;
-    std::vector<UndoLog> undos;
-    std::vector<Counts> counts;
-    for (size_t i = 0; i < n; ++i) {
+// by tests/test_host_stage.py as an independent check of the incremental builder, and for HPC indexes (hpc: the
+// seeds of the homopolymer-compressed genome, genome_seed_counts).
+typedef std::vector<std::pair<uint64_t, int32_t>> Counts;
+struct ScratchOut {
+    std::vector<uint64_t> hash, ends;
+    std::vector<int16_t> pc, cc;
+};
+
+// the nodes [first, last) of the pre-order; `st` / `stack` / `undos` / `counts` hold the root path of `first`'s parent.
+// have[d] = 0: the seeds of the ancestor at depth d were not extracted when a worker replayed its path; they are when the
+// walk comes back up to it (the state is then that ancestor's) and a sibling subtree needs them.
+void scratch_range(const Panman& pm, const SyncmerParams& p, int flank_mask, bool hpc, PanmanState& st, std::vector<int32_t>& stack,
+                   std::vector<UndoLog>& undos, std::vector<Counts>& counts, std::vector<uint8_t>& have, size_t first, size_t last, ScratchOut& o) {
+    for (size_t i = first; i < last; ++i) {
         const int32_t par = pm.nodes[i].parent;
         while (!stack.empty() && stack.back() != par) {
             undo_node(st, undos.back());
             undos.pop_back();
             counts.pop_back();
+            have.pop_back();
             stack.pop_back();
+        }
+        if (!have.empty() && !have.back()) {
+            genome_seed_counts(genome_of_state(pm, st), p, flank_mask, counts.back(), hpc);
+            have.back() = 1;
         }
         undos.emplace_back();
         stack.push_back((int32_t)i);
         apply_node(pm, (int32_t)i, st, &undos.back(), nullptr);
         counts.emplace_back();
-        genome_seed_counts(genome_of_state(pm, st), p, flank_mask, counts.back());
+        have.push_back(1);
+        genome_seed_counts(genome_of_state(pm, st), p, flank_mask, counts.back(), hpc);
         static const Counts empty;
         const Counts& pc = counts.size() >= 2 ? counts[counts.size() - 2] : empty;
         const Counts& cc = counts.back();
@@ -313,26 +323,86 @@ void build_from_scratch(const Panman& pm, const SyncmerParams& p, int flank_mask
         auto emit = [&](uint64_t h, int32_t x, int32_t y) {
             if (x == y) return;
             if (x > INT16_MAX || y > INT16_MAX) throw std::runtime_error("index build: seed count exceeds int16");
-            out.hash.push_back(h);
-            out.parent_count.push_back((int16_t)x);
-            out.child_count.push_back((int16_t)y);
+            o.hash.push_back(h);
+            o.pc.push_back((int16_t)x);
+            o.cc.push_back((int16_t)y);
         };
         while (a < pc.size() || b < cc.size()) {
             if (b == cc.size() || (a < pc.size() && pc[a].first < cc[b].first)) { emit(pc[a].first, pc[a].second, 0); ++a; }
             else if (a == pc.size() || cc[b].first < pc[a].first) { emit(cc[b].first, 0, cc[b].second); ++b; }
             else { emit(pc[a].first, pc[a].second, cc[b].second); ++a; ++b; }
         }
-        out.offsets[i + 1] = out.hash.size();
+        o.ends.push_back(o.hash.size());
+    }
+}
+
+void build_from_scratch(const Panman& pm, const SyncmerParams& p, int flank_mask, bool hpc, size_t max_nodes, LiteIndex& out) {
+    const size_t n = std::min(pm.nodes.size(), max_nodes);
+    // The HPC producer has no incremental form, so it is the one that runs over whole trees: it is cut the way the incremental
+    // builder is (below) -- contiguous chunks of the pre-order, each worker replaying the root path of its chunk's first node
+    // (a node's genome depends on its root path alone) and seeding that node's parent once.  The chunks' outputs are
+    // concatenated in order: the same arrays as the serial walk.  (Without hpc the walk stays serial, as it was.)
+    unsigned n_thr = hpc ? std::min(16u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+    if (hpc)
+        if (const char* e = pmx::opt_str(pmx::O_INDEX_THREADS)) n_thr = (unsigned)std::max(1, atoi(e));
+    const size_t n_chunks = n_thr <= 1 || n < 1024 ? 1 : std::min<size_t>((size_t)n_thr * 6, std::max<size_t>(1, n / 128));
+    struct Chunk { size_t first, last; ScratchOut o; std::string err; };
+    std::vector<Chunk> chunks(n_chunks);
+    for (size_t c = 0; c < n_chunks; ++c) { chunks[c].first = n * c / n_chunks; chunks[c].last = n * (c + 1) / n_chunks; }
+    auto run_chunk = [&](Chunk& ck) {
+        if (ck.first >= ck.last) return;
+        PanmanState st;
+        st.init(pm);
+        std::vector<int32_t> stack, path;
+        std::vector<UndoLog> undos;
+        std::vector<Counts> counts;
+        std::vector<uint8_t> have;
+        if (ck.first > 0)
+            for (int32_t v = pm.nodes[ck.first].parent; v >= 0; v = pm.nodes[(size_t)v].parent) { path.push_back(v); if (v == 0) break; }
+        for (size_t k = path.size(); k-- > 0;) {   // ancestors top down; their seeds are extracted when first needed
+            undos.emplace_back();
+            stack.push_back(path[k]);
+            apply_node(pm, path[k], st, &undos.back(), nullptr);
+            counts.emplace_back();
+            have.push_back(0);
+        }
+        scratch_range(pm, p, flank_mask, hpc, st, stack, undos, counts, have, ck.first, ck.last, ck.o);
+    };
+    if (n_chunks == 1) run_chunk(chunks[0]);
+    else {
+        std::atomic<size_t> next{0};
+        std::vector<std::thread> pool;
+        for (unsigned t = 0; t < std::min<size_t>(n_thr, n_chunks); ++t)
+            pool.emplace_back([&]() {
+                for (;;) {
+                    const size_t c = next.fetch_add(1);
+                    if (c >= n_chunks) break;
+                    try { run_chunk(chunks[c]); }
+                    catch (const std::exception& e) { chunks[c].err = e.what(); if (chunks[c].err.empty()) chunks[c].err = "index build failed"; }
+                }
+            });
+        for (auto& th : pool) th.join();
+        for (const Chunk& ck : chunks)
+            if (!ck.err.empty()) throw std::runtime_error(ck.err);
+    }
+    for (const Chunk& ck : chunks) {
+        const uint64_t base = out.hash.size();
+        out.hash.insert(out.hash.end(), ck.o.hash.begin(), ck.o.hash.end());
+        out.parent_count.insert(out.parent_count.end(), ck.o.pc.begin(), ck.o.pc.end());
+        out.child_count.insert(out.child_count.end(), ck.o.cc.begin(), ck.o.cc.end());
+        for (size_t i = ck.first; i < ck.last; ++i) out.offsets[i + 1] = base + ck.o.ends[i - ck.first];
     }
     for (size_t i = n; i < pm.nodes.size(); ++i) out.offsets[i + 1] = out.hash.size();
 }
 }  // namespace
 
-void build_lite_index(const Panman& pm, const SyncmerParams& p, int flank_mask, LiteIndex& out, int mode, size_t max_nodes) {
+void build_lite_index(const Panman& pm, const SyncmerParams& p, int flank_mask, LiteIndex& out, int mode, size_t max_nodes, bool hpc) {
     if (p.l > 32) throw std::runtime_error("index build: l > 32 unsupported");
+    if (hpc && mode == 2) throw std::runtime_error("index build: the incremental producer has no HPC form");
     out = LiteIndex();
     out.params = p;
     out.flank_mask = flank_mask;
+    out.hpc = hpc;
     const size_t n = pm.nodes.size();
     out.node_id.resize(n);
     out.parent.resize(n);
@@ -343,8 +413,8 @@ void build_lite_index(const Panman& pm, const SyncmerParams& p, int flank_mask, 
     }
     if (n == 0) return;
     (void)has_inverted_blocks;
-    if (mode == 1) {
-        build_from_scratch(pm, p, flank_mask, max_nodes, out);
+    if (mode == 1 || hpc) {
+        build_from_scratch(pm, p, flank_mask, hpc, max_nodes, out);
         return;
     }
     const size_t n_do = std::min(n, max_nodes);
@@ -432,17 +502,34 @@ void build_lite_index(const Panman& pm, const SyncmerParams& p, int flank_mask, 
     for (size_t i = n_do; i < n; ++i) out.offsets[i + 1] = out.hash.size();
 }
 
-void genome_seed_counts(const std::string& genome, const SyncmerParams& p, int flank_mask,
-                        std::vector<std::pair<uint64_t, int32_t>>& sorted_counts) {
+// seeding::hpcCompressWithMapping (src/seeding.cpp:291-306): base 0, then every base whose letter differs from its predecessor's
+// (toupper on both); mapping[j] = index of the j-th kept base
+static void hpc_compress_with_mapping(const std::string& seq, std::string& out, std::vector<int64_t>& mapping) {
+    out.clear();
+    mapping.clear();
+    auto up = [](char c) { return c >= 'a' && c <= 'z' ? (char)(c - 32) : c; };
+    for (size_t i = 0; i < seq.size(); ++i)
+        if (i == 0 || up(seq[i]) != up(seq[i - 1])) { out.push_back(seq[i]); mapping.push_back((int64_t)i); }
+}
+
+void genome_seed_counts(const std::string& genome_in, const SyncmerParams& p, int flank_mask,
+                        std::vector<std::pair<uint64_t, int32_t>>& sorted_counts, bool hpc) {
+    // hpc: the seeds of the compressed genome; the flank mask is judged at the UNCOMPRESSED coordinate of the k-mer's first base,
+    // against the uncompressed length (effectiveCoords[startPos], src/index_single_mode.cpp:878-883)
+    std::string compressed;
+    std::vector<int64_t> mapping;
+    if (hpc) hpc_compress_with_mapping(genome_in, compressed, mapping);
+    const std::string& genome = hpc ? compressed : genome_in;
     std::vector<uint8_t> is_sync;
     std::vector<uint64_t> sh;
     host_syncmers(genome.data(), (int64_t)genome.size(), p, is_sync, sh);
     std::vector<uint64_t> h;
-    const int64_t n = (int64_t)genome.size();
-    for (int64_t i = 0; i < (int64_t)is_sync.size(); ++i) {
-        if (!is_sync[i]) continue;
+    const int64_t n = (int64_t)genome_in.size();
+    for (int64_t j = 0; j < (int64_t)is_sync.size(); ++j) {
+        if (!is_sync[j]) continue;
+        const int64_t i = hpc ? mapping[(size_t)j] : j;
         if (flank_mask > 0 && (i < flank_mask - 1 || i > n - flank_mask)) continue;
-        h.push_back(sh[i]);
+        h.push_back(sh[j]);
     }
     std::unordered_map<uint64_t, int32_t> cnt;
     const int l = p.l < 1 ? 1 : p.l;

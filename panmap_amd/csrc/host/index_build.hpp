@@ -28,13 +28,15 @@ struct LiteIndex {
 // proportional to the mutated columns of every node), or the from-scratch producer (every node's genome
 // re-seeded and diffed against its parent) when the PanMAN has inverted blocks; 1 = from scratch, 2 =
 // incremental.  max_nodes < n_nodes stops after that many nodes in DFS order (tests).
+// hpc: the index of the homopolymer-compressed genomes (always the from-scratch producer; mode 2 throws).
 // Throws std::runtime_error on count overflow.
 void build_lite_index(const Panman& pm, const SyncmerParams& p, int flank_mask, LiteIndex& out, int mode = 0,
-                      size_t max_nodes = (size_t)-1);
+                      size_t max_nodes = (size_t)-1, bool hpc = false);
 
 // From-scratch seed multiset of a genome string with the hard flank mask applied (test helper
-// mirroring src/test/helpers/seed_helpers.cpp:12 extractSeeds + k-min-mers).
+// mirroring src/test/helpers/seed_helpers.cpp:12 extractSeeds + k-min-mers).  hpc: the seeds of hpcCompress(genome), the
+// flank mask judged at the uncompressed coordinate of each k-mer's first base.
 void genome_seed_counts(const std::string& genome, const SyncmerParams& p, int flank_mask,
-                        std::vector<std::pair<uint64_t, int32_t>>& sorted_counts);
+                        std::vector<std::pair<uint64_t, int32_t>>& sorted_counts, bool hpc = false);
 
 }  // namespace pmx

@@ -81,5 +81,9 @@ __global__ void k_score_chains(const uint32_t* chain_off, int64_t n_chains, cons
 __global__ void k_score_getters(const double* metrics5, const int64_t* counts2, int64_t n_nodes, const double* scalars, int64_t n_kept,
                                 double* scores5, const uint32_t* order, double* scores_bfs);
 __global__ void k_fill_u64(uint64_t* p, uint64_t v, uint64_t n);
+// hpc_kernels.hip: homopolymer compression of a read set (one wave per read)
+__global__ void k_hpc_count(const uint8_t* ascii, const int64_t* off, int64_t n_reads, int64_t* len, int64_t* nwords, unsigned long long* stats);
+__global__ void k_hpc_write(const uint8_t* ascii, const int64_t* off, const uint8_t* qual, int64_t n_reads, const int64_t* out_off, uint8_t* out_ascii,
+                            uint8_t* out_qual);
 
 }  // namespace pmx

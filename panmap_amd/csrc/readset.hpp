@@ -53,6 +53,8 @@ struct pmx_readset {
     pmx::DevBuf<char> scan_tmp;    // rewrap: rocprim temp storage
     pmx::DevBuf<unsigned long long> stats;
     int64_t off0 = 0;              // first offset (non-zero for a wrapped slice of a larger offsets array)
+    bool hpc = false;              // the reads are homopolymer-compressed (pmx_readset_hpc_compress): for an HPC index only
+    pmx::DevBuf<int64_t> len_tmp;  // hpc_compress: bases per compressed read (scan input)
     // locality order of the reads (read_locality_key, device/pmx_math.h): computed once per packing, on first request, and
     // shared by the seeding launch order (place stage) and the pair order of the align stage
     mutable pmx::DevBuf<uint32_t> loc_key, loc_key2, loc_idx, loc_perm;
