@@ -1072,6 +1072,34 @@ PMX_HD int compact_chain_pair(const CMemT<PT, CAP>& m, const Opt& o, const RefIn
         const int32_t run_lim = max_dist_x < max_dist_y ? max_dist_x : max_dist_y;
         int r0 = 0, jv = 0;
         uint32_t ax_p = 0, ay_p = 0, f_p = 0;   // anchor i - 1
+        // Dominated tail.  Where the mates overlap on the reference both carry the same minimizers and the sorted anchors
+        // alternate between the mates: neither form above fires (anchor i - 1 is the other mate's), and every anchor after
+        // the overlap pays the whole interleaved stretch again.  Write sc_t(j) = f[j] + comput_sc(t, j), and call an
+        // anchor t FULL when sc_t(j) <= f[t] for every j in [st_t, t - 1] that is valid for t (true after a loop that ran
+        // down to st without the max_skip break: f[t] is the maximum of everything it evaluated, and what the two forms
+        // above skipped was proved not better).  Let i' be the last anchor of i's mate below i (same strand), on i's
+        // diagonal, d = q_i - q_i' = x_i - x_i' in (0, run_lim] (so i' is valid for i with sc_i(i') = f[i'] + min(d, k):
+        // dd == 0 has no penalty when chn_pen_skip == 0), and FULL.  Take j < i' in [st_i, i' - 1] (st never falls, so
+        // j >= st_i'), valid for i.
+        //   * j valid for i' too: from i' to i both dq and dr grow by d, dd and the segment relation stay, so the penalty
+        //     is the same number and dg_i = dg_i' + d; min(dg + d, k) <= min(dg, k) + min(d, k), and in the dr_i'(j) == 0
+        //     case of mates (comput_sc = 1 for i') comput_sc(i, j) <= min(d, k).  x_j <= x_i' < x_i, so i itself never has
+        //     that case.  Hence sc_i(j) <= sc_i'(j) + min(d, k) <= f[i'] + min(d, k) = sc_i(i').
+        //   * j valid for i but not for i': the upper limits and dd only get worse from i' to i, so this needs
+        //     dq_i'(j) <= 0 < dq_i(j), i.e. q_i' <= q_j < q_i, or, for j of i's own mate, x_j == x_i'.  The condition
+        //     below excludes both from registers: i' lies strictly above every earlier anchor of its mate in q and above
+        //     the previous one in x (the anchors are sorted by x), and the other mate's anchors so far are all below q_i'
+        //     or all at or above q_i.
+        // So once the loop has passed i' (visited it, or skipped it as not better), max_f >= sc_i(i') bounds every lower
+        // anchor: none is better, whatever the marks and n_skip do, and (max_f, max_j) is final.  The max_skip break the
+        // reference may still take below i' matters only through the max_ii test, and max_ii < end_j < i' is such a lower
+        // anchor (max_ii >= st_i: same strand, within max_dist_x), which cannot raise max_f either.  The loop therefore
+        // ends at i' -- and, when i' = i - 1 (`extends`), is not entered at all.  Anchor i is then FULL itself unless
+        // the part of the loop that did run took the break.
+        // Per strand and mate s: dl_i = index of the last anchor (-1: none), dl_x / dl_q = its position / query position,
+        // dq_hi / dq_lo = extremes of q so far, dflag bit s = FULL, bit 2 + s = strictly above its mate's earlier anchors.
+        int32_t dl_i0 = -1, dl_i1 = -1, dl_q0 = 0, dl_q1 = 0, dq_hi0 = -1, dq_hi1 = -1, dq_lo0 = 0x7fffffff, dq_lo1 = 0x7fffffff;
+        uint32_t dl_x0 = 0, dl_x1 = 0, dflag = 0;
         for (int i = 0; i < n; ++i) {
             const uint32_t axi = m.X(i);
             const uint32_t ayi = m.Y(i);
@@ -1090,7 +1118,20 @@ PMX_HD int compact_chain_pair(const CMemT<PT, CAP>& m, const Opt& o, const RefIn
             const int32_t dq_p = qi - (int32_t)(ay_p & 0x3ffu);
             const bool extends = use_tab && i > 0 && st <= i - 1 && MT::rev_of(axi ^ ax_p) == 0u && ((ayi ^ ay_p) >> 10 & 1u) == 0u && dq_p > 0 &&
                                  (int32_t)(rpi - MT::pos_of(ax_p)) == dq_p && dq_p <= run_lim;
-            if (extends) {
+            if (i > 0 && MT::rev_of(axi ^ ax_p) != 0u) {   // the other strand starts over
+                dl_i0 = dl_i1 = -1; dq_hi0 = dq_hi1 = -1; dq_lo0 = dq_lo1 = 0x7fffffff; dflag = 0;
+            }
+            const int32_t dl_i = sidi ? dl_i1 : dl_i0, dl_q = sidi ? dl_q1 : dl_q0;
+            const int32_t o_hi = sidi ? dq_hi0 : dq_hi1, o_lo = sidi ? dq_lo0 : dq_lo1;
+            const int32_t d_d = qi - dl_q;
+            const bool dom = use_tab && dl_i >= st && (dflag >> sidi & 5u) == 5u && d_d > 0 && (int32_t)(rpi - (sidi ? dl_x1 : dl_x0)) == d_d &&
+                             d_d <= run_lim && (o_hi < dl_q || o_lo >= qi);
+            const int32_t j_lo = dom ? dl_i : st;
+            if (extends && dom) {   // i' = i - 1: nothing below it can be better
+                max_f = (int32_t)(f_p & 0x3ffu) + (dq_p < k ? dq_p : k);
+                mj = i - 1;
+                j_from = j_lo - 1;
+            } else if (extends) {
                 const int lo = r0 > st ? r0 : st;
                 if (jv < lo) jv = lo;
                 while (qi - (int32_t)(m.Y(jv) & 0x3ffu) > run_lim) ++jv;   // ends at i - 1 at the latest
@@ -1110,7 +1151,7 @@ PMX_HD int compact_chain_pair(const CMemT<PT, CAP>& m, const Opt& o, const RefIn
             PMX_C_COUNT(0, 1);
             int trace_trips = 0, trace_rescan = 0;
             (void)trace_trips; (void)trace_rescan;
-            for (int32_t j = j_from; j >= st && !stop; --j) {
+            for (int32_t j = j_from; j >= j_lo && !stop; --j) {
                 PMX_C_COUNT(1, 1);
                 ++trace_trips;
                 const uint32_t axj = m.X(j);
@@ -1191,6 +1232,13 @@ PMX_HD int compact_chain_pair(const CMemT<PT, CAP>& m, const Opt& o, const RefIn
             if (getenv("PMX_C_DUMP")) fprintf(stderr, "i=%d pos=%u q=%d seg=%d f=%d p=%d r0=%d ext=%d st=%d\n", i, rpi, qi, sidi, max_f, max_j, r0, (int)extends, st);
 #endif
             ax_p = axi; ay_p = ayi; f_p = (uint32_t)max_f;
+            {
+                const bool above = qi > (sidi ? dq_hi1 : dq_hi0) && (dl_i < 0 || rpi != (sidi ? dl_x1 : dl_x0));
+                const uint32_t fl = (stop ? 0u : 1u) | (above ? 4u : 0u);
+                dflag = (dflag & ~(5u << sidi)) | fl << sidi;
+                if (sidi) { dl_i1 = i; dl_x1 = rpi; dl_q1 = qi; dq_hi1 = qi > dq_hi1 ? qi : dq_hi1; dq_lo1 = qi < dq_lo1 ? qi : dq_lo1; }
+                else { dl_i0 = i; dl_x0 = rpi; dl_q0 = qi; dq_hi0 = qi > dq_hi0 ? qi : dq_hi0; dq_lo0 = qi < dq_lo0 ? qi : dq_lo0; }
+            }
         }
     }
 

@@ -5,10 +5,11 @@ an evaluation budget with a second pass, or waves of pairs of equal (predicted) 
 from an 827-base stretch of the genome, i.e. at the depth of the 10M-read batch (~130 pairs per start position): the waves
 of the real launch are then as homogeneous as the pair order by both mates' keys makes them.  profiles/r04/README.md quotes it."""
 import sys, os, ctypes as C, numpy as np
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import panmap_amd as pmx
 from align_checks import hostsim, Rec
-pm = pmx.Panman("tests/golden/sars_20000_twilight_dipper.panman")
+pm = pmx.Panman(os.path.join(ROOT, "tests", "golden", "sars_20000_twilight_dipper.panman"))
 g = pm.genome("node_7618")
 npairs = 64 * 600
 sub = g[8000:8000 + 227 + 600] if os.environ.get("DENSE") else g
@@ -39,6 +40,16 @@ for w in range(0, npairs, 64):
 nw = npairs // 64
 print("per wave: inner loop steps now %.1f, flattened %.1f ; rescan steps now %.1f, flattened %.1f ; anchors max %.1f" % (A / nw, B / nw, A2 / nw, B2 / nw, np.mean([na[w:w+64].max() for w in range(0, npairs, 64)])))
 tot = trips.sum(1)
+# per-anchor trips: how many anchors make t trips, and which share of all evaluations the anchors with >= t trips carry
+live = np.arange(64)[None, :] < na[:, None]
+tl = trips[live]
+hist = np.bincount(tl)
+print("per-anchor trips (anchors):", " ".join("%d:%d" % (t, c) for t, c in enumerate(hist) if c), " max", tl.max())
+for t in (4, 8, 16, 24):
+    print("anchors with >= %2d trips: %.4f of the anchors, %.3f of the evaluations" % (t, (tl >= t).mean(), tl[tl >= t].sum() / max(1, tl.sum())))
+for cap_at, cost in ((16, 3), (8, 3)):
+    tc = np.where(trips >= cap_at, cost, trips)
+    print("if every anchor with >= %d trips cost %d: %.1f steps per wave" % (cap_at, cost, sum(tc[w:w+64].max(0).sum() for w in range(0, npairs, 64)) / nw))
 print("evals per pair percentiles", np.percentile(tot, [10, 50, 75, 90, 95, 98, 99, 99.9]))
 def wave_cost(t):   # sum over anchors of the slowest lane
     return t.max(0).sum()
@@ -61,6 +72,10 @@ print("sorted by cost (ideal homogeneous waves): %.1f" % (sum(wave_cost(srt[w:w+
 print("---- proxies")
 rs1 = ra["rs"][0::2][order]; re1 = ra["re"][0::2][order]; rs2 = ra["rs"][1::2][order]; re2 = ra["re"][1::2][order]
 ov = np.maximum(0, np.minimum(re1, re2) - np.maximum(rs1, rs2))
+print("overlap of the mates on the reference: share of pairs, mean evaluations")
+for lo_, hi_ in ((0, 1), (1, 20), (20, 60), (60, 100), (100, 1 << 30)):
+    sel = (ov >= lo_) & (ov < hi_)
+    print("  [%3d, %s) %.4f %.1f" % (lo_, "%3d" % hi_ if hi_ < 1 << 30 else "inf", sel.mean(), tot[sel].mean() if sel.any() else 0.0))
 print("corr(total evals, overlap)", np.corrcoef(tot, ov)[0, 1], " corr(total, anchors)", np.corrcoef(tot, na)[0, 1])
 def cost_sorted(key):
     o = np.argsort(key, kind="stable")
