@@ -7,8 +7,10 @@
 //   genotype   device pileup of the alignments -> substitution calls -> `<prefix>.vcf` (runGenotyping, src/main.cpp:1828-1875)
 //   consensus  the placed genome with the calls applied -> `<prefix>.consensus.fa` (runConsensus, src/main.cpp:1877-1900)
 // `--stop index|place|align|genotype|consensus` ends after that stage (default: consensus).  --meta ->
-// `<prefix>.mgsr.abundance.out`.  The bwa backend, HPC seeds and BAQ are outside this library: asking for them is an error,
-// not a silent no-op.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
+// `<prefix>.mgsr.abundance.out`.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
+// parts of panmap this build leaves out (--filter-and-assign, --impute, ...), BUILDING a homopolymer-compressed index (one
+// given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta, --batch with
+// --gpus.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -273,348 +275,459 @@ char comp(char b) {   // seeding::reverseComplement (src/seeding.cpp:271-284): A
     switch (b) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return b; }
 }
 
-}  // namespace
+// What lives as long as the process's GPU work: the tree, its index(es), the device and what is resident on it.  Filled in by
+// real_main / run_meta as they go.  close() is an explicit call and NOT a destructor: a rank that dies between two collectives
+// must leave the process (Fatal reaches main) without a barrier and with the communicator as it is -- a barrier or a transport
+// released while unwinding would block that rank for ever, and fork_ranks' first-failure reaping waits for it to exit.
+struct Run {
+    std::string panman_path;
+    pmx_panman* pm = nullptr;                    // opened by panman(), whoever asks first
+    pmx_index *idx = nullptr, *oidx = nullptr;   // (oidx, meta: --meta only)
+    pmx_ctx* ctx = nullptr;
+    int dev = 0;
+    pmx_dist* dist = nullptr;                    // --gpus N: this process is one rank
+    pmx_place* pl = nullptr;
+    pmx_meta* meta = nullptr;
+    bool have_spectrum = false, spectrum_empty = false;
+    double phred[16];
 
-// per-sample resources (freed when the sample is done, whatever way it ends)
-struct SampleGuard {
-    pmx_ctx* ctx;
-    pmx_fastx *f1 = nullptr, *f2 = nullptr;
-    pmx_readset *rs = nullptr, *rs_hpc = nullptr;
-    pmx_aligner* al = nullptr;
-    ~SampleGuard() {
-        if (al) pmx_aligner_free(ctx, al);
-        if (rs_hpc) pmx_readset_free(ctx, rs_hpc);
-        if (rs) pmx_readset_free(ctx, rs);
-        if (f1) pmx_fastx_free(f1);
-        if (f2) pmx_fastx_free(f2);
+    // the PanMAN, opened on first use; nullptr when it does not open (pmx_last_error() says why): what that means is the caller's
+    pmx_panman* panman() {
+        if (!pm && pmx_panman_open(panman_path.c_str(), &pm) != PMX_OK) pm = nullptr;
+        return pm;
+    }
+    // the substitution spectrum of the tree as phred, counted once from the open PanMAN (the reference keeps it in the
+    // index); nullptr when the tree shows no substitution
+    const double* spectrum() {
+        if (!have_spectrum) {
+            int64_t counts[16], n_branches = 0, genome_len = 0;
+            check(pmx_genotype_spectrum_counts(pm, counts, &n_branches, &genome_len), "counting the substitution spectrum");
+            const int rc = pmx_genotype_spectrum_phred(counts, n_branches, genome_len, phred);
+            if (rc < 0) die("substitution spectrum");
+            spectrum_empty = rc == 1;
+            have_spectrum = true;
+        }
+        return spectrum_empty ? nullptr : phred;
+    }
+    // the one teardown list, for the normal ends only (in the parent of the ranks only the host objects exist)
+    void close() {
+        if (meta) pmx_meta_free(ctx, meta);
+        if (dist) { (void)pmx_dist_barrier(dist); pmx_dist_free(dist); }
+        if (pl) pmx_place_free(ctx, pl);
+        if (ctx) pmx_ctx_destroy(ctx);
+        if (idx) pmx_index_close(idx);
+        if (oidx) pmx_index_close(oidx);
+        if (pm) pmx_panman_close(pm);
     }
 };
 
-// One sample through place (+ --refine) (+ align) against the resident index: c.reads1 / c.reads2 / c.output name it.
-// Returns the placed node; throws Fatal.
-// With `dist` (--gpus N) this process is one rank: it seeds and aligns ITS contiguous, pair-aligned shard of the reads; the
-// histograms are merged over the ranks before the (replicated) scoring, candidate scores of --refine are summed, and the
-// records + CIGAR arenas are gathered to rank 0, which writes every output file.
-std::string run_sample(const Config& c, int stop, pmx_panman*& pm, pmx_index* idx, pmx_ctx* ctx, pmx_place* pl, int dev, pmx_dist* dist = nullptr) {
-    const int rank = dist ? pmx_dist_rank(dist) : 0, world = dist ? pmx_dist_world(dist) : 1;
-    const bool writer = rank == 0;
-    // ------------------------------------------------------------------------------------------------ reads
-    SampleGuard g{ctx};
-    pmx_fastx *&f1 = g.f1, *&f2 = g.f2;
-    check(pmx_fastx_read(c.reads1.c_str(), &f1), "reading reads1");
-    const bool paired = !c.reads2.empty();
-    if (paired) check(pmx_fastx_read(c.reads2.c_str(), &f2), "reading reads2");
-    const int64_t n1 = pmx_fastx_num_reads(f1), n2 = paired ? pmx_fastx_num_reads(f2) : 0;
-    if (paired && n1 != n2) die("File " + c.reads2 + " does not contain the same number of reads as " + c.reads1);   // src/placement.cpp:189-192
-    const char *s1, *q1, *nm1, *s2 = nullptr, *q2 = nullptr, *nm2 = nullptr;
-    const int64_t *o1, *no1, *o2 = nullptr, *no2 = nullptr;
-    check(pmx_fastx_views(f1, &s1, &q1, &o1, &nm1, &no1), "reads1 views");
-    if (paired) check(pmx_fastx_views(f2, &s2, &q2, &o2, &nm2, &no2), "reads2 views");
-    // interleaved R1, R2 in FASTQ orientation (extractReadSequences: R2 is NOT reverse-complemented for placement)
-    const int64_t n_reads = n1 + n2;
+// One sample's reads on the host, in one list: R1, R2 interleaved as the place stage takes them (extractReadSequences: R2 in
+// FASTQ orientation, NOT reverse-complemented), or R2 appended behind R1 as --meta takes them (the score of a read does not
+// depend on its place in the list).  off[r] .. off[r + 1] is read r in `concat` and in `quals` (FASTA: zero bytes).
+struct Reads {
+    enum Layout { INTERLEAVED, APPENDED };
+    struct File { pmx_fastx* h = nullptr; ~File() { if (h) pmx_fastx_free(h); } } file1, file2;   // (the views below point into them)
     std::string concat, quals;
-    std::vector<int64_t> off((size_t)n_reads + 1, 0);
-    concat.reserve((size_t)(o1[n1] + (paired ? o2[n2] : 0)));
-    quals.reserve(concat.capacity());
-    for (int64_t i = 0; i < n1; ++i) {
-        off[(size_t)(paired ? 2 * i : i)] = (int64_t)concat.size();
-        concat.append(s1 + o1[i], (size_t)(o1[i + 1] - o1[i]));
-        quals.append(q1 + o1[i], (size_t)(o1[i + 1] - o1[i]));
-        if (paired) {
-            off[(size_t)(2 * i + 1)] = (int64_t)concat.size();
-            concat.append(s2 + o2[i], (size_t)(o2[i + 1] - o2[i]));
-            quals.append(q2 + o2[i], (size_t)(o2[i + 1] - o2[i]));
-        }
-    }
-    off[(size_t)n_reads] = (int64_t)concat.size();
-    // this rank's shard: reads [lo, hi), mates together
-    const int64_t unit = paired ? 2 : 1, n_units = n_reads / unit;
-    const int64_t lo = n_units * rank / world * unit, hi = rank == world - 1 ? n_reads : n_units * (rank + 1) / world * unit;
+    std::vector<int64_t> off;
+    const char *nm1 = nullptr, *nm2 = nullptr;   // the name views of the two files
+    const int64_t *no1 = nullptr, *no2 = nullptr;
+    bool paired = false;
+    int64_t n_reads = 0, unit = 1;               // unit: reads that stay together in a shard
 
-    // ------------------------------------------------------------------------------------------------ place
-    pmx_readset*& rs = g.rs;
-    check(pmx_readset_upload(ctx, concat.data(), off.data() + lo, hi - lo, &rs), "uploading the reads");
-    check(pmx_readset_pack(ctx, rs), "packing the reads");
-    pmx_place_params pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.seed_mask_fraction = c.seed_mask_fraction; pp.min_read_support = c.min_read_support; pp.trim_start = c.trim_start; pp.trim_end = c.trim_end;
-    pp.dedup_reads = c.dedup; pp.force_leaf = c.force_leaf; pp.min_seed_quality = c.min_seed_quality;
-    if (c.min_seed_quality > 0) check(pmx_readset_set_qualities(ctx, rs, quals.data() + off[(size_t)lo]), "attaching the qualities");
-    pmx_place_result res;
-    check(pmx_place_reset(ctx, pl), "place reset");
-    // An HPC index: the placer compresses the reads by itself (the raw reads go on to the align, genotype and consensus stages).
-    // Only the dedup over the ranks needs the compressed set in hand: its calls hash the read bytes and are matched to the
-    // seeding call by the read set, so the shard is compressed here and that set is given to both.
-    pmx_readset* seed_rs = rs;
-    pmx_index_info ii;
-    check(pmx_index_get_info(idx, &ii), "index info");
-    if (ii.hpc && dist && c.dedup && c.min_seed_quality <= 0) {
-        check(pmx_readset_hpc_compress(ctx, rs, &g.rs_hpc), "compressing the reads");
-        check(pmx_readset_pack(ctx, g.rs_hpc), "packing the compressed reads");
-        seed_rs = g.rs_hpc;
+    Reads(const std::string& reads1, const std::string& reads2, Layout layout) {
+        pmx_fastx *&f1 = file1.h, *&f2 = file2.h;
+        check(pmx_fastx_read(reads1.c_str(), &f1), "reading reads1");
+        paired = !reads2.empty();
+        if (paired) check(pmx_fastx_read(reads2.c_str(), &f2), "reading reads2");
+        const int64_t n1 = pmx_fastx_num_reads(f1), n2 = paired ? pmx_fastx_num_reads(f2) : 0;
+        if (paired && layout == INTERLEAVED && n1 != n2) die("File " + reads2 + " does not contain the same number of reads as " + reads1);   // src/placement.cpp:189-192
+        const char *s1, *q1, *s2 = nullptr, *q2 = nullptr;
+        const int64_t *o1, *o2 = nullptr;
+        check(pmx_fastx_views(f1, &s1, &q1, &o1, &nm1, &no1), "reads1 views");
+        if (paired) check(pmx_fastx_views(f2, &s2, &q2, &o2, &nm2, &no2), "reads2 views");
+        n_reads = n1 + n2;
+        unit = paired && layout == INTERLEAVED ? 2 : 1;
+        off.reserve((size_t)n_reads + 1);
+        concat.reserve((size_t)(o1[n1] + (paired ? o2[n2] : 0)));
+        quals.reserve(concat.capacity());
+        auto put = [&](const char* s, const char* q, const int64_t* o, int64_t i) {
+            off.push_back((int64_t)concat.size());
+            concat.append(s + o[i], (size_t)(o[i + 1] - o[i]));
+            quals.append(q + o[i], (size_t)(o[i + 1] - o[i]));
+        };
+        for (int64_t i = 0; i < n1; ++i) {
+            put(s1, q1, o1, i);
+            if (unit == 2) put(s2, q2, o2, i);
+        }
+        if (paired && unit == 1) for (int64_t i = 0; i < n2; ++i) put(s2, q2, o2, i);
+        off.push_back((int64_t)concat.size());
     }
-    if (dist && c.dedup && c.min_seed_quality <= 0) check(pmx_dist_dedup_reads(dist, pl, seed_rs, nullptr), "collapsing duplicate reads over the ranks");
-    check(pmx_place_add_reads(ctx, pl, seed_rs, &pp), "seeding the reads");
-    if (dist) check(pmx_dist_merge_histograms(dist, pl), "merging the ranks' seed histograms");
-    check(pmx_place_score(ctx, pl, &pp, n_reads, &res), "scoring the tree");
-    static const char* metric_names[5] = {"log_raw", "log_cosine", "containment", "weighted_containment", "log_containment"};
-    // --refine (refineTopCandidates, src/placement.cpp:516-698, called at :1910-1914): every candidate's genome is indexed on the
-    // device and the reads -- as extractReadSequences leaves them, mate 2 as sequenced -- are aligned against it
+    int mean_len() const { return (int)(concat.size() / (size_t)std::max<int64_t>(n_reads, 1)); }
+    // the shard of `rank`: reads [*lo, *hi), contiguous, mates together
+    void shard(int rank, int world, int64_t* lo, int64_t* hi) const {
+        const int64_t n_units = n_reads / unit;
+        *lo = n_units * rank / world * unit;
+        *hi = rank == world - 1 ? n_reads : n_units * (rank + 1) / world * unit;
+    }
+    std::string name(int64_t r) const {          // (interleaved layout)
+        const bool second = unit == 2 && (r & 1);
+        const int64_t i = r / unit;
+        std::string nm = second ? std::string(nm2 + no2[i], (size_t)(no2[i + 1] - no2[i])) : std::string(nm1 + no1[i], (size_t)(no1[i + 1] - no1[i]));
+        while (!nm.empty() && nm.back() == '\0') nm.pop_back();
+        return nm;
+    }
+};
+
+// One sample through place (+ --refine) (+ align, genotype, consensus) against the resident index: c.reads1 / c.reads2 /
+// c.output name it.  A call-lifetime struct, one function per step in the order run_sample calls them; it owns the sample's
+// device objects and frees them however the sample ends.  With run.dist (--gpus N) this process is one rank: it seeds and
+// aligns ITS contiguous, pair-aligned shard of the reads; the histograms are merged over the ranks before the (replicated)
+// scoring, candidate scores of --refine are summed, and the records + CIGAR arenas are gathered to rank 0, which writes
+// every output file.
+struct Sample {
+    const Config& c;
+    Run& run;
+    const Reads& reads;
+    pmx_ctx* const ctx;
+    pmx_dist* const dist;
+    const int rank, world;
+    const bool writer, paired;
+    const int64_t n_reads;
+    const int mean_len;
+    const std::string tsv_path, fa_path, bam_path, vcf_path, cons_path;   // each output's name, built here only
+    int64_t lo = 0, hi = 0;                      // this rank's shard
+    pmx_index_info info;
+    // the device objects
+    pmx_readset *rs = nullptr, *rs_hpc = nullptr;
+    pmx_aligner *al = nullptr, *refine_al = nullptr;   // refine_al: the first refine worker's, which works on `ctx`
+    pmx_pileup* pu = nullptr;
+    pmx_genotyper* gt = nullptr;
+    // what the steps leave for the later ones
+    pmx_place_result res;
     pmx_refine_result refined;
-    memset(&refined, 0, sizeof(refined));
-    if (c.refine) {
-        if (!pm && pmx_panman_open(c.panman.c_str(), &pm) != PMX_OK) {
+    std::string node_id, genome;
+    std::vector<pmx_aln_record> recs;            // the whole sample's records and their CIGAR arena (writer)
+    std::vector<uint32_t> arena;
+    std::vector<std::string> names;
+
+    Sample(const Config& c_, Run& run_, const Reads& reads_)
+        : c(c_), run(run_), reads(reads_), ctx(run_.ctx), dist(run_.dist), rank(dist ? pmx_dist_rank(dist) : 0), world(dist ? pmx_dist_world(dist) : 1),
+          writer(rank == 0), paired(reads_.paired), n_reads(reads_.n_reads), mean_len(reads_.mean_len()), tsv_path(c_.output + ".placement.tsv"),
+          fa_path(c_.output + ".ref.fa"), bam_path(c_.output + ".bam"), vcf_path(c_.output + ".vcf"), cons_path(c_.output + ".consensus.fa") {
+        reads.shard(rank, world, &lo, &hi);
+        memset(&refined, 0, sizeof(refined));
+        check(pmx_index_get_info(run.idx, &info), "index info");
+    }
+    ~Sample() {
+        if (gt) pmx_genotype_free(gt);
+        if (pu) pmx_pileup_free(ctx, pu);
+        free_refine_aligner();
+        if (al) pmx_aligner_free(ctx, al);
+        if (rs_hpc) pmx_readset_free(ctx, rs_hpc);
+        if (rs) pmx_readset_free(ctx, rs);
+    }
+    void free_refine_aligner() { if (refine_al) pmx_aligner_free(ctx, refine_al); refine_al = nullptr; }
+
+    // Reads: the shard [lo, hi) of the host reads, the resident placer.  Leaves: `rs` (the shard, packed, on the device; it
+    // goes on to --refine, align and the pileup), the placer's node scores (of the whole sample, on every rank) and `res`.
+    void place() {
+        check(pmx_readset_upload(ctx, reads.concat.data(), reads.off.data() + lo, hi - lo, &rs), "uploading the reads");
+        check(pmx_readset_pack(ctx, rs), "packing the reads");
+        pmx_place_params pp;
+        memset(&pp, 0, sizeof(pp));
+        pp.seed_mask_fraction = c.seed_mask_fraction; pp.min_read_support = c.min_read_support; pp.trim_start = c.trim_start; pp.trim_end = c.trim_end;
+        pp.dedup_reads = c.dedup; pp.force_leaf = c.force_leaf; pp.min_seed_quality = c.min_seed_quality;
+        if (c.min_seed_quality > 0) check(pmx_readset_set_qualities(ctx, rs, reads.quals.data() + reads.off[(size_t)lo]), "attaching the qualities");
+        check(pmx_place_reset(ctx, run.pl), "place reset");
+        // An HPC index: the placer compresses the reads by itself (the raw reads go on to the align, genotype and consensus stages).
+        // Only the dedup over the ranks needs the compressed set in hand: its calls hash the read bytes and are matched to the
+        // seeding call by the read set, so the shard is compressed here and that set is given to both.
+        pmx_readset* seed_rs = rs;
+        const bool dedup_over_ranks = dist && c.dedup && c.min_seed_quality <= 0;
+        if (info.hpc && dedup_over_ranks) {
+            check(pmx_readset_hpc_compress(ctx, rs, &rs_hpc), "compressing the reads");
+            check(pmx_readset_pack(ctx, rs_hpc), "packing the compressed reads");
+            seed_rs = rs_hpc;
+        }
+        if (dedup_over_ranks) check(pmx_dist_dedup_reads(dist, run.pl, seed_rs, nullptr), "collapsing duplicate reads over the ranks");
+        check(pmx_place_add_reads(ctx, run.pl, seed_rs, &pp), "seeding the reads");
+        if (dist) check(pmx_dist_merge_histograms(dist, run.pl), "merging the ranks' seed histograms");
+        check(pmx_place_score(ctx, run.pl, &pp, n_reads, &res), "scoring the tree");
+    }
+
+    // one --refine candidate: its genome indexed on `wctx` in `al` (created on the first call, re-referenced after), the shard's
+    // reads aligned against it, their score sum -> *score
+    int score_candidate(pmx_ctx* wctx, pmx_aligner*& al_w, uint32_t node, int64_t* score) {
+        // one reconstruction per candidate: the worker's buffer keeps the size of the previous genome (genomes of one
+        // tree differ by a few bases) and grows only when the returned length says so
+        thread_local std::string cand;
+        if (cand.size() < 1024) cand.resize(1024);
+        int64_t len = pmx_panman_node_genome(run.pm, (int64_t)node, &cand[0], (int64_t)cand.size());
+        if (len > (int64_t)cand.size()) {
+            cand.resize((size_t)len + (size_t)len / 64);
+            len = pmx_panman_node_genome(run.pm, (int64_t)node, &cand[0], (int64_t)cand.size());
+        }
+        if (len <= 0) { *score = 0; return PMX_OK; }   // (scoreNodeByAlignment returns 0 for an empty genome, src/placement.cpp:496-499)
+        const int rc = al_w ? pmx_aligner_set_reference(wctx, al_w, cand.data(), len, mean_len) : pmx_aligner_create(wctx, cand.data(), len, mean_len, &al_w);
+        if (rc != PMX_OK) return rc;
+        return pmx_align_score_reads(wctx, al_w, rs, paired ? 1 : 0, 0, score);
+    }
+
+    // --refine (refineTopCandidates, src/placement.cpp:516-698, called at :1910-1914): every candidate's genome is indexed on the
+    // device and the reads -- as extractReadSequences leaves them, mate 2 as sequenced -- are aligned against it.
+    // Reads: the placer's node scores, `res`, `rs`, the PanMAN.  Leaves: `refined` (ran = 0 when there was nothing to refine or
+    // the PanMAN does not open, which switches the refinement off); no aligner.
+    void refine() {
+        if (!run.panman()) {
             fprintf(stderr, "panmap: warning: Failed to load full tree for refinement, disabling refinement\n");
-        } else {
-            pmx_index_info info;
-            check(pmx_index_get_info(idx, &info), "index info");
-            std::vector<double> scores5((size_t)info.n_nodes * 5);
-            check(pmx_place_node_outputs(ctx, pl, scores5.data(), nullptr, nullptr), "node scores");
-            pmx_refine_params rp;
-            memset(&rp, 0, sizeof(rp));
-            rp.top_pct = c.refine_top_pct; rp.max_top_n = c.refine_max_top_n; rp.neighbor_radius = c.refine_neighbor_radius; rp.max_neighbor_n = c.refine_max_neighbor_n;
-            std::vector<uint32_t> cands((size_t)info.n_nodes);
-            const int64_t n_cand = pmx_refine_candidates(pmx_index_parents(idx), info.n_nodes, scores5.data(), res.best_index, &rp, cands.data(), (int64_t)cands.size());
-            if (n_cand < 0) die(std::string("refining the placement: ") + pmx_last_error());
-            cands.resize((size_t)n_cand);
-            // The candidates are independent: a few aligners, each with its own context (stream) and host thread, score them
-            // concurrently -- one sample's reads do not fill the GPU.  The first one runs alone (it also computes the read set's
-            // locality order, which the others then share read-only).
-            std::vector<int64_t> cand_score((size_t)n_cand, 0);
-            const int mean_len = (int)(concat.size() / (size_t)std::max<int64_t>(n_reads, 1));
+            return;
+        }
+        std::vector<double> scores5((size_t)info.n_nodes * 5);
+        check(pmx_place_node_outputs(ctx, run.pl, scores5.data(), nullptr, nullptr), "node scores");
+        pmx_refine_params rp;
+        memset(&rp, 0, sizeof(rp));
+        rp.top_pct = c.refine_top_pct; rp.max_top_n = c.refine_max_top_n; rp.neighbor_radius = c.refine_neighbor_radius; rp.max_neighbor_n = c.refine_max_neighbor_n;
+        std::vector<uint32_t> cands((size_t)info.n_nodes);
+        const int64_t n_cand = pmx_refine_candidates(pmx_index_parents(run.idx), info.n_nodes, scores5.data(), res.best_index, &rp, cands.data(), (int64_t)cands.size());
+        if (n_cand < 0) die(std::string("refining the placement: ") + pmx_last_error());
+        cands.resize((size_t)n_cand);
+        // The candidates are independent: a few aligners, each with its own context (stream) and host thread, score them
+        // concurrently -- one sample's reads do not fill the GPU.  The first one runs alone (it also computes the read set's
+        // locality order, which the others then share read-only).
+        std::vector<int64_t> cand_score((size_t)n_cand, 0);
+        if (n_cand > 0) {
+            check(score_candidate(ctx, refine_al, cands[0], &cand_score[0]), "refining the placement");
+            check(pmx_ctx_synchronize(ctx), "refining the placement");
+            int n_workers = 4;
+            if (const char* e = getenv("PMX_REFINE_STREAMS")) n_workers = std::max(1, atoi(e));
+            n_workers = (int)std::min<int64_t>(n_workers, std::max<int64_t>(n_cand - 1, 1));
             std::atomic<int64_t> next{1};
             std::atomic<int> failed{0};
             std::string fail_msg;
             std::mutex fail_mu;
-            auto score_range = [&](pmx_ctx* wctx, pmx_aligner*& al, int64_t i) {
-                // one reconstruction per candidate: the worker's buffer keeps the size of the previous genome (genomes of one
-                // tree differ by a few bases) and grows only when the returned length says so
-                thread_local std::string genome;
-                if (genome.size() < 1024) genome.resize(1024);
-                int64_t len = pmx_panman_node_genome(pm, (int64_t)cands[(size_t)i], &genome[0], (int64_t)genome.size());
-                if (len > (int64_t)genome.size()) {
-                    genome.resize((size_t)len + (size_t)len / 64);
-                    len = pmx_panman_node_genome(pm, (int64_t)cands[(size_t)i], &genome[0], (int64_t)genome.size());
-                }
-                if (len <= 0) { cand_score[(size_t)i] = 0; return PMX_OK; }   // (scoreNodeByAlignment returns 0 for an empty genome, src/placement.cpp:496-499)
-                int rc2 = al ? pmx_aligner_set_reference(wctx, al, genome.data(), len, mean_len) : pmx_aligner_create(wctx, genome.data(), len, mean_len, &al);
-                if (rc2 != PMX_OK) return rc2;
-                return pmx_align_score_reads(wctx, al, rs, paired ? 1 : 0, 0, &cand_score[(size_t)i]);
-            };
-            pmx_aligner* al0 = nullptr;
-            if (n_cand > 0) {
-                check(score_range(ctx, al0, 0), "refining the placement");
-                check(pmx_ctx_synchronize(ctx), "refining the placement");
-                int n_workers = 4;
-                if (const char* e = getenv("PMX_REFINE_STREAMS")) n_workers = std::max(1, atoi(e));
-                n_workers = (int)std::min<int64_t>(n_workers, std::max<int64_t>(n_cand - 1, 1));
-                std::vector<std::thread> pool;
-                for (int wk = 0; wk < n_workers; ++wk)
-                    pool.emplace_back([&, wk]() {
-                        pmx_ctx* wctx = ctx;
-                        pmx_aligner* al = wk == 0 ? al0 : nullptr;
-                        if (wk > 0 && pmx_ctx_create(dev, &wctx) != PMX_OK) { failed = 1; return; }
-                        for (;;) {
-                            const int64_t i = next.fetch_add(1);
-                            if (i >= n_cand || failed.load()) break;
-                            if (score_range(wctx, al, i) != PMX_OK) {
-                                std::lock_guard<std::mutex> g(fail_mu);
-                                if (!failed.exchange(1)) fail_msg = pmx_last_error();
-                                break;
-                            }
+            std::vector<std::thread> pool;
+            for (int wk = 0; wk < n_workers; ++wk)
+                pool.emplace_back([&, wk]() {    // worker 0 goes on with `ctx` and refine_al; the others release what they made, on every path
+                    pmx_ctx* wctx = ctx;
+                    pmx_aligner* own = nullptr;
+                    if (wk > 0 && pmx_ctx_create(run.dev, &wctx) != PMX_OK) { failed = 1; return; }
+                    pmx_aligner*& al_w = wk == 0 ? refine_al : own;
+                    for (;;) {
+                        const int64_t i = next.fetch_add(1);
+                        if (i >= n_cand || failed.load()) break;
+                        if (score_candidate(wctx, al_w, cands[(size_t)i], &cand_score[(size_t)i]) != PMX_OK) {
+                            std::lock_guard<std::mutex> lock(fail_mu);
+                            if (!failed.exchange(1)) fail_msg = pmx_last_error();
+                            break;
                         }
-                        if (wk > 0) { if (al) pmx_aligner_free(wctx, al); pmx_ctx_destroy(wctx); }
-                        else al0 = al;
-                    });
-                for (auto& t : pool) t.join();
-                if (failed.load()) die("refining the placement: " + fail_msg);
-            }
-            if (al0) pmx_aligner_free(ctx, al0);
-            if (dist) check(pmx_dist_sum_i64(dist, cand_score.data(), (int64_t)cand_score.size()), "summing the candidate scores over the ranks");
-            struct Lookup { const std::vector<uint32_t>* nodes; const std::vector<int64_t>* scores; } lk{&cands, &cand_score};
-            auto lookup = [](void* user, uint32_t node, int64_t* score) -> int {
-                const Lookup& l = *(const Lookup*)user;
-                const auto it = std::lower_bound(l.nodes->begin(), l.nodes->end(), node);
-                if (it == l.nodes->end() || *it != node) return PMX_ERR_ARG;
-                *score = (*l.scores)[(size_t)(it - l.nodes->begin())];
-                return PMX_OK;
-            };
-            check(pmx_refine_top_candidates(pmx_index_parents(idx), info.n_nodes, scores5.data(), res.best_index, &rp, lookup, &lk, &refined, nullptr, nullptr, 0),
-                  "refining the placement");
-            if (!refined.ran) fprintf(stderr, "panmap: warning: Refinement skipped: no nodes with positive scores\n");
-            else say(c, "place", "refined against " + std::to_string(refined.n_candidates) + " candidates");
+                    }
+                    if (wk > 0) { if (own) pmx_aligner_free(wctx, own); pmx_ctx_destroy(wctx); }
+                });
+            for (auto& t : pool) t.join();
+            if (failed.load()) die("refining the placement: " + fail_msg);
         }
+        free_refine_aligner();
+        if (dist) check(pmx_dist_sum_i64(dist, cand_score.data(), (int64_t)cand_score.size()), "summing the candidate scores over the ranks");
+        struct Lookup { const std::vector<uint32_t>* nodes; const std::vector<int64_t>* scores; } lk{&cands, &cand_score};
+        auto lookup = [](void* user, uint32_t node, int64_t* score) -> int {
+            const Lookup& l = *(const Lookup*)user;
+            const auto it = std::lower_bound(l.nodes->begin(), l.nodes->end(), node);
+            if (it == l.nodes->end() || *it != node) return PMX_ERR_ARG;
+            *score = (*l.scores)[(size_t)(it - l.nodes->begin())];
+            return PMX_OK;
+        };
+        check(pmx_refine_top_candidates(pmx_index_parents(run.idx), info.n_nodes, scores5.data(), res.best_index, &rp, lookup, &lk, &refined, nullptr, nullptr, 0),
+              "refining the placement");
+        if (!refined.ran) fprintf(stderr, "panmap: warning: Refinement skipped: no nodes with positive scores\n");
+        else say(c, "place", "refined against " + std::to_string(refined.n_candidates) + " candidates");
     }
-    if (writer) {
-        const std::string path = c.output + ".placement.tsv";
-        FILE* f = fopen(path.c_str(), "w");
-        if (!f) die("cannot write " + path);
-        fputs("metric\tscore\tnodes\n", f);
-        for (int m = 0; m < 5; ++m) {
-            std::string ids;
-            if (res.n_tied[m] > 0) {
-                std::vector<uint32_t> tied((size_t)res.n_tied[m]);
-                check(pmx_place_tied(pl, m, tied.data(), (int64_t)tied.size()), "tied nodes");
-                for (size_t j = 0; j < tied.size(); ++j) { if (j) ids += ","; ids += pmx_index_node_id(idx, tied[j]); }
-            } else if (res.best_index[m] != UINT32_MAX) ids = pmx_index_node_id(idx, res.best_index[m]);
-            fprintf(f, "%s\t%.6f\t%s\n", metric_names[m], res.best_score[m], ids.c_str());
-        }
-        if (refined.ran)   // src/placement.cpp:1987-2000
-            for (int m = 0; m < 5; ++m)
-                if (refined.node[m] != UINT32_MAX) fprintf(f, "refined_%s\t%.0f\t%s\n", metric_names[m], (double)refined.score[m], pmx_index_node_id(idx, refined.node[m]));
-        fclose(f);
-        say(c, "place", path);
-    }
-    if (res.best_index[4] == UINT32_MAX) die("No placement found");
-    const std::string node_id = pmx_index_node_id(idx, res.best_index[4]);
-    say(c, "place", node_id + " (log_containment " + std::to_string(res.best_score[4]) + ")");
-    if (stop == 1) return node_id;
 
-    // ------------------------------------------------------------------------------------------------ align
-    if (!pm) check(pmx_panman_open(c.panman.c_str(), &pm), "opening the PanMAN");
-    const int64_t node = pmx_panman_find_node(pm, node_id.c_str());
-    if (node < 0) die("placed node '" + node_id + "' is not in the PanMAN");
-    std::string genome((size_t)pmx_panman_node_genome(pm, node, nullptr, 0), '\0');
-    pmx_panman_node_genome(pm, node, &genome[0], (int64_t)genome.size());
-    if (genome.empty()) die("Empty sequence for node '" + node_id + "', cannot align");
-    if (writer) {
-        const std::string fa = c.output + ".ref.fa";
-        FILE* f = fopen(fa.c_str(), "w");
-        if (!f) die("Cannot write reference file: " + fa);
+    // Reads: `res`, the placer's tie lists, `refined`.  Leaves: `<prefix>.placement.tsv` (writer) and, on every rank, `node_id`,
+    // the log_containment placement; none is Fatal "No placement found", after the file is written.
+    void write_placement() {
+        static const char* metric_names[5] = {"log_raw", "log_cosine", "containment", "weighted_containment", "log_containment"};
+        if (writer) {
+            FILE* f = fopen(tsv_path.c_str(), "w");
+            if (!f) die("cannot write " + tsv_path);
+            fputs("metric\tscore\tnodes\n", f);
+            for (int m = 0; m < 5; ++m) {
+                std::string ids;
+                if (res.n_tied[m] > 0) {
+                    std::vector<uint32_t> tied((size_t)res.n_tied[m]);
+                    check(pmx_place_tied(run.pl, m, tied.data(), (int64_t)tied.size()), "tied nodes");
+                    for (size_t j = 0; j < tied.size(); ++j) { if (j) ids += ","; ids += pmx_index_node_id(run.idx, tied[j]); }
+                } else if (res.best_index[m] != UINT32_MAX) ids = pmx_index_node_id(run.idx, res.best_index[m]);
+                fprintf(f, "%s\t%.6f\t%s\n", metric_names[m], res.best_score[m], ids.c_str());
+            }
+            if (refined.ran)   // src/placement.cpp:1987-2000
+                for (int m = 0; m < 5; ++m)
+                    if (refined.node[m] != UINT32_MAX)
+                        fprintf(f, "refined_%s\t%.0f\t%s\n", metric_names[m], (double)refined.score[m], pmx_index_node_id(run.idx, refined.node[m]));
+            fclose(f);
+            say(c, "place", tsv_path);
+        }
+        if (res.best_index[4] == UINT32_MAX) die("No placement found");
+        node_id = pmx_index_node_id(run.idx, res.best_index[4]);
+        say(c, "place", node_id + " (log_containment " + std::to_string(res.best_score[4]) + ")");
+    }
+
+    // Reads: `node_id`, the PanMAN (a tree that does not open ends the sample).  Leaves: `genome`, the placed node's, and on
+    // the writer `<prefix>.ref.fa` + `.fai`.
+    void placed_genome() {
+        pmx_panman* pm = run.panman();
+        if (!pm) die(std::string("opening the PanMAN: ") + pmx_last_error());
+        const int64_t node = pmx_panman_find_node(pm, node_id.c_str());
+        if (node < 0) die("placed node '" + node_id + "' is not in the PanMAN");
+        genome.assign((size_t)pmx_panman_node_genome(pm, node, nullptr, 0), '\0');
+        pmx_panman_node_genome(pm, node, &genome[0], (int64_t)genome.size());
+        if (genome.empty()) die("Empty sequence for node '" + node_id + "', cannot align");
+        if (!writer) return;
+        FILE* f = fopen(fa_path.c_str(), "w");
+        if (!f) die("Cannot write reference file: " + fa_path);
         fprintf(f, ">%s\n%s\n", node_id.c_str(), genome.c_str());
         fclose(f);
-        FILE* g = fopen((fa + ".fai").c_str(), "w");   // faidx: name, length, offset of the first base, bases per line, bytes per line
-        if (g) { fprintf(g, "%s\t%zu\t%zu\t%zu\t%zu\n", node_id.c_str(), genome.size(), node_id.size() + 2, genome.size(), genome.size() + 1); fclose(g); }
-        say(c, "align", fa);
+        FILE* fai = fopen((fa_path + ".fai").c_str(), "w");   // faidx: name, length, offset of the first base, bases per line, bytes per line
+        if (fai) { fprintf(fai, "%s\t%zu\t%zu\t%zu\t%zu\n", node_id.c_str(), genome.size(), node_id.size() + 2, genome.size(), genome.size() + 1); fclose(fai); }
+        say(c, "align", fa_path);
     }
-    pmx_aligner*& al = g.al;
-    check(pmx_aligner_create(ctx, genome.data(), (int64_t)genome.size(), (int)(concat.size() / (size_t)std::max<int64_t>(n_reads, 1)), &al), "indexing the placed genome");
-    check(pmx_align_readset(ctx, al, rs, paired ? 1 : 0, paired ? 1 : 0), "aligning");   // mate 2 reverse-complemented on the device
-    std::vector<pmx_aln_record> recs((size_t)n_reads);
-    std::vector<uint32_t> arena;
-    if (dist) {
-        int64_t g_records = 0, g_words = 0;
-        check(pmx_dist_gather_alignments(dist, al, 0, &g_records, &g_words), "gathering the ranks' alignments");
-        if (!writer) return node_id;
-        if (g_records != n_reads) die("the gathered alignment records do not cover the sample");
-        arena.resize((size_t)std::max<int64_t>(g_words, 1));
-        check(pmx_dist_fetch_gathered(dist, recs.data(), n_reads, arena.data(), (int64_t)arena.size()), "fetching the gathered alignments");
-    } else {
-        const int64_t words = pmx_align_cigar_words(ctx, al);
-        arena.resize((size_t)std::max<int64_t>(words, 1));
-        check(pmx_align_fetch(ctx, al, recs.data(), n_reads, arena.data(), (int64_t)arena.size()), "fetching the alignments");
-    }
-    // what alignAndWriteBam holds after the aligner call: R2 reverse-complemented, its qualities reversed (src/seeding.cpp:231-269)
-    std::vector<std::string> seq_s((size_t)n_reads), qual_s((size_t)n_reads), name_s((size_t)n_reads);
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const bool second = paired && (r & 1);
-        const int64_t i = paired ? r / 2 : r;
-        const char* nm = second ? nm2 + no2[i] : nm1 + no1[i];
-        name_s[(size_t)r].assign(nm, (size_t)((second ? no2[i + 1] - no2[i] : no1[i + 1] - no1[i])));
-        while (!name_s[(size_t)r].empty() && name_s[(size_t)r].back() == '\0') name_s[(size_t)r].pop_back();
-        std::string sq(concat, (size_t)off[(size_t)r], (size_t)(off[(size_t)r + 1] - off[(size_t)r]));
-        std::string ql(quals, (size_t)off[(size_t)r], sq.size());
-        for (char& ch : ql) if (ch == '\0') ch = 'I';   // FASTA input: missing qualities
-        if (second) {
-            std::string rc(sq.rbegin(), sq.rend());
-            for (char& ch : rc) ch = comp(ch);
-            sq.swap(rc);
-            std::string rq(ql.rbegin(), ql.rend());
-            ql.swap(rq);
-        }
-        seq_s[(size_t)r].swap(sq);
-        qual_s[(size_t)r].swap(ql);
-    }
-    std::vector<const char*> seq_p((size_t)n_reads), qual_p((size_t)n_reads), name_p((size_t)n_reads);
-    std::vector<int> lens((size_t)n_reads);
-    for (int64_t r = 0; r < n_reads; ++r) { seq_p[(size_t)r] = seq_s[(size_t)r].c_str(); qual_p[(size_t)r] = qual_s[(size_t)r].c_str(); name_p[(size_t)r] = name_s[(size_t)r].c_str(); lens[(size_t)r] = (int)seq_s[(size_t)r].size(); }
-    const int64_t n_items = paired ? n_reads / 2 : n_reads;
-    std::vector<align_pair_result_t> results((size_t)std::max<int64_t>(n_items, 1));
-    int64_t n_mapped = 0, n_withheld = 0;
-    auto fill = [&](const pmx_aln_record& r, read_align_t* o) {
-        memset(o, 0, sizeof(*o));
-        if (r.mapped && (r.flags & PMX_ALN_HAS_ALN)) {
-            o->pos = r.rs + 1; o->rs = r.rs; o->re = r.re; o->qs = r.qs; o->qe = r.qe;
-            o->mapq = r.mapq; o->rev = r.rev; o->proper_frag = r.proper_frag; o->n_cigar = r.n_cigar;
-            o->cigar = arena.data() + r.cigar_off;   // (points into the arena: nothing to free)
-        } else o->pos = INT_MAX;
-    };
-    for (int64_t k = 0; k < n_items; ++k) {
-        align_pair_result_t& out = results[(size_t)k];
-        memset(&out, 0, sizeof(out));
-        const pmx_aln_record& a = recs[(size_t)(paired ? 2 * k : k)];
-        const bool invalid = paired ? ((a.flags | recs[(size_t)(2 * k + 1)].flags) & 3) != 0 : (a.flags & 3) != 0;
-        out.r1.pos = out.r2.pos = INT_MAX;
-        if (invalid) { ++n_withheld; continue; }
-        if (!a.mapped) continue;
-        out.mapped = 1;
-        ++n_mapped;
-        fill(a, &out.r1);
-        if (paired) fill(recs[(size_t)(2 * k + 1)], &out.r2);
-    }
-    const std::string bam = c.output + ".bam";
-    check(pmx_write_bam(bam.c_str(), node_id.c_str(), (int64_t)genome.size(), (int)n_reads, seq_p.data(), qual_p.data(), name_p.data(), lens.data(),
-                        results.data(), paired), "writing the BAM");
-    say(c, "align", bam + " (" + std::to_string(n_mapped) + " of " + std::to_string(n_items) + (paired ? " pairs" : " reads") + " mapped" +
-                    (n_withheld ? ", " + std::to_string(n_withheld) + " invalid records withheld" : "") + ")");
-    if (stop < 3) return node_id;
 
-    // ------------------------------------------------------------------------------------------------ genotype
+    // Reads: `genome`, `rs`.  Leaves: `al` with the shard's alignments on the device (the one-rank pileup runs over it) and,
+    // on the writer, the whole sample's `recs` + `arena` on the host (--gpus N: gathered; the other ranks are done here).
+    void align() {
+        check(pmx_aligner_create(ctx, genome.data(), (int64_t)genome.size(), mean_len, &al), "indexing the placed genome");
+        check(pmx_align_readset(ctx, al, rs, paired ? 1 : 0, paired ? 1 : 0), "aligning");   // mate 2 reverse-complemented on the device
+        if (dist) {
+            int64_t g_records = 0, g_words = 0;
+            check(pmx_dist_gather_alignments(dist, al, 0, &g_records, &g_words), "gathering the ranks' alignments");
+            if (!writer) return;
+            if (g_records != n_reads) die("the gathered alignment records do not cover the sample");
+            recs.resize((size_t)n_reads);
+            arena.resize((size_t)std::max<int64_t>(g_words, 1));
+            check(pmx_dist_fetch_gathered(dist, recs.data(), n_reads, arena.data(), (int64_t)arena.size()), "fetching the gathered alignments");
+        } else {
+            recs.resize((size_t)n_reads);
+            arena.resize((size_t)std::max<int64_t>(pmx_align_cigar_words(ctx, al), 1));
+            check(pmx_align_fetch(ctx, al, recs.data(), n_reads, arena.data(), (int64_t)arena.size()), "fetching the alignments");
+        }
+    }
+
+    // Reads: the host reads, `recs`, `arena`.  Leaves: `<prefix>.bam` (+ .bai) and `names`, the reads' names in read order.
+    void write_bam() {
+        // what alignAndWriteBam holds after the aligner call: R2 reverse-complemented, its qualities reversed (src/seeding.cpp:231-269)
+        std::vector<std::string> seq_s((size_t)n_reads), qual_s((size_t)n_reads);
+        names.resize((size_t)n_reads);
+        for (int64_t r = 0; r < n_reads; ++r) {
+            names[(size_t)r] = reads.name(r);
+            std::string sq(reads.concat, (size_t)reads.off[(size_t)r], (size_t)(reads.off[(size_t)r + 1] - reads.off[(size_t)r]));
+            std::string ql(reads.quals, (size_t)reads.off[(size_t)r], sq.size());
+            for (char& ch : ql) if (ch == '\0') ch = 'I';   // FASTA input: missing qualities
+            if (paired && (r & 1)) {
+                std::string rc(sq.rbegin(), sq.rend());
+                for (char& ch : rc) ch = comp(ch);
+                sq.swap(rc);
+                std::string rq(ql.rbegin(), ql.rend());
+                ql.swap(rq);
+            }
+            seq_s[(size_t)r].swap(sq);
+            qual_s[(size_t)r].swap(ql);
+        }
+        std::vector<const char*> seq_p((size_t)n_reads), qual_p((size_t)n_reads), name_p((size_t)n_reads);
+        std::vector<int> lens((size_t)n_reads);
+        for (int64_t r = 0; r < n_reads; ++r) { seq_p[(size_t)r] = seq_s[(size_t)r].c_str(); qual_p[(size_t)r] = qual_s[(size_t)r].c_str(); name_p[(size_t)r] = names[(size_t)r].c_str(); lens[(size_t)r] = (int)seq_s[(size_t)r].size(); }
+        const int64_t n_items = paired ? n_reads / 2 : n_reads;
+        std::vector<align_pair_result_t> results((size_t)std::max<int64_t>(n_items, 1));
+        int64_t n_mapped = 0, n_withheld = 0;
+        auto fill = [&](const pmx_aln_record& r, read_align_t* o) {
+            memset(o, 0, sizeof(*o));
+            if (r.mapped && (r.flags & PMX_ALN_HAS_ALN)) {
+                o->pos = r.rs + 1; o->rs = r.rs; o->re = r.re; o->qs = r.qs; o->qe = r.qe;
+                o->mapq = r.mapq; o->rev = r.rev; o->proper_frag = r.proper_frag; o->n_cigar = r.n_cigar;
+                o->cigar = arena.data() + r.cigar_off;   // (points into the arena: nothing to free)
+            } else o->pos = INT_MAX;
+        };
+        for (int64_t k = 0; k < n_items; ++k) {
+            align_pair_result_t& out = results[(size_t)k];
+            memset(&out, 0, sizeof(out));
+            const pmx_aln_record& a = recs[(size_t)(paired ? 2 * k : k)];
+            const bool invalid = paired ? ((a.flags | recs[(size_t)(2 * k + 1)].flags) & 3) != 0 : (a.flags & 3) != 0;
+            out.r1.pos = out.r2.pos = INT_MAX;
+            if (invalid) { ++n_withheld; continue; }
+            if (!a.mapped) continue;
+            out.mapped = 1;
+            ++n_mapped;
+            fill(a, &out.r1);
+            if (paired) fill(recs[(size_t)(2 * k + 1)], &out.r2);
+        }
+        check(pmx_write_bam(bam_path.c_str(), node_id.c_str(), (int64_t)genome.size(), (int)n_reads, seq_p.data(), qual_p.data(), name_p.data(), lens.data(),
+                            results.data(), paired), "writing the BAM");
+        say(c, "align", bam_path + " (" + std::to_string(n_mapped) + " of " + std::to_string(n_items) + (paired ? " pairs" : " reads") + " mapped" +
+                        (n_withheld ? ", " + std::to_string(n_withheld) + " invalid records withheld" : "") + ")");
+    }
+
     // One rank: the pileup runs over what the align stage left on the device.  --gpus N: rank 0 holds the gathered records
     // and the whole sample's reads on the host and uploads them.  Same tables either way.
-    std::string names_concat;
-    std::vector<int64_t> name_off((size_t)n_reads + 1, 0);
-    for (int64_t r = 0; r < n_reads; ++r) { names_concat += name_s[(size_t)r]; name_off[(size_t)r + 1] = (int64_t)names_concat.size(); }
-    names_concat.push_back('\0');
-    struct PileupGuard { pmx_ctx* ctx; pmx_pileup* pu = nullptr; pmx_genotyper* gt = nullptr; ~PileupGuard() { if (gt) pmx_genotype_free(gt); if (pu) pmx_pileup_free(ctx, pu); } } pg{ctx};
-    check(pmx_pileup_create(ctx, &pg.pu), "creating the pileup");
-    if (dist) {
-        check(pmx_pileup_run_records(ctx, pg.pu, recs.data(), n_reads, arena.data(), (int64_t)arena.size(), concat.data(), quals.data(), off.data(),
-                                     (int64_t)genome.size(), paired ? 1 : 0, paired ? 1 : 0, names_concat.data(), name_off.data(), nullptr), "pileup");
-    } else {
-        check(pmx_readset_set_qualities(ctx, rs, quals.data()), "attaching the qualities");
-        check(pmx_pileup_run(ctx, pg.pu, al, rs, (int64_t)genome.size(), paired ? 1 : 0, paired ? 1 : 0, names_concat.data(), name_off.data(), nullptr), "pileup");
-    }
-    std::vector<uint32_t> hist(genome.size() * PMX_PILEUP_HIST), aux(genome.size() * PMX_PILEUP_AUX);
-    check(pmx_pileup_fetch(ctx, pg.pu, hist.data(), aux.data()), "fetching the pileup tables");
-    // the substitution spectrum of the tree (the reference keeps it in the index; here it is counted from the PanMAN)
-    static bool have_spectrum = false, spectrum_empty = false;
-    static double phred[16];
-    if (!have_spectrum) {
-        int64_t counts[16], n_branches = 0, genome_len = 0;
-        check(pmx_genotype_spectrum_counts(pm, counts, &n_branches, &genome_len), "counting the substitution spectrum");
-        const int rc = pmx_genotype_spectrum_phred(counts, n_branches, genome_len, phred);
-        if (rc < 0) die("substitution spectrum");
-        spectrum_empty = rc == 1;
-        have_spectrum = true;
-    }
-    const int64_t n_calls = pmx_genotype_call(hist.data(), aux.data(), genome.data(), (int64_t)genome.size(), node_id.c_str(), spectrum_empty ? nullptr : phred,
-                                              c.min_depth, c.min_qual, &pg.gt);
-    if (n_calls < 0) die(std::string("calling variants: ") + pmx_last_error());
-    if (c.annotate_vcf && n_calls > 0) {
-        // the written records' sites go through the bias pass of the pileup that is still on the device
-        std::vector<int32_t> sites((size_t)n_calls);
-        std::string letters((size_t)n_calls, 'N');
-        for (int64_t i = 0; i < n_calls; ++i) {
-            sites[(size_t)i] = (int32_t)pmx_genotype_record_pos(pg.gt, i);
-            letters[(size_t)i] = genome[(size_t)sites[(size_t)i]];
+    // Reads: `al` + `rs`, or `recs` + `arena` + the host reads; `names`, `genome`, the tree's spectrum.  Leaves: `pu` (the
+    // pileup, on the device), `gt` (the calls) and `<prefix>.vcf`.
+    void genotype() {
+        std::string names_concat;
+        std::vector<int64_t> name_off((size_t)n_reads + 1, 0);
+        for (int64_t r = 0; r < n_reads; ++r) { names_concat += names[(size_t)r]; name_off[(size_t)r + 1] = (int64_t)names_concat.size(); }
+        names_concat.push_back('\0');
+        check(pmx_pileup_create(ctx, &pu), "creating the pileup");
+        if (dist) {
+            check(pmx_pileup_run_records(ctx, pu, recs.data(), n_reads, arena.data(), (int64_t)arena.size(), reads.concat.data(), reads.quals.data(), reads.off.data(),
+                                         (int64_t)genome.size(), paired ? 1 : 0, paired ? 1 : 0, names_concat.data(), name_off.data(), nullptr), "pileup");
+        } else {
+            check(pmx_readset_set_qualities(ctx, rs, reads.quals.data()), "attaching the qualities");
+            check(pmx_pileup_run(ctx, pu, al, rs, (int64_t)genome.size(), paired ? 1 : 0, paired ? 1 : 0, names_concat.data(), name_off.data(), nullptr), "pileup");
         }
-        std::vector<uint32_t> bias((size_t)n_calls * PMX_PILEUP_BIAS);
-        check(pmx_pileup_bias(ctx, pg.pu, sites.data(), letters.data(), n_calls, bias.data()), "pileup bias pass");
-        check(pmx_genotype_annotate(pg.gt, sites.data(), bias.data(), n_calls), "annotating the records");
+        std::vector<uint32_t> hist(genome.size() * PMX_PILEUP_HIST), aux(genome.size() * PMX_PILEUP_AUX);
+        check(pmx_pileup_fetch(ctx, pu, hist.data(), aux.data()), "fetching the pileup tables");
+        const int64_t n_calls = pmx_genotype_call(hist.data(), aux.data(), genome.data(), (int64_t)genome.size(), node_id.c_str(), run.spectrum(),
+                                                  c.min_depth, c.min_qual, &gt);
+        if (n_calls < 0) die(std::string("calling variants: ") + pmx_last_error());
+        if (c.annotate_vcf && n_calls > 0) {
+            // the written records' sites go through the bias pass of the pileup that is still on the device
+            std::vector<int32_t> sites((size_t)n_calls);
+            std::string letters((size_t)n_calls, 'N');
+            for (int64_t i = 0; i < n_calls; ++i) {
+                sites[(size_t)i] = (int32_t)pmx_genotype_record_pos(gt, i);
+                letters[(size_t)i] = genome[(size_t)sites[(size_t)i]];
+            }
+            std::vector<uint32_t> bias((size_t)n_calls * PMX_PILEUP_BIAS);
+            check(pmx_pileup_bias(ctx, pu, sites.data(), letters.data(), n_calls, bias.data()), "pileup bias pass");
+            check(pmx_genotype_annotate(gt, sites.data(), bias.data(), n_calls), "annotating the records");
+        }
+        check(pmx_genotype_write_vcf(gt, vcf_path.c_str(), node_id.c_str(), (int64_t)genome.size(), bam_path.c_str()), "writing the VCF");
+        say(c, "call", vcf_path + " (" + std::to_string(n_calls) + " variants)");
     }
-    const std::string vcf = c.output + ".vcf";
-    check(pmx_genotype_write_vcf(pg.gt, vcf.c_str(), node_id.c_str(), (int64_t)genome.size(), bam.c_str()), "writing the VCF");
-    say(c, "call", vcf + " (" + std::to_string(n_calls) + " variants)");
-    if (stop < 4) return node_id;
 
-    // ------------------------------------------------------------------------------------------------ consensus
-    std::string sample = c.output.substr(c.output.find_last_of("/\\") + 1);   // src/main.cpp:1889-1892
-    if (sample.empty()) sample = "sample";
-    const std::string cons = c.output + ".consensus.fa";
-    check(pmx_genotype_write_consensus(vcf.c_str(), (c.output + ".ref.fa").c_str(), cons.c_str(), (sample + "_consensus ref=" + node_id).c_str()), "writing the consensus");
-    say(c, "consensus", cons);
-    return node_id;
+    // Reads: `<prefix>.vcf` and `<prefix>.ref.fa` as written.  Leaves: `<prefix>.consensus.fa`.
+    void consensus() {
+        std::string sample = c.output.substr(c.output.find_last_of("/\\") + 1);   // src/main.cpp:1889-1892
+        if (sample.empty()) sample = "sample";
+        check(pmx_genotype_write_consensus(vcf_path.c_str(), fa_path.c_str(), cons_path.c_str(), (sample + "_consensus ref=" + node_id).c_str()), "writing the consensus");
+        say(c, "consensus", cons_path);
+    }
+};
+
+// Returns the placed node; throws Fatal.  `stop`: 1 place, 2 align, 3 genotype, 4 consensus.
+std::string run_sample(const Config& c, int stop, Run& run) {
+    const Reads reads(c.reads1, c.reads2, Reads::INTERLEAVED);
+    Sample s(c, run, reads);
+    s.place();
+    if (c.refine) s.refine();
+    s.write_placement();
+    if (stop == 1) return s.node_id;
+    s.placed_genome();
+    s.align();
+    if (!s.writer) return s.node_id;             // --gpus N: rank 0 has everything now and writes the rest
+    s.write_bam();
+    if (stop < 3) return s.node_id;
+    s.genotype();
+    if (stop < 4) return s.node_id;
+    s.consensus();
+    return s.node_id;
 }
 
 // ------------------------------------------------------------------------------------------------ --gpus N
@@ -707,56 +820,38 @@ int run_meta(Config c) {
     if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
     if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
     if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
-    pmx_panman* pm = nullptr;
-    check(pmx_panman_open(c.panman.c_str(), &pm), "opening the PanMAN");
-    pmx_index *idx = nullptr, *oidx = nullptr;
+    Run run;
+    run.panman_path = c.panman;
+    pmx_panman* pm = run.panman();
+    if (!pm) die(std::string("opening the PanMAN: ") + pmx_last_error());
     {   // the two builds are independent: side by side
         int rc1 = PMX_OK, rc2 = PMX_OK;
         std::string e2;
-        std::thread th([&]() { rc2 = pmx_index_build_ex(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, 0, PMX_INDEX_ORIENTED, -1, &oidx); if (rc2 != PMX_OK) e2 = pmx_last_error(); });
-        rc1 = pmx_index_build_ex(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, 0, 0, -1, &idx);
+        std::thread th([&]() { rc2 = pmx_index_build_ex(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, 0, PMX_INDEX_ORIENTED, -1, &run.oidx); if (rc2 != PMX_OK) e2 = pmx_last_error(); });
+        rc1 = pmx_index_build_ex(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, 0, 0, -1, &run.idx);
         th.join();
         check(rc1, "building the index");
         if (rc2 != PMX_OK) die("building the oriented index: " + e2);
     }
     say(c, "index", "seed index + oriented seed index (in memory)");
-    pmx_fastx *f1 = nullptr, *f2 = nullptr;
-    check(pmx_fastx_read(c.reads1.c_str(), &f1), "reading reads1");
-    if (!c.reads2.empty()) check(pmx_fastx_read(c.reads2.c_str(), &f2), "reading reads2");
-    const char *s1, *q1, *nm1;
-    const int64_t *o1, *no1;
-    check(pmx_fastx_views(f1, &s1, &q1, &o1, &nm1, &no1), "reads1 views");
-    std::string concat(s1, (size_t)o1[pmx_fastx_num_reads(f1)]);
-    std::vector<int64_t> off(o1, o1 + pmx_fastx_num_reads(f1) + 1);
-    if (f2) {   // mates as sequenced, one after the other (the score of a read does not depend on its place in the list)
-        const char *s2, *q2, *nm2;
-        const int64_t *o2, *no2;
-        check(pmx_fastx_views(f2, &s2, &q2, &o2, &nm2, &no2), "reads2 views");
-        const int64_t n2 = pmx_fastx_num_reads(f2), base = (int64_t)concat.size();
-        concat.append(s2, (size_t)o2[n2]);
-        for (int64_t i = 1; i <= n2; ++i) off.push_back(base + o2[i]);
-    }
+    const Reads reads(c.reads1, c.reads2, Reads::APPENDED);   // mates as sequenced, one after the other
     // --gpus N: one rank per GPU, each with a contiguous shard of the reads above (R1 then R2); every rank ends with the whole
     // sample's result (pmx_meta_attach_dist), rank 0 writes it
     Ranks rk;
     int code = 0;
-    if (!fork_ranks(c.gpus, rk, &code)) {
-        pmx_fastx_free(f1);
-        if (f2) pmx_fastx_free(f2);
-        pmx_index_close(idx); pmx_index_close(oidx);
-        pmx_panman_close(pm);
-        return code;
-    }
+    if (!fork_ranks(c.gpus, rk, &code)) { run.close(); return code; }
     if (rk.rank > 0) c.quiet = true;
-    const int64_t n_all = (int64_t)off.size() - 1, lo = n_all * rk.rank / rk.world, hi = n_all * (rk.rank + 1) / rk.world;
-    pmx_ctx* ctx = nullptr;
-    check(pmx_ctx_create(rank_device(rk), &ctx), "opening the GPU");
-    pmx_dist* dist = join_ranks(ctx, rk);
-    pmx_meta* m = nullptr;
-    check(pmx_meta_create(ctx, idx, oidx, &m), "uploading the indexes");
-    if (dist) check(pmx_meta_attach_dist(m, dist), "attaching the ranks");
+    int64_t lo = 0, hi = 0;
+    reads.shard(rk.rank, rk.world, &lo, &hi);
+    run.dev = rank_device(rk);
+    check(pmx_ctx_create(run.dev, &run.ctx), "opening the GPU");
+    run.dist = join_ranks(run.ctx, rk);
+    pmx_ctx* const ctx = run.ctx;
+    pmx_meta*& m = run.meta;
+    check(pmx_meta_create(ctx, run.idx, run.oidx, &m), "uploading the indexes");
+    if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
     check(pmx_meta_set_dust(m, c.dust), "--dust");
-    check(pmx_meta_set_reads(ctx, m, concat.data(), off.data() + lo, hi - lo), "seeding the reads");
+    check(pmx_meta_set_reads(ctx, m, reads.concat.data(), reads.off.data() + lo, hi - lo), "seeding the reads");
     check(pmx_meta_score(ctx, m, c.top_oc, nullptr, 0), "scoring the reads against the candidate nodes");
     say(c, "meta", std::to_string(pmx_meta_num_reads(m)) + " distinct reads x " + std::to_string(pmx_meta_num_candidates(m)) + " candidate nodes");
     pmx_meta_params mp;
@@ -764,17 +859,7 @@ int run_meta(Config c) {
     mp.error_rate = 0.005; mp.em_convergence = c.em_convergence; mp.em_delta_threshold = c.em_delta; mp.prop_threshold = 0.005; mp.discard = c.discard;
     mp.em_max_iterations = c.em_max_iterations; mp.em_max_rounds = c.em_max_rounds;
     check(pmx_meta_em(ctx, m, &mp), "estimating the abundances");
-    if (rk.rank > 0) {
-        pmx_meta_free(ctx, m);
-        (void)pmx_dist_barrier(dist);
-        pmx_dist_free(dist);
-        pmx_ctx_destroy(ctx);
-        pmx_fastx_free(f1);
-        if (f2) pmx_fastx_free(f2);
-        pmx_index_close(idx); pmx_index_close(oidx);
-        pmx_panman_close(pm);
-        return 0;
-    }
+    if (rk.rank > 0) { run.close(); return 0; }
     const std::string path = c.output + ".mgsr.abundance.out";
     FILE* f = fopen(path.c_str(), "w");
     if (!f) die("cannot write " + path);
@@ -787,19 +872,13 @@ int run_meta(Config c) {
         check(pmx_meta_haplotype(m, i, &node, &prop, &n_mem, nullptr, 0), "haplotype");
         std::vector<uint32_t> mem((size_t)std::max<int64_t>(n_mem, 1));
         check(pmx_meta_haplotype(m, i, nullptr, nullptr, nullptr, mem.data(), (int64_t)mem.size()), "haplotype members");
-        std::string ids = pmx_index_node_id(idx, node);
-        for (int64_t k = 0; k < n_mem; ++k) { ids += ","; ids += pmx_index_node_id(idx, mem[(size_t)k]); }
+        std::string ids = pmx_index_node_id(run.idx, node);
+        for (int64_t k = 0; k < n_mem; ++k) { ids += ","; ids += pmx_index_node_id(run.idx, mem[(size_t)k]); }
         fprintf(f, "%s\t%.5f\n", ids.c_str(), prop);
     }
     fclose(f);
     say(c, "meta", path + " (" + std::to_string(n_h) + " haplotypes)");
-    pmx_meta_free(ctx, m);
-    if (dist) { (void)pmx_dist_barrier(dist); pmx_dist_free(dist); }
-    pmx_ctx_destroy(ctx);
-    pmx_fastx_free(f1);
-    if (f2) pmx_fastx_free(f2);
-    pmx_index_close(idx); pmx_index_close(oidx);
-    pmx_panman_close(pm);
+    run.close();
     return 0;
 }
 
@@ -825,21 +904,21 @@ int real_main(int argc, char** argv) {
     }
 
     // ------------------------------------------------------------------------------------------------ index
-    pmx_panman* pm = nullptr;
-    pmx_index* idx = nullptr;
+    Run run;
+    run.panman_path = c.panman;
     bool idx_hpc = false;
     if (exists(c.index) && !c.force_reindex && cached_index_usable(c, &idx_hpc)) {
         if (c.hpc && !idx_hpc) die(std::string(kHpcNeedsIndex) + "; " + c.index + " is not one");
-        check(pmx_index_load(c.index.c_str(), &idx), "loading the index");
+        check(pmx_index_load(c.index.c_str(), &run.idx), "loading the index");
         say(c, "index", c.index + " (cached)" + (idx_hpc ? ", homopolymer-compressed" : ""));
     } else {
         if (c.hpc) die(kHpcNeedsIndex);
-        check(pmx_panman_open(c.panman.c_str(), &pm), "opening the PanMAN");
-        check(pmx_index_build(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, c.flank_mask, &idx), "building the index");
-        check(pmx_index_save(idx, c.index.c_str(), c.zstd_level, c.index_uncompressed ? 1 : 0), "writing the index");
+        if (!run.panman()) die(std::string("opening the PanMAN: ") + pmx_last_error());
+        check(pmx_index_build(run.pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, c.flank_mask, &run.idx), "building the index");
+        check(pmx_index_save(run.idx, c.index.c_str(), c.zstd_level, c.index_uncompressed ? 1 : 0), "writing the index");
         say(c, "index", c.index + " (built)");
     }
-    if (stop == 0 || (c.reads1.empty() && c.batch.empty())) return 0;
+    if (stop == 0 || (c.reads1.empty() && c.batch.empty())) { run.close(); return 0; }
 
     // ------------------------------------------------------------------------------------------------ --gpus N
     // forked HERE: the index (and the PanMAN, when it was opened) is in memory and nothing has touched a GPU yet
@@ -847,23 +926,17 @@ int real_main(int argc, char** argv) {
     if (c.gpus > 1) {
         if (!c.batch.empty()) die("--gpus shards ONE sample over the GPUs; run --batch per GPU instead");
         int code = 0;
-        if (!fork_ranks(c.gpus, rk, &code)) {
-            pmx_index_close(idx);
-            if (pm) pmx_panman_close(pm);
-            return code;
-        }
+        if (!fork_ranks(c.gpus, rk, &code)) { run.close(); return code; }
         if (rk.rank > 0) c.quiet = true;
     }
 
     // ------------------------------------------------------------------------------------------------ samples
-    pmx_ctx* ctx = nullptr;
-    const int dev = rank_device(rk);
-    check(pmx_ctx_create(dev, &ctx), "opening the GPU");
-    pmx_dist* dist = join_ranks(ctx, rk);
-    pmx_place* pl = nullptr;
-    check(pmx_place_create(ctx, idx, &pl), "uploading the index");
+    run.dev = rank_device(rk);
+    check(pmx_ctx_create(run.dev, &run.ctx), "opening the GPU");
+    run.dist = join_ranks(run.ctx, rk);
+    check(pmx_place_create(run.ctx, run.idx, &run.pl), "uploading the index");
     int rc = 0;
-    if (c.batch.empty()) run_sample(c, stop, pm, idx, ctx, pl, dev, dist);
+    if (c.batch.empty()) run_sample(c, stop, run);
     else {
         // runBatchPlacement (src/main.cpp:1464-1666): the samples of the batch file one after the other against the index
         // that stays on the device; one line per sample on stderr, a failed sample does not stop the batch
@@ -878,7 +951,7 @@ int real_main(int argc, char** argv) {
             if (slash != std::string::npos && slash > 0) mkdirs(sc.output.substr(0, slash));
             const auto t0 = std::chrono::steady_clock::now();
             std::string node, err;
-            try { node = run_sample(sc, stop, pm, idx, ctx, pl, dev); }
+            try { node = run_sample(sc, stop, run); }
             catch (const Fatal& f) { err = f.msg; }
             const long long ms = (long long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
             if (!err.empty()) {
@@ -892,13 +965,11 @@ int real_main(int argc, char** argv) {
         fprintf(stderr, "Batch complete: %d placed, %d failed\n", ok, failed);
         rc = failed ? 1 : 0;
     }
-    if (dist) { (void)pmx_dist_barrier(dist); pmx_dist_free(dist); }
-    pmx_place_free(ctx, pl);
-    pmx_ctx_destroy(ctx);
-    pmx_index_close(idx);
-    if (pm) pmx_panman_close(pm);
+    run.close();
     return rc;
 }
+
+}  // namespace
 
 int main(int argc, char** argv) {
     try {

@@ -3,19 +3,13 @@ used as it is, with or without --hpc, and never rebuilt over), --hpc means "the 
 line does not build one.  CPU part: the argument and cache rules.  GPU part: `--stop place` against an HPC index."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import hpc_checks as hc
-from conftest import GOLDEN, ROOT
-
-CLI = os.path.join(ROOT, "panmap_amd", "bin", "panmap")
-
-
-def run(args, cwd):
-    return subprocess.run([CLI] + args, cwd=cwd, capture_output=True, text=True, timeout=120)
+from cli_checks import run
+from conftest import GOLDEN
 
 
 @pytest.fixture(scope="module")
@@ -123,7 +117,7 @@ def test_dedup_over_two_ranks_compares_the_compressed_reads(pmx, ctx, hpc_dir, t
     env = dict(os.environ, PMX_DIST_SAME_DEVICE="1", PMX_DIST_HOST_DIR=str(meet))
     args = ["rsv.panman", "twins.fq", "-i", "hpc.idx", "--stop", "place", "--dedup"]
     r1 = run(args + ["-o", "d1"], hpc_dir)
-    r2 = subprocess.run([CLI] + args + ["-o", "d2", "--gpus", "2"], cwd=hpc_dir, capture_output=True, text=True, timeout=300, env=env)
+    r2 = run(args + ["-o", "d2", "--gpus", "2"], hpc_dir, env=env, timeout=300)
     assert r1.returncode == 0 and r2.returncode == 0, (r1.stderr[-1000:], r2.stderr[-1500:])
     assert (hpc_dir / "d1.placement.tsv").read_text() == want["dedup"]
     assert (hpc_dir / "d2.placement.tsv").read_text() == want["dedup"]

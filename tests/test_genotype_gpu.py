@@ -3,23 +3,15 @@ consensus FASTA, and the device pileup tables against the numpy restatement of t
 every position, on real pairs, synthetic pairs and single-end long reads, with and without the depth cap."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from cli_checks import DEMO, run
+from conftest import GOLDEN
 
 import geno_checks as gc
 from test_genotype_host import GOLDEN_LINE, qual_interval
-
-CLI = os.path.join(ROOT, "panmap_amd", "bin", "panmap")
-DEMO = ["sars_20000_twilight_dipper.panman", "isolate_R1.fastq.gz", "isolate_R2.fastq.gz"]
-
-
-def run(args, cwd, env=None, timeout=240):
-    """one invocation of the command line, with a time limit"""
-    return subprocess.run([CLI] + args, cwd=cwd, capture_output=True, text=True, timeout=timeout, env=env)
 
 
 def _demo_files(tmp_path):
@@ -34,7 +26,7 @@ def _genome():
 @pytest.mark.gpu
 def test_demo_default_stop_writes_the_golden_call_and_consensus(pmx, sars, tmp_path):
     _demo_files(tmp_path)
-    r = run(DEMO + ["-o", "isolate"], tmp_path)
+    r = run(DEMO + ["-o", "isolate"], tmp_path, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "not part of this build" not in r.stderr
     assert open(tmp_path / "isolate.consensus.fa", "rb").read() == open(os.path.join(GOLDEN, "isolate.consensus.fa"), "rb").read()
@@ -54,15 +46,15 @@ def test_demo_default_stop_writes_the_golden_call_and_consensus(pmx, sars, tmp_p
     lo, hi, _, _ = qual_interval(pmx, sars)
     assert lo <= float(f[5]) <= hi and len(f[5].split(".")[1]) == 4
     # the earlier stages are untouched by the later ones
-    r2 = run(DEMO + ["-o", "upto", "--stop", "align"], tmp_path)
+    r2 = run(DEMO + ["-o", "upto", "--stop", "align"], tmp_path, timeout=240)
     assert r2.returncode == 0 and not os.path.exists(tmp_path / "upto.vcf") and not os.path.exists(tmp_path / "upto.consensus.fa")
     for ext in (".placement.tsv", ".ref.fa", ".bam"):
         assert open(tmp_path / ("isolate" + ext), "rb").read() == open(tmp_path / ("upto" + ext), "rb").read(), ext
     # --stop genotype ends before the consensus; the gate's options reach the filter; --baq is refused
-    r3 = run(DEMO + ["-o", "geno", "--stop", "genotype", "--min-qual", "200"], tmp_path)
+    r3 = run(DEMO + ["-o", "geno", "--stop", "genotype", "--min-qual", "200"], tmp_path, timeout=240)
     assert r3.returncode == 0 and not os.path.exists(tmp_path / "geno.consensus.fa")
     assert [l for l in open(tmp_path / "geno.vcf").read().splitlines() if not l.startswith("#")] == []
-    r4 = run(DEMO + ["-o", "baq", "--baq"], tmp_path)
+    r4 = run(DEMO + ["-o", "baq", "--baq"], tmp_path, timeout=240)
     assert r4.returncode == 1 and "--baq" in r4.stderr
 
 
@@ -193,7 +185,7 @@ def test_tables_repeat_and_do_not_depend_on_the_read_order(pmx, ctx):
 @pytest.mark.gpu
 def test_two_ranks_and_batch_write_the_same_files(pmx, tmp_path):
     _demo_files(tmp_path)
-    r1 = run(DEMO + ["-o", "one"], tmp_path)
+    r1 = run(DEMO + ["-o", "one"], tmp_path, timeout=240)
     assert r1.returncode == 0, r1.stderr[-2000:]
     meet = tmp_path / "meet"
     meet.mkdir()

@@ -3,12 +3,11 @@ of `panmap --meta --gpus N` that fails ends the run (the reaping the place path 
 import ctypes as C
 import os
 import shutil
-import subprocess
 import time
 
-from conftest import GOLDEN, ROOT
+from cli_checks import run
+from conftest import GOLDEN
 
-CLI = os.path.join(ROOT, "panmap_amd", "bin", "panmap")
 
 
 def test_attach_dist_and_row_range_are_in_the_abi(pmx):
@@ -26,9 +25,9 @@ def test_a_failing_meta_rank_ends_the_run(pmx, tmp_path):
     (tmp_path / "r.fastq").write_text("@a\nACGTACGTACGTACGTACGTACGTACGTACGTACGT\n+\nIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII\n")
     env = dict(os.environ, PMX_DEVICE="63")
     t0 = time.time()
-    r = subprocess.run([CLI, "rsv.panman", "r.fastq", "--meta", "--gpus", "2"], cwd=tmp_path, capture_output=True, text=True, timeout=120, env=env)
+    r = run(["rsv.panman", "r.fastq", "--meta", "--gpus", "2"], tmp_path, env=env, timeout=120)
     assert r.returncode != 0 and time.time() - t0 < 60, (r.returncode, r.stderr[-500:])
     assert "opening the GPU" in r.stderr, r.stderr[-500:]
     assert not [d for d in os.listdir("/tmp") if d.startswith("panmap_ranks_") and os.path.exists(os.path.join("/tmp", d, "uid"))]
-    r = subprocess.run([CLI, "rsv.panman", "r.fastq", "--meta", "--gpus", "2", "-l", "1"], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+    r = run(["rsv.panman", "r.fastq", "--meta", "--gpus", "2", "-l", "1"], tmp_path, timeout=120)
     assert r.returncode == 1 and "--meta needs l >= 2" in r.stderr

@@ -10,11 +10,11 @@ import sys
 
 import pytest
 
+from cli_checks import run
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "panmap_amd", "bin", "panmap")
 EQUAL = ("lists_equal", "info_equal", "oc_equal", "candidates_equal", "scores_equal", "haplotypes_equal", "em_info_equal")
 
 
@@ -104,9 +104,8 @@ def test_meta_gpus_two_equals_one_through_the_cli(tmp_path):
     env = dict(os.environ, PMX_DIST_SAME_DEVICE="1", PMX_DIST_HOST_DIR=str(meet))
     for extra in ([], ["--dust", "20", "--discard", "0.5"]):
         tag = "f" if extra else "p"
-        r1 = subprocess.run([CLI, "rsv_4K.panman", "mix.fastq", "--meta", "-o", "one" + tag] + extra, cwd=tmp_path, capture_output=True, text=True, timeout=300)
-        r2 = subprocess.run([CLI, "rsv_4K.panman", "mix.fastq", "--meta", "--gpus", "2", "-o", "two" + tag] + extra, cwd=tmp_path, capture_output=True,
-                            text=True, timeout=300, env=env)
+        r1 = run(["rsv_4K.panman", "mix.fastq", "--meta", "-o", "one" + tag] + extra, tmp_path, timeout=300)
+        r2 = run(["rsv_4K.panman", "mix.fastq", "--meta", "--gpus", "2", "-o", "two" + tag] + extra, tmp_path, env=env, timeout=300)
         assert r1.returncode == 0 and r2.returncode == 0, (r1.stderr[-1000:], r2.stderr[-2000:])
         one = open(tmp_path / ("one%s.mgsr.abundance.out" % tag), "rb").read()
         assert one and one == open(tmp_path / ("two%s.mgsr.abundance.out" % tag), "rb").read()

@@ -10,8 +10,9 @@ import pytest
 from conftest import GOLDEN
 
 import bias_checks as bc
+from cli_checks import DEMO, run
 import pileup_golden as pg
-from test_genotype_gpu import DEMO, _demo_files, run
+from test_genotype_gpu import _demo_files
 from test_genotype_host import qual_interval
 from test_pileup_reference import LEGS, leg_set
 from test_vcf_tests_host import checker_bias, compare_with_call
@@ -131,7 +132,7 @@ PARENT_HEADER = """##fileformat=VCFv4.2
 @pytest.mark.gpu
 def test_demo_command_line_annotates_the_record(pmx, sars, tmp_path):
     _demo_files(tmp_path)
-    r = run(DEMO + ["-o", "ann", "--annotate-vcf"], tmp_path)
+    r = run(DEMO + ["-o", "ann", "--annotate-vcf"], tmp_path, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = open(tmp_path / "ann.vcf").read().splitlines()
     golden = open(os.path.join(GOLDEN, "isolate.vcf")).read().splitlines()
@@ -147,7 +148,7 @@ def test_demo_command_line_annotates_the_record(pmx, sars, tmp_path):
     want = [l for l in golden if l.startswith("##INFO=<ID=") and l.split("=<ID=")[1].split(",")[0] in bc.KEYS]
     assert len(want) == 8 and [l for l in lines if l in want] == want
     # without the switch: the file as it was before the switch existed
-    r = run(DEMO + ["-o", "plain"], tmp_path)
+    r = run(DEMO + ["-o", "plain"], tmp_path, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     plain = open(tmp_path / "plain.vcf").read()
     assert plain.startswith(PARENT_HEADER % "plain") and plain.count("\n") == PARENT_HEADER.count("\n") + 1
