@@ -84,7 +84,8 @@ int pmx_index_build_ex(const pmx_panman *pm, int k, int s, int t, int l, int ope
  * are PMX_ERR_UNSUPPORTED).  Not pinned to the reference's incremental HPC producer: DESIGN.md sections 1 and 7. */
 #define PMX_INDEX_HPC 0x200
 #define PMX_ORIENT_XOR 0x9e3779b97f4a7c15ULL
-/* adopt caller-provided SoA arrays (copied): parent[n], offsets[n+1], hash/pc/cc[offsets[n]] */
+/* adopt caller-provided SoA arrays (copied): parent[n], offsets[n+1], hash/pc/cc[offsets[n]]; info->reserved & 1: the arrays
+ * are an oriented index (keys as PMX_INDEX_ORIENTED makes them) */
 int pmx_index_from_arrays(const pmx_index_info *info, const uint32_t *parent, const uint64_t *offsets,
                           const uint64_t *hash, const int16_t *parent_count, const int16_t *child_count,
                           pmx_index **out);
@@ -577,6 +578,34 @@ int pmx_meta_attach_dist(pmx_meta *m, pmx_dist *d);
 int pmx_meta_row_range(const pmx_meta *m, int64_t *first, int64_t *count);
 double pmx_read_dust(const char *seq, int64_t len, int32_t window);
 
+/* --meta --filter-and-assign (filterAndAssignBatch, src/main.cpp:720-1016; scoreReadsBatch / assignReadsBatch,
+ * src/mgsr.cpp:7477-7575, 6415-6516).  Call after pmx_meta_set_reads (mates are independent reads; --dust as set by
+ * pmx_meta_set_dust).  Every merged read is scored against EVERY node, score = max(f, r) as above; with max its best score and
+ * n its seedmers (pmx_meta_read_info): max == 0 -> PMX_META_UNMAPPED; 0 < max < (int32)(discard * n) -> PMX_META_DISCARDED
+ * (the cast truncates, src/mgsr.cpp:1693); else PMX_META_ASSIGNED, and the read's nodes are ALL nodes with score == max, its LCA
+ * node their lowest common ancestor (UINT32_MAX for a read that is not assigned).  Nodes are DFS indices; identical nodes are
+ * NOT folded here (pmx_index_node_heads folds at output time).  --ambiguous-score-threshold(-ratio), --maximum-taxon-number and
+ * --taxonomic-metadata (taxonomy) are not built.  One GPU: PMX_ERR_UNSUPPORTED with an attached dist.
+ * Parity with the reference's own run is unpinned, as for --meta; csrc/meta_assign.hip says how it runs on the device. */
+#define PMX_META_UNMAPPED 0
+#define PMX_META_DISCARDED 1
+#define PMX_META_ASSIGNED 2
+int pmx_meta_assign(pmx_ctx *ctx, pmx_meta *m, double discard);
+/* per merged read (cap >= pmx_meta_num_reads); any pointer may be NULL.  n_nodes is 0 unless the read is assigned */
+int pmx_meta_assign_reads(const pmx_meta *m, uint8_t *state, uint16_t *max_score, uint32_t *lca, uint32_t *n_nodes, int64_t cap);
+/* the assigned nodes as a CSR list: read r's nodes at nodes[offsets[r] .. offsets[r + 1]), ascending; num_reads + 1 offsets */
+int64_t pmx_meta_assign_num_nodes(const pmx_meta *m);
+int pmx_meta_assign_nodes(const pmx_meta *m, int64_t *offsets, uint32_t *nodes, int64_t cap_nodes);
+/* the reads of the last pmx_meta_set_reads in input order -> their merged read, -1 for a read dropped by --dust or without
+ * seedmers (PMX_ERR_UNSUPPORTED with an attached dist: the merged reads are then the whole sample's) */
+int64_t pmx_meta_num_raw_reads(const pmx_meta *m);
+int pmx_meta_raw_to_merged(const pmx_meta *m, int64_t *map, int64_t cap);
+/* Host only, no device.  head[v] of an ORIENTED index: v itself when v is the root or carries changes, else the nearest
+ * ancestor that does -- a node without changes has its parent's seed set, scores as it, and the reference prints it on that
+ * ancestor's line (src/mgsr.cpp:505-532).  pmx_index_lca: the lowest common ancestor of two DFS indices, -1 out of range. */
+int pmx_index_node_heads(const pmx_index *idx_oriented, uint32_t *head);
+int64_t pmx_index_lca(const pmx_index *idx, int64_t a, int64_t b);
+
 /* ------------------------------------------------------------------------------------------
  * GENOTYPE + CONSENSUS stages (runGenotyping / runConsensus, src/main.cpp:1828-1900).  The reference forks
  * `bcftools mpileup -Ou -B`, `bcftools call --ploidy 1 -m -A`, filters the calls (src/genotyping.cpp:167-279) and forks
@@ -725,7 +754,9 @@ int64_t pmx_options_describe(char *buf, int64_t cap);
 /* kernel timing: average duration (ms) of the dominant kernel of the last call, measured with HIP
    events on the context stream; name selects a stage ("pack", "seed", "score", "align") or a kernel of the align stage
    ("align_cseeds" = k_compact_seeds*, "align_dom" = the mapping kernel over every pair, "align_cmulti" = the compact
-   tier's second form, k_align_compact*_multi); < 0: no such span in the last call */
+   tier's second form, k_align_compact*_multi) or a span of --meta ("meta_score" = the bit matrices and the score kernel of
+   pmx_meta_score; "meta_assign" = the device work of pmx_meta_assign up to the scan of the node counts, "meta_assign_emit" = its
+   list kernel, both summed over the call's chunks); < 0: no such span in the last call */
 double pmx_last_kernel_ms(pmx_ctx *ctx, const char *name);
 
 #ifdef __cplusplus

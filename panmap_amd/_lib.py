@@ -212,6 +212,14 @@ SIGNATURES = {
     "pmx_meta_attach_dist": (_i32, [_vp, _vp]),
     "pmx_meta_row_range": (_i32, [_vp, _vp, _vp]),
     "pmx_read_dust": (C.c_double, [_cp, _i64, _i32]),
+    "pmx_meta_assign": (_i32, [_vp, _vp, C.c_double]),
+    "pmx_meta_assign_reads": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64]),
+    "pmx_meta_assign_num_nodes": (_i64, [_vp]),
+    "pmx_meta_assign_nodes": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_meta_num_raw_reads": (_i64, [_vp]),
+    "pmx_meta_raw_to_merged": (_i32, [_vp, _vp, _i64]),
+    "pmx_index_node_heads": (_i32, [_vp, _vp]),
+    "pmx_index_lca": (_i64, [_vp, _i64, _i64]),
     "pmx_dist_unique_id": (_i32, [_vp]),
     "pmx_dist_init": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "pmx_dist_free": (None, [_vp]),

@@ -96,13 +96,14 @@ class Index:
         return cls(h)
 
     @classmethod
-    def from_arrays(cls, k, s, t, l, open_syncmer, parent, offsets, hashes, parent_counts, child_counts, flank_mask=0, hpc=False):
+    def from_arrays(cls, k, s, t, l, open_syncmer, parent, offsets, hashes, parent_counts, child_counts, flank_mask=0, hpc=False, oriented=False):
+        """oriented: the arrays are an oriented (--meta) index, keys as Index.build(mode=ORIENTED) makes them"""
         parent = np.ascontiguousarray(parent, np.uint32)
         offsets = np.ascontiguousarray(offsets, np.uint64)
         hashes = np.ascontiguousarray(hashes, np.uint64)
         pc = np.ascontiguousarray(parent_counts, np.int16)
         cc = np.ascontiguousarray(child_counts, np.int16)
-        info = _lib.IndexInfo(k, s, t, l, int(open_syncmer), int(bool(hpc)), flank_mask, 0, len(parent), len(hashes))
+        info = _lib.IndexInfo(k, s, t, l, int(open_syncmer), int(bool(hpc)), flank_mask, int(bool(oriented)), len(parent), len(hashes))
         h = C.c_void_p()
         check(lib.pmx_index_from_arrays(C.byref(info), parent.ctypes.data, offsets.ctypes.data, hashes.ctypes.data,
                                         pc.ctypes.data, cc.ctypes.data, C.byref(h)), "pmx_index_from_arrays")
@@ -136,6 +137,16 @@ class Index:
     def node_id(self, dfs_index: int) -> str:
         p = lib.pmx_index_node_id(self._h, int(dfs_index))
         return p.decode() if p else ""
+
+    def node_heads(self) -> np.ndarray:
+        """per node of an ORIENTED index: itself, or (a non-root node without changes) the nearest ancestor that has some --
+        identical nodes fold into it (src/mgsr.cpp:505-532)"""
+        out = np.zeros(self.info.n_nodes, np.uint32)
+        check(lib.pmx_index_node_heads(self._h, out.ctypes.data), "pmx_index_node_heads")
+        return out
+
+    def lca(self, a: int, b: int) -> int:
+        return int(lib.pmx_index_lca(self._h, int(a), int(b)))
 
     def close(self):
         if self._h:

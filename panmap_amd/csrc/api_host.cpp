@@ -156,6 +156,7 @@ int pmx_index_from_arrays(const pmx_index_info* info, const uint32_t* parent, co
     pmx::LiteIndex& L = ix->ix;
     L.params.k = info->k; L.params.s = info->s; L.params.t = info->t; L.params.l = info->l;
     L.params.open = info->open_syncmer != 0;
+    L.params.oriented = (info->reserved & 1) != 0;
     L.hpc = info->hpc != 0;
     L.flank_mask = info->flank_mask;
     L.parent.assign(parent, parent + n);
@@ -204,6 +205,26 @@ int pmx_index_read_header(const char* path, pmx_index_info* info, int* uncompres
 const char* pmx_index_node_id(const pmx_index* idx, int64_t dfs_index) {
     if (!idx || dfs_index < 0 || (size_t)dfs_index >= idx->ix.node_id.size()) return nullptr;
     return idx->ix.node_id[(size_t)dfs_index].c_str();
+}
+
+// identical nodes (src/mgsr.cpp:505-532): a non-root node without changes in the oriented index folds into the nearest
+// ancestor that has some (parents come first in DFS pre-order, so one pass does it)
+int pmx_index_node_heads(const pmx_index* idx, uint32_t* head) {
+    if (!idx || !head) return PMX_ERR_ARG;
+    const pmx::LiteIndex& L = idx->ix;
+    if (!L.params.oriented) { pmx::set_error("pmx_index_node_heads needs the oriented index"); return PMX_ERR_ARG; }
+    for (size_t v = 0; v < L.n_nodes(); ++v) head[v] = v > 0 && L.offsets[v] == L.offsets[v + 1] ? head[L.parent[v]] : (uint32_t)v;
+    return PMX_OK;
+}
+
+// (a parent's DFS index is below its child's: the deeper of the two is the larger index)
+int64_t pmx_index_lca(const pmx_index* idx, int64_t a, int64_t b) {
+    if (!idx || a < 0 || b < 0 || a >= (int64_t)idx->ix.n_nodes() || b >= (int64_t)idx->ix.n_nodes()) return -1;
+    while (a != b) {
+        if (a > b) a = idx->ix.parent[(size_t)a];
+        else b = idx->ix.parent[(size_t)b];
+    }
+    return a;
 }
 
 void pmx_index_close(pmx_index* idx) { delete idx; }

@@ -26,6 +26,7 @@
 //     the host with the libm the oracle uses), FP64 throughout, every reduction in a fixed order (bit-stable runs):
 //     k_meta_denoms (a wave per read), k_meta_colsum (a thread per candidate over a chunk of reads; chunk partials added in
 //     chunk order).  HBM-bound: 2 B per (read, candidate) per pass, six passes per SQUAREM iteration.
+// --filter-and-assign (every read against EVERY node, no score matrix) is meta_assign.hip, on the state of meta_state.hpp.
 // Read-side seedmer extraction is host C++ here (threads; the k-min-mer definitions of host/seed_host.hpp); moving it into
 // the seeding kernel is the next step.  parity: the reference's own MGSR index and EM cannot be built here (panman / TBB /
 // Eigen / abseil are absent): scores and EM are checked by the test suite against a direct restatement (per-node seed
@@ -50,6 +51,7 @@
 #include "device/dev_util.hpp"
 #include "host/index_build.hpp"
 #include "host/seed_host.hpp"
+#include "meta_state.hpp"
 #include "place_kernels.h"
 #include "readset.hpp"
 
@@ -61,17 +63,6 @@ constexpr int64_t kColsumChunk = 256;
 constexpr int64_t kSumBlock = 1024;
 // reads per launch of the seeding kernel in list mode: bounds the list arrays (one slot per base)
 constexpr int64_t kListChunk = 2000000;
-
-// index of `key` in the ascending array keys[0..n), or -1
-__device__ __forceinline__ int64_t find_sorted(const uint64_t* __restrict__ keys, int64_t n, uint64_t key) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && keys[lo] == key ? lo : -1;
-}
 
 // first position in the ascending array a[0..n) whose value is >= v
 __device__ __forceinline__ int lower_bound_u32(const uint32_t* __restrict__ a, int n, uint32_t v) {
@@ -108,17 +99,6 @@ __global__ void k_meta_mask_events(const uint64_t* __restrict__ ch_key, const in
             const unsigned long long bits = (b1 == 63 ? ~0ULL : ((1ULL << (b1 + 1)) - 1ULL)) & ~((1ULL << b0) - 1ULL);
             atomicXor(&row[w], bits);
         }
-    }
-}
-
-// bit-sliced counters: plane[p] holds bit p of 64 independent counts; add one 64-bit row of 0/1 increments
-template <int PLANES>
-__device__ __forceinline__ void planes_add(unsigned long long (&plane)[PLANES], unsigned long long inc) {
-#pragma unroll
-    for (int p = 0; p < PLANES; ++p) {
-        const unsigned long long carry = plane[p] & inc;
-        plane[p] ^= inc;
-        inc = carry;
     }
 }
 
@@ -386,54 +366,6 @@ __global__ void k_em_choose(const double* p0, const double* p2, const double* sq
 }
 }  // namespace
 
-struct pmx_meta_group {
-    uint32_t node;                   // representative (lowest DFS index of the group)
-    std::vector<uint32_t> members;   // the other candidates with the same score column
-    double prop = 0.0;
-};
-
-struct pmx_meta {
-    pmx_ctx* ctx = nullptr;
-    const pmx_index* idx_std = nullptr;
-    int64_t n_nodes = 0, n_changes = 0;
-    SyncmerParams params;
-    // oriented index on the device
-    DevBuf<uint64_t> ch_key;
-    DevBuf<int16_t> ch_pc, ch_cc;
-    DevBuf<uint32_t> ch_node, subtree_end;
-    pmx_place* placer = nullptr;
-    // reads (merged by seedmer list)
-    int64_t n_raw_reads = 0, n_reads = 0, n_seedmers = 0;
-    std::vector<int64_t> h_read_off;
-    std::vector<uint64_t> h_seed_hash;
-    std::vector<uint8_t> h_seed_rev;
-    std::vector<int64_t> h_mult;
-    std::vector<uint64_t> h_uniq;
-    DevBuf<int64_t> d_read_off;
-    DevBuf<uint32_t> d_seed_uid;
-    DevBuf<uint8_t> d_seed_rev;
-    DevBuf<uint64_t> d_uniq;
-    std::vector<double> oc;                 // per node
-    // candidates
-    std::vector<uint32_t> cand;             // DFS indices, ascending
-    DevBuf<uint32_t> d_cand;
-    DevBuf<unsigned long long> mask_fwd, mask_rev;
-    DevBuf<uint16_t> score;                 // [n_reads][n_cand]
-    // result
-    std::vector<pmx_meta_group> groups;     // sorted by proportion, descending
-    int em_rounds = 0, em_iterations = 0;
-    double llh = 0.0;
-    double dust_threshold = 100.0;          // --dust: 100 = no filter
-    int64_t n_dust_dropped = 0;
-    int64_t longest = 0;                    // seedmers of the longest merged read
-    // --gpus N (pmx_meta_attach_dist): `score` holds merged reads [row_first, row_first + row_count) only (pass A), score_em
-    // the EM rows this rank owns (pass B)
-    pmx_dist* dist = nullptr;
-    bool reads_set = false;
-    int64_t row_first = 0, row_count = 0;
-    DevBuf<uint16_t> score_em;
-};
-
 namespace {
 // the order of merged reads: lexicographic on the hash list, then on the orientation list (the order the vector comparisons gave)
 int cmp_lists(const uint64_t* xh, const uint8_t* xv, int64_t xn, const uint64_t* yh, const uint8_t* yv, int64_t yn) {
@@ -540,6 +472,7 @@ struct MetaReads {
     int64_t n_reads;
     std::string kept_concat;
     std::vector<int64_t> kept_off;
+    std::vector<int64_t> kept_raw;    // kept read -> the caller's read (filled when any read was dropped)
     const int64_t n_raw;              // reads the caller passed
     int64_t n_dusty = 0;              // of them, dropped by --dust
     int64_t n_kept_all;               // kept reads of the whole sample (--gpus N: over all ranks)
@@ -601,6 +534,7 @@ void MetaReads::drop_dusty() {
         if (dusty[(size_t)r]) continue;
         kept_concat.append(concat + offsets[r], (size_t)(offsets[r + 1] - offsets[r]));
         kept_off.push_back((int64_t)kept_concat.size());
+        kept_raw.push_back(r);
     }
     concat = kept_concat.data();
     offsets = kept_off.data();
@@ -673,7 +607,7 @@ int MetaReads::seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc) {
 // Reads with the same seedmer list (hash and orientation, in order) are one read with a multiplicity; a read without
 // seedmers scores 0 everywhere and carries no weight in the EM (src/mgsr.cpp:8170-8173): dropped here.
 // Reads: r_off / r_hash / r_rev.  Leaves: m->h_read_off / h_seed_hash / h_seed_rev / h_mult, sorted by cmp_lists, with
-// m->n_reads / n_seedmers, and this rank's raw and dropped counts.
+// m->n_reads / n_seedmers, this rank's raw and dropped counts, and m->h_raw_to_merged (the caller's read -> its merged read).
 void MetaReads::merge_equal_lists() {
     std::vector<int64_t> order;
     for (int64_t r = 0; r < n_reads; ++r)
@@ -683,8 +617,12 @@ void MetaReads::merge_equal_lists() {
     m->n_dust_dropped = n_dusty;
     m->h_read_off.assign(1, 0);
     m->h_seed_hash.clear(); m->h_seed_rev.clear(); m->h_mult.clear();
+    m->h_raw_to_merged.assign((size_t)n_raw, -1);
     for (size_t i = 0; i < order.size(); ++i) {
-        if (i > 0 && cmp(order[i - 1], order[i]) == 0) { ++m->h_mult.back(); continue; }
+        const bool copy = i > 0 && cmp(order[i - 1], order[i]) == 0;
+        const int64_t raw = kept_raw.empty() ? order[i] : kept_raw[(size_t)order[i]];
+        m->h_raw_to_merged[(size_t)raw] = (int64_t)m->h_mult.size() - (copy ? 1 : 0);   // the merged read made last, or the one made now
+        if (copy) { ++m->h_mult.back(); continue; }
         const ListView o = list(order[i]);
         m->h_seed_hash.insert(m->h_seed_hash.end(), o.h, o.h + o.n);
         m->h_seed_rev.insert(m->h_seed_rev.end(), o.v, o.v + o.n);
@@ -703,6 +641,7 @@ void MetaReads::merge_over_ranks() {
     m->n_raw_reads = m->n_dust_dropped = n_kept_all = 0;
     for (size_t r = 0; r < counts.size() / 5; ++r) { m->n_raw_reads += counts[5 * r]; m->n_dust_dropped += counts[5 * r + 1]; n_kept_all += counts[5 * r + 2]; }
     merge_runs_over_ranks(m, counts, 5);
+    m->h_raw_to_merged.clear();   // (the merged reads are the whole sample's now: this rank's map no longer names them)
 }
 
 // Reads: the merged lists in m->h_*.  Leaves: m->h_uniq (the distinct hashes, ascending) and, on the device, the offsets,
@@ -711,7 +650,8 @@ void MetaReads::upload_lists() {
     m->h_uniq = m->h_seed_hash;
     std::sort(m->h_uniq.begin(), m->h_uniq.end());
     m->h_uniq.erase(std::unique(m->h_uniq.begin(), m->h_uniq.end()), m->h_uniq.end());
-    std::vector<uint32_t> uid((size_t)m->n_seedmers);
+    std::vector<uint32_t>& uid = m->h_seed_uid;
+    uid.resize((size_t)m->n_seedmers);
     for (int64_t i = 0; i < m->n_seedmers; ++i)
         uid[(size_t)i] = (uint32_t)(std::lower_bound(m->h_uniq.begin(), m->h_uniq.end(), m->h_seed_hash[(size_t)i]) - m->h_uniq.begin());
     m->d_read_off.ensure((size_t)m->n_reads + 1);
@@ -724,7 +664,7 @@ void MetaReads::upload_lists() {
         PMX_HIP(hipMemcpyAsync(m->d_seed_rev.p, m->h_seed_rev.data(), (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
         PMX_HIP(hipMemcpyAsync(m->d_uniq.p, m->h_uniq.data(), sizeof(uint64_t) * m->h_uniq.size(), hipMemcpyHostToDevice, ctx->stream));
     }
-    PMX_HIP(hipStreamSynchronize(ctx->stream));   // (uid goes out of scope)
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
 }
 
 // Overlap coefficients through the place stage: seed the reads on the device, score the tree with every read seed kept
@@ -1166,6 +1106,8 @@ int pmx_meta_create(pmx_ctx* ctx, const pmx_index* idx_std, const pmx_index* idx
     std::vector<uint32_t> end((size_t)n);
     for (int64_t v = 0; v < n; ++v) end[v] = (uint32_t)v;
     for (int64_t v = n - 1; v > 0; --v) end[O->parent[v]] = std::max(end[O->parent[v]], end[v]);
+    m->h_parent = O->parent;
+    m->h_subtree_end = end;
     std::vector<uint32_t> node((size_t)c);
     for (int64_t v = 0; v < n; ++v)
         for (uint64_t q = O->offsets[v]; q < O->offsets[v + 1]; ++q) node[q] = (uint32_t)v;
@@ -1226,6 +1168,7 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     if (rc != PMX_OK) return rc;
     m->cand.clear();
     m->groups.clear();
+    m->assigned = false;
     m->row_first = 0;
     m->row_count = m->dist ? 0 : m->n_reads;
     m->reads_set = true;
@@ -1243,13 +1186,15 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
     m->groups.clear();
     own_row_slice(m);
     if (m->cand.empty() || m->n_reads == 0) return PMX_OK;
-    build_masks(ctx, m);
     m->score.ensure((size_t)m->row_count * m->cand.size());
     int64_t longest = 0;
     for (int64_t r = 0; r < m->n_reads; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
     if (longest >= 65535) return fail(PMX_ERR_UNSUPPORTED, "a read with 65,535 seedmers or more (16-bit scores)");
     m->longest = longest;
+    timer_begin(ctx, "meta_score");
+    build_masks(ctx, m);
     score_rows(ctx, m, m->row_first, m->row_count, m->score.p);
+    timer_end(ctx, "meta_score", 1);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
     PMX_CATCH

@@ -374,6 +374,7 @@ double pmx_last_kernel_ms(pmx_ctx* ctx, const char* name) {
     if (!ctx || !name) return -1.0;
     auto it = ctx->timers.find(name);
     if (it == ctx->timers.end() || !it->second.pending) return -1.0;
+    if (it->second.summed) return it->second.sum_ms;
     float ms = 0.f;
     if (hipEventSynchronize(it->second.e1) != hipSuccess) return -1.0;
     if (hipEventElapsedTime(&ms, it->second.e0, it->second.e1) != hipSuccess) return -1.0;

@@ -8,7 +8,7 @@
 //   consensus  the placed genome with the calls applied -> `<prefix>.consensus.fa` (runConsensus, src/main.cpp:1877-1900)
 // `--stop index|place|align|genotype|consensus` ends after that stage (default: consensus).  --meta ->
 // `<prefix>.mgsr.abundance.out`.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
-// parts of panmap this build leaves out (--filter-and-assign, --impute, ...), BUILDING a homopolymer-compressed index (one
+// parts of panmap this build leaves out (--impute, ...), BUILDING a homopolymer-compressed index (one
 // given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta, --batch with
 // --gpus.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
 #include <signal.h>
@@ -43,6 +43,7 @@ struct Config {
     bool dedup = false, force_leaf = false;
     int trim_start = 0, trim_end = 0, min_seed_quality = 0, min_read_support = -1;
     bool meta = false;     // --meta: haplotype deconvolution (src/main.cpp:1192-1313)
+    bool filter_and_assign = false;   // --meta --filter-and-assign: reads to their best-scoring nodes (src/main.cpp:720-1016)
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
     int em_max_iterations = 1000, em_max_rounds = 5;
@@ -77,6 +78,8 @@ void usage() {
           "      --annotate-vcf         add VDB, SGB, RPBZ, MQBZ, MQSBZ, BQBZ, SCBZ and MQ0F to the INFO of the VCF records\n"
           "      --batch FILE           one sample per line: reads1 [reads2] [prefix]; the index stays resident\n"
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
+          "      --meta --filter-and-assign   assign every read to the nodes it scores best on -> <prefix>.mgsr.assignedReads.fastq,\n"
+          "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU; no taxonomy options)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange\n"
           "      --refine               re-rank the top candidates by aligning the reads against them\n"
@@ -136,6 +139,10 @@ Config parse(int argc, char** argv) {
         else if (a == "--refine-neighbor-radius") c.refine_neighbor_radius = atoi(v().c_str());
         else if (a == "--refine-max-neighbor-n") c.refine_max_neighbor_n = atoi(v().c_str());
         else if (a == "--meta") c.meta = true;
+        else if (a == "--filter-and-assign") c.filter_and_assign = true;
+        else if (a == "--breadth-ratio" || a == "--jplace" || a.rfind("--taxonomic-", 0) == 0 || a == "--maximum-taxon-number" ||
+                 a == "--ambiguous-score-threshold" || a == "--ambiguous-score-threshold-ratio" || a == "--mask-read-ends")
+            die("option " + a + " is not accepted: --filter-and-assign is built without taxonomy, breadth ratios, jplace output and read-end masking");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
         else if (a == "--em-convergence-threshold") c.em_convergence = atof(v().c_str());
         else if (a == "--em-delta-threshold") c.em_delta = atof(v().c_str());
@@ -147,7 +154,7 @@ Config parse(int argc, char** argv) {
         else if (a == "--min-qual") c.min_qual = atof(v().c_str());
         else if (a == "--annotate-vcf") c.annotate_vcf = true;
         else if (a == "--baq") die("--baq (base alignment quality) is not implemented in this build; the pileup runs as `mpileup -B` does");
-        else if (a == "--filter-and-assign" || a == "--impute" || a == "--extent-guard" || a == "--reference-node" ||
+        else if (a == "--impute" || a == "--extent-guard" || a == "--reference-node" ||
                  a == "--dump-sequence" || a == "--dump-all-scores")
             die("option " + a + " belongs to a part of panmap this build does not implement (index / place / align / genotype / consensus only)");
         else if (a.size() > 1 && a[0] == '-') die("unknown option " + a + " (see --help)");
@@ -333,6 +340,7 @@ struct Reads {
     const int64_t *no1 = nullptr, *no2 = nullptr;
     bool paired = false;
     int64_t n_reads = 0, unit = 1;               // unit: reads that stay together in a shard
+    int64_t n_first = 0;                         // reads of the first file
 
     Reads(const std::string& reads1, const std::string& reads2, Layout layout) {
         pmx_fastx *&f1 = file1.h, *&f2 = file2.h;
@@ -346,6 +354,7 @@ struct Reads {
         check(pmx_fastx_views(f1, &s1, &q1, &o1, &nm1, &no1), "reads1 views");
         if (paired) check(pmx_fastx_views(f2, &s2, &q2, &o2, &nm2, &no2), "reads2 views");
         n_reads = n1 + n2;
+        n_first = n1;
         unit = paired && layout == INTERLEAVED ? 2 : 1;
         off.reserve((size_t)n_reads + 1);
         concat.reserve((size_t)(o1[n1] + (paired ? o2[n2] : 0)));
@@ -369,9 +378,9 @@ struct Reads {
         *lo = n_units * rank / world * unit;
         *hi = rank == world - 1 ? n_reads : n_units * (rank + 1) / world * unit;
     }
-    std::string name(int64_t r) const {          // (interleaved layout)
-        const bool second = unit == 2 && (r & 1);
-        const int64_t i = r / unit;
+    std::string name(int64_t r) const {          // (either layout: mates alternate, or the second file follows the first)
+        const bool second = unit == 2 ? (r & 1) != 0 : r >= n_first;
+        const int64_t i = unit == 2 ? r / 2 : second ? r - n_first : r;
         std::string nm = second ? std::string(nm2 + no2[i], (size_t)(no2[i + 1] - no2[i])) : std::string(nm1 + no1[i], (size_t)(no1[i + 1] - no1[i]));
         while (!nm.empty() && nm.back() == '\0') nm.pop_back();
         return nm;
@@ -812,11 +821,86 @@ pmx_dist* join_ranks(pmx_ctx* ctx, const Ranks& rk) {
     return dist;
 }
 
+// --meta --filter-and-assign (filterAndAssignBatch, src/main.cpp:720-1016; writeAssignedReadsOut, :522-558, :889-903), after
+// pmx_meta_set_reads: every read against every node, then the three files.  `<prefix>.mgsr.assignedReads.fastq` holds the
+// assigned reads in input order (FASTA input: quality `I`); `.mgsr.assignedReads.out` and `.mgsr.assignedReadsLCANode.out` hold
+// one line per head node that has reads, `head[,nodes folded into it]<TAB>.<TAB>count<TAB>indices into the FASTQ`, by
+// ascending DFS index of the head (the reference's orders come from hash-map iteration: DESIGN.md section 4.3).
+void write_assigned(const Config& c, Run& run, const Reads& reads) {
+    pmx_meta* m = run.meta;
+    check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
+    const int64_t n_merged = pmx_meta_num_reads(m), n_nodes_total = pmx_meta_assign_num_nodes(m);
+    std::vector<uint8_t> state((size_t)std::max<int64_t>(n_merged, 1));
+    std::vector<uint32_t> lca(state.size()), nodes((size_t)std::max<int64_t>(n_nodes_total, 1));
+    std::vector<int64_t> off((size_t)n_merged + 1), merged((size_t)std::max<int64_t>(reads.n_reads, 1));
+    check(pmx_meta_assign_reads(m, state.data(), nullptr, lca.data(), nullptr, n_merged), "the reads' states");
+    check(pmx_meta_assign_nodes(m, off.data(), nodes.data(), (int64_t)nodes.size()), "the reads' nodes");
+    check(pmx_meta_raw_to_merged(m, merged.data(), reads.n_reads), "the reads' merged reads");
+    pmx_index_info info;
+    check(pmx_index_get_info(run.oidx, &info), "index info");
+    std::vector<uint32_t> head((size_t)info.n_nodes);
+    check(pmx_index_node_heads(run.oidx, head.data()), "folding identical nodes");
+    // the FASTQ, and per merged read the FASTQ positions of its copies (ascending: input order)
+    const std::string fq_path = c.output + ".mgsr.assignedReads.fastq";
+    FILE* fq = fopen(fq_path.c_str(), "w");
+    if (!fq) die("cannot write " + fq_path);
+    std::vector<std::vector<int64_t>> copies((size_t)n_merged);
+    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0;
+    for (int64_t r = 0; r < reads.n_reads; ++r) {
+        const int64_t mr = merged[(size_t)r];
+        const int st = mr < 0 ? PMX_META_UNMAPPED : state[(size_t)mr];
+        if (st != PMX_META_ASSIGNED) { (st == PMX_META_DISCARDED ? n_discarded : n_unmapped)++; continue; }
+        const size_t at = (size_t)reads.off[(size_t)r], len = (size_t)(reads.off[(size_t)r + 1] - reads.off[(size_t)r]);
+        const std::string qual = len > 0 && reads.quals[at] == '\0' ? std::string(len, 'I') : reads.quals.substr(at, len);   // src/main.cpp:889-903
+        fprintf(fq, "@%s\n%.*s\n+\n%s\n", reads.name(r).c_str(), (int)len, reads.concat.data() + at, qual.c_str());
+        copies[(size_t)mr].push_back(n_written++);
+    }
+    fclose(fq);
+    // read -> nodes inverted to head -> reads, for the assigned nodes and for the LCA node
+    std::vector<std::vector<int64_t>> by_node((size_t)info.n_nodes), by_lca((size_t)info.n_nodes);
+    for (int64_t mr = 0; mr < n_merged; ++mr) {
+        if (copies[(size_t)mr].empty()) continue;
+        uint32_t prev = UINT32_MAX;
+        std::vector<uint32_t> hs;
+        for (int64_t q = off[(size_t)mr]; q < off[(size_t)mr + 1]; ++q) hs.push_back(head[nodes[(size_t)q]]);
+        std::sort(hs.begin(), hs.end());
+        for (uint32_t h : hs) {
+            if (h != prev) by_node[h].insert(by_node[h].end(), copies[(size_t)mr].begin(), copies[(size_t)mr].end());
+            prev = h;
+        }
+        std::vector<int64_t>& l = by_lca[head[lca[(size_t)mr]]];
+        l.insert(l.end(), copies[(size_t)mr].begin(), copies[(size_t)mr].end());
+    }
+    std::vector<std::vector<uint32_t>> folded((size_t)info.n_nodes);
+    for (uint32_t v = 0; v < (uint32_t)info.n_nodes; ++v)
+        if (head[v] != v) folded[head[v]].push_back(v);
+    auto write_out = [&](const std::string& path, std::vector<std::vector<int64_t>>& groups) {
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) die("cannot write " + path);
+        for (uint32_t h = 0; h < (uint32_t)info.n_nodes; ++h) {
+            std::vector<int64_t>& g = groups[h];
+            if (g.empty()) continue;
+            std::sort(g.begin(), g.end());
+            std::string ids = pmx_index_node_id(run.idx, h);
+            for (uint32_t v : folded[h]) { ids += ","; ids += pmx_index_node_id(run.idx, v); }
+            fprintf(f, "%s\t.\t%zu\t", ids.c_str(), g.size());
+            for (size_t i = 0; i < g.size(); ++i) fprintf(f, i ? ",%lld" : "%lld", (long long)g[i]);
+            fputc('\n', f);
+        }
+        fclose(f);
+    };
+    write_out(c.output + ".mgsr.assignedReads.out", by_node);
+    write_out(c.output + ".mgsr.assignedReadsLCANode.out", by_lca);
+    say(c, "meta", fq_path + " (" + std::to_string(n_written) + " assigned, " + std::to_string(n_discarded) + " discarded, " + std::to_string(n_unmapped) +
+                       " unmapped reads)");
+}
+
 // --meta (runDeconvolution, src/main.cpp:1192-1313): reads of a mixed sample -> `<prefix>.mgsr.abundance.out`, one line per
 // estimated haplotype: node id (+ the nodes merged into it, comma-joined) <TAB> proportion with five decimals, by proportion.
 // The two indexes of the tree (the place stage's and its oriented form, without flank mask) are built in memory.
 int run_meta(Config c) {
     if (c.reads1.empty()) die("--meta needs reads");
+    if (c.filter_and_assign && c.gpus > 1) die("--filter-and-assign runs on one GPU: drop --gpus");
     if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
     if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
     if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
@@ -852,6 +936,11 @@ int run_meta(Config c) {
     if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
     check(pmx_meta_set_dust(m, c.dust), "--dust");
     check(pmx_meta_set_reads(ctx, m, reads.concat.data(), reads.off.data() + lo, hi - lo), "seeding the reads");
+    if (c.filter_and_assign) {
+        write_assigned(c, run, reads);
+        run.close();
+        return 0;
+    }
     check(pmx_meta_score(ctx, m, c.top_oc, nullptr, 0), "scoring the reads against the candidate nodes");
     say(c, "meta", std::to_string(pmx_meta_num_reads(m)) + " distinct reads x " + std::to_string(pmx_meta_num_candidates(m)) + " candidate nodes");
     pmx_meta_params mp;
@@ -896,6 +985,7 @@ int real_main(int argc, char** argv) {
     if (!c.batch.empty() && !c.reads1.empty()) die("--batch takes the read files from the batch file, not from the command line");
     if (c.gpus < 1) die("--gpus expects a positive number");
 
+    if (c.filter_and_assign && !c.meta) die("--filter-and-assign needs --meta");
     if (c.meta) {   // the reference's --meta has no HPC
         pmx_index_info h;
         if (c.hpc) die("--meta has no homopolymer-compressed form: drop --hpc");

@@ -110,6 +110,8 @@ struct KernelTimer {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int launches = 0;
     bool pending = false;
+    bool summed = false;   // a span in pieces (timer_sum_*): sum_ms is its duration
+    double sum_ms = 0.0;
 };
 
 }  // namespace pmx
@@ -138,6 +140,19 @@ inline void timer_end(pmx_ctx* ctx, const char* name, int launches) {
     PMX_HIP(hipEventRecord(t.e1, ctx->stream));
     t.launches = launches;
     t.pending = true;
+}
+// A span made of several pieces with host work between them (the chunks of pmx_meta_assign): timer_sum_reset, then per piece
+// timer_begin / timer_end and, once the stream was synchronized, timer_sum_add; pmx_last_kernel_ms reports the sum.
+inline void timer_sum_reset(pmx_ctx* ctx, const char* name) {
+    KernelTimer& t = ctx->timers[name];
+    t.summed = true;
+    t.sum_ms = 0.0;
+}
+inline void timer_sum_add(pmx_ctx* ctx, const char* name) {
+    KernelTimer& t = ctx->timers[name];
+    float ms = 0.f;
+    PMX_HIP(hipEventElapsedTime(&ms, t.e0, t.e1));
+    t.sum_ms += (double)ms;
 }
 inline int grid_for(int64_t n, int block, int max_blocks) {
     int64_t g = (n + block - 1) / block;

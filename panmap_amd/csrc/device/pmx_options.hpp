@@ -34,6 +34,7 @@
     X(PLACE_TREE_KERNEL, "ab", "node scoring: the flag-per-node persistent kernel instead of the chains kernel")                               \
     X(PLACE_NO_GRAPH, "ab", "node scoring by levels: plain launches instead of the captured HIP graph")                                        \
     X(PLACE_TEST_STARVED, "test", "node scoring: make the persistent kernel report a starved grid (exercises the level-kernel fall-back)")     \
+    X(META_ASSIGN_CHUNK, "test", "--meta --filter-and-assign: merged reads per chunk of pmx_meta_assign (default: what the bit-matrix budget holds)")           \
     X(ALIGN_NO_COMPACT, "ab", "align: skip the compact tier (every pair through the general tiers)")                                           \
     X(ALIGN_COMPACT_FUSED, "ab", "align: compact tier as one kernel (sketch + probes inside k_align_compact)")                                 \
     X(ALIGN_COMPACT_POS32, "test", "align: compact tier with 32-bit position words whatever the reference length")                             \

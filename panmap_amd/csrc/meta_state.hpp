@@ -1,0 +1,91 @@
+// What the two translation units of --meta share: the state behind a pmx_meta handle (api_meta.hip makes and fills it,
+// meta_assign.hip reads the merged reads and the oriented index from it) and the two device helpers both scoring kernels use.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "api_internal.hpp"
+#include "device/dev_util.hpp"
+#include "host/seed_host.hpp"
+
+// index of `key` in the ascending array keys[0..n), or -1
+__device__ __forceinline__ int64_t find_sorted(const uint64_t* __restrict__ keys, int64_t n, uint64_t key) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && keys[lo] == key ? lo : -1;
+}
+
+// bit-sliced counters: plane[p] holds bit p of 64 independent counts; add one 64-bit row of 0/1 increments
+template <int PLANES>
+__device__ __forceinline__ void planes_add(unsigned long long (&plane)[PLANES], unsigned long long inc) {
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) {
+        const unsigned long long carry = plane[p] & inc;
+        plane[p] ^= inc;
+        inc = carry;
+    }
+}
+
+struct pmx_meta_group {
+    uint32_t node;                   // representative (lowest DFS index of the group)
+    std::vector<uint32_t> members;   // the other candidates with the same score column
+    double prop = 0.0;
+};
+
+struct pmx_meta {
+    pmx_ctx* ctx = nullptr;
+    const pmx_index* idx_std = nullptr;
+    int64_t n_nodes = 0, n_changes = 0;
+    pmx::SyncmerParams params;
+    // oriented index on the device
+    pmx::DevBuf<uint64_t> ch_key;
+    pmx::DevBuf<int16_t> ch_pc, ch_cc;
+    pmx::DevBuf<uint32_t> ch_node, subtree_end;
+    std::vector<uint32_t> h_parent, h_subtree_end;   // the tree on the host (pmx_meta_assign: LCA)
+    pmx_place* placer = nullptr;
+    // reads (merged by seedmer list)
+    int64_t n_raw_reads = 0, n_reads = 0, n_seedmers = 0;
+    std::vector<int64_t> h_read_off;
+    std::vector<uint64_t> h_seed_hash;
+    std::vector<uint8_t> h_seed_rev;
+    std::vector<int64_t> h_mult;
+    std::vector<uint64_t> h_uniq;
+    std::vector<uint32_t> h_seed_uid;       // every seedmer as its index into h_uniq
+    std::vector<int64_t> h_raw_to_merged;   // per raw read of the last set_reads: its merged read, -1 = dropped (DUST, no seedmers); one rank only
+    pmx::DevBuf<int64_t> d_read_off;
+    pmx::DevBuf<uint32_t> d_seed_uid;
+    pmx::DevBuf<uint8_t> d_seed_rev;
+    pmx::DevBuf<uint64_t> d_uniq;
+    std::vector<double> oc;                 // per node
+    // candidates
+    std::vector<uint32_t> cand;             // DFS indices, ascending
+    pmx::DevBuf<uint32_t> d_cand;
+    pmx::DevBuf<unsigned long long> mask_fwd, mask_rev;
+    pmx::DevBuf<uint16_t> score;            // [n_reads][n_cand]
+    // result
+    std::vector<pmx_meta_group> groups;     // sorted by proportion, descending
+    int em_rounds = 0, em_iterations = 0;
+    double llh = 0.0;
+    double dust_threshold = 100.0;          // --dust: 100 = no filter
+    int64_t n_dust_dropped = 0;
+    int64_t longest = 0;                    // seedmers of the longest merged read
+    // --gpus N (pmx_meta_attach_dist): `score` holds merged reads [row_first, row_first + row_count) only (pass A), score_em
+    // the EM rows this rank owns (pass B)
+    pmx_dist* dist = nullptr;
+    bool reads_set = false;
+    int64_t row_first = 0, row_count = 0;
+    pmx::DevBuf<uint16_t> score_em;
+    // pmx_meta_assign (meta_assign.hip), per merged read of the last call; emptied by set_reads
+    bool assigned = false;
+    std::vector<uint8_t> as_state;
+    std::vector<uint16_t> as_max;
+    std::vector<uint32_t> as_lca, as_count;
+    std::vector<int64_t> as_off;            // n_reads + 1 offsets into as_nodes
+    std::vector<uint32_t> as_nodes;         // the assigned nodes of every read, ascending DFS indices
+};

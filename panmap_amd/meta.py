@@ -12,6 +12,48 @@ from .api import Context, Index, Panman, concat_reads
 
 ORIENTED = 0x100     # PMX_INDEX_ORIENTED
 ORIENT_XOR = 0x9e3779b97f4a7c15
+UNMAPPED, DISCARDED, ASSIGNED = 0, 1, 2    # PMX_META_*: the state of a read after Meta.assign
+
+
+class AssignResult:
+    """--meta --filter-and-assign, per RAW read of the last set_reads (input order): `state` (UNMAPPED / DISCARDED / ASSIGNED;
+    a read dropped by --dust or without seedmers is UNMAPPED), `max` (its best score over all nodes), `lca` (the head of the
+    LCA of its assigned nodes, -1 unless assigned), `merged` (its merged read, -1 = dropped).  `heads` folds identical
+    nodes (Index.node_heads of the oriented index).  The assigned reads, in input order, are the records of
+    `<prefix>.mgsr.assignedReads.fastq`: `fastq_index[read]` is a read's position there (-1 unless assigned)."""
+
+    def __init__(self, merged, state, mx, lca, offsets, nodes, heads):
+        self.merged, self.heads, self._off, self._nodes = merged, heads, offsets, nodes
+        has = merged >= 0
+        at = np.where(has, merged, 0)
+        self.state = np.where(has, state[at], UNMAPPED).astype(np.uint8) if len(state) else np.zeros(len(merged), np.uint8)
+        self.max = np.where(has, mx[at], 0).astype(np.int64) if len(mx) else np.zeros(len(merged), np.int64)
+        self.lca = np.full(len(merged), -1, np.int64)
+        ok = self.state == ASSIGNED
+        self.lca[ok] = heads[lca[at[ok]]]
+        self.fastq_index = np.full(len(merged), -1, np.int64)
+        self.fastq_index[ok] = np.arange(int(ok.sum()))
+
+    def nodes_of(self, read: int) -> np.ndarray:
+        """the assigned nodes of a raw read (all nodes whose score equals its maximum; DFS indices, ascending, not folded);
+        empty unless the read is assigned"""
+        r = int(self.merged[read])
+        return self._nodes[self._off[r]:self._off[r + 1]] if r >= 0 else self._nodes[:0]
+
+    def by_node(self):
+        """{head: sorted FASTQ indices of the reads assigned to the head or to a node folded into it}"""
+        out = {}
+        for read in np.nonzero(self.state == ASSIGNED)[0]:
+            for h in np.unique(self.heads[self.nodes_of(read)]).tolist():
+                out.setdefault(h, []).append(int(self.fastq_index[read]))
+        return out
+
+    def by_lca(self):
+        """{head of the LCA node: sorted FASTQ indices}"""
+        out = {}
+        for read in np.nonzero(self.state == ASSIGNED)[0]:
+            out.setdefault(int(self.lca[read]), []).append(int(self.fastq_index[read]))
+        return out
 
 
 class Meta:
@@ -63,6 +105,24 @@ class Meta:
         mp = params if params is not None else _lib.MetaParams()
         check(lib.pmx_meta_em(self.ctx._h, self._h, C.byref(mp)), "pmx_meta_em")
         return self.haplotypes()
+
+    def assign(self, discard: float = 0.0) -> AssignResult:
+        """--filter-and-assign on the reads of the last set_reads: every read against every node (pmx_meta_assign)"""
+        check(lib.pmx_meta_assign(self.ctx._h, self._h, float(discard)), "pmx_meta_assign")
+        n = self.n_reads
+        state, mx = np.zeros(n, np.uint8), np.zeros(n, np.uint16)
+        lca, cnt = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        check(lib.pmx_meta_assign_reads(self._h, state.ctypes.data, mx.ctypes.data, lca.ctypes.data, cnt.ctypes.data, n), "pmx_meta_assign_reads")
+        off, nodes = np.zeros(n + 1, np.int64), np.zeros(max(int(lib.pmx_meta_assign_num_nodes(self._h)), 1), np.uint32)
+        check(lib.pmx_meta_assign_nodes(self._h, off.ctypes.data, nodes.ctypes.data, len(nodes)), "pmx_meta_assign_nodes")
+        assert np.array_equal(np.diff(off), cnt)
+        return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads())
+
+    def raw_to_merged(self) -> np.ndarray:
+        """per read of the last set_reads (input order): its merged read, -1 when --dust dropped it or it has no seedmers"""
+        out = np.zeros(int(lib.pmx_meta_num_raw_reads(self._h)), np.int64)
+        check(lib.pmx_meta_raw_to_merged(self._h, out.ctypes.data, len(out)), "pmx_meta_raw_to_merged")
+        return out
 
     # ---- accessors
     @property
@@ -139,3 +199,23 @@ def format_abundance(haplotypes, node_id) -> str:
     for node, prop, members in haplotypes:
         lines.append(",".join([node_id(node)] + [node_id(x) for x in members]) + "\t%.5f" % prop)
     return "\n".join(lines) + ("\n" if lines else "")
+
+
+def format_assigned(result: AssignResult, node_id, heads=None):
+    """(`<prefix>.mgsr.assignedReads.out`, `<prefix>.mgsr.assignedReadsLCANode.out`) (writeAssignedReadsOut,
+    src/main.cpp:522-558): one line per head node that has reads, `head[,folded nodes]<TAB>.<TAB>count<TAB>i,j,k` -- the taxon
+    column is always `.`, the indices are positions in the assigned-reads FASTQ, ascending.  Canonical order (the
+    reference's comes from hash-map iteration): lines by ascending DFS index of the head, ids on a line the head, then the
+    nodes folded into it by ascending DFS index."""
+    heads = np.asarray(result.heads if heads is None else heads)
+    members = {}
+    for v in np.nonzero(heads != np.arange(len(heads)))[0].tolist():
+        members.setdefault(int(heads[v]), []).append(v)
+
+    def text(groups):
+        lines = []
+        for h in sorted(groups):
+            ids = ",".join(node_id(x) for x in [h] + members.get(h, []))
+            lines.append("%s\t.\t%d\t%s" % (ids, len(groups[h]), ",".join(str(i) for i in sorted(groups[h]))))
+        return "\n".join(lines) + ("\n" if lines else "")
+    return text(result.by_node()), text(result.by_lca())

@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""--meta --filter-and-assign: device time of pmx_meta_assign (pmx_last_kernel_ms "meta_assign" + "meta_assign_emit") against
+the only other route to the same answer, pmx_meta_score with EVERY node as a candidate ("meta_score": bit matrices + score
+kernel; the download of the score matrix and a host argmax are not counted).  Each is run twice, the second run is reported
+(the first one allocates inside the span).
+  meta_assign_timing.py rsv  [n_reads]   rsv_4K, reads at step 1 over two of its genomes (default 20,000)
+  meta_assign_timing.py sars [n_reads]   SARS-CoV-2 20k tree, the 5-haplotype mixture of test_config5_sars_five_haplotypes (default 200,000)"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def _fasta(path):
+    return "".join(x.strip() for x in open(path) if not x.startswith(">")).upper()
+
+
+def rsv_reads(pmx, n):
+    rng = np.random.default_rng(1330)
+    reads = []
+    for g in (_fasta(os.path.join(GOLDEN, "MZ515733.1.fa")), _fasta(os.path.join(GOLDEN, "rsv_4K.panman.random.node_1330.fa"))):
+        reads += [g[i:i + 150].encode() for i in range(min(n // 2, len(g) - 149))]
+    for i in range(0, len(reads), 3):
+        reads[i] = pmx.reverse_complement(reads[i])
+    for i in range(1, len(reads), 6):
+        q = bytearray(reads[i])
+        for p in rng.integers(0, len(q), 2):
+            q[p] = b"ACGT"[(b"ACGT".index(q[p]) + 1) % 4] if q[p] in b"ACGT" else q[p]
+        reads[i] = bytes(q)
+    concat, off = pmx.concat_reads(reads)
+    return np.frombuffer(concat, np.uint8), off
+
+
+def sars_reads(pmx, pm, n):
+    golden = [x.rstrip("\n").split("\t") for x in open(os.path.join(GOLDEN, "example.mgsr.abundance.out"))]
+    parts, offs, base = [], [np.zeros(1, np.int64)], 0
+    for i, (name, share) in enumerate(zip([g[0] for g in golden[:5]], [0.50, 0.20, 0.15, 0.10, 0.05])):
+        c, o = pmx.simulate_paired_reads(pm.genome(pm.find_node(name)), int(n * share) // 2, seed=10 + i)
+        parts.append(c if isinstance(c, np.ndarray) else np.frombuffer(c, np.uint8))
+        offs.append(np.asarray(o[1:], np.int64) + base)
+        base += int(o[-1])
+    return np.concatenate(parts), np.concatenate(offs)
+
+
+def main():
+    import panmap_amd as pmx
+    from panmap_amd._lib import lib
+    which = sys.argv[1] if len(sys.argv) > 1 else "rsv"
+    n = int(sys.argv[2]) if len(sys.argv) > 2 else (20000 if which == "rsv" else 200000)
+    pm = pmx.Panman(os.path.join(GOLDEN, "rsv_4K.panman" if which == "rsv" else "sars_20000_twilight_dipper.panman"))
+    ctx = pmx.Context(0)
+    meta = pmx.Meta.build(ctx, pm)
+    concat, off = rsv_reads(pmx, n) if which == "rsv" else sars_reads(pmx, pm, n)
+    meta.set_reads(concat=concat, offsets=off)
+    n_nodes = meta.index.info.n_nodes
+    ms = lambda name: float(lib.pmx_last_kernel_ms(ctx._h, name.encode()))
+    out = dict(case=which, reads=len(off) - 1, distinct_reads=meta.n_reads, nodes=n_nodes)
+    _, h, _ = meta.read_seedmers()
+    words = ((n_nodes + 63) // 64 + 1) & ~1
+    out["distinct_seedmers"] = int(len(np.unique(h)))
+    out["bit_matrix_bytes"] = 2 * out["distinct_seedmers"] * words * 8     # (of all reads: split over chunks of at most 2 GiB)
+    for rep in range(2):
+        t0 = time.perf_counter()
+        res = meta.assign(0.0)
+        out["assign_wall_s"] = time.perf_counter() - t0
+        out["assign_ms"], out["assign_emit_ms"] = ms("meta_assign"), ms("meta_assign_emit")
+    out["assigned_reads"] = int((res.state == 2).sum())
+    out["assigned_nodes_total"] = int(lib.pmx_meta_assign_num_nodes(meta._h))
+    every = np.arange(n_nodes, dtype=np.uint32)
+    for rep in range(2):
+        meta.score(candidates=every)
+        out["score_all_nodes_ms"] = ms("meta_score")
+    out["score_matrix_bytes"] = meta.n_reads * n_nodes * 2
+    if which == "rsv":                                          # the two routes agree (the big case would download 7 GB)
+        sc = meta.scores()
+        merged_max = np.zeros(meta.n_reads, np.int64)
+        merged_max[res.merged[res.merged >= 0]] = res.max[res.merged >= 0]
+        out["max_equal"] = bool(np.array_equal(sc.max(axis=1).astype(np.int64), merged_max))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
