@@ -584,18 +584,51 @@ double pmx_read_dust(const char *seq, int64_t len, int32_t window);
  * n its seedmers (pmx_meta_read_info): max == 0 -> PMX_META_UNMAPPED; 0 < max < (int32)(discard * n) -> PMX_META_DISCARDED
  * (the cast truncates, src/mgsr.cpp:1693); else PMX_META_ASSIGNED, and the read's nodes are ALL nodes with score == max, its LCA
  * node their lowest common ancestor (UINT32_MAX for a read that is not assigned).  Nodes are DFS indices; identical nodes are
- * NOT folded here (pmx_index_node_heads folds at output time).  --ambiguous-score-threshold(-ratio), --maximum-taxon-number and
- * --taxonomic-metadata (taxonomy) are not built.  One GPU: PMX_ERR_UNSUPPORTED with an attached dist.
+ * NOT folded here (pmx_index_node_heads folds at output time).  One GPU: PMX_ERR_UNSUPPORTED with an attached dist.
+ * With a taxonomy (pmx_meta_set_taxonomy, below) an assigned read whose best-scoring or near-best-scoring nodes span more than
+ * max_taxa taxa becomes PMX_META_OVER_TAXA instead: no nodes, no LCA.  PMX_ERR_UNSUPPORTED then for discard > 0 together with
+ * a non-zero ambiguity threshold.  Without a taxonomy nothing of it runs.
  * Parity with the reference's own run is unpinned, as for --meta; csrc/meta_assign.hip says how it runs on the device. */
 #define PMX_META_UNMAPPED 0
 #define PMX_META_DISCARDED 1
 #define PMX_META_ASSIGNED 2
+#define PMX_META_OVER_TAXA 3
 int pmx_meta_assign(pmx_ctx *ctx, pmx_meta *m, double discard);
 /* per merged read (cap >= pmx_meta_num_reads); any pointer may be NULL.  n_nodes is 0 unless the read is assigned */
 int pmx_meta_assign_reads(const pmx_meta *m, uint8_t *state, uint16_t *max_score, uint32_t *lca, uint32_t *n_nodes, int64_t cap);
 /* the assigned nodes as a CSR list: read r's nodes at nodes[offsets[r] .. offsets[r + 1]), ascending; num_reads + 1 offsets */
 int64_t pmx_meta_assign_num_nodes(const pmx_meta *m);
 int pmx_meta_assign_nodes(const pmx_meta *m, int64_t *offsets, uint32_t *nodes, int64_t cap_nodes);
+/* The taxonomy filter of --filter-and-assign (--taxonomic-metadata, --maximum-taxon-number; fillTaxonIndices, src/mgsr.cpp:
+ * 156-196; checkTaxonIndicesBatch, :6463-6496).  node_taxon: per DFS index of the oriented index the node's own taxon in [0,
+ * n_taxa), -1 = none (any node, internal ones included).  S(v) = the taxa in the subtree of v, in the tree as indexed (identical
+ * nodes not folded); a node is over when |S(v)| > max_taxa.  A read's taxa are the union of S(v) over the nodes where one of
+ * its seedmers changes presence (in either orientation; at the root: is present) and its score is >= lo = max(0, max - amb),
+ * amb = max(abs, (int)(max * ratio)) (pmx_meta_set_ambiguous: --ambiguous-score-threshold, -ratio; both 0 = its best nodes);
+ * it is over when one of those nodes is, or the union exceeds max_taxa.  max_taxa 0 clears the taxonomy (node_taxon may be
+ * NULL); max_taxa > 16 is PMX_ERR_UNSUPPORTED.  Both hold for the pmx_meta_assign calls that follow. */
+int pmx_meta_set_taxonomy(pmx_meta *m, const int32_t *node_taxon, int64_t n_nodes, int64_t n_taxa, int32_t max_taxa);
+int pmx_meta_set_ambiguous(pmx_meta *m, int32_t abs, double ratio);
+/* the taxa of every merged read of the last pmx_meta_assign (cap >= pmx_meta_num_reads reads): n_taxa[r] ids, ascending, at
+ * taxa[r * max_taxa] with max_taxa = pmx_meta_assign_max_taxa (0: the call ran without a taxonomy); n_taxa is 0 unless the
+ * read is assigned */
+int pmx_meta_assign_taxa(const pmx_meta *m, uint32_t *n_taxa, uint32_t *taxa, int64_t cap);
+int32_t pmx_meta_assign_max_taxa(const pmx_meta *m);
+/* S(v) of the taxonomy that is set: its size (ids[0 .. size) ascending, ids may be NULL), -1 when it exceeds max_taxa, -2 for
+ * a bad argument or without a taxonomy */
+int64_t pmx_meta_node_taxa(const pmx_meta *m, int64_t v, uint32_t *ids, int64_t cap);
+/* Host only.  The taxonomic metadata table (loadTaxonomicMetadata, src/mgsr.cpp:198-256): tokens separated by white space; the
+ * header token equal to `rank` names the column, which must not be the first; on every other line the first token is a node
+ * identifier and the token in that column its taxon (`.`: the line is skipped; empty lines too); a taxon's index is its order
+ * of first appearance; a later line for an identifier replaces an earlier one.  PMX_ERR_IO: the file cannot be read;
+ * PMX_ERR_ARG: no such rank in the header, or in its first column; PMX_ERR_FORMAT: no header line, or a line that ends before
+ * the column.  pmx_taxonomy_lookup: the taxon of an identifier, -1 when the table has none. */
+typedef struct pmx_taxonomy pmx_taxonomy;
+int pmx_taxonomy_load(const char *path, const char *rank, pmx_taxonomy **out);
+void pmx_taxonomy_free(pmx_taxonomy *t);
+int64_t pmx_taxonomy_num_taxa(const pmx_taxonomy *t);
+const char *pmx_taxonomy_taxon_name(const pmx_taxonomy *t, int64_t taxon);
+int64_t pmx_taxonomy_lookup(const pmx_taxonomy *t, const char *identifier);
 /* the reads of the last pmx_meta_set_reads in input order -> their merged read, -1 for a read dropped by --dust or without
  * seedmers (PMX_ERR_UNSUPPORTED with an attached dist: the merged reads are then the whole sample's) */
 int64_t pmx_meta_num_raw_reads(const pmx_meta *m);
@@ -756,7 +789,8 @@ int64_t pmx_options_describe(char *buf, int64_t cap);
    ("align_cseeds" = k_compact_seeds*, "align_dom" = the mapping kernel over every pair, "align_cmulti" = the compact
    tier's second form, k_align_compact*_multi) or a span of --meta ("meta_score" = the bit matrices and the score kernel of
    pmx_meta_score; "meta_assign" = the device work of pmx_meta_assign up to the scan of the node counts, "meta_assign_emit" = its
-   list kernel, both summed over the call's chunks); < 0: no such span in the last call */
+   list kernel, both summed over the call's chunks; with a taxonomy "meta_assign" ends before the taxonomy kernels and
+   "meta_assign_taxa" holds them and that scan); < 0: no such span in the last call */
 double pmx_last_kernel_ms(pmx_ctx *ctx, const char *name);
 
 #ifdef __cplusplus

@@ -216,6 +216,16 @@ SIGNATURES = {
     "pmx_meta_assign_reads": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64]),
     "pmx_meta_assign_num_nodes": (_i64, [_vp]),
     "pmx_meta_assign_nodes": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_meta_set_taxonomy": (_i32, [_vp, _vp, _i64, _i64, _i32]),
+    "pmx_meta_set_ambiguous": (_i32, [_vp, _i32, C.c_double]),
+    "pmx_meta_assign_taxa": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_meta_assign_max_taxa": (_i32, [_vp]),
+    "pmx_meta_node_taxa": (_i64, [_vp, _i64, _vp, _i64]),
+    "pmx_taxonomy_load": (_i32, [_cp, _cp, _vp]),
+    "pmx_taxonomy_free": (None, [_vp]),
+    "pmx_taxonomy_num_taxa": (_i64, [_vp]),
+    "pmx_taxonomy_taxon_name": (_cp, [_vp, _i64]),
+    "pmx_taxonomy_lookup": (_i64, [_vp, _cp]),
     "pmx_meta_num_raw_reads": (_i64, [_vp]),
     "pmx_meta_raw_to_merged": (_i32, [_vp, _vp, _i64]),
     "pmx_index_node_heads": (_i32, [_vp, _vp]),

@@ -44,6 +44,11 @@ struct Config {
     int trim_start = 0, trim_end = 0, min_seed_quality = 0, min_read_support = -1;
     bool meta = false;     // --meta: haplotype deconvolution (src/main.cpp:1192-1313)
     bool filter_and_assign = false;   // --meta --filter-and-assign: reads to their best-scoring nodes (src/main.cpp:720-1016)
+    // the taxonomy filter of --filter-and-assign (src/main.cpp:2068-2083); `taxonomy_options`: the ones given besides the file
+    std::string taxonomic_metadata, taxonomic_rank = "Family";
+    int maximum_taxon_number = 1, ambiguous_score = 0;
+    double ambiguous_ratio = 0.0;
+    std::vector<std::string> taxonomy_options;
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
     int em_max_iterations = 1000, em_max_rounds = 5;
@@ -79,7 +84,11 @@ void usage() {
           "      --batch FILE           one sample per line: reads1 [reads2] [prefix]; the index stays resident\n"
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
           "      --meta --filter-and-assign   assign every read to the nodes it scores best on -> <prefix>.mgsr.assignedReads.fastq,\n"
-          "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU; no taxonomy options)\n"
+          "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU)\n"
+          "      --taxonomic-metadata TSV     ... and drop the reads whose best-scoring nodes span more than N taxa: node id in the first\n"
+          "                             column, the taxa of --taxonomic-rank NAME (default Family) in the column of that name\n"
+          "      --maximum-taxon-number N (default 1, at most 16)   --ambiguous-score-threshold N / --ambiguous-score-threshold-ratio F:\n"
+          "                             count the nodes within max(N, int(best * F)) of a read's best score too (not with --discard > 0)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange\n"
           "      --refine               re-rank the top candidates by aligning the reads against them\n"
@@ -140,9 +149,13 @@ Config parse(int argc, char** argv) {
         else if (a == "--refine-max-neighbor-n") c.refine_max_neighbor_n = atoi(v().c_str());
         else if (a == "--meta") c.meta = true;
         else if (a == "--filter-and-assign") c.filter_and_assign = true;
-        else if (a == "--breadth-ratio" || a == "--jplace" || a.rfind("--taxonomic-", 0) == 0 || a == "--maximum-taxon-number" ||
-                 a == "--ambiguous-score-threshold" || a == "--ambiguous-score-threshold-ratio" || a == "--mask-read-ends")
-            die("option " + a + " is not accepted: --filter-and-assign is built without taxonomy, breadth ratios, jplace output and read-end masking");
+        else if (a == "--taxonomic-metadata") c.taxonomic_metadata = v();
+        else if (a == "--taxonomic-rank") { c.taxonomic_rank = v(); c.taxonomy_options.push_back(a); }
+        else if (a == "--maximum-taxon-number") { c.maximum_taxon_number = atoi(v().c_str()); c.taxonomy_options.push_back(a); }
+        else if (a == "--ambiguous-score-threshold") { c.ambiguous_score = atoi(v().c_str()); c.taxonomy_options.push_back(a); }
+        else if (a == "--ambiguous-score-threshold-ratio") { c.ambiguous_ratio = atof(v().c_str()); c.taxonomy_options.push_back(a); }
+        else if (a == "--breadth-ratio" || a == "--jplace" || a == "--mask-read-ends")
+            die("option " + a + " is not accepted: --filter-and-assign is built without breadth ratios, jplace output and read-end masking");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
         else if (a == "--em-convergence-threshold") c.em_convergence = atof(v().c_str());
         else if (a == "--em-delta-threshold") c.em_delta = atof(v().c_str());
@@ -826,8 +839,16 @@ pmx_dist* join_ranks(pmx_ctx* ctx, const Ranks& rk) {
 // assigned reads in input order (FASTA input: quality `I`); `.mgsr.assignedReads.out` and `.mgsr.assignedReadsLCANode.out` hold
 // one line per head node that has reads, `head[,nodes folded into it]<TAB>.<TAB>count<TAB>indices into the FASTQ`, by
 // ascending DFS index of the head (the reference's orders come from hash-map iteration: DESIGN.md section 4.3).
-void write_assigned(const Config& c, Run& run, const Reads& reads) {
+// With `taxonomy` (--taxonomic-metadata) the reads spanning more than --maximum-taxon-number taxa are in none of the files, and
+// the second column holds the taxon names of the head's subtree by ascending taxon index, `.` when there are none or too many.
+void write_assigned(const Config& c, Run& run, const Reads& reads, const pmx_taxonomy* taxonomy) {
     pmx_meta* m = run.meta;
+    if (taxonomy) {
+        std::vector<int32_t> node_taxon;
+        for (int64_t v = 0; pmx_index_node_id(run.idx, v); ++v) node_taxon.push_back((int32_t)pmx_taxonomy_lookup(taxonomy, pmx_index_node_id(run.idx, v)));
+        check(pmx_meta_set_taxonomy(m, node_taxon.data(), (int64_t)node_taxon.size(), pmx_taxonomy_num_taxa(taxonomy), c.maximum_taxon_number), "--taxonomic-metadata");
+        check(pmx_meta_set_ambiguous(m, c.ambiguous_score, c.ambiguous_ratio), "--ambiguous-score-threshold");
+    }
     check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
     const int64_t n_merged = pmx_meta_num_reads(m), n_nodes_total = pmx_meta_assign_num_nodes(m);
     std::vector<uint8_t> state((size_t)std::max<int64_t>(n_merged, 1));
@@ -845,11 +866,11 @@ void write_assigned(const Config& c, Run& run, const Reads& reads) {
     FILE* fq = fopen(fq_path.c_str(), "w");
     if (!fq) die("cannot write " + fq_path);
     std::vector<std::vector<int64_t>> copies((size_t)n_merged);
-    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0;
+    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0, n_over = 0;
     for (int64_t r = 0; r < reads.n_reads; ++r) {
         const int64_t mr = merged[(size_t)r];
         const int st = mr < 0 ? PMX_META_UNMAPPED : state[(size_t)mr];
-        if (st != PMX_META_ASSIGNED) { (st == PMX_META_DISCARDED ? n_discarded : n_unmapped)++; continue; }
+        if (st != PMX_META_ASSIGNED) { (st == PMX_META_OVER_TAXA ? n_over : st == PMX_META_DISCARDED ? n_discarded : n_unmapped)++; continue; }
         const size_t at = (size_t)reads.off[(size_t)r], len = (size_t)(reads.off[(size_t)r + 1] - reads.off[(size_t)r]);
         const std::string qual = len > 0 && reads.quals[at] == '\0' ? std::string(len, 'I') : reads.quals.substr(at, len);   // src/main.cpp:889-903
         fprintf(fq, "@%s\n%.*s\n+\n%s\n", reads.name(r).c_str(), (int)len, reads.concat.data() + at, qual.c_str());
@@ -883,7 +904,11 @@ void write_assigned(const Config& c, Run& run, const Reads& reads) {
             std::sort(g.begin(), g.end());
             std::string ids = pmx_index_node_id(run.idx, h);
             for (uint32_t v : folded[h]) { ids += ","; ids += pmx_index_node_id(run.idx, v); }
-            fprintf(f, "%s\t.\t%zu\t", ids.c_str(), g.size());
+            std::string taxa;
+            uint32_t tx[16];
+            const int64_t n_tx = taxonomy ? pmx_meta_node_taxa(m, h, tx, 16) : 0;
+            for (int64_t i = 0; i < n_tx; ++i) { if (i) taxa += ","; taxa += pmx_taxonomy_taxon_name(taxonomy, tx[i]); }
+            fprintf(f, "%s\t%s\t%zu\t", ids.c_str(), taxa.empty() ? "." : taxa.c_str(), g.size());
             for (size_t i = 0; i < g.size(); ++i) fprintf(f, i ? ",%lld" : "%lld", (long long)g[i]);
             fputc('\n', f);
         }
@@ -892,7 +917,8 @@ void write_assigned(const Config& c, Run& run, const Reads& reads) {
     write_out(c.output + ".mgsr.assignedReads.out", by_node);
     write_out(c.output + ".mgsr.assignedReadsLCANode.out", by_lca);
     say(c, "meta", fq_path + " (" + std::to_string(n_written) + " assigned, " + std::to_string(n_discarded) + " discarded, " + std::to_string(n_unmapped) +
-                       " unmapped reads)");
+                       " unmapped reads" +
+                       (taxonomy ? ", " + std::to_string(n_over) + " spanning more than " + std::to_string(c.maximum_taxon_number) + " taxa" : std::string()) + ")");
 }
 
 // --meta (runDeconvolution, src/main.cpp:1192-1313): reads of a mixed sample -> `<prefix>.mgsr.abundance.out`, one line per
@@ -904,6 +930,25 @@ int run_meta(Config c) {
     if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
     if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
     if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
+    // the taxonomy filter: read the table before anything else is opened
+    const bool with_taxonomy = !c.taxonomic_metadata.empty();
+    if ((with_taxonomy || !c.taxonomy_options.empty()) && !c.filter_and_assign)
+        die("option " + (with_taxonomy ? std::string("--taxonomic-metadata") : c.taxonomy_options[0]) + " is not accepted without --filter-and-assign");
+    if (!with_taxonomy && !c.taxonomy_options.empty()) die("option " + c.taxonomy_options[0] + " is not accepted without --taxonomic-metadata");
+    struct Taxonomy {
+        pmx_taxonomy* t = nullptr;
+        ~Taxonomy() { pmx_taxonomy_free(t); }
+    } taxonomy;
+    if (with_taxonomy) {
+        if (c.maximum_taxon_number < 1 || c.maximum_taxon_number > 16) die("--maximum-taxon-number must be between 1 and 16");
+        if (c.ambiguous_score < 0 || c.ambiguous_ratio < 0.0) die("--ambiguous-score-threshold and --ambiguous-score-threshold-ratio must not be negative");
+        if (c.discard > 0.0 && (c.ambiguous_score > 0 || c.ambiguous_ratio > 0.0))
+            die("--discard above 0 cannot be combined with --ambiguous-score-threshold or --ambiguous-score-threshold-ratio: which near-best nodes "
+                "count would then depend on the order of a node's seed changes in the reference");
+        const int rc = pmx_taxonomy_load(c.taxonomic_metadata.c_str(), c.taxonomic_rank.c_str(), &taxonomy.t);
+        if (rc == PMX_ERR_IO) die("option --taxonomic-metadata is not accepted: cannot read " + c.taxonomic_metadata);
+        check(rc, "--taxonomic-metadata");
+    }
     Run run;
     run.panman_path = c.panman;
     pmx_panman* pm = run.panman();
@@ -937,7 +982,7 @@ int run_meta(Config c) {
     check(pmx_meta_set_dust(m, c.dust), "--dust");
     check(pmx_meta_set_reads(ctx, m, reads.concat.data(), reads.off.data() + lo, hi - lo), "seeding the reads");
     if (c.filter_and_assign) {
-        write_assigned(c, run, reads);
+        write_assigned(c, run, reads, taxonomy.t);
         run.close();
         return 0;
     }

@@ -16,8 +16,17 @@
 // the latest); every later node in DFS order is recorded too, the whole subtree of that node included.  The unrecorded changes
 // lie before the flag was set, at scores below the threshold <= max, where the read is not in the running set anyway.  So the
 // read is reported exactly at the nodes with score == max, and the LCA accumulated at :6437 is the LCA of that set.
-// (--ambiguous-score-threshold(-ratio), --maximum-taxon-number and --taxonomic-metadata act through taxonomy only,
-//  checkTaxonIndicesBatch :6463-6496: not built.)
+//
+// Taxonomy (--taxonomic-metadata, --maximum-taxon-number M, --ambiguous-score-threshold A, -ratio; fillTaxonIndices :156-196,
+// checkTaxonIndicesBatch :6463-6496).  Every node has S(v), the taxa of its subtree, "over" when |S(v)| > M.  A read with max != 0
+// after the discard step has amb = max(A, (int)(max * ratio)), lo = max(0, max - amb); at every node where it has a RECORD (one of
+// its seedmers changes presence there, 0 <-> positive, in either orientation; :7488-7552) and scores >= lo, S(v) joins the
+// read's set; the read is over, and dropped from both assignments, when it meets an over node or its set exceeds M.
+// In closed form (DESIGN.md section 4.3 has the argument): for lo >= 1 the records need not be told apart, the union over ALL
+// nodes with score >= lo is the same set, because an unrecorded qualifying node has a recorded ancestor with its score, whose
+// S contains its own; with amb == 0 those nodes are the best columns that k_meta_assign_max leaves in its word masks.  Only lo
+// == 0 needs the recorded nodes themselves: the touch matrix of k_assign_mark_ends.  A discard threshold with amb > 0 is refused:
+// the reference then starts recording in the middle of a node's updates, in an order this index does not keep.
 //
 // Here every node is a column.  Nodes are in DFS pre-order, so a seedmer that becomes present / absent at node v toggles the
 // columns [v, subtree_end[v]]:
@@ -30,6 +39,7 @@
 //     stays bit-sliced: a plane-wise compare gives the columns where same > other and the score planes by select, one
 //     top-down pass over the planes gives the word's maximum and the columns that reach it.  A wave max-reduction gives the
 //     read's maximum; the same lanes then clear the words that fell short and count what is left;
+//   * with a taxonomy, k_meta_assign_near<PLANES> (only with an ambiguity option) and k_meta_assign_taxa: see there;
 //   * k_meta_assign_emit: after an exclusive scan of the node counts, a wave per read expands its set bits into the CSR list
 //     read -> DFS indices, ascending.
 // The merged reads are processed in chunks, each with the rows of ITS distinct seedmers, so that the two bit matrices stay
@@ -53,17 +63,22 @@
 using namespace pmx;
 
 namespace {
-// the two (distinct seedmer x node) bit matrices of a chunk together; 2 GiB holds the SARS 20k tree (626 words a row) with
-// 100,000 distinct seedmers: 2 x 100,000 x 626 x 8 B = 1.0 GB
+// the (distinct seedmer x node) bit matrices of a chunk together (two; three with the touch matrix); 2 GiB holds the SARS 20k
+// tree (626 words a row) with 100,000 distinct seedmers: 2 x 100,000 x 626 x 8 B = 1.0 GB
 constexpr size_t kAssignMatrixBytes = (size_t)2 << 30;
-// the per-read word masks and word maxima of a chunk (10 B per read and word)
+// the per-read word masks and word maxima of a chunk (10 B per read and word; 18 B with k_meta_assign_near's rows)
 constexpr size_t kAssignReadRowBytes = (size_t)1 << 30;
+// the most taxa a read or a node may span (--maximum-taxon-number): k_meta_assign_taxa keeps a read's set in registers
+constexpr int kAssignMaxTaxa = 16;
 
 // Every count change of the oriented index whose seedmer becomes present (parent count 0) or absent (child count 0) and whose
-// hash the chunk's reads carry: the two end bits of its column range [v, subtree_end[v]] in the seedmer's row.
+// hash the chunk's reads carry: the two end bits of its column range [v, subtree_end[v]] in the seedmer's row.  With `touch`
+// (one matrix for both orientations, or null) also bit v itself: the seedmer changes presence AT v.  The end bits cannot
+// serve for that: the closing bit of one transition cancels the opening bit of the next.
 __global__ void k_assign_mark_ends(const uint64_t* __restrict__ ch_key, const int16_t* __restrict__ ch_pc, const int16_t* __restrict__ ch_cc,
                                    const uint32_t* __restrict__ ch_node, int64_t n_changes, const uint32_t* __restrict__ subtree_end, int64_t n_nodes,
-                                   const uint64_t* __restrict__ uniq, int64_t n_uniq, int words, unsigned long long* mask_fwd, unsigned long long* mask_rev) {
+                                   const uint64_t* __restrict__ uniq, int64_t n_uniq, int words, unsigned long long* mask_fwd, unsigned long long* mask_rev,
+                                   unsigned long long* touch) {
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_changes; c += (int64_t)gridDim.x * blockDim.x) {
         const bool was = ch_pc[c] > 0, is = ch_cc[c] > 0;
         if (was == is) continue;
@@ -74,6 +89,7 @@ __global__ void k_assign_mark_ends(const uint64_t* __restrict__ ch_key, const in
         if (uid < 0) continue;
         row += (size_t)uid * (size_t)words;
         const uint32_t v = ch_node[c];
+        if (touch) atomicOr(&touch[(size_t)uid * (size_t)words + (v >> 6)], 1ULL << (v & 63));   // (either orientation; never cancels)
         const int64_t e = (int64_t)subtree_end[v] + 1;
         atomicXor(&row[v >> 6], 1ULL << (v & 63));
         if (e < n_nodes) atomicXor(&row[e >> 6], 1ULL << (e & 63));   // (a range that ends with the last node has no closing bit)
@@ -123,6 +139,31 @@ __device__ __forceinline__ void word_max(const unsigned long long (&same)[PLANES
     *mx = m;
 }
 
+// the same / other planes of one read (seedmers [i0, i1)) over the pair of words q of its seedmers' rows
+template <int PLANES>
+__device__ __forceinline__ void read_planes(const unsigned long long* __restrict__ mask_fwd, const unsigned long long* __restrict__ mask_rev,
+                                            const uint32_t* __restrict__ seed_uid, const uint8_t* __restrict__ seed_rev, int64_t i0, int64_t i1,
+                                            int64_t seed_base, int words, int q, unsigned long long (&same0)[PLANES], unsigned long long (&other0)[PLANES],
+                                            unsigned long long (&same1)[PLANES], unsigned long long (&other1)[PLANES]) {
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) { same0[p] = 0; other0[p] = 0; same1[p] = 0; other1[p] = 0; }
+    for (int64_t i = i0; i < i1; ++i) {
+        const size_t at = (size_t)seed_uid[i - seed_base] * (size_t)words + (size_t)(2 * q);
+        const ulonglong2 f = *reinterpret_cast<const ulonglong2*>(mask_fwd + at), b = *reinterpret_cast<const ulonglong2*>(mask_rev + at);
+        const bool rev = seed_rev[i] != 0;
+        planes_add<PLANES>(same0, rev ? b.x : f.x);    // the genome holds it the way the read does
+        planes_add<PLANES>(other0, rev ? f.x : b.x);
+        planes_add<PLANES>(same1, rev ? b.y : f.y);
+        planes_add<PLANES>(other1, rev ? f.y : b.y);
+    }
+}
+
+// the columns < N of the word at column c0
+__device__ __forceinline__ unsigned long long valid_columns(int64_t n_nodes, int64_t c0) {
+    const int64_t left = n_nodes - c0;
+    return left >= 64 ? ~0ULL : left <= 0 ? 0ULL : (1ULL << left) - 1ULL;
+}
+
 // A wave per merged read of the chunk (reads [0, n_reads) of read_off, which points at the chunk's first read; seed_uid holds
 // the chunk's seedmers from seed_base on as rows of the chunk's matrices, seed_rev is indexed like the whole sample's).
 // wmask / wmax: [n_reads][words] scratch; the outputs are per read.  state: 0 unmapped, 1 discarded, 2 assigned; count,
@@ -143,20 +184,8 @@ __global__ void __launch_bounds__(256) k_meta_assign_max(const int64_t* __restri
         uint32_t best = 0;
         for (int q = lane; q < pairs; q += 64) {
             unsigned long long same0[PLANES], other0[PLANES], same1[PLANES], other1[PLANES];
-#pragma unroll
-            for (int p = 0; p < PLANES; ++p) { same0[p] = 0; other0[p] = 0; same1[p] = 0; other1[p] = 0; }
-            for (int64_t i = i0; i < i1; ++i) {
-                const size_t at = (size_t)seed_uid[i - seed_base] * (size_t)words + (size_t)(2 * q);
-                const ulonglong2 f = *reinterpret_cast<const ulonglong2*>(mask_fwd + at), b = *reinterpret_cast<const ulonglong2*>(mask_rev + at);
-                const bool rev = seed_rev[i] != 0;
-                planes_add<PLANES>(same0, rev ? b.x : f.x);    // the genome holds it the way the read does
-                planes_add<PLANES>(other0, rev ? f.x : b.x);
-                planes_add<PLANES>(same1, rev ? b.y : f.y);
-                planes_add<PLANES>(other1, rev ? f.y : b.y);
-            }
-            const int64_t c0 = (int64_t)q * 128, left0 = n_nodes - c0, left1 = left0 - 64;
-            const unsigned long long v0 = left0 >= 64 ? ~0ULL : left0 <= 0 ? 0ULL : (1ULL << left0) - 1ULL;
-            const unsigned long long v1 = left1 >= 64 ? ~0ULL : left1 <= 0 ? 0ULL : (1ULL << left1) - 1ULL;
+            read_planes<PLANES>(mask_fwd, mask_rev, seed_uid, seed_rev, i0, i1, seed_base, words, q, same0, other0, same1, other1);
+            const unsigned long long v0 = valid_columns(n_nodes, (int64_t)q * 128), v1 = valid_columns(n_nodes, (int64_t)q * 128 + 64);
             unsigned long long m0, m1;
             uint32_t x0, x1;
             word_max<PLANES>(same0, other0, v0, &m0, &x0);
@@ -194,6 +223,131 @@ __global__ void __launch_bounds__(256) k_meta_assign_max(const int64_t* __restri
     }
 }
 
+// the columns of one word where max(same, other) >= lo (1 <= lo < 2^PLANES), bit-sliced against the scalar lo
+template <int PLANES>
+__device__ __forceinline__ unsigned long long word_ge(const unsigned long long (&same)[PLANES], const unsigned long long (&other)[PLANES], uint32_t lo) {
+    unsigned long long gt = 0, eq = ~0ULL;   // same > other, as in word_max
+#pragma unroll
+    for (int p = PLANES - 1; p >= 0; --p) {
+        gt |= eq & same[p] & ~other[p];
+        eq &= ~(same[p] ^ other[p]);
+    }
+    unsigned long long above = 0, tie = ~0ULL;   // score > lo / score == lo on the planes seen so far
+#pragma unroll
+    for (int p = PLANES - 1; p >= 0; --p) {
+        const unsigned long long plane = (gt & same[p]) | (~gt & other[p]);
+        if ((lo >> p) & 1u) tie &= plane;
+        else { above |= tie & plane; tie &= ~plane; }
+    }
+    return above | tie;
+}
+
+// Taxonomy with a non-zero ambiguity option (checkTaxonIndicesBatch, src/mgsr.cpp:6463-6496): a wave per ASSIGNED read of the
+// chunk, a lane per pair of words, the loads of k_meta_assign_max.  amb = max(amb_abs, (int)(max * amb_ratio)), lo = max(0, max -
+// amb).  lo >= 1: the read's row of `near` gets the columns < N with score >= lo (the records of the
+// reference need not be told apart there).  lo == 0: the nodes where one of the read's seedmers changes presence, the OR of its
+// seedmers' rows of `touch` (the host allocates `touch` whenever some maximum can give lo == 0).
+template <int PLANES>
+__global__ void __launch_bounds__(256) k_meta_assign_near(const int64_t* __restrict__ read_off, int64_t seed_base, const uint32_t* __restrict__ seed_uid,
+                                                         const uint8_t* __restrict__ seed_rev, int64_t n_reads, const unsigned long long* __restrict__ mask_fwd,
+                                                         const unsigned long long* __restrict__ mask_rev, const unsigned long long* __restrict__ touch, int words,
+                                                         int64_t n_nodes, int amb_abs, double amb_ratio, const uint16_t* __restrict__ in_max,
+                                                         const uint8_t* __restrict__ in_state, unsigned long long* near) {
+    const int lane = threadIdx.x & 63;
+    const int pairs = words >> 1;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        if (in_state[r] != PMX_META_ASSIGNED) continue;
+        const int64_t i0 = read_off[r], i1 = read_off[r + 1];
+        const int mx = (int)in_max[r];
+        const int lo = max(0, mx - max(amb_abs, (int)((double)mx * amb_ratio)));
+        unsigned long long* rnear = near + (size_t)r * (size_t)words;
+        if (lo == 0) {
+            for (int w = lane; w < words; w += 64) {
+                unsigned long long acc = 0;
+                for (int64_t i = i0; i < i1; ++i) acc |= touch[(size_t)seed_uid[i - seed_base] * (size_t)words + (size_t)w];
+                rnear[w] = acc;
+            }
+            continue;
+        }
+        for (int q = lane; q < pairs; q += 64) {
+            unsigned long long same0[PLANES], other0[PLANES], same1[PLANES], other1[PLANES];
+            read_planes<PLANES>(mask_fwd, mask_rev, seed_uid, seed_rev, i0, i1, seed_base, words, q, same0, other0, same1, other1);
+            rnear[2 * q] = word_ge<PLANES>(same0, other0, (uint32_t)lo) & valid_columns(n_nodes, (int64_t)q * 128);
+            rnear[2 * q + 1] = word_ge<PLANES>(same1, other1, (uint32_t)lo) & valid_columns(n_nodes, (int64_t)q * 128 + 64);
+        }
+    }
+}
+
+// The taxa of every ASSIGNED read of the chunk: U = the union of S(v) over its qualifying nodes (rows of `qual`: the best
+// columns, or k_meta_assign_near's), S(v) from the node table of pmx_meta_set_taxonomy: tx_over = the nodes with |S(v)| >
+// max_taxa as a row of `words` words, tx_count[v] <= max_taxa ids at tx_ids[v * max_taxa].  A wave per read, a lane per word, 64
+// words a step.  A qualifying node in tx_over ends the read at once (one ballot a step).  Otherwise every lane walks its set
+// bits and offers the next taxon of its node that the set does not hold; the lowest offering lane's id goes into the set
+// (`set`, `nset`: the same in every lane), which drops that id from every lane's offers.  |U| > max_taxa: the read's state
+// becomes PMX_META_OVER_TAXA and its node count 0, so that the scan and k_meta_assign_emit pass it by.  Else its taxa, ascending,
+// at rd_tax[r * max_taxa].  max_taxa <= kAssignMaxTaxa.
+__global__ void __launch_bounds__(256) k_meta_assign_taxa(const unsigned long long* __restrict__ qual, int words, int64_t n_reads,
+                                                         const unsigned long long* __restrict__ tx_over, const uint8_t* __restrict__ tx_count,
+                                                         const uint32_t* __restrict__ tx_ids, int max_taxa, uint8_t* state, uint32_t* count, uint8_t* rd_ntax,
+                                                         uint32_t* rd_tax) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        if (state[r] != PMX_META_ASSIGNED) {
+            if (lane == 0) rd_ntax[r] = 0;
+            continue;
+        }
+        uint32_t set[kAssignMaxTaxa];
+#pragma unroll
+        for (int k = 0; k < kAssignMaxTaxa; ++k) set[k] = 0;
+        int nset = 0;
+        bool over = false;
+        for (int base = 0; base < words && !over; base += 64) {
+            const int w = base + lane;
+            unsigned long long q = w < words ? qual[(size_t)r * (size_t)words + (size_t)w] : 0ULL;
+            if (__ballot(w < words && (q & tx_over[w]) != 0)) { over = true; break; }
+            int j = 0;   // the next taxon of the node of q's lowest bit
+            for (;;) {
+                bool have = false;
+                uint32_t cand = 0;
+                while (q) {
+                    const size_t v = (size_t)w * 64 + (size_t)(__ffsll((long long)q) - 1);
+                    if (j >= (int)tx_count[v]) { q &= q - 1; j = 0; continue; }
+                    cand = tx_ids[v * (size_t)max_taxa + (size_t)j];
+                    bool held = false;
+#pragma unroll
+                    for (int k = 0; k < kAssignMaxTaxa; ++k) held |= k < nset && set[k] == cand;
+                    if (!held) { have = true; break; }
+                    ++j;
+                }
+                const unsigned long long offers = __ballot(have);
+                if (!offers) break;
+                if (nset == max_taxa) { over = true; break; }
+                const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)cand, __ffsll((long long)offers) - 1));
+#pragma unroll
+                for (int k = 0; k < kAssignMaxTaxa; ++k)
+                    if (k == nset) set[k] = id;
+                ++nset;
+            }
+        }
+        if (over) {
+            if (lane == 0) { state[r] = PMX_META_OVER_TAXA; count[r] = 0; rd_ntax[r] = 0; }
+            continue;
+        }
+        // ascending: lane k < nset holds set[k] and writes it at its rank
+        uint32_t mine = 0;
+        int rank = 0;
+#pragma unroll
+        for (int k = 0; k < kAssignMaxTaxa; ++k)
+            if (k == lane) mine = set[k];
+#pragma unroll
+        for (int k = 0; k < kAssignMaxTaxa; ++k) rank += k < nset && set[k] < mine;
+        if (lane < nset) rd_tax[(size_t)r * (size_t)max_taxa + (size_t)rank] = mine;
+        if (lane == 0) rd_ntax[r] = (uint8_t)nset;
+    }
+}
+
 // A wave per read: the set bits of its word masks as DFS indices, ascending, at off[r] of `nodes` (off: the exclusive scan of
 // the counts).  64 words a step, a lane per word; the lanes' positions are the running sum of their popcounts.
 __global__ void __launch_bounds__(256) k_meta_assign_emit(const uint32_t* __restrict__ count, const int64_t* __restrict__ off, int64_t n_reads,
@@ -223,6 +377,8 @@ __global__ void __launch_bounds__(256) k_meta_assign_emit(const uint32_t* __rest
 }
 
 // One call of pmx_meta_assign: the plan of the chunks, then one function per chunk step.
+int assign_words(int64_t n_nodes) { return (int)(((n_nodes + 63) / 64 + 1) & ~(int64_t)1); }
+
 struct AssignStage {
     pmx_ctx* const ctx;
     pmx_meta* const m;
@@ -230,22 +386,32 @@ struct AssignStage {
     const double discard;
     const int64_t n_reads;
     const int words;   // 64-bit words of a row: one bit per node, padded to an even count
+    // taxonomy (pmx_meta_set_taxonomy / pmx_meta_set_ambiguous): none, the best columns, or k_meta_assign_near's rows
+    const int max_taxa;
+    const bool near;    // an ambiguity option is non-zero
+    bool touch = false; // ... and some maximum gives lo == 0: the touch matrix is needed
     std::vector<int64_t> chunk_first;                  // first merged read of every chunk, then n_reads
     // per merged read, on the device
     DevBuf<uint16_t> d_max;
     DevBuf<uint32_t> d_count, d_first, d_last;
-    DevBuf<uint8_t> d_state;
+    DevBuf<uint8_t> d_state, d_ntax;
+    DevBuf<uint32_t> d_tax;
     // per chunk
     DevBuf<uint64_t> d_uniq;
     DevBuf<uint32_t> d_uid, d_nodes;
-    DevBuf<unsigned long long> d_fwd, d_rev, d_wmask;
+    DevBuf<unsigned long long> d_fwd, d_rev, d_touch, d_wmask, d_near;
     DevBuf<uint16_t> d_wmax;
     DevBuf<int64_t> d_off;
     DevBuf<char> tmp;
     std::vector<int64_t> h_off;
 
     AssignStage(pmx_ctx* c, pmx_meta* mm, double d)
-        : ctx(c), m(mm), st(c->stream), discard(d), n_reads(mm->n_reads), words((int)(((mm->n_nodes + 63) / 64 + 1) & ~(int64_t)1)) {}
+        : ctx(c), m(mm), st(c->stream), discard(d), n_reads(mm->n_reads), words(assign_words(mm->n_nodes)), max_taxa(mm->max_taxa),
+          near(mm->max_taxa > 0 && (mm->amb_abs > 0 || mm->amb_ratio > 0.0)) {
+        // lo = max(0, max - max(abs, (int)(max * ratio))) == 0 for some maximum a read of this set can have
+        for (int64_t mx = 1; near && !touch && mx <= mm->longest; ++mx)
+            touch = mx <= std::max<int64_t>(mm->amb_abs, (int64_t)((double)mx * mm->amb_ratio));
+    }
     void plan_chunks();
     void run_chunk(int64_t r0, int64_t r1);
     void finish();
@@ -254,8 +420,8 @@ struct AssignStage {
 // Chunks of consecutive merged reads whose distinct seedmers fit kAssignMatrixBytes and whose word masks fit
 // kAssignReadRowBytes (a read that alone exceeds them is a chunk of its own); PMX_META_ASSIGN_CHUNK forces a size in reads.
 void AssignStage::plan_chunks() {
-    const int64_t cap_rows = std::max<int64_t>(1, (int64_t)(kAssignMatrixBytes / (16 * (size_t)words)));
-    int64_t cap_reads = std::max<int64_t>(1, (int64_t)(kAssignReadRowBytes / (10 * (size_t)words)));
+    const int64_t cap_rows = std::max<int64_t>(1, (int64_t)(kAssignMatrixBytes / ((touch ? 24 : 16) * (size_t)words)));
+    int64_t cap_reads = std::max<int64_t>(1, (int64_t)(kAssignReadRowBytes / ((near ? 18 : 10) * (size_t)words)));
     if (const char* f = opt_str(O_META_ASSIGN_CHUNK)) cap_reads = std::max<int64_t>(1, atoll(f));
     std::vector<int64_t> seen(m->h_uniq.size(), -1);   // the chunk (by its first read) that last counted the seedmer
     chunk_first.assign(1, 0);
@@ -277,6 +443,7 @@ void AssignStage::plan_chunks() {
 }
 
 // Merged reads [r0, r1): their distinct seedmers' rows, the reads' maxima and assigned nodes.
+// With a taxonomy the reads spanning too many taxa become PMX_META_OVER_TAXA before the scan (d_ntax, d_tax: the others' taxa).
 // Leaves: d_max .. d_state of the reads, m->as_off (r0, r1] and m->as_nodes grown by the chunk's lists.
 void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     const int64_t n = r1 - r0, s0 = m->h_read_off[(size_t)r0], s1 = m->h_read_off[(size_t)r1];
@@ -292,14 +459,18 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     const size_t mat = (size_t)n_rows * (size_t)words;
     d_uniq.ensure((size_t)n_rows); d_uid.ensure(uid.size()); d_fwd.ensure(mat); d_rev.ensure(mat);
     d_wmask.ensure((size_t)n * (size_t)words); d_wmax.ensure((size_t)n * (size_t)words); d_off.ensure((size_t)n + 1);
+    if (touch) d_touch.ensure(mat);
+    if (near) d_near.ensure((size_t)n * (size_t)words);
     PMX_HIP(hipMemcpyAsync(d_uniq.p, uniq.data(), sizeof(uint64_t) * (size_t)n_rows, hipMemcpyHostToDevice, st));
     PMX_HIP(hipMemcpyAsync(d_uid.p, uid.data(), sizeof(uint32_t) * uid.size(), hipMemcpyHostToDevice, st));
     timer_begin(ctx, "meta_assign");
     PMX_HIP(hipMemsetAsync(d_fwd.p, 0, sizeof(unsigned long long) * mat, st));
     PMX_HIP(hipMemsetAsync(d_rev.p, 0, sizeof(unsigned long long) * mat, st));
+    if (touch) PMX_HIP(hipMemsetAsync(d_touch.p, 0, sizeof(unsigned long long) * mat, st));
     if (m->n_changes > 0)
         hipLaunchKernelGGL(k_assign_mark_ends, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->ch_key.p, m->ch_pc.p, m->ch_cc.p,
-                           m->ch_node.p, m->n_changes, m->subtree_end.p, m->n_nodes, d_uniq.p, n_rows, words, d_fwd.p, d_rev.p);
+                           m->ch_node.p, m->n_changes, m->subtree_end.p, m->n_nodes, d_uniq.p, n_rows, words, d_fwd.p, d_rev.p,
+                           touch ? d_touch.p : nullptr);
     hipLaunchKernelGGL(k_assign_prefix_xor, dim3(grid_for(2 * n_rows * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words);
     const dim3 grid(grid_for(n * 64, 256, ctx->n_cu * 16)), block(256);
     if (m->longest < 128)
@@ -309,14 +480,30 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
         hipLaunchKernelGGL(k_meta_assign_max<16>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p, words, m->n_nodes,
                            discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
     PMX_HIP(hipGetLastError());
+    if (max_taxa > 0) {   // its own span: "meta_assign" then ends here, the scan below belongs to "meta_assign_taxa"
+        timer_end(ctx, "meta_assign", 1);
+        timer_begin(ctx, "meta_assign_taxa");
+        if (near) {
+            if (m->longest < 128)
+                hipLaunchKernelGGL(k_meta_assign_near<7>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
+                                   touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
+            else
+                hipLaunchKernelGGL(k_meta_assign_near<16>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
+                                   touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
+        }
+        hipLaunchKernelGGL(k_meta_assign_taxa, grid, block, 0, st, near ? d_near.p : d_wmask.p, words, n, m->tx_over.p, m->tx_count.p, m->tx_ids.p, max_taxa,
+                           d_state.p + r0, d_count.p + r0, d_ntax.p + r0, d_tax.p + (size_t)r0 * (size_t)max_taxa);
+        PMX_HIP(hipGetLastError());
+    }
     // (d_count has one entry past the last read, zero: the scan's entry n is the chunk's total; the entry it reads past the
     //  chunk's own counts plays no part in any output)
     PMX_ROCPRIM(tmp, exclusive_scan, d_count.p + r0, d_off.p, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
-    timer_end(ctx, "meta_assign", 1);
+    timer_end(ctx, max_taxa > 0 ? "meta_assign_taxa" : "meta_assign", 1);
     h_off.resize((size_t)n + 1);
     PMX_HIP(hipMemcpyAsync(h_off.data(), d_off.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipStreamSynchronize(st));   // (uniq / uid go out of scope; the total sizes the list)
     timer_sum_add(ctx, "meta_assign");
+    if (max_taxa > 0) timer_sum_add(ctx, "meta_assign_taxa");
     const int64_t total = h_off[(size_t)n], base = (int64_t)m->as_nodes.size();
     for (int64_t i = 1; i <= n; ++i) m->as_off[(size_t)(r0 + i)] = base + h_off[(size_t)i];
     if (total == 0) return;
@@ -340,6 +527,10 @@ void AssignStage::finish() {
     PMX_HIP(hipMemcpyAsync(m->as_state.data(), d_state.p, (size_t)n_reads, hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(first.data(), d_first.p, sizeof(uint32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(last.data(), d_last.p, sizeof(uint32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
+    if (max_taxa > 0) {
+        PMX_HIP(hipMemcpyAsync(m->as_ntax.data(), d_ntax.p, (size_t)n_reads, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(m->as_tax.data(), d_tax.p, sizeof(uint32_t) * (size_t)n_reads * (size_t)max_taxa, hipMemcpyDeviceToHost, st));
+    }
     PMX_HIP(hipStreamSynchronize(st));
     for (int64_t r = 0; r < n_reads; ++r) {
         if (m->as_state[(size_t)r] != PMX_META_ASSIGNED) continue;
@@ -356,6 +547,9 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     if (!ctx || !m || !(discard >= 0.0 && discard <= 1.0)) return PMX_ERR_ARG;   // src/main.cpp:1358-1361
     if (m->dist) return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign runs on one GPU: not with an attached dist");
     if (!m->reads_set) return fail(PMX_ERR_ARG, "pmx_meta_assign: call pmx_meta_set_reads first");
+    if (m->max_taxa > 0 && discard > 0.0 && (m->amb_abs > 0 || m->amb_ratio > 0.0))
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: a discard threshold together with an ambiguity threshold (the reference's records then depend "
+                                         "on the order of a node's seed changes)");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     m->assigned = false;
@@ -370,11 +564,20 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     m->as_lca.assign((size_t)n, UINT32_MAX);
     m->as_off.assign((size_t)n + 1, 0);
     m->as_nodes.clear();
+    m->as_max_taxa = m->max_taxa;
+    m->as_ntax.assign((size_t)n, 0);
+    m->as_tax.assign((size_t)n * (size_t)m->max_taxa, 0);
     if (n > 0) {
         AssignStage S(ctx, m, discard);
         S.plan_chunks();
         S.d_max.alloc((size_t)n); S.d_count.alloc((size_t)n + 1); S.d_first.alloc((size_t)n); S.d_last.alloc((size_t)n); S.d_state.alloc((size_t)n);
+        if (m->max_taxa > 0) {
+            S.d_ntax.alloc((size_t)n); S.d_tax.alloc((size_t)n * (size_t)m->max_taxa);
+            PMX_HIP(hipMemsetAsync(S.d_tax.p, 0, sizeof(uint32_t) * (size_t)n * (size_t)m->max_taxa, ctx->stream));   // (a read fills its first ids only)
+            timer_sum_reset(ctx, "meta_assign_taxa");
+        }
         timer_sum_reset(ctx, "meta_assign");
+        if (auto t = ctx->timers.find("meta_assign_taxa"); t != ctx->timers.end()) t->second.pending = false;   // (no such span without a taxonomy)
         timer_sum_reset(ctx, "meta_assign_emit");
         PMX_HIP(hipMemsetAsync(S.d_count.p, 0, sizeof(uint32_t) * ((size_t)n + 1), ctx->stream));
         for (size_t c = 0; c + 1 < S.chunk_first.size(); ++c) S.run_chunk(S.chunk_first[c], S.chunk_first[c + 1]);
@@ -401,6 +604,83 @@ int pmx_meta_assign_nodes(const pmx_meta* m, int64_t* offsets, uint32_t* nodes, 
     std::copy(m->as_off.begin(), m->as_off.end(), offsets);
     if (nodes) std::copy(m->as_nodes.begin(), m->as_nodes.end(), nodes);
     return PMX_OK;
+}
+
+// S(v) of every node, bottom-up in the unfolded tree (nodes are in pre-order: children after their parents), each capped at
+// max_taxa + 1 ids; then the node table of k_meta_assign_taxa.
+int pmx_meta_set_taxonomy(pmx_meta* m, const int32_t* node_taxon, int64_t n_nodes, int64_t n_taxa, int32_t max_taxa) {
+    if (!m || max_taxa < 0) return PMX_ERR_ARG;
+    if (max_taxa == 0) {
+        m->max_taxa = 0;
+        m->n_taxa = 0;
+        m->h_tx_count.clear(); m->h_tx_ids.clear(); m->h_tx_over.clear();
+        return PMX_OK;
+    }
+    if (!node_taxon || n_nodes != m->n_nodes || n_taxa < 0) return PMX_ERR_ARG;
+    if (max_taxa > kAssignMaxTaxa) return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_set_taxonomy: at most 16 taxa a read (max_taxa)");
+    for (int64_t v = 0; v < n_nodes; ++v)
+        if (node_taxon[v] < -1 || node_taxon[v] >= n_taxa) return fail(PMX_ERR_ARG, "pmx_meta_set_taxonomy: a taxon outside [0, n_taxa)");
+    PMX_TRY
+    PMX_HIP(hipSetDevice(m->ctx->device));
+    const size_t M = (size_t)max_taxa, n = (size_t)n_nodes;
+    std::vector<std::vector<uint32_t>> S(n);   // ascending; max_taxa + 1 ids = over
+    auto add = [&](std::vector<uint32_t>& s, uint32_t t) {
+        const auto at = std::lower_bound(s.begin(), s.end(), t);
+        if ((at == s.end() || *at != t) && s.size() <= M) s.insert(at, t);
+    };
+    for (size_t v = n; v-- > 0;) {
+        if (node_taxon[v] >= 0) add(S[v], (uint32_t)node_taxon[v]);
+        if (v > 0) {
+            std::vector<uint32_t>& up = S[m->h_parent[v]];
+            for (uint32_t t : S[v]) add(up, t);
+        }
+    }
+    const size_t words = (size_t)assign_words(n_nodes);
+    m->h_tx_count.assign(n, 0);
+    m->h_tx_ids.assign(n * M, 0);
+    m->h_tx_over.assign(words, 0ULL);
+    for (size_t v = 0; v < n; ++v) {
+        if (S[v].size() > M) { m->h_tx_over[v >> 6] |= 1ULL << (v & 63); continue; }
+        m->h_tx_count[v] = (uint8_t)S[v].size();
+        std::copy(S[v].begin(), S[v].end(), m->h_tx_ids.begin() + v * M);
+    }
+    const hipStream_t st = m->ctx->stream;
+    m->tx_count.ensure(n); m->tx_ids.ensure(n * M); m->tx_over.ensure(words);
+    PMX_HIP(hipMemcpyAsync(m->tx_count.p, m->h_tx_count.data(), n, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(m->tx_ids.p, m->h_tx_ids.data(), sizeof(uint32_t) * n * M, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipMemcpyAsync(m->tx_over.p, m->h_tx_over.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    m->max_taxa = max_taxa;
+    m->n_taxa = n_taxa;
+    return PMX_OK;
+    PMX_CATCH
+}
+
+int pmx_meta_set_ambiguous(pmx_meta* m, int32_t abs, double ratio) {
+    if (!m || abs < 0 || !(ratio >= 0.0)) return PMX_ERR_ARG;
+    m->amb_abs = abs;
+    m->amb_ratio = std::min(ratio, 1.0);   // (from 1 on amb >= max, lo = 0: all the same)
+    return PMX_OK;
+}
+
+int pmx_meta_assign_taxa(const pmx_meta* m, uint32_t* n_taxa, uint32_t* taxa, int64_t cap) {
+    if (!m || !m->assigned || cap < m->n_reads) return PMX_ERR_ARG;
+    if (n_taxa) std::copy(m->as_ntax.begin(), m->as_ntax.end(), n_taxa);
+    if (taxa) std::copy(m->as_tax.begin(), m->as_tax.end(), taxa);
+    return PMX_OK;
+}
+
+int32_t pmx_meta_assign_max_taxa(const pmx_meta* m) { return m && m->assigned ? m->as_max_taxa : 0; }
+
+int64_t pmx_meta_node_taxa(const pmx_meta* m, int64_t v, uint32_t* ids, int64_t cap) {
+    if (!m || m->max_taxa == 0 || v < 0 || v >= m->n_nodes) return -2;
+    if ((m->h_tx_over[(size_t)v >> 6] >> (v & 63)) & 1ULL) return -1;
+    const int64_t c = m->h_tx_count[(size_t)v];
+    if (ids) {
+        if (cap < c) return -2;
+        std::copy_n(m->h_tx_ids.begin() + (size_t)v * (size_t)m->max_taxa, (size_t)c, ids);
+    }
+    return c;
 }
 
 int64_t pmx_meta_num_raw_reads(const pmx_meta* m) { return m ? m->n_raw_reads : 0; }

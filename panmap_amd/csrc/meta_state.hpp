@@ -88,4 +88,18 @@ struct pmx_meta {
     std::vector<uint32_t> as_lca, as_count;
     std::vector<int64_t> as_off;            // n_reads + 1 offsets into as_nodes
     std::vector<uint32_t> as_nodes;         // the assigned nodes of every read, ascending DFS indices
+    int32_t as_max_taxa = 0;                // max_taxa of that call: as_tax holds as_max_taxa ids a read, as_ntax of them set
+    std::vector<uint8_t> as_ntax;
+    std::vector<uint32_t> as_tax;
+    // taxonomy (pmx_meta_set_taxonomy; max_taxa 0 = none) and the ambiguity thresholds (pmx_meta_set_ambiguous).  The node table:
+    // the taxa S(v) of every node's subtree, ascending, max_taxa slots a node; h_tx_over: bit v = |S(v)| > max_taxa (then no ids)
+    int32_t max_taxa = 0, amb_abs = 0;
+    int64_t n_taxa = 0;
+    double amb_ratio = 0.0;
+    std::vector<uint8_t> h_tx_count;
+    std::vector<uint32_t> h_tx_ids;
+    std::vector<unsigned long long> h_tx_over;
+    pmx::DevBuf<uint8_t> tx_count;
+    pmx::DevBuf<uint32_t> tx_ids;
+    pmx::DevBuf<unsigned long long> tx_over;
 };

@@ -2,6 +2,7 @@
 Host-side mirror of the reference's flow: reads -> Meta.set_reads -> Meta.score (candidates + parsimony scores) -> Meta.em
 -> the `<prefix>.mgsr.abundance.out` text (node[,merged nodes...]<TAB>proportion with five decimals, by proportion)."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -12,7 +13,7 @@ from .api import Context, Index, Panman, concat_reads
 
 ORIENTED = 0x100     # PMX_INDEX_ORIENTED
 ORIENT_XOR = 0x9e3779b97f4a7c15
-UNMAPPED, DISCARDED, ASSIGNED = 0, 1, 2    # PMX_META_*: the state of a read after Meta.assign
+UNMAPPED, DISCARDED, ASSIGNED, OVER_TAXA = 0, 1, 2, 3    # PMX_META_*: the state of a read after Meta.assign
 
 
 class AssignResult:
@@ -20,10 +21,13 @@ class AssignResult:
     a read dropped by --dust or without seedmers is UNMAPPED), `max` (its best score over all nodes), `lca` (the head of the
     LCA of its assigned nodes, -1 unless assigned), `merged` (its merged read, -1 = dropped).  `heads` folds identical
     nodes (Index.node_heads of the oriented index).  The assigned reads, in input order, are the records of
-    `<prefix>.mgsr.assignedReads.fastq`: `fastq_index[read]` is a read's position there (-1 unless assigned)."""
+    `<prefix>.mgsr.assignedReads.fastq`: `fastq_index[read]` is a read's position there (-1 unless assigned).
+    With a taxonomy (Meta.set_taxonomy) a read that spans too many taxa is OVER_TAXA: no nodes, no LCA, not in the FASTQ;
+    `read_taxa` ((n_taxa, taxa[merged reads][max_taxa])) and `node_sets` (node -> S(node), None when over) feed taxa_of / node_taxa."""
 
-    def __init__(self, merged, state, mx, lca, offsets, nodes, heads):
+    def __init__(self, merged, state, mx, lca, offsets, nodes, heads, read_taxa=None, node_sets=None):
         self.merged, self.heads, self._off, self._nodes = merged, heads, offsets, nodes
+        self._read_taxa, self._node_sets = read_taxa, node_sets
         has = merged >= 0
         at = np.where(has, merged, 0)
         self.state = np.where(has, state[at], UNMAPPED).astype(np.uint8) if len(state) else np.zeros(len(merged), np.uint8)
@@ -39,6 +43,19 @@ class AssignResult:
         empty unless the read is assigned"""
         r = int(self.merged[read])
         return self._nodes[self._off[r]:self._off[r + 1]] if r >= 0 else self._nodes[:0]
+
+    def taxa_of(self, read: int) -> np.ndarray:
+        """the taxa of a raw read (the union over its qualifying nodes' subtrees, ascending); empty unless the read is assigned
+        and a taxonomy was set"""
+        r = int(self.merged[read])
+        if r < 0 or self._read_taxa is None:
+            return np.zeros(0, np.uint32)
+        return self._read_taxa[1][r, :self._read_taxa[0][r]]
+
+    def node_taxa(self, v: int):
+        """S(v): the taxa in the subtree of node v (identical nodes not folded), ascending; None when they exceed max_taxa;
+        empty without a taxonomy"""
+        return np.zeros(0, np.uint32) if self._node_sets is None else self._node_sets(int(v))
 
     def by_node(self):
         """{head: sorted FASTQ indices of the reads assigned to the head or to a node folded into it}"""
@@ -106,8 +123,30 @@ class Meta:
         check(lib.pmx_meta_em(self.ctx._h, self._h, C.byref(mp)), "pmx_meta_em")
         return self.haplotypes()
 
-    def assign(self, discard: float = 0.0) -> AssignResult:
-        """--filter-and-assign on the reads of the last set_reads: every read against every node (pmx_meta_assign)"""
+    def set_taxonomy(self, node_taxon=None, max_taxa: int = 1, n_taxa=None):
+        """--taxonomic-metadata / --maximum-taxon-number for the assign calls that follow: `node_taxon[v]` is the taxon of the
+        node with DFS index v of the oriented index, -1 = none (load_taxonomy makes it); a read whose qualifying nodes span
+        more than `max_taxa` taxa becomes OVER_TAXA.  max_taxa=0 clears the taxonomy."""
+        if max_taxa == 0:
+            check(lib.pmx_meta_set_taxonomy(self._h, None, 0, 0, 0), "pmx_meta_set_taxonomy")
+            return
+        t = np.ascontiguousarray(node_taxon, np.int32)
+        n_taxa = int(t.max()) + 1 if n_taxa is None and len(t) else int(n_taxa or 0)
+        check(lib.pmx_meta_set_taxonomy(self._h, t.ctypes.data, len(t), n_taxa, int(max_taxa)), "pmx_meta_set_taxonomy")
+
+    def node_taxa(self, v: int):
+        """S(v) of the taxonomy that is set (ascending ids), None when it exceeds max_taxa"""
+        ids = np.zeros(16, np.uint32)
+        n = int(lib.pmx_meta_node_taxa(self._h, int(v), ids.ctypes.data, len(ids)))
+        if n < -1:
+            raise ValueError("node_taxa: no taxonomy is set, or no such node")
+        return None if n < 0 else ids[:n].copy()
+
+    def assign(self, discard: float = 0.0, ambiguous: int = 0, ambiguous_ratio: float = 0.0) -> AssignResult:
+        """--filter-and-assign on the reads of the last set_reads: every read against every node (pmx_meta_assign).
+        `ambiguous` / `ambiguous_ratio` (--ambiguous-score-threshold, -ratio) widen the nodes whose taxa count for a read from
+        its best ones to those within max(ambiguous, int(max * ratio)) of its best score; they act through a taxonomy only."""
+        check(lib.pmx_meta_set_ambiguous(self._h, int(ambiguous), float(ambiguous_ratio)), "pmx_meta_set_ambiguous")
         check(lib.pmx_meta_assign(self.ctx._h, self._h, float(discard)), "pmx_meta_assign")
         n = self.n_reads
         state, mx = np.zeros(n, np.uint8), np.zeros(n, np.uint16)
@@ -116,7 +155,14 @@ class Meta:
         off, nodes = np.zeros(n + 1, np.int64), np.zeros(max(int(lib.pmx_meta_assign_num_nodes(self._h)), 1), np.uint32)
         check(lib.pmx_meta_assign_nodes(self._h, off.ctypes.data, nodes.ctypes.data, len(nodes)), "pmx_meta_assign_nodes")
         assert np.array_equal(np.diff(off), cnt)
-        return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads())
+        read_taxa, node_sets = None, None
+        max_taxa = int(lib.pmx_meta_assign_max_taxa(self._h))
+        if max_taxa > 0:
+            nt, tx = np.zeros(n, np.uint32), np.zeros((n, max_taxa), np.uint32)
+            check(lib.pmx_meta_assign_taxa(self._h, nt.ctypes.data, tx.ctypes.data, n), "pmx_meta_assign_taxa")
+            sets = [self.node_taxa(v) for v in range(self.index_oriented.info.n_nodes)]   # (copied: the result outlives a later set_taxonomy)
+            read_taxa, node_sets = (nt, tx), sets.__getitem__
+        return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads(), read_taxa, node_sets)
 
     def raw_to_merged(self) -> np.ndarray:
         """per read of the last set_reads (input order): its merged read, -1 when --dust dropped it or it has no seedmers"""
@@ -201,10 +247,26 @@ def format_abundance(haplotypes, node_id) -> str:
     return "\n".join(lines) + ("\n" if lines else "")
 
 
-def format_assigned(result: AssignResult, node_id, heads=None):
+def load_taxonomy(path: str, rank: str, node_ids):
+    """--taxonomic-metadata / --taxonomic-rank (pmx_taxonomy_load; loadTaxonomicMetadata, src/mgsr.cpp:198-256): (taxon names
+    in order of first appearance, int32 array with the taxon of every identifier of `node_ids`, -1 = none).  With node_ids
+    = [index.node_id(v) for v in range(n_nodes)] the array is Meta.set_taxonomy's node_taxon."""
+    h = C.c_void_p()
+    check(lib.pmx_taxonomy_load(os.fsencode(path), rank.encode(), C.byref(h)), "pmx_taxonomy_load")
+    try:
+        names = [lib.pmx_taxonomy_taxon_name(h, i).decode() for i in range(int(lib.pmx_taxonomy_num_taxa(h)))]
+        taxon = np.array([lib.pmx_taxonomy_lookup(h, x.encode()) for x in node_ids], np.int32).reshape(-1)
+    finally:
+        lib.pmx_taxonomy_free(h)
+    return names, taxon
+
+
+def format_assigned(result: AssignResult, node_id, heads=None, taxon_names=None):
     """(`<prefix>.mgsr.assignedReads.out`, `<prefix>.mgsr.assignedReadsLCANode.out`) (writeAssignedReadsOut,
-    src/main.cpp:522-558): one line per head node that has reads, `head[,folded nodes]<TAB>.<TAB>count<TAB>i,j,k` -- the taxon
-    column is always `.`, the indices are positions in the assigned-reads FASTQ, ascending.  Canonical order (the
+    src/main.cpp:522-558): one line per head node that has reads, `head[,folded nodes]<TAB>taxa<TAB>count<TAB>i,j,k` -- the
+    indices are positions in the assigned-reads FASTQ, ascending.  The taxon column is `.` without `taxon_names`; with them
+    (a result of a Meta with a taxonomy) the names of the head's S(head) by ascending taxon index joined with `,` (the
+    reference iterates a hash set), `.` when the set is empty or over max_taxa.  Canonical order (the
     reference's comes from hash-map iteration): lines by ascending DFS index of the head, ids on a line the head, then the
     nodes folded into it by ascending DFS index."""
     heads = np.asarray(result.heads if heads is None else heads)
@@ -216,6 +278,8 @@ def format_assigned(result: AssignResult, node_id, heads=None):
         lines = []
         for h in sorted(groups):
             ids = ",".join(node_id(x) for x in [h] + members.get(h, []))
-            lines.append("%s\t.\t%d\t%s" % (ids, len(groups[h]), ",".join(str(i) for i in sorted(groups[h]))))
+            taxa = result.node_taxa(h) if taxon_names is not None else None
+            col = ",".join(taxon_names[t] for t in taxa) if taxa is not None and len(taxa) else "."
+            lines.append("%s\t%s\t%d\t%s" % (ids, col, len(groups[h]), ",".join(str(i) for i in sorted(groups[h]))))
         return "\n".join(lines) + ("\n" if lines else "")
     return text(result.by_node()), text(result.by_lca())

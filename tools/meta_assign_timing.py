@@ -3,6 +3,10 @@
 the only other route to the same answer, pmx_meta_score with EVERY node as a candidate ("meta_score": bit matrices + score
 kernel; the download of the score matrix and a host argmax are not counted).  Each is run twice, the second run is reported
 (the first one allocates inside the span).
+With `taxonomy` as the last argument instead: the taxonomy filter.  Every node gets a taxon by the labelling of tests/taxa_checks.py
+with 16 taxa (a leaf v with v % 7 != 3 and an internal node with v % 11 == 5 get (16 v) // n), at most one taxon a read.  Three
+calls, each run twice: without a taxonomy, with it, and with it and --ambiguous-score-threshold-ratio 0.1; "meta_assign_taxa" is
+the taxonomy pass (its kernels and the scan of the node counts, which "meta_assign" holds without a taxonomy).
   meta_assign_timing.py rsv  [n_reads]   rsv_4K, reads at step 1 over two of its genomes (default 20,000)
   meta_assign_timing.py sars [n_reads]   SARS-CoV-2 20k tree, the 5-haplotype mixture of test_config5_sars_five_haplotypes (default 200,000)"""
 import json
@@ -48,9 +52,30 @@ def sars_reads(pmx, pm, n):
     return np.concatenate(parts), np.concatenate(offs)
 
 
+def label(parent, n_taxa=16):
+    n = len(parent)
+    internal = np.zeros(n, bool)
+    internal[np.asarray(parent[1:], np.int64)] = True
+    v = np.arange(n)
+    return np.where(np.where(internal, v % 11 == 5, v % 7 != 3), (v * n_taxa) // n, -1).astype(np.int32)
+
+
+def taxonomy_mode(meta, ms, out):
+    taxon = label(meta.index_oriented.arrays()["parent"])
+    for name, with_taxonomy, ratio in (("plain", False, 0.0), ("taxa", True, 0.0), ("taxa_ratio_0.1", True, 0.1)):
+        meta.set_taxonomy(taxon, 1) if with_taxonomy else meta.set_taxonomy(max_taxa=0)
+        for rep in range(2):
+            res = meta.assign(0.0, ambiguous_ratio=ratio)
+            out[name] = dict(assign_ms=ms("meta_assign"), taxa_ms=ms("meta_assign_taxa"), emit_ms=ms("meta_assign_emit"),
+                             assigned=int((res.state == 2).sum()), over=int((res.state == 3).sum()))
+
+
 def main():
     import panmap_amd as pmx
     from panmap_amd._lib import lib
+    taxonomy = sys.argv[-1] == "taxonomy"
+    if taxonomy:
+        sys.argv.pop()
     which = sys.argv[1] if len(sys.argv) > 1 else "rsv"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else (20000 if which == "rsv" else 200000)
     pm = pmx.Panman(os.path.join(GOLDEN, "rsv_4K.panman" if which == "rsv" else "sars_20000_twilight_dipper.panman"))
@@ -65,6 +90,10 @@ def main():
     words = ((n_nodes + 63) // 64 + 1) & ~1
     out["distinct_seedmers"] = int(len(np.unique(h)))
     out["bit_matrix_bytes"] = 2 * out["distinct_seedmers"] * words * 8     # (of all reads: split over chunks of at most 2 GiB)
+    if taxonomy:
+        taxonomy_mode(meta, ms, out)
+        print(json.dumps(out))
+        return
     for rep in range(2):
         t0 = time.perf_counter()
         res = meta.assign(0.0)
