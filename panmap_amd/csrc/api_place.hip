@@ -1307,8 +1307,8 @@ struct ScoreStage {
     // read_filters
     int64_t n_kept = 0, min_support = 0;
     unsigned long long h_stats[4] = {0, 0, 0, 0};
-    // score_terms: the five term arrays, n_changes doubles each, in pl->terms
-    double *t_mag = nullptr, *t_raw = nullptr, *t_cos = nullptr, *t_wc = nullptr, *t_lc = nullptr;
+    // score_terms: the five term arrays, n_changes doubles each, in pl->terms, and pl->term_meta
+    TermArrays ta = {};
     bool persistent = false;      // the scoring form just launched leaves a status word (k_score_chains / k_score_tree)
     // fetch (the node scores go to pl->h_scores)
     double h_scal[3] = {0, 0, 0};
@@ -1407,11 +1407,12 @@ void ScoreStage::score_terms() {
     const int64_t n_ch = pl->n_changes;
     pl->terms.ensure((size_t)std::max<int64_t>(n_ch, 1) * 5);
     pl->term_meta.ensure((size_t)std::max<int64_t>(n_ch, 1));
-    t_mag = pl->terms.p;
-    t_raw = t_mag + n_ch; t_cos = t_mag + 2 * n_ch; t_wc = t_mag + 3 * n_ch; t_lc = t_mag + 4 * n_ch;
+    double* const t = pl->terms.p;
+    ta = {t, t + n_ch, t + 2 * n_ch, t + 3 * n_ch, t + 4 * n_ch, pl->term_meta.p};
     if (n_ch > 0)
         hipLaunchKernelGGL(k_score_terms, dim3(grid_for(n_ch, 256, G)), dim3(256), 0, st, pl->ch_hash.p, pl->ch_par.p, pl->ch_child.p, n_ch,
-                           pl->tkeys.p, pl->tvals.p, pl->tcap - 1, n_kept > 0 ? 1 : 0, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p);
+                           pl->tkeys.p, pl->tvals.p, pl->tcap - 1, n_kept > 0 ? 1 : 0, t, t + n_ch, t + 2 * n_ch, t + 3 * n_ch, t + 4 * n_ch,
+                           pl->term_meta.p);
 }
 
 // the per-node flags of the persistent kernels: a node is done when its flag holds the epoch of this call
@@ -1433,17 +1434,16 @@ void ScoreStage::launch_chains() {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_chains + 3) / 4));
     pl->last_grid_waves = (int64_t)grid * 4;
     hipLaunchKernelGGL(k_score_chains, dim3(grid), dim3(256), 0, st, pl->chain_off.p, pl->n_chains, pl->chain_nodes.p, pl->chain_beg.p,
-                       pl->chain_end.p, pl->parent.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p,
-                       pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
+                       pl->chain_end.p, pl->parent.p, ta, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
+                       pl->tree_done.p + pl->n_nodes);
 }
 
 // per-node flags in BFS order (k_score_tree; kept for comparison), resident like the chains kernel
 void ScoreStage::launch_tree() {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_nodes + 3) / 4));
     pl->last_grid_waves = (int64_t)grid * 4;
-    hipLaunchKernelGGL(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, t_mag, t_raw,
-                       t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
-                       pl->tree_done.p + pl->n_nodes);
+    hipLaunchKernelGGL(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, ta,
+                       pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
 }
 
 // one launch per BFS level (k_score_level); needs no co-residency
@@ -1453,14 +1453,14 @@ void ScoreStage::launch_levels() {
         const int64_t beg = pl->level_off[lv], cnt = pl->level_off[lv + 1] - beg;
         if (cnt <= 0) continue;
         hipLaunchKernelGGL(k_score_level, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, pl->level_nodes.p + beg, cnt, pl->parent.p,
-                           pl->offsets.p, t_mag, t_raw, t_cos, t_wc, t_lc, pl->term_meta.p, pl->metrics5.p, pl->counts2.p);
+                           pl->offsets.p, ta, pl->metrics5.p, pl->counts2.p);
     }
 }
 
 // The level launches are a fixed, launch-bound chain (122 dependent launches for the SARS tree, none of
 // whose arguments change between calls): captured once into a HIP graph and replayed.
 void ScoreStage::launch_levels_graph() {
-    const void* sig[3] = {(const void*)t_mag, (const void*)pl->metrics5.p, (const void*)pl->term_meta.p};
+    const void* sig[3] = {(const void*)ta.mag, (const void*)pl->metrics5.p, (const void*)pl->term_meta.p};
     if (!pl->level_graph_exec || pl->level_graph_sig[0] != sig[0] || pl->level_graph_sig[1] != sig[1] || pl->level_graph_sig[2] != sig[2]) {
         if (pl->level_graph_exec) { (void)hipGraphExecDestroy(pl->level_graph_exec); pl->level_graph_exec = nullptr; }
         hipGraph_t graph = nullptr;

@@ -1,4 +1,5 @@
-// Declarations shared between place_kernels.hip and the host orchestration in api_device.hip.
+// Declarations shared between the kernel files place_kernels.hip (read packing, seeding, histogram) and
+// place_kernels_score.hip (scoring pass) and the host orchestration in api_place.hip.
 #pragma once
 #include <stdint.h>
 
@@ -18,6 +19,13 @@ namespace pmx {
 struct SeedParams {
     int k, s, t, l, open;
     int trim_start, trim_end;
+};
+
+// the per-change terms of the scoring pass, one array per accumulator plus the flags byte: written by k_score_terms,
+// read by the three node-scoring kernels (n_changes entries each)
+struct TermArrays {
+    const double *mag, *raw, *cos, *wc, *lc;
+    const uint8_t* meta;
 };
 
 __global__ void k_pack_reads(const uint8_t* ascii, const int64_t* off, const int64_t* woff, int64_t n_reads, int64_t n_words,
@@ -68,15 +76,12 @@ __global__ void k_wc_denominator(const uint64_t* ch_hash, const int16_t* ch_chil
 __global__ void k_score_terms(const uint64_t* ch_hash, const int16_t* ch_par, const int16_t* ch_child, int64_t n_changes,
                               const uint64_t* tkeys, const double* tvals, uint64_t mask, int has_kept, double* t_mag, double* t_raw,
                               double* t_cos, double* t_wc, double* t_lc, uint8_t* t_meta);
-__global__ void k_score_level(const uint32_t* level_nodes, int64_t n_level, const uint32_t* parent, const uint64_t* offsets,
-                              const double* t_mag, const double* t_raw, const double* t_cos, const double* t_wc, const double* t_lc,
-                              const uint8_t* t_meta, double* metrics5, int64_t* counts2);
-__global__ void k_score_tree(const uint32_t* order, int64_t n_nodes, const uint32_t* parent, const uint64_t* offsets, const double* t_mag,
-                             const double* t_raw, const double* t_cos, const double* t_wc, const double* t_lc, const uint8_t* t_meta,
+__global__ void k_score_level(const uint32_t* level_nodes, int64_t n_level, const uint32_t* parent, const uint64_t* offsets, TermArrays ta,
+                              double* metrics5, int64_t* counts2);
+__global__ void k_score_tree(const uint32_t* order, int64_t n_nodes, const uint32_t* parent, const uint64_t* offsets, TermArrays ta,
                              double* metrics5, int64_t* counts2, uint32_t* done, uint32_t epoch, uint32_t* status);
 __global__ void k_score_chains(const uint32_t* chain_off, int64_t n_chains, const uint32_t* chain_nodes, const uint64_t* chain_beg,
-                               const uint64_t* chain_end, const uint32_t* parent, const double* t_mag, const double* t_raw, const double* t_cos,
-                               const double* t_wc, const double* t_lc, const uint8_t* t_meta, double* metrics5, int64_t* counts2,
+                               const uint64_t* chain_end, const uint32_t* parent, TermArrays ta, double* metrics5, int64_t* counts2,
                                uint32_t* done, uint32_t epoch, uint32_t* status);
 __global__ void k_score_getters(const double* metrics5, const int64_t* counts2, int64_t n_nodes, const double* scalars, int64_t n_kept,
                                 double* scores5, const uint32_t* order, double* scores_bfs);
