@@ -629,6 +629,20 @@ void pmx_taxonomy_free(pmx_taxonomy *t);
 int64_t pmx_taxonomy_num_taxa(const pmx_taxonomy *t);
 const char *pmx_taxonomy_taxon_name(const pmx_taxonomy *t, int64_t taxon);
 int64_t pmx_taxonomy_lookup(const pmx_taxonomy *t, const char *identifier);
+/* --breadth-ratio of --filter-and-assign (calculateBreadthRatio, src/mgsr.cpp:6518-6584): whether the reads assigned to a node
+ * cover its genome.  pmx_meta_set_breadth(on): the pmx_meta_assign calls that follow also compute it (default off: nothing of it
+ * runs or is allocated).  pmx_meta_breadth: per DFS index (cap_nodes >= the index's nodes; any pointer may be NULL), over the
+ * assignment of the last pmx_meta_assign (reads that are PMX_META_ASSIGNED; a merged read counts with its multiplicity):
+ *   total_ref_seeds  distinct seedmer hashes of the node's genome, either orientation (node->totalRefSeeds, mgsr.cpp:590-610)
+ *   observed         distinct hashes among them that some read assigned to the node carries (ObservedBreadthCount)
+ *   depth            sum over the reads assigned to the node of multiplicity x (distinct hashes of the read that the node holds)
+ * A node folded into its head (pmx_index_node_heads) carries its head's numbers.  The file's four ratios follow on the host:
+ * obs / total and depth / total (0 when total is 0), 1 - exp(-mean depth) (0 when that is 0), observed over expected ratio (0 when
+ * expected is 0).  PMX_ERR_ARG when the last pmx_meta_assign ran without breadth (pmx_meta_set_reads empties it, like the other
+ * results).  pmx_meta_assign with breadth is PMX_ERR_UNSUPPORTED when one bit per (distinct seedmer of the reads, node) exceeds
+ * 8 GiB: nothing is approximated. */
+int pmx_meta_set_breadth(pmx_meta *m, int on);
+int pmx_meta_breadth(const pmx_meta *m, uint64_t *total_ref_seeds, uint64_t *observed, uint64_t *depth, int64_t cap_nodes);
 /* the reads of the last pmx_meta_set_reads in input order -> their merged read, -1 for a read dropped by --dust or without
  * seedmers (PMX_ERR_UNSUPPORTED with an attached dist: the merged reads are then the whole sample's) */
 int64_t pmx_meta_num_raw_reads(const pmx_meta *m);
@@ -790,7 +804,8 @@ int64_t pmx_options_describe(char *buf, int64_t cap);
    tier's second form, k_align_compact*_multi) or a span of --meta ("meta_score" = the bit matrices and the score kernel of
    pmx_meta_score; "meta_assign" = the device work of pmx_meta_assign up to the scan of the node counts, "meta_assign_emit" = its
    list kernel, both summed over the call's chunks; with a taxonomy "meta_assign" ends before the taxonomy kernels and
-   "meta_assign_taxa" holds them and that scan); < 0: no such span in the last call */
+   "meta_assign_taxa" holds them and that scan; with pmx_meta_set_breadth "meta_breadth" = the breadth kernels, summed likewise, and "meta_breadth_count" = the column
+   count kernel among them); < 0: no such span in the last call */
 double pmx_last_kernel_ms(pmx_ctx *ctx, const char *name);
 
 #ifdef __cplusplus

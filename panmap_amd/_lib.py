@@ -216,6 +216,8 @@ SIGNATURES = {
     "pmx_meta_assign_reads": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64]),
     "pmx_meta_assign_num_nodes": (_i64, [_vp]),
     "pmx_meta_assign_nodes": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_meta_set_breadth": (_i32, [_vp, _i32]),
+    "pmx_meta_breadth": (_i32, [_vp, _vp, _vp, _vp, _i64]),
     "pmx_meta_set_taxonomy": (_i32, [_vp, _vp, _i64, _i64, _i32]),
     "pmx_meta_set_ambiguous": (_i32, [_vp, _i32, C.c_double]),
     "pmx_meta_assign_taxa": (_i32, [_vp, _vp, _vp, _i64]),

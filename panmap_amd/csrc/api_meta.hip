@@ -1098,6 +1098,7 @@ int pmx_meta_create(pmx_ctx* ctx, const pmx_index* idx_std, const pmx_index* idx
     std::unique_ptr<pmx_meta> m(new pmx_meta());
     m->ctx = ctx;
     m->idx_std = idx_std;
+    m->idx_oriented = idx_oriented;
     m->params = O->params;
     const int64_t n = (int64_t)O->parent.size(), c = (int64_t)O->hash.size();
     m->n_nodes = n;

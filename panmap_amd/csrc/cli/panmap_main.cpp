@@ -18,6 +18,7 @@
 
 #include <cerrno>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -49,6 +50,7 @@ struct Config {
     int maximum_taxon_number = 1, ambiguous_score = 0;
     double ambiguous_ratio = 0.0;
     std::vector<std::string> taxonomy_options;
+    bool breadth_ratio = false;       // --breadth-ratio: <prefix>.mgsr.breadths.out (src/main.cpp:957-1015)
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
     int em_max_iterations = 1000, em_max_rounds = 5;
@@ -85,6 +87,8 @@ void usage() {
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
           "      --meta --filter-and-assign   assign every read to the nodes it scores best on -> <prefix>.mgsr.assignedReads.fastq,\n"
           "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU)\n"
+          "      --breadth-ratio        ... and write <prefix>.mgsr.breadths.out: per node the distinct seeds of its genome, how many of them\n"
+          "                             the reads assigned to it hit, their depth, and the observed / expected breadth ratios (a switch)\n"
           "      --taxonomic-metadata TSV     ... and drop the reads whose best-scoring nodes span more than N taxa: node id in the first\n"
           "                             column, the taxa of --taxonomic-rank NAME (default Family) in the column of that name\n"
           "      --maximum-taxon-number N (default 1, at most 16)   --ambiguous-score-threshold N / --ambiguous-score-threshold-ratio F:\n"
@@ -154,8 +158,16 @@ Config parse(int argc, char** argv) {
         else if (a == "--maximum-taxon-number") { c.maximum_taxon_number = atoi(v().c_str()); c.taxonomy_options.push_back(a); }
         else if (a == "--ambiguous-score-threshold") { c.ambiguous_score = atoi(v().c_str()); c.taxonomy_options.push_back(a); }
         else if (a == "--ambiguous-score-threshold-ratio") { c.ambiguous_ratio = atof(v().c_str()); c.taxonomy_options.push_back(a); }
-        else if (a == "--breadth-ratio" || a == "--jplace" || a == "--mask-read-ends")
-            die("option " + a + " is not accepted: --filter-and-assign is built without breadth ratios, jplace output and read-end masking");
+        else if (a == "--breadth-ratio") {   // po::bool_switch in the reference: a number after it would silently become a reads file
+            const std::string next = has_val ? val : i + 1 < argc ? std::string(argv[i + 1]) : std::string();
+            char* end = nullptr;
+            if (!next.empty()) (void)strtod(next.c_str(), &end);
+            if (has_val || (end && *end == '\0'))
+                die("option --breadth-ratio is not accepted with a value (" + next + "): it is a switch, as in the reference");
+            c.breadth_ratio = true;
+        }
+        else if (a == "--jplace" || a == "--mask-read-ends")
+            die("option " + a + " is not accepted: --filter-and-assign is built without jplace output and read-end masking");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
         else if (a == "--em-convergence-threshold") c.em_convergence = atof(v().c_str());
         else if (a == "--em-delta-threshold") c.em_delta = atof(v().c_str());
@@ -849,6 +861,7 @@ void write_assigned(const Config& c, Run& run, const Reads& reads, const pmx_tax
         check(pmx_meta_set_taxonomy(m, node_taxon.data(), (int64_t)node_taxon.size(), pmx_taxonomy_num_taxa(taxonomy), c.maximum_taxon_number), "--taxonomic-metadata");
         check(pmx_meta_set_ambiguous(m, c.ambiguous_score, c.ambiguous_ratio), "--ambiguous-score-threshold");
     }
+    check(pmx_meta_set_breadth(m, c.breadth_ratio ? 1 : 0), "--breadth-ratio");
     check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
     const int64_t n_merged = pmx_meta_num_reads(m), n_nodes_total = pmx_meta_assign_num_nodes(m);
     std::vector<uint8_t> state((size_t)std::max<int64_t>(n_merged, 1));
@@ -916,6 +929,28 @@ void write_assigned(const Config& c, Run& run, const Reads& reads, const pmx_tax
     };
     write_out(c.output + ".mgsr.assignedReads.out", by_node);
     write_out(c.output + ".mgsr.assignedReadsLCANode.out", by_lca);
+    if (c.breadth_ratio) {
+        // src/main.cpp:992-1013, calculateBreadthRatio (src/mgsr.cpp:6518-6584): a line per head node, with or without reads, in the
+        // pre-order of the collapsed tree (= ascending DFS index of the heads); the header alone when no read was assigned
+        const std::string path = c.output + ".mgsr.breadths.out";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) die("cannot write " + path);
+        fputs("NodeId\tTotalRefSeeds\tObservedBreadthCount\tObservedBreadthRatio\tTotalDepth\tMeanDepth\tExpectedBreadthRatio\tObservedToExpectedBreadthRatio\n", f);
+        std::vector<uint64_t> total((size_t)info.n_nodes), observed((size_t)info.n_nodes), depth((size_t)info.n_nodes);
+        check(pmx_meta_breadth(m, total.data(), observed.data(), depth.data(), info.n_nodes), "the breadth of the nodes");
+        for (uint32_t h = 0; n_written > 0 && h < (uint32_t)info.n_nodes; ++h) {
+            if (head[h] != h) continue;
+            std::string ids = pmx_index_node_id(run.idx, h);
+            for (uint32_t v : folded[h]) { ids += ","; ids += pmx_index_node_id(run.idx, v); }
+            const double t = (double)total[h];
+            const double ratio = total[h] > 0 ? (double)observed[h] / t : 0.0, mean = total[h] > 0 ? (double)depth[h] / t : 0.0;
+            const double expected = mean > 0 ? 1.0 - std::exp(-mean) : 0.0;
+            fprintf(f, "%s\t%llu\t%llu\t%g\t%llu\t%g\t%g\t%g\n", ids.c_str(), (unsigned long long)total[h], (unsigned long long)observed[h], ratio,
+                    (unsigned long long)depth[h], mean, expected, expected > 0 ? ratio / expected : 0.0);
+        }
+        fclose(f);
+        say(c, "meta", path);
+    }
     say(c, "meta", fq_path + " (" + std::to_string(n_written) + " assigned, " + std::to_string(n_discarded) + " discarded, " + std::to_string(n_unmapped) +
                        " unmapped reads" +
                        (taxonomy ? ", " + std::to_string(n_over) + " spanning more than " + std::to_string(c.maximum_taxon_number) + " taxa" : std::string()) + ")");
@@ -1030,6 +1065,7 @@ int real_main(int argc, char** argv) {
     if (!c.batch.empty() && !c.reads1.empty()) die("--batch takes the read files from the batch file, not from the command line");
     if (c.gpus < 1) die("--gpus expects a positive number");
 
+    if (c.breadth_ratio && !c.filter_and_assign) die("option --breadth-ratio is not accepted without --filter-and-assign");
     if (c.filter_and_assign && !c.meta) die("--filter-and-assign needs --meta");
     if (c.meta) {   // the reference's --meta has no HPC
         pmx_index_info h;

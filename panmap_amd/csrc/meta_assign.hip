@@ -7,6 +7,7 @@
 // mgsr.cpp:1693, static_cast<int32_t>(discard * n), n = the read's seedmers, :1640, 1667): max == 0 -> unmapped, max below
 // the threshold -> discarded, else assigned; the assigned nodes of a read are the nodes whose score equals its maximum, and
 // its LCA node is their lowest common ancestor (assignReadsBatchHelper, :6415-6461).
+// --breadth-ratio (calculateBreadthRatio, :6518-6584): see "Breadth" below.
 //
 // keepForFilterAndAssign changes nothing about that set.  scoreReadsBatchHelper records a read's score at a node only once the
 // flag is set, and sets it at the first node (in DFS order) where the score reaches the threshold (:7508-7513, :7549-7551);
@@ -53,6 +54,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "api_internal.hpp"
@@ -376,6 +379,195 @@ __global__ void __launch_bounds__(256) k_meta_assign_emit(const uint32_t* __rest
     }
 }
 
+// ---- Breadth (--breadth-ratio; calculateBreadthRatio, src/mgsr.cpp:6518-6584; src/main.cpp:957-1015).
+// The reference reads the assigned FASTQ back, scores and assigns those reads again (the same assignment: a read's fate depends
+// on its own list only) and walks the collapsed tree: at node v, for every merged read r assigned to v and every DISTINCT hash
+// s of r that v's genome holds in either orientation, seedHitCounts[s] += dup(r), totalDepth += dup(r).  In closed form, with
+// P[s][v] = fwd row | rev row of seedmer s and mask[r][v] = the best columns of an ASSIGNED read:
+//   observed(v) = |{ s : some r carries s, mask[r][v] and P[s][v] }|,   depth(v) = sum_r mult(r) |{ s in distinct(r) : P[s][v] }| mask[r][v].
+// Both come from bit matrices the chunk already holds:
+//   * k_meta_breadth_rows, once per chunk after the states are final: a wave per (block of rows, span of 64 words), a lane
+//     per word.  For a row, p = fwd | rev once; for each of the row's carriers (the chunk's inverted list row -> reads, a read
+//     once per row however often it repeats the hash) that is ASSIGNED, its mask word mk: a |= mk, and mk & p is added with
+//     weight mult(r) into bit-sliced per-column counters (planes_add from every set bit of the weight).  a & p is ORed into the
+//     row of `hit`, the (distinct seedmer of the READ SET x node) matrix that lives across the chunks, so that a seedmer whose
+//     carriers fall into different chunks is counted once.  One wave owns a (row, word) within a launch and launches are
+//     stream-ordered: a plain read-modify-write.
+//   * k_meta_breadth_count, once at the end: the same layout over `hit`, every row's word added into the counters.
+// The counters hold kBreadthPlanes bits a column.  `sum`, the weight added since the last flush, bounds every column and is the
+// same in all lanes; a weight is added in pieces of at most cap - sum and the counters are flushed when sum reaches cap
+// (<= 2^kBreadthPlanes - 1; PMX_META_BREADTH_FLUSH lowers it for the tests), so no column can wrap whatever the multiplicities.
+// A flush transposes: for every word j of the span the 64 lanes take the 64 columns of that word (lane c assembles bit c of
+// lane j's planes, read across the wave) and add them to out[] with ONE wave instruction over 64 consecutive 64-bit counters.
+// Integer sums only: no result depends on the order or on the chunking.
+constexpr size_t kBreadthHitBytes = (size_t)8 << 30;
+constexpr int kBreadthPlanes = 20;
+// k_meta_breadth_rows adds into kBreadthLowPlanes planes first and carries them into the full counters once their own weight
+// sum would pass 2^kBreadthLowPlanes - 1: an add then costs 4 plane steps, not 20, and the carry 20 steps per 15 unit weights
+constexpr int kBreadthLowPlanes = 4;
+
+// `inc` added `weight` times (weight < 2^PLANES, the same in all lanes)
+template <int PLANES>
+__device__ __forceinline__ void planes_add_weighted(unsigned long long (&plane)[PLANES], unsigned long long inc, uint32_t weight) {
+    if (weight == 1u) { planes_add<PLANES>(plane, inc); return; }
+#pragma unroll
+    for (int b = 0; b < PLANES; ++b) {
+        if (((weight >> b) & 1u) == 0u) continue;
+        unsigned long long carry = inc;
+#pragma unroll
+        for (int p = b; p < PLANES; ++p) {
+            const unsigned long long t = plane[p] & carry;
+            plane[p] ^= carry;
+            carry = t;
+        }
+    }
+}
+
+// plane += low, a LOW-plane number per column; low is cleared
+template <int LOW, int PLANES>
+__device__ __forceinline__ void planes_spill(unsigned long long (&low)[LOW], unsigned long long (&plane)[PLANES]) {
+    unsigned long long carry = 0;
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) {
+        const unsigned long long x = p < LOW ? low[p] : 0ULL, h = plane[p];
+        plane[p] = h ^ x ^ carry;
+        carry = (h & x) | (carry & (h ^ x));
+    }
+#pragma unroll
+    for (int p = 0; p < LOW; ++p) low[p] = 0;
+}
+
+// lane j's value in every lane (j the same in all lanes)
+__device__ __forceinline__ unsigned long long lane_value(unsigned long long x, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, j), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), j);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// The counters of a wave (lane l: the 64 columns of word w0 + l) added to out[column], then cleared: for every word j of the
+// span that has a count, lane c assembles the count of column c of that word from bit c of lane j's planes, and the wave adds
+// 64 consecutive counters with one instruction.  All lanes of the wave call it together.
+template <int PLANES>
+__device__ __forceinline__ void planes_flush(unsigned long long (&plane)[PLANES], int lane, int w0, int words, unsigned long long* __restrict__ out) {
+    unsigned long long any = 0;
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) any |= plane[p];
+    unsigned long long todo = __ballot(any != 0 && w0 + lane < words);
+    while (todo) {
+        const int j = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        unsigned long long c = 0;
+#pragma unroll
+        for (int p = 0; p < PLANES; ++p) c |= ((lane_value(plane[p], j) >> lane) & 1ULL) << p;
+        if (c) atomicAdd(&out[(size_t)(w0 + j) * 64 + (size_t)lane], c);
+    }
+#pragma unroll
+    for (int p = 0; p < PLANES; ++p) plane[p] = 0;
+}
+
+// One chunk's part of hit[] and depth[] (see "Breadth").  Rows [0, n_rows) of the chunk's fwd / rev matrices; row_id: the row
+// of `hit` (the seedmer's index among the read set's distinct seedmers); car_off / car: the chunk's reads (indices into mult /
+// wmask, which point at the chunk's first read, read0; state_words: the states of ALL reads, four to a word, padded to whole
+// words) that carry the row's seedmer.  The carriers are taken four at a time,
+// their states, multiplicities and mask words loaded before any is used (a read that is not ASSIGNED is loaded too and masked
+// out): one load after the other left the kernel waiting on latency.
+__global__ void __launch_bounds__(256) k_meta_breadth_rows(const unsigned long long* __restrict__ mask_fwd, const unsigned long long* __restrict__ mask_rev,
+                                                           int64_t n_rows, int words, const uint32_t* __restrict__ row_id, const int64_t* __restrict__ car_off,
+                                                           const uint32_t* __restrict__ car, const uint32_t* __restrict__ state_words, int64_t read0,
+                                                           const int64_t* __restrict__ mult,
+                                                           const unsigned long long* __restrict__ wmask, int rows_per_block, uint32_t cap,
+                                                           unsigned long long* hit, unsigned long long* depth) {
+    const int lane = threadIdx.x & 63;
+    // (said to the compiler: the wave's index is the same in all lanes, so rows, carriers and their loads are scalar)
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int spans = (words + 63) >> 6;
+    const int64_t n_items = ((n_rows + rows_per_block - 1) / rows_per_block) * spans;
+    for (int64_t item = wave; item < n_items; item += n_waves) {
+        const int64_t row0 = (item / spans) * rows_per_block, row1 = min(n_rows, row0 + rows_per_block);
+        const int w0 = (int)(item % spans) * 64, w = min(w0 + lane, words - 1);   // (a lane past the row reads its last word, and drops it)
+        const bool live = w0 + lane < words;
+        constexpr uint32_t low_cap = (1u << kBreadthLowPlanes) - 1u;
+        unsigned long long plane[kBreadthPlanes], low[kBreadthLowPlanes];
+#pragma unroll
+        for (int p = 0; p < kBreadthPlanes; ++p) plane[p] = 0;
+#pragma unroll
+        for (int p = 0; p < kBreadthLowPlanes; ++p) low[p] = 0;
+        uint32_t sum = 0, low_sum = 0;   // the weight in plane + low / in low since the last flush / spill
+        for (int64_t row = row0; row < row1; ++row) {
+            const size_t at = (size_t)row * (size_t)words + (size_t)w;
+            const unsigned long long p = live ? (mask_fwd[at] | mask_rev[at]) : 0ULL;
+            unsigned long long a = 0;
+            const int64_t c1 = car_off[row + 1];
+            for (int64_t c = car_off[row]; c < c1; c += 4) {
+                uint32_t r[4];
+                bool ok[4];
+                uint64_t weight[4];
+                unsigned long long mk[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) r[u] = car[min(c + u, c1 - 1)];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int64_t at_state = read0 + r[u];   // (a byte of its word: a scalar load, no wait on the vector loads in flight)
+                    ok[u] = (c + u < c1) & (((state_words[at_state >> 2] >> ((at_state & 3) * 8)) & 0xffu) == (uint32_t)PMX_META_ASSIGNED);
+                    weight[u] = (uint64_t)mult[r[u]];
+                    mk[u] = wmask[(size_t)r[u] * (size_t)words + (size_t)w];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (!ok[u]) continue;
+                    a |= mk[u];
+                    const unsigned long long inc = mk[u] & p;   // (p is 0 in a lane past the row)
+                    if (__ballot(inc != 0) == 0) continue;
+                    uint64_t rem = weight[u];
+                    while (rem) {
+                        if (sum == cap) {
+                            planes_spill(low, plane);
+                            planes_flush<kBreadthPlanes>(plane, lane, w0, words, depth);
+                            sum = low_sum = 0;
+                        }
+                        const uint32_t piece = (uint32_t)min(rem, (uint64_t)(cap - sum));
+                        if (piece > low_cap - low_sum) { planes_spill(low, plane); low_sum = 0; }
+                        if (piece <= low_cap) { planes_add_weighted<kBreadthLowPlanes>(low, inc, piece); low_sum += piece; }
+                        else planes_add_weighted<kBreadthPlanes>(plane, inc, piece);
+                        sum += piece;
+                        rem -= piece;
+                    }
+                }
+            }
+            const unsigned long long x = a & p;
+            if (x) hit[(size_t)row_id[row] * (size_t)words + (size_t)w] |= x;
+        }
+        if (sum) {
+            planes_spill(low, plane);
+            planes_flush<kBreadthPlanes>(plane, lane, w0, words, depth);
+        }
+    }
+}
+
+// observed[column] += the set bits of hit's rows, once per call: the layout of k_meta_breadth_rows.
+__global__ void __launch_bounds__(256) k_meta_breadth_count(const unsigned long long* __restrict__ hit, int64_t n_rows, int words, int rows_per_block,
+                                                            uint32_t cap, unsigned long long* observed) {
+    const int lane = threadIdx.x & 63;
+    // (said to the compiler: the wave's index is the same in all lanes, so rows, carriers and their loads are scalar)
+    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int spans = (words + 63) >> 6;
+    const int64_t n_items = ((n_rows + rows_per_block - 1) / rows_per_block) * spans;
+    for (int64_t item = wave; item < n_items; item += n_waves) {
+        const int64_t row0 = (item / spans) * rows_per_block, row1 = min(n_rows, row0 + rows_per_block);
+        const int w0 = (int)(item % spans) * 64, w = w0 + lane;
+        unsigned long long plane[kBreadthPlanes];
+#pragma unroll
+        for (int p = 0; p < kBreadthPlanes; ++p) plane[p] = 0;
+        uint32_t sum = 0;
+        for (int64_t row = row0; row < row1; ++row) {
+            planes_add<kBreadthPlanes>(plane, w < words ? hit[(size_t)row * (size_t)words + (size_t)w] : 0ULL);
+            if (++sum == cap) { planes_flush<kBreadthPlanes>(plane, lane, w0, words, observed); sum = 0; }
+        }
+        if (sum) planes_flush<kBreadthPlanes>(plane, lane, w0, words, observed);
+    }
+}
+
 // One call of pmx_meta_assign: the plan of the chunks, then one function per chunk step.
 int assign_words(int64_t n_nodes) { return (int)(((n_nodes + 63) / 64 + 1) & ~(int64_t)1); }
 
@@ -404,10 +596,17 @@ struct AssignStage {
     DevBuf<int64_t> d_off;
     DevBuf<char> tmp;
     std::vector<int64_t> h_off;
+    // breadth (pmx_meta_set_breadth): hit, depth, observed and the multiplicities live across the chunks; the inverted list
+    // (row -> the chunk's reads that carry it) and the rows' places in `hit` are per chunk
+    const bool breadth;
+    uint32_t breadth_cap = (1u << kBreadthPlanes) - 1u;
+    DevBuf<unsigned long long> d_hit, d_depth, d_observed;
+    DevBuf<int64_t> d_mult, d_car_off;
+    DevBuf<uint32_t> d_car, d_row_id;
 
     AssignStage(pmx_ctx* c, pmx_meta* mm, double d)
         : ctx(c), m(mm), st(c->stream), discard(d), n_reads(mm->n_reads), words(assign_words(mm->n_nodes)), max_taxa(mm->max_taxa),
-          near(mm->max_taxa > 0 && (mm->amb_abs > 0 || mm->amb_ratio > 0.0)) {
+          near(mm->max_taxa > 0 && (mm->amb_abs > 0 || mm->amb_ratio > 0.0)), breadth(mm->breadth_on) {
         // lo = max(0, max - max(abs, (int)(max * ratio))) == 0 for some maximum a read of this set can have
         for (int64_t mx = 1; near && !touch && mx <= mm->longest; ++mx)
             touch = mx <= std::max<int64_t>(mm->amb_abs, (int64_t)((double)mx * mm->amb_ratio));
@@ -415,6 +614,8 @@ struct AssignStage {
     void plan_chunks();
     void run_chunk(int64_t r0, int64_t r1);
     void finish();
+    void breadth_begin();
+    int breadth_rows_per_block(int64_t n_rows) const;
 };
 
 // Chunks of consecutive merged reads whose distinct seedmers fit kAssignMatrixBytes and whose word masks fit
@@ -463,6 +664,34 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     if (near) d_near.ensure((size_t)n * (size_t)words);
     PMX_HIP(hipMemcpyAsync(d_uniq.p, uniq.data(), sizeof(uint64_t) * (size_t)n_rows, hipMemcpyHostToDevice, st));
     PMX_HIP(hipMemcpyAsync(d_uid.p, uid.data(), sizeof(uint32_t) * uid.size(), hipMemcpyHostToDevice, st));
+    std::vector<int64_t> car_off;   // breadth: the chunk's inverted list, alive until the synchronize below
+    std::vector<uint32_t> car;
+    if (breadth) {
+        car_off.assign((size_t)n_rows + 1, 0);
+        std::vector<uint32_t> mine;
+        for (int pass = 0; pass < 2; ++pass) {   // count, then fill: a read once per row
+            for (int64_t r = r0; r < r1; ++r) {
+                mine.assign(uid.begin() + (m->h_read_off[(size_t)r] - s0), uid.begin() + (m->h_read_off[(size_t)r + 1] - s0));
+                std::sort(mine.begin(), mine.end());
+                mine.erase(std::unique(mine.begin(), mine.end()), mine.end());
+                for (uint32_t row : mine) {
+                    if (pass == 0) ++car_off[(size_t)row + 1];
+                    else car[(size_t)car_off[(size_t)row]++] = (uint32_t)(r - r0);
+                }
+            }
+            if (pass == 0) {
+                for (int64_t i = 0; i < n_rows; ++i) car_off[(size_t)i + 1] += car_off[(size_t)i];
+                car.resize((size_t)car_off[(size_t)n_rows]);
+            } else {   // (the fill moved every offset to its row's end: shift them back)
+                for (int64_t i = n_rows; i > 0; --i) car_off[(size_t)i] = car_off[(size_t)i - 1];
+                car_off[0] = 0;
+            }
+        }
+        d_car_off.ensure(car_off.size()); d_car.ensure(car.size()); d_row_id.ensure((size_t)n_rows);
+        PMX_HIP(hipMemcpyAsync(d_car_off.p, car_off.data(), sizeof(int64_t) * car_off.size(), hipMemcpyHostToDevice, st));
+        if (!car.empty()) PMX_HIP(hipMemcpyAsync(d_car.p, car.data(), sizeof(uint32_t) * car.size(), hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_row_id.p, ids.data(), sizeof(uint32_t) * (size_t)n_rows, hipMemcpyHostToDevice, st));
+    }
     timer_begin(ctx, "meta_assign");
     PMX_HIP(hipMemsetAsync(d_fwd.p, 0, sizeof(unsigned long long) * mat, st));
     PMX_HIP(hipMemsetAsync(d_rev.p, 0, sizeof(unsigned long long) * mat, st));
@@ -499,11 +728,21 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     //  chunk's own counts plays no part in any output)
     PMX_ROCPRIM(tmp, exclusive_scan, d_count.p + r0, d_off.p, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
     timer_end(ctx, max_taxa > 0 ? "meta_assign_taxa" : "meta_assign", 1);
+    if (breadth) {   // the states are final
+        timer_begin(ctx, "meta_breadth");
+        const int rpb = breadth_rows_per_block(n_rows);
+        const int64_t items = ((n_rows + rpb - 1) / rpb) * (int64_t)((words + 63) / 64);
+        hipLaunchKernelGGL(k_meta_breadth_rows, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words, d_row_id.p,
+                           d_car_off.p, d_car.p, reinterpret_cast<const uint32_t*>(d_state.p), r0, d_mult.p + r0, d_wmask.p, rpb, breadth_cap, d_hit.p, d_depth.p);
+        PMX_HIP(hipGetLastError());
+        timer_end(ctx, "meta_breadth", 1);
+    }
     h_off.resize((size_t)n + 1);
     PMX_HIP(hipMemcpyAsync(h_off.data(), d_off.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipStreamSynchronize(st));   // (uniq / uid go out of scope; the total sizes the list)
     timer_sum_add(ctx, "meta_assign");
     if (max_taxa > 0) timer_sum_add(ctx, "meta_assign_taxa");
+    if (breadth) timer_sum_add(ctx, "meta_breadth");
     const int64_t total = h_off[(size_t)n], base = (int64_t)m->as_nodes.size();
     for (int64_t i = 1; i <= n; ++i) m->as_off[(size_t)(r0 + i)] = base + h_off[(size_t)i];
     if (total == 0) return;
@@ -538,6 +777,68 @@ void AssignStage::finish() {
         while (m->h_subtree_end[a] < last[(size_t)r]) a = m->h_parent[a];
         m->as_lca[(size_t)r] = a;
     }
+    if (!breadth) return;
+    // observed: the column counts of `hit`, once
+    const int64_t n_uniq = (int64_t)m->h_uniq.size();
+    const int rpb = breadth_rows_per_block(n_uniq);
+    const int64_t items = ((n_uniq + rpb - 1) / rpb) * (int64_t)((words + 63) / 64);
+    timer_begin(ctx, "meta_breadth");
+    timer_begin(ctx, "meta_breadth_count");   // (the count kernel alone; "meta_breadth" holds it too)
+    hipLaunchKernelGGL(k_meta_breadth_count, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_hit.p, n_uniq, words, rpb, breadth_cap, d_observed.p);
+    PMX_HIP(hipGetLastError());
+    timer_end(ctx, "meta_breadth_count", 1);
+    timer_end(ctx, "meta_breadth", 1);
+    PMX_HIP(hipMemcpyAsync(m->br_observed.data(), d_observed.p, sizeof(uint64_t) * (size_t)m->n_nodes, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(m->br_depth.data(), d_depth.p, sizeof(uint64_t) * (size_t)m->n_nodes, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    timer_sum_add(ctx, "meta_breadth");
+}
+
+// Rows a wave walks before it expands its counters: enough (block, span) items for 32 waves a CU, 16 to 512 rows.
+int AssignStage::breadth_rows_per_block(int64_t n_rows) const {
+    const int64_t spans = (words + 63) / 64;
+    return (int)std::min<int64_t>(512, std::max<int64_t>(16, n_rows * spans / ((int64_t)ctx->n_cu * 32)));
+}
+
+// The buffers that live across the chunks, zeroed; the flush bound.
+void AssignStage::breadth_begin() {
+    const size_t mat = m->h_uniq.size() * (size_t)words, cols = (size_t)words * 64;
+    d_hit.alloc(mat); d_depth.alloc(cols); d_observed.alloc(cols); d_mult.alloc((size_t)n_reads);
+    PMX_HIP(hipMemsetAsync(d_hit.p, 0, sizeof(unsigned long long) * mat, st));
+    PMX_HIP(hipMemsetAsync(d_depth.p, 0, sizeof(unsigned long long) * cols, st));
+    PMX_HIP(hipMemsetAsync(d_observed.p, 0, sizeof(unsigned long long) * cols, st));
+    PMX_HIP(hipMemcpyAsync(d_mult.p, m->h_mult.data(), sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    if (const char* f = opt_str(O_META_BREADTH_FLUSH)) breadth_cap = (uint32_t)std::min<long long>(breadth_cap, std::max<long long>(1, atoll(f)));
+}
+
+// TotalRefSeeds of every node (node->totalRefSeeds, src/mgsr.cpp:590-610): the distinct hashes of its genome, a hash being the
+// pair {key, key ^ PMX_ORIENT_XOR} of the oriented index, present when either count is positive.  One DFS over the changes
+// (nodes are in pre-order: the open ancestors are a stack), applied on the way in and reverted on the way out.
+std::vector<uint64_t> total_ref_seeds(const pmx_meta* m) {
+    const LiteIndex* O = pmx_index_internal(m->idx_oriented);
+    std::vector<uint64_t> total((size_t)m->n_nodes);
+    std::unordered_map<uint64_t, int16_t> count;
+    count.reserve(O->hash.size());
+    int64_t present = 0;
+    auto set = [&](uint64_t key, int16_t to) {
+        const auto o = count.find(key ^ PMX_ORIENT_XOR);
+        const bool other = o != count.end() && o->second > 0;
+        int16_t& c = count[key];
+        present += (int64_t)(to > 0 || other) - (int64_t)(c > 0 || other);
+        c = to;
+    };
+    std::vector<uint32_t> open;
+    for (int64_t v = 0; v < m->n_nodes; ++v) {
+        while (!open.empty() && (int64_t)m->h_subtree_end[open.back()] < v) {
+            const uint32_t u = open.back();
+            open.pop_back();
+            for (uint64_t q = O->offsets[(size_t)u + 1]; q > O->offsets[u]; --q) set(O->hash[q - 1], O->parent_count[q - 1]);
+        }
+        for (uint64_t q = O->offsets[(size_t)v]; q < O->offsets[(size_t)v + 1]; ++q) set(O->hash[q], O->child_count[q]);
+        total[(size_t)v] = (uint64_t)present;
+        open.push_back((uint32_t)v);
+    }
+    return total;
 }
 }  // namespace
 
@@ -550,9 +851,16 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     if (m->max_taxa > 0 && discard > 0.0 && (m->amb_abs > 0 || m->amb_ratio > 0.0))
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: a discard threshold together with an ambiguity threshold (the reference's records then depend "
                                          "on the order of a node's seed changes)");
+    if (m->breadth_on) {   // nothing is approximated: the hit matrix fits its budget or the call is refused
+        const size_t bytes = m->h_uniq.size() * (size_t)assign_words(m->n_nodes) * sizeof(unsigned long long);
+        if (bytes > kBreadthHitBytes)
+            return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign with breadth: the hit matrix (distinct seedmers of the reads x nodes, one bit each) needs " +
+                                                 std::to_string(bytes) + " bytes, the budget is " + std::to_string(kBreadthHitBytes));
+    }
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     m->assigned = false;
+    m->as_breadth = false;
     const int64_t n = m->n_reads;
     int64_t longest = 0;
     for (int64_t r = 0; r < n; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
@@ -567,10 +875,18 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     m->as_max_taxa = m->max_taxa;
     m->as_ntax.assign((size_t)n, 0);
     m->as_tax.assign((size_t)n * (size_t)m->max_taxa, 0);
+    if (m->breadth_on) {
+        if (m->total_ref_seeds.empty()) m->total_ref_seeds = total_ref_seeds(m);
+        m->br_observed.assign((size_t)m->n_nodes, 0);
+        m->br_depth.assign((size_t)m->n_nodes, 0);
+    }
+    for (const char* span : {"meta_breadth", "meta_breadth_count"})   // (no such span without breadth)
+        if (auto t = ctx->timers.find(span); t != ctx->timers.end()) t->second.pending = false;
     if (n > 0) {
         AssignStage S(ctx, m, discard);
         S.plan_chunks();
-        S.d_max.alloc((size_t)n); S.d_count.alloc((size_t)n + 1); S.d_first.alloc((size_t)n); S.d_last.alloc((size_t)n); S.d_state.alloc((size_t)n);
+        S.d_max.alloc((size_t)n); S.d_count.alloc((size_t)n + 1); S.d_first.alloc((size_t)n); S.d_last.alloc((size_t)n);
+        S.d_state.alloc((size_t)n + (m->breadth_on ? 3 : 0));   // (k_meta_breadth_rows reads the states by whole words)
         if (m->max_taxa > 0) {
             S.d_ntax.alloc((size_t)n); S.d_tax.alloc((size_t)n * (size_t)m->max_taxa);
             PMX_HIP(hipMemsetAsync(S.d_tax.p, 0, sizeof(uint32_t) * (size_t)n * (size_t)m->max_taxa, ctx->stream));   // (a read fills its first ids only)
@@ -579,13 +895,32 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
         timer_sum_reset(ctx, "meta_assign");
         if (auto t = ctx->timers.find("meta_assign_taxa"); t != ctx->timers.end()) t->second.pending = false;   // (no such span without a taxonomy)
         timer_sum_reset(ctx, "meta_assign_emit");
+        if (S.breadth) {
+            timer_sum_reset(ctx, "meta_breadth");
+            S.breadth_begin();
+        }
         PMX_HIP(hipMemsetAsync(S.d_count.p, 0, sizeof(uint32_t) * ((size_t)n + 1), ctx->stream));
         for (size_t c = 0; c + 1 < S.chunk_first.size(); ++c) S.run_chunk(S.chunk_first[c], S.chunk_first[c + 1]);
         S.finish();
     }
     m->assigned = true;
+    m->as_breadth = m->breadth_on;
     return PMX_OK;
     PMX_CATCH
+}
+
+int pmx_meta_set_breadth(pmx_meta* m, int on) {
+    if (!m) return PMX_ERR_ARG;
+    m->breadth_on = on != 0;
+    return PMX_OK;
+}
+
+int pmx_meta_breadth(const pmx_meta* m, uint64_t* total_ref_seeds, uint64_t* observed, uint64_t* depth, int64_t cap_nodes) {
+    if (!m || !m->assigned || !m->as_breadth || cap_nodes < m->n_nodes) return PMX_ERR_ARG;
+    if (total_ref_seeds) std::copy(m->total_ref_seeds.begin(), m->total_ref_seeds.end(), total_ref_seeds);
+    if (observed) std::copy(m->br_observed.begin(), m->br_observed.end(), observed);
+    if (depth) std::copy(m->br_depth.begin(), m->br_depth.end(), depth);
+    return PMX_OK;
 }
 
 int pmx_meta_assign_reads(const pmx_meta* m, uint8_t* state, uint16_t* max_score, uint32_t* lca, uint32_t* n_nodes, int64_t cap) {

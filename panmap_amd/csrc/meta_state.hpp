@@ -41,6 +41,7 @@ struct pmx_meta_group {
 struct pmx_meta {
     pmx_ctx* ctx = nullptr;
     const pmx_index* idx_std = nullptr;
+    const pmx_index* idx_oriented = nullptr;   // (read again by pmx_meta_assign with breadth: TotalRefSeeds)
     int64_t n_nodes = 0, n_changes = 0;
     pmx::SyncmerParams params;
     // oriented index on the device
@@ -91,6 +92,10 @@ struct pmx_meta {
     int32_t as_max_taxa = 0;                // max_taxa of that call: as_tax holds as_max_taxa ids a read, as_ntax of them set
     std::vector<uint8_t> as_ntax;
     std::vector<uint32_t> as_tax;
+    // breadth (pmx_meta_set_breadth; calculateBreadthRatio, src/mgsr.cpp:6518-6584), per node: total_ref_seeds once per pmx_meta,
+    // br_observed / br_depth of the last pmx_meta_assign when as_breadth
+    bool breadth_on = false, as_breadth = false;
+    std::vector<uint64_t> total_ref_seeds, br_observed, br_depth;
     // taxonomy (pmx_meta_set_taxonomy; max_taxa 0 = none) and the ambiguity thresholds (pmx_meta_set_ambiguous).  The node table:
     // the taxa S(v) of every node's subtree, ascending, max_taxa slots a node; h_tx_over: bit v = |S(v)| > max_taxa (then no ids)
     int32_t max_taxa = 0, amb_abs = 0;

@@ -2,6 +2,7 @@
 Host-side mirror of the reference's flow: reads -> Meta.set_reads -> Meta.score (candidates + parsimony scores) -> Meta.em
 -> the `<prefix>.mgsr.abundance.out` text (node[,merged nodes...]<TAB>proportion with five decimals, by proportion)."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -23,10 +24,13 @@ class AssignResult:
     nodes (Index.node_heads of the oriented index).  The assigned reads, in input order, are the records of
     `<prefix>.mgsr.assignedReads.fastq`: `fastq_index[read]` is a read's position there (-1 unless assigned).
     With a taxonomy (Meta.set_taxonomy) a read that spans too many taxa is OVER_TAXA: no nodes, no LCA, not in the FASTQ;
-    `read_taxa` ((n_taxa, taxa[merged reads][max_taxa])) and `node_sets` (node -> S(node), None when over) feed taxa_of / node_taxa."""
+    `read_taxa` ((n_taxa, taxa[merged reads][max_taxa])) and `node_sets` (node -> S(node), None when over) feed taxa_of / node_taxa.
+    `breadth`: None, or with Meta.assign(breadth=True) three int64 arrays per node (DFS index; a folded node carries its head's
+    numbers): (total_ref_seeds, observed, depth) of pmx_meta_breadth -- format_breadths writes the file from them."""
 
-    def __init__(self, merged, state, mx, lca, offsets, nodes, heads, read_taxa=None, node_sets=None):
+    def __init__(self, merged, state, mx, lca, offsets, nodes, heads, read_taxa=None, node_sets=None, breadth=None):
         self.merged, self.heads, self._off, self._nodes = merged, heads, offsets, nodes
+        self.breadth = breadth
         self._read_taxa, self._node_sets = read_taxa, node_sets
         has = merged >= 0
         at = np.where(has, merged, 0)
@@ -142,10 +146,12 @@ class Meta:
             raise ValueError("node_taxa: no taxonomy is set, or no such node")
         return None if n < 0 else ids[:n].copy()
 
-    def assign(self, discard: float = 0.0, ambiguous: int = 0, ambiguous_ratio: float = 0.0) -> AssignResult:
+    def assign(self, discard: float = 0.0, ambiguous: int = 0, ambiguous_ratio: float = 0.0, breadth: bool = False) -> AssignResult:
         """--filter-and-assign on the reads of the last set_reads: every read against every node (pmx_meta_assign).
         `ambiguous` / `ambiguous_ratio` (--ambiguous-score-threshold, -ratio) widen the nodes whose taxa count for a read from
-        its best ones to those within max(ambiguous, int(max * ratio)) of its best score; they act through a taxonomy only."""
+        its best ones to those within max(ambiguous, int(max * ratio)) of its best score; they act through a taxonomy only.
+        `breadth` (--breadth-ratio): also the per-node seed breadth of the assignment, in AssignResult.breadth."""
+        check(lib.pmx_meta_set_breadth(self._h, int(bool(breadth))), "pmx_meta_set_breadth")
         check(lib.pmx_meta_set_ambiguous(self._h, int(ambiguous), float(ambiguous_ratio)), "pmx_meta_set_ambiguous")
         check(lib.pmx_meta_assign(self.ctx._h, self._h, float(discard)), "pmx_meta_assign")
         n = self.n_reads
@@ -162,7 +168,13 @@ class Meta:
             check(lib.pmx_meta_assign_taxa(self._h, nt.ctypes.data, tx.ctypes.data, n), "pmx_meta_assign_taxa")
             sets = [self.node_taxa(v) for v in range(self.index_oriented.info.n_nodes)]   # (copied: the result outlives a later set_taxonomy)
             read_taxa, node_sets = (nt, tx), sets.__getitem__
-        return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads(), read_taxa, node_sets)
+        numbers = None
+        if breadth:
+            n_nodes = self.index_oriented.info.n_nodes
+            u = [np.zeros(n_nodes, np.uint64) for _ in range(3)]
+            check(lib.pmx_meta_breadth(self._h, u[0].ctypes.data, u[1].ctypes.data, u[2].ctypes.data, n_nodes), "pmx_meta_breadth")
+            numbers = tuple(x.astype(np.int64) for x in u)
+        return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads(), read_taxa, node_sets, numbers)
 
     def raw_to_merged(self) -> np.ndarray:
         """per read of the last set_reads (input order): its merged read, -1 when --dust dropped it or it has no seedmers"""
@@ -283,3 +295,32 @@ def format_assigned(result: AssignResult, node_id, heads=None, taxon_names=None)
             lines.append("%s\t%s\t%d\t%s" % (ids, col, len(groups[h]), ",".join(str(i) for i in sorted(groups[h]))))
         return "\n".join(lines) + ("\n" if lines else "")
     return text(result.by_node()), text(result.by_lca())
+
+
+BREADTHS_HEADER = ("NodeId\tTotalRefSeeds\tObservedBreadthCount\tObservedBreadthRatio\tTotalDepth\tMeanDepth\tExpectedBreadthRatio\t"
+                   "ObservedToExpectedBreadthRatio")
+
+
+def format_breadths(result: AssignResult, node_id, heads=None) -> str:
+    """`<prefix>.mgsr.breadths.out` (src/main.cpp:957-1015; calculateBreadthRatio, src/mgsr.cpp:6518-6584) from a result of
+    Meta.assign(breadth=True): the header, then one line per HEAD node, with or without reads, by ascending DFS index (the
+    reference's pre-order of the collapsed tree): `head[,folded nodes]`, TotalRefSeeds, ObservedBreadthCount, its ratio to
+    TotalRefSeeds, TotalDepth, MeanDepth = depth / TotalRefSeeds, ExpectedBreadthRatio = 1 - exp(-MeanDepth), observed over
+    expected; a ratio whose denominator is 0 is 0; doubles as %g.  The header alone when no read is assigned."""
+    if result.breadth is None:
+        raise ValueError("format_breadths: the result was made without breadth=True")
+    heads = np.asarray(result.heads if heads is None else heads)
+    lines = [BREADTHS_HEADER]
+    if (result.state == ASSIGNED).any():
+        members = {}
+        for v in np.nonzero(heads != np.arange(len(heads)))[0].tolist():
+            members.setdefault(int(heads[v]), []).append(v)
+        total, observed, depth = result.breadth
+        for h in np.nonzero(heads == np.arange(len(heads)))[0].tolist():
+            t, o, d = int(total[h]), int(observed[h]), int(depth[h])
+            ratio = o / t if t > 0 else 0.0
+            mean = d / t if t > 0 else 0.0
+            expected = 1.0 - math.exp(-mean) if mean > 0 else 0.0
+            lines.append("%s\t%d\t%d\t%g\t%d\t%g\t%g\t%g" % (",".join(node_id(x) for x in [h] + members.get(h, [])), t, o, ratio, d, mean, expected,
+                                                              ratio / expected if expected > 0 else 0.0))
+    return "\n".join(lines) + "\n"

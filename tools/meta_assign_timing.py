@@ -7,6 +7,8 @@ With `taxonomy` as the last argument instead: the taxonomy filter.  Every node g
 with 16 taxa (a leaf v with v % 7 != 3 and an internal node with v % 11 == 5 get (16 v) // n), at most one taxon a read.  Three
 calls, each run twice: without a taxonomy, with it, and with it and --ambiguous-score-threshold-ratio 0.1; "meta_assign_taxa" is
 the taxonomy pass (its kernels and the scan of the node counts, which "meta_assign" holds without a taxonomy).
+With `breadth` as the last argument instead: --breadth-ratio.  Two calls, each run twice: without breadth and with it; "meta_breadth" is
+the breadth pass (k_meta_breadth_rows per chunk and k_meta_breadth_count once), hit_matrix_bytes the matrix it keeps across the chunks.
   meta_assign_timing.py rsv  [n_reads]   rsv_4K, reads at step 1 over two of its genomes (default 20,000)
   meta_assign_timing.py sars [n_reads]   SARS-CoV-2 20k tree, the 5-haplotype mixture of test_config5_sars_five_haplotypes (default 200,000)"""
 import json
@@ -70,11 +72,23 @@ def taxonomy_mode(meta, ms, out):
                              assigned=int((res.state == 2).sum()), over=int((res.state == 3).sum()))
 
 
+def breadth_mode(meta, ms, out):
+    for name, on in (("off", False), ("on", True)):
+        for rep in range(2):
+            t0 = time.perf_counter()
+            res = meta.assign(0.0, breadth=on)
+            out[name] = dict(wall_s=time.perf_counter() - t0, assign_ms=ms("meta_assign"), emit_ms=ms("meta_assign_emit"), breadth_ms=ms("meta_breadth"),
+                             assigned=int((res.state == 2).sum()))
+    total, observed, depth = res.breadth
+    out["hit_matrix_bytes"] = out["bit_matrix_bytes"] // 2
+    out["nodes_with_hits"], out["observed_sum"], out["depth_sum"] = int((observed > 0).sum()), int(observed.sum()), int(depth.sum())
+
+
 def main():
     import panmap_amd as pmx
     from panmap_amd._lib import lib
-    taxonomy = sys.argv[-1] == "taxonomy"
-    if taxonomy:
+    taxonomy, breadth = sys.argv[-1] == "taxonomy", sys.argv[-1] == "breadth"
+    if taxonomy or breadth:
         sys.argv.pop()
     which = sys.argv[1] if len(sys.argv) > 1 else "rsv"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else (20000 if which == "rsv" else 200000)
@@ -90,8 +104,8 @@ def main():
     words = ((n_nodes + 63) // 64 + 1) & ~1
     out["distinct_seedmers"] = int(len(np.unique(h)))
     out["bit_matrix_bytes"] = 2 * out["distinct_seedmers"] * words * 8     # (of all reads: split over chunks of at most 2 GiB)
-    if taxonomy:
-        taxonomy_mode(meta, ms, out)
+    if taxonomy or breadth:
+        taxonomy_mode(meta, ms, out) if taxonomy else breadth_mode(meta, ms, out)
         print(json.dumps(out))
         return
     for rep in range(2):
