@@ -569,6 +569,24 @@ int pmx_meta_em_info(const pmx_meta *m, int32_t *rounds, int32_t *iterations, do
  * greater than T (src/mgsr.cpp:1593-1594, 1833-1834).  pmx_read_dust = mgsr::getDust (src/mgsr.cpp:1505-1568; host, no
  * device): Prinseq-scaled score over base triplets in a sliding window of `window` triplets (the reference uses 64). */
 int pmx_meta_set_dust(pmx_meta *m, double threshold);
+/* --mask-reads N / --mask-seeds N (src/main.cpp:2026-2030; initializeQueryData, src/mgsr.cpp:2049-2139), both 0 = off, for the
+ * pmx_meta_set_reads calls that follow.  On the merged reads, count[h] = the sum of the multiplicities of the merged reads whose
+ * list holds hash h (once per read, either orientation).  mask_reads T > 0: a merged read with an entry of count <= T is
+ * dropped; mask_seeds T > 0: every entry of count <= T is removed, the rest keeps its order, a read left empty is dropped and
+ * reads that became equal stay apart.  Everything after -- overlap coefficients, candidates, scores, EM, the read getters,
+ * pmx_meta_raw_to_merged (-1 for a read of a dropped merged read) -- is of the survivors.  Both > 0: PMX_ERR_ARG, "Only one
+ * masking parameter can be set at a time" (src/mgsr.cpp:2049-2053); a negative value: PMX_ERR_ARG.  --gpus N: the same masks
+ * on every rank.  pmx_meta_assign on reads set with a mask is PMX_ERR_UNSUPPORTED: the reference's reader for
+ * --filter-and-assign never masks (initializeQueryDataBatch, src/mgsr.cpp:1575). */
+int pmx_meta_set_masks(pmx_meta *m, int64_t mask_reads, int64_t mask_seeds);
+/* of the last pmx_meta_set_reads (src/mgsr.cpp:2049-2139, reported at :2220-2230): numMaskReads (merged reads dropped by
+ * mask_reads), numMaskSeeds (entries removed by mask_seeds), numPassedReads (merged reads left); pointers may be NULL */
+int pmx_meta_mask_info(const pmx_meta *m, int64_t *reads_dropped, int64_t *seeds_removed, int64_t *reads_left);
+/* the distinct hashes of the merged reads BEFORE masking, ascending, with count[h] (kminmerCounts, src/mgsr.cpp:2049-2139:
+ * :2055-2060); pmx_meta_mask_num_counts of them (0 when the last pmx_meta_set_reads ran without a mask, and
+ * pmx_meta_mask_counts is PMX_ERR_ARG then); either array may be NULL */
+int64_t pmx_meta_mask_num_counts(const pmx_meta *m);
+int pmx_meta_mask_counts(const pmx_meta *m, uint64_t *hash, int64_t *count, int64_t cap);
 /* --meta --gpus N: call after pmx_meta_create, before pmx_meta_set_reads (`d` on the same context, kept alive by the caller).
  * From then on set_reads, score and em are COLLECTIVE: every rank calls them in the same order, set_reads with its own shard of
  * the raw reads.  The merged reads, overlap coefficients, candidates, haplotypes and em_info are then those of one rank over the

@@ -209,6 +209,10 @@ SIGNATURES = {
     "pmx_meta_haplotype": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64]),
     "pmx_meta_em_info": (_i32, [_vp, _vp, _vp, _vp]),
     "pmx_meta_set_dust": (_i32, [_vp, C.c_double]),
+    "pmx_meta_set_masks": (_i32, [_vp, _i64, _i64]),
+    "pmx_meta_mask_info": (_i32, [_vp, _vp, _vp, _vp]),
+    "pmx_meta_mask_num_counts": (_i64, [_vp]),
+    "pmx_meta_mask_counts": (_i32, [_vp, _vp, _vp, _i64]),
     "pmx_meta_attach_dist": (_i32, [_vp, _vp]),
     "pmx_meta_row_range": (_i32, [_vp, _vp, _vp]),
     "pmx_read_dust": (C.c_double, [_cp, _i64, _i32]),

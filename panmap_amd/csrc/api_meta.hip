@@ -26,7 +26,8 @@
 //     the host with the libm the oracle uses), FP64 throughout, every reduction in a fixed order (bit-stable runs):
 //     k_meta_denoms (a wave per read), k_meta_colsum (a thread per candidate over a chunk of reads; chunk partials added in
 //     chunk order).  HBM-bound: 2 B per (read, candidate) per pass, six passes per SQUAREM iteration.
-// --filter-and-assign (every read against EVERY node, no score matrix) is meta_assign.hip, on the state of meta_state.hpp.
+// --filter-and-assign (every read against EVERY node, no score matrix) is meta_assign.hip, on the state of meta_state.hpp;
+// --mask-reads / --mask-seeds (merged reads or list entries with low-coverage k-min-mers leave the sample) is meta_mask.hip.
 // Read-side seedmer extraction is host C++ here (threads; the k-min-mer definitions of host/seed_host.hpp); moving it into
 // the seeding kernel is the next step.  parity: the reference's own MGSR index and EM cannot be built here (panman / TBB /
 // Eigen / abseil are absent): scores and EM are checked by the test suite against a direct restatement (per-node seed
@@ -1165,7 +1166,8 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     R.merge_equal_lists();
     if (m->dist) R.merge_over_ranks();
     R.upload_lists();
-    rc = R.overlap_coefficients();
+    // the low-coverage masks (src/mgsr.cpp:2049-2139), when one is set: the reads that survive are the sample from here on
+    rc = meta_masks_set(ctx, m) ? meta_masked_overlap_coefficients(ctx, m) : R.overlap_coefficients();
     if (rc != PMX_OK) return rc;
     m->cand.clear();
     m->groups.clear();

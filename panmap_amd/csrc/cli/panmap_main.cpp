@@ -51,6 +51,10 @@ struct Config {
     double ambiguous_ratio = 0.0;
     std::vector<std::string> taxonomy_options;
     bool breadth_ratio = false;       // --breadth-ratio: <prefix>.mgsr.breadths.out (src/main.cpp:957-1015)
+    // --mask-reads N / --mask-seeds N: the low-coverage masks of --meta (src/main.cpp:2026-2030, src/mgsr.cpp:2049-2139);
+    // `mask_options`: the ones given, in order
+    int64_t mask_reads = 0, mask_seeds = 0;
+    std::vector<std::string> mask_options;
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
     int em_max_iterations = 1000, em_max_rounds = 5;
@@ -93,6 +97,9 @@ void usage() {
           "                             column, the taxa of --taxonomic-rank NAME (default Family) in the column of that name\n"
           "      --maximum-taxon-number N (default 1, at most 16)   --ambiguous-score-threshold N / --ambiguous-score-threshold-ratio F:\n"
           "                             count the nodes within max(N, int(best * F)) of a read's best score too (not with --discard > 0)\n"
+          "      --mask-reads N         --meta: drop every read that carries a k-min-mer seen at most N times in the whole sample (counted\n"
+          "                             over the distinct reads, each with its number of copies)      --mask-seeds N   remove those\n"
+          "                             k-min-mers from the reads instead (one of the two; also with --gpus N; not with --filter-and-assign)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange\n"
           "      --refine               re-rank the top candidates by aligning the reads against them\n"
@@ -166,6 +173,10 @@ Config parse(int argc, char** argv) {
                 die("option --breadth-ratio is not accepted with a value (" + next + "): it is a switch, as in the reference");
             c.breadth_ratio = true;
         }
+        else if (a == "--mask-reads") { c.mask_reads = atoll(v().c_str()); c.mask_options.push_back(a); }
+        else if (a == "--mask-seeds") { c.mask_seeds = atoll(v().c_str()); c.mask_options.push_back(a); }
+        else if (a == "--amplicon-depth" || a == "--mask-reads-relative-frequency" || a == "--mask-seeds-relative-frequency")
+            die("option " + a + " is not accepted: it needs amplicon groups, which this build does not make");
         else if (a == "--jplace" || a == "--mask-read-ends")
             die("option " + a + " is not accepted: --filter-and-assign is built without jplace output and read-end masking");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
@@ -965,6 +976,10 @@ int run_meta(Config c) {
     if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
     if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
     if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
+    if (!c.mask_options.empty() && c.filter_and_assign)   // (initializeQueryDataBatch, src/mgsr.cpp:1575, never masks)
+        die("option " + c.mask_options[0] + " is not accepted with --filter-and-assign: the reference's reader for that mode never masks");
+    if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
+    if (c.mask_reads > 0 && c.mask_seeds > 0) die("Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
     // the taxonomy filter: read the table before anything else is opened
     const bool with_taxonomy = !c.taxonomic_metadata.empty();
     if ((with_taxonomy || !c.taxonomy_options.empty()) && !c.filter_and_assign)
@@ -1015,7 +1030,17 @@ int run_meta(Config c) {
     check(pmx_meta_create(ctx, run.idx, run.oidx, &m), "uploading the indexes");
     if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
     check(pmx_meta_set_dust(m, c.dust), "--dust");
+    check(pmx_meta_set_masks(m, c.mask_reads, c.mask_seeds), "--mask-reads / --mask-seeds");
     check(pmx_meta_set_reads(ctx, m, reads.concat.data(), reads.off.data() + lo, hi - lo), "seeding the reads");
+    if (c.mask_reads > 0 || c.mask_seeds > 0) {   // the reference's two lines (src/mgsr.cpp:2220-2230)
+        int64_t dropped = 0, removed = 0, left = 0;
+        check(pmx_meta_mask_info(m, &dropped, &removed, &left), "the numbers of the masks");
+        say(c, "meta", c.mask_reads > 0 ? "Mask-reads " + std::to_string(c.mask_reads) + " turned on: " + std::to_string(dropped) +
+                                              " reads containing low coverage kminmers will be skipped during placement and EM... Total reads to process: " +
+                                              std::to_string(left)
+                                        : "Mask-seeds " + std::to_string(c.mask_seeds) + " turned on: " + std::to_string(removed) +
+                                              " seeds are removed during placement and EM... Total reads to process: " + std::to_string(left));
+    }
     if (c.filter_and_assign) {
         write_assigned(c, run, reads, taxonomy.t);
         run.close();
@@ -1067,6 +1092,7 @@ int real_main(int argc, char** argv) {
 
     if (c.breadth_ratio && !c.filter_and_assign) die("option --breadth-ratio is not accepted without --filter-and-assign");
     if (c.filter_and_assign && !c.meta) die("--filter-and-assign needs --meta");
+    if (!c.mask_options.empty() && !c.meta) die("option " + c.mask_options[0] + " is not accepted without --meta");
     if (c.meta) {   // the reference's --meta has no HPC
         pmx_index_info h;
         if (c.hpc) die("--meta has no homopolymer-compressed form: drop --hpc");

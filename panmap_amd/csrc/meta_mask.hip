@@ -1,0 +1,368 @@
+// --meta --mask-reads N / --mask-seeds N: the low-coverage k-min-mer masks (ThreadsManager::initializeQueryData,
+// src/mgsr.cpp:2049-2139), a step of pmx_meta_set_reads between the upload of the merged lists and the overlap coefficients.
+//
+// The reference's rule, on the reads AFTER equal seedmer lists were merged into one read with a multiplicity:
+//   count[h] = sum of the multiplicities of the merged reads that carry hash h -- a read adds its multiplicity ONCE per
+//              distinct hash, however often its list repeats it (the loop is over uniqueSeedmers), either orientation;
+//   mask-reads T > 0: a merged read with any list entry of count <= T is dropped (numMaskReads counts them);
+//   mask-seeds T > 0 (only when mask-reads is off): every list entry of count <= T is removed, the rest keeps its order
+//              (numMaskSeeds counts the removed entries); a read left empty is dropped; reads that became equal stay apart.
+// Everything downstream -- the hash set of the overlap coefficients, the score rows, the EM's reads and weights -- sees the
+// survivors only.
+//
+// Here, on the merged lists as upload_lists left them (offsets, every entry as its index `uid` into the ascending distinct
+// hashes, orientations), a wave per merged read in every kernel, like k_meta_assign_max:
+//   * k_meta_mask_count: the read's uids go to the wave's stretch of LDS; the lane that holds entry i adds mult[r] to
+//     count[uid_i] with one 64-bit atomic iff no entry j < i of the read has the same uid (all lanes read the same j: a
+//     broadcast, no bank conflict).  Quadratic in the read's entries, so only for reads of at most kMaskQuadratic entries
+//     (short reads carry ~20; PMX_META_MASK_LONG lowers the bound for the tests).
+//   * longer reads (a 20 kb read has ~3,300 entries, the limit is 65,534): k_meta_mask_long_keys writes (ordinal of the long
+//     read << 32 | uid) per entry, one rocprim radix sort puts equal pairs next to each other, k_meta_mask_long_add adds the
+//     read's multiplicity at the first key of every run.  n log n instead of n^2, and no LDS bound.
+//   * k_meta_mask_flag: an entry is kept iff count[uid] > T.  mask-reads: the ballots of the read decide the whole read;
+//     mask-seeds: the popcounts are its new length.  Writes the new length (0 = dropped), alive[r], used[uid] = 1 for every
+//     surviving entry (plain stores of the same value) and feeds the two counters.
+//   * exclusive scans (rocprim) of the new lengths, of alive[] and of used[]: new offsets, new read indices, new uids.
+//   * k_meta_mask_compact: a wave per surviving read; ballot + popcount prefix place the surviving entries in their order;
+//     hash, new uid, orientation per entry, offset and multiplicity per read.  k_meta_mask_compact_uniq: the surviving
+//     distinct hashes with their counts.
+// All sums are integers: nothing depends on the order of the atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include <rocprim/rocprim.hpp>
+
+#include "api_internal.hpp"
+#include "device/dev_util.hpp"
+#include "meta_state.hpp"
+
+using namespace pmx;
+
+namespace {
+constexpr int kMaskWaves = 4;             // waves per block (256 threads)
+constexpr int kMaskQuadratic = 1024;      // entries a read may have on the in-LDS path: 4 KB of uids per wave, 16 KB per block
+
+// (same-wave LDS traffic is ordered by the hardware; this pins the compiler)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__global__ void __launch_bounds__(64 * kMaskWaves) k_meta_mask_count(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid,
+                                                                     const int64_t* __restrict__ mult, int64_t n_reads, int bound,
+                                                                     unsigned long long* count) {
+    __shared__ uint32_t s_uid[kMaskWaves][kMaskQuadratic];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t wave = (int64_t)blockIdx.x * kMaskWaves + wib, n_waves = (int64_t)gridDim.x * kMaskWaves;
+    uint32_t* uids = s_uid[wib];
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        const int64_t o = read_off[r], n64 = read_off[r + 1] - o;
+        if (n64 > (int64_t)bound) continue;   // (bound <= kMaskQuadratic; the sorted path counts this read)
+        const int n = (int)n64;
+        const unsigned long long w = (unsigned long long)mult[r];
+        for (int i = lane; i < n; i += 64) uids[i] = seed_uid[o + i];
+        wave_lds_sync();
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const uint32_t u = i < n ? uids[i] : 0u;
+            bool first = i < n;
+            const int j1 = min(i0 + 63, n - 1);   // (the same in all lanes: every lane reads uids[j], one broadcast)
+            for (int j = 0; j < j1; ++j) first &= !(j < i && uids[j] == u);
+            if (first) atomicAdd(&count[u], w);
+        }
+        wave_lds_sync();
+    }
+}
+
+// entry e of long read `ordinal` -> ordinal << 32 | uid at key[long_off[ordinal] + e]
+__global__ void __launch_bounds__(256) k_meta_mask_long_keys(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid,
+                                                             const uint32_t* __restrict__ long_read, const int64_t* __restrict__ long_off, int64_t n_long,
+                                                             uint64_t* __restrict__ key) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t q = wave; q < n_long; q += n_waves) {
+        const int64_t r = long_read[q], o = read_off[r], n = read_off[r + 1] - o, dst = long_off[q];
+        for (int64_t e = lane; e < n; e += 64) key[dst + e] = ((uint64_t)q << 32) | (uint64_t)seed_uid[o + e];
+    }
+}
+
+// the sorted keys: the first of every run of equal (read, uid) pairs adds the read's multiplicity
+__global__ void k_meta_mask_long_add(const uint64_t* __restrict__ key, int64_t n_keys, const uint32_t* __restrict__ long_read,
+                                     const int64_t* __restrict__ mult, unsigned long long* count) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_keys; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t k = key[i];
+        if (i > 0 && key[i - 1] == k) continue;
+        atomicAdd(&count[(uint32_t)k], (unsigned long long)mult[long_read[k >> 32]]);
+    }
+}
+
+// whole_reads: --mask-reads (a read with an entry at or below the threshold goes as a whole), else --mask-seeds.
+// ctr[0]: reads dropped by --mask-reads, ctr[1]: entries removed by --mask-seeds.
+__global__ void __launch_bounds__(256) k_meta_mask_flag(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid, int64_t n_reads,
+                                                        const unsigned long long* __restrict__ count, unsigned long long threshold, int whole_reads,
+                                                        int64_t* __restrict__ new_len, uint32_t* __restrict__ alive, uint32_t* used,
+                                                        unsigned long long* ctr) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        const int64_t o = read_off[r], n = read_off[r + 1] - o;
+        int64_t kept = 0;
+        for (int64_t i0 = 0; i0 < n; i0 += 64) {
+            const int64_t i = i0 + lane;
+            const uint32_t u = i < n ? seed_uid[o + i] : 0u;
+            const bool keep = i < n && count[u] > threshold;
+            kept += __popcll(__ballot(keep));
+            if (keep && !whole_reads) used[u] = 1u;
+        }
+        const int64_t len = whole_reads ? (kept == n ? n : 0) : kept;
+        if (whole_reads && len > 0)
+            for (int64_t i = lane; i < n; i += 64) used[seed_uid[o + i]] = 1u;
+        if (lane == 0) {
+            new_len[r] = len;
+            alive[r] = len > 0 ? 1u : 0u;
+            if (whole_reads && len == 0) atomicAdd(&ctr[0], 1ULL);
+            if (!whole_reads && kept < n) atomicAdd(&ctr[1], (unsigned long long)(n - kept));
+        }
+    }
+}
+
+// new_off / read_pos / uid_pos: the exclusive scans of new_len / alive / used
+__global__ void __launch_bounds__(256) k_meta_mask_compact(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid,
+                                                           const uint8_t* __restrict__ seed_rev, const uint64_t* __restrict__ uniq,
+                                                           const int64_t* __restrict__ mult, int64_t n_reads, const unsigned long long* __restrict__ count,
+                                                           unsigned long long threshold, const int64_t* __restrict__ new_len,
+                                                           const int64_t* __restrict__ new_off, const uint32_t* __restrict__ read_pos,
+                                                           const uint32_t* __restrict__ uid_pos, int64_t* __restrict__ out_off,
+                                                           uint64_t* __restrict__ out_hash, uint32_t* __restrict__ out_uid, uint8_t* __restrict__ out_rev,
+                                                           int64_t* __restrict__ out_mult) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    if (wave == 0 && lane == 0) out_off[read_pos[n_reads]] = new_off[n_reads];   // (the end of the last surviving read)
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        if (new_len[r] == 0) continue;
+        const int64_t o = read_off[r], n = read_off[r + 1] - o;
+        int64_t at = new_off[r];   // (the read's entries go to [new_off[r], new_off[r] + new_len[r]): as many as are kept below)
+        for (int64_t i0 = 0; i0 < n; i0 += 64) {
+            const int64_t i = i0 + lane;
+            const uint32_t u = i < n ? seed_uid[o + i] : 0u;
+            const bool keep = i < n && count[u] > threshold;
+            const unsigned long long b = __ballot(keep);
+            if (keep) {
+                const int64_t dst = at + __popcll(b & ((1ULL << lane) - 1ULL));
+                out_hash[dst] = uniq[u];
+                out_uid[dst] = uid_pos[u];
+                out_rev[dst] = seed_rev[o + i];
+            }
+            at += __popcll(b);
+        }
+        if (lane == 0) {
+            out_off[read_pos[r]] = new_off[r];
+            out_mult[read_pos[r]] = mult[r];
+        }
+    }
+}
+
+__global__ void k_meta_mask_compact_uniq(const uint64_t* __restrict__ uniq, const unsigned long long* __restrict__ count, const uint32_t* __restrict__ used,
+                                         const uint32_t* __restrict__ uid_pos, int64_t n_uniq, uint64_t* __restrict__ out_uniq,
+                                         int64_t* __restrict__ out_count) {
+    for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n_uniq; u += (int64_t)gridDim.x * blockDim.x) {
+        if (!used[u]) continue;
+        out_uniq[uid_pos[u]] = uniq[u];
+        out_count[uid_pos[u]] = (int64_t)count[u];
+    }
+}
+
+// entries a read may have on the in-LDS path: kMaskQuadratic, or what PMX_META_MASK_LONG lowers it to
+int quadratic_bound() {
+    int bound = kMaskQuadratic;
+    if (const char* e = opt_str(O_META_MASK_LONG)) bound = (int)std::max<long long>(1, std::min<long long>(kMaskQuadratic, atoll(e)));
+    return bound;
+}
+}  // namespace
+
+void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
+    const bool whole_reads = m->lowcov_reads > 0;
+    const unsigned long long threshold = (unsigned long long)(whole_reads ? m->lowcov_reads : m->lowcov_seeds);
+    const int64_t n_reads = m->n_reads, n_seedmers = m->n_seedmers, n_uniq = (int64_t)m->h_uniq.size();
+    hipStream_t st = ctx->stream;
+    const int G = ctx->n_cu * 8;
+    m->masked = true;
+    m->lowcov_reads_dropped = m->lowcov_seeds_removed = 0;
+    m->lowcov_reads_left = n_reads;
+    m->lowcov_hash = m->h_uniq;
+    m->lowcov_count.assign((size_t)n_uniq, 0);
+    if (auto t = ctx->timers.find("meta_mask"); t != ctx->timers.end()) t->second.pending = false;
+    if (n_reads == 0 || n_seedmers == 0) return;   // (merged reads have entries: both or neither)
+
+    // the reads of the sorted path, with the offsets of their keys
+    const int bound = quadratic_bound();
+    std::vector<uint32_t> long_read;
+    std::vector<int64_t> long_off(1, 0);
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const int64_t n = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
+        if (n > bound) { long_read.push_back((uint32_t)r); long_off.push_back(long_off.back() + n); }
+    }
+    const int64_t n_long = (int64_t)long_read.size(), n_keys = long_off.back();
+
+    DevBuf<int64_t> d_mult, d_new_len, d_new_off, d_long_off;
+    DevBuf<unsigned long long> d_count, d_ctr;
+    DevBuf<uint32_t> d_alive, d_read_pos, d_used, d_uid_pos, d_long_read;
+    DevBuf<uint64_t> d_key, d_key_sorted;
+    DevBuf<char> tmp;
+    d_mult.alloc((size_t)n_reads); d_new_len.alloc((size_t)n_reads + 1); d_new_off.alloc((size_t)n_reads + 1);
+    d_alive.alloc((size_t)n_reads + 1); d_read_pos.alloc((size_t)n_reads + 1);
+    d_count.alloc((size_t)n_uniq); d_used.alloc((size_t)n_uniq + 1); d_uid_pos.alloc((size_t)n_uniq + 1);
+    d_ctr.alloc(2);
+    PMX_HIP(hipMemcpyAsync(d_mult.p, m->h_mult.data(), sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    if (n_long > 0) {
+        d_long_read.alloc((size_t)n_long); d_long_off.alloc((size_t)n_long + 1); d_key.alloc((size_t)n_keys); d_key_sorted.alloc((size_t)n_keys);
+        PMX_HIP(hipMemcpyAsync(d_long_read.p, long_read.data(), sizeof(uint32_t) * (size_t)n_long, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_long_off.p, long_off.data(), sizeof(int64_t) * ((size_t)n_long + 1), hipMemcpyHostToDevice, st));
+    }
+
+    timer_begin(ctx, "meta_mask");
+    PMX_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long) * (size_t)n_uniq, st));
+    PMX_HIP(hipMemsetAsync(d_used.p, 0, sizeof(uint32_t) * ((size_t)n_uniq + 1), st));
+    PMX_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long) * 2, st));
+    PMX_HIP(hipMemsetAsync(d_new_len.p + n_reads, 0, sizeof(int64_t), st));   // (the scans run over one entry more: their totals)
+    PMX_HIP(hipMemsetAsync(d_alive.p + n_reads, 0, sizeof(uint32_t), st));
+    if (n_long < n_reads)
+        hipLaunchKernelGGL(k_meta_mask_count, dim3(grid_for(n_reads * 64, 64 * kMaskWaves, G)), dim3(64 * kMaskWaves), 0, st, m->d_read_off.p, m->d_seed_uid.p,
+                           d_mult.p, n_reads, bound, d_count.p);
+    if (n_long > 0) {
+        hipLaunchKernelGGL(k_meta_mask_long_keys, dim3(grid_for(n_long * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_long_read.p,
+                           d_long_off.p, n_long, d_key.p);
+        unsigned end_bit = 33;   // (the uid, and the bits of the greatest ordinal)
+        while (end_bit < 64 && ((uint64_t)(n_long - 1) >> (end_bit - 32)) != 0) ++end_bit;
+        PMX_ROCPRIM(tmp, radix_sort_keys, d_key.p, d_key_sorted.p, (size_t)n_keys, 0u, end_bit, st);
+        hipLaunchKernelGGL(k_meta_mask_long_add, dim3(grid_for(n_keys, 256, G)), dim3(256), 0, st, d_key_sorted.p, n_keys, d_long_read.p, d_mult.p, d_count.p);
+    }
+    hipLaunchKernelGGL(k_meta_mask_flag, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, n_reads, d_count.p,
+                       threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p);
+    PMX_HIP(hipGetLastError());
+    PMX_ROCPRIM(tmp, exclusive_scan, d_new_len.p, d_new_off.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), st);
+    PMX_ROCPRIM(tmp, exclusive_scan, d_alive.p, d_read_pos.p, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st);
+    PMX_ROCPRIM(tmp, exclusive_scan, d_used.p, d_uid_pos.p, 0u, (size_t)n_uniq + 1, rocprim::plus<uint32_t>(), st);
+    // the survivors' sizes, for the buffers of the compaction
+    int64_t left_seedmers = 0;
+    uint32_t left_reads = 0, left_uniq = 0;
+    unsigned long long h_ctr[2] = {0, 0};
+    PMX_HIP(hipMemcpyAsync(&left_seedmers, d_new_off.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(&left_reads, d_read_pos.p + n_reads, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(&left_uniq, d_uid_pos.p + n_uniq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(h_ctr, d_ctr.p, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipStreamSynchronize(st));
+    DevBuf<int64_t> o_off, o_mult, o_count;
+    DevBuf<uint64_t> o_hash, o_uniq;
+    DevBuf<uint32_t> o_uid;
+    DevBuf<uint8_t> o_rev;
+    o_off.alloc((size_t)left_reads + 1); o_mult.alloc((size_t)left_reads); o_count.alloc((size_t)left_uniq);
+    o_hash.alloc((size_t)left_seedmers); o_uid.alloc((size_t)left_seedmers); o_rev.alloc((size_t)left_seedmers); o_uniq.alloc((size_t)left_uniq);
+    hipLaunchKernelGGL(k_meta_mask_compact, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p,
+                       m->d_uniq.p, d_mult.p, n_reads, d_count.p, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p, o_hash.p, o_uid.p,
+                       o_rev.p, o_mult.p);
+    hipLaunchKernelGGL(k_meta_mask_compact_uniq, dim3(grid_for(n_uniq, 256, G)), dim3(256), 0, st, m->d_uniq.p, d_count.p, d_used.p, d_uid_pos.p, n_uniq,
+                       o_uniq.p, o_count.p);
+    PMX_HIP(hipGetLastError());
+    timer_end(ctx, "meta_mask", 1);
+
+    // the host's copies, which meta_assign.hip, the EM and the getters read; the counts before masking
+    std::vector<uint32_t> read_pos((size_t)n_reads + 1);
+    PMX_HIP(hipMemcpyAsync(m->lowcov_count.data(), d_count.p, sizeof(int64_t) * (size_t)n_uniq, hipMemcpyDeviceToHost, st));
+    PMX_HIP(hipMemcpyAsync(read_pos.data(), d_read_pos.p, sizeof(uint32_t) * ((size_t)n_reads + 1), hipMemcpyDeviceToHost, st));
+    m->h_read_off.assign((size_t)left_reads + 1, 0);
+    m->h_mult.resize((size_t)left_reads);
+    m->h_seed_hash.resize((size_t)left_seedmers); m->h_seed_uid.resize((size_t)left_seedmers); m->h_seed_rev.resize((size_t)left_seedmers);
+    m->h_uniq.resize((size_t)left_uniq);
+    PMX_HIP(hipMemcpyAsync(m->h_read_off.data(), o_off.p, sizeof(int64_t) * ((size_t)left_reads + 1), hipMemcpyDeviceToHost, st));
+    if (left_reads > 0) {
+        PMX_HIP(hipMemcpyAsync(m->h_mult.data(), o_mult.p, sizeof(int64_t) * (size_t)left_reads, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(m->h_seed_hash.data(), o_hash.p, sizeof(uint64_t) * (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(m->h_seed_uid.data(), o_uid.p, sizeof(uint32_t) * (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(m->h_seed_rev.data(), o_rev.p, (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(m->h_uniq.data(), o_uniq.p, sizeof(uint64_t) * (size_t)left_uniq, hipMemcpyDeviceToHost, st));
+    }
+    PMX_HIP(hipStreamSynchronize(st));
+    for (int64_t& to : m->h_raw_to_merged)
+        if (to >= 0) to = read_pos[(size_t)to + 1] > read_pos[(size_t)to] ? (int64_t)read_pos[(size_t)to] : -1;
+    m->d_read_off.swap(o_off); m->d_seed_uid.swap(o_uid); m->d_seed_rev.swap(o_rev); m->d_uniq.swap(o_uniq); m->d_uniq_count.swap(o_count);
+    m->n_reads = left_reads;
+    m->n_seedmers = left_seedmers;
+    m->lowcov_reads_dropped = (int64_t)h_ctr[0];
+    m->lowcov_seeds_removed = (int64_t)h_ctr[1];
+    m->lowcov_reads_left = left_reads;
+}
+
+bool meta_masks_set(pmx_ctx* ctx, pmx_meta* m) {
+    m->masked = false;
+    if (m->lowcov_reads <= 0 && m->lowcov_seeds <= 0) {
+        if (auto t = ctx->timers.find("meta_mask"); t != ctx->timers.end()) t->second.pending = false;   // (no such span without a mask)
+        return false;
+    }
+    meta_apply_masks(ctx, m);
+    return true;
+}
+
+// Overlap coefficients after meta_apply_masks: their numerator set is the hashes the surviving lists hold
+// (allSeedmerHashesSet, src/mgsr.cpp:5685-5768), so the placer's histogram is loaded with exactly those, from the device
+// arrays the mask step left (each with its occurrence count before masking: at min_read_support 1 only its presence acts);
+// the raw reads are not seeded again.  --gpus N: every rank holds the whole sample's survivors, nothing is exchanged.
+// Reads: m->d_uniq / d_uniq_count / h_uniq / h_mult.  Leaves: m->oc.
+int meta_masked_overlap_coefficients(pmx_ctx* ctx, pmx_meta* m) {
+    m->oc.assign((size_t)m->n_nodes, 0.0);
+    if (m->n_reads == 0) return PMX_OK;
+    pmx_place_params pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.min_read_support = 1;
+    pmx_place_result res;
+    int64_t n_kept = 0;
+    for (int64_t w : m->h_mult) n_kept += w;
+    int rc = pmx_place_reset(ctx, m->placer);
+    if (rc == PMX_OK) rc = pmx_place_histogram_merge_device(ctx, m->placer, m->d_uniq.p, m->d_uniq_count.p, (int64_t)m->h_uniq.size());
+    if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept, &res);
+    if (rc != PMX_OK) return rc;
+    std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
+    rc = pmx_place_node_outputs(ctx, m->placer, nullptr, nullptr, counts2.data());
+    if (rc != PMX_OK) return rc;
+    for (int64_t v = 0; v < m->n_nodes; ++v)
+        m->oc[(size_t)v] = counts2[2 * (size_t)v + 1] > 0 ? (double)counts2[2 * (size_t)v] / (double)counts2[2 * (size_t)v + 1] : 0.0;
+    return PMX_OK;
+}
+
+extern "C" {
+
+int pmx_meta_set_masks(pmx_meta* m, int64_t mask_reads, int64_t mask_seeds) {
+    if (!m) return PMX_ERR_ARG;
+    if (mask_reads < 0 || mask_seeds < 0) return fail(PMX_ERR_ARG, "pmx_meta_set_masks: a masking parameter must not be negative");
+    if (mask_reads > 0 && mask_seeds > 0) return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
+    m->lowcov_reads = mask_reads;
+    m->lowcov_seeds = mask_seeds;
+    return PMX_OK;
+}
+
+int pmx_meta_mask_info(const pmx_meta* m, int64_t* reads_dropped, int64_t* seeds_removed, int64_t* reads_left) {
+    if (!m) return PMX_ERR_ARG;
+    if (reads_dropped) *reads_dropped = m->masked ? m->lowcov_reads_dropped : 0;
+    if (seeds_removed) *seeds_removed = m->masked ? m->lowcov_seeds_removed : 0;
+    if (reads_left) *reads_left = m->n_reads;
+    return PMX_OK;
+}
+
+int64_t pmx_meta_mask_num_counts(const pmx_meta* m) { return m && m->masked ? (int64_t)m->lowcov_hash.size() : 0; }
+
+int pmx_meta_mask_counts(const pmx_meta* m, uint64_t* hash, int64_t* count, int64_t cap) {
+    if (!m) return PMX_ERR_ARG;
+    if (!m->masked) return fail(PMX_ERR_ARG, "pmx_meta_mask_counts: the last pmx_meta_set_reads ran without a mask");
+    if (cap < (int64_t)m->lowcov_hash.size()) return PMX_ERR_ARG;
+    if (hash) std::copy(m->lowcov_hash.begin(), m->lowcov_hash.end(), hash);
+    if (count) std::copy(m->lowcov_count.begin(), m->lowcov_count.end(), count);
+    return PMX_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// What the two translation units of --meta share: the state behind a pmx_meta handle (api_meta.hip makes and fills it,
-// meta_assign.hip reads the merged reads and the oriented index from it) and the two device helpers both scoring kernels use.
+// What the translation units of --meta share: the state behind a pmx_meta handle (api_meta.hip makes and fills it,
+// meta_assign.hip reads the merged reads and the oriented index from it, meta_mask.hip rewrites the merged reads under a
+// low-coverage mask) and the two device helpers both scoring kernels use.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -96,6 +97,16 @@ struct pmx_meta {
     // br_observed / br_depth of the last pmx_meta_assign when as_breadth
     bool breadth_on = false, as_breadth = false;
     std::vector<uint64_t> total_ref_seeds, br_observed, br_depth;
+    // low-coverage masks (pmx_meta_set_masks; meta_mask.hip; src/mgsr.cpp:2049-2139): the thresholds the next set_reads applies
+    // (at most one above 0), and of the last set_reads: whether it masked, the reference's three numbers, the distinct hashes
+    // of the merged reads BEFORE masking (ascending) with their occurrence counts, and on the device the counts of the
+    // surviving distinct hashes (one per entry of d_uniq)
+    int64_t lowcov_reads = 0, lowcov_seeds = 0;
+    bool masked = false;
+    int64_t lowcov_reads_dropped = 0, lowcov_seeds_removed = 0, lowcov_reads_left = 0;
+    std::vector<uint64_t> lowcov_hash;
+    std::vector<int64_t> lowcov_count;
+    pmx::DevBuf<int64_t> d_uniq_count;
     // taxonomy (pmx_meta_set_taxonomy; max_taxa 0 = none) and the ambiguity thresholds (pmx_meta_set_ambiguous).  The node table:
     // the taxa S(v) of every node's subtree, ascending, max_taxa slots a node; h_tx_over: bit v = |S(v)| > max_taxa (then no ids)
     int32_t max_taxa = 0, amb_abs = 0;
@@ -108,3 +119,13 @@ struct pmx_meta {
     pmx::DevBuf<uint32_t> tx_ids;
     pmx::DevBuf<unsigned long long> tx_over;
 };
+
+// meta_mask.hip, a step of pmx_meta_set_reads (after the lists were uploaded, when a mask is set): counts every distinct hash
+// of the merged reads, drops reads (lowcov_reads) or list entries (lowcov_seeds) whose count is at most the threshold and
+// leaves m->h_* / d_* / n_reads / n_seedmers / h_raw_to_merged describing the survivors.  Throws pmx::HipError.
+void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m);
+// what pmx_meta_set_reads asks after upload_lists: false when no mask is set (m->masked cleared, no "meta_mask" span, nothing
+// launched or allocated), else meta_apply_masks has run
+bool meta_masks_set(pmx_ctx* ctx, pmx_meta* m);
+// ... and then the overlap coefficients of the survivors (m->oc), from the device arrays that step left; a place-API code
+int meta_masked_overlap_coefficients(pmx_ctx* ctx, pmx_meta* m);

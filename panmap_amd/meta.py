@@ -115,6 +115,27 @@ class Meta:
         """--dust: the next set_reads drops reads whose DUST score is non-zero and above `threshold` (100 = off)"""
         check(lib.pmx_meta_set_dust(self._h, float(threshold)), "pmx_meta_set_dust")
 
+    def set_masks(self, reads: int = 0, seeds: int = 0):
+        """--mask-reads / --mask-seeds (src/mgsr.cpp:2049-2139) for the set_reads calls that follow; at most one above 0.  With
+        count[h] = the summed multiplicities of the merged reads that carry hash h: `reads` = T drops every merged read with a
+        seedmer of count <= T, `seeds` = T removes those seedmers from the lists (a read left empty goes).  Everything after
+        set_reads is of the survivors; assign() refuses such a read set.  --gpus N: the same masks on every rank."""
+        check(lib.pmx_meta_set_masks(self._h, int(reads), int(seeds)), "pmx_meta_set_masks")
+
+    def mask_info(self):
+        """of the last set_reads: merged reads dropped by mask-reads, seedmers removed by mask-seeds, merged reads left"""
+        d, s, n = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib.pmx_meta_mask_info(self._h, C.byref(d), C.byref(s), C.byref(n)), "pmx_meta_mask_info")
+        return dict(reads_dropped=int(d.value), seeds_removed=int(s.value), reads_left=int(n.value))
+
+    def mask_counts(self):
+        """(hash, count): the distinct hashes of the merged reads BEFORE masking, ascending, with their occurrence counts
+        (a set_reads with a mask set must have run)"""
+        n = int(lib.pmx_meta_mask_num_counts(self._h))
+        h, c = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.int64)
+        check(lib.pmx_meta_mask_counts(self._h, h.ctypes.data, c.ctypes.data, n), "pmx_meta_mask_counts")
+        return h[:n], c[:n]
+
     def score(self, top_oc: int = 1000, candidates=None):
         if candidates is not None:
             c = np.ascontiguousarray(candidates, np.uint32)
