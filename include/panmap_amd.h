@@ -587,6 +587,52 @@ int pmx_meta_mask_info(const pmx_meta *m, int64_t *reads_dropped, int64_t *seeds
  * pmx_meta_mask_counts is PMX_ERR_ARG then); either array may be NULL */
 int64_t pmx_meta_mask_num_counts(const pmx_meta *m);
 int pmx_meta_mask_counts(const pmx_meta *m, uint64_t *hash, int64_t *count, int64_t cap);
+/* --amplicon-depth FILE, --mask-reads-relative-frequency X, --mask-seeds-relative-frequency X (src/main.cpp:2032-2040;
+ * extractReadSequences, src/mgsr.cpp:1216-1342; initializeQueryData, :1774-2235).  pmx_meta_set_amplicons: the amplicon of every
+ * raw read of the pmx_meta_set_reads calls that follow, until cleared with NULL / 0 -- group_of_read[r] in [0, n_groups], the
+ * value n_groups meaning "not listed in the file" (the reference's last group).  A set_reads with another n_reads, or with a
+ * value out of range, is PMX_ERR_ARG.  With amplicons set:
+ *   - reads are merged by seedmer list WITHIN their amplicon: the same list in two amplicons stays two merged reads, each with
+ *     its own multiplicity.  Merged reads are ordered by (amplicon, hash list, orientation list);
+ *   - a mask counts within the amplicon: count[g][h] = the summed multiplicities of the merged reads of g that carry h, and a
+ *     read of g is masked against the threshold of g.  T_g = the absolute parameter of pmx_meta_set_masks, or under a relative
+ *     parameter rf (size_t)(rf * (double)N_g), N_g = the raw reads of g passed to set_reads (before --dust, reads without
+ *     seedmers included).  The unlisted group always takes the absolute parameter, so a relative parameter leaves it unmasked;
+ *     a threshold of 0 masks nothing in its group.  numMaskReads / numMaskSeeds (pmx_meta_mask_info) are summed over the groups,
+ *     pmx_meta_mask_counts reports per distinct hash of the sample the sum over the groups;
+ *   - amplicons alone (no mask parameter above 0) only change the merge: no mask step runs;
+ *   - pmx_meta_raw_to_merged names the merged read of the raw read's own amplicon; pmx_meta_assign is PMX_ERR_UNSUPPORTED
+ *     (the reference's batch reader takes no such file).
+ * pmx_meta_set_relative_masks: both 0 = off; a negative value is PMX_ERR_ARG; more than one of the four masking parameters
+ * above 0 is PMX_ERR_ARG, "Only one masking parameter can be set at a time" (checked by whichever setter is called second and by
+ * set_reads).  A relative parameter without amplicons does nothing in the reference (its single group is the unlisted one);
+ * here set_reads refuses it with PMX_ERR_ARG.  A read set of 2^32 - 1 list entries or more under amplicons with a mask is
+ * PMX_ERR_CAPACITY.  --gpus N: every rank passes the groups of its own shard with the same n_groups; ranks that disagree on
+ * n_groups all return PMX_ERR_ARG from set_reads. */
+int pmx_meta_set_amplicons(pmx_meta *m, const int32_t *group_of_read, int64_t n_reads, int32_t n_groups);
+int pmx_meta_set_relative_masks(pmx_meta *m, double reads_rf, double seeds_rf);
+/* of the last pmx_meta_set_reads, when it ran with amplicons (PMX_ERR_ARG otherwise): the amplicon of every merged read (cap >=
+ * pmx_meta_num_reads); per group g in [0, n_groups] (cap >= pmx_meta_num_amplicon_groups = n_groups + 1, 0 without amplicons)
+ * its raw reads N_g, the threshold applied (0 without a mask), its merged reads before masking and its merged reads left; any
+ * pointer may be NULL */
+int pmx_meta_read_amplicons(const pmx_meta *m, int32_t *amplicon, int64_t cap);
+int32_t pmx_meta_num_amplicon_groups(const pmx_meta *m);
+int pmx_meta_amplicon_info(const pmx_meta *m, int64_t *raw_reads, int64_t *threshold, int64_t *merged_before, int64_t *merged_left, int64_t cap);
+/* the (group, hash, count) triples BEFORE masking, ascending by (group, hash); pmx_meta_amplicon_num_counts of them (0, and
+ * pmx_meta_amplicon_counts PMX_ERR_ARG, unless the last pmx_meta_set_reads ran with amplicons AND a mask); any array may be NULL */
+int64_t pmx_meta_amplicon_num_counts(const pmx_meta *m);
+int pmx_meta_amplicon_counts(const pmx_meta *m, int32_t *group, uint64_t *hash, int64_t *count, int64_t cap);
+/* Host only.  The table of --amplicon-depth: one `read id <TAB> primer id` per line; groups numbered by first appearance of the
+ * primer id; a later line for a read id replaces an earlier one (the earlier primer keeps its group, possibly empty); empty
+ * lines are skipped.  PMX_ERR_IO: the file cannot be read; PMX_ERR_FORMAT (the message holds the line number): a line that does
+ * not have exactly two tab-separated non-empty fields.  pmx_amplicons_lookup: the group of a read name (the FASTQ header up to
+ * the first white space), -1 when unlisted. */
+typedef struct pmx_amplicons pmx_amplicons;
+int pmx_amplicons_load(const char *path, pmx_amplicons **out);
+void pmx_amplicons_free(pmx_amplicons *a);
+int32_t pmx_amplicons_num_groups(const pmx_amplicons *a);
+const char *pmx_amplicons_group_name(const pmx_amplicons *a, int32_t g);
+int32_t pmx_amplicons_lookup(const pmx_amplicons *a, const char *read_name);
 /* --meta --gpus N: call after pmx_meta_create, before pmx_meta_set_reads (`d` on the same context, kept alive by the caller).
  * From then on set_reads, score and em are COLLECTIVE: every rank calls them in the same order, set_reads with its own shard of
  * the raw reads.  The merged reads, overlap coefficients, candidates, haplotypes and em_info are then those of one rank over the
@@ -823,7 +869,8 @@ int64_t pmx_options_describe(char *buf, int64_t cap);
    pmx_meta_score; "meta_assign" = the device work of pmx_meta_assign up to the scan of the node counts, "meta_assign_emit" = its
    list kernel, both summed over the call's chunks; with a taxonomy "meta_assign" ends before the taxonomy kernels and
    "meta_assign_taxa" holds them and that scan; with pmx_meta_set_breadth "meta_breadth" = the breadth kernels, summed likewise, and "meta_breadth_count" = the column
-   count kernel among them); < 0: no such span in the last call */
+   count kernel among them; "meta_mask" = the mask step of pmx_meta_set_reads, and with amplicons "meta_mask_sort" = the sort
+   of its (amplicon, hash) keys inside it); < 0: no such span in the last call */
 double pmx_last_kernel_ms(pmx_ctx *ctx, const char *name);
 
 #ifdef __cplusplus

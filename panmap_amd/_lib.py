@@ -213,6 +213,18 @@ SIGNATURES = {
     "pmx_meta_mask_info": (_i32, [_vp, _vp, _vp, _vp]),
     "pmx_meta_mask_num_counts": (_i64, [_vp]),
     "pmx_meta_mask_counts": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_meta_set_amplicons": (_i32, [_vp, _vp, _i64, _i32]),
+    "pmx_meta_set_relative_masks": (_i32, [_vp, C.c_double, C.c_double]),
+    "pmx_meta_read_amplicons": (_i32, [_vp, _vp, _i64]),
+    "pmx_meta_num_amplicon_groups": (_i32, [_vp]),
+    "pmx_meta_amplicon_info": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64]),
+    "pmx_meta_amplicon_num_counts": (_i64, [_vp]),
+    "pmx_meta_amplicon_counts": (_i32, [_vp, _vp, _vp, _vp, _i64]),
+    "pmx_amplicons_load": (_i32, [_cp, _vp]),
+    "pmx_amplicons_free": (None, [_vp]),
+    "pmx_amplicons_num_groups": (_i32, [_vp]),
+    "pmx_amplicons_group_name": (_cp, [_vp, _i32]),
+    "pmx_amplicons_lookup": (_i32, [_vp, _cp]),
     "pmx_meta_attach_dist": (_i32, [_vp, _vp]),
     "pmx_meta_row_range": (_i32, [_vp, _vp, _vp]),
     "pmx_read_dust": (C.c_double, [_cp, _i64, _i32]),

@@ -384,7 +384,9 @@ int cmp_lists(const uint64_t* xh, const uint8_t* xv, int64_t xn, const uint64_t*
 void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int k) {
     pmx_ctx* ctx = m->ctx;
     const int world = (int)(counts.size() / (size_t)k);
-    auto run_bytes = [](int64_t nr, int64_t ns) { return (size_t)(16 * nr + 8 * ns + ((ns + 7) & ~(int64_t)7)); };
+    const bool amps = m->amp_on;   // (the same on every rank: merge_over_ranks checked); then the amplicon of every read ends the run
+    auto amp_at = [](int64_t nr, int64_t ns) { return (size_t)(16 * nr + 8 * ns + ((ns + 7) & ~(int64_t)7)); };
+    auto run_bytes = [&](int64_t nr, int64_t ns) { return amp_at(nr, ns) + (amps ? (size_t)((4 * nr + 7) & ~(int64_t)7) : 0); };
     size_t mx = 8;
     for (int r = 0; r < world; ++r) mx = std::max(mx, run_bytes(counts[(size_t)r * k + 3], counts[(size_t)r * k + 4]));
     // this rank's run: lengths, multiplicities (int64), hashes (uint64), orientations (bytes)
@@ -399,6 +401,7 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
         memcpy(mine.data() + 16 * nr, m->h_seed_hash.data(), 8 * (size_t)ns);
         memcpy(mine.data() + 16 * nr + 8 * ns, m->h_seed_rev.data(), (size_t)ns);
     }
+    if (amps && nr > 0) memcpy(mine.data() + amp_at(nr, ns), m->h_read_amp.data(), 4 * (size_t)nr);
     DevBuf<char> d_mine, d_all;
     d_mine.alloc(mx);
     d_all.alloc(mx * (size_t)world);
@@ -407,18 +410,21 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
     dist_all_gather(m->dist, d_mine.p, mx, d_all.p);
     PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, ctx->stream));
     PMX_HIP(hipStreamSynchronize(ctx->stream));
-    struct Run { const int64_t *len, *mult; const uint64_t* h; const uint8_t* v; int64_t n, i, at; };
+    struct Run { const int64_t *len, *mult; const uint64_t* h; const uint8_t* v; const int32_t* amp; int64_t n, i, at; };
     std::vector<Run> runs;
     for (int r = 0; r < world; ++r) {
         const char* b = all.data() + (size_t)r * mx;
         const int64_t rn = counts[(size_t)r * k + 3], rs = counts[(size_t)r * k + 4];
-        runs.push_back(Run{(const int64_t*)b, (const int64_t*)(b + 8 * rn), (const uint64_t*)(b + 16 * rn), (const uint8_t*)(b + 16 * rn + 8 * rs), rn, 0, 0});
+        runs.push_back(Run{(const int64_t*)b, (const int64_t*)(b + 8 * rn), (const uint64_t*)(b + 16 * rn), (const uint8_t*)(b + 16 * rn + 8 * rs),
+                           amps ? (const int32_t*)(b + amp_at(rn, rs)) : nullptr, rn, 0, 0});
     }
-    auto cmp_heads = [](const Run& x, const Run& y) {
+    auto cmp_heads = [amps](const Run& x, const Run& y) {
+        if (amps && x.amp[x.i] != y.amp[y.i]) return x.amp[x.i] < y.amp[y.i] ? -1 : 1;
         return cmp_lists(x.h + x.at, x.v + x.at, x.len[x.i], y.h + y.at, y.v + y.at, y.len[y.i]);
     };
     m->h_read_off.assign(1, 0);
     m->h_seed_hash.clear(); m->h_seed_rev.clear(); m->h_mult.clear();
+    std::vector<int32_t> merged_amp;
     for (;;) {
         int lo = -1;
         for (int r = 0; r < world; ++r)
@@ -429,6 +435,7 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
         m->h_seed_hash.insert(m->h_seed_hash.end(), head.h + head.at, head.h + head.at + len);
         m->h_seed_rev.insert(m->h_seed_rev.end(), head.v + head.at, head.v + head.at + len);
         m->h_read_off.push_back((int64_t)m->h_seed_hash.size());
+        if (amps) merged_amp.push_back(head.amp[head.i]);
         int64_t mult = 0;
         for (int r = lo; r < world; ++r) {   // (a run holds a list once; the ranks below `lo` hold greater heads)
             Run& x = runs[r];
@@ -440,6 +447,7 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
         }
         m->h_mult.push_back(mult);
     }
+    m->h_read_amp.swap(merged_amp);
     m->n_reads = (int64_t)m->h_mult.size();
     m->n_seedmers = (int64_t)m->h_seed_hash.size();
 }
@@ -492,8 +500,12 @@ struct MetaReads {
         DevBuf<unsigned long long> d_ctr;  // the seeding kernel's counters (not read here)
     };
 
+    // amplicons (pmx_meta_set_amplicons): whether they are set; then m->amp_of_raw holds the amplicon of every read the caller passed
+    const bool amplicons;
+
     MetaReads(pmx_ctx* c, pmx_meta* mm, const char* cc, const int64_t* off, int64_t n)
-        : ctx(c), m(mm), concat(cc), offsets(off), n_reads(n), n_raw(n), n_kept_all(n) {}
+        : ctx(c), m(mm), concat(cc), offsets(off), n_reads(n), n_raw(n), n_kept_all(n), amplicons(mm->amp_set) {}
+    int32_t amp_of(int64_t kept) const { return m->amp_of_raw[(size_t)(kept_raw.empty() ? kept : kept_raw[(size_t)kept])]; }
     struct ListView { const uint64_t* h; const uint8_t* v; int64_t n; };
     ListView list(int64_t r) const { return ListView{r_hash.data() + r_off[(size_t)r], r_rev.data() + r_off[(size_t)r], r_off[(size_t)r + 1] - r_off[(size_t)r]}; }
     // (lexicographic on the hash list, then on the orientation list: the order the vector comparisons gave)
@@ -503,7 +515,8 @@ struct MetaReads {
     int seedmer_lists();
     int seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc);
     void merge_equal_lists();
-    void merge_over_ranks();
+    void amplicon_tallies();
+    int merge_over_ranks();
     void upload_lists();
     int overlap_coefficients();
 };
@@ -613,14 +626,35 @@ void MetaReads::merge_equal_lists() {
     std::vector<int64_t> order;
     for (int64_t r = 0; r < n_reads; ++r)
         if (r_off[(size_t)r + 1] > r_off[(size_t)r]) order.push_back(r);
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { const int c = cmp(a, b); return c < 0 || (c == 0 && a < b); });
+    // amplicons: reads are merged within their amplicon only, the amplicon is the first key of the order; N_g counts the reads
+    // the caller passed (readSequencesByGroup[groupId].size(): before DUST, reads without seedmers included)
+    m->amp_on = amplicons;
+    m->n_amp = amplicons ? m->amp_n_groups + 1 : 0;
+    m->h_read_amp.clear();
+    m->ampc_group.clear(); m->ampc_hash.clear(); m->ampc_count.clear();
+    m->amp_raw.assign((size_t)m->n_amp, 0);
+    m->amp_thr.assign((size_t)m->n_amp, 0);
+    std::vector<int32_t> group;   // per kept read
+    if (amplicons) {
+        for (int32_t g : m->amp_of_raw) ++m->amp_raw[(size_t)g];
+        group.resize((size_t)n_reads);
+        for (int64_t r = 0; r < n_reads; ++r) group[(size_t)r] = amp_of(r);
+        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+            if (group[(size_t)a] != group[(size_t)b]) return group[(size_t)a] < group[(size_t)b];
+            const int c = cmp(a, b);
+            return c < 0 || (c == 0 && a < b);
+        });
+    } else {
+        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { const int c = cmp(a, b); return c < 0 || (c == 0 && a < b); });
+    }
     m->n_raw_reads = n_raw;
     m->n_dust_dropped = n_dusty;
     m->h_read_off.assign(1, 0);
     m->h_seed_hash.clear(); m->h_seed_rev.clear(); m->h_mult.clear();
     m->h_raw_to_merged.assign((size_t)n_raw, -1);
     for (size_t i = 0; i < order.size(); ++i) {
-        const bool copy = i > 0 && cmp(order[i - 1], order[i]) == 0;
+        const bool copy = i > 0 && (!amplicons || group[(size_t)order[i - 1]] == group[(size_t)order[i]]) && cmp(order[i - 1], order[i]) == 0;
+        if (amplicons && !copy) m->h_read_amp.push_back(group[(size_t)order[i]]);
         const int64_t raw = kept_raw.empty() ? order[i] : kept_raw[(size_t)order[i]];
         m->h_raw_to_merged[(size_t)raw] = (int64_t)m->h_mult.size() - (copy ? 1 : 0);   // the merged read made last, or the one made now
         if (copy) { ++m->h_mult.back(); continue; }
@@ -632,17 +666,42 @@ void MetaReads::merge_equal_lists() {
     }
     m->n_reads = (int64_t)m->h_mult.size();
     m->n_seedmers = (int64_t)m->h_seed_hash.size();
+    amplicon_tallies();
 }
 
-// --gpus N: the ranks' runs become the whole sample's; the raw, DUST-dropped and kept read counts are summed.
+// the merged reads of every amplicon, before a mask (and left, until a mask says otherwise)
+void MetaReads::amplicon_tallies() {
+    m->amp_before.assign((size_t)m->n_amp, 0);
+    for (int32_t g : m->h_read_amp) ++m->amp_before[(size_t)g];
+    m->amp_left = m->amp_before;
+}
+
+// --gpus N: the ranks' runs become the whole sample's; the raw, DUST-dropped and kept read counts are summed, with amplicons
+// also the raw reads of every amplicon (the run carries the amplicon of every merged read, and the merge compares it first).
+// The sixth count is the rank's number of amplicon groups + 1 (0 without amplicons): ranks that disagree all return
+// PMX_ERR_ARG here, after the exchange that showed it to each of them and before any further collective.
 // Reads and leaves what merge_equal_lists left, now for the whole sample, on every rank.
-void MetaReads::merge_over_ranks() {
-    const int64_t mine[5] = {n_raw, n_dusty, n_reads, m->n_reads, m->n_seedmers};
-    const std::vector<int64_t> counts = dist_exchange_counts(m->dist, mine, 5);
+int MetaReads::merge_over_ranks() {
+    const int k = 6;
+    const int64_t mine[k] = {n_raw, n_dusty, n_reads, m->n_reads, m->n_seedmers, (int64_t)m->n_amp};
+    const std::vector<int64_t> counts = dist_exchange_counts(m->dist, mine, k);
+    const size_t world = counts.size() / k;
+    for (size_t r = 0; r < world; ++r)
+        if (counts[k * r + 5] != counts[5])
+            return fail(PMX_ERR_ARG, "pmx_meta_set_reads: the ranks disagree on the amplicon groups (rank " + std::to_string(r) + " has " +
+                                         std::to_string(counts[k * r + 5] - 1) + ", rank 0 has " + std::to_string(counts[5] - 1) + "; -1 = none set)");
     m->n_raw_reads = m->n_dust_dropped = n_kept_all = 0;
-    for (size_t r = 0; r < counts.size() / 5; ++r) { m->n_raw_reads += counts[5 * r]; m->n_dust_dropped += counts[5 * r + 1]; n_kept_all += counts[5 * r + 2]; }
-    merge_runs_over_ranks(m, counts, 5);
+    for (size_t r = 0; r < world; ++r) { m->n_raw_reads += counts[k * r]; m->n_dust_dropped += counts[k * r + 1]; n_kept_all += counts[k * r + 2]; }
+    if (amplicons) {
+        const std::vector<int64_t> raw = dist_exchange_counts(m->dist, m->amp_raw.data(), m->n_amp);
+        m->amp_raw.assign((size_t)m->n_amp, 0);
+        for (size_t r = 0; r < world; ++r)
+            for (int32_t g = 0; g < m->n_amp; ++g) m->amp_raw[(size_t)g] += raw[r * (size_t)m->n_amp + (size_t)g];
+    }
+    merge_runs_over_ranks(m, counts, k);
+    amplicon_tallies();
     m->h_raw_to_merged.clear();   // (the merged reads are the whole sample's now: this rank's map no longer names them)
+    return PMX_OK;
 }
 
 // Reads: the merged lists in m->h_*.  Leaves: m->h_uniq (the distinct hashes, ascending) and, on the device, the offsets,
@@ -1159,12 +1218,28 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     if (!ctx || !m || !offsets || n_reads < 0 || (!concat && n_reads > 0)) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
+    // the masking parameters and the amplicons as the setters left them (src/mgsr.cpp:2049-2053; a relative parameter without
+    // amplicons would do nothing in the reference, whose single group is the unlisted one: refused)
+    const bool relative = m->lowcov_reads_rf > 0 || m->lowcov_seeds_rf > 0;
+    if ((m->lowcov_reads > 0) + (m->lowcov_seeds > 0) + (m->lowcov_reads_rf > 0) + (m->lowcov_seeds_rf > 0) > 1)
+        return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");
+    if (relative && !m->amp_set)
+        return fail(PMX_ERR_ARG, "pmx_meta_set_reads: a relative-frequency mask needs amplicons (pmx_meta_set_amplicons): its threshold is a share of "
+                                 "the reads of an amplicon group, and without groups every read is unlisted and takes no relative threshold");
+    if (m->amp_set && (int64_t)m->amp_of_raw.size() != n_reads)
+        return fail(PMX_ERR_ARG, "pmx_meta_set_reads: " + std::to_string(n_reads) + " reads, but pmx_meta_set_amplicons named the amplicons of " +
+                                     std::to_string(m->amp_of_raw.size()));
     MetaReads R(ctx, m, concat, offsets, n_reads);
     R.drop_dusty();
     int rc = R.seedmer_lists();
     if (rc != PMX_OK) return rc;
     R.merge_equal_lists();
-    if (m->dist) R.merge_over_ranks();
+    if (m->dist) {
+        rc = R.merge_over_ranks();
+        if (rc != PMX_OK) return rc;
+    }
+    if (m->amp_on && (m->lowcov_reads > 0 || m->lowcov_seeds > 0 || relative) && m->n_seedmers >= (int64_t)UINT32_MAX)
+        return fail(PMX_ERR_CAPACITY, "pmx_meta_set_reads: a mask within amplicons indexes the list entries with 32 bits; the merged reads hold 2^32 - 1 or more");
     R.upload_lists();
     // the low-coverage masks (src/mgsr.cpp:2049-2139), when one is set: the reads that survive are the sample from here on
     rc = meta_masks_set(ctx, m) ? meta_masked_overlap_coefficients(ctx, m) : R.overlap_coefficients();

@@ -55,6 +55,10 @@ struct Config {
     // `mask_options`: the ones given, in order
     int64_t mask_reads = 0, mask_seeds = 0;
     std::vector<std::string> mask_options;
+    // --amplicon-depth FILE (read id <TAB> primer id) and the masks whose threshold is a share of an amplicon's reads
+    // (src/main.cpp:2032-2040, src/mgsr.cpp:1216-1342, 2062-2075); they are listed in mask_options too
+    std::string amplicon_depth;
+    double mask_reads_rf = 0.0, mask_seeds_rf = 0.0;
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
     int em_max_iterations = 1000, em_max_rounds = 5;
@@ -100,6 +104,10 @@ void usage() {
           "      --mask-reads N         --meta: drop every read that carries a k-min-mer seen at most N times in the whole sample (counted\n"
           "                             over the distinct reads, each with its number of copies)      --mask-seeds N   remove those\n"
           "                             k-min-mers from the reads instead (one of the two; also with --gpus N; not with --filter-and-assign)\n"
+          "      --amplicon-depth TSV   --meta: `read id <TAB> primer id` per line; reads are collapsed and the masks count within the reads\n"
+          "                             of a primer (amplicon), the reads that are not listed forming one more group\n"
+          "      --mask-reads-relative-frequency F / --mask-seeds-relative-frequency F   as --mask-reads / --mask-seeds with the threshold\n"
+          "                             int(F x the reads of the amplicon); needs --amplicon-depth; unlisted reads stay unmasked (one of the four)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange\n"
           "      --refine               re-rank the top candidates by aligning the reads against them\n"
@@ -175,8 +183,9 @@ Config parse(int argc, char** argv) {
         }
         else if (a == "--mask-reads") { c.mask_reads = atoll(v().c_str()); c.mask_options.push_back(a); }
         else if (a == "--mask-seeds") { c.mask_seeds = atoll(v().c_str()); c.mask_options.push_back(a); }
-        else if (a == "--amplicon-depth" || a == "--mask-reads-relative-frequency" || a == "--mask-seeds-relative-frequency")
-            die("option " + a + " is not accepted: it needs amplicon groups, which this build does not make");
+        else if (a == "--amplicon-depth") { c.amplicon_depth = v(); c.mask_options.push_back(a); }
+        else if (a == "--mask-reads-relative-frequency") { c.mask_reads_rf = atof(v().c_str()); c.mask_options.push_back(a); }
+        else if (a == "--mask-seeds-relative-frequency") { c.mask_seeds_rf = atof(v().c_str()); c.mask_options.push_back(a); }
         else if (a == "--jplace" || a == "--mask-read-ends")
             die("option " + a + " is not accepted: --filter-and-assign is built without jplace output and read-end masking");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
@@ -979,7 +988,28 @@ int run_meta(Config c) {
     if (!c.mask_options.empty() && c.filter_and_assign)   // (initializeQueryDataBatch, src/mgsr.cpp:1575, never masks)
         die("option " + c.mask_options[0] + " is not accepted with --filter-and-assign: the reference's reader for that mode never masks");
     if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
-    if (c.mask_reads > 0 && c.mask_seeds > 0) die("Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
+    if (c.mask_reads_rf < 0.0 || c.mask_seeds_rf < 0.0)
+        die("--mask-reads-relative-frequency and --mask-seeds-relative-frequency must not be negative");
+    if ((c.mask_reads > 0) + (c.mask_seeds > 0) + (c.mask_reads_rf > 0.0) + (c.mask_seeds_rf > 0.0) > 1)
+        die("Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
+    // the amplicons: read the table before anything else is opened.  (A relative mask without the file does nothing in the
+    // reference, whose single group is then the unlisted one: refused)
+    struct Amplicons {
+        pmx_amplicons* a = nullptr;
+        ~Amplicons() { pmx_amplicons_free(a); }
+    } amplicons;
+    if (c.amplicon_depth.empty())
+        for (const std::string& o : c.mask_options)
+            if (o == "--mask-reads-relative-frequency" || o == "--mask-seeds-relative-frequency")
+                die("option " + o + " is not accepted without --amplicon-depth: its threshold is a share of the reads of amplicon groups, which this "
+                    "build does not make without that file");
+    if (!c.amplicon_depth.empty()) {
+        const int rc = pmx_amplicons_load(c.amplicon_depth.c_str(), &amplicons.a);
+        if (rc == PMX_ERR_IO)
+            die("option --amplicon-depth is not accepted: cannot read " + c.amplicon_depth + ", the file that names the amplicon groups, which this build "
+                "does not make by itself");
+        if (rc != PMX_OK) die(std::string("option --amplicon-depth is not accepted: ") + pmx_last_error());
+    }
     // the taxonomy filter: read the table before anything else is opened
     const bool with_taxonomy = !c.taxonomic_metadata.empty();
     if ((with_taxonomy || !c.taxonomy_options.empty()) && !c.filter_and_assign)
@@ -1031,15 +1061,35 @@ int run_meta(Config c) {
     if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
     check(pmx_meta_set_dust(m, c.dust), "--dust");
     check(pmx_meta_set_masks(m, c.mask_reads, c.mask_seeds), "--mask-reads / --mask-seeds");
+    check(pmx_meta_set_relative_masks(m, c.mask_reads_rf, c.mask_seeds_rf), "--mask-reads-relative-frequency / --mask-seeds-relative-frequency");
+    if (amplicons.a) {   // the amplicon of every read of this rank's shard, by its own name (mates one by one); unlisted: the last group
+        const int32_t n_groups = pmx_amplicons_num_groups(amplicons.a);
+        std::vector<int32_t> group((size_t)(hi - lo));
+        for (int64_t r = lo; r < hi; ++r) {
+            const int32_t g = pmx_amplicons_lookup(amplicons.a, reads.name(r).c_str());
+            group[(size_t)(r - lo)] = g < 0 ? n_groups : g;
+        }
+        check(pmx_meta_set_amplicons(m, group.data(), hi - lo, n_groups), "--amplicon-depth");
+        if (!c.quiet) {   // (over the whole sample, whatever the shard)
+            int64_t unlisted = 0;
+            for (int64_t r = 0; r < reads.n_reads; ++r) unlisted += pmx_amplicons_lookup(amplicons.a, reads.name(r).c_str()) < 0;
+            say(c, "meta", "Amplicons: " + std::to_string(n_groups) + " groups in " + c.amplicon_depth + ", " + std::to_string(unlisted) + " of " +
+                               std::to_string(reads.n_reads) + " reads not listed");
+        }
+    }
     check(pmx_meta_set_reads(ctx, m, reads.concat.data(), reads.off.data() + lo, hi - lo), "seeding the reads");
-    if (c.mask_reads > 0 || c.mask_seeds > 0) {   // the reference's two lines (src/mgsr.cpp:2220-2230)
+    if (c.mask_reads > 0 || c.mask_seeds > 0 || c.mask_reads_rf > 0.0 || c.mask_seeds_rf > 0.0) {   // the reference's two lines (src/mgsr.cpp:2220-2230)
         int64_t dropped = 0, removed = 0, left = 0;
         check(pmx_meta_mask_info(m, &dropped, &removed, &left), "the numbers of the masks");
-        say(c, "meta", c.mask_reads > 0 ? "Mask-reads " + std::to_string(c.mask_reads) + " turned on: " + std::to_string(dropped) +
-                                              " reads containing low coverage kminmers will be skipped during placement and EM... Total reads to process: " +
-                                              std::to_string(left)
-                                        : "Mask-seeds " + std::to_string(c.mask_seeds) + " turned on: " + std::to_string(removed) +
-                                              " seeds are removed during placement and EM... Total reads to process: " + std::to_string(left));
+        char rf[64];   // (a relative parameter as the reference's stream prints a double)
+        snprintf(rf, sizeof(rf), "%g", c.mask_reads_rf > 0.0 ? c.mask_reads_rf : c.mask_seeds_rf);
+        const bool whole_reads = c.mask_reads > 0 || c.mask_reads_rf > 0.0;
+        const std::string value = c.mask_reads > 0 ? std::to_string(c.mask_reads) : c.mask_seeds > 0 ? std::to_string(c.mask_seeds) : std::string(rf);
+        say(c, "meta", whole_reads ? "Mask-reads " + value + " turned on: " + std::to_string(dropped) +
+                                         " reads containing low coverage kminmers will be skipped during placement and EM... Total reads to process: " +
+                                         std::to_string(left)
+                                   : "Mask-seeds " + value + " turned on: " + std::to_string(removed) +
+                                         " seeds are removed during placement and EM... Total reads to process: " + std::to_string(left));
     }
     if (c.filter_and_assign) {
         write_assigned(c, run, reads, taxonomy.t);

@@ -851,6 +851,9 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     if (m->masked)   // (the reference's reader for this mode, initializeQueryDataBatch, never masks: src/mgsr.cpp:1575)
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with a low-coverage mask (pmx_meta_set_masks), which --filter-and-assign "
                                          "does not have: clear the masks and set the reads again");
+    if (m->amp_on)   // (that reader takes no amplicon file either)
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with amplicons (pmx_meta_set_amplicons), which --filter-and-assign does not "
+                                         "have: clear the amplicons and set the reads again");
     if (m->max_taxa > 0 && discard > 0.0 && (m->amb_abs > 0 || m->amb_ratio > 0.0))
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: a discard threshold together with an ambiguity threshold (the reference's records then depend "
                                          "on the order of a node's seed changes)");

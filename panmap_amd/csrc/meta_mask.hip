@@ -27,6 +27,19 @@
 //     hash, new uid, orientation per entry, offset and multiplicity per read.  k_meta_mask_compact_uniq: the surviving
 //     distinct hashes with their counts.
 // All sums are integers: nothing depends on the order of the atomics.
+//
+// With amplicons (--amplicon-depth; pmx_meta_set_amplicons; src/mgsr.cpp:1216-1342, :2062-2075) the rule holds within every
+// amplicon: count[g][h] is over the merged reads of g, and a read of g is masked against the threshold of g -- the absolute
+// parameter, or (size_t)(relative parameter * raw reads of g); the unlisted group, the last, always takes the absolute one.
+// Then, and only then, the count key is the pair (amplicon, hash): k_meta_amp_keys writes amplicon << 32 | uid with the entry's
+// index, one rocprim radix_sort_pairs sorts them, k_meta_amp_heads + an exclusive scan rank the distinct pairs (ascending by
+// (amplicon, hash)), k_meta_amp_scatter gives every entry its pair's rank `pid` and fills the pair table.  The counting
+// kernels run unchanged on the pids (within one read equal pids are exactly equal uids), k_meta_amp_totals adds every pair's
+// count into its hash's total, and the GROUPED forms of k_meta_mask_flag / k_meta_mask_compact read the count through the pid
+// and compare it with thr[amplicon of the read].  No launch depends on the number of amplicons and there is no
+// amplicons x hashes table.  Without amplicons nothing of this runs or is allocated.
+// Resource report (gfx950): no kernel of this file uses scratch, all are at 8 waves/SIMD; the new ones take 10-18 VGPRs, the
+// GROUPED forms 38 / 39 against 36 / 32 of the plain ones.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -104,19 +117,25 @@ __global__ void k_meta_mask_long_add(const uint64_t* __restrict__ key, int64_t n
 
 // whole_reads: --mask-reads (a read with an entry at or below the threshold goes as a whole), else --mask-seeds.
 // ctr[0]: reads dropped by --mask-reads, ctr[1]: entries removed by --mask-seeds.
+// GROUPED (amplicons): the count of entry e is count[seed_pid[e]], the count of its (amplicon, hash) pair, and the threshold is
+// that of the read's amplicon, thr[read_amp[r]] (the same in all lanes); used[] stays per hash.  Else seed_pid / read_amp / thr
+// are not read.
+template <bool GROUPED>
 __global__ void __launch_bounds__(256) k_meta_mask_flag(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid, int64_t n_reads,
                                                         const unsigned long long* __restrict__ count, unsigned long long threshold, int whole_reads,
                                                         int64_t* __restrict__ new_len, uint32_t* __restrict__ alive, uint32_t* used,
-                                                        unsigned long long* ctr) {
+                                                        unsigned long long* ctr, const uint32_t* __restrict__ seed_pid,
+                                                        const int32_t* __restrict__ read_amp, const unsigned long long* __restrict__ thr) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t r = wave; r < n_reads; r += n_waves) {
         const int64_t o = read_off[r], n = read_off[r + 1] - o;
+        if (GROUPED) threshold = thr[read_amp[r]];
         int64_t kept = 0;
         for (int64_t i0 = 0; i0 < n; i0 += 64) {
             const int64_t i = i0 + lane;
             const uint32_t u = i < n ? seed_uid[o + i] : 0u;
-            const bool keep = i < n && count[u] > threshold;
+            const bool keep = i < n && count[GROUPED ? seed_pid[o + i] : u] > threshold;
             kept += __popcll(__ballot(keep));
             if (keep && !whole_reads) used[u] = 1u;
         }
@@ -132,7 +151,9 @@ __global__ void __launch_bounds__(256) k_meta_mask_flag(const int64_t* __restric
     }
 }
 
-// new_off / read_pos / uid_pos: the exclusive scans of new_len / alive / used
+// new_off / read_pos / uid_pos: the exclusive scans of new_len / alive / used.  GROUPED: as in k_meta_mask_flag, and the
+// amplicon of every surviving read goes to out_amp.
+template <bool GROUPED>
 __global__ void __launch_bounds__(256) k_meta_mask_compact(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid,
                                                            const uint8_t* __restrict__ seed_rev, const uint64_t* __restrict__ uniq,
                                                            const int64_t* __restrict__ mult, int64_t n_reads, const unsigned long long* __restrict__ count,
@@ -140,18 +161,21 @@ __global__ void __launch_bounds__(256) k_meta_mask_compact(const int64_t* __rest
                                                            const int64_t* __restrict__ new_off, const uint32_t* __restrict__ read_pos,
                                                            const uint32_t* __restrict__ uid_pos, int64_t* __restrict__ out_off,
                                                            uint64_t* __restrict__ out_hash, uint32_t* __restrict__ out_uid, uint8_t* __restrict__ out_rev,
-                                                           int64_t* __restrict__ out_mult) {
+                                                           int64_t* __restrict__ out_mult, const uint32_t* __restrict__ seed_pid,
+                                                           const int32_t* __restrict__ read_amp, const unsigned long long* __restrict__ thr,
+                                                           int32_t* __restrict__ out_amp) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     if (wave == 0 && lane == 0) out_off[read_pos[n_reads]] = new_off[n_reads];   // (the end of the last surviving read)
     for (int64_t r = wave; r < n_reads; r += n_waves) {
         if (new_len[r] == 0) continue;
         const int64_t o = read_off[r], n = read_off[r + 1] - o;
+        if (GROUPED) threshold = thr[read_amp[r]];
         int64_t at = new_off[r];   // (the read's entries go to [new_off[r], new_off[r] + new_len[r]): as many as are kept below)
         for (int64_t i0 = 0; i0 < n; i0 += 64) {
             const int64_t i = i0 + lane;
             const uint32_t u = i < n ? seed_uid[o + i] : 0u;
-            const bool keep = i < n && count[u] > threshold;
+            const bool keep = i < n && count[GROUPED ? seed_pid[o + i] : u] > threshold;
             const unsigned long long b = __ballot(keep);
             if (keep) {
                 const int64_t dst = at + __popcll(b & ((1ULL << lane) - 1ULL));
@@ -164,6 +188,7 @@ __global__ void __launch_bounds__(256) k_meta_mask_compact(const int64_t* __rest
         if (lane == 0) {
             out_off[read_pos[r]] = new_off[r];
             out_mult[read_pos[r]] = mult[r];
+            if (GROUPED) out_amp[read_pos[r]] = read_amp[r];
         }
     }
 }
@@ -178,18 +203,71 @@ __global__ void k_meta_mask_compact_uniq(const uint64_t* __restrict__ uniq, cons
     }
 }
 
+// ---- amplicons: the count key is (amplicon, hash).  Every entry gets the rank `pid` of its pair among the distinct pairs of
+// the sample, ascending by (amplicon, hash); the counting kernels above then run on seed_pid in place of seed_uid (within one
+// read equal pids are exactly equal uids).  The number of launches does not depend on the number of amplicons.
+
+// a wave per merged read: entry e -> key[e] = amplicon << 32 | uid, val[e] = e (e < 2^32 - 1: the caller refuses more)
+__global__ void __launch_bounds__(256) k_meta_amp_keys(const int64_t* __restrict__ read_off, const uint32_t* __restrict__ seed_uid,
+                                                       const int32_t* __restrict__ read_amp, int64_t n_reads, uint64_t* __restrict__ key,
+                                                       uint32_t* __restrict__ val) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        const int64_t o = read_off[r], n = read_off[r + 1] - o;
+        const uint64_t hi = (uint64_t)(uint32_t)read_amp[r] << 32;
+        for (int64_t e = o + lane; e < o + n; e += 64) {
+            key[e] = hi | (uint64_t)seed_uid[e];
+            val[e] = (uint32_t)e;
+        }
+    }
+}
+
+// the sorted keys: head[i] = 1 at the first key of every run of equal pairs; head[n_keys] = 0 (the scan's total)
+__global__ void k_meta_amp_heads(const uint64_t* __restrict__ key, int64_t n_keys, uint32_t* __restrict__ head) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n_keys; i += (int64_t)gridDim.x * blockDim.x)
+        head[i] = i < n_keys && (i == 0 || key[i - 1] != key[i]) ? 1u : 0u;
+}
+
+// before: the exclusive scan of head.  The pair of sorted position i has rank before[i] + head[i] - 1 (< n_keys): to the entry
+// val[i], and its key to the pair table
+__global__ void k_meta_amp_scatter(const uint64_t* __restrict__ key, const uint32_t* __restrict__ val, const uint32_t* __restrict__ head,
+                                   const uint32_t* __restrict__ before, int64_t n_keys, uint32_t* __restrict__ seed_pid,
+                                   uint64_t* __restrict__ pair_key) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_keys; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t pid = before[i] + head[i] - 1u;
+        seed_pid[val[i]] = pid;
+        if (head[i]) pair_key[pid] = key[i];
+    }
+}
+
+// every pair's count into its hash's total over the amplicons (*n_pairs: the scan's total, on the device)
+__global__ void k_meta_amp_totals(const uint64_t* __restrict__ pair_key, const unsigned long long* __restrict__ count,
+                                  const uint32_t* __restrict__ n_pairs, unsigned long long* total) {
+    const int64_t n = (int64_t)*n_pairs;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x)
+        atomicAdd(&total[(uint32_t)pair_key[p]], count[p]);
+}
+
 // entries a read may have on the in-LDS path: kMaskQuadratic, or what PMX_META_MASK_LONG lowers it to
 int quadratic_bound() {
     int bound = kMaskQuadratic;
     if (const char* e = opt_str(O_META_MASK_LONG)) bound = (int)std::max<long long>(1, std::min<long long>(kMaskQuadratic, atoll(e)));
     return bound;
 }
+
+// the threshold of a group under a relative parameter (src/mgsr.cpp:2062-2075): the IEEE product, truncated
+unsigned long long relative_threshold(double rf, int64_t n_raw) {
+    const double t = rf * (double)n_raw;
+    return t >= 18446744073709551615.0 ? ~0ULL : (unsigned long long)(size_t)t;
+}
 }  // namespace
 
 void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
-    const bool whole_reads = m->lowcov_reads > 0;
+    const bool whole_reads = m->lowcov_reads > 0 || m->lowcov_reads_rf > 0;
     const unsigned long long threshold = (unsigned long long)(whole_reads ? m->lowcov_reads : m->lowcov_seeds);
     const int64_t n_reads = m->n_reads, n_seedmers = m->n_seedmers, n_uniq = (int64_t)m->h_uniq.size();
+    const bool grouped = m->amp_on;
     hipStream_t st = ctx->stream;
     const int G = ctx->n_cu * 8;
     m->masked = true;
@@ -197,7 +275,17 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     m->lowcov_reads_left = n_reads;
     m->lowcov_hash = m->h_uniq;
     m->lowcov_count.assign((size_t)n_uniq, 0);
+    // amplicons: the threshold of every group (the unlisted one, the last, always takes the absolute parameter)
+    std::vector<unsigned long long> thr;
+    if (grouped) {
+        const double rf = whole_reads ? m->lowcov_reads_rf : m->lowcov_seeds_rf;
+        thr.assign((size_t)m->n_amp, threshold);
+        if (rf > 0)
+            for (int32_t g = 0; g + 1 < m->n_amp; ++g) thr[(size_t)g] = relative_threshold(rf, m->amp_raw[(size_t)g]);
+        for (int32_t g = 0; g < m->n_amp; ++g) m->amp_thr[(size_t)g] = (int64_t)std::min<unsigned long long>(thr[(size_t)g], (unsigned long long)INT64_MAX);
+    }
     if (auto t = ctx->timers.find("meta_mask"); t != ctx->timers.end()) t->second.pending = false;
+    if (auto t = ctx->timers.find("meta_mask_sort"); t != ctx->timers.end()) t->second.pending = false;
     if (n_reads == 0 || n_seedmers == 0) return;   // (merged reads have entries: both or neither)
 
     // the reads of the sorted path, with the offsets of their keys
@@ -219,6 +307,21 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     d_alive.alloc((size_t)n_reads + 1); d_read_pos.alloc((size_t)n_reads + 1);
     d_count.alloc((size_t)n_uniq); d_used.alloc((size_t)n_uniq + 1); d_uid_pos.alloc((size_t)n_uniq + 1);
     d_ctr.alloc(2);
+    // amplicons: per entry its pair's rank, per pair its key and count (at most one pair per entry), and d_count above the
+    // per-hash totals over the amplicons
+    DevBuf<int32_t> d_read_amp, o_amp;
+    DevBuf<unsigned long long> d_thr, d_pair_count;
+    DevBuf<uint64_t> d_akey, d_akey_sorted, d_pair_key;
+    DevBuf<uint32_t> d_aval, d_aval_sorted, d_head, d_before, d_seed_pid;
+    if (grouped) {
+        d_read_amp.alloc((size_t)n_reads); d_thr.alloc(thr.size()); d_pair_count.alloc((size_t)n_seedmers); d_pair_key.alloc((size_t)n_seedmers);
+        d_akey.alloc((size_t)n_seedmers); d_akey_sorted.alloc((size_t)n_seedmers); d_aval.alloc((size_t)n_seedmers); d_aval_sorted.alloc((size_t)n_seedmers);
+        d_head.alloc((size_t)n_seedmers + 1); d_before.alloc((size_t)n_seedmers + 1); d_seed_pid.alloc((size_t)n_seedmers);
+        PMX_HIP(hipMemcpyAsync(d_read_amp.p, m->h_read_amp.data(), sizeof(int32_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+        PMX_HIP(hipMemcpyAsync(d_thr.p, thr.data(), sizeof(unsigned long long) * thr.size(), hipMemcpyHostToDevice, st));
+    }
+    const uint32_t* count_id = grouped ? d_seed_pid.p : m->d_seed_uid.p;           // what the counting kernels index their counters with
+    unsigned long long* counters = grouped ? d_pair_count.p : d_count.p;
     PMX_HIP(hipMemcpyAsync(d_mult.p, m->h_mult.data(), sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
     if (n_long > 0) {
         d_long_read.alloc((size_t)n_long); d_long_off.alloc((size_t)n_long + 1); d_key.alloc((size_t)n_keys); d_key_sorted.alloc((size_t)n_keys);
@@ -232,19 +335,42 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     PMX_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long) * 2, st));
     PMX_HIP(hipMemsetAsync(d_new_len.p + n_reads, 0, sizeof(int64_t), st));   // (the scans run over one entry more: their totals)
     PMX_HIP(hipMemsetAsync(d_alive.p + n_reads, 0, sizeof(uint32_t), st));
+    if (grouped) {
+        PMX_HIP(hipMemsetAsync(d_pair_count.p, 0, sizeof(unsigned long long) * (size_t)n_seedmers, st));
+        hipLaunchKernelGGL(k_meta_amp_keys, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_read_amp.p, n_reads,
+                           d_akey.p, d_aval.p);
+        unsigned end_bit = 32;   // (the uid, and the bits of the greatest amplicon)
+        while (end_bit < 64 && ((uint64_t)(m->n_amp - 1) >> (end_bit - 32)) != 0) ++end_bit;
+        timer_begin(ctx, "meta_mask_sort");   // (a span of its own inside "meta_mask": the share the key sort takes)
+        PMX_ROCPRIM(tmp, radix_sort_pairs, d_akey.p, d_akey_sorted.p, d_aval.p, d_aval_sorted.p, (size_t)n_seedmers, 0u, end_bit, st);
+        timer_end(ctx, "meta_mask_sort", 1);
+        hipLaunchKernelGGL(k_meta_amp_heads, dim3(grid_for(n_seedmers + 1, 256, G)), dim3(256), 0, st, d_akey_sorted.p, n_seedmers, d_head.p);
+        PMX_HIP(hipGetLastError());
+        PMX_ROCPRIM(tmp, exclusive_scan, d_head.p, d_before.p, 0u, (size_t)n_seedmers + 1, rocprim::plus<uint32_t>(), st);
+        hipLaunchKernelGGL(k_meta_amp_scatter, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_akey_sorted.p, d_aval_sorted.p, d_head.p, d_before.p,
+                           n_seedmers, d_seed_pid.p, d_pair_key.p);
+    }
     if (n_long < n_reads)
-        hipLaunchKernelGGL(k_meta_mask_count, dim3(grid_for(n_reads * 64, 64 * kMaskWaves, G)), dim3(64 * kMaskWaves), 0, st, m->d_read_off.p, m->d_seed_uid.p,
-                           d_mult.p, n_reads, bound, d_count.p);
+        hipLaunchKernelGGL(k_meta_mask_count, dim3(grid_for(n_reads * 64, 64 * kMaskWaves, G)), dim3(64 * kMaskWaves), 0, st, m->d_read_off.p, count_id,
+                           d_mult.p, n_reads, bound, counters);
     if (n_long > 0) {
-        hipLaunchKernelGGL(k_meta_mask_long_keys, dim3(grid_for(n_long * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_long_read.p,
+        hipLaunchKernelGGL(k_meta_mask_long_keys, dim3(grid_for(n_long * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, count_id, d_long_read.p,
                            d_long_off.p, n_long, d_key.p);
         unsigned end_bit = 33;   // (the uid, and the bits of the greatest ordinal)
         while (end_bit < 64 && ((uint64_t)(n_long - 1) >> (end_bit - 32)) != 0) ++end_bit;
         PMX_ROCPRIM(tmp, radix_sort_keys, d_key.p, d_key_sorted.p, (size_t)n_keys, 0u, end_bit, st);
-        hipLaunchKernelGGL(k_meta_mask_long_add, dim3(grid_for(n_keys, 256, G)), dim3(256), 0, st, d_key_sorted.p, n_keys, d_long_read.p, d_mult.p, d_count.p);
+        hipLaunchKernelGGL(k_meta_mask_long_add, dim3(grid_for(n_keys, 256, G)), dim3(256), 0, st, d_key_sorted.p, n_keys, d_long_read.p, d_mult.p, counters);
     }
-    hipLaunchKernelGGL(k_meta_mask_flag, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, n_reads, d_count.p,
-                       threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p);
+    if (grouped) {
+        hipLaunchKernelGGL(k_meta_amp_totals, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_pair_key.p, d_pair_count.p, d_before.p + n_seedmers,
+                           d_count.p);
+        hipLaunchKernelGGL(k_meta_mask_flag<true>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, n_reads,
+                           d_pair_count.p, threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, d_seed_pid.p, d_read_amp.p, d_thr.p);
+    } else {
+        hipLaunchKernelGGL(k_meta_mask_flag<false>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, n_reads, d_count.p,
+                           threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, (const uint32_t*)nullptr, (const int32_t*)nullptr,
+                           (const unsigned long long*)nullptr);
+    }
     PMX_HIP(hipGetLastError());
     PMX_ROCPRIM(tmp, exclusive_scan, d_new_len.p, d_new_off.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), st);
     PMX_ROCPRIM(tmp, exclusive_scan, d_alive.p, d_read_pos.p, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st);
@@ -257,6 +383,8 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     PMX_HIP(hipMemcpyAsync(&left_reads, d_read_pos.p + n_reads, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(&left_uniq, d_uid_pos.p + n_uniq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(h_ctr, d_ctr.p, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+    uint32_t n_pairs = 0;
+    if (grouped) PMX_HIP(hipMemcpyAsync(&n_pairs, d_before.p + n_seedmers, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipStreamSynchronize(st));
     DevBuf<int64_t> o_off, o_mult, o_count;
     DevBuf<uint64_t> o_hash, o_uniq;
@@ -264,9 +392,16 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     DevBuf<uint8_t> o_rev;
     o_off.alloc((size_t)left_reads + 1); o_mult.alloc((size_t)left_reads); o_count.alloc((size_t)left_uniq);
     o_hash.alloc((size_t)left_seedmers); o_uid.alloc((size_t)left_seedmers); o_rev.alloc((size_t)left_seedmers); o_uniq.alloc((size_t)left_uniq);
-    hipLaunchKernelGGL(k_meta_mask_compact, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p,
-                       m->d_uniq.p, d_mult.p, n_reads, d_count.p, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p, o_hash.p, o_uid.p,
-                       o_rev.p, o_mult.p);
+    if (grouped) {
+        o_amp.alloc((size_t)left_reads);
+        hipLaunchKernelGGL(k_meta_mask_compact<true>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p,
+                           m->d_uniq.p, d_mult.p, n_reads, d_pair_count.p, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p, o_hash.p,
+                           o_uid.p, o_rev.p, o_mult.p, d_seed_pid.p, d_read_amp.p, d_thr.p, o_amp.p);
+    } else {
+        hipLaunchKernelGGL(k_meta_mask_compact<false>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p,
+                           m->d_uniq.p, d_mult.p, n_reads, d_count.p, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p, o_hash.p, o_uid.p,
+                           o_rev.p, o_mult.p, (const uint32_t*)nullptr, (const int32_t*)nullptr, (const unsigned long long*)nullptr, (int32_t*)nullptr);
+    }
     hipLaunchKernelGGL(k_meta_mask_compact_uniq, dim3(grid_for(n_uniq, 256, G)), dim3(256), 0, st, m->d_uniq.p, d_count.p, d_used.p, d_uid_pos.p, n_uniq,
                        o_uniq.p, o_count.p);
     PMX_HIP(hipGetLastError());
@@ -288,7 +423,25 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
         PMX_HIP(hipMemcpyAsync(m->h_seed_rev.data(), o_rev.p, (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
         PMX_HIP(hipMemcpyAsync(m->h_uniq.data(), o_uniq.p, sizeof(uint64_t) * (size_t)left_uniq, hipMemcpyDeviceToHost, st));
     }
+    std::vector<uint64_t> pair_key((size_t)n_pairs);
+    if (grouped) {   // the triples before masking (in pair order: ascending by (amplicon, hash)) and the survivors' amplicons
+        m->ampc_count.resize((size_t)n_pairs);
+        m->h_read_amp.resize((size_t)left_reads);
+        PMX_HIP(hipMemcpyAsync(pair_key.data(), d_pair_key.p, sizeof(uint64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+        PMX_HIP(hipMemcpyAsync(m->ampc_count.data(), d_pair_count.p, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
+        if (left_reads > 0) PMX_HIP(hipMemcpyAsync(m->h_read_amp.data(), o_amp.p, sizeof(int32_t) * (size_t)left_reads, hipMemcpyDeviceToHost, st));
+    }
     PMX_HIP(hipStreamSynchronize(st));
+    if (grouped) {
+        m->ampc_group.resize((size_t)n_pairs);
+        m->ampc_hash.resize((size_t)n_pairs);
+        for (size_t p = 0; p < (size_t)n_pairs; ++p) {
+            m->ampc_group[p] = (int32_t)(pair_key[p] >> 32);
+            m->ampc_hash[p] = m->lowcov_hash[(size_t)(uint32_t)pair_key[p]];
+        }
+        m->amp_left.assign((size_t)m->n_amp, 0);
+        for (int32_t g : m->h_read_amp) ++m->amp_left[(size_t)g];
+    }
     for (int64_t& to : m->h_raw_to_merged)
         if (to >= 0) to = read_pos[(size_t)to + 1] > read_pos[(size_t)to] ? (int64_t)read_pos[(size_t)to] : -1;
     m->d_read_off.swap(o_off); m->d_seed_uid.swap(o_uid); m->d_seed_rev.swap(o_rev); m->d_uniq.swap(o_uniq); m->d_uniq_count.swap(o_count);
@@ -301,8 +454,9 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
 
 bool meta_masks_set(pmx_ctx* ctx, pmx_meta* m) {
     m->masked = false;
-    if (m->lowcov_reads <= 0 && m->lowcov_seeds <= 0) {
+    if (m->lowcov_reads <= 0 && m->lowcov_seeds <= 0 && !(m->lowcov_reads_rf > 0) && !(m->lowcov_seeds_rf > 0)) {
         if (auto t = ctx->timers.find("meta_mask"); t != ctx->timers.end()) t->second.pending = false;   // (no such span without a mask)
+        if (auto t = ctx->timers.find("meta_mask_sort"); t != ctx->timers.end()) t->second.pending = false;
         return false;
     }
     meta_apply_masks(ctx, m);
@@ -340,9 +494,71 @@ extern "C" {
 int pmx_meta_set_masks(pmx_meta* m, int64_t mask_reads, int64_t mask_seeds) {
     if (!m) return PMX_ERR_ARG;
     if (mask_reads < 0 || mask_seeds < 0) return fail(PMX_ERR_ARG, "pmx_meta_set_masks: a masking parameter must not be negative");
-    if (mask_reads > 0 && mask_seeds > 0) return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
+    if ((mask_reads > 0) + (mask_seeds > 0) + (m->lowcov_reads_rf > 0) + (m->lowcov_seeds_rf > 0) > 1)
+        return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
     m->lowcov_reads = mask_reads;
     m->lowcov_seeds = mask_seeds;
+    return PMX_OK;
+}
+
+int pmx_meta_set_relative_masks(pmx_meta* m, double reads_rf, double seeds_rf) {
+    if (!m) return PMX_ERR_ARG;
+    if (!(reads_rf >= 0) || !(seeds_rf >= 0)) return fail(PMX_ERR_ARG, "pmx_meta_set_relative_masks: a masking parameter must not be negative");
+    if ((reads_rf > 0) + (seeds_rf > 0) + (m->lowcov_reads > 0) + (m->lowcov_seeds > 0) > 1)
+        return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");
+    m->lowcov_reads_rf = reads_rf;
+    m->lowcov_seeds_rf = seeds_rf;
+    return PMX_OK;
+}
+
+int pmx_meta_set_amplicons(pmx_meta* m, const int32_t* group_of_read, int64_t n_reads, int32_t n_groups) {
+    if (!m || n_reads < 0 || n_groups < 0) return PMX_ERR_ARG;
+    if (!group_of_read) {   // cleared
+        if (n_reads != 0) return PMX_ERR_ARG;
+        m->amp_set = false;
+        m->amp_n_groups = 0;
+        m->amp_of_raw.clear();
+        return PMX_OK;
+    }
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (group_of_read[r] < 0 || group_of_read[r] > n_groups)
+            return fail(PMX_ERR_ARG, "pmx_meta_set_amplicons: the amplicon of read " + std::to_string(r) + " is not in [0, n_groups]");
+    m->amp_set = true;
+    m->amp_n_groups = n_groups;
+    m->amp_of_raw.assign(group_of_read, group_of_read + n_reads);
+    return PMX_OK;
+}
+
+int pmx_meta_read_amplicons(const pmx_meta* m, int32_t* amplicon, int64_t cap) {
+    if (!m) return PMX_ERR_ARG;
+    if (!m->amp_on) return fail(PMX_ERR_ARG, "pmx_meta_read_amplicons: the last pmx_meta_set_reads ran without amplicons");
+    if (cap < m->n_reads) return PMX_ERR_ARG;
+    if (amplicon) std::copy(m->h_read_amp.begin(), m->h_read_amp.end(), amplicon);
+    return PMX_OK;
+}
+
+int32_t pmx_meta_num_amplicon_groups(const pmx_meta* m) { return m && m->amp_on ? m->n_amp : 0; }
+
+int pmx_meta_amplicon_info(const pmx_meta* m, int64_t* raw_reads, int64_t* threshold, int64_t* merged_before, int64_t* merged_left, int64_t cap) {
+    if (!m) return PMX_ERR_ARG;
+    if (!m->amp_on) return fail(PMX_ERR_ARG, "pmx_meta_amplicon_info: the last pmx_meta_set_reads ran without amplicons");
+    if (cap < (int64_t)m->n_amp) return PMX_ERR_ARG;
+    if (raw_reads) std::copy(m->amp_raw.begin(), m->amp_raw.end(), raw_reads);
+    if (threshold) std::copy(m->amp_thr.begin(), m->amp_thr.end(), threshold);
+    if (merged_before) std::copy(m->amp_before.begin(), m->amp_before.end(), merged_before);
+    if (merged_left) std::copy(m->amp_left.begin(), m->amp_left.end(), merged_left);
+    return PMX_OK;
+}
+
+int64_t pmx_meta_amplicon_num_counts(const pmx_meta* m) { return m && m->amp_on && m->masked ? (int64_t)m->ampc_hash.size() : 0; }
+
+int pmx_meta_amplicon_counts(const pmx_meta* m, int32_t* group, uint64_t* hash, int64_t* count, int64_t cap) {
+    if (!m) return PMX_ERR_ARG;
+    if (!m->amp_on || !m->masked) return fail(PMX_ERR_ARG, "pmx_meta_amplicon_counts: the last pmx_meta_set_reads ran without amplicons or without a mask");
+    if (cap < (int64_t)m->ampc_hash.size()) return PMX_ERR_ARG;
+    if (group) std::copy(m->ampc_group.begin(), m->ampc_group.end(), group);
+    if (hash) std::copy(m->ampc_hash.begin(), m->ampc_hash.end(), hash);
+    if (count) std::copy(m->ampc_count.begin(), m->ampc_count.end(), count);
     return PMX_OK;
 }
 

@@ -107,6 +107,22 @@ struct pmx_meta {
     std::vector<uint64_t> lowcov_hash;
     std::vector<int64_t> lowcov_count;
     pmx::DevBuf<int64_t> d_uniq_count;
+    // amplicons (pmx_meta_set_amplicons / pmx_meta_set_relative_masks; src/mgsr.cpp:1216-1342, :2062-2075).  What the next
+    // set_reads applies: amp_of_raw (the amplicon of every raw read, in [0, amp_n_groups], amp_n_groups = unlisted) and the
+    // relative parameters.  Of the last set_reads when amp_on: n_amp = its groups + 1, the amplicon of every merged read
+    // (survivors after a mask), per group its raw reads, threshold, merged reads before masking and left, and under a mask
+    // the (group, hash, count) triples before masking, ascending
+    bool amp_set = false;
+    int32_t amp_n_groups = 0;
+    std::vector<int32_t> amp_of_raw;
+    double lowcov_reads_rf = 0.0, lowcov_seeds_rf = 0.0;
+    bool amp_on = false;
+    int32_t n_amp = 0;
+    std::vector<int32_t> h_read_amp;
+    std::vector<int64_t> amp_raw, amp_thr, amp_before, amp_left;
+    std::vector<int32_t> ampc_group;
+    std::vector<uint64_t> ampc_hash;
+    std::vector<int64_t> ampc_count;
     // taxonomy (pmx_meta_set_taxonomy; max_taxa 0 = none) and the ambiguity thresholds (pmx_meta_set_ambiguous).  The node table:
     // the taxa S(v) of every node's subtree, ascending, max_taxa slots a node; h_tx_over: bit v = |S(v)| > max_taxa (then no ids)
     int32_t max_taxa = 0, amb_abs = 0;
@@ -122,7 +138,8 @@ struct pmx_meta {
 
 // meta_mask.hip, a step of pmx_meta_set_reads (after the lists were uploaded, when a mask is set): counts every distinct hash
 // of the merged reads, drops reads (lowcov_reads) or list entries (lowcov_seeds) whose count is at most the threshold and
-// leaves m->h_* / d_* / n_reads / n_seedmers / h_raw_to_merged describing the survivors.  Throws pmx::HipError.
+// leaves m->h_* / d_* / n_reads / n_seedmers / h_raw_to_merged describing the survivors.  With amplicons (m->amp_on) the counts
+// and the thresholds are per amplicon, and it also leaves h_read_amp, amp_thr, amp_left and the ampc_* triples.  Throws pmx::HipError.
 void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m);
 // what pmx_meta_set_reads asks after upload_lists: false when no mask is set (m->masked cleared, no "meta_mask" span, nothing
 // launched or allocated), else meta_apply_masks has run

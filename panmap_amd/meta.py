@@ -136,6 +136,44 @@ class Meta:
         check(lib.pmx_meta_mask_counts(self._h, h.ctypes.data, c.ctypes.data, n), "pmx_meta_mask_counts")
         return h[:n], c[:n]
 
+    def set_amplicons(self, groups=None, n_groups: int = 0):
+        """--amplicon-depth (src/mgsr.cpp:1216-1342) for the set_reads calls that follow: `groups[r]` in [0, n_groups] is the
+        amplicon of raw read r, the value n_groups meaning "not listed" (load_amplicons(...).groups_of makes it).  Reads are then
+        merged within their amplicon only, ordered by (amplicon, hash list, orientation list), and a mask counts and thresholds
+        per amplicon.  groups=None clears.  assign() refuses such a read set.  --gpus N: every rank passes its shard's groups."""
+        if groups is None:
+            check(lib.pmx_meta_set_amplicons(self._h, None, 0, 0), "pmx_meta_set_amplicons")
+            return
+        g = np.ascontiguousarray(groups, np.int32)
+        check(lib.pmx_meta_set_amplicons(self._h, g.ctypes.data, len(g), int(n_groups)), "pmx_meta_set_amplicons")
+
+    def set_relative_masks(self, reads: float = 0.0, seeds: float = 0.0):
+        """--mask-reads-relative-frequency / --mask-seeds-relative-frequency (src/mgsr.cpp:2062-2075): as set_masks, with the
+        threshold of a listed amplicon g being int(x * N_g), N_g its raw reads; the unlisted group stays unmasked.  At most one
+        of the four masking parameters above 0; set_reads refuses a relative one without amplicons."""
+        check(lib.pmx_meta_set_relative_masks(self._h, float(reads), float(seeds)), "pmx_meta_set_relative_masks")
+
+    def read_amplicons(self) -> np.ndarray:
+        """the amplicon of every merged read of the last set_reads (which ran with amplicons)"""
+        out = np.zeros(self.n_reads, np.int32)
+        check(lib.pmx_meta_read_amplicons(self._h, out.ctypes.data, len(out)), "pmx_meta_read_amplicons")
+        return out
+
+    def amplicon_info(self):
+        """per amplicon of the last set_reads, the unlisted group last: raw reads N_g, the threshold applied (0 without a mask),
+        merged reads before masking, merged reads left"""
+        n = int(lib.pmx_meta_num_amplicon_groups(self._h))
+        a = [np.zeros(max(n, 1), np.int64) for _ in range(4)]
+        check(lib.pmx_meta_amplicon_info(self._h, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, n), "pmx_meta_amplicon_info")
+        return dict(raw_reads=a[0][:n], threshold=a[1][:n], merged_before=a[2][:n], merged_left=a[3][:n])
+
+    def amplicon_counts(self):
+        """(group, hash, count) BEFORE masking, ascending by (group, hash) (a set_reads with amplicons and a mask must have run)"""
+        n = int(lib.pmx_meta_amplicon_num_counts(self._h))
+        g, h, c = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.int64)
+        check(lib.pmx_meta_amplicon_counts(self._h, g.ctypes.data, h.ctypes.data, c.ctypes.data, n), "pmx_meta_amplicon_counts")
+        return g[:n], h[:n], c[:n]
+
     def score(self, top_oc: int = 1000, candidates=None):
         if candidates is not None:
             c = np.ascontiguousarray(candidates, np.uint32)
@@ -292,6 +330,37 @@ def load_taxonomy(path: str, rank: str, node_ids):
     finally:
         lib.pmx_taxonomy_free(h)
     return names, taxon
+
+
+class Amplicons:
+    """the table of --amplicon-depth (load_amplicons): `names` = the primer ids by first appearance (the groups)"""
+
+    def __init__(self, path: str):
+        self._h = C.c_void_p()
+        check(lib.pmx_amplicons_load(os.fsencode(path), C.byref(self._h)), "pmx_amplicons_load")
+        self.names = [lib.pmx_amplicons_group_name(self._h, g).decode() for g in range(int(lib.pmx_amplicons_num_groups(self._h)))]
+
+    def lookup(self, read_name) -> int:
+        """the group of a read name (the FASTQ header up to the first white space), -1 when the file does not list it"""
+        return int(lib.pmx_amplicons_lookup(self._h, read_name.encode() if isinstance(read_name, str) else read_name))
+
+    def groups_of(self, names) -> np.ndarray:
+        """Meta.set_amplicons' `groups` for reads with these names: an unlisted read gets len(self.names)"""
+        g = np.array([self.lookup(x) for x in names], np.int32).reshape(-1)
+        return np.where(g < 0, len(self.names), g).astype(np.int32)
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib.pmx_amplicons_free(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def load_amplicons(path: str) -> Amplicons:
+    """--amplicon-depth (pmx_amplicons_load; extractReadSequences, src/mgsr.cpp:1216-1342): `read id <TAB> primer id` lines"""
+    return Amplicons(path)
 
 
 def format_assigned(result: AssignResult, node_id, heads=None, taxon_names=None):

@@ -6,6 +6,8 @@ low-complexity reads).
                                     mask_seeds 1, `runs` times after one warm-up; the share of merged reads on the sorted path
   meta_mask_timing.py wall [runs]   per sample: the wall time of set_reads with the masks OFF, `runs` times after one warm-up
                                     (works on a build without the masks too: run it once per build, PMX_LIB_PATH picks the build)
+  --amplicons G (mask mode)         deal the reads round-robin into G amplicons (pmx_meta_set_amplicons, no read unlisted): the
+                                    same spans with the (amplicon, hash) count key, plus "meta_mask_sort", the sort of the keys
 One JSON line per sample."""
 import json
 import os
@@ -22,8 +24,14 @@ def main():
     import numpy as np
     import panmap_amd as pmx
     from dist_meta_worker import sample
-    mode = sys.argv[1] if len(sys.argv) > 1 else "mask"
-    runs = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    argv = sys.argv[1:]
+    n_amplicons = 0
+    if "--amplicons" in argv:
+        at = argv.index("--amplicons")
+        n_amplicons = int(argv[at + 1])
+        del argv[at:at + 2]
+    mode = argv[0] if len(argv) > 0 else "mask"
+    runs = int(argv[1]) if len(argv) > 1 else 3
     ctx = pmx.Context(0)
     for case in ("rsv", "sars"):
         pm, reads, _, _ = sample(pmx, case)
@@ -43,13 +51,20 @@ def main():
             ns, _ = meta.read_info()
             out.update(merged_reads=int(len(ns)), seedmers=int(ns.sum()), share_on_sorted_path=float((ns > 1024).mean()))
             meta.set_masks(seeds=1)
+            if n_amplicons > 0:
+                meta.set_amplicons(np.arange(len(reads), dtype=np.int32) % n_amplicons, n_amplicons)
+                out.update(amplicons=n_amplicons)
             set_reads()
-            span, wall = [], []
+            span, wall, sort = [], [], []
             for _ in range(runs):
                 wall.append(set_reads())
                 span.append(ctx.kernel_ms("meta_mask"))
+                sort.append(ctx.kernel_ms("meta_mask_sort"))
             out.update(mask_info=meta.mask_info(), meta_mask_ms=span, meta_mask_ms_median=statistics.median(span), set_reads_ms=wall,
                        set_reads_ms_median=statistics.median(wall))
+            if n_amplicons > 0:
+                out.update(merged_reads_in_amplicons=int(meta.amplicon_info()["merged_before"].sum()), meta_mask_sort_ms=sort,
+                           meta_mask_sort_ms_median=statistics.median(sort))
         else:
             wall = [set_reads() for _ in range(runs)]
             out.update(merged_reads=meta.n_reads, set_reads_ms=wall, set_reads_ms_median=statistics.median(wall))
