@@ -458,17 +458,23 @@ void score_rows(pmx_ctx* ctx, pmx_meta* m, int64_t first, int64_t count, uint16_
     const int n_cand = (int)m->cand.size(), words = (n_cand + 63) / 64;
     const int64_t threads = count * (int64_t)words;
     const dim3 grid(grid_for(threads, 256, ctx->n_cu * 16)), block(256);
-    if (m->longest < 128)
-        hipLaunchKernelGGL(k_meta_scores<7>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count, m->mask_fwd.p,
-                           m->mask_rev.p, words, n_cand, out);
-    else
-        hipLaunchKernelGGL(k_meta_scores<16>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count, m->mask_fwd.p,
-                           m->mask_rev.p, words, n_cand, out);
+    meta_with_planes(m->longest, [&](auto planes) {
+        hipLaunchKernelGGL(k_meta_scores<decltype(planes)::value>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count,
+                           m->mask_fwd.p, m->mask_rev.p, words, n_cand, out);
+    });
     PMX_HIP(hipGetLastError());
 }
 
 // a read set made inside a step: released when the step ends, on every way out of it (the step's caller has set the device)
 using ReadSetGuard = std::unique_ptr<pmx_readset>;
+
+// the place stage's parameters for the overlap coefficients: every read seed kept
+pmx_place_params overlap_place_params() {
+    pmx_place_params pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.min_read_support = 1;
+    return pp;
+}
 
 // One call of pmx_meta_set_reads: one function per step, in the order the entry point calls them.  A step that calls into the
 // read-set or place API returns that API's code; the others throw (HipError).
@@ -511,6 +517,7 @@ struct MetaReads {
     // (lexicographic on the hash list, then on the orientation list: the order the vector comparisons gave)
     int cmp(int64_t a, int64_t b) const { const ListView x = list(a), y = list(b); return cmp_lists(x.h, x.v, x.n, y.h, y.v, y.n); }
 
+    int check_settings() const;
     void drop_dusty();
     int seedmer_lists();
     int seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc);
@@ -520,6 +527,21 @@ struct MetaReads {
     void upload_lists();
     int overlap_coefficients();
 };
+
+// The masking parameters and the amplicons as the setters left them (src/mgsr.cpp:2049-2053; a relative parameter without
+// amplicons would do nothing in the reference, whose single group is the unlisted one: refused).  Reads: them, n_raw.
+// Leaves nothing: PMX_OK, or the refusal.
+int MetaReads::check_settings() const {
+    if (meta_masks_above_zero(m->lowcov_reads, m->lowcov_seeds, m->lowcov_reads_rf, m->lowcov_seeds_rf) > 1)
+        return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");
+    if ((m->lowcov_reads_rf > 0 || m->lowcov_seeds_rf > 0) && !m->amp_set)
+        return fail(PMX_ERR_ARG, "pmx_meta_set_reads: a relative-frequency mask needs amplicons (pmx_meta_set_amplicons): its threshold is a share of "
+                                 "the reads of an amplicon group, and without groups every read is unlisted and takes no relative threshold");
+    if (m->amp_set && (int64_t)m->amp_of_raw.size() != n_raw)
+        return fail(PMX_ERR_ARG, "pmx_meta_set_reads: " + std::to_string(n_raw) + " reads, but pmx_meta_set_amplicons named the amplicons of " +
+                                     std::to_string(m->amp_of_raw.size()));
+    return PMX_OK;
+}
 
 // --dust.  Reads: the caller's reads, m->dust_threshold.  Leaves: concat / offsets / n_reads describe the kept reads only
 // (re-concatenated when any was dropped), n_dusty, n_kept_all.  Nothing below knows about DUST.
@@ -734,29 +756,16 @@ void MetaReads::upload_lists() {
 int MetaReads::overlap_coefficients() {
     m->oc.assign((size_t)m->n_nodes, 0.0);
     if (n_kept_all <= 0) return PMX_OK;
-    int rc;
-    {   // (the read set is released as soon as the tree is scored)
-        pmx_readset* rs = nullptr;
-        rc = pmx_readset_upload(ctx, concat, offsets, n_reads, &rs);
-        if (rc != PMX_OK) return rc;
-        const ReadSetGuard rs_guard(rs);
-        pmx_place_params pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.min_read_support = 1;
-        pmx_place_result res;
-        rc = pmx_readset_pack(ctx, rs);
-        if (rc == PMX_OK) rc = pmx_place_reset(ctx, m->placer);
-        if (rc == PMX_OK) rc = pmx_place_add_reads(ctx, m->placer, rs, &pp);
-        if (rc == PMX_OK && m->dist) rc = pmx_dist_merge_histograms(m->dist, m->placer);
-        if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept_all, &res);
-    }
+    pmx_readset* rs = nullptr;
+    int rc = pmx_readset_upload(ctx, concat, offsets, n_reads, &rs);
     if (rc != PMX_OK) return rc;
-    std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
-    rc = pmx_place_node_outputs(ctx, m->placer, nullptr, nullptr, counts2.data());
-    if (rc != PMX_OK) return rc;
-    for (int64_t v = 0; v < m->n_nodes; ++v)
-        m->oc[(size_t)v] = counts2[2 * (size_t)v + 1] > 0 ? (double)counts2[2 * (size_t)v] / (double)counts2[2 * (size_t)v + 1] : 0.0;
-    return PMX_OK;
+    ReadSetGuard rs_guard(rs);
+    const pmx_place_params pp = overlap_place_params();
+    rc = pmx_readset_pack(ctx, rs);
+    if (rc == PMX_OK) rc = pmx_place_reset(ctx, m->placer);
+    if (rc == PMX_OK) rc = pmx_place_add_reads(ctx, m->placer, rs, &pp);
+    if (rc == PMX_OK && m->dist) rc = pmx_dist_merge_histograms(m->dist, m->placer);
+    return meta_overlap_from_histogram(ctx, m, rc, n_kept_all, &rs_guard);
 }
 
 // ---- pmx_meta_score's steps
@@ -1143,6 +1152,21 @@ bool drop_low_proportions(std::vector<int>& cols, std::vector<std::vector<uint32
 }
 }  // namespace
 
+// (declared in meta_state.hpp: MetaReads::overlap_coefficients and meta_mask.hip's path end here)
+int meta_overlap_from_histogram(pmx_ctx* ctx, pmx_meta* m, int rc, int64_t n_kept, ReadSetGuard* seeded) {
+    const pmx_place_params pp = overlap_place_params();
+    pmx_place_result res;
+    if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept, &res);
+    if (seeded) seeded->reset();
+    if (rc != PMX_OK) return rc;
+    std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
+    rc = pmx_place_node_outputs(ctx, m->placer, nullptr, nullptr, counts2.data());
+    if (rc != PMX_OK) return rc;
+    for (int64_t v = 0; v < m->n_nodes; ++v)
+        m->oc[(size_t)v] = counts2[2 * (size_t)v + 1] > 0 ? (double)counts2[2 * (size_t)v] / (double)counts2[2 * (size_t)v + 1] : 0.0;
+    return PMX_OK;
+}
+
 extern "C" {
 
 int pmx_meta_create(pmx_ctx* ctx, const pmx_index* idx_std, const pmx_index* idx_oriented, pmx_meta** out) {
@@ -1218,31 +1242,22 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     if (!ctx || !m || !offsets || n_reads < 0 || (!concat && n_reads > 0)) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    // the masking parameters and the amplicons as the setters left them (src/mgsr.cpp:2049-2053; a relative parameter without
-    // amplicons would do nothing in the reference, whose single group is the unlisted one: refused)
-    const bool relative = m->lowcov_reads_rf > 0 || m->lowcov_seeds_rf > 0;
-    if ((m->lowcov_reads > 0) + (m->lowcov_seeds > 0) + (m->lowcov_reads_rf > 0) + (m->lowcov_seeds_rf > 0) > 1)
-        return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");
-    if (relative && !m->amp_set)
-        return fail(PMX_ERR_ARG, "pmx_meta_set_reads: a relative-frequency mask needs amplicons (pmx_meta_set_amplicons): its threshold is a share of "
-                                 "the reads of an amplicon group, and without groups every read is unlisted and takes no relative threshold");
-    if (m->amp_set && (int64_t)m->amp_of_raw.size() != n_reads)
-        return fail(PMX_ERR_ARG, "pmx_meta_set_reads: " + std::to_string(n_reads) + " reads, but pmx_meta_set_amplicons named the amplicons of " +
-                                     std::to_string(m->amp_of_raw.size()));
     MetaReads R(ctx, m, concat, offsets, n_reads);
+    int rc = R.check_settings();
+    if (rc != PMX_OK) return rc;
     R.drop_dusty();
-    int rc = R.seedmer_lists();
+    rc = R.seedmer_lists();
     if (rc != PMX_OK) return rc;
     R.merge_equal_lists();
     if (m->dist) {
         rc = R.merge_over_ranks();
         if (rc != PMX_OK) return rc;
     }
-    if (m->amp_on && (m->lowcov_reads > 0 || m->lowcov_seeds > 0 || relative) && m->n_seedmers >= (int64_t)UINT32_MAX)
+    if (m->amp_on && meta_masks_above_zero(m->lowcov_reads, m->lowcov_seeds, m->lowcov_reads_rf, m->lowcov_seeds_rf) > 0 && m->n_seedmers >= (int64_t)UINT32_MAX)
         return fail(PMX_ERR_CAPACITY, "pmx_meta_set_reads: a mask within amplicons indexes the list entries with 32 bits; the merged reads hold 2^32 - 1 or more");
     R.upload_lists();
     // the low-coverage masks (src/mgsr.cpp:2049-2139), when one is set: the reads that survive are the sample from here on
-    rc = meta_masks_set(ctx, m) ? meta_masked_overlap_coefficients(ctx, m) : R.overlap_coefficients();
+    rc = meta_apply_masks(ctx, m) ? meta_masked_overlap_coefficients(ctx, m) : R.overlap_coefficients();
     if (rc != PMX_OK) return rc;
     m->cand.clear();
     m->groups.clear();
@@ -1265,10 +1280,8 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
     own_row_slice(m);
     if (m->cand.empty() || m->n_reads == 0) return PMX_OK;
     m->score.ensure((size_t)m->row_count * m->cand.size());
-    int64_t longest = 0;
-    for (int64_t r = 0; r < m->n_reads; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
-    if (longest >= 65535) return fail(PMX_ERR_UNSUPPORTED, "a read with 65,535 seedmers or more (16-bit scores)");
-    m->longest = longest;
+    const int rc = meta_longest_read(m);
+    if (rc != PMX_OK) return rc;
     timer_begin(ctx, "meta_score");
     build_masks(ctx, m);
     score_rows(ctx, m, m->row_first, m->row_count, m->score.p);

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <chrono>
 #include <fstream>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -866,160 +867,85 @@ pmx_dist* join_ranks(pmx_ctx* ctx, const Ranks& rk) {
     return dist;
 }
 
-// --meta --filter-and-assign (filterAndAssignBatch, src/main.cpp:720-1016; writeAssignedReadsOut, :522-558, :889-903), after
-// pmx_meta_set_reads: every read against every node, then the three files.  `<prefix>.mgsr.assignedReads.fastq` holds the
-// assigned reads in input order (FASTA input: quality `I`); `.mgsr.assignedReads.out` and `.mgsr.assignedReadsLCANode.out` hold
-// one line per head node that has reads, `head[,nodes folded into it]<TAB>.<TAB>count<TAB>indices into the FASTQ`, by
-// ascending DFS index of the head (the reference's orders come from hash-map iteration: DESIGN.md section 4.3).
-// With `taxonomy` (--taxonomic-metadata) the reads spanning more than --maximum-taxon-number taxa are in none of the files, and
-// the second column holds the taxon names of the head's subtree by ascending taxon index, `.` when there are none or too many.
-void write_assigned(const Config& c, Run& run, const Reads& reads, const pmx_taxonomy* taxonomy) {
-    pmx_meta* m = run.meta;
-    if (taxonomy) {
-        std::vector<int32_t> node_taxon;
-        for (int64_t v = 0; pmx_index_node_id(run.idx, v); ++v) node_taxon.push_back((int32_t)pmx_taxonomy_lookup(taxonomy, pmx_index_node_id(run.idx, v)));
-        check(pmx_meta_set_taxonomy(m, node_taxon.data(), (int64_t)node_taxon.size(), pmx_taxonomy_num_taxa(taxonomy), c.maximum_taxon_number), "--taxonomic-metadata");
-        check(pmx_meta_set_ambiguous(m, c.ambiguous_score, c.ambiguous_ratio), "--ambiguous-score-threshold");
-    }
-    check(pmx_meta_set_breadth(m, c.breadth_ratio ? 1 : 0), "--breadth-ratio");
-    check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
-    const int64_t n_merged = pmx_meta_num_reads(m), n_nodes_total = pmx_meta_assign_num_nodes(m);
-    std::vector<uint8_t> state((size_t)std::max<int64_t>(n_merged, 1));
-    std::vector<uint32_t> lca(state.size()), nodes((size_t)std::max<int64_t>(n_nodes_total, 1));
-    std::vector<int64_t> off((size_t)n_merged + 1), merged((size_t)std::max<int64_t>(reads.n_reads, 1));
-    check(pmx_meta_assign_reads(m, state.data(), nullptr, lca.data(), nullptr, n_merged), "the reads' states");
-    check(pmx_meta_assign_nodes(m, off.data(), nodes.data(), (int64_t)nodes.size()), "the reads' nodes");
-    check(pmx_meta_raw_to_merged(m, merged.data(), reads.n_reads), "the reads' merged reads");
-    pmx_index_info info;
-    check(pmx_index_get_info(run.oidx, &info), "index info");
-    std::vector<uint32_t> head((size_t)info.n_nodes);
-    check(pmx_index_node_heads(run.oidx, head.data()), "folding identical nodes");
-    // the FASTQ, and per merged read the FASTQ positions of its copies (ascending: input order)
-    const std::string fq_path = c.output + ".mgsr.assignedReads.fastq";
-    FILE* fq = fopen(fq_path.c_str(), "w");
-    if (!fq) die("cannot write " + fq_path);
-    std::vector<std::vector<int64_t>> copies((size_t)n_merged);
-    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0, n_over = 0;
-    for (int64_t r = 0; r < reads.n_reads; ++r) {
-        const int64_t mr = merged[(size_t)r];
-        const int st = mr < 0 ? PMX_META_UNMAPPED : state[(size_t)mr];
-        if (st != PMX_META_ASSIGNED) { (st == PMX_META_OVER_TAXA ? n_over : st == PMX_META_DISCARDED ? n_discarded : n_unmapped)++; continue; }
-        const size_t at = (size_t)reads.off[(size_t)r], len = (size_t)(reads.off[(size_t)r + 1] - reads.off[(size_t)r]);
-        const std::string qual = len > 0 && reads.quals[at] == '\0' ? std::string(len, 'I') : reads.quals.substr(at, len);   // src/main.cpp:889-903
-        fprintf(fq, "@%s\n%.*s\n+\n%s\n", reads.name(r).c_str(), (int)len, reads.concat.data() + at, qual.c_str());
-        copies[(size_t)mr].push_back(n_written++);
-    }
-    fclose(fq);
-    // read -> nodes inverted to head -> reads, for the assigned nodes and for the LCA node
-    std::vector<std::vector<int64_t>> by_node((size_t)info.n_nodes), by_lca((size_t)info.n_nodes);
-    for (int64_t mr = 0; mr < n_merged; ++mr) {
-        if (copies[(size_t)mr].empty()) continue;
-        uint32_t prev = UINT32_MAX;
-        std::vector<uint32_t> hs;
-        for (int64_t q = off[(size_t)mr]; q < off[(size_t)mr + 1]; ++q) hs.push_back(head[nodes[(size_t)q]]);
-        std::sort(hs.begin(), hs.end());
-        for (uint32_t h : hs) {
-            if (h != prev) by_node[h].insert(by_node[h].end(), copies[(size_t)mr].begin(), copies[(size_t)mr].end());
-            prev = h;
-        }
-        std::vector<int64_t>& l = by_lca[head[lca[(size_t)mr]]];
-        l.insert(l.end(), copies[(size_t)mr].begin(), copies[(size_t)mr].end());
-    }
-    std::vector<std::vector<uint32_t>> folded((size_t)info.n_nodes);
-    for (uint32_t v = 0; v < (uint32_t)info.n_nodes; ++v)
-        if (head[v] != v) folded[head[v]].push_back(v);
-    auto write_out = [&](const std::string& path, std::vector<std::vector<int64_t>>& groups) {
-        FILE* f = fopen(path.c_str(), "w");
-        if (!f) die("cannot write " + path);
-        for (uint32_t h = 0; h < (uint32_t)info.n_nodes; ++h) {
-            std::vector<int64_t>& g = groups[h];
-            if (g.empty()) continue;
-            std::sort(g.begin(), g.end());
-            std::string ids = pmx_index_node_id(run.idx, h);
-            for (uint32_t v : folded[h]) { ids += ","; ids += pmx_index_node_id(run.idx, v); }
-            std::string taxa;
-            uint32_t tx[16];
-            const int64_t n_tx = taxonomy ? pmx_meta_node_taxa(m, h, tx, 16) : 0;
-            for (int64_t i = 0; i < n_tx; ++i) { if (i) taxa += ","; taxa += pmx_taxonomy_taxon_name(taxonomy, tx[i]); }
-            fprintf(f, "%s\t%s\t%zu\t", ids.c_str(), taxa.empty() ? "." : taxa.c_str(), g.size());
-            for (size_t i = 0; i < g.size(); ++i) fprintf(f, i ? ",%lld" : "%lld", (long long)g[i]);
-            fputc('\n', f);
-        }
-        fclose(f);
-    };
-    write_out(c.output + ".mgsr.assignedReads.out", by_node);
-    write_out(c.output + ".mgsr.assignedReadsLCANode.out", by_lca);
-    if (c.breadth_ratio) {
-        // src/main.cpp:992-1013, calculateBreadthRatio (src/mgsr.cpp:6518-6584): a line per head node, with or without reads, in the
-        // pre-order of the collapsed tree (= ascending DFS index of the heads); the header alone when no read was assigned
-        const std::string path = c.output + ".mgsr.breadths.out";
-        FILE* f = fopen(path.c_str(), "w");
-        if (!f) die("cannot write " + path);
-        fputs("NodeId\tTotalRefSeeds\tObservedBreadthCount\tObservedBreadthRatio\tTotalDepth\tMeanDepth\tExpectedBreadthRatio\tObservedToExpectedBreadthRatio\n", f);
-        std::vector<uint64_t> total((size_t)info.n_nodes), observed((size_t)info.n_nodes), depth((size_t)info.n_nodes);
-        check(pmx_meta_breadth(m, total.data(), observed.data(), depth.data(), info.n_nodes), "the breadth of the nodes");
-        for (uint32_t h = 0; n_written > 0 && h < (uint32_t)info.n_nodes; ++h) {
-            if (head[h] != h) continue;
-            std::string ids = pmx_index_node_id(run.idx, h);
-            for (uint32_t v : folded[h]) { ids += ","; ids += pmx_index_node_id(run.idx, v); }
-            const double t = (double)total[h];
-            const double ratio = total[h] > 0 ? (double)observed[h] / t : 0.0, mean = total[h] > 0 ? (double)depth[h] / t : 0.0;
-            const double expected = mean > 0 ? 1.0 - std::exp(-mean) : 0.0;
-            fprintf(f, "%s\t%llu\t%llu\t%g\t%llu\t%g\t%g\t%g\n", ids.c_str(), (unsigned long long)total[h], (unsigned long long)observed[h], ratio,
-                    (unsigned long long)depth[h], mean, expected, expected > 0 ? ratio / expected : 0.0);
-        }
-        fclose(f);
-        say(c, "meta", path);
-    }
-    say(c, "meta", fq_path + " (" + std::to_string(n_written) + " assigned, " + std::to_string(n_discarded) + " discarded, " + std::to_string(n_unmapped) +
-                       " unmapped reads" +
-                       (taxonomy ? ", " + std::to_string(n_over) + " spanning more than " + std::to_string(c.maximum_taxon_number) + " taxa" : std::string()) + ")");
+// the id of node `head` and, comma-joined behind it, the ids of the n nodes that share its line: those folded into it
+// (identical nodes, src/mgsr.cpp:505-532) or the haplotypes merged with it
+std::string joined_ids(const pmx_index* idx, uint32_t head, const uint32_t* others, size_t n) {
+    std::string ids = pmx_index_node_id(idx, head);
+    for (size_t i = 0; i < n; ++i) { ids += ","; ids += pmx_index_node_id(idx, others[i]); }
+    return ids;
 }
 
-// --meta (runDeconvolution, src/main.cpp:1192-1313): reads of a mixed sample -> `<prefix>.mgsr.abundance.out`, one line per
-// estimated haplotype: node id (+ the nodes merged into it, comma-joined) <TAB> proportion with five decimals, by proportion.
-// The two indexes of the tree (the place stage's and its oriented form, without flank mask) are built in memory.
-int run_meta(Config c) {
-    if (c.reads1.empty()) die("--meta needs reads");
-    if (c.filter_and_assign && c.gpus > 1) die("--filter-and-assign runs on one GPU: drop --gpus");
-    if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
-    if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
-    if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
-    if (!c.mask_options.empty() && c.filter_and_assign)   // (initializeQueryDataBatch, src/mgsr.cpp:1575, never masks)
-        die("option " + c.mask_options[0] + " is not accepted with --filter-and-assign: the reference's reader for that mode never masks");
-    if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
-    if (c.mask_reads_rf < 0.0 || c.mask_seeds_rf < 0.0)
-        die("--mask-reads-relative-frequency and --mask-seeds-relative-frequency must not be negative");
-    if ((c.mask_reads > 0) + (c.mask_seeds > 0) + (c.mask_reads_rf > 0.0) + (c.mask_seeds_rf > 0.0) > 1)
-        die("Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
-    // the amplicons: read the table before anything else is opened.  (A relative mask without the file does nothing in the
-    // reference, whose single group is then the unlisted one: refused)
-    struct Amplicons {
-        pmx_amplicons* a = nullptr;
-        ~Amplicons() { pmx_amplicons_free(a); }
-    } amplicons;
-    if (c.amplicon_depth.empty())
-        for (const std::string& o : c.mask_options)
-            if (o == "--mask-reads-relative-frequency" || o == "--mask-seeds-relative-frequency")
-                die("option " + o + " is not accepted without --amplicon-depth: its threshold is a share of the reads of amplicon groups, which this "
-                    "build does not make without that file");
-    if (!c.amplicon_depth.empty()) {
+// One --meta sample (runDeconvolution, src/main.cpp:1192-1313; --filter-and-assign: filterAndAssignBatch, :720-1016).  A
+// call-lifetime struct, one function per step in the order run_meta calls them; it owns the Run, the two tables, the reads,
+// the ranks and this rank's shard.  The two indexes of the tree (the place stage's and its oriented form, without flank mask)
+// are built in memory.  --gpus N: one rank per GPU, each with a contiguous shard of the reads (R1 then R2); every rank ends with
+// the whole sample's result (pmx_meta_attach_dist), rank 0 writes it.  run.close() is run_meta's call at the normal ends.
+struct MetaSample {
+    Config c;                                    // (quiet in the ranks above 0)
+    Run run;
+    struct Amplicons { pmx_amplicons* a = nullptr; ~Amplicons() { pmx_amplicons_free(a); } } amplicons;   // --amplicon-depth
+    struct Taxonomy { pmx_taxonomy* t = nullptr; ~Taxonomy() { pmx_taxonomy_free(t); } } taxonomy;        // --taxonomic-metadata
+    std::unique_ptr<const Reads> reads_p;        // mates as sequenced, one after the other
+    Ranks rk;
+    int64_t lo = 0, hi = 0;                      // this rank's shard
+    // --filter-and-assign, what assign() leaves for the writers: per merged read its state, LCA node and nodes [off[r], off[r + 1])
+    // of `nodes`; per read of the input its merged read; per node its head, per head the nodes folded into it
+    int64_t n_merged = 0, n_nodes = 0;
+    std::vector<uint8_t> state;
+    std::vector<uint32_t> lca, nodes, head;
+    std::vector<int64_t> off, merged;
+    std::vector<std::vector<uint32_t>> folded;
+    // ... and write_fastq: per merged read the FASTQ positions of its copies (ascending: input order), the four tallies
+    std::string fq_path;
+    std::vector<std::vector<int64_t>> copies;
+    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0, n_over = 0;
+
+    explicit MetaSample(const Config& c_) : c(c_) {}
+    const Reads& reads() const { return *reads_p; }
+    bool masking() const { return c.mask_reads > 0 || c.mask_seeds > 0 || c.mask_reads_rf > 0.0 || c.mask_seeds_rf > 0.0; }
+    std::string ids_of_head(uint32_t h) const { return joined_ids(run.idx, h, folded[h].data(), folded[h].size()); }
+
+    // the refusals that need no file
+    void refuse_options() const {
+        if (c.reads1.empty()) die("--meta needs reads");
+        if (c.filter_and_assign && c.gpus > 1) die("--filter-and-assign runs on one GPU: drop --gpus");
+        if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
+        if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
+        if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
+        if (!c.mask_options.empty() && c.filter_and_assign)   // (initializeQueryDataBatch, src/mgsr.cpp:1575, never masks)
+            die("option " + c.mask_options[0] + " is not accepted with --filter-and-assign: the reference's reader for that mode never masks");
+        if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
+        if (c.mask_reads_rf < 0.0 || c.mask_seeds_rf < 0.0)
+            die("--mask-reads-relative-frequency and --mask-seeds-relative-frequency must not be negative");
+        if ((c.mask_reads > 0) + (c.mask_seeds > 0) + (c.mask_reads_rf > 0.0) + (c.mask_seeds_rf > 0.0) > 1)
+            die("Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
+    }
+
+    // The amplicons: the table is read before anything else is opened.  (A relative mask without the file does nothing in the
+    // reference, whose single group is then the unlisted one: refused.)  Leaves: amplicons.a, null without --amplicon-depth.
+    void load_amplicons() {
+        if (c.amplicon_depth.empty()) {
+            for (const std::string& o : c.mask_options)
+                if (o == "--mask-reads-relative-frequency" || o == "--mask-seeds-relative-frequency")
+                    die("option " + o + " is not accepted without --amplicon-depth: its threshold is a share of the reads of amplicon groups, which this "
+                        "build does not make without that file");
+            return;
+        }
         const int rc = pmx_amplicons_load(c.amplicon_depth.c_str(), &amplicons.a);
         if (rc == PMX_ERR_IO)
             die("option --amplicon-depth is not accepted: cannot read " + c.amplicon_depth + ", the file that names the amplicon groups, which this build "
                 "does not make by itself");
         if (rc != PMX_OK) die(std::string("option --amplicon-depth is not accepted: ") + pmx_last_error());
     }
-    // the taxonomy filter: read the table before anything else is opened
-    const bool with_taxonomy = !c.taxonomic_metadata.empty();
-    if ((with_taxonomy || !c.taxonomy_options.empty()) && !c.filter_and_assign)
-        die("option " + (with_taxonomy ? std::string("--taxonomic-metadata") : c.taxonomy_options[0]) + " is not accepted without --filter-and-assign");
-    if (!with_taxonomy && !c.taxonomy_options.empty()) die("option " + c.taxonomy_options[0] + " is not accepted without --taxonomic-metadata");
-    struct Taxonomy {
-        pmx_taxonomy* t = nullptr;
-        ~Taxonomy() { pmx_taxonomy_free(t); }
-    } taxonomy;
-    if (with_taxonomy) {
+
+    // The taxonomy filter: its refusals, then the table, read before anything else is opened.  Leaves: taxonomy.t, null
+    // without --taxonomic-metadata.
+    void load_taxonomy() {
+        const bool with_taxonomy = !c.taxonomic_metadata.empty();
+        if ((with_taxonomy || !c.taxonomy_options.empty()) && !c.filter_and_assign)
+            die("option " + (with_taxonomy ? std::string("--taxonomic-metadata") : c.taxonomy_options[0]) + " is not accepted without --filter-and-assign");
+        if (!with_taxonomy && !c.taxonomy_options.empty()) die("option " + c.taxonomy_options[0] + " is not accepted without --taxonomic-metadata");
+        if (!with_taxonomy) return;
         if (c.maximum_taxon_number < 1 || c.maximum_taxon_number > 16) die("--maximum-taxon-number must be between 1 and 16");
         if (c.ambiguous_score < 0 || c.ambiguous_ratio < 0.0) die("--ambiguous-score-threshold and --ambiguous-score-threshold-ratio must not be negative");
         if (c.discard > 0.0 && (c.ambiguous_score > 0 || c.ambiguous_ratio > 0.0))
@@ -1029,11 +955,12 @@ int run_meta(Config c) {
         if (rc == PMX_ERR_IO) die("option --taxonomic-metadata is not accepted: cannot read " + c.taxonomic_metadata);
         check(rc, "--taxonomic-metadata");
     }
-    Run run;
-    run.panman_path = c.panman;
-    pmx_panman* pm = run.panman();
-    if (!pm) die(std::string("opening the PanMAN: ") + pmx_last_error());
-    {   // the two builds are independent: side by side
+
+    // Leaves: the open PanMAN, run.idx and run.oidx; the two builds are independent: side by side.
+    void build_indexes() {
+        run.panman_path = c.panman;
+        pmx_panman* pm = run.panman();
+        if (!pm) die(std::string("opening the PanMAN: ") + pmx_last_error());
         int rc1 = PMX_OK, rc2 = PMX_OK;
         std::string e2;
         std::thread th([&]() { rc2 = pmx_index_build_ex(pm, c.k, c.s, c.t, c.l, c.open_syncmer ? 1 : 0, 0, PMX_INDEX_ORIENTED, -1, &run.oidx); if (rc2 != PMX_OK) e2 = pmx_last_error(); });
@@ -1041,46 +968,56 @@ int run_meta(Config c) {
         th.join();
         check(rc1, "building the index");
         if (rc2 != PMX_OK) die("building the oriented index: " + e2);
+        say(c, "index", "seed index + oriented seed index (in memory)");
     }
-    say(c, "index", "seed index + oriented seed index (in memory)");
-    const Reads reads(c.reads1, c.reads2, Reads::APPENDED);   // mates as sequenced, one after the other
-    // --gpus N: one rank per GPU, each with a contiguous shard of the reads above (R1 then R2); every rank ends with the whole
-    // sample's result (pmx_meta_attach_dist), rank 0 writes it
-    Ranks rk;
-    int code = 0;
-    if (!fork_ranks(c.gpus, rk, &code)) { run.close(); return code; }
-    if (rk.rank > 0) c.quiet = true;
-    int64_t lo = 0, hi = 0;
-    reads.shard(rk.rank, rk.world, &lo, &hi);
-    run.dev = rank_device(rk);
-    check(pmx_ctx_create(run.dev, &run.ctx), "opening the GPU");
-    run.dist = join_ranks(run.ctx, rk);
-    pmx_ctx* const ctx = run.ctx;
-    pmx_meta*& m = run.meta;
-    check(pmx_meta_create(ctx, run.idx, run.oidx, &m), "uploading the indexes");
-    if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
-    check(pmx_meta_set_dust(m, c.dust), "--dust");
-    check(pmx_meta_set_masks(m, c.mask_reads, c.mask_seeds), "--mask-reads / --mask-seeds");
-    check(pmx_meta_set_relative_masks(m, c.mask_reads_rf, c.mask_seeds_rf), "--mask-reads-relative-frequency / --mask-seeds-relative-frequency");
-    if (amplicons.a) {   // the amplicon of every read of this rank's shard, by its own name (mates one by one); unlisted: the last group
+
+    // Leaves: the whole sample's reads on the host (before the fork: every rank inherits them).
+    void read_reads() { reads_p.reset(new Reads(c.reads1, c.reads2, Reads::APPENDED)); }
+
+    // -> true in a rank, false in the parent once the ranks have ended (*code = the run's exit code).
+    // In a rank, leaves: rk, the shard [lo, hi), the rank's device open and the ranks joined (run.ctx, run.dist).
+    bool open_rank(int* code) {
+        if (!fork_ranks(c.gpus, rk, code)) return false;
+        if (rk.rank > 0) c.quiet = true;
+        reads().shard(rk.rank, rk.world, &lo, &hi);
+        run.dev = rank_device(rk);
+        check(pmx_ctx_create(run.dev, &run.ctx), "opening the GPU");
+        run.dist = join_ranks(run.ctx, rk);
+        return true;
+    }
+
+    // Leaves: run.meta with the indexes on the device, the ranks attached, --dust, the masks and, with --amplicon-depth, the
+    // amplicon of every read of this rank's shard, by its own name (mates one by one); unlisted: the last group.
+    void configure() {
+        pmx_meta*& m = run.meta;
+        check(pmx_meta_create(run.ctx, run.idx, run.oidx, &m), "uploading the indexes");
+        if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
+        check(pmx_meta_set_dust(m, c.dust), "--dust");
+        check(pmx_meta_set_masks(m, c.mask_reads, c.mask_seeds), "--mask-reads / --mask-seeds");
+        check(pmx_meta_set_relative_masks(m, c.mask_reads_rf, c.mask_seeds_rf), "--mask-reads-relative-frequency / --mask-seeds-relative-frequency");
+        if (!amplicons.a) return;
         const int32_t n_groups = pmx_amplicons_num_groups(amplicons.a);
         std::vector<int32_t> group((size_t)(hi - lo));
         for (int64_t r = lo; r < hi; ++r) {
-            const int32_t g = pmx_amplicons_lookup(amplicons.a, reads.name(r).c_str());
+            const int32_t g = pmx_amplicons_lookup(amplicons.a, reads().name(r).c_str());
             group[(size_t)(r - lo)] = g < 0 ? n_groups : g;
         }
         check(pmx_meta_set_amplicons(m, group.data(), hi - lo, n_groups), "--amplicon-depth");
-        if (!c.quiet) {   // (over the whole sample, whatever the shard)
-            int64_t unlisted = 0;
-            for (int64_t r = 0; r < reads.n_reads; ++r) unlisted += pmx_amplicons_lookup(amplicons.a, reads.name(r).c_str()) < 0;
-            say(c, "meta", "Amplicons: " + std::to_string(n_groups) + " groups in " + c.amplicon_depth + ", " + std::to_string(unlisted) + " of " +
-                               std::to_string(reads.n_reads) + " reads not listed");
-        }
+        if (c.quiet) return;
+        int64_t unlisted = 0;   // (over the whole sample, whatever the shard)
+        for (int64_t r = 0; r < reads().n_reads; ++r) unlisted += pmx_amplicons_lookup(amplicons.a, reads().name(r).c_str()) < 0;
+        say(c, "meta", "Amplicons: " + std::to_string(n_groups) + " groups in " + c.amplicon_depth + ", " + std::to_string(unlisted) + " of " +
+                           std::to_string(reads().n_reads) + " reads not listed");
     }
-    check(pmx_meta_set_reads(ctx, m, reads.concat.data(), reads.off.data() + lo, hi - lo), "seeding the reads");
-    if (c.mask_reads > 0 || c.mask_seeds > 0 || c.mask_reads_rf > 0.0 || c.mask_seeds_rf > 0.0) {   // the reference's two lines (src/mgsr.cpp:2220-2230)
+
+    // Reads: the shard.  Leaves: the merged reads of the whole sample in run.meta, masked when a mask is set.
+    void set_reads() { check(pmx_meta_set_reads(run.ctx, run.meta, reads().concat.data(), reads().off.data() + lo, hi - lo), "seeding the reads"); }
+
+    // the reference's two lines (src/mgsr.cpp:2220-2230)
+    void report_masks() const {
+        if (!masking()) return;
         int64_t dropped = 0, removed = 0, left = 0;
-        check(pmx_meta_mask_info(m, &dropped, &removed, &left), "the numbers of the masks");
+        check(pmx_meta_mask_info(run.meta, &dropped, &removed, &left), "the numbers of the masks");
         char rf[64];   // (a relative parameter as the reference's stream prints a double)
         snprintf(rf, sizeof(rf), "%g", c.mask_reads_rf > 0.0 ? c.mask_reads_rf : c.mask_seeds_rf);
         const bool whole_reads = c.mask_reads > 0 || c.mask_reads_rf > 0.0;
@@ -1091,38 +1028,190 @@ int run_meta(Config c) {
                                    : "Mask-seeds " + value + " turned on: " + std::to_string(removed) +
                                          " seeds are removed during placement and EM... Total reads to process: " + std::to_string(left));
     }
-    if (c.filter_and_assign) {
-        write_assigned(c, run, reads, taxonomy.t);
-        run.close();
-        return 0;
+
+    // ---- --filter-and-assign (writeAssignedReadsOut, src/main.cpp:522-558, :889-903), after set_reads: every read against every
+    // node, then the files.  `<prefix>.mgsr.assignedReads.fastq` holds the assigned reads in input order (FASTA input: quality
+    // `I`); `.mgsr.assignedReads.out` and `.mgsr.assignedReadsLCANode.out` hold one line per head node that has reads,
+    // `head[,nodes folded into it]<TAB>.<TAB>count<TAB>indices into the FASTQ`, by ascending DFS index of the head (the reference's
+    // orders come from hash-map iteration: DESIGN.md section 4.3).  With --taxonomic-metadata the reads spanning more than
+    // --maximum-taxon-number taxa are in none of the files, and the second column holds the taxon names of the head's subtree by
+    // ascending taxon index, `.` when there are none or too many.
+
+    // Leaves: the assignment on the device's side done and downloaded: state / lca / off / nodes / merged, head / folded.
+    void assign() {
+        pmx_meta* m = run.meta;
+        if (taxonomy.t) {
+            std::vector<int32_t> node_taxon;
+            for (int64_t v = 0; pmx_index_node_id(run.idx, v); ++v) node_taxon.push_back((int32_t)pmx_taxonomy_lookup(taxonomy.t, pmx_index_node_id(run.idx, v)));
+            check(pmx_meta_set_taxonomy(m, node_taxon.data(), (int64_t)node_taxon.size(), pmx_taxonomy_num_taxa(taxonomy.t), c.maximum_taxon_number), "--taxonomic-metadata");
+            check(pmx_meta_set_ambiguous(m, c.ambiguous_score, c.ambiguous_ratio), "--ambiguous-score-threshold");
+        }
+        check(pmx_meta_set_breadth(m, c.breadth_ratio ? 1 : 0), "--breadth-ratio");
+        check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
+        n_merged = pmx_meta_num_reads(m);
+        state.resize((size_t)std::max<int64_t>(n_merged, 1));
+        lca.resize(state.size());
+        nodes.resize((size_t)std::max<int64_t>(pmx_meta_assign_num_nodes(m), 1));
+        off.resize((size_t)n_merged + 1);
+        merged.resize((size_t)std::max<int64_t>(reads().n_reads, 1));
+        check(pmx_meta_assign_reads(m, state.data(), nullptr, lca.data(), nullptr, n_merged), "the reads' states");
+        check(pmx_meta_assign_nodes(m, off.data(), nodes.data(), (int64_t)nodes.size()), "the reads' nodes");
+        check(pmx_meta_raw_to_merged(m, merged.data(), reads().n_reads), "the reads' merged reads");
+        pmx_index_info info;
+        check(pmx_index_get_info(run.oidx, &info), "index info");
+        n_nodes = info.n_nodes;
+        head.resize((size_t)n_nodes);
+        check(pmx_index_node_heads(run.oidx, head.data()), "folding identical nodes");
+        folded.resize((size_t)n_nodes);
+        for (uint32_t v = 0; v < (uint32_t)n_nodes; ++v)
+            if (head[v] != v) folded[head[v]].push_back(v);
     }
-    check(pmx_meta_score(ctx, m, c.top_oc, nullptr, 0), "scoring the reads against the candidate nodes");
-    say(c, "meta", std::to_string(pmx_meta_num_reads(m)) + " distinct reads x " + std::to_string(pmx_meta_num_candidates(m)) + " candidate nodes");
-    pmx_meta_params mp;
-    memset(&mp, 0, sizeof(mp));
-    mp.error_rate = 0.005; mp.em_convergence = c.em_convergence; mp.em_delta_threshold = c.em_delta; mp.prop_threshold = 0.005; mp.discard = c.discard;
-    mp.em_max_iterations = c.em_max_iterations; mp.em_max_rounds = c.em_max_rounds;
-    check(pmx_meta_em(ctx, m, &mp), "estimating the abundances");
-    if (rk.rank > 0) { run.close(); return 0; }
-    const std::string path = c.output + ".mgsr.abundance.out";
-    FILE* f = fopen(path.c_str(), "w");
-    if (!f) die("cannot write " + path);
-    const int64_t n_h = pmx_meta_num_haplotypes(m);
-    if (n_h == 0) fprintf(stderr, "No reads remain for node scoring and EM after discarding low-score reads... Exiting... \n");   // src/main.cpp:1244-1247
-    for (int64_t i = 0; i < n_h; ++i) {
-        uint32_t node = 0;
-        double prop = 0;
-        int64_t n_mem = 0;
-        check(pmx_meta_haplotype(m, i, &node, &prop, &n_mem, nullptr, 0), "haplotype");
-        std::vector<uint32_t> mem((size_t)std::max<int64_t>(n_mem, 1));
-        check(pmx_meta_haplotype(m, i, nullptr, nullptr, nullptr, mem.data(), (int64_t)mem.size()), "haplotype members");
-        std::string ids = pmx_index_node_id(run.idx, node);
-        for (int64_t k = 0; k < n_mem; ++k) { ids += ","; ids += pmx_index_node_id(run.idx, mem[(size_t)k]); }
-        fprintf(f, "%s\t%.5f\n", ids.c_str(), prop);
+
+    // Reads: state, merged, the reads.  Leaves: the FASTQ, `copies`, the four tallies.
+    void write_fastq() {
+        const Reads& rd = reads();
+        fq_path = c.output + ".mgsr.assignedReads.fastq";
+        FILE* fq = fopen(fq_path.c_str(), "w");
+        if (!fq) die("cannot write " + fq_path);
+        copies.resize((size_t)n_merged);
+        for (int64_t r = 0; r < rd.n_reads; ++r) {
+            const int64_t mr = merged[(size_t)r];
+            const int st = mr < 0 ? PMX_META_UNMAPPED : state[(size_t)mr];
+            if (st != PMX_META_ASSIGNED) { (st == PMX_META_OVER_TAXA ? n_over : st == PMX_META_DISCARDED ? n_discarded : n_unmapped)++; continue; }
+            const size_t at = (size_t)rd.off[(size_t)r], len = (size_t)(rd.off[(size_t)r + 1] - rd.off[(size_t)r]);
+            const std::string qual = len > 0 && rd.quals[at] == '\0' ? std::string(len, 'I') : rd.quals.substr(at, len);   // src/main.cpp:889-903
+            fprintf(fq, "@%s\n%.*s\n+\n%s\n", rd.name(r).c_str(), (int)len, rd.concat.data() + at, qual.c_str());
+            copies[(size_t)mr].push_back(n_written++);
+        }
+        fclose(fq);
     }
-    fclose(f);
-    say(c, "meta", path + " (" + std::to_string(n_h) + " haplotypes)");
-    run.close();
+
+    // one of the two node-list files: a line per head with reads (`groups[h]`: their FASTQ positions, sorted here)
+    void write_node_list(const std::string& path, std::vector<std::vector<int64_t>>& groups) const {
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) die("cannot write " + path);
+        for (uint32_t h = 0; h < (uint32_t)n_nodes; ++h) {
+            std::vector<int64_t>& g = groups[h];
+            if (g.empty()) continue;
+            std::sort(g.begin(), g.end());
+            std::string taxa;
+            uint32_t tx[16];
+            const int64_t n_tx = taxonomy.t ? pmx_meta_node_taxa(run.meta, h, tx, 16) : 0;
+            for (int64_t i = 0; i < n_tx; ++i) { if (i) taxa += ","; taxa += pmx_taxonomy_taxon_name(taxonomy.t, tx[i]); }
+            fprintf(f, "%s\t%s\t%zu\t", ids_of_head(h).c_str(), taxa.empty() ? "." : taxa.c_str(), g.size());
+            for (size_t i = 0; i < g.size(); ++i) fprintf(f, i ? ",%lld" : "%lld", (long long)g[i]);
+            fputc('\n', f);
+        }
+        fclose(f);
+    }
+
+    // Reads: off / nodes / lca / head, copies.  Read -> nodes inverted to head -> reads, for the assigned nodes and for the LCA
+    // node.  Leaves: the two node-list files.
+    void write_node_lists() const {
+        std::vector<std::vector<int64_t>> by_node((size_t)n_nodes), by_lca((size_t)n_nodes);
+        for (int64_t mr = 0; mr < n_merged; ++mr) {
+            if (copies[(size_t)mr].empty()) continue;
+            uint32_t prev = UINT32_MAX;
+            std::vector<uint32_t> hs;
+            for (int64_t q = off[(size_t)mr]; q < off[(size_t)mr + 1]; ++q) hs.push_back(head[nodes[(size_t)q]]);
+            std::sort(hs.begin(), hs.end());
+            for (uint32_t h : hs) {
+                if (h != prev) by_node[h].insert(by_node[h].end(), copies[(size_t)mr].begin(), copies[(size_t)mr].end());
+                prev = h;
+            }
+            std::vector<int64_t>& l = by_lca[head[lca[(size_t)mr]]];
+            l.insert(l.end(), copies[(size_t)mr].begin(), copies[(size_t)mr].end());
+        }
+        write_node_list(c.output + ".mgsr.assignedReads.out", by_node);
+        write_node_list(c.output + ".mgsr.assignedReadsLCANode.out", by_lca);
+    }
+
+    // --breadth-ratio (src/main.cpp:992-1013, calculateBreadthRatio, src/mgsr.cpp:6518-6584): a line per head node, with or without
+    // reads, in the pre-order of the collapsed tree (= ascending DFS index of the heads); the header alone when no read was assigned
+    void write_breadths() const {
+        const std::string path = c.output + ".mgsr.breadths.out";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) die("cannot write " + path);
+        fputs("NodeId\tTotalRefSeeds\tObservedBreadthCount\tObservedBreadthRatio\tTotalDepth\tMeanDepth\tExpectedBreadthRatio\tObservedToExpectedBreadthRatio\n", f);
+        std::vector<uint64_t> total((size_t)n_nodes), observed((size_t)n_nodes), depth((size_t)n_nodes);
+        check(pmx_meta_breadth(run.meta, total.data(), observed.data(), depth.data(), n_nodes), "the breadth of the nodes");
+        for (uint32_t h = 0; n_written > 0 && h < (uint32_t)n_nodes; ++h) {
+            if (head[h] != h) continue;
+            const double t = (double)total[h];
+            const double ratio = total[h] > 0 ? (double)observed[h] / t : 0.0, mean = total[h] > 0 ? (double)depth[h] / t : 0.0;
+            const double expected = mean > 0 ? 1.0 - std::exp(-mean) : 0.0;
+            fprintf(f, "%s\t%llu\t%llu\t%g\t%llu\t%g\t%g\t%g\n", ids_of_head(h).c_str(), (unsigned long long)total[h], (unsigned long long)observed[h], ratio,
+                    (unsigned long long)depth[h], mean, expected, expected > 0 ? ratio / expected : 0.0);
+        }
+        fclose(f);
+        say(c, "meta", path);
+    }
+
+    // the line that ends the mode: the FASTQ's name and the four tallies of write_fastq
+    void report_assigned() const {
+        say(c, "meta", fq_path + " (" + std::to_string(n_written) + " assigned, " + std::to_string(n_discarded) + " discarded, " + std::to_string(n_unmapped) +
+                           " unmapped reads" +
+                           (taxonomy.t ? ", " + std::to_string(n_over) + " spanning more than " + std::to_string(c.maximum_taxon_number) + " taxa" : std::string()) + ")");
+    }
+
+    // ---- the abundances.  Reads: the merged reads.  Leaves: the candidates scored and the EM's haplotypes in run.meta, on every rank.
+    void estimate() {
+        pmx_meta* m = run.meta;
+        check(pmx_meta_score(run.ctx, m, c.top_oc, nullptr, 0), "scoring the reads against the candidate nodes");
+        say(c, "meta", std::to_string(pmx_meta_num_reads(m)) + " distinct reads x " + std::to_string(pmx_meta_num_candidates(m)) + " candidate nodes");
+        pmx_meta_params mp;
+        memset(&mp, 0, sizeof(mp));
+        mp.error_rate = 0.005; mp.em_convergence = c.em_convergence; mp.em_delta_threshold = c.em_delta; mp.prop_threshold = 0.005; mp.discard = c.discard;
+        mp.em_max_iterations = c.em_max_iterations; mp.em_max_rounds = c.em_max_rounds;
+        check(pmx_meta_em(run.ctx, m, &mp), "estimating the abundances");
+    }
+
+    // `<prefix>.mgsr.abundance.out`, one line per estimated haplotype: node id (+ the nodes merged into it, comma-joined) <TAB>
+    // proportion with five decimals, by proportion
+    void write_abundance() const {
+        pmx_meta* m = run.meta;
+        const std::string path = c.output + ".mgsr.abundance.out";
+        FILE* f = fopen(path.c_str(), "w");
+        if (!f) die("cannot write " + path);
+        const int64_t n_h = pmx_meta_num_haplotypes(m);
+        if (n_h == 0) fprintf(stderr, "No reads remain for node scoring and EM after discarding low-score reads... Exiting... \n");   // src/main.cpp:1244-1247
+        for (int64_t i = 0; i < n_h; ++i) {
+            uint32_t node = 0;
+            double prop = 0;
+            int64_t n_mem = 0;
+            check(pmx_meta_haplotype(m, i, &node, &prop, &n_mem, nullptr, 0), "haplotype");
+            std::vector<uint32_t> mem((size_t)std::max<int64_t>(n_mem, 1));
+            check(pmx_meta_haplotype(m, i, nullptr, nullptr, nullptr, mem.data(), (int64_t)mem.size()), "haplotype members");
+            fprintf(f, "%s\t%.5f\n", joined_ids(run.idx, node, mem.data(), (size_t)n_mem).c_str(), prop);
+        }
+        fclose(f);
+        say(c, "meta", path + " (" + std::to_string(n_h) + " haplotypes)");
+    }
+};
+
+int run_meta(const Config& c) {
+    MetaSample s(c);
+    s.refuse_options();
+    s.load_amplicons();
+    s.load_taxonomy();
+    s.build_indexes();
+    s.read_reads();
+    int code = 0;
+    if (!s.open_rank(&code)) { s.run.close(); return code; }
+    s.configure();
+    s.set_reads();
+    s.report_masks();
+    if (s.c.filter_and_assign) {
+        s.assign();
+        s.write_fastq();
+        s.write_node_lists();
+        if (s.c.breadth_ratio) s.write_breadths();
+        s.report_assigned();
+    } else {
+        s.estimate();
+        if (s.rk.rank == 0) s.write_abundance();
+    }
+    s.run.close();
     return 0;
 }
 

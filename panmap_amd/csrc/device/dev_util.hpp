@@ -141,6 +141,10 @@ inline void timer_end(pmx_ctx* ctx, const char* name, int launches) {
     t.launches = launches;
     t.pending = true;
 }
+// "No such span in this call": what an earlier call recorded under `name` is not reported again (pmx_last_kernel_ms < 0).
+inline void timer_cancel(pmx_ctx* ctx, const char* name) {
+    if (auto t = ctx->timers.find(name); t != ctx->timers.end()) t->second.pending = false;
+}
 // A span made of several pieces with host work between them (the chunks of pmx_meta_assign): timer_sum_reset, then per piece
 // timer_begin / timer_end and, once the stream was synchronized, timer_sum_add; pmx_last_kernel_ms reports the sum.
 inline void timer_sum_reset(pmx_ctx* ctx, const char* name) {

@@ -612,6 +612,7 @@ struct AssignStage {
             touch = mx <= std::max<int64_t>(mm->amb_abs, (int64_t)((double)mx * mm->amb_ratio));
     }
     void plan_chunks();
+    void begin();
     void run_chunk(int64_t r0, int64_t r1);
     void finish();
     void breadth_begin();
@@ -641,6 +642,28 @@ void AssignStage::plan_chunks() {
         }
     }
     chunk_first.push_back(n_reads);
+}
+
+// Leaves: the per-read device buffers of the call (d_tax and d_count zeroed: a read fills its first ids only, the scans read
+// one count past the last read), the summed spans of the call reset (no "meta_assign_taxa" span without a taxonomy) and,
+// with breadth, what breadth_begin leaves.
+void AssignStage::begin() {
+    const size_t n = (size_t)n_reads;
+    d_max.alloc(n); d_count.alloc(n + 1); d_first.alloc(n); d_last.alloc(n);
+    d_state.alloc(n + (breadth ? 3 : 0));   // (k_meta_breadth_rows reads the states by whole words)
+    if (max_taxa > 0) {
+        d_ntax.alloc(n); d_tax.alloc(n * (size_t)max_taxa);
+        PMX_HIP(hipMemsetAsync(d_tax.p, 0, sizeof(uint32_t) * n * (size_t)max_taxa, st));
+        timer_sum_reset(ctx, "meta_assign_taxa");
+    }
+    timer_sum_reset(ctx, "meta_assign");
+    timer_cancel(ctx, "meta_assign_taxa");
+    timer_sum_reset(ctx, "meta_assign_emit");
+    if (breadth) {
+        timer_sum_reset(ctx, "meta_breadth");
+        breadth_begin();
+    }
+    PMX_HIP(hipMemsetAsync(d_count.p, 0, sizeof(uint32_t) * (n + 1), st));
 }
 
 // Merged reads [r0, r1): their distinct seedmers' rows, the reads' maxima and assigned nodes.
@@ -702,24 +725,19 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
                            touch ? d_touch.p : nullptr);
     hipLaunchKernelGGL(k_assign_prefix_xor, dim3(grid_for(2 * n_rows * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words);
     const dim3 grid(grid_for(n * 64, 256, ctx->n_cu * 16)), block(256);
-    if (m->longest < 128)
-        hipLaunchKernelGGL(k_meta_assign_max<7>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p, words, m->n_nodes,
-                           discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
-    else
-        hipLaunchKernelGGL(k_meta_assign_max<16>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p, words, m->n_nodes,
-                           discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
+    meta_with_planes(m->longest, [&](auto planes) {
+        hipLaunchKernelGGL(k_meta_assign_max<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
+                           words, m->n_nodes, discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
+    });
     PMX_HIP(hipGetLastError());
     if (max_taxa > 0) {   // its own span: "meta_assign" then ends here, the scan below belongs to "meta_assign_taxa"
         timer_end(ctx, "meta_assign", 1);
         timer_begin(ctx, "meta_assign_taxa");
-        if (near) {
-            if (m->longest < 128)
-                hipLaunchKernelGGL(k_meta_assign_near<7>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
-                                   touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
-            else
-                hipLaunchKernelGGL(k_meta_assign_near<16>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
-                                   touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
-        }
+        if (near)
+            meta_with_planes(m->longest, [&](auto planes) {
+                hipLaunchKernelGGL(k_meta_assign_near<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p,
+                                   d_rev.p, touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
+            });
         hipLaunchKernelGGL(k_meta_assign_taxa, grid, block, 0, st, near ? d_near.p : d_wmask.p, words, n, m->tx_over.p, m->tx_count.p, m->tx_ids.p, max_taxa,
                            d_state.p + r0, d_count.p + r0, d_ntax.p + r0, d_tax.p + (size_t)r0 * (size_t)max_taxa);
         PMX_HIP(hipGetLastError());
@@ -840,6 +858,28 @@ std::vector<uint64_t> total_ref_seeds(const pmx_meta* m) {
     }
     return total;
 }
+
+// The results of a call that assigns nothing, sized for the merged reads: every read unmapped, no nodes, no taxa; with breadth
+// zero counts per node and TotalRefSeeds, computed on the first such call.  No "meta_breadth" spans are left from an earlier call.
+void reset_assign_results(pmx_ctx* ctx, pmx_meta* m) {
+    const size_t n = (size_t)m->n_reads;
+    m->as_state.assign(n, PMX_META_UNMAPPED);
+    m->as_max.assign(n, 0);
+    m->as_count.assign(n, 0);
+    m->as_lca.assign(n, UINT32_MAX);
+    m->as_off.assign(n + 1, 0);
+    m->as_nodes.clear();
+    m->as_max_taxa = m->max_taxa;
+    m->as_ntax.assign(n, 0);
+    m->as_tax.assign(n * (size_t)m->max_taxa, 0);
+    if (m->breadth_on) {
+        if (m->total_ref_seeds.empty()) m->total_ref_seeds = total_ref_seeds(m);
+        m->br_observed.assign((size_t)m->n_nodes, 0);
+        m->br_depth.assign((size_t)m->n_nodes, 0);
+    }
+    timer_cancel(ctx, "meta_breadth");
+    timer_cancel(ctx, "meta_breadth_count");
+}
 }  // namespace
 
 extern "C" {
@@ -867,45 +907,13 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     PMX_HIP(hipSetDevice(ctx->device));
     m->assigned = false;
     m->as_breadth = false;
-    const int64_t n = m->n_reads;
-    int64_t longest = 0;
-    for (int64_t r = 0; r < n; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
-    if (longest >= 65535) return fail(PMX_ERR_UNSUPPORTED, "a read with 65,535 seedmers or more (16-bit scores)");
-    m->longest = longest;
-    m->as_state.assign((size_t)n, PMX_META_UNMAPPED);
-    m->as_max.assign((size_t)n, 0);
-    m->as_count.assign((size_t)n, 0);
-    m->as_lca.assign((size_t)n, UINT32_MAX);
-    m->as_off.assign((size_t)n + 1, 0);
-    m->as_nodes.clear();
-    m->as_max_taxa = m->max_taxa;
-    m->as_ntax.assign((size_t)n, 0);
-    m->as_tax.assign((size_t)n * (size_t)m->max_taxa, 0);
-    if (m->breadth_on) {
-        if (m->total_ref_seeds.empty()) m->total_ref_seeds = total_ref_seeds(m);
-        m->br_observed.assign((size_t)m->n_nodes, 0);
-        m->br_depth.assign((size_t)m->n_nodes, 0);
-    }
-    for (const char* span : {"meta_breadth", "meta_breadth_count"})   // (no such span without breadth)
-        if (auto t = ctx->timers.find(span); t != ctx->timers.end()) t->second.pending = false;
-    if (n > 0) {
+    const int rc = meta_longest_read(m);
+    if (rc != PMX_OK) return rc;
+    reset_assign_results(ctx, m);
+    if (m->n_reads > 0) {
         AssignStage S(ctx, m, discard);
         S.plan_chunks();
-        S.d_max.alloc((size_t)n); S.d_count.alloc((size_t)n + 1); S.d_first.alloc((size_t)n); S.d_last.alloc((size_t)n);
-        S.d_state.alloc((size_t)n + (m->breadth_on ? 3 : 0));   // (k_meta_breadth_rows reads the states by whole words)
-        if (m->max_taxa > 0) {
-            S.d_ntax.alloc((size_t)n); S.d_tax.alloc((size_t)n * (size_t)m->max_taxa);
-            PMX_HIP(hipMemsetAsync(S.d_tax.p, 0, sizeof(uint32_t) * (size_t)n * (size_t)m->max_taxa, ctx->stream));   // (a read fills its first ids only)
-            timer_sum_reset(ctx, "meta_assign_taxa");
-        }
-        timer_sum_reset(ctx, "meta_assign");
-        if (auto t = ctx->timers.find("meta_assign_taxa"); t != ctx->timers.end()) t->second.pending = false;   // (no such span without a taxonomy)
-        timer_sum_reset(ctx, "meta_assign_emit");
-        if (S.breadth) {
-            timer_sum_reset(ctx, "meta_breadth");
-            S.breadth_begin();
-        }
-        PMX_HIP(hipMemsetAsync(S.d_count.p, 0, sizeof(uint32_t) * ((size_t)n + 1), ctx->stream));
+        S.begin();
         for (size_t c = 0; c + 1 < S.chunk_first.size(); ++c) S.run_chunk(S.chunk_first[c], S.chunk_first[c + 1]);
         S.finish();
     }

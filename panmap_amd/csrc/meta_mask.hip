@@ -38,6 +38,19 @@
 // count into its hash's total, and the GROUPED forms of k_meta_mask_flag / k_meta_mask_compact read the count through the pid
 // and compare it with thr[amplicon of the read].  No launch depends on the number of amplicons and there is no
 // amplicons x hashes table.  Without amplicons nothing of this runs or is allocated.
+//
+// The host side is MaskStage, a struct that lives for one call, one function per step; meta_apply_masks calls them in order:
+//   reset_results      the results of a mask that removes nothing (host);
+//   group_thresholds   amplicons: thr[] and m->amp_thr (host); a sample without merged reads ends here;
+//   plan_sorted_path   the reads beyond the in-LDS bound, with the offsets of their keys (host);
+//   upload             every allocation but the survivors', and the host-to-device copies;
+//   clear_counters     the memsets, the first work inside the "meta_mask" span;
+//   rank_pairs         amplicons: keys, the "meta_mask_sort" span, heads, scan, scatter;
+//   count              the in-LDS kernel, the sorted path, k_meta_amp_totals with amplicons;
+//   flag_and_size      k_meta_mask_flag, the three scans, the one synchronize that sizes the survivors;
+//   compact            the survivors' buffers, k_meta_mask_compact, k_meta_mask_compact_uniq; the span ends;
+//   publish            the host's copies, the (group, hash, count) triples, amp_left, h_raw_to_merged, the swaps, the numbers.
+// The GROUPED kernels are launched from one argument list each: the amplicon buffers' pointers are null without amplicons.
 // Resource report (gfx950): no kernel of this file uses scratch, all are at 8 waves/SIMD; the new ones take 10-18 VGPRs, the
 // GROUPED forms 38 / 39 against 36 / 32 of the plain ones.
 #include <hip/hip_runtime.h>
@@ -46,6 +59,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
@@ -261,58 +275,111 @@ unsigned long long relative_threshold(double rf, int64_t n_raw) {
     const double t = rf * (double)n_raw;
     return t >= 18446744073709551615.0 ? ~0ULL : (unsigned long long)(size_t)t;
 }
-}  // namespace
+template <class F>
+void with_grouped(bool grouped, F&& launch) {   // GROUPED as a compile-time constant: the launch is written once
+    if (grouped) launch(std::true_type());
+    else launch(std::false_type());
+}
 
-void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
-    const bool whole_reads = m->lowcov_reads > 0 || m->lowcov_reads_rf > 0;
-    const unsigned long long threshold = (unsigned long long)(whole_reads ? m->lowcov_reads : m->lowcov_seeds);
-    const int64_t n_reads = m->n_reads, n_seedmers = m->n_seedmers, n_uniq = (int64_t)m->h_uniq.size();
-    const bool grouped = m->amp_on;
-    hipStream_t st = ctx->stream;
-    const int G = ctx->n_cu * 8;
-    m->masked = true;
-    m->lowcov_reads_dropped = m->lowcov_seeds_removed = 0;
-    m->lowcov_reads_left = n_reads;
-    m->lowcov_hash = m->h_uniq;
-    m->lowcov_count.assign((size_t)n_uniq, 0);
-    // amplicons: the threshold of every group (the unlisted one, the last, always takes the absolute parameter)
-    std::vector<unsigned long long> thr;
-    if (grouped) {
-        const double rf = whole_reads ? m->lowcov_reads_rf : m->lowcov_seeds_rf;
-        thr.assign((size_t)m->n_amp, threshold);
-        if (rf > 0)
-            for (int32_t g = 0; g + 1 < m->n_amp; ++g) thr[(size_t)g] = relative_threshold(rf, m->amp_raw[(size_t)g]);
-        for (int32_t g = 0; g < m->n_amp; ++g) m->amp_thr[(size_t)g] = (int64_t)std::min<unsigned long long>(thr[(size_t)g], (unsigned long long)INT64_MAX);
-    }
-    if (auto t = ctx->timers.find("meta_mask"); t != ctx->timers.end()) t->second.pending = false;
-    if (auto t = ctx->timers.find("meta_mask_sort"); t != ctx->timers.end()) t->second.pending = false;
-    if (n_reads == 0 || n_seedmers == 0) return;   // (merged reads have entries: both or neither)
-
-    // the reads of the sorted path, with the offsets of their keys
-    const int bound = quadratic_bound();
+// One call of the mask step on a sample that has merged reads: one function per step, in the order meta_apply_masks calls
+// them.  The device buffers live until the call ends; every step throws (HipError).
+struct MaskStage {
+    pmx_ctx* const ctx;
+    pmx_meta* const m;
+    const hipStream_t st;
+    const int G;                              // blocks of a grid-stride launch at most
+    const bool whole_reads, grouped;          // --mask-reads (else --mask-seeds); with amplicons
+    const unsigned long long threshold;       // the absolute parameter
+    const int64_t n_reads, n_seedmers, n_uniq;   // before masking
+    std::vector<unsigned long long> thr;      // grouped: the threshold of every group
+    // plan_sorted_path
+    int bound = kMaskQuadratic;
     std::vector<uint32_t> long_read;
-    std::vector<int64_t> long_off(1, 0);
-    for (int64_t r = 0; r < n_reads; ++r) {
-        const int64_t n = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
-        if (n > bound) { long_read.push_back((uint32_t)r); long_off.push_back(long_off.back() + n); }
-    }
-    const int64_t n_long = (int64_t)long_read.size(), n_keys = long_off.back();
-
+    std::vector<int64_t> long_off;
+    int64_t n_long = 0, n_keys = 0;
+    // upload: per merged read, per distinct hash, the sorted path's keys
     DevBuf<int64_t> d_mult, d_new_len, d_new_off, d_long_off;
     DevBuf<unsigned long long> d_count, d_ctr;
     DevBuf<uint32_t> d_alive, d_read_pos, d_used, d_uid_pos, d_long_read;
     DevBuf<uint64_t> d_key, d_key_sorted;
     DevBuf<char> tmp;
-    d_mult.alloc((size_t)n_reads); d_new_len.alloc((size_t)n_reads + 1); d_new_off.alloc((size_t)n_reads + 1);
-    d_alive.alloc((size_t)n_reads + 1); d_read_pos.alloc((size_t)n_reads + 1);
-    d_count.alloc((size_t)n_uniq); d_used.alloc((size_t)n_uniq + 1); d_uid_pos.alloc((size_t)n_uniq + 1);
-    d_ctr.alloc(2);
-    // amplicons: per entry its pair's rank, per pair its key and count (at most one pair per entry), and d_count above the
-    // per-hash totals over the amplicons
+    // amplicons (null pointers otherwise): per entry its pair's rank, per pair its key and count (at most one pair per entry);
+    // d_count above then holds the per-hash totals over the amplicons
     DevBuf<int32_t> d_read_amp, o_amp;
     DevBuf<unsigned long long> d_thr, d_pair_count;
     DevBuf<uint64_t> d_akey, d_akey_sorted, d_pair_key;
     DevBuf<uint32_t> d_aval, d_aval_sorted, d_head, d_before, d_seed_pid;
+    const uint32_t* count_id = nullptr;       // what the counting kernels index their counters with: pids or uids
+    unsigned long long* counters = nullptr;   // ... and the counters: per pair or per hash
+    // flag_and_size: the survivors' sizes, the two counters of k_meta_mask_flag, the distinct pairs
+    int64_t left_seedmers = 0;
+    uint32_t left_reads = 0, left_uniq = 0, n_pairs = 0;
+    unsigned long long h_ctr[2] = {0, 0};
+    // compact: the survivors
+    DevBuf<int64_t> o_off, o_mult, o_count;
+    DevBuf<uint64_t> o_hash, o_uniq;
+    DevBuf<uint32_t> o_uid;
+    DevBuf<uint8_t> o_rev;
+
+    MaskStage(pmx_ctx* c, pmx_meta* mm)
+        : ctx(c), m(mm), st(c->stream), G(c->n_cu * 8), whole_reads(mm->lowcov_reads > 0 || mm->lowcov_reads_rf > 0), grouped(mm->amp_on),
+          threshold((unsigned long long)(whole_reads ? mm->lowcov_reads : mm->lowcov_seeds)), n_reads(mm->n_reads), n_seedmers(mm->n_seedmers),
+          n_uniq((int64_t)mm->h_uniq.size()) {}
+    bool empty() const { return n_reads == 0 || n_seedmers == 0; }   // (merged reads have entries: both or neither)
+    void reset_results();
+    void group_thresholds();
+    void plan_sorted_path();
+    void upload();
+    void clear_counters();
+    void rank_pairs();
+    void count();
+    void flag_and_size();
+    void compact();
+    void publish();
+};
+
+// Reads: the sample before masking.  Leaves: m->masked and the results of a mask that removes nothing: the three numbers, the
+// distinct hashes with zero counts.
+void MaskStage::reset_results() {
+    m->masked = true;
+    m->lowcov_reads_dropped = m->lowcov_seeds_removed = 0;
+    m->lowcov_reads_left = n_reads;
+    m->lowcov_hash = m->h_uniq;
+    m->lowcov_count.assign((size_t)n_uniq, 0);
+}
+
+// Amplicons only (host).  Reads: the parameters, m->amp_raw.  Leaves: thr[] and m->amp_thr: a share of the group's raw reads
+// under a relative parameter, else the absolute parameter; the unlisted group, the last, always takes the absolute one.
+void MaskStage::group_thresholds() {
+    if (!grouped) return;
+    const double rf = whole_reads ? m->lowcov_reads_rf : m->lowcov_seeds_rf;
+    thr.assign((size_t)m->n_amp, threshold);
+    if (rf > 0)
+        for (int32_t g = 0; g + 1 < m->n_amp; ++g) thr[(size_t)g] = relative_threshold(rf, m->amp_raw[(size_t)g]);
+    for (int32_t g = 0; g < m->n_amp; ++g) m->amp_thr[(size_t)g] = (int64_t)std::min<unsigned long long>(thr[(size_t)g], (unsigned long long)INT64_MAX);
+}
+
+// Host.  Reads: m->h_read_off.  Leaves: bound, and the reads with more entries than it, which the sorted path counts:
+// long_read[q] with the offset long_off[q] of its keys, n_long, n_keys.
+void MaskStage::plan_sorted_path() {
+    bound = quadratic_bound();
+    long_off.assign(1, 0);
+    for (int64_t r = 0; r < n_reads; ++r) {
+        const int64_t n = m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r];
+        if (n > bound) { long_read.push_back((uint32_t)r); long_off.push_back(long_off.back() + n); }
+    }
+    n_long = (int64_t)long_read.size();
+    n_keys = long_off.back();
+}
+
+// Reads: the plan, thr[], m->h_mult / h_read_amp.  Leaves: every buffer of the call but the survivors', allocated; on the
+// device the multiplicities, the long reads' plan and, with amplicons, the reads' amplicons and thr[]; count_id / counters.
+// The amplicon buffers are made only when grouped.
+void MaskStage::upload() {
+    d_mult.alloc((size_t)n_reads); d_new_len.alloc((size_t)n_reads + 1); d_new_off.alloc((size_t)n_reads + 1);
+    d_alive.alloc((size_t)n_reads + 1); d_read_pos.alloc((size_t)n_reads + 1);
+    d_count.alloc((size_t)n_uniq); d_used.alloc((size_t)n_uniq + 1); d_uid_pos.alloc((size_t)n_uniq + 1);
+    d_ctr.alloc(2);
     if (grouped) {
         d_read_amp.alloc((size_t)n_reads); d_thr.alloc(thr.size()); d_pair_count.alloc((size_t)n_seedmers); d_pair_key.alloc((size_t)n_seedmers);
         d_akey.alloc((size_t)n_seedmers); d_akey_sorted.alloc((size_t)n_seedmers); d_aval.alloc((size_t)n_seedmers); d_aval_sorted.alloc((size_t)n_seedmers);
@@ -320,36 +387,49 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
         PMX_HIP(hipMemcpyAsync(d_read_amp.p, m->h_read_amp.data(), sizeof(int32_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
         PMX_HIP(hipMemcpyAsync(d_thr.p, thr.data(), sizeof(unsigned long long) * thr.size(), hipMemcpyHostToDevice, st));
     }
-    const uint32_t* count_id = grouped ? d_seed_pid.p : m->d_seed_uid.p;           // what the counting kernels index their counters with
-    unsigned long long* counters = grouped ? d_pair_count.p : d_count.p;
+    count_id = grouped ? d_seed_pid.p : m->d_seed_uid.p;
+    counters = grouped ? d_pair_count.p : d_count.p;
     PMX_HIP(hipMemcpyAsync(d_mult.p, m->h_mult.data(), sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
     if (n_long > 0) {
         d_long_read.alloc((size_t)n_long); d_long_off.alloc((size_t)n_long + 1); d_key.alloc((size_t)n_keys); d_key_sorted.alloc((size_t)n_keys);
         PMX_HIP(hipMemcpyAsync(d_long_read.p, long_read.data(), sizeof(uint32_t) * (size_t)n_long, hipMemcpyHostToDevice, st));
         PMX_HIP(hipMemcpyAsync(d_long_off.p, long_off.data(), sizeof(int64_t) * ((size_t)n_long + 1), hipMemcpyHostToDevice, st));
     }
+}
 
-    timer_begin(ctx, "meta_mask");
+// Leaves: zero in the counters of every hash (and pair), in used[], in the two counters of k_meta_mask_flag and in the entry
+// past the last read of new_len[] / alive[] (the scans run over one entry more: their totals).
+void MaskStage::clear_counters() {
     PMX_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long) * (size_t)n_uniq, st));
     PMX_HIP(hipMemsetAsync(d_used.p, 0, sizeof(uint32_t) * ((size_t)n_uniq + 1), st));
     PMX_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long) * 2, st));
-    PMX_HIP(hipMemsetAsync(d_new_len.p + n_reads, 0, sizeof(int64_t), st));   // (the scans run over one entry more: their totals)
+    PMX_HIP(hipMemsetAsync(d_new_len.p + n_reads, 0, sizeof(int64_t), st));
     PMX_HIP(hipMemsetAsync(d_alive.p + n_reads, 0, sizeof(uint32_t), st));
-    if (grouped) {
-        PMX_HIP(hipMemsetAsync(d_pair_count.p, 0, sizeof(unsigned long long) * (size_t)n_seedmers, st));
-        hipLaunchKernelGGL(k_meta_amp_keys, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_read_amp.p, n_reads,
-                           d_akey.p, d_aval.p);
-        unsigned end_bit = 32;   // (the uid, and the bits of the greatest amplicon)
-        while (end_bit < 64 && ((uint64_t)(m->n_amp - 1) >> (end_bit - 32)) != 0) ++end_bit;
-        timer_begin(ctx, "meta_mask_sort");   // (a span of its own inside "meta_mask": the share the key sort takes)
-        PMX_ROCPRIM(tmp, radix_sort_pairs, d_akey.p, d_akey_sorted.p, d_aval.p, d_aval_sorted.p, (size_t)n_seedmers, 0u, end_bit, st);
-        timer_end(ctx, "meta_mask_sort", 1);
-        hipLaunchKernelGGL(k_meta_amp_heads, dim3(grid_for(n_seedmers + 1, 256, G)), dim3(256), 0, st, d_akey_sorted.p, n_seedmers, d_head.p);
-        PMX_HIP(hipGetLastError());
-        PMX_ROCPRIM(tmp, exclusive_scan, d_head.p, d_before.p, 0u, (size_t)n_seedmers + 1, rocprim::plus<uint32_t>(), st);
-        hipLaunchKernelGGL(k_meta_amp_scatter, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_akey_sorted.p, d_aval_sorted.p, d_head.p, d_before.p,
-                           n_seedmers, d_seed_pid.p, d_pair_key.p);
-    }
+    if (grouped) PMX_HIP(hipMemsetAsync(d_pair_count.p, 0, sizeof(unsigned long long) * (size_t)n_seedmers, st));
+}
+
+// Amplicons only: the (amplicon, hash) pairs ranked.  Reads: the merged lists on the device, d_read_amp.  Leaves: d_seed_pid
+// (per entry the rank of its pair, ascending by (amplicon, hash)), d_pair_key (per pair its key), d_before[n_seedmers] (the
+// number of distinct pairs); the "meta_mask_sort" span around the key sort.
+void MaskStage::rank_pairs() {
+    hipLaunchKernelGGL(k_meta_amp_keys, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_read_amp.p, n_reads,
+                       d_akey.p, d_aval.p);
+    unsigned end_bit = 32;   // (the uid, and the bits of the greatest amplicon)
+    while (end_bit < 64 && ((uint64_t)(m->n_amp - 1) >> (end_bit - 32)) != 0) ++end_bit;
+    timer_begin(ctx, "meta_mask_sort");   // (a span of its own inside "meta_mask": the share the key sort takes)
+    PMX_ROCPRIM(tmp, radix_sort_pairs, d_akey.p, d_akey_sorted.p, d_aval.p, d_aval_sorted.p, (size_t)n_seedmers, 0u, end_bit, st);
+    timer_end(ctx, "meta_mask_sort", 1);
+    hipLaunchKernelGGL(k_meta_amp_heads, dim3(grid_for(n_seedmers + 1, 256, G)), dim3(256), 0, st, d_akey_sorted.p, n_seedmers, d_head.p);
+    PMX_HIP(hipGetLastError());
+    PMX_ROCPRIM(tmp, exclusive_scan, d_head.p, d_before.p, 0u, (size_t)n_seedmers + 1, rocprim::plus<uint32_t>(), st);
+    hipLaunchKernelGGL(k_meta_amp_scatter, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_akey_sorted.p, d_aval_sorted.p, d_head.p, d_before.p,
+                       n_seedmers, d_seed_pid.p, d_pair_key.p);
+}
+
+// Reads: count_id (uids, or pids), the multiplicities, the plan.  Leaves: counters[] = per hash (per pair) the sum of the
+// multiplicities of the merged reads that carry it: the in-LDS kernel for the reads within the bound, keys + sort + add for the
+// longer ones.  With amplicons also d_count[] = every hash's total over its pairs.
+void MaskStage::count() {
     if (n_long < n_reads)
         hipLaunchKernelGGL(k_meta_mask_count, dim3(grid_for(n_reads * 64, 64 * kMaskWaves, G)), dim3(64 * kMaskWaves), 0, st, m->d_read_off.p, count_id,
                            d_mult.p, n_reads, bound, counters);
@@ -361,53 +441,52 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
         PMX_ROCPRIM(tmp, radix_sort_keys, d_key.p, d_key_sorted.p, (size_t)n_keys, 0u, end_bit, st);
         hipLaunchKernelGGL(k_meta_mask_long_add, dim3(grid_for(n_keys, 256, G)), dim3(256), 0, st, d_key_sorted.p, n_keys, d_long_read.p, d_mult.p, counters);
     }
-    if (grouped) {
+    if (grouped)
         hipLaunchKernelGGL(k_meta_amp_totals, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_pair_key.p, d_pair_count.p, d_before.p + n_seedmers,
                            d_count.p);
-        hipLaunchKernelGGL(k_meta_mask_flag<true>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, n_reads,
-                           d_pair_count.p, threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, d_seed_pid.p, d_read_amp.p, d_thr.p);
-    } else {
-        hipLaunchKernelGGL(k_meta_mask_flag<false>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, n_reads, d_count.p,
-                           threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, (const uint32_t*)nullptr, (const int32_t*)nullptr,
-                           (const unsigned long long*)nullptr);
-    }
+}
+
+// Reads: counters[], the thresholds.  Leaves: per read its new length and alive[], per hash used[], their exclusive scans
+// (d_new_off, d_read_pos, d_uid_pos) and, after the call's one synchronize before the compaction, the survivors' sizes
+// left_seedmers / left_reads / left_uniq, h_ctr[] and n_pairs on the host.
+void MaskStage::flag_and_size() {
+    with_grouped(grouped, [&](auto g) {
+        hipLaunchKernelGGL(k_meta_mask_flag<decltype(g)::value>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p,
+                           n_reads, counters, threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, d_seed_pid.p, d_read_amp.p, d_thr.p);
+    });
     PMX_HIP(hipGetLastError());
     PMX_ROCPRIM(tmp, exclusive_scan, d_new_len.p, d_new_off.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), st);
     PMX_ROCPRIM(tmp, exclusive_scan, d_alive.p, d_read_pos.p, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st);
     PMX_ROCPRIM(tmp, exclusive_scan, d_used.p, d_uid_pos.p, 0u, (size_t)n_uniq + 1, rocprim::plus<uint32_t>(), st);
-    // the survivors' sizes, for the buffers of the compaction
-    int64_t left_seedmers = 0;
-    uint32_t left_reads = 0, left_uniq = 0;
-    unsigned long long h_ctr[2] = {0, 0};
     PMX_HIP(hipMemcpyAsync(&left_seedmers, d_new_off.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(&left_reads, d_read_pos.p + n_reads, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(&left_uniq, d_uid_pos.p + n_uniq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(h_ctr, d_ctr.p, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
-    uint32_t n_pairs = 0;
     if (grouped) PMX_HIP(hipMemcpyAsync(&n_pairs, d_before.p + n_seedmers, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PMX_HIP(hipStreamSynchronize(st));
-    DevBuf<int64_t> o_off, o_mult, o_count;
-    DevBuf<uint64_t> o_hash, o_uniq;
-    DevBuf<uint32_t> o_uid;
-    DevBuf<uint8_t> o_rev;
+}
+
+// Reads: the flags' scans and the sizes.  Leaves: the survivors in o_*: offsets, hash / new uid / orientation per entry,
+// multiplicity (and amplicon) per read, the surviving distinct hashes with their counts before masking.
+void MaskStage::compact() {
     o_off.alloc((size_t)left_reads + 1); o_mult.alloc((size_t)left_reads); o_count.alloc((size_t)left_uniq);
     o_hash.alloc((size_t)left_seedmers); o_uid.alloc((size_t)left_seedmers); o_rev.alloc((size_t)left_seedmers); o_uniq.alloc((size_t)left_uniq);
-    if (grouped) {
-        o_amp.alloc((size_t)left_reads);
-        hipLaunchKernelGGL(k_meta_mask_compact<true>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p,
-                           m->d_uniq.p, d_mult.p, n_reads, d_pair_count.p, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p, o_hash.p,
-                           o_uid.p, o_rev.p, o_mult.p, d_seed_pid.p, d_read_amp.p, d_thr.p, o_amp.p);
-    } else {
-        hipLaunchKernelGGL(k_meta_mask_compact<false>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, m->d_seed_rev.p,
-                           m->d_uniq.p, d_mult.p, n_reads, d_count.p, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p, o_hash.p, o_uid.p,
-                           o_rev.p, o_mult.p, (const uint32_t*)nullptr, (const int32_t*)nullptr, (const unsigned long long*)nullptr, (int32_t*)nullptr);
-    }
+    if (grouped) o_amp.alloc((size_t)left_reads);
+    with_grouped(grouped, [&](auto g) {
+        hipLaunchKernelGGL(k_meta_mask_compact<decltype(g)::value>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p,
+                           m->d_seed_rev.p, m->d_uniq.p, d_mult.p, n_reads, counters, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p,
+                           o_hash.p, o_uid.p, o_rev.p, o_mult.p, d_seed_pid.p, d_read_amp.p, d_thr.p, o_amp.p);
+    });
     hipLaunchKernelGGL(k_meta_mask_compact_uniq, dim3(grid_for(n_uniq, 256, G)), dim3(256), 0, st, m->d_uniq.p, d_count.p, d_used.p, d_uid_pos.p, n_uniq,
                        o_uniq.p, o_count.p);
     PMX_HIP(hipGetLastError());
-    timer_end(ctx, "meta_mask", 1);
+}
 
-    // the host's copies, which meta_assign.hip, the EM and the getters read; the counts before masking
+// Reads: o_*, d_count / d_read_pos, the pair table.  Leaves: the sample as its survivors -- the host's copies, which
+// meta_assign.hip, the EM and the getters read, m->d_* (swapped with o_*), n_reads / n_seedmers, h_raw_to_merged rewritten
+// through read_pos -- with the counts before masking (m->lowcov_count), the three numbers and, with amplicons, the
+// (group, hash, count) triples before masking in pair order, the survivors' amplicons and amp_left.
+void MaskStage::publish() {
     std::vector<uint32_t> read_pos((size_t)n_reads + 1);
     PMX_HIP(hipMemcpyAsync(m->lowcov_count.data(), d_count.p, sizeof(int64_t) * (size_t)n_uniq, hipMemcpyDeviceToHost, st));
     PMX_HIP(hipMemcpyAsync(read_pos.data(), d_read_pos.p, sizeof(uint32_t) * ((size_t)n_reads + 1), hipMemcpyDeviceToHost, st));
@@ -424,7 +503,7 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
         PMX_HIP(hipMemcpyAsync(m->h_uniq.data(), o_uniq.p, sizeof(uint64_t) * (size_t)left_uniq, hipMemcpyDeviceToHost, st));
     }
     std::vector<uint64_t> pair_key((size_t)n_pairs);
-    if (grouped) {   // the triples before masking (in pair order: ascending by (amplicon, hash)) and the survivors' amplicons
+    if (grouped) {
         m->ampc_count.resize((size_t)n_pairs);
         m->h_read_amp.resize((size_t)left_reads);
         PMX_HIP(hipMemcpyAsync(pair_key.data(), d_pair_key.p, sizeof(uint64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
@@ -451,15 +530,30 @@ void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     m->lowcov_seeds_removed = (int64_t)h_ctr[1];
     m->lowcov_reads_left = left_reads;
 }
+}  // namespace
 
-bool meta_masks_set(pmx_ctx* ctx, pmx_meta* m) {
+// The mask step of pmx_meta_set_reads.  False when no mask is set: m->masked cleared, nothing launched or allocated.  Else the
+// steps of MaskStage in order; a sample without merged reads ends after the host's resets, ahead of every allocation and
+// launch.  Either way no "meta_mask" / "meta_mask_sort" span is left from an earlier call; a run that launches records its own.
+bool meta_apply_masks(pmx_ctx* ctx, pmx_meta* m) {
     m->masked = false;
-    if (m->lowcov_reads <= 0 && m->lowcov_seeds <= 0 && !(m->lowcov_reads_rf > 0) && !(m->lowcov_seeds_rf > 0)) {
-        if (auto t = ctx->timers.find("meta_mask"); t != ctx->timers.end()) t->second.pending = false;   // (no such span without a mask)
-        if (auto t = ctx->timers.find("meta_mask_sort"); t != ctx->timers.end()) t->second.pending = false;
-        return false;
-    }
-    meta_apply_masks(ctx, m);
+    timer_cancel(ctx, "meta_mask");
+    timer_cancel(ctx, "meta_mask_sort");
+    if (meta_masks_above_zero(m->lowcov_reads, m->lowcov_seeds, m->lowcov_reads_rf, m->lowcov_seeds_rf) == 0) return false;
+    MaskStage S(ctx, m);
+    S.reset_results();
+    S.group_thresholds();
+    if (S.empty()) return true;
+    S.plan_sorted_path();
+    S.upload();
+    timer_begin(ctx, "meta_mask");
+    S.clear_counters();
+    if (S.grouped) S.rank_pairs();
+    S.count();
+    S.flag_and_size();
+    S.compact();
+    timer_end(ctx, "meta_mask", 1);
+    S.publish();
     return true;
 }
 
@@ -471,22 +565,11 @@ bool meta_masks_set(pmx_ctx* ctx, pmx_meta* m) {
 int meta_masked_overlap_coefficients(pmx_ctx* ctx, pmx_meta* m) {
     m->oc.assign((size_t)m->n_nodes, 0.0);
     if (m->n_reads == 0) return PMX_OK;
-    pmx_place_params pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.min_read_support = 1;
-    pmx_place_result res;
     int64_t n_kept = 0;
     for (int64_t w : m->h_mult) n_kept += w;
     int rc = pmx_place_reset(ctx, m->placer);
     if (rc == PMX_OK) rc = pmx_place_histogram_merge_device(ctx, m->placer, m->d_uniq.p, m->d_uniq_count.p, (int64_t)m->h_uniq.size());
-    if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept, &res);
-    if (rc != PMX_OK) return rc;
-    std::vector<int64_t> counts2((size_t)m->n_nodes * 2);
-    rc = pmx_place_node_outputs(ctx, m->placer, nullptr, nullptr, counts2.data());
-    if (rc != PMX_OK) return rc;
-    for (int64_t v = 0; v < m->n_nodes; ++v)
-        m->oc[(size_t)v] = counts2[2 * (size_t)v + 1] > 0 ? (double)counts2[2 * (size_t)v] / (double)counts2[2 * (size_t)v + 1] : 0.0;
-    return PMX_OK;
+    return meta_overlap_from_histogram(ctx, m, rc, n_kept, nullptr);
 }
 
 extern "C" {
@@ -494,7 +577,7 @@ extern "C" {
 int pmx_meta_set_masks(pmx_meta* m, int64_t mask_reads, int64_t mask_seeds) {
     if (!m) return PMX_ERR_ARG;
     if (mask_reads < 0 || mask_seeds < 0) return fail(PMX_ERR_ARG, "pmx_meta_set_masks: a masking parameter must not be negative");
-    if ((mask_reads > 0) + (mask_seeds > 0) + (m->lowcov_reads_rf > 0) + (m->lowcov_seeds_rf > 0) > 1)
+    if (meta_masks_above_zero(mask_reads, mask_seeds, m->lowcov_reads_rf, m->lowcov_seeds_rf) > 1)
         return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");   // src/mgsr.cpp:2049-2053
     m->lowcov_reads = mask_reads;
     m->lowcov_seeds = mask_seeds;
@@ -504,7 +587,7 @@ int pmx_meta_set_masks(pmx_meta* m, int64_t mask_reads, int64_t mask_seeds) {
 int pmx_meta_set_relative_masks(pmx_meta* m, double reads_rf, double seeds_rf) {
     if (!m) return PMX_ERR_ARG;
     if (!(reads_rf >= 0) || !(seeds_rf >= 0)) return fail(PMX_ERR_ARG, "pmx_meta_set_relative_masks: a masking parameter must not be negative");
-    if ((reads_rf > 0) + (seeds_rf > 0) + (m->lowcov_reads > 0) + (m->lowcov_seeds > 0) > 1)
+    if (meta_masks_above_zero(m->lowcov_reads, m->lowcov_seeds, reads_rf, seeds_rf) > 1)
         return fail(PMX_ERR_ARG, "Only one masking parameter can be set at a time");
     m->lowcov_reads_rf = reads_rf;
     m->lowcov_seeds_rf = seeds_rf;

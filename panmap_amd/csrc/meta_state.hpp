@@ -1,10 +1,13 @@
 // What the translation units of --meta share: the state behind a pmx_meta handle (api_meta.hip makes and fills it,
 // meta_assign.hip reads the merged reads and the oriented index from it, meta_mask.hip rewrites the merged reads under a
-// low-coverage mask) and the two device helpers both scoring kernels use.
+// low-coverage mask), the two device helpers both scoring kernels use, and the few host helpers more than one of them needs.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "api_internal.hpp"
@@ -136,13 +139,38 @@ struct pmx_meta {
     pmx::DevBuf<unsigned long long> tx_over;
 };
 
-// meta_mask.hip, a step of pmx_meta_set_reads (after the lists were uploaded, when a mask is set): counts every distinct hash
-// of the merged reads, drops reads (lowcov_reads) or list entries (lowcov_seeds) whose count is at most the threshold and
-// leaves m->h_* / d_* / n_reads / n_seedmers / h_raw_to_merged describing the survivors.  With amplicons (m->amp_on) the counts
-// and the thresholds are per amplicon, and it also leaves h_read_amp, amp_thr, amp_left and the ampc_* triples.  Throws pmx::HipError.
-void meta_apply_masks(pmx_ctx* ctx, pmx_meta* m);
-// what pmx_meta_set_reads asks after upload_lists: false when no mask is set (m->masked cleared, no "meta_mask" span, nothing
-// launched or allocated), else meta_apply_masks has run
-bool meta_masks_set(pmx_ctx* ctx, pmx_meta* m);
+// how many of the four masking parameters are above 0: at most one may be ("Only one masking parameter ...", src/mgsr.cpp:2049-2053)
+inline int meta_masks_above_zero(int64_t reads, int64_t seeds, double reads_rf, double seeds_rf) {
+    return (reads > 0) + (seeds > 0) + (reads_rf > 0) + (seeds_rf > 0);
+}
+
+// The plane count of the bit-sliced scoring kernels for a sample whose longest merged read has `longest` seedmers: launch is
+// called with it as a compile-time constant, std::integral_constant<int, 7> (counts below 128) or <int, 16>.
+template <class F>
+inline void meta_with_planes(int64_t longest, F&& launch) {
+    if (longest < 128) launch(std::integral_constant<int, 7>());
+    else launch(std::integral_constant<int, 16>());
+}
+
+// m->longest = the seedmers of the longest merged read; refused from 65,535 on (the scores are 16-bit)
+inline int meta_longest_read(pmx_meta* m) {
+    int64_t longest = 0;
+    for (int64_t r = 0; r < m->n_reads; ++r) longest = std::max(longest, m->h_read_off[(size_t)r + 1] - m->h_read_off[(size_t)r]);
+    if (longest >= 65535) return pmx::fail(PMX_ERR_UNSUPPORTED, "a read with 65,535 seedmers or more (16-bit scores)");
+    m->longest = longest;
+    return PMX_OK;
+}
+
+// meta_mask.hip, a step of pmx_meta_set_reads after the lists were uploaded.  False when no mask is set: m->masked cleared, no
+// "meta_mask" span, nothing launched or allocated.  Else it counts every distinct hash of the merged reads, drops reads
+// (lowcov_reads) or list entries (lowcov_seeds) whose count is at most the threshold and leaves m->h_* / d_* / n_reads /
+// n_seedmers / h_raw_to_merged describing the survivors.  With amplicons (m->amp_on) the counts and the thresholds are per
+// amplicon, and it also leaves h_read_amp, amp_thr, amp_left and the ampc_* triples.  Throws pmx::HipError.
+bool meta_apply_masks(pmx_ctx* ctx, pmx_meta* m);
 // ... and then the overlap coefficients of the survivors (m->oc), from the device arrays that step left; a place-API code
 int meta_masked_overlap_coefficients(pmx_ctx* ctx, pmx_meta* m);
+// api_meta.hip, the tail both overlap-coefficient paths share once the placer's histogram is loaded (`rc`: how loading it
+// went; not PMX_OK: returned as it is): the tree scored with every read seed kept and n_kept reads, the per-node counts,
+// m->oc = intersection / genome seeds.  `seeded`, when given, is the read set the histogram was seeded from: released as soon
+// as the tree is scored, however that went.
+int meta_overlap_from_histogram(pmx_ctx* ctx, pmx_meta* m, int rc, int64_t n_kept, std::unique_ptr<pmx_readset>* seeded);

@@ -233,6 +233,43 @@ def test_one_meta_through_masks_on_off_on(pmx, rsv_meta, masked, baseline):
     assert meta.mask_info() == masked[(2, 0)]["mask_info"]
 
 
+_NOTHING_TO_MASK = {"no_reads": [], "no_seedmers": [b"ACGTTGCAAC", b"TTGACCATGA", b"GATTACAGTC"]}   # (10 bases: below k, no seedmer)
+
+
+@pytest.mark.parametrize("reads", sorted(_NOTHING_TO_MASK))
+@pytest.mark.parametrize("setting", [(1, 0), (0, 1), "amplicons"], ids=["mask_reads", "mask_seeds", "amplicons_relative"])
+def test_a_sample_without_merged_reads(rsv_meta, masked, setting, reads):
+    """set_reads of no reads, and of three reads that yield no seedmer, under a mask: the mask step ends before it allocates or
+    launches anything.  No error, mask_info all zeros, no counts, no "meta_mask" span (the fixtures' masked runs left one), and
+    the Meta is as good as before: the family under the same mask equals the fixture's result.  "amplicons": two amplicon
+    groups (the reads alternate between the first one and the unlisted one) and --mask-reads-relative-frequency 0.5; the family
+    then follows under mask_reads 1, without amplicons, which the fixture holds."""
+    pm, ctx, meta = rsv_meta
+    sample = _NOTHING_TO_MASK[reads]
+    mask = (1, 0) if setting == "amplicons" else setting
+    if setting == "amplicons":
+        meta.set_amplicons(np.array([0, 2, 0][:len(sample)], np.int32), 2)
+        meta.set_relative_masks(reads=0.5)
+    else:
+        meta.set_masks(*mask)
+    try:
+        meta.set_reads(sample)
+    finally:
+        meta.set_masks(0, 0)
+        meta.set_relative_masks(0, 0)
+        meta.set_amplicons(None)
+    assert meta.n_reads == 0
+    assert meta.mask_info() == dict(reads_dropped=0, seeds_removed=0, reads_left=0)
+    ch, cc = meta.mask_counts()
+    assert len(ch) == 0 and len(cc) == 0
+    assert ctx.kernel_ms("meta_mask") < 0
+    got, want = _read_side(meta, mc.family().reads, *mask), masked[mask]
+    for name in ("lists", "info", "counts"):
+        assert all(np.array_equal(g, w) for g, w in zip(got[name], want[name])), name
+    assert np.array_equal(got["raw_to_merged"], want["raw_to_merged"]) and got["mask_info"] == want["mask_info"]
+    assert ctx.kernel_ms("meta_mask") >= 0
+
+
 def test_refusals(pmx, rsv_meta):
     pm, ctx, meta = rsv_meta
     with pytest.raises(pmx.PmxError, match="Only one masking parameter can be set at a time"):
