@@ -152,6 +152,15 @@ int pmx_readset_order_pairs(pmx_ctx *ctx, pmx_readset *rs);
    over an HPC index takes such a set (it also takes the plain set and compresses it itself); the align stage, pmx_readset_order_pairs
    and pmx_pileup_run refuse it (PMX_ERR_ARG): they work on the uncompressed reads. */
 int pmx_readset_hpc_compress(pmx_ctx *ctx, const pmx_readset *src, pmx_readset **out);
+/* a read set made of the reads src[idx[0]], ..., src[idx[n-1]] of another, in that order: the nodeSeqs / nodeQuals copies of
+   alignAssignedReads (src/main.cpp:691-699), as one gather on the device instead of a host copy per read.  idx is a HOST
+   array; indices may repeat and come in any order, n == 0 gives a set of zero reads; an index outside [0, reads of src), a
+   null argument or n < 0 is PMX_ERR_ARG with nothing launched.  *out == NULL makes a new read set, otherwise that object's
+   buffers are reused and grown only when needed.  The result owns its bases, its n+1 offsets (starting at 0) and, when src
+   has them, its qualities; it keeps src's HPC mark and is NOT packed: call pmx_readset_pack, as after
+   pmx_readset_hpc_compress.  src may be packed or not, and may be a wrapped slice.  Stream-ordered on the context's
+   stream, with one read-back (the size of the result). */
+int pmx_readset_select(pmx_ctx *ctx, const pmx_readset *src, const int64_t *idx /* host */, int64_t n, pmx_readset **out);
 int pmx_readset_is_hpc(const pmx_readset *rs);
 int pmx_readset_has_qualities(const pmx_readset *rs);
 /* download a read set's ASCII bases, offsets (n+1, starting at 0) and, if present and qual != NULL, qualities:

@@ -8,6 +8,7 @@ from .api import (METRICS, Aligner, align_reads_direct, write_bam, records_to_re
                   concat_reads, extract_read_sequences, format_placement_tsv, place_lite, read_fastq_paired,
                   read_fastx, reverse_complement, FastxReads, read_fastq_paired_native, read_fastx_native)
 from .meta import Meta, AssignResult, Amplicons, format_abundance, format_assigned, format_breadths, load_amplicons, load_taxonomy, read_dust  # noqa: F401
+from .meta import align_assigned, format_reference_fasta, sanitize_node_id  # noqa: F401
 from ._lib import MetaParams  # noqa: F401
 from .api import reload_options, describe_options  # noqa: F401
 from .api import Dist, score_reads_vs_reference, last_error, refine_top_candidates, refine_candidates, refine_placement, format_refined_tsv  # noqa: F401

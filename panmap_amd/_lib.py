@@ -131,6 +131,7 @@ SIGNATURES = {
     "pmx_readset_order_pairs": (_i32, [_vp, _vp]),
     "pmx_readset_pack_range": (_i32, [_vp, _vp, _i64, _i64]),
     "pmx_readset_hpc_compress": (_i32, [_vp, _vp, _PP]),
+    "pmx_readset_select": (_i32, [_vp, _vp, _vp, _i64, _PP]),
     "pmx_readset_is_hpc": (_i32, [_vp]),
     "pmx_readset_has_qualities": (_i32, [_vp]),
     "pmx_readset_export": (_i64, [_vp, _vp, _vp, _i64, _vp, _vp]),

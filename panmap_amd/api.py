@@ -452,6 +452,23 @@ class ReadSet:
             out.pack()
         return out
 
+    def select(self, indices, pack: bool = True, out: Optional["ReadSet"] = None) -> "ReadSet":
+        """the reads self[indices[0]], self[indices[1]], ... as a read set of their own, gathered on the device
+        (pmx_readset_select): bases, offsets and, when this set has them, qualities.  Indices may repeat and come in any order.
+        `out`: a read set returned by an earlier call, whose buffers are reused."""
+        idx = np.ascontiguousarray(indices, np.int64).reshape(-1)
+        if out is None:
+            out = ReadSet.__new__(ReadSet)
+            out.ctx = self.ctx
+            out._h = C.c_void_p()
+        check(lib.pmx_readset_select(self.ctx._h, self._h, idx.ctypes.data, len(idx), C.byref(out._h)), "pmx_readset_select")
+        out._keep = None   # (only now: after a failed call a wrapped `out` still points at the buffers its keepalive holds)
+        out.n_reads = len(idx)
+        out.total_bases = int(lib.pmx_readset_export(self.ctx._h, out._h, None, -1, None, None))
+        if pack:
+            out.pack()
+        return out
+
     @property
     def is_hpc(self) -> bool:
         return bool(lib.pmx_readset_is_hpc(self._h))

@@ -574,13 +574,6 @@ int pmx_readset_pack_range(pmx_ctx* ctx, pmx_readset* rs, int64_t r0, int64_t r1
 
 // ------------------------------------------------------------------------- homopolymer compression (hpc_kernels.hip)
 namespace {
-// a buffer pmx_readset_hpc_compress writes is the object's own, never one a caller wrapped
-template <class T>
-void own_ensure(DevBuf<T>& b, size_t count) {
-    if (!b.owned) b.release();
-    b.ensure(count);
-}
-
 // dst = the HPC form of the reads [r0, r1) of src: count (k_hpc_count), the byte and word offsets as two exclusive scans, write
 // (k_hpc_write), then the bookkeeping of the rewrap path from one 32-byte read-back.  No host pass over the reads.
 void hpc_compress_into(pmx_ctx* ctx, const pmx_readset* src, int64_t r0, int64_t r1, pmx_readset* dst) {

@@ -7,7 +7,8 @@
 //   genotype   device pileup of the alignments -> substitution calls -> `<prefix>.vcf` (runGenotyping, src/main.cpp:1828-1875)
 //   consensus  the placed genome with the calls applied -> `<prefix>.consensus.fa` (runConsensus, src/main.cpp:1877-1900)
 // `--stop index|place|align|genotype|consensus` ends after that stage (default: consensus).  --meta ->
-// `<prefix>.mgsr.abundance.out`.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
+// `<prefix>.mgsr.abundance.out`; --meta --filter-and-assign --align-reads [--min-num-align N] -> `<prefix>_mgsr_aligned/`: one
+// BAM (+ .bai) per node with at least N assigned reads, and their genomes in reference.fa.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
 // parts of panmap this build leaves out (--impute, ...), BUILDING a homopolymer-compressed index (one
 // given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta, --batch with
 // --gpus.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
@@ -16,6 +17,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <cctype>
 #include <cerrno>
 #include <climits>
 #include <cmath>
@@ -52,6 +54,11 @@ struct Config {
     double ambiguous_ratio = 0.0;
     std::vector<std::string> taxonomy_options;
     bool breadth_ratio = false;       // --breadth-ratio: <prefix>.mgsr.breadths.out (src/main.cpp:957-1015)
+    // --align-reads / --min-num-align N: a BAM per assigned node (alignAssignedReads, src/main.cpp:615-717); `align_options`: the
+    // ones given, in order
+    bool align_reads = false;
+    int min_num_align = 10;
+    std::vector<std::string> align_options;
     // --mask-reads N / --mask-seeds N: the low-coverage masks of --meta (src/main.cpp:2026-2030, src/mgsr.cpp:2049-2139);
     // `mask_options`: the ones given, in order
     int64_t mask_reads = 0, mask_seeds = 0;
@@ -98,6 +105,8 @@ void usage() {
           "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU)\n"
           "      --breadth-ratio        ... and write <prefix>.mgsr.breadths.out: per node the distinct seeds of its genome, how many of them\n"
           "                             the reads assigned to it hit, their depth, and the observed / expected breadth ratios (a switch)\n"
+          "      --align-reads          ... and align the reads of every node that has at least --min-num-align N (default 10) of them to that\n"
+          "                             node's genome -> <prefix>_mgsr_aligned/<node>.bam (+ .bai) and reference.fa (minimap2 presets)\n"
           "      --taxonomic-metadata TSV     ... and drop the reads whose best-scoring nodes span more than N taxa: node id in the first\n"
           "                             column, the taxa of --taxonomic-rank NAME (default Family) in the column of that name\n"
           "      --maximum-taxon-number N (default 1, at most 16)   --ambiguous-score-threshold N / --ambiguous-score-threshold-ratio F:\n"
@@ -182,6 +191,8 @@ Config parse(int argc, char** argv) {
                 die("option --breadth-ratio is not accepted with a value (" + next + "): it is a switch, as in the reference");
             c.breadth_ratio = true;
         }
+        else if (a == "--align-reads") { c.align_reads = true; c.align_options.push_back(a); }
+        else if (a == "--min-num-align") { c.min_num_align = atoi(v().c_str()); c.align_options.push_back(a); }
         else if (a == "--mask-reads") { c.mask_reads = atoll(v().c_str()); c.mask_options.push_back(a); }
         else if (a == "--mask-seeds") { c.mask_seeds = atoll(v().c_str()); c.mask_options.push_back(a); }
         else if (a == "--amplicon-depth") { c.amplicon_depth = v(); c.mask_options.push_back(a); }
@@ -899,6 +910,10 @@ struct MetaSample {
     std::string fq_path;
     std::vector<std::vector<int64_t>> copies;
     int64_t n_written = 0, n_unmapped = 0, n_discarded = 0, n_over = 0;
+    // ... write_fastq and write_node_lists for --align-reads: per FASTQ position its read of the input, per head the FASTQ
+    // positions of its reads (ascending)
+    std::vector<int64_t> fq_read;
+    std::vector<std::vector<int64_t>> by_node;
 
     explicit MetaSample(const Config& c_) : c(c_) {}
     const Reads& reads() const { return *reads_p; }
@@ -1082,6 +1097,7 @@ struct MetaSample {
             const std::string qual = len > 0 && rd.quals[at] == '\0' ? std::string(len, 'I') : rd.quals.substr(at, len);   // src/main.cpp:889-903
             fprintf(fq, "@%s\n%.*s\n+\n%s\n", rd.name(r).c_str(), (int)len, rd.concat.data() + at, qual.c_str());
             copies[(size_t)mr].push_back(n_written++);
+            if (c.align_reads) fq_read.push_back(r);
         }
         fclose(fq);
     }
@@ -1106,9 +1122,10 @@ struct MetaSample {
     }
 
     // Reads: off / nodes / lca / head, copies.  Read -> nodes inverted to head -> reads, for the assigned nodes and for the LCA
-    // node.  Leaves: the two node-list files.
-    void write_node_lists() const {
-        std::vector<std::vector<int64_t>> by_node((size_t)n_nodes), by_lca((size_t)n_nodes);
+    // node.  Leaves: the two node-list files and `by_node`, each head's list sorted.
+    void write_node_lists() {
+        std::vector<std::vector<int64_t>> by_lca((size_t)n_nodes);
+        by_node.assign((size_t)n_nodes, {});
         for (int64_t mr = 0; mr < n_merged; ++mr) {
             if (copies[(size_t)mr].empty()) continue;
             uint32_t prev = UINT32_MAX;
@@ -1145,6 +1162,202 @@ struct MetaSample {
         }
         fclose(f);
         say(c, "meta", path);
+    }
+
+    // ---- --align-reads (alignAssignedReads, src/main.cpp:615-717, called at :943-946), after write_node_lists: every head with at
+    // least --min-num-align reads (negative: 0) gets those reads -- single-end, a mate 2 as sequenced, ascending FASTQ position --
+    // aligned to its own ungapped genome: `<prefix>_mgsr_aligned/<sanitised id>.bam` (+ .bai), and the genomes in
+    // `<prefix>_mgsr_aligned/reference.fa` as `>id` + lines of at most 80 bases.  Heads by ascending DFS index (the reference
+    // iterates a hash map); the aligner is this library's, not bwa (DESIGN.md sections 4.3 and 7).  The assigned reads go to the
+    // device once; a node's reads are one pmx_readset_select of that set.
+    std::string al_dir;
+    std::vector<uint32_t> al_todo;               // the qualifying heads, ascending
+    int64_t al_skipped = 0;                      // heads with reads, but fewer than --min-num-align
+    std::vector<std::string> al_seq, al_qual, al_name;   // the records of the FASTQ (a name ends at its first white space, as kseq reads it)
+    pmx_readset* al_rs = nullptr;                // ... on the device, with their qualities
+    FILE* al_fa = nullptr;                       // reference.fa: a node's text is written once every node before it has been
+    std::vector<std::string> al_fa_text;
+    std::vector<char> al_fa_ready;
+    size_t al_fa_next = 0;
+    std::mutex al_fa_mu;
+    std::atomic<int64_t> al_done{0};
+
+    static std::string sanitize(const std::string& id) {
+        std::string out = id;
+        for (char& ch : out)
+            if (ch == '/' || ch == '\\' || isspace((unsigned char)ch)) ch = '_';
+        return out;
+    }
+
+    // Reads: by_node, fq_read, the reads.  Leaves: al_todo / al_skipped, the directory with an empty reference.fa open, the
+    // records of the FASTQ on the host and in al_rs.  Two qualifying heads with one file name end the run here.
+    void align_reads_setup() {
+        const size_t k = (size_t)std::max(c.min_num_align, 0);
+        for (uint32_t h = 0; h < (uint32_t)n_nodes; ++h) {
+            if (by_node[h].empty()) continue;
+            if (by_node[h].size() < k) ++al_skipped;
+            else al_todo.push_back(h);
+        }
+        std::vector<std::pair<std::string, uint32_t>> stems;
+        for (uint32_t h : al_todo) stems.emplace_back(sanitize(pmx_index_node_id(run.idx, h)), h);
+        std::sort(stems.begin(), stems.end());
+        for (size_t i = 1; i < stems.size(); ++i)
+            if (stems[i].first == stems[i - 1].first)
+                die("--align-reads: the nodes '" + std::string(pmx_index_node_id(run.idx, stems[i - 1].second)) + "' and '" +
+                    pmx_index_node_id(run.idx, stems[i].second) + "' would both be written to " + stems[i].first + ".bam");
+        al_dir = c.output + "_mgsr_aligned";
+        mkdirs(al_dir);
+        const std::string fa_path = al_dir + "/reference.fa";
+        al_fa = fopen(fa_path.c_str(), "w");
+        if (!al_fa) die("cannot write " + fa_path);
+        al_fa_text.resize(al_todo.size());
+        al_fa_ready.assign(al_todo.size(), 0);
+        if (al_todo.empty()) return;
+        const Reads& rd = reads();
+        std::string concat, quals;
+        std::vector<int64_t> offs(1, 0);
+        for (int64_t r : fq_read) {
+            const size_t at = (size_t)rd.off[(size_t)r], len = (size_t)(rd.off[(size_t)r + 1] - rd.off[(size_t)r]);
+            al_seq.emplace_back(rd.concat, at, len);
+            al_qual.push_back(len > 0 && rd.quals[at] == '\0' ? std::string(len, 'I') : rd.quals.substr(at, len));   // (as write_fastq wrote them)
+            std::string nm = rd.name(r);
+            for (size_t i = 0; i < nm.size(); ++i)
+                if (isspace((unsigned char)nm[i])) { nm.resize(i); break; }
+            al_name.push_back(nm);
+            concat += al_seq.back();
+            quals += al_qual.back();
+            offs.push_back((int64_t)concat.size());
+        }
+        check(pmx_readset_upload(run.ctx, concat.data(), offs.data(), (int64_t)fq_read.size(), &al_rs), "uploading the assigned reads");
+        check(pmx_readset_set_qualities(run.ctx, al_rs, quals.data()), "attaching the qualities of the assigned reads");
+    }
+
+    // node i's text of reference.fa is known: write it, and what waited for it, in node order
+    void publish_reference(size_t i, const std::string& id, const char* genome, int64_t len) {
+        std::string text = ">" + id + "\n";
+        for (int64_t at = 0; at < len; at += 80) { text.append(genome + at, (size_t)std::min<int64_t>(80, len - at)); text += '\n'; }
+        std::lock_guard<std::mutex> lock(al_fa_mu);
+        al_fa_text[i].swap(text);
+        al_fa_ready[i] = 1;
+        for (; al_fa_next < al_fa_text.size() && al_fa_ready[al_fa_next]; ++al_fa_next) {
+            fwrite(al_fa_text[al_fa_next].data(), 1, al_fa_text[al_fa_next].size(), al_fa);
+            std::string().swap(al_fa_text[al_fa_next]);
+        }
+    }
+
+    // one qualifying head on `wctx`: its genome into reference.fa, its reads selected into `sel_w` and aligned by `al_w` (both made
+    // on the first call, reused after), the records fetched, the BAM written.  -> a PMX code; pmx_last_error() says why
+    int align_node(pmx_ctx* wctx, pmx_aligner*& al_w, pmx_readset*& sel_w, size_t i) {
+        const uint32_t h = al_todo[i];
+        const std::vector<int64_t>& idx = by_node[h];
+        const int64_t n = (int64_t)idx.size();
+        const std::string id = pmx_index_node_id(run.idx, h);
+        thread_local std::string genome;   // (one reconstruction per node: score_candidate's way)
+        if (genome.size() < 1024) genome.resize(1024);
+        int64_t len = pmx_panman_node_genome(run.pm, (int64_t)h, &genome[0], (int64_t)genome.size());
+        if (len > (int64_t)genome.size()) {
+            genome.resize((size_t)len + (size_t)len / 64);
+            len = pmx_panman_node_genome(run.pm, (int64_t)h, &genome[0], (int64_t)genome.size());
+        }
+        publish_reference(i, id, genome.data(), std::max<int64_t>(len, 0));
+        if (len <= 0) {   // (the reference's aligner call fails on it: a warning, the node is not counted)
+            fprintf(stderr, "panmap: warning: Alignment/BAM write failed for node %s\n", id.c_str());
+            return PMX_OK;
+        }
+        int64_t bases = 0;
+        for (int64_t j : idx) bases += (int64_t)al_seq[(size_t)j].size();
+        const int mean_len = (int)(bases / std::max<int64_t>(n, 1));   // (of this node's reads: the reference's call sees only those)
+        int rc = pmx_readset_select(wctx, al_rs, idx.data(), n, &sel_w);
+        if (rc == PMX_OK) rc = pmx_readset_pack(wctx, sel_w);
+        if (rc == PMX_OK) rc = al_w ? pmx_aligner_set_reference(wctx, al_w, genome.data(), len, mean_len) : pmx_aligner_create(wctx, genome.data(), len, mean_len, &al_w);
+        if (rc == PMX_OK) rc = pmx_align_readset(wctx, al_w, sel_w, 0, 0);
+        if (rc != PMX_OK) return rc;
+        const int64_t words = pmx_align_cigar_words(wctx, al_w);
+        if (words < 0) return (int)words;
+        std::vector<pmx_aln_record> recs((size_t)std::max<int64_t>(n, 1));
+        std::vector<uint32_t> arena((size_t)std::max<int64_t>(words, 1));
+        rc = pmx_align_fetch(wctx, al_w, recs.data(), n, arena.data(), (int64_t)arena.size());
+        if (rc != PMX_OK) return rc;
+        std::vector<const char*> seq_p((size_t)n), qual_p((size_t)n), name_p((size_t)n);
+        std::vector<int> lens((size_t)n);
+        std::vector<align_pair_result_t> results((size_t)std::max<int64_t>(n, 1));
+        for (int64_t q = 0; q < n; ++q) {
+            const size_t j = (size_t)idx[(size_t)q];
+            seq_p[(size_t)q] = al_seq[j].c_str(); qual_p[(size_t)q] = al_qual[j].c_str(); name_p[(size_t)q] = al_name[j].c_str(); lens[(size_t)q] = (int)al_seq[j].size();
+            align_pair_result_t& out = results[(size_t)q];
+            memset(&out, 0, sizeof(out));
+            out.r1.pos = out.r2.pos = INT_MAX;
+            const pmx_aln_record& r = recs[(size_t)q];
+            if ((r.flags & 3) != 0 || !r.mapped) continue;   // (an invalid record is withheld: Sample::write_bam)
+            out.mapped = 1;
+            if (r.flags & PMX_ALN_HAS_ALN) {
+                read_align_t& o = out.r1;
+                o.pos = r.rs + 1; o.rs = r.rs; o.re = r.re; o.qs = r.qs; o.qe = r.qe;
+                o.mapq = r.mapq; o.rev = r.rev; o.proper_frag = r.proper_frag; o.n_cigar = r.n_cigar;
+                o.cigar = arena.data() + r.cigar_off;   // (points into the arena: nothing to free)
+            }
+        }
+        rc = pmx_write_bam((al_dir + "/" + sanitize(id) + ".bam").c_str(), id.c_str(), len, (int)n, seq_p.data(), qual_p.data(), name_p.data(), lens.data(), results.data(), false);
+        if (rc == PMX_OK) ++al_done;
+        return rc;
+    }
+
+    // Work layout of Sample::refine(): the first node on the run's context, then a few workers, each with a context, an aligner
+    // and a selected read set of its own, take the nodes from a counter; the first failure stops them all.
+    // Leaves: the BAMs, reference.fa closed, the reference's closing line.
+    void align_reads() {
+        align_reads_setup();
+        const int64_t n_todo = (int64_t)al_todo.size();
+        pmx_aligner* al0 = nullptr;
+        pmx_readset* sel0 = nullptr;
+        std::atomic<int> failed{0};
+        std::string fail_msg;
+        if (n_todo > 0) {
+            if (align_node(run.ctx, al0, sel0, 0) != PMX_OK) { failed = 1; fail_msg = pmx_last_error(); }
+            int n_workers = 4;
+            if (const char* e = getenv("PMX_ALIGN_READS_STREAMS")) n_workers = std::max(1, atoi(e));
+            n_workers = (int)std::min<int64_t>(n_workers, std::max<int64_t>(n_todo - 1, 1));
+            std::atomic<int64_t> next{1};
+            std::mutex fail_mu;
+            std::vector<std::thread> pool;
+            for (int wk = 0; wk < n_workers && !failed.load() && n_todo > 1; ++wk)
+                pool.emplace_back([&, wk]() {    // worker 0 goes on with the run's context, al0 and sel0; the others release what they made, on every path
+                    pmx_ctx* wctx = run.ctx;
+                    pmx_aligner* own_al = nullptr;
+                    pmx_readset* own_sel = nullptr;
+                    if (wk > 0 && pmx_ctx_create(run.dev, &wctx) != PMX_OK) {
+                        std::lock_guard<std::mutex> lock(fail_mu);
+                        if (!failed.exchange(1)) fail_msg = pmx_last_error();
+                        return;
+                    }
+                    pmx_aligner*& al_w = wk == 0 ? al0 : own_al;
+                    pmx_readset*& sel_w = wk == 0 ? sel0 : own_sel;
+                    for (;;) {
+                        const int64_t i = next.fetch_add(1);
+                        if (i >= n_todo || failed.load()) break;
+                        if (align_node(wctx, al_w, sel_w, (size_t)i) != PMX_OK) {
+                            std::lock_guard<std::mutex> lock(fail_mu);
+                            if (!failed.exchange(1)) fail_msg = pmx_last_error();
+                            break;
+                        }
+                    }
+                    if (wk > 0) {
+                        if (own_al) pmx_aligner_free(wctx, own_al);
+                        if (own_sel) pmx_readset_free(wctx, own_sel);
+                        pmx_ctx_destroy(wctx);
+                    }
+                });
+            for (auto& t : pool) t.join();
+        }
+        if (al0) pmx_aligner_free(run.ctx, al0);
+        if (sel0) pmx_readset_free(run.ctx, sel0);
+        if (al_rs) pmx_readset_free(run.ctx, al_rs);
+        al_rs = nullptr;
+        fclose(al_fa);
+        al_fa = nullptr;
+        if (failed.load()) die("aligning the assigned reads: " + fail_msg);
+        say(c, "meta", "Aligned reads for " + std::to_string(al_done.load()) + " nodes (" + std::to_string(al_skipped) + " below minNumAlign=" +
+                           std::to_string(std::max(c.min_num_align, 0)) + ")");
     }
 
     // the line that ends the mode: the FASTQ's name and the four tallies of write_fastq
@@ -1205,6 +1418,7 @@ int run_meta(const Config& c) {
         s.assign();
         s.write_fastq();
         s.write_node_lists();
+        if (s.c.align_reads) s.align_reads();
         if (s.c.breadth_ratio) s.write_breadths();
         s.report_assigned();
     } else {
@@ -1230,6 +1444,8 @@ int real_main(int argc, char** argv) {
     if (c.gpus < 1) die("--gpus expects a positive number");
 
     if (c.breadth_ratio && !c.filter_and_assign) die("option --breadth-ratio is not accepted without --filter-and-assign");
+    if (!c.align_options.empty() && !c.filter_and_assign) die("option " + c.align_options[0] + " is not accepted without --filter-and-assign");
+    if (!c.align_options.empty() && !c.align_reads) die("option --min-num-align is not accepted without --align-reads");
     if (c.filter_and_assign && !c.meta) die("--filter-and-assign needs --meta");
     if (!c.mask_options.empty() && !c.meta) die("option " + c.mask_options[0] + " is not accepted without --meta");
     if (c.meta) {   // the reference's --meta has no HPC

@@ -55,6 +55,7 @@ struct pmx_readset {
     int64_t off0 = 0;              // first offset (non-zero for a wrapped slice of a larger offsets array)
     bool hpc = false;              // the reads are homopolymer-compressed (pmx_readset_hpc_compress): for an HPC index only
     pmx::DevBuf<int64_t> len_tmp;  // hpc_compress: bases per compressed read (scan input)
+    pmx::DevBuf<int64_t> sel_idx;  // select: the picked read indices of the source (pmx_readset_select)
     // locality order of the reads (read_locality_key, device/pmx_math.h): computed once per packing, on first request, and
     // shared by the seeding launch order (place stage) and the pair order of the align stage
     mutable pmx::DevBuf<uint32_t> loc_key, loc_key2, loc_idx, loc_perm;
@@ -84,6 +85,13 @@ struct pmx_readset {
 
 struct pmx_ctx;
 namespace pmx {
+// a buffer pmx_readset_hpc_compress / pmx_readset_select writes is the object's own, never one a caller wrapped
+template <class T>
+inline void own_ensure(DevBuf<T>& b, size_t count) {
+    if (!b.owned) b.release();
+    b.ensure(count);
+}
+
 // reads sorted by locality key (stable), as a permutation of 0..n-1 on the device; enqueued on the context's stream the
 // first time it is asked for after a (re)packing.  nullptr for read sets too small or too large for it.
 const uint32_t* readset_locality_order(pmx_ctx* ctx, const pmx_readset* rs);

@@ -387,6 +387,67 @@ def format_assigned(result: AssignResult, node_id, heads=None, taxon_names=None)
     return text(result.by_node()), text(result.by_lca())
 
 
+def sanitize_node_id(node_id: str) -> str:
+    """the file stem of a node's BAM (alignAssignedReads' sanitize, src/main.cpp:615-717): `/`, `\\` and every character that
+    isspace() knows in the "C" locale become `_`"""
+    return "".join("_" if ch in "/\\ \t\n\v\f\r" else ch for ch in node_id)
+
+
+def format_reference_fasta(pairs) -> str:
+    """`<prefix>_mgsr_aligned/reference.fa` from (id, genome) pairs in node order: `>id`, then the genome in lines of at most 80
+    bases (an empty genome: the header alone)"""
+    out = []
+    for node_id, genome in pairs:
+        g = genome.decode() if isinstance(genome, (bytes, bytearray)) else genome
+        out.append(">%s\n" % node_id)
+        out.extend(g[i:i + 80] + "\n" for i in range(0, len(g), 80))
+    return "".join(out)
+
+
+def align_assigned(ctx: Context, pm: Panman, index: Index, result: AssignResult, reads, quals=None, min_num_align: int = 10):
+    """--align-reads (alignAssignedReads, src/main.cpp:615-717): a generator over the head nodes of result.by_node() that have at
+    least `min_num_align` reads (negative: 0), by ascending DFS index; it yields (head, fastq_indices, genome, records, cigars)
+    with the node's reads -- ascending FASTQ index, every read single-end, a mate 2 as sequenced -- aligned to the node's own
+    ungapped genome.  `reads` (and `quals`) are the raw reads given to Meta.set_reads; the assigned ones are uploaded once,
+    each node's reads are one ReadSet.select of that set, and one Aligner is re-targeted node by node.  mean_read_len is the
+    mean over the node's reads: the reference's aligner call sees only those.  `index`: the tree's index (its nodes are the
+    PanMAN's, in DFS order)."""
+    from .api import Aligner, ReadSet
+    if index.info.n_nodes != pm.num_nodes or len(result.heads) != pm.num_nodes:
+        raise ValueError("align_assigned: the index, the result and the PanMAN are not of one tree")
+    by_node = result.by_node()
+    k = max(int(min_num_align), 0)
+    todo = [h for h in sorted(by_node) if len(by_node[h]) >= k]
+    if not todo:
+        return
+    order = np.nonzero(result.fastq_index >= 0)[0]           # input order == ascending FASTQ index
+    assigned = [bytes(reads[i]) for i in order.tolist()]
+    lens = np.fromiter((len(r) for r in assigned), np.int64, len(assigned))
+    rs = ReadSet(ctx, assigned, pack=False)
+    if quals is not None:
+        rs.set_qualities([bytes(quals[i]) for i in order.tolist()])
+    aligner, sel = None, None
+    try:
+        for h in todo:
+            idx = np.asarray(sorted(by_node[h]), np.int64)
+            genome = pm.genome(h)
+            mean_len = int(lens[idx].sum() // max(len(idx), 1))
+            sel = rs.select(idx, out=sel)
+            if aligner is None:
+                aligner = Aligner(ctx, genome, mean_len)
+            else:
+                aligner.set_reference(genome, mean_len)
+            aligner.align_readset(sel, paired=False)
+            recs, cig = aligner.fetch()
+            yield h, idx.tolist(), genome, recs.copy(), cig.copy()
+    finally:
+        if aligner is not None:
+            aligner.close()
+        if sel is not None:
+            sel.close()
+        rs.close()
+
+
 BREADTHS_HEADER = ("NodeId\tTotalRefSeeds\tObservedBreadthCount\tObservedBreadthRatio\tTotalDepth\tMeanDepth\tExpectedBreadthRatio\t"
                    "ObservedToExpectedBreadthRatio")
 
