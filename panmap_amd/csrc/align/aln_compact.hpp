@@ -220,6 +220,11 @@ struct CSeedOutT {
     }
 };
 #define PMX_C_NSEED_BAIL 0xffffu   // the hand-over count (seeds | seeds of mate 1 << 8) of a pair the seeding already gave up on
+// bit 15 of the hand-over count (the counts need six bits each; with it the low byte is still a count, never 0xff): the
+// mates do not overlap on the reference -- the pair is on the simple list (aln_compact_simple.hpp)
+#define PMX_C_NSEED_SIMPLE 0x8000u
+#define PMX_C_NSEED_N(c) ((int)((c) & 0xffu))
+#define PMX_C_NSEED_N0(c) ((int)((c) >> 8 & 0x7fu))
 
 PMX_HD uint64_t c_bitrev64(uint64_t x) {
 #if defined(__clang__)
@@ -346,8 +351,8 @@ struct CList {
 };
 
 // mm_cal_fuzzy_len + mm_reg_set_coor (hit.c:8-40) on a per-mate anchor list
-template <class MT>
-PMX_HD void c_reg_set_coor(const CList<MT>& a, CReg& r, int32_t qlen, int span) {
+template <class LT>
+PMX_HD void c_reg_set_coor(const LT& a, CReg& r, int32_t qlen, int span) {
     const int32_t x0 = a.x(0), y0 = a.y(0);
     const int32_t xl = a.x(r.cnt - 1), yl = a.y(r.cnt - 1);
     r.rs = x0 + 1 > span ? x0 + 1 - span : 0;
@@ -366,8 +371,8 @@ PMX_HD void c_reg_set_coor(const CList<MT>& a, CReg& r, int32_t qlen, int span) 
 }
 
 // mm_fix_bad_ends (align.c:464-502) on a per-mate list (r.as == 0, no LONG_JOIN marks)
-template <class MT>
-PMX_HD void c_fix_bad_ends(const CList<MT>& a, const CReg& r, int span, int bw, int min_match, int32_t* as, int32_t* cnt) {
+template <class LT>
+PMX_HD void c_fix_bad_ends(const LT& a, const CReg& r, int span, int bw, int min_match, int32_t* as, int32_t* cnt) {
     *as = 0;
     *cnt = r.cnt;
     if (r.cnt < 3) return;
@@ -413,8 +418,9 @@ struct CRefFn {
 // MULTI (aln_compact_multi.hpp): the region is one of several of its mate; `al` is still the region's own list, `mate`
 // the mate's whole anchor list (n_a entries, the region's at [as, as + cnt)): neighbouring chains of the same strand
 // fence the end extensions off (align.c:636-691; extension_reach, aln_align.hpp).
-template <bool MULTI = false, class MT>
-PMX_HD int c_align1(const CList<MT>& al, const Opt& o, const RefIndex& ri, const CRead& rd, int qlen, CReg& r, const CList<MT>* mate = nullptr, int as = 0,
+// LT: CList, or any list with x(i) / y(i) (and rev(i) for MULTI) -- CEnds of aln_compact_simple.hpp
+template <bool MULTI = false, class LT>
+PMX_HD int c_align1(const LT& al, const Opt& o, const RefIndex& ri, const CRead& rd, int qlen, CReg& r, const LT* mate = nullptr, int as = 0,
                     int n_a = 0) {
     const int span = o.k;
     const int32_t rev = r.rev;
@@ -658,6 +664,10 @@ struct CSeeder {
     int pending;           // seed of the previous read's last minimizer (its right neighbour is not known yet)
     uint64_t cw;
     int ck;
+    // where the read lies on the reference, projected from its first seed along that seed's diagonal: [ext_lo, ext_lo +
+    // len); INT32_MIN while the read has no seed.  (compact_seed_pair classes the pair by the two mates' extents.)
+    int kk;
+    int32_t ext_lo;
     // the read's packed words, fetched together when the read starts (its record is one line: word by word, 32 bases apart in
     // time, the line was gone from the L2 in between -- the records of the pairs a CU works on fill its share of the L2 --
     // and came from HBM again: 3.8 line fetches per pair instead of one)
@@ -708,6 +718,10 @@ struct CSeeder {
                         if (n_s >= MS::kCap || (pv[b] >> (8 * sizeof(PT) - 1) >> 1) != 0u) bail = true;
                         else {
                             m.setSeed(n_s, pv[b], (yl[b] + ((uint32_t)sum << 1)) | (seg ? PMX_CQ_SEG : 0u) | (tandem ? PMX_CQ_TANDEM : 0u));
+                            if (ext_lo == INT32_MIN) {   // read base j lies at rpos - q + j, or, on the other strand, at rpos + q - (k - 1) - j
+                                const int32_t rpos = (int32_t)(pv[b] >> 1), q = (int32_t)(yl[b] >> 1);
+                                ext_lo = ((pv[b] ^ yl[b]) & 1u) ? rpos + q - (kk - 1) - (r.len - 1) : rpos - q;
+                            }
                             pending = has_next ? -1 : n_s;   // (only the read's last minimizer has no right neighbour yet)
                             ++n_s;
                         }
@@ -820,16 +834,19 @@ PMX_HD bool sketch_distinct(int len, int k, BaseFn& base_at, PushFn& push) {
 // The pair, in two parts.  rd / amb = the two mates as packed by the host.
 // (1) compact_seed_pair: envelope checks, minimizers -> index probes -> seeds, into whatever `ms` is (CMemT: the pair's
 //     LDS block; CSeedOutT: the HBM hand-over).  PMX_C_DONE with the seed count in *n_seeds, or PMX_C_BAIL.
+//     *simple (when asked for): both mates have a seed, the first form's memory holds the seeds, and the mates, each
+//     projected from its first seed, do not overlap on the reference -- aln_compact_simple.hpp chains such a pair.
 // (2) compact_chain_pair: from the seeds in X / Y of the pair's LDS block to the records; `out` is only meaningful when
 //     PMX_C_DONE is returned.
 // compact_map_pair runs both on one memory block (the fused form: hostsim, PMX_ALIGN_COMPACT_FUSED).
 // prof (read only when prof_on): 8 per-lane cycle accumulators (sketch, probes, merge, chain fill, backtrack, regions, align + mapq, pairing)
 template <class MS>
 PMX_HD int compact_seed_pair(const MS& ms, const Opt& o, const RefIndex& ri, const CRead* rd, const uint32_t* const* amb, int* n_seeds, int* n_first,
-                              unsigned long long* prof = nullptr, bool prof_on = false) {
+                              unsigned long long* prof = nullptr, bool prof_on = false, bool* simple = nullptr) {
     typedef typename MS::PosT PT;
     *n_seeds = 0;
     *n_first = 0;
+    if (simple) *simple = false;
 #if defined(__HIP_DEVICE_COMPILE__)
     unsigned long long prof_t = prof_on ? (unsigned long long)clock64() : 0ULL;
 #endif
@@ -846,24 +863,29 @@ PMX_HD int compact_seed_pair(const MS& ms, const Opt& o, const RefIndex& ri, con
     // ---------------------------------------------------------------- minimizers -> index probes -> seeds (X, Y)
     CSeeder<MS> sd{ms, ri};
     sd.n_s = 0; sd.bail = false; sd.have_prev = false; sd.prev_key = 0; sd.pending = -1;
+    sd.kk = k;
+    int32_t ext0 = INT32_MIN;
     {
         const CRead r0 = rd[0], r1 = rd[1];
         for (int s = 0; s < 2; ++s) {
             sd.r.w = s ? r1.w : r0.w; sd.r.len = s ? r1.len : r0.len; sd.r.flip = s ? r1.flip : r0.flip;
             sd.seg = s; sd.sum = s ? qlen0 : 0;
             sd.n_q = 0; sd.first_of_read = true; sd.ovf = false; sd.cw = 0; sd.ck = -1;
+            sd.ext_lo = INT32_MIN;
             sd.load_words();
             if (!sketch_distinct<PMX_C_W>(sd.r.len, k, sd, sd)) sd.bail = true;
             PMX_C_STAMP(0);
             if (sd.ovf) sd.bail = true;
             sd.drain(true);
-            if (s == 0) *n_first = sd.n_s;
+            if (s == 0) { *n_first = sd.n_s; ext0 = sd.ext_lo; }
             PMX_C_STAMP(1);
         }
     }
     if (sd.bail) return PMX_C_BAIL;
     ms.flush_tail(sd.n_s);
     *n_seeds = sd.n_s;
+    if (simple)
+        *simple = ext0 != INT32_MIN && sd.ext_lo != INT32_MIN && sd.n_s <= PMX_C_CAP1 && (sd.ext_lo >= ext0 + qlen0 || ext0 >= sd.ext_lo + qlen1);
     return PMX_C_DONE;
 }
 
@@ -872,6 +894,49 @@ PMX_HD int compact_seed_pair(const MS& ms, const Opt& o, const RefIndex& ri, con
 #include "aln_compact_multi.hpp"
 namespace pmx {
 namespace aln {
+
+// Pairing (pe.c:76-177) with one aligned, kept region per mate, and the pair's record; out.mapped stays 0 for a pair the
+// record rules leave unmapped.
+PMX_HD void c_pair_record(const Opt& o, CReg& R0, CReg& R1, int max_chain_gap_ref, CResult& out) {
+    // Two entries sorted by key = rs << 1 | (segment ^ rev) (ties keep mate 0 first).  The scan pairs the SECOND entry with
+    // the first iff the first is a "left" end (key bit 0 clear), the second a "right" end on the same strand, the gap
+    // between them at most max_gap_ref and their DP scores reach the threshold; with one candidate the pair's mapq is the
+    // larger of the two, floored at 2.
+    if (o.pe_ori >= 0) {
+        const uint64_t key0 = (uint64_t)(uint32_t)(R0.rs << 1) | (uint32_t)(0 ^ R0.rev), key1 = (uint64_t)(uint32_t)(R1.rs << 1) | (uint32_t)(1 ^ R1.rev);
+        int dp_thres = R0.dp_max + R1.dp_max - o.pe_bonus;
+        if (dp_thres < 0) dp_thres = 0;
+        const bool swap = key1 < key0;
+        const CReg& A_ = swap ? R1 : R0;
+        const CReg& B_ = swap ? R0 : R1;
+        const uint64_t ka = swap ? key1 : key0, kb = swap ? key0 : key1;
+        const bool proper = !(ka & 1ULL) && (kb & 1ULL) && A_.rev == B_.rev && !(B_.rs - A_.re > max_chain_gap_ref) &&
+                            !(B_.dp_max + A_.dp_max < dp_thres) && ((int64_t)(B_.dp_max + A_.dp_max) << 32) > 0;
+        if (proper) {
+            R0.proper_frag = R1.proper_frag = 1;
+            const int mapq_pe = R0.mapq > R1.mapq ? R0.mapq : R1.mapq;
+            if (R0.mapq < mapq_pe) R0.mapq = (int)(.2f * R0.mapq + .8f * mapq_pe + .499f);
+            if (R1.mapq < mapq_pe) R1.mapq = (int)(.2f * R1.mapq + .8f * mapq_pe + .499f);
+            if (R0.mapq < 2) R0.mapq = 2;
+            if (R1.mapq < 2) R1.mapq = 2;
+        }
+    }
+
+    // the record (src/mm_align.c:271-354)
+    if (R0.has_p && R0.blen > 0) out.edit[0] = R0.blen - R0.mlen;   // (no ambiguous base on either side in this tier)
+    if (R1.has_p && R1.blen > 0) out.edit[1] = R1.blen - R1.mlen;
+    if (!(R0.score > 0 && R1.score > 0)) return;
+    out.mapped = 1;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const CReg& r = s == 0 ? R0 : R1;
+        CMate& t = out.m[s];
+        t.rs = r.rs; t.re = r.re; t.qs = r.qs; t.qe = r.qe;
+        t.dp_max = r.dp_max;
+        t.cigar = (uint32_t)r.m_len << 4;
+        t.mapq = (uint8_t)r.mapq; t.rev = (uint8_t)r.rev; t.proper_frag = (uint8_t)r.proper_frag; t.has_aln = 1;
+    }
+}
 
 // MULTI: follow up to PMX_CM_MAXC fragment chains and several regions per mate (compact_regions_multi) instead of bailing
 template <bool MULTI = false, class PT, int CAP>
@@ -1345,46 +1410,9 @@ PMX_HD int compact_chain_pair(const CMemT<PT, CAP>& m, const Opt& o, const RefIn
     }
 
     PMX_C_STAMP(6);
-    // ---------------------------------------------------------------- pairing (pe.c:76-177) with one region per mate
-    // Two entries sorted by key = rs << 1 | (segment ^ rev) (ties keep mate 0 first).  The scan pairs the SECOND entry with
-    // the first iff the first is a "left" end (key bit 0 clear), the second a "right" end on the same strand, the gap
-    // between them at most max_gap_ref and their DP scores reach the threshold; with one candidate the pair's mapq is the
-    // larger of the two, floored at 2.
-    if (o.pe_ori >= 0) {
-        const uint64_t key0 = (uint64_t)(uint32_t)(R0.rs << 1) | (uint32_t)(0 ^ R0.rev), key1 = (uint64_t)(uint32_t)(R1.rs << 1) | (uint32_t)(1 ^ R1.rev);
-        int dp_thres = R0.dp_max + R1.dp_max - o.pe_bonus;
-        if (dp_thres < 0) dp_thres = 0;
-        const bool swap = key1 < key0;
-        const CReg& A_ = swap ? R1 : R0;
-        const CReg& B_ = swap ? R0 : R1;
-        const uint64_t ka = swap ? key1 : key0, kb = swap ? key0 : key1;
-        const bool proper = !(ka & 1ULL) && (kb & 1ULL) && A_.rev == B_.rev && !(B_.rs - A_.re > max_chain_gap_ref) &&
-                            !(B_.dp_max + A_.dp_max < dp_thres) && ((int64_t)(B_.dp_max + A_.dp_max) << 32) > 0;
-        if (proper) {
-            R0.proper_frag = R1.proper_frag = 1;
-            const int mapq_pe = R0.mapq > R1.mapq ? R0.mapq : R1.mapq;
-            if (R0.mapq < mapq_pe) R0.mapq = (int)(.2f * R0.mapq + .8f * mapq_pe + .499f);
-            if (R1.mapq < mapq_pe) R1.mapq = (int)(.2f * R1.mapq + .8f * mapq_pe + .499f);
-            if (R0.mapq < 2) R0.mapq = 2;
-            if (R1.mapq < 2) R1.mapq = 2;
-        }
-    }
-
+    // ---------------------------------------------------------------- pairing (pe.c:76-177), the record (src/mm_align.c:271-354)
+    c_pair_record(o, R0, R1, max_chain_gap_ref, out);
     PMX_C_STAMP(7);
-    // ---------------------------------------------------------------- the record (src/mm_align.c:271-354)
-    if (R0.has_p && R0.blen > 0) out.edit[0] = R0.blen - R0.mlen;   // (no ambiguous base on either side in this tier)
-    if (R1.has_p && R1.blen > 0) out.edit[1] = R1.blen - R1.mlen;
-    if (!(R0.score > 0 && R1.score > 0)) return PMX_C_DONE;
-    out.mapped = 1;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const CReg& r = s == 0 ? R0 : R1;
-        CMate& t = out.m[s];
-        t.rs = r.rs; t.re = r.re; t.qs = r.qs; t.qe = r.qe;
-        t.dp_max = r.dp_max;
-        t.cigar = (uint32_t)r.m_len << 4;
-        t.mapq = (uint8_t)r.mapq; t.rev = (uint8_t)r.rev; t.proper_frag = (uint8_t)r.proper_frag; t.has_aln = 1;
-    }
     return PMX_C_DONE;
 }
 

@@ -20,6 +20,7 @@
 #define PMX_C_PEN_SAME 128
 #define PMX_C_PEN_DIFF 1024
 #define PMX_C_PEN_BYTES (PMX_C_PEN_SAME + PMX_C_PEN_DIFF)
+#define PMX_C_SIMPLE_LDS_PAD 16   // k_align_simple*: unused bytes in front of its tables (its only LDS)
 // second form of the tier (several regions per mate, aln_compact_multi.hpp): its workspace in HBM
 #define PMX_CM_MAXC 4            // fragment chains of a pair (and therefore regions per mate) this form follows
 #define PMX_CM_SREGS (4 * PMX_CM_MAXC)   // region records per pair: fragment chains, mate 0, mate 1, the sorter's copy (24 words each)

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "align/aln_compact.hpp"
+#include "align/aln_compact_simple.hpp"
 #include "align/aln_host.hpp"
 #include "align_kernel.h"
 #include "device/dev_util.hpp"
@@ -48,6 +49,7 @@ __device__ __forceinline__ int64_t compact_item(const AlignArgs& A, int64_t it, 
 // minimizer queue (112 bytes per pair, 7 KB per wave), so the CU holds as many waves as the registers allow (the fused
 // kernel: seven, by its 21 KB of work state per wave) -- this part is pure integer arithmetic plus a few probes.
 // Seeds go to the pair's hand-over words (CSeedOutT), the count (or PMX_C_NSEED_BAIL) to cseed_n[position].
+// With simple_list, the count also carries the pair's class (PMX_C_NSEED_SIMPLE: the mates do not overlap on the reference).
 template <class PT>
 __device__ __forceinline__ void compact_seeds_body(const AlignArgs& A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t c_lds[];
@@ -60,16 +62,65 @@ __device__ __forceinline__ void compact_seeds_body(const AlignArgs& A) {
         const int64_t it = it0 + lane;
         so.out = (c_g32*)(A.cseeds + (size_t)it * CSeedOutT<PT>::kPairWords);
         int n_s = 0, n_s0 = 0, rc = PMX_C_DONE;
+        bool simple = false;
         if (it < A.n_items) {
             CRead rd[2];
             const uint32_t* amb[2];
             compact_item(A, it, rd, amb);
             unsigned long long pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            rc = compact_seed_pair(so, A.opt, A.ri, rd, amb, &n_s, &n_s0, pacc, A.prof != nullptr);
+            rc = compact_seed_pair(so, A.opt, A.ri, rd, amb, &n_s, &n_s0, pacc, A.prof != nullptr, &simple);
             if (A.prof && lane == 0)
                 for (int k = 0; k < 2; ++k) atomicAdd(&A.prof[k], pacc[k]);
-            A.cseed_n[it] = (uint16_t)(rc == PMX_C_DONE ? (n_s | n_s0 << 8) : (int)PMX_C_NSEED_BAIL);
+            simple = simple && rc == PMX_C_DONE && A.simple_list != nullptr;
+            A.cseed_n[it] = (uint16_t)(rc == PMX_C_DONE ? (n_s | n_s0 << 8 | (simple ? (int)PMX_C_NSEED_SIMPLE : 0)) : (int)PMX_C_NSEED_BAIL);
         }
+    }
+}
+// The two class lists from the counts' class bits: every launch position goes to one of them, the simple pairs to the
+// first, everything else -- the pairs the seeding gave up on too: the chain kernel hands them to the bail list -- to the
+// second.  A kernel of its own, 6 bytes per pair: inside k_compact_seeds the append cost that kernel its fourth wave per
+// SIMD (132 VGPRs).  A workgroup takes PMX_C_CLASS_BLOCK consecutive positions and claims its stretch of each list with
+// ONE atomic: with one per wave of 64 positions, as multi_list is filled, the 78,000 waves of a 5M-pair launch queue on
+// two addresses and the kernel takes 1.24 ms instead of 0.1.  Inside the stretch: wave by wave, pass by pass, lane by lane.
+#define PMX_C_CLASS_PASSES 8
+#define PMX_C_CLASS_BLOCK (256 * PMX_C_CLASS_PASSES)
+__global__ void __launch_bounds__(256) k_compact_classes(AlignArgs A) {
+    __shared__ unsigned int w_s[4], w_r[4];
+    __shared__ unsigned long long b_s, b_r;
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    const int64_t base = (int64_t)blockIdx.x * PMX_C_CLASS_BLOCK + wave * (64 * PMX_C_CLASS_PASSES);
+    const int64_t rest_at = (A.n_items + 63) & ~(int64_t)63;
+    unsigned long long smask[PMX_C_CLASS_PASSES], rmask[PMX_C_CLASS_PASSES];
+    unsigned int n_s = 0, n_r = 0;
+#pragma unroll
+    for (int p = 0; p < PMX_C_CLASS_PASSES; ++p) {
+        const int64_t it = base + p * 64 + lane;
+        const bool in = it < A.n_items;
+        const unsigned int c = in ? (unsigned int)A.cseed_n[it] : PMX_C_NSEED_BAIL;
+        const bool simple = c != PMX_C_NSEED_BAIL && (c & PMX_C_NSEED_SIMPLE) != 0u;
+        smask[p] = __ballot(simple);
+        rmask[p] = __ballot(in && !simple);
+        n_s += (unsigned int)__popcll(smask[p]);
+        n_r += (unsigned int)__popcll(rmask[p]);
+    }
+    if (lane == 0) { w_s[wave] = n_s; w_r[wave] = n_r; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int t_s = w_s[0] + w_s[1] + w_s[2] + w_s[3], t_r = w_r[0] + w_r[1] + w_r[2] + w_r[3];
+        b_s = t_s ? atomicAdd(A.multi_count + 2, (unsigned long long)t_s) : 0ULL;
+        b_r = t_r ? atomicAdd(A.multi_count + 3, (unsigned long long)t_r) : 0ULL;
+    }
+    __syncthreads();
+    unsigned long long at_s = b_s, at_r = b_r;
+    for (int w = 0; w < wave; ++w) { at_s += w_s[w]; at_r += w_r[w]; }
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+#pragma unroll
+    for (int p = 0; p < PMX_C_CLASS_PASSES; ++p) {
+        const int64_t it = base + p * 64 + lane;
+        if (smask[p] >> lane & 1ULL) A.simple_list[at_s + __popcll(smask[p] & below)] = (uint32_t)it;
+        else if (rmask[p] >> lane & 1ULL) A.simple_list[rest_at + at_r + __popcll(rmask[p] & below)] = (uint32_t)it;
+        at_s += (unsigned long long)__popcll(smask[p]);
+        at_r += (unsigned long long)__popcll(rmask[p]);
     }
 }
 __global__ void __launch_bounds__(64) k_compact_seeds16(AlignArgs A) { compact_seeds_body<uint16_t>(A); }
@@ -143,9 +194,13 @@ __device__ __forceinline__ void align_compact_body(const AlignArgs& A) {
                   "LDS size the host launches with");
     m.base = (c_u32*)c_lds + lane;
     const int64_t n_threads = (int64_t)gridDim.x * 64;
+    // With class lists (two-kernel form): the launch positions of the second list, whose length is only known on the device --
+    // the grid is sized for every position, workgroups beyond the list's end leave at once.
+    const uint32_t* const rest = PRESEEDED && A.simple_list ? A.simple_list + ((A.n_items + 63) & ~(int64_t)63) : nullptr;
+    const int64_t n_pos = rest ? (int64_t)A.multi_count[3] : A.n_items;
     // every lane of the wave runs the same number of iterations (arena and bail-list slots are claimed once per wave)
-    for (int64_t it0 = (int64_t)blockIdx.x * 64; it0 < A.n_items; it0 += n_threads) {
-        const int64_t it = it0 + lane;
+    for (int64_t it0 = (int64_t)blockIdx.x * 64; it0 < n_pos; it0 += n_threads) {
+        const int64_t it = rest ? (it0 + lane < n_pos ? (int64_t)rest[it0 + lane] : A.n_items) : it0 + lane;
         int64_t item = -1;
         int rc = PMX_C_DONE;
         CResult res;
@@ -162,11 +217,11 @@ __device__ __forceinline__ void align_compact_body(const AlignArgs& A) {
                 item = compact_item(A, it, rd, amb);
                 const uint32_t c = A.cseed_n[it];
                 if (c == PMX_C_NSEED_BAIL) rc = PMX_C_BAIL;
-                else { n_s = (int)(c & 0xffu); n_s0 = (int)(c >> 8); }
+                else { n_s = PMX_C_NSEED_N(c); n_s0 = PMX_C_NSEED_N0(c); }
             }
             CSeedOutT<PT> so;
             so.q = nullptr; so.st = nullptr;
-            so.out = (c_g32*)(A.cseeds + (size_t)it * CSeedOutT<PT>::kPairWords);
+            so.out = (c_g32*)(A.cseeds + (size_t)(it < A.n_items ? it : 0) * CSeedOutT<PT>::kPairWords);
             const int n_load = n_s < MT::kCap ? n_s : MT::kCap;
             for (int i0 = 0; __ballot(i0 < n_load) != 0ULL; i0 += 4) {
                 uint32_t x[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0};
@@ -238,7 +293,7 @@ __device__ __forceinline__ void align_compact_multi_body(const AlignArgs& A) {
             const uint32_t* amb[2];
             item = compact_item(A, it, rd, amb);
             const uint32_t c = A.cseed_n[it];
-            const int n_s = (int)(c & 0xffu), n_s0 = (int)(c >> 8);
+            const int n_s = PMX_C_NSEED_N(c), n_s0 = PMX_C_NSEED_N0(c);
             CSeedOutT<PT> so;
             so.q = nullptr; so.st = nullptr;
             so.out = (c_g32*)(A.cseeds + (size_t)it * CSeedOutT<PT>::kPairWords);
@@ -257,6 +312,67 @@ __device__ __forceinline__ void align_compact_multi_body(const AlignArgs& A) {
     }
 }
 
+// The pairs of the simple list (launch positions; mates that do not overlap on the reference): thread per pair, chained
+// from the hand-over words in registers (align/aln_compact_simple.hpp).  The only LDS is the penalty tables.  A pair the
+// path does not finish goes where the first form sends a pair it leaves after the seeds: to the second form's list (which
+// finishes a superset of the first form's pairs), or, without a second form, to the bail list.  One workgroup per 64
+// launch positions of the whole launch, as for the chain kernel: those beyond the list's end leave at once.
+template <class PT>
+__device__ __forceinline__ void align_simple_body(const AlignArgs& A) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t c_lds[];
+    const int lane = (int)(threadIdx.x & 63u);
+    // (16 bytes in: CPenTab marks "no tables" with a null pointer, and LDS offset 0 compares equal to nullptr in these
+    //  address_space(3) pointer types)
+    c_u8* pen = (c_u8*)((c_u32*)c_lds + PMX_C_SIMPLE_LDS_PAD / 4);
+    CPenTab tab;
+    tab.same = pen; tab.diff = pen + PMX_C_PEN_SAME;
+    for (int dd = lane; dd < PMX_C_PEN_DIFF; dd += 64) {
+        int ps, pd;
+        c_pen_values(A.opt.chn_pen_gap, dd, &ps, &pd);
+        if (dd < PMX_C_PEN_SAME) pen[dd] = (uint8_t)(ps < 255 ? ps : 255);
+        pen[PMX_C_PEN_SAME + dd] = (uint8_t)(pd < 255 ? pd : 255);
+    }
+    __syncthreads();
+    const int64_t n_list = (int64_t)A.multi_count[2];
+    const int64_t n_threads = (int64_t)gridDim.x * 64;
+    for (int64_t e0 = (int64_t)blockIdx.x * 64; e0 < n_list; e0 += n_threads) {
+        const int64_t e = e0 + lane;
+        int64_t item = -1, it = 0;
+        int rc = PMX_C_DONE;
+        CResult res;
+        res.mapped = 0;
+        if (e < n_list) {
+            it = (int64_t)A.simple_list[e];
+            CRead rd[2];
+            const uint32_t* amb[2];
+            item = compact_item(A, it, rd, amb);
+            const uint32_t c = A.cseed_n[it];
+            CSeedOutT<PT> so;
+            so.q = nullptr; so.st = nullptr;
+            so.out = (c_g32*)(A.cseeds + (size_t)it * CSeedOutT<PT>::kPairWords);
+            rc = compact_chain_simple(so, A.opt, A.ri, rd, PMX_C_NSEED_N(c), PMX_C_NSEED_N0(c), res, tab, A.edits != nullptr);
+        }
+        const bool done = item >= 0 && rc == PMX_C_DONE;
+        bool bail = item >= 0 && rc != PMX_C_DONE;
+        const unsigned long long dmask = __ballot(done);
+        if (dmask && lane == 0) atomicAdd(A.multi_count + 4, (unsigned long long)__popcll(dmask));
+        if (A.multi_list) {
+            const unsigned long long mmask = __ballot(bail);
+            if (mmask) {
+                unsigned long long mbase = 0;
+                if (lane == 0) mbase = atomicAdd(A.multi_count, (unsigned long long)__popcll(mmask));
+                mbase = __shfl(mbase, 0);
+                if (bail) A.multi_list[mbase + __popcll(mmask & ((1ULL << lane) - 1ULL))] = (uint32_t)it;
+            }
+            bail = false;
+        }
+        compact_emit(A, lane, item, bail, done, res);
+    }
+}
+
+// (four waves per SIMD: the register budget the kernel is written for)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_align_simple16(AlignArgs A) { align_simple_body<uint16_t>(A); }
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) k_align_simple32(AlignArgs A) { align_simple_body<uint32_t>(A); }
 __global__ void __launch_bounds__(64) k_align_compact16(AlignArgs A) { align_compact_body<uint16_t, true>(A); }
 __global__ void __launch_bounds__(64) k_align_compact32(AlignArgs A) { align_compact_body<uint32_t, true>(A); }
 __global__ void __launch_bounds__(64) k_align_compact16_fused(AlignArgs A) { align_compact_body<uint16_t, false>(A); }

@@ -105,7 +105,7 @@ struct AlignSwitches {
     const bool no_mv_handover = on(O_ALIGN_NO_MV_HANDOVER), no_lds_ring = on(O_ALIGN_NO_LDS_RING), no_lane_ring = on(O_ALIGN_NO_LANE_RING);
     const bool no_rows_dp = on(O_ALIGN_NO_ROWS_DP), no_dp_fast = on(O_ALIGN_NO_DP_FAST), no_work_queue = on(O_ALIGN_NO_WORK_QUEUE);
     const bool no_pair_sort = on(O_ALIGN_NO_PAIR_SORT), pair_key1 = on(O_ALIGN_PAIR_KEY1), no_dedup = on(O_ALIGN_NO_DEDUP);
-    const bool compact_pos32 = on(O_ALIGN_COMPACT_POS32), compact_fused = on(O_ALIGN_COMPACT_FUSED), no_multi = on(O_ALIGN_NO_MULTI);
+    const bool compact_pos32 = on(O_ALIGN_COMPACT_POS32), compact_fused = on(O_ALIGN_COMPACT_FUSED), no_multi = on(O_ALIGN_NO_MULTI), no_simple = on(O_ALIGN_NO_SIMPLE);
     const bool resident_grid = on(O_ALIGN_RESIDENT_GRID), dpg_no_serve = on(O_DPG_NO_SERVE);
     const bool prof = on(O_ALIGN_PROF), verbose = on(O_ALIGN_VERBOSE);                                                    // diagnostics
     const bool dp_hist = on(O_DP_HIST), dpg_prof = on(O_DPG_PROF), dpg_shadow = on(O_DPG_SHADOW), dpg_check_list = on(O_DPG_CHECK_LIST);
@@ -229,7 +229,7 @@ bool AlignStage::setup(int revcomp_mate2, uint64_t cigar_cap) {
     PMX_HIP(hipMemsetAsync(al->stats.p, 0, 4 * sizeof(unsigned long long), stream));
     al->dd_count.ensure(4);   // distinct-pair map: [0] representatives, [1] copies of an arena-overflowed representative, [2] copies of bails
     PMX_HIP(hipMemsetAsync(al->dd_count.p, 0, 4 * sizeof(unsigned long long), stream));
-    al->last_dp_slots = 0; al->last_compact = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_huge = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
+    al->last_dp_slots = 0; al->last_compact = 0; al->last_simple = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_huge = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
     memset(&al->last_stats, 0, sizeof(al->last_stats));
     if (n_items <= 0) return false;
     al->last_stats.n_items = n_items;
@@ -434,7 +434,7 @@ const uint32_t* AlignStage::launch_order() {
 // Compact tier (align_kernel_compact.hip): every pair of the launch order first, work state in LDS; what it cannot finish
 // comes back as the bail list (al->bail_list), which is the launch order of the tail.  -> the length of that list.
 // Its kernels read, beyond the base: n_items, pair_perm, retry_list / retry_count (the bail list), cseeds / cseed_n,
-// multi_list / multi_count (chain kernel and second form), multi_ws (second form).
+// multi_list / multi_count (chain kernel and second form), multi_ws (second form), simple_list (seeds and chain kernels).
 int64_t AlignStage::compact_tier(const uint32_t* order) {
     al->bail_list.ensure((size_t)n_items);
     const bool pos16 = al->ri.len <= 32767 && !sw.compact_pos32;
@@ -459,8 +459,18 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
     // -- 7 KB per wave against the 21 KB of the pairs' work state, so that part runs at the occupancy its
     // registers allow instead of seven waves per CU; the seeds cross in HBM (224 bytes per pair with 16-bit
     // position words).  PMX_ALIGN_COMPACT_FUSED keeps everything in k_align_compact.
+    // PMX_ALIGN_NO_SIMPLE: no class lists, the chain kernel runs every launch position.
+    const bool c_simple = !c_fused && !sw.no_simple;
     if (!c_fused) {
         const size_t blocks = (size_t)((n_launch + 63) / 64);
+        // [0] length of multi_list, [1] pairs the second form finished, [2] / [3] lengths of the two class lists, [4] pairs k_align_simple finished
+        al->multi_count.ensure(8);
+        PMX_HIP(hipMemsetAsync(al->multi_count.p, 0, 8 * sizeof(unsigned long long), stream));
+        if (c_simple) {
+            al->simple_list.ensure(blocks * 64 * 2);   // the simple list, behind it (from n_launch rounded up to 64) the other
+            A.simple_list = al->simple_list.p;
+            A.multi_count = al->multi_count.p;
+        }
         al->cseeds.ensure(blocks * (size_t)PMX_C_CAP * (pos16 ? 1 : 2) * 64);
         al->cseed_n.ensure(blocks * 64);
         A.cseeds = al->cseeds.p;
@@ -475,6 +485,10 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         hipLaunchKernelGGL(s_kern, dim3((unsigned)s_grid), dim3(64), ((size_t)PMX_C_SEEDQ * 2 + 8) * 64 * sizeof(uint32_t),   // queues + eight staging words per lane
                            stream, A);
         PMX_HIP(hipGetLastError());
+        if (c_simple) {
+            hipLaunchKernelGGL(k_compact_classes, dim3((unsigned)((n_launch + 2047) / 2048)), dim3(256), 0, stream, A);   // PMX_C_CLASS_BLOCK positions each
+            PMX_HIP(hipGetLastError());
+        }
         timer_end(ctx, "align_cseeds", 1);
     }
     // Second form (k_align_compact*_multi): the pairs that leave the first one after their seeds -- a third chain, two
@@ -484,12 +498,19 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
     const bool c_multi = !c_fused && !sw.no_multi;
     if (c_multi) {
         al->multi_list.ensure((size_t)n_items);
-        al->multi_count.ensure(4);   // [0] length of multi_list, [1] pairs the second form finished
-        PMX_HIP(hipMemsetAsync(al->multi_count.p, 0, 2 * sizeof(unsigned long long), stream));
         A.multi_list = al->multi_list.p;
         A.multi_count = al->multi_count.p;
     }
-    timer_begin(ctx, "align_dom");   // the dominant kernel on its own (bench.py roofline)
+    timer_begin(ctx, "align_dom");   // the dominant kernels on their own (bench.py roofline): the chain work of every pair
+    // Pairs whose mates do not overlap on the reference (half of a 300 +- 30 bp library of 150-base reads) are chained
+    // from their hand-over words in registers, k_align_simple*: no per-pair LDS, so the kernel runs at the waves its
+    // registers allow; the chain kernel below then runs the other list.  Both lists' lengths stay on the device: one
+    // workgroup per 64 positions of the launch, those beyond a list's end leave at once (a resident grid striding over
+    // the lists -- PMX_ALIGN_COMPACT_WAVES -- is the slower form here as it is for the chain kernel alone).
+    if (c_simple) {
+        hipLaunchKernelGGL(pos16 ? k_align_simple16 : k_align_simple32, dim3((unsigned)c_grid), dim3(64), (size_t)PMX_C_SIMPLE_LDS_PAD + PMX_C_PEN_BYTES, stream, A);
+        PMX_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(c_kern, dim3((unsigned)c_grid), dim3(64), c_lds, stream, A);
     PMX_HIP(hipGetLastError());
     timer_end(ctx, "align_dom", 1);
@@ -509,8 +530,14 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         pair_count_copies(ctx, al, al->bail_list.p, al->retry_count.p + 2, rs->pd_mult.p, n_launch);
         PMX_HIP(hipMemcpyAsync(&h_dups, al->dd_count.p + 2, sizeof(h_dups), hipMemcpyDeviceToHost, stream));
     }
+    unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};   // multi_count[0 .. 4]
     PMX_HIP(hipMemcpyAsync(&h_bail, al->retry_count.p + 2, sizeof(h_bail), hipMemcpyDeviceToHost, stream));
+    if (!c_fused) PMX_HIP(hipMemcpyAsync(h_cnt, al->multi_count.p, sizeof(h_cnt), hipMemcpyDeviceToHost, stream));
     PMX_HIP(hipStreamSynchronize(stream));
+    if (sw.verbose && !c_fused)
+        fprintf(stderr, "align: compact tier, %lld launch positions: simple list %llu (k_align_simple finished %llu), other list %llu; second form: %llu listed, %llu finished; %llu bails\n",
+                (long long)n_launch, h_cnt[2], h_cnt[4], h_cnt[3], h_cnt[0], h_cnt[1], h_bail);
+    al->last_simple = (int64_t)h_cnt[4];
     al->last_compact = n_items - (int64_t)h_bail - (int64_t)h_dups;
     return (int64_t)h_bail;
 }

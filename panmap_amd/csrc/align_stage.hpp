@@ -39,6 +39,7 @@ struct pmx_aligner {
     pmx::DevBuf<uint32_t> multi_list;        // compact tier, second form (several regions per mate): launch positions + counters
     pmx::DevBuf<unsigned long long> multi_count;
     pmx::DevBuf<uint32_t> multi_ws;
+    pmx::DevBuf<uint32_t> simple_list;       // compact tier: the two class lists of launch positions (AlignArgs::simple_list)
     pmx::DevBuf<uint8_t> dp_req;
     pmx::DevBuf<pmx::aln::DpRes> dp_res;
     pmx::DevBuf<uint32_t> dp_ncached, dp_slot_pairs, dp_list_a, dp_list_b;
@@ -60,7 +61,7 @@ struct pmx_aligner {
     pmx::DevBuf<int32_t> edits;              // AlignArgs::edits while pmx_align_score_reads runs
     bool want_edits = false;
     pmx_align_stats last_stats;
-    int64_t last_dp_slots = 0, last_compact = 0;
+    int64_t last_dp_slots = 0, last_compact = 0, last_simple = 0;
     int64_t n_records = 0;
     uint64_t cigar_cap = 0;
     size_t dev_total_mem = 0;            // hipMemGetInfo total, asked once

@@ -43,6 +43,7 @@
     X(ALIGN_NO_DEDUP, "ab", "align: every pair through the compact tier and the tail, no distinct-pair map (copies are not fanned out)")       \
     X(ALIGN_DEDUP_DEPTH, "tune", "align: distinct-pair map from this many pairs per reference base (default 64; 0 = always)")                  \
     X(ALIGN_NO_MULTI, "ab", "align: compact tier without its second form (several regions per mate): every bail to the thread-per-pair tier")  \
+    X(ALIGN_NO_SIMPLE, "ab", "align: compact tier without the register-only chain kernel for mates that do not overlap: every pair through k_align_compact") \
     X(ALIGN_COMPACT_WAVES, "tune", "align: compact chain kernel on a resident grid of N waves per CU (default: one workgroup per 64 pairs)")    \
     X(ALIGN_CSEED_WAVES, "tune", "align: compact seeds kernel on a resident grid of N waves per CU")                                           \
     X(ALIGN_NO_TPP, "ab", "align: no thread-per-pair tier (bails straight to the wave tiers)")                                                 \

@@ -97,3 +97,11 @@ def cost_sorted_blocked(key, B):
     return c / nw
 for B in (1024, 4096, 16384):
     print("sorted by (overlap>>3, anchors) within blocks of %5d: %.1f" % (B, cost_sorted_blocked((ov >> 3) * 64 + na, B)))
+# ---- the register-only chain path (align/aln_compact_simple.hpp): which share of these pairs the seeding classes simple
+# (mates that do not overlap on the reference) and which share the path finishes -- the decision rule of profiles/r14
+import tempfile
+import chain_simple_cases as cs
+cls, forms = cs.host_chain_simple(tempfile.mkdtemp(prefix="chain_simple_"), g, [r if i % 2 == 0 else pmx.reverse_complement(r) for i, r in enumerate(reads)])
+d1 = forms[1][1]
+print("---- simple path: classed simple %.4f of the pairs, finished %.4f, bailed %.4f; first form finishes %.4f; finished by the first form but not by the path, among the classed: %.4f"
+      % ((cls >= 2).mean(), (cls == 2).mean(), (cls == 3).mean(), d1.mean(), ((cls == 3) & (d1 == 1)).mean()))

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Host parity sweep of the compact align tier (both forms, two-kernel and fused, 16- and 32-bit position words) against the
-reference's own aligner (oracle/_ref): read length, insert size, substitution rate, indels, several genomes of the SARS
-tree.  CPU only (the kernel source built for the host, tests/hostsim); every pair a form finishes must carry the
-reference's record.  python tools/host_parity_sweep_compact.py [pairs per case]"""
+"""Host parity sweep of the compact align tier (both forms, two-kernel and fused, 16- and 32-bit position words, and the
+register-only chain path for mates that do not overlap, align/aln_compact_simple.hpp) against the reference's own aligner
+(oracle/_ref): read length, insert size, substitution rate, indels, several genomes of the SARS tree.  CPU only (the kernel
+source built for the host, tests/hostsim); every pair a form finishes must carry the reference's record.
+python tools/host_parity_sweep_compact.py [pairs per case]"""
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -13,6 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import panmap_amd as pmx          # noqa: E402
 import align_checks as ac         # noqa: E402
+import chain_simple_cases as cs   # noqa: E402
 from oracle import oracle         # noqa: E402
 
 
@@ -26,6 +29,7 @@ def main():
                                                     (75, 80.0, 0.002, 0), (125, 200.0, 0.02, 9), (160, 170.0, 0.001, 0), (150, 500.0, 0.03, 0)):
             cases.append((node, read_len, insert, sub, indel_every))
     total = bad_total = 0
+    tmp = tempfile.mkdtemp(prefix="chain_simple_")
     for node, read_len, insert, sub, indel_every in cases:
         g = pm.genome(node)
         concat, off = pmx.simulate_paired_reads(g, n_pairs, read_len=read_len, seed=int(rng.integers(1, 1 << 30)), sub_rate=sub,
@@ -55,6 +59,16 @@ def main():
             total += len(idx)
             bad_total += len(bad)
             line += "  %s %d/%d%s" % (name, len(idx), len(want), "" if not bad else " BAD %d" % len(bad))
+            if bad:
+                print(bad[:3])
+        for name, pos32 in (("simple path", False), ("simple path, 32-bit positions", True)):
+            cls, forms = cs.host_chain_simple(tmp, g, reads, pos32)
+            got = forms[0][0]
+            idx = [i for i in range(len(want)) if cls[i] == 2]
+            bad = ac.compare_results([got[i] for i in idx], [want[i] for i in idx])
+            total += len(idx)
+            bad_total += len(bad)
+            line += "  %s %d/%d (classed %d)%s" % (name, len(idx), len(want), int((cls >= 2).sum()), "" if not bad else " BAD %d" % len(bad))
             if bad:
                 print(bad[:3])
         print(line, flush=True)
