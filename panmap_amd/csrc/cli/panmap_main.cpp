@@ -10,9 +10,12 @@
 // `<prefix>.mgsr.abundance.out`; --meta --filter-and-assign --align-reads [--min-num-align N] -> `<prefix>_mgsr_aligned/`: one
 // BAM (+ .bai) per node with at least N assigned reads, and their genomes in reference.fa.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
 // parts of panmap this build leaves out (--impute, ...), BUILDING a homopolymer-compressed index (one
-// given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta, --batch with
-// --gpus.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
+// given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta.
+// --batch FILE runs the samples of a batch file against what stays resident (the index, or with --meta both indexes and the
+// pmx_meta); with --gpus N the samples are DEALT to N processes, one per GPU, which exchange nothing: every sample's files are
+// what the one-GPU run writes.  Output prefix: -o, else derived from reads1 as the reference derives it.  Exit code 130 on SIGINT.
 #include <signal.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -31,6 +34,7 @@
 #include <chrono>
 #include <fstream>
 #include <memory>
+#include <new>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -99,7 +103,9 @@ void usage() {
           "      --stop STAGE           index|place|align|genotype|consensus (default consensus)\n"
           "      --min-depth N          high-quality bases a call needs (default 1)     --min-qual F   lowest QUAL kept (default 30)\n"
           "      --annotate-vcf         add VDB, SGB, RPBZ, MQBZ, MQSBZ, BQBZ, SCBZ and MQ0F to the INFO of the VCF records\n"
-          "      --batch FILE           one sample per line: reads1 [reads2] [prefix]; the index stays resident\n"
+          "      --batch FILE           one sample per line: reads1 [reads2] [prefix]; the index stays resident (with --meta: both\n"
+          "                             indexes and the device state; not with --amplicon-depth).  With --gpus N (at most 16) the samples\n"
+          "                             are dealt to N processes, one per GPU, each sample whole on one GPU: the files of the one-GPU run\n"
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
           "      --meta --filter-and-assign   assign every read to the nodes it scores best on -> <prefix>.mgsr.assignedReads.fastq,\n"
           "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU)\n"
@@ -119,7 +125,8 @@ void usage() {
           "      --mask-reads-relative-frequency F / --mask-seeds-relative-frequency F   as --mask-reads / --mask-seeds with the threshold\n"
           "                             int(F x the reads of the amplicon); needs --amplicon-depth; unlisted reads stay unmasked (one of the four)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
-          "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange\n"
+          "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange (with --batch:\n"
+          "                             whole samples dealt instead, nothing exchanged; also for --meta --filter-and-assign)\n"
           "      --refine               re-rank the top candidates by aligning the reads against them\n"
           "      --refine-top-pct F / --refine-max-top-n N / --refine-neighbor-radius N / --refine-max-neighbor-n N\n"
           "  -i, --index PATH           load a pre-built index       --index-out PATH   write the built index here\n"
@@ -295,6 +302,11 @@ std::vector<BatchEntry> read_batch_file(const std::string& path) {
         out.push_back(e);
     }
     return out;
+}
+std::vector<BatchEntry> read_samples(const std::string& path) {   // ... of which there must be one
+    std::vector<BatchEntry> samples = read_batch_file(path);
+    if (samples.empty()) die("No samples found in batch file");
+    return samples;
 }
 void mkdirs(const std::string& dir) {   // fs::create_directories
     std::string cur;
@@ -805,12 +817,15 @@ struct Ranks {
     std::string meet_dir;
 };
 
-// -> true in a rank (rk filled in), false in the parent once the ranks have ended (*code = the run's exit code)
-bool fork_ranks(int n, Ranks& rk, int* code) {
+// -> true in a rank (rk filled in), false in the parent once the ranks have ended (*code = the run's exit code).
+// rendezvous = false: ranks that never meet (--batch) get no directory
+bool fork_ranks(int n, Ranks& rk, int* code, bool rendezvous = true) {
     if (n <= 1) return true;
     char tmpl[] = "/tmp/panmap_ranks_XXXXXX";
-    if (!mkdtemp(tmpl)) die("cannot create a rendezvous directory under /tmp");
-    rk.meet_dir = tmpl;
+    if (rendezvous) {
+        if (!mkdtemp(tmpl)) die("cannot create a rendezvous directory under /tmp");
+        rk.meet_dir = tmpl;
+    }
     fflush(stdout); fflush(stderr);
     std::vector<pid_t> kids;
     for (int r = 0; r < n; ++r) {
@@ -842,9 +857,11 @@ bool fork_ranks(int n, Ranks& rk, int* code) {
             for (pid_t o : kids) if (o > 0) kill(o, SIGTERM);
         }
     }
-    unlink((rk.meet_dir + "/uid.tmp").c_str());
-    unlink((rk.meet_dir + "/uid").c_str());
-    rmdir(rk.meet_dir.c_str());
+    if (rendezvous) {
+        unlink((rk.meet_dir + "/uid.tmp").c_str());
+        unlink((rk.meet_dir + "/uid").c_str());
+        rmdir(rk.meet_dir.c_str());
+    }
     *code = worst;
     return false;
 }
@@ -878,6 +895,61 @@ pmx_dist* join_ranks(pmx_ctx* ctx, const Ranks& rk) {
     return dist;
 }
 
+// ------------------------------------------------------------------------------------------------ --batch
+// The samples of a batch file are DEALT, not sharded: each one runs whole, on one GPU, against what that process keeps
+// resident, exactly as it runs under --gpus 1 -- so its files are the one-GPU run's by construction.  With --gpus N the ranks
+// never meet (no rendezvous, no pmx_dist): all they share is this block, mapped by the parent before the fork.  A rank takes
+// the next sample of the file until none is left, and adds each sample to one of the two counts the parent reports at the
+// end.  One process (--gpus 1) runs the same loop alone: the file's order.
+struct Deal {
+    std::atomic<int64_t> next, done, failed;
+    static_assert(std::atomic<int64_t>::is_always_lock_free, "the batch counters are shared between processes");
+
+    static Deal* map() {
+        void* p = mmap(nullptr, sizeof(Deal), PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+        if (p == MAP_FAILED) die("cannot map the counters of the batch");
+        Deal* d = new (p) Deal;
+        d->next.store(0); d->done.store(0); d->failed.store(0);
+        return d;
+    }
+};
+
+// One rank's (or the only process's) part of the batch.  run_one(sample) runs one sample and returns what its report line
+// says behind `->`; a Fatal is that sample's failure and the batch goes on (runBatchPlacement, src/main.cpp:1464-1666).  The
+// line -- `[position in the file/samples] prefix -> ... (NNNms)` -- leaves in one write(2), so the lines of several ranks
+// cannot interleave.
+template <class RunOne>
+void run_dealt(const std::vector<BatchEntry>& samples, Deal& deal, RunOne&& run_one) {
+    const int64_t n = (int64_t)samples.size();
+    for (int64_t i; (i = deal.next.fetch_add(1)) < n;) {
+        const BatchEntry& e = samples[(size_t)i];
+        const size_t slash = e.prefix.find_last_of('/');
+        if (slash != std::string::npos && slash > 0) mkdirs(e.prefix.substr(0, slash));
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string what;
+        bool ok = true;
+        try { what = run_one(e); }
+        catch (const Fatal& f) { ok = false; what = f.msg == "No placement found" ? std::string("NO PLACEMENT") : "failed: " + f.msg; }
+        const long long ms = (long long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
+        const std::string line = "[" + std::to_string(i + 1) + "/" + std::to_string(n) + "] " + e.prefix + " -> " + what + " (" + std::to_string(ms) + "ms)\n";
+        if (write(2, line.data(), line.size()) < 0) {}   // (nowhere to report it)
+        (ok ? deal.done : deal.failed).fetch_add(1);
+    }
+}
+
+// The end of the batch, in the parent of the ranks or in the only process.  code: what fork_ranks returned -- non-zero when a
+// rank could not start or died; its samples are not dealt again, and nothing more is started after a GPU process has died.
+int end_batch(Deal* deal, int code, size_t n_samples, const char* verb) {
+    const long long done = (long long)deal->done.load(), failed = (long long)deal->failed.load();
+    munmap(deal, sizeof(Deal));
+    if (code) {
+        fprintf(stderr, "panmap: error: a rank ended with code %d; %lld of %zu samples had been reported, the others are not run\n", code, done + failed, n_samples);
+        return code;
+    }
+    fprintf(stderr, "Batch complete: %lld %s, %lld failed\n", done, verb, failed);
+    return failed ? 1 : 0;
+}
+
 // the id of node `head` and, comma-joined behind it, the ids of the n nodes that share its line: those folded into it
 // (identical nodes, src/mgsr.cpp:505-532) or the haplotypes merged with it
 std::string joined_ids(const pmx_index* idx, uint32_t head, const uint32_t* others, size_t n) {
@@ -886,44 +958,27 @@ std::string joined_ids(const pmx_index* idx, uint32_t head, const uint32_t* othe
     return ids;
 }
 
-// One --meta sample (runDeconvolution, src/main.cpp:1192-1313; --filter-and-assign: filterAndAssignBatch, :720-1016).  A
-// call-lifetime struct, one function per step in the order run_meta calls them; it owns the Run, the two tables, the reads,
-// the ranks and this rank's shard.  The two indexes of the tree (the place stage's and its oriented form, without flank mask)
-// are built in memory.  --gpus N: one rank per GPU, each with a contiguous shard of the reads (R1 then R2); every rank ends with
-// the whole sample's result (pmx_meta_attach_dist), rank 0 writes it.  run.close() is run_meta's call at the normal ends.
-struct MetaSample {
+// What one --meta process keeps for all its samples (runDeconvolution, src/main.cpp:1192-1313; --filter-and-assign:
+// filterAndAssignBatch, :720-1016): the Run with the PanMAN, the two indexes of the tree (the place stage's and its oriented
+// form, without flank mask, built in memory), the context and the pmx_meta with its settings; the two tables; the ranks.  One
+// function per step in the order run_meta calls them.  --gpus N without --batch: one rank per GPU, each with a contiguous shard
+// of the one sample's reads (R1 then R2); every rank ends with the whole sample's result (pmx_meta_attach_dist), rank 0 writes
+// it.  With --batch the ranks never meet: each runs whole samples.  run.close() is run_meta's call at the normal ends.
+struct MetaRun {
     Config c;                                    // (quiet in the ranks above 0)
     Run run;
     struct Amplicons { pmx_amplicons* a = nullptr; ~Amplicons() { pmx_amplicons_free(a); } } amplicons;   // --amplicon-depth
     struct Taxonomy { pmx_taxonomy* t = nullptr; ~Taxonomy() { pmx_taxonomy_free(t); } } taxonomy;        // --taxonomic-metadata
-    std::unique_ptr<const Reads> reads_p;        // mates as sequenced, one after the other
     Ranks rk;
-    int64_t lo = 0, hi = 0;                      // this rank's shard
-    // --filter-and-assign, what assign() leaves for the writers: per merged read its state, LCA node and nodes [off[r], off[r + 1])
-    // of `nodes`; per read of the input its merged read; per node its head, per head the nodes folded into it
-    int64_t n_merged = 0, n_nodes = 0;
-    std::vector<uint8_t> state;
-    std::vector<uint32_t> lca, nodes, head;
-    std::vector<int64_t> off, merged;
-    std::vector<std::vector<uint32_t>> folded;
-    // ... and write_fastq: per merged read the FASTQ positions of its copies (ascending: input order), the four tallies
-    std::string fq_path;
-    std::vector<std::vector<int64_t>> copies;
-    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0, n_over = 0;
-    // ... write_fastq and write_node_lists for --align-reads: per FASTQ position its read of the input, per head the FASTQ
-    // positions of its reads (ascending)
-    std::vector<int64_t> fq_read;
-    std::vector<std::vector<int64_t>> by_node;
 
-    explicit MetaSample(const Config& c_) : c(c_) {}
-    const Reads& reads() const { return *reads_p; }
-    bool masking() const { return c.mask_reads > 0 || c.mask_seeds > 0 || c.mask_reads_rf > 0.0 || c.mask_seeds_rf > 0.0; }
-    std::string ids_of_head(uint32_t h) const { return joined_ids(run.idx, h, folded[h].data(), folded[h].size()); }
+    explicit MetaRun(const Config& c_) : c(c_) {}
 
     // the refusals that need no file
     void refuse_options() const {
-        if (c.reads1.empty()) die("--meta needs reads");
-        if (c.filter_and_assign && c.gpus > 1) die("--filter-and-assign runs on one GPU: drop --gpus");
+        if (c.reads1.empty() && c.batch.empty()) die("--meta needs reads");
+        if (c.filter_and_assign && c.gpus > 1 && c.batch.empty()) die("--filter-and-assign runs on one GPU: drop --gpus");
+        if (!c.batch.empty() && !c.amplicon_depth.empty())
+            die("option --amplicon-depth is not accepted with --batch: one table cannot name the reads of several samples");
         if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
         if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
         if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
@@ -986,23 +1041,20 @@ struct MetaSample {
         say(c, "index", "seed index + oriented seed index (in memory)");
     }
 
-    // Leaves: the whole sample's reads on the host (before the fork: every rank inherits them).
-    void read_reads() { reads_p.reset(new Reads(c.reads1, c.reads2, Reads::APPENDED)); }
-
+    // n ranks; meet: they join each other (one sample, sharded) -- or never meet (--batch: whole samples, dealt).
     // -> true in a rank, false in the parent once the ranks have ended (*code = the run's exit code).
-    // In a rank, leaves: rk, the shard [lo, hi), the rank's device open and the ranks joined (run.ctx, run.dist).
-    bool open_rank(int* code) {
-        if (!fork_ranks(c.gpus, rk, code)) return false;
+    // In a rank, leaves: rk, the rank's device open and, when they meet, the ranks joined (run.ctx, run.dist).
+    bool open_rank(int n, bool meet, int* code) {
+        if (!fork_ranks(n, rk, code, meet)) return false;
         if (rk.rank > 0) c.quiet = true;
-        reads().shard(rk.rank, rk.world, &lo, &hi);
         run.dev = rank_device(rk);
         check(pmx_ctx_create(run.dev, &run.ctx), "opening the GPU");
-        run.dist = join_ranks(run.ctx, rk);
+        if (meet) run.dist = join_ranks(run.ctx, rk);
         return true;
     }
 
-    // Leaves: run.meta with the indexes on the device, the ranks attached, --dust, the masks and, with --amplicon-depth, the
-    // amplicon of every read of this rank's shard, by its own name (mates one by one); unlisted: the last group.
+    // Leaves: run.meta with the indexes on the device, the ranks attached, --dust, the masks and what --filter-and-assign is
+    // run with: the taxonomy, the ambiguity thresholds, --breadth-ratio.  None of it depends on a sample's reads.
     void configure() {
         pmx_meta*& m = run.meta;
         check(pmx_meta_create(run.ctx, run.idx, run.oidx, &m), "uploading the indexes");
@@ -1010,6 +1062,63 @@ struct MetaSample {
         check(pmx_meta_set_dust(m, c.dust), "--dust");
         check(pmx_meta_set_masks(m, c.mask_reads, c.mask_seeds), "--mask-reads / --mask-seeds");
         check(pmx_meta_set_relative_masks(m, c.mask_reads_rf, c.mask_seeds_rf), "--mask-reads-relative-frequency / --mask-seeds-relative-frequency");
+        if (!c.filter_and_assign) return;
+        if (taxonomy.t) {
+            std::vector<int32_t> node_taxon;
+            for (int64_t v = 0; pmx_index_node_id(run.idx, v); ++v) node_taxon.push_back((int32_t)pmx_taxonomy_lookup(taxonomy.t, pmx_index_node_id(run.idx, v)));
+            check(pmx_meta_set_taxonomy(m, node_taxon.data(), (int64_t)node_taxon.size(), pmx_taxonomy_num_taxa(taxonomy.t), c.maximum_taxon_number), "--taxonomic-metadata");
+            check(pmx_meta_set_ambiguous(m, c.ambiguous_score, c.ambiguous_ratio), "--ambiguous-score-threshold");
+        }
+        check(pmx_meta_set_breadth(m, c.breadth_ratio ? 1 : 0), "--breadth-ratio");
+    }
+};
+
+// One sample of a --meta process: its reads, this rank's shard of them, and what the steps leave for one another.  A
+// call-lifetime struct, one function per step in the order meta_steps calls them.  Nothing of a sample outlives it: the
+// tallies and lists below start empty for every sample of a batch.  `c`: the sample's reads1 / reads2 / output (--batch: a
+// copy of the run's with those three set, and quiet).
+struct MetaSample {
+    const Config& c;
+    Run& run;
+    const MetaRun::Amplicons& amplicons;
+    const MetaRun::Taxonomy& taxonomy;
+    std::unique_ptr<const Reads> reads_p;        // mates as sequenced, one after the other
+    int64_t lo = 0, hi = 0;                      // this rank's shard
+    // --filter-and-assign, what assign() leaves for the writers: per merged read its state, LCA node and nodes [off[r], off[r + 1])
+    // of `nodes`; per read of the input its merged read; per node its head, per head the nodes folded into it
+    int64_t n_merged = 0, n_nodes = 0;
+    std::vector<uint8_t> state;
+    std::vector<uint32_t> lca, nodes, head;
+    std::vector<int64_t> off, merged;
+    std::vector<std::vector<uint32_t>> folded;
+    // ... and write_fastq: per merged read the FASTQ positions of its copies (ascending: input order), the four tallies
+    std::string fq_path;
+    std::vector<std::vector<int64_t>> copies;
+    int64_t n_written = 0, n_unmapped = 0, n_discarded = 0, n_over = 0;
+    // ... write_fastq and write_node_lists for --align-reads: per FASTQ position its read of the input, per head the FASTQ
+    // positions of its reads (ascending)
+    std::vector<int64_t> fq_read;
+    std::vector<std::vector<int64_t>> by_node;
+
+    MetaSample(MetaRun& mr, const Config& c_) : c(c_), run(mr.run), amplicons(mr.amplicons), taxonomy(mr.taxonomy) {}
+    ~MetaSample() {                              // (a sample that failed inside --align-reads)
+        if (al_rs) pmx_readset_free(run.ctx, al_rs);
+        if (al_fa) fclose(al_fa);
+    }
+    const Reads& reads() const { return *reads_p; }
+    bool masking() const { return c.mask_reads > 0 || c.mask_seeds > 0 || c.mask_reads_rf > 0.0 || c.mask_seeds_rf > 0.0; }
+    std::string ids_of_head(uint32_t h) const { return joined_ids(run.idx, h, folded[h].data(), folded[h].size()); }
+
+    // Leaves: the whole sample's reads on the host (one sample over --gpus N: before the fork, every rank inherits them).
+    void read_reads() { reads_p.reset(new Reads(c.reads1, c.reads2, Reads::APPENDED)); }
+
+    // Leaves: the shard [lo, hi) of rank `rank` of `world` (a dealt sample: all of it, 0 of 1).
+    void take_shard(int rank, int world) { reads().shard(rank, world, &lo, &hi); }
+
+    // --amplicon-depth.  Leaves: in run.meta the amplicon of every read of this rank's shard, by its own name (mates one by one);
+    // unlisted: the last group.
+    void set_amplicons() {
+        pmx_meta* m = run.meta;
         if (!amplicons.a) return;
         const int32_t n_groups = pmx_amplicons_num_groups(amplicons.a);
         std::vector<int32_t> group((size_t)(hi - lo));
@@ -1055,13 +1164,6 @@ struct MetaSample {
     // Leaves: the assignment on the device's side done and downloaded: state / lca / off / nodes / merged, head / folded.
     void assign() {
         pmx_meta* m = run.meta;
-        if (taxonomy.t) {
-            std::vector<int32_t> node_taxon;
-            for (int64_t v = 0; pmx_index_node_id(run.idx, v); ++v) node_taxon.push_back((int32_t)pmx_taxonomy_lookup(taxonomy.t, pmx_index_node_id(run.idx, v)));
-            check(pmx_meta_set_taxonomy(m, node_taxon.data(), (int64_t)node_taxon.size(), pmx_taxonomy_num_taxa(taxonomy.t), c.maximum_taxon_number), "--taxonomic-metadata");
-            check(pmx_meta_set_ambiguous(m, c.ambiguous_score, c.ambiguous_ratio), "--ambiguous-score-threshold");
-        }
-        check(pmx_meta_set_breadth(m, c.breadth_ratio ? 1 : 0), "--breadth-ratio");
         check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
         n_merged = pmx_meta_num_reads(m);
         state.resize((size_t)std::max<int64_t>(n_merged, 1));
@@ -1402,16 +1504,9 @@ struct MetaSample {
     }
 };
 
-int run_meta(const Config& c) {
-    MetaSample s(c);
-    s.refuse_options();
-    s.load_amplicons();
-    s.load_taxonomy();
-    s.build_indexes();
-    s.read_reads();
-    int code = 0;
-    if (!s.open_rank(&code)) { s.run.close(); return code; }
-    s.configure();
+// one sample whose reads and shard are in hand, against the configured run; writer: this process writes the abundances (every
+// rank of a sharded sample ends with them)
+void meta_steps(MetaSample& s, bool writer) {
     s.set_reads();
     s.report_masks();
     if (s.c.filter_and_assign) {
@@ -1423,10 +1518,52 @@ int run_meta(const Config& c) {
         s.report_assigned();
     } else {
         s.estimate();
-        if (s.rk.rank == 0) s.write_abundance();
+        if (writer) s.write_abundance();
     }
-    s.run.close();
-    return 0;
+}
+
+int run_meta(const Config& c) {
+    MetaRun mr(c);
+    mr.refuse_options();
+    const bool batch = !c.batch.empty();
+    std::vector<BatchEntry> samples;
+    if (batch) samples = read_samples(c.batch);
+    mr.load_amplicons();
+    mr.load_taxonomy();
+    mr.build_indexes();
+    int code = 0;
+    if (!batch) {   // one sample, sharded over the ranks
+        MetaSample s(mr, mr.c);
+        s.read_reads();
+        if (!mr.open_rank(c.gpus, true, &code)) { mr.run.close(); return code; }
+        mr.configure();
+        s.take_shard(mr.rk.rank, mr.rk.world);
+        s.set_amplicons();
+        meta_steps(s, mr.rk.rank == 0);
+        mr.run.close();
+        return 0;
+    }
+    // --batch: the samples dealt to ranks that never meet, as in real_main; the rank that takes a sample reads its reads
+    fprintf(stderr, "Batch mode: %zu samples\n", samples.size());
+    fflush(stderr);
+    Deal* deal = Deal::map();
+    if (!mr.open_rank((int)std::min<size_t>((size_t)c.gpus, samples.size()), false, &code)) {
+        mr.run.close();
+        return end_batch(deal, code, samples.size(), "done");
+    }
+    mr.configure();
+    run_dealt(samples, *deal, [&](const BatchEntry& e) {
+        Config sc = mr.c;
+        sc.reads1 = e.reads1; sc.reads2 = e.reads2; sc.output = e.prefix; sc.quiet = true;
+        MetaSample s(mr, sc);
+        s.read_reads();
+        s.take_shard(0, 1);
+        meta_steps(s, true);
+        return c.filter_and_assign ? std::to_string(s.n_written) + " assigned reads" : std::to_string(pmx_meta_num_haplotypes(mr.run.meta)) + " haplotypes";
+    });
+    const int rc = mr.rk.world == 1 ? end_batch(deal, 0, samples.size(), "done") : 0;
+    mr.run.close();
+    return rc;
 }
 
 int real_main(int argc, char** argv) {
@@ -1442,6 +1579,7 @@ int real_main(int argc, char** argv) {
     if (c.output.empty()) c.output = derive_prefix(c);
     if (!c.batch.empty() && !c.reads1.empty()) die("--batch takes the read files from the batch file, not from the command line");
     if (c.gpus < 1) die("--gpus expects a positive number");
+    if (!c.batch.empty() && c.gpus > 16) die("--batch deals its samples to at most 16 ranks: --gpus " + std::to_string(c.gpus) + " is too many");
 
     if (c.breadth_ratio && !c.filter_and_assign) die("option --breadth-ratio is not accepted without --filter-and-assign");
     if (!c.align_options.empty() && !c.filter_and_assign) die("option " + c.align_options[0] + " is not accepted without --filter-and-assign");
@@ -1454,6 +1592,9 @@ int real_main(int argc, char** argv) {
         if (exists(c.index) && pmx_index_read_header(c.index.c_str(), &h, nullptr) == PMX_OK && h.hpc) die("--meta cannot use the homopolymer-compressed index " + c.index);
         return run_meta(c);
     }
+    // the batch file is read, and found wanting, before anything is built or opened
+    std::vector<BatchEntry> samples;
+    if (!c.batch.empty() && stop != 0) samples = read_samples(c.batch);
 
     // ------------------------------------------------------------------------------------------------ index
     Run run;
@@ -1473,49 +1614,44 @@ int real_main(int argc, char** argv) {
     if (stop == 0 || (c.reads1.empty() && c.batch.empty())) { run.close(); return 0; }
 
     // ------------------------------------------------------------------------------------------------ --gpus N
-    // forked HERE: the index (and the PanMAN, when it was opened) is in memory and nothing has touched a GPU yet
+    // forked HERE: the index (and the PanMAN, when it was opened) is in memory and nothing has touched a GPU yet.  One sample
+    // is sharded over the ranks, which meet through RCCL; the samples of --batch are dealt to ranks that never meet, and no
+    // more of those than there are samples
+    const bool batch = !c.batch.empty();
     Ranks rk;
+    Deal* deal = nullptr;
+    if (batch) {
+        fprintf(stderr, "Batch mode: %zu samples\n", samples.size());
+        fflush(stderr);
+        deal = Deal::map();
+    }
     if (c.gpus > 1) {
-        if (!c.batch.empty()) die("--gpus shards ONE sample over the GPUs; run --batch per GPU instead");
         int code = 0;
-        if (!fork_ranks(c.gpus, rk, &code)) { run.close(); return code; }
+        const int n_ranks = batch ? (int)std::min<size_t>((size_t)c.gpus, samples.size()) : c.gpus;
+        if (!fork_ranks(n_ranks, rk, &code, !batch)) {
+            run.close();
+            return batch ? end_batch(deal, code, samples.size(), "placed") : code;
+        }
         if (rk.rank > 0) c.quiet = true;
     }
 
     // ------------------------------------------------------------------------------------------------ samples
     run.dev = rank_device(rk);
     check(pmx_ctx_create(run.dev, &run.ctx), "opening the GPU");
-    run.dist = join_ranks(run.ctx, rk);
+    if (!batch) run.dist = join_ranks(run.ctx, rk);
     check(pmx_place_create(run.ctx, run.idx, &run.pl), "uploading the index");
     int rc = 0;
-    if (c.batch.empty()) run_sample(c, stop, run);
+    if (!batch) run_sample(c, stop, run);
     else {
-        // runBatchPlacement (src/main.cpp:1464-1666): the samples of the batch file one after the other against the index
-        // that stays on the device; one line per sample on stderr, a failed sample does not stop the batch
-        const std::vector<BatchEntry> samples = read_batch_file(c.batch);
-        if (samples.empty()) die("No samples found in batch file");
-        fprintf(stderr, "Batch mode: %zu samples\n", samples.size());
-        int ok = 0, failed = 0;
-        for (size_t i = 0; i < samples.size(); ++i) {
+        // runBatchPlacement (src/main.cpp:1464-1666): the samples this process takes, one after the other against the index
+        // that stays on the device; one line per sample on stderr, a failed sample does not stop the batch.  A rank exits 0
+        // whatever its samples did: the counts are in the shared block, and the parent reports them
+        run_dealt(samples, *deal, [&](const BatchEntry& e) {
             Config sc = c;
-            sc.reads1 = samples[i].reads1; sc.reads2 = samples[i].reads2; sc.output = samples[i].prefix; sc.quiet = true;
-            const size_t slash = sc.output.find_last_of('/');
-            if (slash != std::string::npos && slash > 0) mkdirs(sc.output.substr(0, slash));
-            const auto t0 = std::chrono::steady_clock::now();
-            std::string node, err;
-            try { node = run_sample(sc, stop, run); }
-            catch (const Fatal& f) { err = f.msg; }
-            const long long ms = (long long)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count();
-            if (!err.empty()) {
-                fprintf(stderr, "[%zu/%zu] %s -> %s (%lldms)\n", i + 1, samples.size(), sc.output.c_str(), err == "No placement found" ? "NO PLACEMENT" : ("failed: " + err).c_str(), ms);
-                ++failed;
-            } else {
-                fprintf(stderr, "[%zu/%zu] %s -> %s (%lldms)\n", i + 1, samples.size(), sc.output.c_str(), node.c_str(), ms);
-                ++ok;
-            }
-        }
-        fprintf(stderr, "Batch complete: %d placed, %d failed\n", ok, failed);
-        rc = failed ? 1 : 0;
+            sc.reads1 = e.reads1; sc.reads2 = e.reads2; sc.output = e.prefix; sc.quiet = true;
+            return run_sample(sc, stop, run);
+        });
+        if (rk.world == 1) rc = end_batch(deal, 0, samples.size(), "placed");
     }
     run.close();
     return rc;
