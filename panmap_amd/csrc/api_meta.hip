@@ -1069,9 +1069,15 @@ EmRound::EmRound(EmStage* stage, const std::vector<int>& cols) : S(stage), m(sta
     PMX_HIP(hipMemcpyAsync(d_ctl.p, &h_ctl, sizeof(h_ctl), hipMemcpyHostToDevice, st));
     d_done = &d_ctl.p->done;
     // the in-order sums of the small kernels read a copy of the vector in LDS (2 x n_cols doubles at most); beyond 160 KB a
-    // scratch vector in global memory stands in
+    // scratch vector in global memory stands in.  The 160 KB of a workgroup hold the kernels' static __shared__ words too
+    // (s_alpha and s_sum of k_em_extrapolate): at exactly 10,240 columns the dynamic part alone fills them, and a launch
+    // that asks for more is not refused with an error: the queue aborts (HSA_STATUS_ERROR_INVALID_ALLOCATION)
     const size_t em_lds = 2 * sizeof(double) * (size_t)n_cols;
-    if (em_lds > (size_t)160 * 1024) { d_em_work.alloc(2 * (size_t)n_cols); em_work = d_em_work.p; }
+    hipFuncAttributes fa_norm, fa_extra;
+    PMX_HIP(hipFuncGetAttributes(&fa_norm, (const void*)k_em_normalize));
+    PMX_HIP(hipFuncGetAttributes(&fa_extra, (const void*)k_em_extrapolate));
+    const size_t em_static = std::max<size_t>({fa_norm.sharedSizeBytes, fa_extra.sharedSizeBytes, 2 * sizeof(double)});
+    if (em_lds + em_static > (size_t)160 * 1024) { d_em_work.alloc(2 * (size_t)n_cols); em_work = d_em_work.p; }
     else if (em_lds > (size_t)64 * 1024) {
         PMX_HIP(hipFuncSetAttribute((const void*)k_em_normalize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));
         PMX_HIP(hipFuncSetAttribute((const void*)k_em_extrapolate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)em_lds));

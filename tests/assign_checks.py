@@ -206,9 +206,6 @@ class CraftedTree:
 
 def _make_tree(name, parent, seqs, extra_hashes, rng):
     n = len(parent)
-    children = [[] for _ in range(n)]
-    for v in range(1, n):
-        children[int(parent[v])].append(v)
     end = np.arange(n)
     for v in range(n - 1, 0, -1):
         end[parent[v]] = max(end[parent[v]], end[v])
@@ -250,7 +247,17 @@ def _make_tree(name, parent, seqs, extra_hashes, rng):
     for h in extra_hashes:                                       # seedmers only junctions and mutated reads have
         if h not in seen and rng.random() < 0.3:
             toggle(pick(), (h, int(rng.integers(2))))
-    # one DFS turns the plan into count changes: the oriented index and the plain one (counts of both orientations added)
+    return tree_from_plan(name, parent, plan, rng)
+
+
+def tree_from_plan(name, parent, plan, rng):
+    """plan: node -> {(hash, orientation): "toggle" | "bump"}; a toggle makes an absent seedmer present with a count of 1 to 3
+    and a present one absent, a bump adds one to a present one's count.  One DFS turns the plan into count changes: the
+    oriented index and the plain one (counts of both orientations added)"""
+    n = len(parent)
+    children = [[] for _ in range(n)]
+    for v in range(1, n):
+        children[int(parent[v])].append(v)
     state = {}
     o_rows, p_rows = [[] for _ in range(n)], [[] for _ in range(n)]
 
@@ -348,6 +355,24 @@ def rsv_restated(arrays, discard, dust=100.0):
 
 
 # ------------------------------------------------------------------------------------------------ comparison
+def flat(lists):
+    """seedmer lists -> (offsets, hashes, orientations)"""
+    off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
+    return off, np.array([h for x in lists for h, _ in x], np.uint64), np.array([int(v) for x in lists for _, v in x], np.uint8)
+
+
+def check_against_oracle(arrays, R, nodes):
+    """the restatement's presence and scores at `nodes` against oracle_meta's tree-walking ones"""
+    off, h, rev = flat(R.lists)
+    read_hashes = set(h.tolist())
+    for node in nodes:
+        counts = om.node_seed_counts(arrays, int(node), read_hashes)
+        for u, key in enumerate(R.uniq.tolist()):
+            c = counts.get(key, [0, 0])
+            assert (c[0] > 0, c[1] > 0) == tuple(R.presence[u, node]), (node, key)
+        assert np.array_equal(om.read_scores_np(counts, off, h, rev), R.scores[:, node]), node
+
+
 def check_result(res, want, parent, heads, label=""):
     """a Meta.assign result against the restatement, read by read"""
     assert np.array_equal(res.merged, want.merged), label

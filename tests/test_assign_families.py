@@ -11,20 +11,7 @@ from conftest import GOLDEN
 from oracle import oracle_meta as om
 
 
-def _flat(lists):
-    off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
-    return off, np.array([h for x in lists for h, _ in x], np.uint64), np.array([int(v) for x in lists for _, v in x], np.uint8)
-
-
-def _check_against_oracle(arrays, R, nodes):
-    off, h, rev = _flat(R.lists)
-    read_hashes = set(h.tolist())
-    for node in nodes:
-        counts = om.node_seed_counts(arrays, int(node), read_hashes)
-        for u, key in enumerate(R.uniq.tolist()):
-            c = counts.get(key, [0, 0])
-            assert (c[0] > 0, c[1] > 0) == tuple(R.presence[u, node]), (node, key)
-        assert np.array_equal(om.read_scores_np(counts, off, h, rev), R.scores[:, node]), node
+_check_against_oracle = ac.check_against_oracle
 
 
 def test_crafted_family_reaches_every_case():
