@@ -416,8 +416,8 @@ int pmx_align_dp_batch(pmx_ctx *ctx, pmx_aligner *al, const uint8_t *seqs, const
  *   WAVE_LONG        one request per wave on the layout of the long-read launch (dp_fast LDS copy unless no_dp_fast).
  *   WAVE_GENERAL     the same on the general layout of the wave tiers (no dp_fast: the anti-diagonal kernel on the layout's arrays).
  *   SW_LL            sw_ll (ksw_ll_i16) on the long-read layout: score in .score, .qe / .te / .ok as it leaves them.
- * max_read_len / n_segs: what the layouts are planned from, by the planners the stage itself uses.  no_rows_dp / no_dp_fast: the
- * PMX_ALIGN_NO_ROWS_DP / PMX_ALIGN_NO_DP_FAST switches as arguments.  caps[0] receives the capacities planned (SERVE: class 2,
+ * max_read_len / n_segs: what the layouts are planned from, by the planners the stage itself uses.  no_rows_dp: never the
+ * row-by-row DP; no_dp_fast: no LDS copy of small DPs' arrays (the stage itself passes 0 for both).  caps[0] receives the capacities planned (SERVE: class 2,
  * caps[1] class 1) also when n == 0; a request beyond them comes back served = 0.  CIGARs go to cigar_arena (arena_cap words;
  * n * caps[0].max_cigar always suffices) at out[i].cigar_off.  path_taken: PMX_DP_PATH_* of the implementation that ran. */
 #define PMX_DP_PROBE_SERVE 0

@@ -425,13 +425,13 @@ __device__ void sketch_segment_lanes(Work& W, const uint8_t* seq, int len, int w
 
 PMX_HDN void sketch_segment(Work& W, Ptr<const uint8_t> seq, int len, int w, int k, uint32_t rid) {
 #if PMX_W == 64 && defined(__HIP_DEVICE_COMPILE__)
-    if ((k & 1) && w >= 1 && w <= 20 && len >= 64 && !W.sk_no_lane_ring) {   // (sr: w = 11, map-ont: 10, map-hifi: 19)
+    if ((k & 1) && w >= 1 && w <= 20 && len >= 64) {   // (sr: w = 11, map-ont: 10, map-hifi: 19)
         if (w <= 12) sketch_segment_lanes<12>(W, seq, len, w, k, rid);
         else sketch_segment_lanes<20>(W, seq, len, w, k, rid);
         wave_sync();
         return;
     }
-    if (w >= 1 && w <= 64 && !W.sk_no_lane_ring) {
+    if (w >= 1 && w <= 64) {
         sketch_segment_wave(W, seq, len, w, k, rid);
         return;
     }

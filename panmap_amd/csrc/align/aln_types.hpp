@@ -497,8 +497,7 @@ struct Work {
     // DP work actually run for this pair by the wave models / host (statistics only: GCUPS in bench.py)
     uint32_t dp_run_calls;
     uint64_t dp_run_cells;
-    int sk_no_lane_ring;   // wave models: 1 = sketch with the ring in LDS (comparison / fallback switch)
-    int no_rows_dp;        // wave-per-read kernels: 1 = never the row-by-row DP (aln_ksw_rows.hpp; comparison switch)
+    int no_rows_dp;        // wave-per-read kernels: 1 = never the row-by-row DP (aln_ksw_rows.hpp; pmx_align_dp_probe's argument)
     int mv_ready;          // mv[] / n_mv already hold this pair's minimizers (handed over by the thread-per-pair kernel)   // [0..11] phases, [16..23] sub-phases of seeding / chaining / align1 (PMX_ALIGN_PROF)
 };
 

@@ -25,7 +25,6 @@ __global__ void __launch_bounds__(64, 2) k_align_dp_probe(DpProbeArgs A) {
         bind_work(W, A.layout, fast, slow);
         W.n_segs = 1;
         W.prof = nullptr;
-        W.sk_no_lane_ring = 0;
         W.no_rows_dp = A.no_rows_dp;
         W.mv_ready = 0;
         W.dp_path = 0;

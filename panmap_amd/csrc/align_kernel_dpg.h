@@ -35,7 +35,7 @@ struct DpgArgs {
     unsigned long long* stats;  // [0] DP calls, [1] cells
     unsigned long long* prof;   // diagnostic (NULL = off): wave cycles of [0] set-up, [1] fill, [2] replay, [3] traceback + hand-over, [4] tasks, [5] fill steps
     uint32_t n_entries;         // entries behind dp_req_base (an id beyond it is counted in counts[15] and skipped)
-    int shadow;                 // diagnostic: results go to dp_res_base (a copy), the requests stay posted for the wave service
+    int shadow;                 // pmx_align_dp_batch: the requests stay posted (not marked served), so that the launch can be repeated
 };
 
 __global__ void k_dpg_collect(DpgArgs D);

@@ -11,19 +11,12 @@
 using namespace pmx;
 using namespace pmx::aln;
 
-// pair order from the read order: first mates (even read indices) of the read set's locality order -> pair indices
-struct IsEvenRead {
-    __host__ __device__ bool operator()(const uint32_t& r) const { return (r & 1u) == 0u; }
-};
 // pair key = locality key of mate 1 (fragment start) in the high half, of mate 2 (fragment end) in the low half
 __global__ void k_pair_keys(const uint32_t* __restrict__ read_key, int64_t n_pairs, uint64_t* key, uint32_t* idx) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pairs; i += (int64_t)gridDim.x * blockDim.x) {
         key[i] = (uint64_t)read_key[2 * i] << 32 | (uint64_t)read_key[2 * i + 1];
         idx[i] = (uint32_t)i;
     }
-}
-__global__ void k_halve(const uint32_t* __restrict__ in, int64_t n, uint32_t* out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = in[i] >> 1;
 }
 
 // Distinct-pair map (readset_pair_map): a pair's content is its two 64-byte read records (bases, ambiguity words, length),
@@ -199,15 +192,6 @@ void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st) {
     hipLaunchKernelGGL(k_pair_reps, dim3(grid), dim3(256), 0, st, rs->pd_idx2.p, rs->pd_gs.p, n, rs->pd_rep.p, rs->pd_mult.p);
     PMX_HIP(hipGetLastError());
     rs->has_pair_map = true;
-}
-
-const uint32_t* pair_order_mate1(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* read_order) {
-    const int64_t n_items = rs->n / 2;
-    al->pp_idx.ensure((size_t)rs->n); al->pp_idx2.ensure((size_t)n_items + 1);
-    PMX_ROCPRIM(al->pp_tmp, select, read_order, al->pp_idx.p, al->pp_idx2.p + n_items, (size_t)rs->n, IsEvenRead(), ctx->stream);
-    hipLaunchKernelGGL(k_halve, dim3((unsigned)std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
-                       al->pp_idx.p, n_items, al->pp_idx2.p);
-    return al->pp_idx2.p;
 }
 
 int64_t pair_select_reps(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* order, int64_t n_pairs) {

@@ -100,18 +100,13 @@ namespace {
 // Every switch the stage reads (device/pmx_options.hpp), parsed here and nowhere below.
 struct AlignSwitches {
     static bool on(OptId id) { return pmx::opt_str(id) != nullptr; }
-    const bool no_tier1 = on(O_ALIGN_NO_TIER1), no_tpp = on(O_ALIGN_NO_TPP), no_compact = on(O_ALIGN_NO_COMPACT);
-    const bool no_dp_service = on(O_ALIGN_NO_DP_SERVICE), no_dp_group = on(O_ALIGN_NO_DP_GROUP), dp_one_class = on(O_ALIGN_DP_ONE_CLASS);
-    const bool no_mv_handover = on(O_ALIGN_NO_MV_HANDOVER), no_lds_ring = on(O_ALIGN_NO_LDS_RING), no_lane_ring = on(O_ALIGN_NO_LANE_RING);
-    const bool no_rows_dp = on(O_ALIGN_NO_ROWS_DP), no_dp_fast = on(O_ALIGN_NO_DP_FAST), no_work_queue = on(O_ALIGN_NO_WORK_QUEUE);
-    const bool no_pair_sort = on(O_ALIGN_NO_PAIR_SORT), pair_key1 = on(O_ALIGN_PAIR_KEY1), no_dedup = on(O_ALIGN_NO_DEDUP);
+    const bool no_tpp = on(O_ALIGN_NO_TPP), no_compact = on(O_ALIGN_NO_COMPACT), no_dedup = on(O_ALIGN_NO_DEDUP);
     const bool compact_pos32 = on(O_ALIGN_COMPACT_POS32), compact_fused = on(O_ALIGN_COMPACT_FUSED), no_multi = on(O_ALIGN_NO_MULTI), no_simple = on(O_ALIGN_NO_SIMPLE);
-    const bool resident_grid = on(O_ALIGN_RESIDENT_GRID), dpg_no_serve = on(O_DPG_NO_SERVE);
     const bool prof = on(O_ALIGN_PROF), verbose = on(O_ALIGN_VERBOSE);                                                    // diagnostics
-    const bool dp_hist = on(O_DP_HIST), dpg_prof = on(O_DPG_PROF), dpg_shadow = on(O_DPG_SHADOW), dpg_check_list = on(O_DPG_CHECK_LIST);
+    const bool dp_hist = on(O_DP_HIST), dpg_prof = on(O_DPG_PROF);
     int waves_per_simd = 4;
     int tpp_waves = 16;                 // 4 per SIMD: what k_align_reads_tpp's register allocation targets (PMX_TPP_OCC)
-    int dpg_waves = 8;
+    int dpg_waves = kDpgWavesDefault;
     int compact_waves = 0, cseed_waves = 0;   // waves per CU of a resident grid; 0 = one workgroup per 64 pairs
     int test_max_cigar = 0;             // test hook: cap the CIGAR operations per region in EVERY tier, so that gapped alignments overflow and
                                         // the boundary's handling of invalid records can be exercised (tests/test_align_gpu.py)
@@ -170,15 +165,15 @@ struct AlignStage {
     const int64_t n_items;      // an odd trailing read is ignored (src/mm_align.c:372)
     const int n_segs;
     const AlignKernel kern, kern_t1;
-    AlignArgs base{};           // reads, reference, options, outputs, stats / edits / prof, paired, revcomp_mate2, sk_no_lane_ring, no_rows_dp,
-                                // the first mv_epoch of the call, and (plan_tier0) the thread-per-pair arena; every other field zero
+    AlignArgs base{};           // reads, reference, options, outputs, stats / edits / prof, paired, revcomp_mate2, the first mv_epoch
+                                // of the call, and (plan_tier0) the thread-per-pair arena; every other field zero
     Layout general, compact;    // wave tiers: general capacities; all-LDS layout (typical short-read pairs)
     // thread-per-pair tier and its DP service (plan_tier0)
     Layout tpp_layout;
     DpServePlan dpp;            // the wave service's two classes
     size_t tpp_raw_stride = 0, tpp_lds_bytes = 0;
     int64_t tpp_max_grid = 0;
-    bool use_dp_service = false, use_compact = false, dpg_ok = false;
+    bool use_compact = false, dpg_ok = false;
     DpgArgs dpg_base;           // scoring parameters of the grouped service (dpg_setup)
     // launch order (launch_order)
     bool dedup = false;         // distinct-pair map in use: the compact tier and the tail run representatives only
@@ -204,9 +199,7 @@ struct AlignStage {
     void tail(const uint32_t* order, int64_t n_t0);
     // diagnostics (each behind its switch: they download and print)
     void print_dp_requests(int round, int64_t n_dp);
-    void check_dpg_list(int64_t n_ent, uint32_t n_entries);
     void print_dpg_prof();
-    void compare_dpg_shadow(int round, int64_t n_dp);
     void print_compact_prof();
     void print_phase_prof(bool tier1_fits);
 };
@@ -254,8 +247,6 @@ bool AlignStage::setup(int revcomp_mate2, uint64_t cigar_cap) {
     base.stats = al->stats.p;
     base.edits = al->want_edits ? al->edits.p : nullptr;
     base.prof = sw.prof ? al->prof.p : nullptr;
-    base.sk_no_lane_ring = sw.no_lane_ring ? 1 : 0;
-    base.no_rows_dp = sw.no_rows_dp ? 1 : 0;
     base.mv_epoch = ++al->mv_epoch;
     general = hooked(plan_general_layout((int)rs->max_len, n_segs, al->opt));
     compact = hooked(plan_layout_compact((int)rs->max_len, n_segs, al->opt));
@@ -277,7 +268,7 @@ void AlignStage::launch_wave(AlignArgs A, AlignKernel kfn, const Layout& L, int6
     int64_t grid = (int64_t)ctx->n_cu * waves_per_cu;
     // a few thousand pairs: one workgroup each, so that the hardware hands a free slot the next pair (with a resident
     // grid and a strided loop a wave that drew two slow pairs decides the launch)
-    if (n_work <= 16384 && !sw.resident_grid) grid = n_work;
+    if (n_work <= 16384) grid = n_work;
     if (grid > n_work) grid = n_work;
     if (max_grid > 0 && grid > max_grid) grid = max_grid;
     A.layout = L;
@@ -346,14 +337,12 @@ void AlignStage::long_reads() {
     // wave's HBM slab whatever the LDS budget, and the kernel is bound by the latency of those accesses: what counts is
     // resident waves (16 per CU: 32.4 k reads/s, 8 per CU: 21.1 k) and that the DPs -- nearly all a few hundred bases
     // wide -- run on a small LDS copy of their arrays (plan_layout dp_fast_tlen)
-    const Layout g1 = hooked(plan_long_reads_layout((int)rs->max_len, n_segs, al->opt, sw.no_dp_fast));
+    const Layout g1 = hooked(plan_long_reads_layout((int)rs->max_len, n_segs, al->opt, false));
     al->retry_list.ensure((size_t)n_items);
     timer_begin(ctx, "align_dom");
     AlignArgs A = base;
-    if (!sw.no_work_queue) {   // the waves draw their reads from a counter
-        PMX_HIP(hipMemsetAsync(al->retry_count.p + 3, 0, sizeof(unsigned long long), stream));
-        A.work_queue = al->retry_count.p + 3;
-    }
+    PMX_HIP(hipMemsetAsync(al->retry_count.p + 3, 0, sizeof(unsigned long long), stream));   // the waves draw their reads from a counter
+    A.work_queue = al->retry_count.p + 3;
     launch_wave(A, kern, g1, n_items, nullptr, general.tb_cap > g1.tb_cap ? al->retry_list.p : nullptr, al->slow2);
     timer_end(ctx, "align_dom", 1);
     int64_t n_retry = 0, unused = 0;
@@ -380,41 +369,34 @@ void AlignStage::plan_tier0() {
     base.tpp.base = al->slab0.p;
     base.tpp.wave_stride = (uint32_t)tpp_wave_stride;
     dpp = plan_dp_serve(ctx, (int)rs->max_len, n_segs, al->opt);
-    dpg_ok = dpg_setup(al->opt, dpg_base) && !sw.no_dp_group;
-    use_dp_service = !sw.no_dp_service;
-    if (use_dp_service) {
-        al->dp_req.ensure((size_t)n_items * PMX_DP_REQ_PER_PASS * sizeof(DpReq));
-        al->dp_res.ensure((size_t)n_items * PMX_DP_MAX_CALLS);
-        al->dp_ncached.ensure((size_t)n_items);
-        al->dp_slot_pairs.ensure((size_t)n_items);
-        al->dp_list_a.ensure((size_t)n_items);
-        al->dp_list_b.ensure((size_t)n_items);
-        al->slow.ensure(dpp.dp_stride * (size_t)dpp.dp_max_grid);
-        al->slow2.ensure(dpp.dps_stride * (size_t)dpp.dps_max_grid);
-        if (!sw.no_mv_handover)
-            al->mv_handover.ensure((size_t)std::min<int64_t>(std::min<int64_t>(n_items, UINT32_MAX - 1), 131072) * ((size_t)tpp_layout.caps.max_mini + 1u));
-    }
+    dpg_ok = dpg_setup(al->opt, dpg_base);
+    al->dp_req.ensure((size_t)n_items * PMX_DP_REQ_PER_PASS * sizeof(DpReq));
+    al->dp_res.ensure((size_t)n_items * PMX_DP_MAX_CALLS);
+    al->dp_ncached.ensure((size_t)n_items);
+    al->dp_slot_pairs.ensure((size_t)n_items);
+    al->dp_list_a.ensure((size_t)n_items);
+    al->dp_list_b.ensure((size_t)n_items);
+    al->slow.ensure(dpp.dp_stride * (size_t)dpp.dp_max_grid);
+    al->slow2.ensure(dpp.dps_stride * (size_t)dpp.dps_max_grid);
+    al->mv_handover.ensure((size_t)std::min<int64_t>(std::min<int64_t>(n_items, UINT32_MAX - 1), 131072) * ((size_t)tpp_layout.caps.max_mini + 1u));
     // minimizer window ring in LDS when 16 waves per CU still fit (12 B x w x 64 lanes per wave)
     tpp_lds_bytes = (size_t)al->opt.w * 64 * 12;
-    if (tpp_lds_bytes * (size_t)sw.tpp_waves > (size_t)150 * 1024 || sw.no_lds_ring) tpp_lds_bytes = 0;
+    if (tpp_lds_bytes * (size_t)sw.tpp_waves > (size_t)150 * 1024) tpp_lds_bytes = 0;
 }
 
 // Launch order of the first pass: pairs sorted by a locality key; with the compact tier and enough depth, the
 // representatives of the distinct pairs in that order (sets n_launch and dedup).  nullptr = input order.
 const uint32_t* AlignStage::launch_order() {
+    // the read set's locality order (shared with the seeding stage)
+    const uint32_t* read_order = readset_locality_order(ctx, rs);
     const uint32_t* order = nullptr;
-    if (!sw.no_pair_sort) {
-        // the read set's locality order (shared with the seeding stage); pairs: the even reads of it, in that order
-        const uint32_t* read_order = readset_locality_order(ctx, rs);
-        if (read_order && !paired) order = read_order;
-        // pairs by (key of mate 1, key of mate 2): the 64 pairs of a wave then start AND end within a few bases
-        // of each other -- same anchors, same overlap of the mates, same trip counts in every per-lane loop
-        // (round 3, 10M reads: k_align_compact16 28.2 -> 25.0 ms against the order by mate 1 alone, which
-        // PMX_ALIGN_PAIR_KEY1 still selects; the extra 64-bit sort of the pairs is ~1 ms of that)
-        // (made ahead of time by pmx_readset_order_pairs when the host asked for it: then only an event to wait for)
-        else if (read_order && !sw.pair_key1) order = readset_pair_order(ctx, rs, nullptr);
-        else if (read_order) order = pair_order_mate1(ctx, al, rs, read_order);
-    }
+    if (read_order && !paired) order = read_order;
+    // pairs by (key of mate 1, key of mate 2): the 64 pairs of a wave then start AND end within a few bases
+    // of each other -- same anchors, same overlap of the mates, same trip counts in every per-lane loop
+    // (round 3, 10M reads: k_align_compact16 28.2 -> 25.0 ms against the order by mate 1 alone; the extra
+    // 64-bit sort of the pairs is ~1 ms of that)
+    // (made ahead of time by pmx_readset_order_pairs when the host asked for it: then only an event to wait for)
+    else if (read_order) order = readset_pair_order(ctx, rs, nullptr);
     // Distinct pairs (readset_pair_map): the compact tier and the tail run one representative of every set of equal
     // pairs, in launch order, and k_pair_fanout hands the copies their results at the end (10M bench reads: 18 % of
     // the pairs are copies).  PMX_ALIGN_NO_DEDUP: every pair.
@@ -547,18 +529,14 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
 // the pairs for the wave tiers and the DP requests are counted in, the thread-per-pair layout.
 AlignArgs AlignStage::tail_args() {
     AlignArgs T = base;
-    if (use_dp_service) {
-        PMX_HIP(hipMemsetAsync(al->dp_ncached.p, 0, sizeof(uint32_t) * (size_t)n_items, stream));
-        T.dp_req_base = al->dp_req.p; T.dp_res_base = al->dp_res.p; T.dp_ncached = al->dp_ncached.p;
-        T.dp_slot_pairs = al->dp_slot_pairs.p;
-        T.dp_slot_cap = (uint32_t)std::min<int64_t>(n_items, UINT32_MAX - 1);
-        if (!sw.no_mv_handover) {
-            T.mv_stride = (uint32_t)tpp_layout.caps.max_mini + 1u;
-            T.mv_slots = (uint32_t)std::min<int64_t>(T.dp_slot_cap, 131072);
-            T.mv_handover = al->mv_handover.p;
-            T.mv_epoch = ++al->mv_epoch;
-        }
-    }
+    PMX_HIP(hipMemsetAsync(al->dp_ncached.p, 0, sizeof(uint32_t) * (size_t)n_items, stream));
+    T.dp_req_base = al->dp_req.p; T.dp_res_base = al->dp_res.p; T.dp_ncached = al->dp_ncached.p;
+    T.dp_slot_pairs = al->dp_slot_pairs.p;
+    T.dp_slot_cap = (uint32_t)std::min<int64_t>(n_items, UINT32_MAX - 1);
+    T.mv_stride = (uint32_t)tpp_layout.caps.max_mini + 1u;
+    T.mv_slots = (uint32_t)std::min<int64_t>(T.dp_slot_cap, 131072);
+    T.mv_handover = al->mv_handover.p;
+    T.mv_epoch = ++al->mv_epoch;
     T.tpp_ring_w = tpp_lds_bytes ? al->opt.w : 0;
     T.dp_count = al->retry_count.p + 1;
     T.retry_list = al->retry_list2.p;
@@ -596,26 +574,18 @@ void AlignStage::dp_round(const AlignArgs& T, int round, int64_t n_dp, const uin
         DpgArgs DG = dpg_base;
         DG.dp_req_base = al->dp_req.p; DG.dp_res_base = al->dp_res.p; DG.stats = base.stats;
         DG.n_entries = (uint32_t)std::min<size_t>(al->dp_req.n / sizeof(DpReq), UINT32_MAX);
-        if (sw.dpg_shadow) {   // diagnostic: both services run, results compared
-            al->dpg_shadow.ensure((size_t)n_items * PMX_DP_MAX_CALLS);
-            PMX_HIP(hipMemsetAsync(al->dpg_shadow.p, 0xee, sizeof(DpRes) * (size_t)n_items * PMX_DP_MAX_CALLS, stream));
-            DG.dp_res_base = al->dpg_shadow.p; DG.stats = nullptr; DG.shadow = 1;
-        }
         if (sw.dpg_prof) { al->dpg_prof.ensure(8); PMX_HIP(hipMemsetAsync(al->dpg_prof.p, 0, 64, stream)); DG.prof = al->dpg_prof.p; }
-        dpg_launch(ctx, al, DG, n_dp, cur, sw.dpg_waves, !sw.dpg_no_serve);
-        if (sw.dpg_check_list) check_dpg_list(n_dp * PMX_DP_REQ_PER_PASS, DG.n_entries);
+        dpg_launch(ctx, al, DG, n_dp, cur, sw.dpg_waves, true);
         if (sw.dpg_prof) print_dpg_prof();
-        if (!sw.dpg_shadow && !sw.dpg_no_serve) {
-            // what did the grouped service leave?  Nothing: no launch of the wave service.  A handful (a side beyond 128
-            // bases on 150 bp reads: ~8 requests per 400k pairs): those pairs go to the wave-per-pair tier instead
-            uint32_t left[2] = {0, 0};
-            PMX_HIP(hipMemcpyAsync(left, al->dpg_counts.p + PMX_DPG_NO_BUCKET - 1, sizeof(left), hipMemcpyDeviceToHost, stream));
-            PMX_HIP(hipStreamSynchronize(stream));
-            if (left[0] + left[1] == 0) wave_service = false;
-            else if ((int64_t)left[0] + left[1] <= sw.dpg_left_few) {
-                hipLaunchKernelGGL(k_dpg_refuse_left, dim3((unsigned)std::min<int64_t>((n_dp * PMX_DP_REQ_PER_PASS + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, stream, DG);
-                wave_service = false;
-            }
+        // what did the grouped service leave?  Nothing: no launch of the wave service.  A handful (a side beyond 128
+        // bases on 150 bp reads: ~8 requests per 400k pairs): those pairs go to the wave-per-pair tier instead
+        uint32_t left[2] = {0, 0};
+        PMX_HIP(hipMemcpyAsync(left, al->dpg_counts.p + PMX_DPG_NO_BUCKET - 1, sizeof(left), hipMemcpyDeviceToHost, stream));
+        PMX_HIP(hipStreamSynchronize(stream));
+        if (left[0] + left[1] == 0) wave_service = false;
+        else if ((int64_t)left[0] + left[1] <= sw.dpg_left_few) {
+            hipLaunchKernelGGL(k_dpg_refuse_left, dim3((unsigned)std::min<int64_t>((n_dp * PMX_DP_REQ_PER_PASS + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, stream, DG);
+            wave_service = false;
         }
     }
     if (wave_service) {
@@ -623,10 +593,9 @@ void AlignStage::dp_round(const AlignArgs& T, int round, int64_t n_dp, const uin
         A.dp_req_base = al->dp_req.p; A.dp_res_base = al->dp_res.p;
         A.n_items = n_dp;
         A.worklist = cur;
-        launch_dp_serve(A, dpp, !sw.dp_one_class, al->slow.p, al->slow2.p, stream);
+        launch_dp_serve(A, dpp, true, al->slow.p, al->slow2.p, stream);
     }
     PMX_HIP(hipGetLastError());
-    if (dpg_ok && sw.dpg_shadow) compare_dpg_shadow(round, n_dp);
     launch_tpp(T, round, n_dp, cur, next, nullptr);
 }
 
@@ -713,24 +682,6 @@ void AlignStage::print_dp_requests(int round, int64_t n_dp) {
         fprintf(stderr, "  0x%02x %6d %6d %8d %8ld %10ld\n", std::get<0>(kv.first), std::get<1>(kv.first), std::get<2>(kv.first), std::get<3>(kv.first), kv.second.first, kv.second.second);
 }
 
-// diagnostic (PMX_DPG_CHECK_LIST): the sorted request list against the bucket counts
-void AlignStage::check_dpg_list(int64_t n_ent, uint32_t n_entries) {
-    std::vector<uint32_t> k2((size_t)n_ent), i2((size_t)n_ent), cn(16);
-    PMX_HIP(hipStreamSynchronize(stream));
-    PMX_HIP(hipMemcpy(k2.data(), al->dpg_keys2.p, (size_t)n_ent * 4, hipMemcpyDeviceToHost));
-    PMX_HIP(hipMemcpy(i2.data(), al->dpg_ids2.p, (size_t)n_ent * 4, hipMemcpyDeviceToHost));
-    PMX_HIP(hipMemcpy(cn.data(), al->dpg_counts.p, 64, hipMemcpyDeviceToHost));
-    long unsorted = 0, bad_id = 0, cnt[16] = {0};
-    for (int64_t i = 0; i < n_ent; ++i) {
-        if (i && k2[(size_t)i] < k2[(size_t)i - 1]) ++unsorted;
-        if (i2[(size_t)i] >= n_entries) ++bad_id;
-        ++cnt[(k2[(size_t)i] >> 8) & 15];
-    }
-    fprintf(stderr, "[dpg list] %lld entries, %ld out of order, %ld ids out of range; buckets (device/host):", (long long)n_ent, unsorted, bad_id);
-    for (int b = 0; b < 16; ++b) fprintf(stderr, " %u/%ld", cn[(size_t)b], cnt[b]);
-    fprintf(stderr, "\n");
-}
-
 // diagnostic (PMX_DPG_PROF): the grouped service's phase cycles
 void AlignStage::print_dpg_prof() {
     unsigned long long h[8];
@@ -738,51 +689,6 @@ void AlignStage::print_dpg_prof() {
     PMX_HIP(hipStreamSynchronize(stream));
     const double t = (double)std::max<unsigned long long>(h[4], 1);
     fprintf(stderr, "[dpg prof] %llu tasks; cycles per task (lane 0 of the wave): set-up %.0f fill %.0f replay %.0f traceback %.0f; fill steps %.1f\n", h[4], h[0] / t, h[1] / t, h[2] / t, h[3] / t, h[5] / t);
-}
-
-// diagnostic (PMX_DPG_SHADOW): the grouped service wrote its results to a copy; compare them with the wave service's
-void AlignStage::compare_dpg_shadow(int round, int64_t n_dp) {
-    const size_t n_ent = (size_t)n_dp * PMX_DP_REQ_PER_PASS, n_res = (size_t)n_items * PMX_DP_MAX_CALLS;
-    std::vector<uint32_t> keys(n_ent), ids(n_ent);
-    std::vector<DpRes> a(n_res), b(n_res);
-    std::vector<DpReq> rq((size_t)n_items * PMX_DP_REQ_PER_PASS);
-    PMX_HIP(hipStreamSynchronize(stream));
-    PMX_HIP(hipMemcpy(keys.data(), al->dpg_keys.p, n_ent * 4, hipMemcpyDeviceToHost));
-    PMX_HIP(hipMemcpy(ids.data(), al->dpg_ids.p, n_ent * 4, hipMemcpyDeviceToHost));
-    PMX_HIP(hipMemcpy(a.data(), al->dp_res.p, n_res * sizeof(DpRes), hipMemcpyDeviceToHost));
-    PMX_HIP(hipMemcpy(b.data(), al->dpg_shadow.p, n_res * sizeof(DpRes), hipMemcpyDeviceToHost));
-    // (the requests were marked served by the wave service: their headers are intact apart from `call`, which the
-    //  collect pass read before; the call index is recovered from the result that carries the request's key)
-    long n_cmp = 0, n_bad = 0, shown = 0;
-    for (size_t i = 0; i < n_ent; ++i) {
-        if ((keys[i] >> 8) >= PMX_DPG_NO_BUCKET) continue;
-        const size_t slot = ids[i] / PMX_DP_REQ_PER_PASS;
-        for (int c = 0; c < PMX_DP_MAX_CALLS; ++c) {
-            const DpRes& y = b[slot * PMX_DP_MAX_CALLS + c];
-            if (y.key == 0xeeeeeeeeu) continue;   // not written by the grouped service
-            const DpRes& x = a[slot * PMX_DP_MAX_CALLS + c];
-            ++n_cmp;
-            bool same = x.key == y.key;
-            if (same && x.key != 0xffffffffu) {
-                same = memcmp(&x.ez, &y.ez, sizeof(Ez)) == 0;
-                for (int k = 0; same && k < x.ez.n_cigar && k < PMX_DP_MAX_CIGAR; ++k) same = x.cigar[k] == y.cigar[k];
-            }
-            if (!same) {
-                ++n_bad;
-                if (shown++ < 12) {
-                    fprintf(stderr, "[dpg shadow] slot %zu call %d key %08x/%08x\n  wave : max %u zd %d maxq %d maxt %d mqe %d mqe_t %d mte %d mte_q %d score %d ncig %d reach %d\n  group: max %u zd %d maxq %d maxt %d mqe %d mqe_t %d mte %d mte_q %d score %d ncig %d reach %d\n",
-                            slot, c, x.key, y.key, x.ez.max, x.ez.zdropped, x.ez.max_q, x.ez.max_t, x.ez.mqe, x.ez.mqe_t, x.ez.mte, x.ez.mte_q, x.ez.score, x.ez.n_cigar, x.ez.reach_end,
-                            y.ez.max, y.ez.zdropped, y.ez.max_q, y.ez.max_t, y.ez.mqe, y.ez.mqe_t, y.ez.mte, y.ez.mte_q, y.ez.score, y.ez.n_cigar, y.ez.reach_end);
-                    fprintf(stderr, "  wave cigar:");
-                    for (int k = 0; k < x.ez.n_cigar && k < PMX_DP_MAX_CIGAR; ++k) fprintf(stderr, " %u%c", x.cigar[k] >> 4, "MID"[x.cigar[k] & 3]);
-                    fprintf(stderr, "\n  group cigar:");
-                    for (int k = 0; k < y.ez.n_cigar && k < PMX_DP_MAX_CIGAR; ++k) fprintf(stderr, " %u%c", y.cigar[k] >> 4, "MID"[y.cigar[k] & 3]);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-    }
-    fprintf(stderr, "[dpg shadow] round %d: %ld results compared, %ld differ\n", round, n_cmp, n_bad);
 }
 
 // diagnostic (PMX_ALIGN_PROF): the compact tier's own phase profile, then the accumulators start over for the general tiers
@@ -833,7 +739,7 @@ int pmx::align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs
     PMX_HIP(hipSetDevice(ctx->device));
     AlignStage S(ctx, al, rs, paired, allow_dedup);
     if (!S.setup(revcomp_mate2, cigar_cap)) return PMX_OK;
-    const bool tier1_fits = !S.sw.no_tier1 && al->opt.is_sr_like && PMX_ALIGN_WORK_BYTES + S.compact.fast_bytes + 16 <= 40 * 1024;
+    const bool tier1_fits = al->opt.is_sr_like && PMX_ALIGN_WORK_BYTES + S.compact.fast_bytes + 16 <= 40 * 1024;
     const bool use_tier0 = tier1_fits && !S.sw.no_tpp;
     timer_begin(ctx, "align");
     if (!tier1_fits) S.long_reads();

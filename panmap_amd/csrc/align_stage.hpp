@@ -30,8 +30,6 @@ struct pmx_aligner {
     pmx::DevBuf<unsigned long long> cigar_used;
     pmx::DevBuf<uint8_t> slow, slow2, slab0, slab_raw;
     pmx::DevBuf<pmx::aln::A128> mv_handover;
-    pmx::DevBuf<uint32_t> pp_idx, pp_idx2;   // pair order from the read order alone (PMX_ALIGN_PAIR_KEY1)
-    pmx::DevBuf<char> pp_tmp;
     uint32_t mv_epoch = 0;
     pmx::DevBuf<uint32_t> retry_list2, bail_list;
     pmx::DevBuf<uint32_t> cseeds;            // compact tier, two-kernel form: seed hand-over (AlignArgs::cseeds / cseed_n)
@@ -46,7 +44,6 @@ struct pmx_aligner {
     pmx::DevBuf<uint32_t> dpg_keys, dpg_keys2, dpg_ids, dpg_ids2, dpg_counts;   // grouped DP service (align_kernel_dpg.hip)
     pmx::DevBuf<char> dpg_tmp;
     pmx::DevBuf<uint8_t> dpg_tb;
-    pmx::DevBuf<pmx::aln::DpRes> dpg_shadow;
     pmx::DevBuf<unsigned long long> dpg_prof;
     int64_t last_dp_requests = 0;
     int last_dp_rounds = 0;
@@ -77,6 +74,7 @@ namespace pmx {
 // align_stage.hip: one attempt of pmx_align_readset with a CIGAR arena of `cigar_cap` words (the caller redoes an overflow)
 int align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int paired, int revcomp_mate2, uint64_t cigar_cap, bool allow_dedup);
 // align_stage.hip: the grouped DP service (align_kernel_dpg.hip), shared with pmx_align_dp_batch
+constexpr int kDpgWavesDefault = 8;   // its waves per CU unless PMX_ALIGN_DPG_WAVES says otherwise
 bool dpg_setup(const aln::Opt& o, aln::DpgArgs& DG);
 void dpg_launch(pmx_ctx* ctx, pmx_aligner* al, aln::DpgArgs& DG, int64_t n_slots, const uint32_t* worklist, int waves_per_cu, bool serve);
 
@@ -101,8 +99,6 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
                    const int32_t* flag, pmx_dp_probe_result* out, uint32_t* cigar_arena, int64_t arena_cap, pmx_dp_probe_caps* caps);
 
 // align_pairs.hip (readset_pair_order / readset_pair_map: readset.hpp)
-// pair order by mate 1's locality key alone: the even reads of the read order, halved -> al->pp_idx2
-const uint32_t* pair_order_mate1(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* read_order);
 // the representatives of the distinct-pair map in launch order (`order`, nullptr = input order) -> al->dd_list; their number
 int64_t pair_select_reps(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* order, int64_t n_pairs);
 // al->dd_count[2] += the copies the representatives list[0 .. *n_list) stand for (n_launch bounds the list: sizes the grid)

@@ -392,7 +392,7 @@ int pmx_align_dp_batch(pmx_ctx* ctx, pmx_aligner* al, const uint8_t* seqs, const
     DG.dp_req_base = d_req.p; DG.dp_res_base = d_res.p;
     DG.n_entries = (uint32_t)req.size();
     DG.shadow = 1;   // the requests stay posted: the launch can be repeated
-    int dpg_waves = 8;
+    int dpg_waves = pmx::kDpgWavesDefault;
     if (const char* e = pmx::opt_str(pmx::O_ALIGN_DPG_WAVES)) dpg_waves = std::max(1, atoi(e));
     if (ok) {
         hipEvent_t e0 = nullptr, e1 = nullptr;

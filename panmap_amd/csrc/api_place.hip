@@ -98,8 +98,7 @@ namespace {
 // Every switch the stage reads (device/pmx_options.hpp), parsed here and nowhere below.
 struct PlaceSwitches {
     static bool on(OptId id) { return pmx::opt_str(id) != nullptr; }
-    const bool seed_safe_bound = on(O_SEED_SAFE_BOUND), seed_no_hint = on(O_SEED_NO_HINT);                                // table bound policy
-    const bool seed_generic = on(O_SEED_GENERIC), seed_no_sort = on(O_SEED_NO_SORT), seed_no_collapse = on(O_SEED_NO_COLLAPSE);   // kernel path
+    const bool seed_no_collapse = on(O_SEED_NO_COLLAPSE);   // kernel path
     const bool level_kernels = on(O_PLACE_LEVEL_KERNELS), tree_kernel = on(O_PLACE_TREE_KERNEL), no_graph = on(O_PLACE_NO_GRAPH);   // scoring form
     const bool test_starved = on(O_PLACE_TEST_STARVED);
     const bool prof = on(O_PLACE_PROF);   // diagnostics
@@ -862,7 +861,7 @@ SeedStage::SeedStage(pmx_ctx* c, pmx_place* p, const pmx_readset* r, const pmx_p
     lds_ks = (size_t)(PMX_SEED_BLOCK / 64) * PMX_SEED_QCAP_KS * sizeof(uint64_t) + (size_t)PMX_SEED_CACHE * 14 + 35 * sizeof(uint64_t) +   // + the base-hash tables
              (size_t)(PMX_SEED_BLOCK / 64) * (64 * sizeof(uint32_t) + PMX_SEED_QCAP_KS);                                                   // + multiplicities, pushing lanes
     quality_mode = pp->min_seed_quality > 0 && rs->has_qual;
-    ks_path = sp.k == 19 && sp.s == 8 && sp.t == 0 && (l == 3 || l == 1) && !quality_mode && !sw.seed_generic;
+    ks_path = sp.k == 19 && sp.s == 8 && sp.t == 0 && (l == 3 || l == 1) && !quality_mode;
     // Read collapse ahead of the seeding kernel (k_collapse_reads: src/placement.cpp:1550-1593 seeds every distinct read once,
     // with its multiplicity): reads of up to 160 bases on the specialised kernel's path
     collapse = ks_path && rs->max_len <= 160 && !sw.seed_no_collapse;
@@ -889,10 +888,10 @@ SeedStage::SeedStage(pmx_ctx* c, pmx_place* p, const pmx_readset* r, const pmx_p
     // Once a histogram has been finished its density (distinct seeds per read base) sizes the next optimistic table:
     // twice that, at least 1/256 of the safe bound (1/64 until round 4: 2^25 slots at a load of 3.5 % for 10M reads; every table atomic missed the L2 and the compaction scanned 512 MB) -- batches of one run look alike, and a table 16x smaller is 16x
     // cheaper to clear and to compact.
-    if (!pl->table_dirty && !sw.seed_safe_bound) {
+    if (!pl->table_dirty) {
         bound_div = 8;
         if (sw.seed_bound_div > 0) bound_div = sw.seed_bound_div;   // (tests force the redo with a large value)
-        else if (pl->keys_per_base > 0 && !sw.seed_no_hint) bound_frac = std::min(1.0 / 8, std::max(2 * pl->keys_per_base, 1.0 / 256));
+        else if (pl->keys_per_base > 0) bound_frac = std::min(1.0 / 8, std::max(2 * pl->keys_per_base, 1.0 / 256));
     }
     // A launch of one chunk is latency-bound (every wave walks its 150 bases one after the other, a few waves per
     // SIMD): the chunks of a group run concurrently on side streams, sharing the table (all they do is atomics).
@@ -914,7 +913,7 @@ void SeedStage::dedup_mask() {
 // seeding order (default-parameter kernel): reads that start with the same 16 bases next to each other, so that a
 // block's (seed, count) cache sees its seeds many times (k_seed_histogram_ks)
 void SeedStage::seeding_order() {
-    if (!ks_path || sw.seed_no_sort) return;
+    if (!ks_path) return;
     const bool whole = rr0 == 0 && rr1 == rs->n;
     perm = whole ? readset_locality_order(ctx, rs) : readset_locality_order_range(ctx, rs, rr0, rr1);
 }

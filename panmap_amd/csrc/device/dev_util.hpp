@@ -91,10 +91,9 @@ inline void rocprim_two_calls(DevBuf<char>& tmp, Call call) {
 // (GPU_MAX_HW_QUEUES, 4 by default); streams that land on one queue execute strictly in submission order: kernels of two
 // contexts then never overlap, and a kernel queued behind the barrier packet of a long host-to-device copy of ANOTHER stream
 // waits for that copy.  A stream created with a CU mask gets its own queue; the mask enables every CU.
-// (PMX_CTX_POOLED_QUEUE=1: ordinary pooled streams.)
 inline hipStream_t create_dedicated_stream(int n_cu) {
     hipStream_t st = nullptr;
-    if (!pmx::opt_str(pmx::O_CTX_POOLED_QUEUE) && n_cu > 0) {
+    if (n_cu > 0) {
         std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0xffffffffu);
         if (n_cu % 32) mask.back() = (1u << (n_cu % 32)) - 1u;
         if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) {

@@ -8,6 +8,7 @@
 //   env   deployment: which device, how many host threads, the test transport's directory
 //   test  forces a rare path so that a test can reach it (capacity overflows, redo loops, fall-back tiers)
 //   ab    keeps the previous form of a design decision selectable, for same-box A/B measurements of the two forms
+//         (a test or ab switch stays only while a test or a script under tools/ sets it: tests/test_host_stage.py)
 //   tune  a resource size (waves per CU, chunk sizes); the default is the measured optimum on MI355X
 //   diag  prints / profiles; never changes results
 #pragma once
@@ -19,12 +20,7 @@
     X(FASTX_THREADS, "env", "host threads of the FASTQ scan")                                                                                  \
     X(BAM_THREADS, "env", "host threads of the BAM writer (record building + BGZF deflate)")                                                   \
     X(DIST_HOST_DIR, "env", "multi-rank exchange through files in this directory instead of RCCL: functional tests on a box with fewer GPUs than ranks; never for a number") \
-    X(CTX_POOLED_QUEUE, "ab", "context streams from HIP's pool of hardware queues instead of a queue of their own")                            \
     X(SEED_NO_COLLAPSE, "ab", "seeding: every read through the seeding kernel, no collapse of identical reads (k_collapse_reads)")             \
-    X(SEED_GENERIC, "ab", "seeding: the generic kernel (LDS rings) also for the default k=19 s=8 parameters")                                  \
-    X(SEED_NO_SORT, "ab", "seeding: reads in input order, not in locality order")                                                              \
-    X(SEED_SAFE_BOUND, "ab", "seeding: size the seed table by one key per base from the start (no optimistic table + redo)")                   \
-    X(SEED_NO_HINT, "ab", "seeding: do not size the optimistic table by the previous histogram's density")                                     \
     X(SEED_BOUND_DIV, "test", "seeding: optimistic table = safe bound / N (a large N forces the overflow redo)")                               \
     X(SEED_CHUNK_MB, "tune", "seeding: bases per launch, in MB (default: a third of the range, 64..512)")                                      \
     X(SEED_PAR, "tune", "seeding: concurrent launches per group, 1..4 (default 3)")                                                            \
@@ -47,19 +43,6 @@
     X(ALIGN_COMPACT_WAVES, "tune", "align: compact chain kernel on a resident grid of N waves per CU (default: one workgroup per 64 pairs)")    \
     X(ALIGN_CSEED_WAVES, "tune", "align: compact seeds kernel on a resident grid of N waves per CU")                                           \
     X(ALIGN_NO_TPP, "ab", "align: no thread-per-pair tier (bails straight to the wave tiers)")                                                 \
-    X(ALIGN_NO_TIER1, "ab", "align: no compact-layout wave tier")                                                                              \
-    X(ALIGN_NO_DP_SERVICE, "ab", "align: thread-per-pair tier posts no DP requests")                                                           \
-    X(ALIGN_NO_DP_GROUP, "ab", "align: DP requests through the wave-per-request service only (no eight-lane groups)")                          \
-    X(ALIGN_DP_ONE_CLASS, "ab", "align: wave-per-request DP service in one size class")                                                        \
-    X(ALIGN_NO_ROWS_DP, "ab", "align: anti-diagonal DPs in the wave tiers (no row-by-row form)")                                               \
-    X(ALIGN_NO_DP_FAST, "ab", "align, long reads: no LDS copy of small DPs' arrays")                                                           \
-    X(ALIGN_NO_WORK_QUEUE, "ab", "align, long reads: reads strided over the waves instead of drawn from a counter")                            \
-    X(ALIGN_NO_PAIR_SORT, "ab", "align: pairs in input order")                                                                                 \
-    X(ALIGN_PAIR_KEY1, "ab", "align: pair order by mate 1's locality key alone")                                                               \
-    X(ALIGN_NO_MV_HANDOVER, "ab", "align: wave tier sketches again instead of taking the minimizers a DP-posting pair left")                   \
-    X(ALIGN_NO_LDS_RING, "ab", "align: thread-per-pair minimizer window ring in the arena instead of LDS")                                     \
-    X(ALIGN_NO_LANE_RING, "ab", "align: wave tier window ring in LDS instead of across the lanes")                                             \
-    X(ALIGN_RESIDENT_GRID, "ab", "align: wave tiers on a resident strided grid even for few pairs")                                            \
     X(ALIGN_HOST_INDEX, "ab", "align: reference minimizer index built on the host and uploaded (the device build's checker)")                  \
     X(ALIGN_BAIL_TPP_MIN, "tune", "align: fewer compact-tier bails than this go straight to the wave tier (default 4096)")                     \
     X(ALIGN_TPP_MIN, "tune", "align: fewer DP requests than this end the service rounds (default 8192)")                                       \
@@ -76,9 +59,6 @@
     X(ALIGN_VERBOSE, "diag", "align: print the wave-tier launches")                                                                            \
     X(DP_HIST, "diag", "align: print the shapes of the posted DP requests")                                                                    \
     X(DPG_PROF, "diag", "align: grouped DP service phase cycles")                                                                              \
-    X(DPG_SHADOW, "diag", "align: run both DP services and compare their results")                                                             \
-    X(DPG_CHECK_LIST, "diag", "align: check the grouped service's sorted request list")                                                        \
-    X(DPG_NO_SERVE, "test", "align: grouped DP service collects but serves nothing")                                                           \
     X(DPG_LEFT_TO_WAVE_TIER, "tune", "align: at most this many requests the grouped service leaves go to the wave tier (default 256)")
 
 namespace pmx {

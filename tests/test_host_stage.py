@@ -353,7 +353,7 @@ def test_one_table_of_switches(pmx, monkeypatch):
     import re
     text = pmx.describe_options()
     names = [l.split(" ")[0] for l in text.splitlines()]
-    assert len(names) == len(set(names)) >= 50 and all(n.startswith("PMX_") for n in names)
+    assert len(names) == len(set(names)) == 45 and all(n.startswith("PMX_") for n in names)
     assert all(re.match(r"PMX_\w+ \[(env|test|ab|tune|diag)\] \S", l) for l in text.splitlines())
     monkeypatch.setenv("PMX_INDEX_THREADS", "3")          # (conftest re-reads the table)
     assert "PMX_INDEX_THREADS [env]" in pmx.describe_options() and "(= 3)" in [l for l in pmx.describe_options().splitlines() if l.startswith("PMX_INDEX_THREADS")][0]
@@ -367,3 +367,26 @@ def test_one_table_of_switches(pmx, monkeypatch):
             if f.endswith((".hip", ".hpp", ".cpp", ".h")):
                 for m in re.finditer(r'getenv\("(PMX_\w+)"\)', open(os.path.join(dp, f)).read()):
                     assert m.group(1) == "PMX_C_DUMP", (f, m.group(1))      # (hostsim-only debug print in aln_compact.hpp)
+
+
+def test_every_ab_and_test_switch_is_set_somewhere(pmx):
+    """an `ab` or `test` switch is a supported configuration of the library only while something runs it: each one is named
+    in a file under tests/ or tools/, or in bench.py (A/B runs of two builds go through tools/ab.sh, not through switches)"""
+    # The one exception: PMX_SEED_BOUND_DIV is the only handle on the seed table's clear-and-redo (add_reads_impl), and it has
+    # no test yet because the redo itself fails.  On the SARS tree the forced table never goes below its floor of 65,536
+    # slots: 2,000 simulated reads (12,629 distinct seeds) report 0 failed inserts, so nothing is redone; 60,000 reads (115,522
+    # distinct seeds) report a failed insert, the seeding is redone, and the next pmx_place_score ends in "seed table
+    # overflow (internal sizing error)": the redo leaves the counters read after the first pass marked valid.  The switch
+    # leaves this set with the fix of that and its test.
+    untested = {"PMX_SEED_BOUND_DIV"}
+    users = [os.path.join(ROOT, "bench.py")]
+    for top in ("tests", "tools"):
+        for dp, dn, fn in os.walk(os.path.join(ROOT, top)):
+            dn[:] = [d for d in dn if d not in ("__pycache__", "golden")]
+            users += [os.path.join(dp, f) for f in fn if not f.endswith(".pyc") and f != os.path.basename(__file__)]   # (naming a switch here is no use of it)
+    text = "\n".join(open(u, errors="replace").read() for u in users)
+    lines = [l for l in pmx.describe_options().splitlines() if re.match(r"PMX_\w+ \[(ab|test)\] ", l)]
+    assert len(lines) >= 10
+    unused = [n for n in (l.split(" ")[0] for l in lines) if n not in untested and not re.search(r"\b%s\b" % n, text)]
+    assert not [n for n in untested if re.search(r"\b%s\b" % n, text)], "a listed exception has a user now: take it off the list"
+    assert not unused, "no test, tool or benchmark sets %s: retire the switch or give it a test" % ", ".join(unused)
