@@ -163,8 +163,8 @@ const uint32_t* readset_pair_order(pmx_ctx* ctx, const pmx_readset* rs, hipStrea
         PMX_HIP(hipStreamWaitEvent(side, rs->pair_ev, 0));
         st = side;
     }
-    hipLaunchKernelGGL(k_pair_keys, dim3((unsigned)std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, st, rs->loc_key.p, n_items,
-                       rs->pp_key.p, rs->pp_idx.p);
+    PMX_LAUNCH(k_pair_keys, dim3((unsigned)std::min<int64_t>((n_items + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, st, rs->loc_key.p, n_items,
+               rs->pp_key.p, rs->pp_idx.p);
     PMX_ROCPRIM(rs->pp_tmp, radix_sort_pairs, rs->pp_key.p, rs->pp_key2.p, rs->pp_idx.p, rs->pp_idx2.p, (size_t)n_items, 0, 64, st);
     // (the map, too, depends on the reads alone; below a million pairs the align stage seldom wants it -- PMX_ALIGN_DEDUP_DEPTH
     //  -- and makes it itself when it does)
@@ -183,14 +183,13 @@ void readset_pair_map(pmx_ctx* ctx, const pmx_readset* rs, hipStream_t st) {
     rs->pd_key.ensure((size_t)n); rs->pd_key2.ensure((size_t)n); rs->pd_idx.ensure((size_t)n); rs->pd_idx2.ensure((size_t)n);
     rs->pd_gs.ensure((size_t)n); rs->pd_rep.ensure((size_t)n); rs->pd_mult.ensure((size_t)n);
     const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 8);
-    hipLaunchKernelGGL(k_pair_hashes, dim3(grid), dim3(256), 0, st, rs->recs.p, n, rs->pd_key.p, rs->pd_idx.p);
+    PMX_LAUNCH(k_pair_hashes, dim3(grid), dim3(256), 0, st, rs->recs.p, n, rs->pd_key.p, rs->pd_idx.p);
     PMX_ROCPRIM(rs->pd_tmp, radix_sort_pairs, rs->pd_key.p, rs->pd_key2.p, rs->pd_idx.p, rs->pd_idx2.p, (size_t)n, 0, 32, st);
     // (the unsorted keys are spent: their buffer takes the group starts before the scan)
-    hipLaunchKernelGGL(k_pair_group_starts, dim3(grid), dim3(256), 0, st, rs->recs.p, rs->pd_key2.p, rs->pd_idx2.p, n, rs->pd_key.p);
+    PMX_LAUNCH(k_pair_group_starts, dim3(grid), dim3(256), 0, st, rs->recs.p, rs->pd_key2.p, rs->pd_idx2.p, n, rs->pd_key.p);
     // (the sort and the scan share one temporary; the scan needs less of it, so it grows at the sort alone)
     PMX_ROCPRIM(rs->pd_tmp, inclusive_scan, rs->pd_key.p, rs->pd_gs.p, (size_t)n, rocprim::maximum<uint32_t>(), st);
-    hipLaunchKernelGGL(k_pair_reps, dim3(grid), dim3(256), 0, st, rs->pd_idx2.p, rs->pd_gs.p, n, rs->pd_rep.p, rs->pd_mult.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_pair_reps, dim3(grid), dim3(256), 0, st, rs->pd_idx2.p, rs->pd_gs.p, n, rs->pd_rep.p, rs->pd_mult.p);
     rs->has_pair_map = true;
 }
 
@@ -203,21 +202,18 @@ int64_t pair_select_reps(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, c
     if (order) PMX_ROCPRIM(al->dd_tmp, select, order, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream);
     else PMX_ROCPRIM(al->dd_tmp, select, every, al->dd_list.p, al->dd_count.p, (size_t)n_pairs, is_rep, ctx->stream);
     unsigned long long h_reps = 0;
-    PMX_HIP(hipMemcpyAsync(&h_reps, al->dd_count.p, sizeof(h_reps), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(&h_reps, al->dd_count, 1, ctx->stream);
     return (int64_t)h_reps;
 }
 
 void pair_count_copies(pmx_ctx* ctx, pmx_aligner* al, const uint32_t* list, const unsigned long long* n_list, const uint32_t* mult, int64_t n_launch) {
     const unsigned dgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_launch + 255) / 256, (int64_t)ctx->n_cu * 8));
-    hipLaunchKernelGGL(k_pair_dup_count, dim3(dgrid), dim3(256), 0, ctx->stream, list, n_list, mult, al->dd_count.p + 2);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_pair_dup_count, dim3(dgrid), dim3(256), 0, ctx->stream, list, n_list, mult, al->dd_count.p + 2);
 }
 
 void pair_fanout(pmx_ctx* ctx, pmx_aligner* al, const uint32_t* rep, int64_t n_pairs, int32_t* edits) {
-    hipLaunchKernelGGL(k_pair_fanout, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_pairs + 256 * PMX_FANOUT_ROUNDS - 1) / (256 * PMX_FANOUT_ROUNDS), (int64_t)ctx->n_cu * 8))), dim3(256), 0,
-                       ctx->stream, rep, n_pairs, al->records.p, edits, al->cigars.p, (uint64_t)al->cigar_cap, al->cigar_used.p, al->dd_count.p + 1);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_pair_fanout, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_pairs + 256 * PMX_FANOUT_ROUNDS - 1) / (256 * PMX_FANOUT_ROUNDS), (int64_t)ctx->n_cu * 8))), dim3(256), 0,
+               ctx->stream, rep, n_pairs, al->records.p, edits, al->cigars.p, (uint64_t)al->cigar_cap, al->cigar_used.p, al->dd_count.p + 1);
 }
 }  // namespace pmx
 

@@ -50,11 +50,10 @@ void dpg_launch(pmx_ctx* ctx, pmx_aligner* al, DpgArgs& DG, int64_t n_slots, con
     DG.keys = al->dpg_keys.p; DG.ids = al->dpg_ids.p; DG.sorted_ids = al->dpg_ids2.p; DG.counts = al->dpg_counts.p;
     DG.tb = al->dpg_tb.p;
     if (!DG.dp_req_base || !DG.dp_res_base) throw std::runtime_error("grouped DP service: a buffer is missing");
-    PMX_HIP(hipMemsetAsync(al->dpg_counts.p, 0, 16 * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_dpg_collect, dim3((unsigned)std::min<int64_t>((n_ent + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream, DG);
+    PMX_ZERO(al->dpg_counts, 16, ctx->stream);
+    PMX_LAUNCH(k_dpg_collect, dim3((unsigned)std::min<int64_t>((n_ent + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream, DG);
     PMX_ROCPRIM(al->dpg_tmp, radix_sort_pairs, al->dpg_keys.p, al->dpg_keys2.p, al->dpg_ids.p, al->dpg_ids2.p, (size_t)n_ent, 0, 12, ctx->stream);
-    if (serve) hipLaunchKernelGGL(k_align_dp_group, dim3((unsigned)grid), dim3(64), PMX_DPG_LDS_BYTES, ctx->stream, DG);
-    PMX_HIP(hipGetLastError());
+    if (serve) PMX_LAUNCH(k_align_dp_group, dim3((unsigned)grid), dim3(64), PMX_DPG_LDS_BYTES, ctx->stream, DG);
 }
 
 // The wave DP service's layouts, LDS bytes, slab strides and resident grids
@@ -84,13 +83,13 @@ void launch_dp_serve(AlignArgs A, const DpServePlan& P, bool two_class, uint8_t*
     // (tier 0 runs for the short-read preset only; with max_gap of a long-read preset the arrays of this class exceed the LDS of a
     //  CU and pmx_align_dp_probe is left with the small class)
     if (P.dp_max_grid > 0)
-        hipLaunchKernelGGL(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(P.dp_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), P.dp_lds, stream, A);
+        PMX_LAUNCH(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(P.dp_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), P.dp_lds, stream, A);
     if (two_class) {
         A.layout = P.dps_layout;
         A.slow_stride = P.dps_stride;
         A.slow_base = slow2;
         A.dp_class = 1;
-        hipLaunchKernelGGL(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(P.dps_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), P.dps_lds, stream, A);
+        PMX_LAUNCH(k_align_dp_serve, dim3((unsigned)std::min<int64_t>(P.dps_max_grid, n_dp * PMX_DP_REQ_PER_PASS)), dim3(64), P.dps_lds, stream, A);
     }
 }
 }  // namespace pmx
@@ -214,24 +213,24 @@ bool AlignStage::setup(int revcomp_mate2, uint64_t cigar_cap) {
     }
     al->n_records = rs->n;
     al->records.ensure((size_t)std::max<int64_t>(rs->n, 1));
-    PMX_HIP(hipMemsetAsync(al->records.p, 0, sizeof(AlnRecord) * (size_t)std::max<int64_t>(rs->n, 1), stream));
+    PMX_ZERO(al->records, (size_t)std::max<int64_t>(rs->n, 1), stream);
     al->cigar_cap = cigar_cap;
     al->cigars.ensure(al->cigar_cap);
-    PMX_HIP(hipMemsetAsync(al->cigar_used.p, 0, sizeof(unsigned long long), stream));
+    PMX_ZERO(al->cigar_used, 1, stream);
     al->stats.ensure(4);
-    PMX_HIP(hipMemsetAsync(al->stats.p, 0, 4 * sizeof(unsigned long long), stream));
+    PMX_ZERO(al->stats, 4, stream);
     al->dd_count.ensure(4);   // distinct-pair map: [0] representatives, [1] copies of an arena-overflowed representative, [2] copies of bails
-    PMX_HIP(hipMemsetAsync(al->dd_count.p, 0, 4 * sizeof(unsigned long long), stream));
+    PMX_ZERO(al->dd_count, 4, stream);
     al->last_dp_slots = 0; al->last_compact = 0; al->last_simple = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_huge = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
     memset(&al->last_stats, 0, sizeof(al->last_stats));
     if (n_items <= 0) return false;
     al->last_stats.n_items = n_items;
     if (sw.prof) {
         al->prof.ensure(32);
-        PMX_HIP(hipMemsetAsync(al->prof.p, 0, 32 * sizeof(unsigned long long), stream));
+        PMX_ZERO(al->prof, 32, stream);
     }
     al->retry_count.ensure(4);   // [0] pairs for the next (wave) tier, [1] DP requests of the current tier-0 round, [2] compact-tier bails, [3] long reads: work queue
-    PMX_HIP(hipMemsetAsync(al->retry_count.p, 0, 4 * sizeof(unsigned long long), stream));
+    PMX_ZERO(al->retry_count, 4, stream);
     if (al->want_edits) al->edits.ensure((size_t)std::max<int64_t>(rs->n, 1));
 
     base.words = rs->words.p; base.amb = rs->amb.p; base.woff = rs->woff.p; base.off = rs->off.p;
@@ -291,16 +290,14 @@ void AlignStage::launch_wave(AlignArgs A, AlignKernel kfn, const Layout& L, int6
     A.worklist = worklist;
     A.retry_list = retry_list;
     A.retry_count = al->retry_count.p;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(64), lds_bytes, stream, A);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(kfn, dim3((unsigned)grid), dim3(64), lds_bytes, stream, A);
 }
 
 // reads both counters; [1] is reset for the next round, [0] only when asked
 void AlignStage::read_counts(int64_t& n_next_tier, int64_t& n_dp, bool reset_next_tier) {
     unsigned long long h[2] = {0, 0};
-    PMX_HIP(hipMemcpyAsync(h, al->retry_count.p, sizeof(h), hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipStreamSynchronize(stream));
-    PMX_HIP(hipMemsetAsync(al->retry_count.p + (reset_next_tier ? 0 : 1), 0, sizeof(unsigned long long) * (reset_next_tier ? 2 : 1), stream));
+    PMX_D2H_SYNC(h, al->retry_count, stream);
+    PMX_ZERO(pmx::at(al->retry_count, reset_next_tier ? 0 : 1), reset_next_tier ? 2 : 1, stream);
     n_next_tier = (int64_t)h[0];
     n_dp = (int64_t)h[1];
 }
@@ -341,7 +338,7 @@ void AlignStage::long_reads() {
     al->retry_list.ensure((size_t)n_items);
     timer_begin(ctx, "align_dom");
     AlignArgs A = base;
-    PMX_HIP(hipMemsetAsync(al->retry_count.p + 3, 0, sizeof(unsigned long long), stream));   // the waves draw their reads from a counter
+    PMX_ZERO(pmx::at(al->retry_count, 3), 1, stream);   // the waves draw their reads from a counter
     A.work_queue = al->retry_count.p + 3;
     launch_wave(A, kern, g1, n_items, nullptr, general.tb_cap > g1.tb_cap ? al->retry_list.p : nullptr, al->slow2);
     timer_end(ctx, "align_dom", 1);
@@ -447,7 +444,7 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         const size_t blocks = (size_t)((n_launch + 63) / 64);
         // [0] length of multi_list, [1] pairs the second form finished, [2] / [3] lengths of the two class lists, [4] pairs k_align_simple finished
         al->multi_count.ensure(8);
-        PMX_HIP(hipMemsetAsync(al->multi_count.p, 0, 8 * sizeof(unsigned long long), stream));
+        PMX_ZERO(al->multi_count, 8, stream);
         if (c_simple) {
             al->simple_list.ensure(blocks * 64 * 2);   // the simple list, behind it (from n_launch rounded up to 64) the other
             A.simple_list = al->simple_list.p;
@@ -464,12 +461,10 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         int64_t s_grid = (n_launch + 63) / 64;
         if (sw.cseed_waves) s_grid = std::min<int64_t>((int64_t)ctx->n_cu * sw.cseed_waves, s_grid);
         timer_begin(ctx, "align_cseeds");
-        hipLaunchKernelGGL(s_kern, dim3((unsigned)s_grid), dim3(64), ((size_t)PMX_C_SEEDQ * 2 + 8) * 64 * sizeof(uint32_t),   // queues + eight staging words per lane
-                           stream, A);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(s_kern, dim3((unsigned)s_grid), dim3(64), ((size_t)PMX_C_SEEDQ * 2 + 8) * 64 * sizeof(uint32_t),   // queues + eight staging words per lane
+                   stream, A);
         if (c_simple) {
-            hipLaunchKernelGGL(k_compact_classes, dim3((unsigned)((n_launch + 2047) / 2048)), dim3(256), 0, stream, A);   // PMX_C_CLASS_BLOCK positions each
-            PMX_HIP(hipGetLastError());
+            PMX_LAUNCH(k_compact_classes, dim3((unsigned)((n_launch + 2047) / 2048)), dim3(256), 0, stream, A);   // PMX_C_CLASS_BLOCK positions each
         }
         timer_end(ctx, "align_cseeds", 1);
     }
@@ -490,11 +485,9 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
     // workgroup per 64 positions of the launch, those beyond a list's end leave at once (a resident grid striding over
     // the lists -- PMX_ALIGN_COMPACT_WAVES -- is the slower form here as it is for the chain kernel alone).
     if (c_simple) {
-        hipLaunchKernelGGL(pos16 ? k_align_simple16 : k_align_simple32, dim3((unsigned)c_grid), dim3(64), (size_t)PMX_C_SIMPLE_LDS_PAD + PMX_C_PEN_BYTES, stream, A);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(pos16 ? k_align_simple16 : k_align_simple32, dim3((unsigned)c_grid), dim3(64), (size_t)PMX_C_SIMPLE_LDS_PAD + PMX_C_PEN_BYTES, stream, A);
     }
-    hipLaunchKernelGGL(c_kern, dim3((unsigned)c_grid), dim3(64), c_lds, stream, A);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(c_kern, dim3((unsigned)c_grid), dim3(64), c_lds, stream, A);
     timer_end(ctx, "align_dom", 1);
     if (c_multi) {
         // (the list's length stays on the device: a resident grid -- seven waves per CU by the LDS -- strides over it)
@@ -502,19 +495,18 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         al->multi_ws.ensure((size_t)m_grid * PMX_CM_WS_WORDS * 64);
         A.multi_ws = al->multi_ws.p;
         timer_begin(ctx, "align_cmulti");
-        hipLaunchKernelGGL(pos16 ? k_align_compact16_multi : k_align_compact32_multi, dim3((unsigned)m_grid), dim3(64), c_lds_full, stream, A);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(pos16 ? k_align_compact16_multi : k_align_compact32_multi, dim3((unsigned)m_grid), dim3(64), c_lds_full, stream, A);
         timer_end(ctx, "align_cmulti", 1);
     }
     if (sw.prof) print_compact_prof();
     unsigned long long h_dups = 0, h_bail = 0;
     if (dedup) {   // the copies of the pairs handed to the general tiers (compact_tier_items counts pairs, copies too)
         pair_count_copies(ctx, al, al->bail_list.p, al->retry_count.p + 2, rs->pd_mult.p, n_launch);
-        PMX_HIP(hipMemcpyAsync(&h_dups, al->dd_count.p + 2, sizeof(h_dups), hipMemcpyDeviceToHost, stream));
+        PMX_D2H(&h_dups, pmx::at(al->dd_count, 2), 1, stream);
     }
     unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};   // multi_count[0 .. 4]
-    PMX_HIP(hipMemcpyAsync(&h_bail, al->retry_count.p + 2, sizeof(h_bail), hipMemcpyDeviceToHost, stream));
-    if (!c_fused) PMX_HIP(hipMemcpyAsync(h_cnt, al->multi_count.p, sizeof(h_cnt), hipMemcpyDeviceToHost, stream));
+    PMX_D2H(&h_bail, pmx::at(al->retry_count, 2), 1, stream);
+    if (!c_fused) PMX_D2H(h_cnt, al->multi_count, stream);
     PMX_HIP(hipStreamSynchronize(stream));
     if (sw.verbose && !c_fused)
         fprintf(stderr, "align: compact tier, %lld launch positions: simple list %llu (k_align_simple finished %llu), other list %llu; second form: %llu listed, %llu finished; %llu bails\n",
@@ -529,7 +521,7 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
 // the pairs for the wave tiers and the DP requests are counted in, the thread-per-pair layout.
 AlignArgs AlignStage::tail_args() {
     AlignArgs T = base;
-    PMX_HIP(hipMemsetAsync(al->dp_ncached.p, 0, sizeof(uint32_t) * (size_t)n_items, stream));
+    PMX_ZERO(al->dp_ncached, n_items, stream);
     T.dp_req_base = al->dp_req.p; T.dp_res_base = al->dp_res.p; T.dp_ncached = al->dp_ncached.p;
     T.dp_slot_pairs = al->dp_slot_pairs.p;
     T.dp_slot_cap = (uint32_t)std::min<int64_t>(n_items, UINT32_MAX - 1);
@@ -557,8 +549,7 @@ void AlignStage::launch_tpp(const AlignArgs& T, int round, int64_t n_work, const
     A.dp_round = round;
     A.dp_next_list = next_list;
     A.pair_perm = pair_perm;
-    hipLaunchKernelGGL(k_align_reads_tpp, dim3((unsigned)grid), dim3(64), tpp_lds_bytes, stream, A);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_align_reads_tpp, dim3((unsigned)grid), dim3(64), tpp_lds_bytes, stream, A);
 }
 
 // One DP service round over the slots `cur` (nullptr: 0 .. n_dp-1): the grouped service, what it left, the wave service
@@ -574,17 +565,16 @@ void AlignStage::dp_round(const AlignArgs& T, int round, int64_t n_dp, const uin
         DpgArgs DG = dpg_base;
         DG.dp_req_base = al->dp_req.p; DG.dp_res_base = al->dp_res.p; DG.stats = base.stats;
         DG.n_entries = (uint32_t)std::min<size_t>(al->dp_req.n / sizeof(DpReq), UINT32_MAX);
-        if (sw.dpg_prof) { al->dpg_prof.ensure(8); PMX_HIP(hipMemsetAsync(al->dpg_prof.p, 0, 64, stream)); DG.prof = al->dpg_prof.p; }
+        if (sw.dpg_prof) { al->dpg_prof.ensure(8); PMX_ZERO(al->dpg_prof, 8, stream); DG.prof = al->dpg_prof.p; }
         dpg_launch(ctx, al, DG, n_dp, cur, sw.dpg_waves, true);
         if (sw.dpg_prof) print_dpg_prof();
         // what did the grouped service leave?  Nothing: no launch of the wave service.  A handful (a side beyond 128
         // bases on 150 bp reads: ~8 requests per 400k pairs): those pairs go to the wave-per-pair tier instead
         uint32_t left[2] = {0, 0};
-        PMX_HIP(hipMemcpyAsync(left, al->dpg_counts.p + PMX_DPG_NO_BUCKET - 1, sizeof(left), hipMemcpyDeviceToHost, stream));
-        PMX_HIP(hipStreamSynchronize(stream));
+        PMX_D2H_SYNC(left, pmx::at(al->dpg_counts, PMX_DPG_NO_BUCKET - 1), stream);
         if (left[0] + left[1] == 0) wave_service = false;
         else if ((int64_t)left[0] + left[1] <= sw.dpg_left_few) {
-            hipLaunchKernelGGL(k_dpg_refuse_left, dim3((unsigned)std::min<int64_t>((n_dp * PMX_DP_REQ_PER_PASS + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, stream, DG);
+            PMX_LAUNCH(k_dpg_refuse_left, dim3((unsigned)std::min<int64_t>((n_dp * PMX_DP_REQ_PER_PASS + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, stream, DG);
             wave_service = false;
         }
     }
@@ -595,7 +585,6 @@ void AlignStage::dp_round(const AlignArgs& T, int round, int64_t n_dp, const uin
         A.worklist = cur;
         launch_dp_serve(A, dpp, true, al->slow.p, al->slow2.p, stream);
     }
-    PMX_HIP(hipGetLastError());
     launch_tpp(T, round, n_dp, cur, next, nullptr);
 }
 
@@ -642,7 +631,7 @@ void AlignStage::tail(const uint32_t* order, int64_t n_t0) {
         if (!cur) {      // round-1 remainder: slots are 0..n-1
             std::vector<uint32_t> iota((size_t)n_small);
             for (int64_t i = 0; i < n_small; ++i) iota[(size_t)i] = (uint32_t)i;
-            PMX_HIP(hipMemcpyAsync(lists[0], iota.data(), sizeof(uint32_t) * (size_t)n_small, hipMemcpyHostToDevice, stream));
+            PMX_H2D(lists[0], iota, n_small, stream);
             PMX_HIP(hipStreamSynchronize(stream));
             cur = lists[0];
         }
@@ -654,7 +643,7 @@ void AlignStage::tail(const uint32_t* order, int64_t n_t0) {
         int64_t unused = 0;
         read_counts(n_t1, unused, false);
     }
-    PMX_HIP(hipMemsetAsync(al->retry_count.p, 0, 2 * sizeof(unsigned long long), stream));
+    PMX_ZERO(al->retry_count, 2, stream);
     const uint32_t* t1_list = al->retry_list2.p;
     if (skip_t0) { t1_list = order; n_t1 = n_t0; }
     al->last_tpp_retry += n_t1;
@@ -664,8 +653,7 @@ void AlignStage::tail(const uint32_t* order, int64_t n_t0) {
 // diagnostic (PMX_DP_HIST): the shapes of the posted requests
 void AlignStage::print_dp_requests(int round, int64_t n_dp) {
     std::vector<DpReq> h((size_t)n_dp * PMX_DP_REQ_PER_PASS);
-    PMX_HIP(hipMemcpyAsync(h.data(), al->dp_req.p, h.size() * sizeof(DpReq), hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipStreamSynchronize(stream));
+    PMX_D2H_SYNC(h, pmx::as<DpReq>(al->dp_req), stream);
     std::map<std::tuple<int, int, int, int>, std::pair<long, long>> hist;   // (flag, q bucket, t bucket, band-free) -> (n, cells)
     long n_req = 0;
     for (const DpReq& r : h) {
@@ -685,8 +673,7 @@ void AlignStage::print_dp_requests(int round, int64_t n_dp) {
 // diagnostic (PMX_DPG_PROF): the grouped service's phase cycles
 void AlignStage::print_dpg_prof() {
     unsigned long long h[8];
-    PMX_HIP(hipMemcpyAsync(h, al->dpg_prof.p, 64, hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipStreamSynchronize(stream));
+    PMX_D2H_SYNC(h, al->dpg_prof, stream);
     const double t = (double)std::max<unsigned long long>(h[4], 1);
     fprintf(stderr, "[dpg prof] %llu tasks; cycles per task (lane 0 of the wave): set-up %.0f fill %.0f replay %.0f traceback %.0f; fill steps %.1f\n", h[4], h[0] / t, h[1] / t, h[2] / t, h[3] / t, h[5] / t);
 }
@@ -694,9 +681,8 @@ void AlignStage::print_dpg_prof() {
 // diagnostic (PMX_ALIGN_PROF): the compact tier's own phase profile, then the accumulators start over for the general tiers
 void AlignStage::print_compact_prof() {
     unsigned long long h[8];
-    PMX_HIP(hipMemcpyAsync(h, al->prof.p, sizeof(h), hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipStreamSynchronize(stream));
-    PMX_HIP(hipMemsetAsync(al->prof.p, 0, 32 * sizeof(unsigned long long), stream));
+    PMX_D2H_SYNC(h, al->prof, stream);
+    PMX_ZERO(al->prof, 32, stream);
     static const char* cn[8] = {"sketch", "probes", "merge", "chain fill", "backtrack", "regions", "align+mapq", "pairing"};
     const double waves = (double)((n_items + 63) / 64);
     fprintf(stderr, "[pmx compact tier: cycles per wave (lane 0)]");
@@ -707,8 +693,7 @@ void AlignStage::print_compact_prof() {
 // diagnostic (PMX_ALIGN_PROF): the per-phase profile of the general tiers, at the end of the call
 void AlignStage::print_phase_prof(bool tier1_fits) {
     unsigned long long h[32];
-    PMX_HIP(hipMemcpyAsync(h, al->prof.p, sizeof(h), hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipStreamSynchronize(stream));
+    PMX_D2H_SYNC(h, al->prof, stream);
     static const char* names[16] = {"decode", "sketch", "seed+heap", "chain", "gen_regs+post", "seg_gen", "squeeze", "align1(all regs)", "filter/sort/parent", "mapq", "pair", "output", "", "", "", ""};
     fprintf(stderr, "[pmx align phase cycles per item]");
     for (int k = 0; k < 12; ++k) fprintf(stderr, " %s=%.0f", names[k], (double)h[k] / (double)n_items);
@@ -763,7 +748,6 @@ int pmx::align_readset_once(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs
     }
     timer_end(ctx, "align", 1);
     if (S.sw.prof) S.print_phase_prof(tier1_fits);
-    PMX_HIP(hipGetLastError());
     return PMX_OK;
     PMX_CATCH
 }
@@ -821,8 +805,8 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
         const int64_t g0 = std::min<int64_t>(P.dp_max_grid, n * PMX_DP_REQ_PER_PASS), g1 = std::min<int64_t>(P.dps_max_grid, n * PMX_DP_REQ_PER_PASS);
         slow.alloc(P.dp_stride * (size_t)std::max<int64_t>(g0, 1));
         slow2.alloc(P.dps_stride * (size_t)g1);
-        PMX_HIP(hipMemcpyAsync(d_req.p, req.data(), req.size() * sizeof(DpReq), hipMemcpyHostToDevice, stream));
-        PMX_HIP(hipMemsetAsync(d_res.p, 0xff, sizeof(DpRes) * (size_t)n * PMX_DP_MAX_CALLS, stream));
+        PMX_H2D(pmx::as<DpReq>(d_req), req, stream);
+        PMX_FILL(d_res, 0xff, (size_t)n * PMX_DP_MAX_CALLS, stream);
         const size_t lds_max = std::max(class2_fits ? P.dp_lds : 0, P.dps_lds);
         if (lds_max > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_align_dp_serve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         AlignArgs A{};
@@ -831,10 +815,9 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
         A.dp_req_base = d_req.p; A.dp_res_base = d_res.p;
         A.n_items = n;
         launch_dp_serve(A, P, two_class, slow.p, slow2.p, stream);
-        PMX_HIP(hipGetLastError());
         std::vector<DpRes> res((size_t)n * PMX_DP_MAX_CALLS);
-        PMX_HIP(hipMemcpyAsync(res.data(), d_res.p, res.size() * sizeof(DpRes), hipMemcpyDeviceToHost, stream));
-        PMX_HIP(hipMemcpyAsync(req.data(), d_req.p, req.size() * sizeof(DpReq), hipMemcpyDeviceToHost, stream));   // (a served entry holds its PMX_DPP_* code)
+        PMX_D2H(res, d_res, stream);
+        PMX_D2H(req, pmx::as<DpReq>(d_req), stream);   // (a served entry holds its PMX_DPP_* code)
         PMX_HIP(hipStreamSynchronize(stream));
         for (int64_t i = 0; i < n; ++i) {
             const DpRes& R = res[(size_t)i * PMX_DP_MAX_CALLS];
@@ -875,12 +858,12 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
     d_out.alloc((size_t)n);
     d_cig.alloc((size_t)n * (size_t)L.caps.max_cigar);
     slab.alloc(A.slow_stride * (size_t)grid);
-    PMX_HIP(hipMemcpyAsync(d_seqs.p, seqs, (size_t)total, hipMemcpyHostToDevice, stream));
-    PMX_HIP(hipMemcpyAsync(d_off.p, q_off, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, stream));
-    PMX_HIP(hipMemcpyAsync(d_off.p + (n + 1), t_off, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, stream));
+    PMX_H2D(d_seqs, seqs, total, stream);
+    PMX_H2D(d_off, q_off, n + 1, stream);
+    PMX_H2D(pmx::at(d_off, n + 1), t_off, n + 1, stream);
     const int32_t* par[4] = {w, zdrop, end_bonus, flag};
-    for (int k = 0; k < 4; ++k) PMX_HIP(hipMemcpyAsync(d_par.p + (size_t)k * n, par[k], sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, stream));
-    PMX_HIP(hipMemsetAsync(d_out.p, 0, sizeof(DpProbeOut) * (size_t)n, stream));
+    for (int k = 0; k < 4; ++k) PMX_H2D(pmx::at(d_par, (size_t)k * n), par[k], n, stream);
+    PMX_ZERO(d_out, n, stream);
     A.seqs = d_seqs.p; A.q_off = d_off.p; A.t_off = d_off.p + (n + 1);
     A.w = d_par.p; A.zdrop = d_par.p + n; A.end_bonus = d_par.p + 2 * n; A.flag = d_par.p + 3 * n;
     A.n = n;
@@ -890,13 +873,11 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
     A.opt = al->opt;
     A.layout = L;
     A.slow_base = slab.p;
-    hipLaunchKernelGGL(k_align_dp_probe, dim3((unsigned)grid), dim3(64), lds_bytes, stream, A);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_align_dp_probe, dim3((unsigned)grid), dim3(64), lds_bytes, stream, A);
     std::vector<DpProbeOut> res((size_t)n);
     std::vector<uint32_t> cig((size_t)n * (size_t)L.caps.max_cigar);
-    PMX_HIP(hipMemcpyAsync(res.data(), d_out.p, sizeof(DpProbeOut) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipMemcpyAsync(cig.data(), d_cig.p, sizeof(uint32_t) * cig.size(), hipMemcpyDeviceToHost, stream));
-    PMX_HIP(hipStreamSynchronize(stream));
+    PMX_D2H(res, d_out, n, stream);
+    PMX_D2H_SYNC(cig, d_cig, stream);
     for (int64_t i = 0; i < n; ++i) {
         const DpProbeOut& R = res[(size_t)i];
         pmx_dp_probe_result& o = out[i];

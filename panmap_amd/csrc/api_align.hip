@@ -36,14 +36,6 @@ __global__ void k_sum_edits(const AlnRecord* __restrict__ recs, const int32_t* _
     }
 }
 
-namespace {
-template <class T>
-void upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
-    d.ensure(h.size());
-    if (!h.empty()) PMX_HIP(hipMemcpyAsync(d.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st));
-}
-}  // namespace
-
 extern "C" {
 
 int pmx_aligner_set_reference(pmx_ctx* ctx, pmx_aligner* al, const char* reference, int64_t ref_len, int mean_read_len) {
@@ -114,14 +106,13 @@ int pmx_aligner_index_digest(pmx_ctx* ctx, pmx_aligner* al, uint64_t out[5]) {
     const size_t cap = (size_t)r.ht_mask + 1;
     std::vector<HtEnt> ht(cap);
     std::vector<uint32_t> pv(cap);
-    PMX_HIP(hipMemcpyAsync(ht.data(), r.ht, cap * sizeof(HtEnt), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(pv.data(), r.ht_pv, cap * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H(ht, r.ht, cap, ctx->stream);
+    PMX_D2H_SYNC(pv, r.ht_pv, cap, ctx->stream);
     uint64_t n_pos = 0, n_keys = 0;
     for (const HtEnt& e : ht)
         if (e.key != UINT64_MAX) { ++n_keys; n_pos = std::max<uint64_t>(n_pos, (uint64_t)e.off + e.cnt); }
     std::vector<uint64_t> pos((size_t)n_pos);
-    if (n_pos) PMX_HIP(hipMemcpy(pos.data(), r.pos, n_pos * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    PMX_D2H_BLOCKING(pos.data(), r.pos, n_pos);
     uint64_t digest = 0, covered = 0;
     for (size_t s = 0; s < cap; ++s) {
         const HtEnt& e = ht[s];
@@ -185,10 +176,9 @@ int pmx_align_readset(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int 
         if (rc != PMX_OK) return rc;
         unsigned long long used = 0, st[4] = {0, 0, 0, 0}, dd[2] = {0, 0};
         PMX_TRY
-        PMX_HIP(hipMemcpyAsync(&used, al->cigar_used.p, sizeof(used), hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(st, al->stats.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(dd, al->dd_count.p, sizeof(dd), hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
+        PMX_D2H(&used, al->cigar_used, 1, ctx->stream);
+        PMX_D2H(st, al->stats, ctx->stream);
+        PMX_D2H_SYNC(dd, al->dd_count, ctx->stream);
         PMX_CATCH
         al->last_cigar_used = used;
         al->last_stats.dp_calls = (int64_t)st[0];
@@ -220,14 +210,13 @@ static int score_reads_impl(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     al->stats.ensure(4);
-    PMX_HIP(hipMemsetAsync(al->stats.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    PMX_ZERO(al->stats, 2, ctx->stream);
     const int64_t n = al->n_records;
     if (n > 0)
-        hipLaunchKernelGGL(k_sum_edits, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream, al->records.p,
-                           al->edits.p, n, al->stats.p, n_flagged ? rs->off.p : (const int64_t*)nullptr);
+        PMX_LAUNCH(k_sum_edits, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cu * 8)), dim3(256), 0, ctx->stream, al->records.p,
+                   al->edits.p, n, al->stats.p, n_flagged ? rs->off.p : (const int64_t*)nullptr);
     unsigned long long h[2] = {0, 0};
-    PMX_HIP(hipMemcpyAsync(h, al->stats.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(h, al->stats, ctx->stream);
     if (n_flagged) *n_flagged = (int64_t)h[1];
     else if (h[1]) return fail(PMX_ERR_UNSUPPORTED, "reads with flagged (overflow / unsupported) records: their edit counts are not the reference's");
     *score = -(int64_t)h[0];
@@ -341,9 +330,8 @@ int pmx_align_fetch(pmx_ctx* ctx, pmx_aligner* al, pmx_aln_record* records, int6
     if (used < 0) return (int)used;
     if (used > arena_cap || (used > 0 && !cigar_arena)) return fail(PMX_ERR_CAPACITY, "CIGAR arena buffer too small");
     if (al->n_records > 0)
-        PMX_HIP(hipMemcpyAsync(records, al->records.p, sizeof(AlnRecord) * (size_t)al->n_records, hipMemcpyDeviceToHost, ctx->stream));
-    if (used > 0) PMX_HIP(hipMemcpyAsync(cigar_arena, al->cigars.p, sizeof(uint32_t) * (size_t)used, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+        PMX_D2H(records, al->records, al->n_records, ctx->stream);
+    PMX_D2H_SYNC(cigar_arena, al->cigars, used, ctx->stream);
     return PMX_OK;
     PMX_CATCH
 }
@@ -387,8 +375,8 @@ int pmx_align_dp_batch(pmx_ctx* ctx, pmx_aligner* al, const uint8_t* seqs, const
     DevBuf<DpRes> d_res;
     d_req.alloc(req.size() * sizeof(DpReq));
     d_res.alloc((size_t)n * PMX_DP_MAX_CALLS);
-    PMX_HIP(hipMemcpyAsync(d_req.p, req.data(), req.size() * sizeof(DpReq), hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemsetAsync(d_res.p, 0xff, sizeof(DpRes) * (size_t)n * PMX_DP_MAX_CALLS, ctx->stream));
+    PMX_H2D(pmx::as<DpReq>(d_req), req, ctx->stream);
+    PMX_FILL(d_res, 0xff, (size_t)n * PMX_DP_MAX_CALLS, ctx->stream);
     DG.dp_req_base = d_req.p; DG.dp_res_base = d_res.p;
     DG.n_entries = (uint32_t)req.size();
     DG.shadow = 1;   // the requests stay posted: the launch can be repeated
@@ -402,7 +390,7 @@ int pmx_align_dp_batch(pmx_ctx* ctx, pmx_aligner* al, const uint8_t* seqs, const
             dpg_launch(ctx, al, DG, n, nullptr, dpg_waves, false);   // collect + order
             PMX_HIP(hipEventRecord(e0, ctx->stream));
             const int64_t grid = std::min<int64_t>((int64_t)ctx->n_cu * dpg_waves, (n * PMX_DP_REQ_PER_PASS + 7) / 8 + PMX_DPG_BUCKETS);
-            hipLaunchKernelGGL(k_align_dp_group, dim3((unsigned)grid), dim3(64), PMX_DPG_LDS_BYTES, ctx->stream, DG);
+            PMX_LAUNCH(k_align_dp_group, dim3((unsigned)grid), dim3(64), PMX_DPG_LDS_BYTES, ctx->stream, DG);
             PMX_HIP(hipEventRecord(e1, ctx->stream));
             PMX_HIP(hipEventSynchronize(e1));
             float ms = 0;
@@ -413,8 +401,7 @@ int pmx_align_dp_batch(pmx_ctx* ctx, pmx_aligner* al, const uint8_t* seqs, const
         if (kernel_ms) *kernel_ms = best;
     }
     std::vector<DpRes> res((size_t)n * PMX_DP_MAX_CALLS);
-    PMX_HIP(hipMemcpyAsync(res.data(), d_res.p, res.size() * sizeof(DpRes), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(res, d_res, ctx->stream);
     for (int64_t i = 0; i < n; ++i) {
         const DpRes& R = res[(size_t)i * PMX_DP_MAX_CALLS];
         pmx_dp_result& o = out[i];
@@ -467,8 +454,8 @@ int pmx_align_fetch_async(pmx_ctx* ctx, pmx_aligner* al, pmx_aln_record* records
         PMX_HIP(hipEventRecord(al->ev_results, ctx->stream));
         PMX_HIP(hipStreamWaitEvent(st, al->ev_results, 0));
     }
-    if (al->n_records > 0) PMX_HIP(hipMemcpyAsync(records, al->records.p, sizeof(AlnRecord) * (size_t)al->n_records, hipMemcpyDeviceToHost, st));
-    if (used > 0) PMX_HIP(hipMemcpyAsync(cigar_arena, al->cigars.p, sizeof(uint32_t) * (size_t)used, hipMemcpyDeviceToHost, st));
+    PMX_D2H(records, al->records, al->n_records, st);
+    PMX_D2H(cigar_arena, al->cigars, used, st);
     if (st != ctx->stream) {
         PMX_HIP(hipEventRecord(al->ev_fetched, st));
         al->fetch_pending = true;
@@ -482,7 +469,7 @@ int pmx_align_copy_records_device(pmx_ctx* ctx, pmx_aligner* al, void* d_records
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     if (al->n_records > 0)
-        PMX_HIP(hipMemcpyAsync(d_records, al->records.p, sizeof(AlnRecord) * (size_t)al->n_records, hipMemcpyDeviceToDevice, ctx->stream));
+        PMX_D2D(d_records, al->records, al->n_records, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
     PMX_CATCH
@@ -494,7 +481,7 @@ int pmx_align_copy_cigars_device(pmx_ctx* ctx, pmx_aligner* al, void* d_cigars, 
     PMX_HIP(hipSetDevice(ctx->device));
     const int64_t used = pmx_align_cigar_words(ctx, al);
     if (n_words < used) return fail(PMX_ERR_CAPACITY, "CIGAR arena buffer too small");
-    if (used > 0) PMX_HIP(hipMemcpyAsync(d_cigars, al->cigars.p, sizeof(uint32_t) * (size_t)used, hipMemcpyDeviceToDevice, ctx->stream));
+    PMX_D2D(d_cigars, al->cigars, used, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
     PMX_CATCH

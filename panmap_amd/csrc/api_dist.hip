@@ -109,7 +109,7 @@ struct RcclTransport : Transport {
         }
         PMX_NCCL(rccl().GroupEnd());
         if (rank == root && sizes[root] > 0)
-            PMX_HIP(hipMemcpyAsync((char*)d_all + offs[root], d_mine, sizes[root], hipMemcpyDeviceToDevice, st));
+            PMX_D2D((char*)d_all + offs[root], d_mine, sizes[root], st);
     }
 };
 
@@ -153,30 +153,28 @@ struct HostDirTransport : Transport {
     }
     void all_gather(hipStream_t st, const void* d_mine, size_t bytes, void* d_all) override {
         std::vector<char> mine(bytes);
-        if (bytes) PMX_HIP(hipMemcpyAsync(mine.data(), d_mine, bytes, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
+        PMX_D2H_SYNC(mine, d_mine, bytes, st);
         publish(mine);
         for (int r = 0; r < world; ++r) {
             std::vector<char> b = r == rank ? mine : take(r);
             if (b.size() != bytes) throw std::runtime_error("host transport: size mismatch in all_gather");
-            if (bytes) PMX_HIP(hipMemcpy((char*)d_all + (size_t)r * bytes, b.data(), bytes, hipMemcpyHostToDevice));
+            PMX_H2D_BLOCKING((char*)d_all + (size_t)r * bytes, b.data(), bytes);
         }
         round_done();
     }
     void gather_v(hipStream_t st, const void* d_mine, const std::vector<size_t>& sizes, const std::vector<size_t>& offs, void* d_all, int root) override {
         std::vector<char> mine(sizes[rank]);
-        if (!mine.empty()) PMX_HIP(hipMemcpyAsync(mine.data(), d_mine, mine.size(), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
+        PMX_D2H_SYNC(mine, d_mine, st);
         publish(rank == root ? std::vector<char>() : mine);
         for (int r = 0; r < world; ++r) {
             if (r == rank) continue;
             std::vector<char> b = take(r);                 // (every rank reads every file: the round doubles as a barrier)
             if (rank == root) {
                 if (b.size() != sizes[r]) throw std::runtime_error("host transport: size mismatch in gather");
-                if (!b.empty()) PMX_HIP(hipMemcpy((char*)d_all + offs[r], b.data(), b.size(), hipMemcpyHostToDevice));
+                PMX_H2D_BLOCKING((char*)d_all + offs[r], b.data(), b.size());
             }
         }
-        if (rank == root && !mine.empty()) PMX_HIP(hipMemcpy((char*)d_all + offs[root], mine.data(), mine.size(), hipMemcpyHostToDevice));
+        if (rank == root) PMX_H2D_BLOCKING((char*)d_all + offs[root], mine.data(), mine.size());
         round_done();
     }
 };
@@ -206,11 +204,10 @@ struct pmx_dist {
     std::vector<int64_t> exchange_counts(const int64_t* mine, int k) {
         const int world = tp->world;
         d_meta.ensure((size_t)k * (size_t)(world + 1));
-        PMX_HIP(hipMemcpyAsync(d_meta.p, mine, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice, ctx->stream));
+        PMX_H2D(d_meta, mine, k, ctx->stream);
         tp->all_gather(ctx->stream, d_meta.p, sizeof(int64_t) * (size_t)k, d_meta.p + k);
         std::vector<int64_t> all((size_t)k * (size_t)world);
-        PMX_HIP(hipMemcpyAsync(all.data(), d_meta.p + k, sizeof(int64_t) * all.size(), hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
+        PMX_D2H_SYNC(all, pmx::at(d_meta, k), ctx->stream);
         return all;
     }
 };
@@ -343,10 +340,10 @@ int pmx_dist_dedup_reads(pmx_dist* d, pmx_place* pl, const pmx_readset* rs, int6
         DevBuf<uint64_t> padded, all, seen;
         padded.alloc(2 * (size_t)mx);
         all.alloc(2 * (size_t)mx * (size_t)world);
-        PMX_HIP(hipMemsetAsync(padded.p, 0, sizeof(uint64_t) * 2 * (size_t)mx, ctx->stream));
+        PMX_ZERO(padded, 2 * (size_t)mx, ctx->stream);
         if (kept > 0) {
-            PMX_HIP(hipMemcpyAsync(padded.p, mine.p, sizeof(uint64_t) * (size_t)kept, hipMemcpyDeviceToDevice, ctx->stream));
-            PMX_HIP(hipMemcpyAsync(padded.p + mx, mine.p + std::max<int64_t>(n, 1), sizeof(uint64_t) * (size_t)kept, hipMemcpyDeviceToDevice, ctx->stream));
+            PMX_D2D(padded, mine, kept, ctx->stream);
+            PMX_D2D(pmx::at(padded, mx), pmx::at(mine, std::max<int64_t>(n, 1)), kept, ctx->stream);
         }
         d->tp->all_gather(ctx->stream, padded.p, sizeof(uint64_t) * 2 * (size_t)mx, all.p);
         if (lower > 0) {
@@ -354,8 +351,8 @@ int pmx_dist_dedup_reads(pmx_dist* d, pmx_place* pl, const pmx_readset* rs, int6
             int64_t at = 0;
             for (int r = 0; r < rank; ++r) {
                 if (sizes[r] == 0) continue;
-                PMX_HIP(hipMemcpyAsync(seen.p + at, all.p + (size_t)r * 2 * (size_t)mx, sizeof(uint64_t) * (size_t)sizes[r], hipMemcpyDeviceToDevice, ctx->stream));
-                PMX_HIP(hipMemcpyAsync(seen.p + lower + at, all.p + (size_t)r * 2 * (size_t)mx + (size_t)mx, sizeof(uint64_t) * (size_t)sizes[r], hipMemcpyDeviceToDevice, ctx->stream));
+                PMX_D2D(pmx::at(seen, at), pmx::at(all, (size_t)r * 2 * (size_t)mx), sizes[r], ctx->stream);
+                PMX_D2D(pmx::at(seen, lower + at), pmx::at(all, (size_t)r * 2 * (size_t)mx + (size_t)mx), sizes[r], ctx->stream);
                 at += sizes[r];
             }
             const int rc = pmx_place_dedup_drop_seen(ctx, pl, rs, seen.p, seen.p + lower, lower);
@@ -432,12 +429,11 @@ int pmx_dist_gather_alignments(pmx_dist* d, pmx_aligner* al, int root, int64_t* 
         int64_t r_at = 0, w_at = 0;
         for (int r = 0; r < world; ++r) {
             if (w_at > 0 && d->rank_records[r] > 0)
-                hipLaunchKernelGGL(k_rebase_cigars, dim3(grid_for(d->rank_records[r], 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
-                                   reinterpret_cast<pmx::aln::AlnRecord*>(d->g_records.p) + r_at, d->rank_records[r], (uint32_t)w_at);
+                PMX_LAUNCH(k_rebase_cigars, dim3(grid_for(d->rank_records[r], 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
+                           reinterpret_cast<pmx::aln::AlnRecord*>(d->g_records.p) + r_at, d->rank_records[r], (uint32_t)w_at);
             r_at += d->rank_records[r];
             w_at += d->rank_words[r];
         }
-        PMX_HIP(hipGetLastError());
         d->g_n_records = tot_r;
         d->g_n_words = tot_w;
     } else {
@@ -483,11 +479,10 @@ int pmx_dist_plan_alignments(pmx_dist* d, pmx_aligner* al, int64_t* record_base,
     d->shard_records = mine[0]; d->shard_words = mine[1]; d->shard_record_base = my_r; d->shard_word_base = my_w;
     d->s_records.ensure((size_t)std::max<int64_t>(mine[0], 1));
     if (mine[0] > 0) {
-        PMX_HIP(hipMemcpyAsync(d->s_records.p, pmx_align_device_records(al), sizeof(pmx_aln_record) * (size_t)mine[0], hipMemcpyDeviceToDevice, ctx->stream));
+        PMX_D2D(d->s_records, pmx_align_device_records(al), mine[0], ctx->stream);
         if (my_w > 0)
-            hipLaunchKernelGGL(k_rebase_cigars, dim3(grid_for(mine[0], 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<pmx::aln::AlnRecord*>(d->s_records.p), mine[0], (uint32_t)my_w);
-        PMX_HIP(hipGetLastError());
+            PMX_LAUNCH(k_rebase_cigars, dim3(grid_for(mine[0], 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
+                       reinterpret_cast<pmx::aln::AlnRecord*>(d->s_records.p), mine[0], (uint32_t)my_w);
     }
     if (record_base) *record_base = my_r;
     if (word_base) *word_base = my_w;
@@ -515,9 +510,9 @@ int pmx_dist_fetch_shard_async(pmx_dist* d, pmx_aligner* al, pmx_aln_record* rec
         PMX_HIP(hipStreamWaitEvent(st, d->ev_gathered, 0));
     }
     if (d->shard_records > 0)
-        PMX_HIP(hipMemcpyAsync(records_all + d->shard_record_base, d->s_records.p, sizeof(pmx_aln_record) * (size_t)d->shard_records, hipMemcpyDeviceToHost, st));
+        PMX_D2H(records_all + d->shard_record_base, d->s_records, d->shard_records, st);
     if (d->shard_words > 0)
-        PMX_HIP(hipMemcpyAsync(cigars_all + d->shard_word_base, pmx_align_device_cigars(al), sizeof(uint32_t) * (size_t)d->shard_words, hipMemcpyDeviceToHost, st));
+        PMX_D2H(cigars_all + d->shard_word_base, pmx_align_device_cigars(al), d->shard_words, st);
     if (st != ctx->stream) {
         PMX_HIP(hipEventRecord(d->ev_fetched, st));
         d->fetch_pending = true;
@@ -543,9 +538,8 @@ int pmx_dist_fetch_gathered(pmx_dist* d, pmx_aln_record* records, int64_t n_reco
     PMX_TRY
     pmx_ctx* ctx = d->ctx;
     PMX_HIP(hipSetDevice(ctx->device));
-    if (d->g_n_records > 0) PMX_HIP(hipMemcpyAsync(records, d->g_records.p, sizeof(pmx_aln_record) * (size_t)d->g_n_records, hipMemcpyDeviceToHost, ctx->stream));
-    if (d->g_n_words > 0) PMX_HIP(hipMemcpyAsync(cigar_arena, d->g_cigars.p, sizeof(uint32_t) * (size_t)d->g_n_words, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H(records, d->g_records, d->g_n_records, ctx->stream);
+    PMX_D2H_SYNC(cigar_arena, d->g_cigars, d->g_n_words, ctx->stream);
     return PMX_OK;
     PMX_CATCH
 }
@@ -565,8 +559,8 @@ int pmx_dist_fetch_gathered_async(pmx_dist* d, pmx_aln_record* records, int64_t 
         PMX_HIP(hipEventRecord(d->ev_gathered, ctx->stream));
         PMX_HIP(hipStreamWaitEvent(st, d->ev_gathered, 0));
     }
-    if (d->g_n_records > 0) PMX_HIP(hipMemcpyAsync(records, d->g_records.p, sizeof(pmx_aln_record) * (size_t)d->g_n_records, hipMemcpyDeviceToHost, st));
-    if (d->g_n_words > 0) PMX_HIP(hipMemcpyAsync(cigar_arena, d->g_cigars.p, sizeof(uint32_t) * (size_t)d->g_n_words, hipMemcpyDeviceToHost, st));
+    PMX_D2H(records, d->g_records, d->g_n_records, st);
+    PMX_D2H(cigar_arena, d->g_cigars, d->g_n_words, st);
     if (st != ctx->stream) {
         PMX_HIP(hipEventRecord(d->ev_fetched, st));
         d->fetch_pending = true;

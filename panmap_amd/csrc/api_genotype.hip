@@ -163,13 +163,13 @@ int run_core(pmx_ctx* ctx, pmx_pileup* pu, const pmx_aln_record* h_recs, int64_t
     pu->s_idx.ensure(sw.s_idx.size());
     hipStream_t st = ctx->stream;
     if (n > 0) {
-        PMX_HIP(hipMemcpyAsync(pu->rinfo.p, sw.rinfo.data(), (size_t)n, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(pu->rank.p, sw.rank.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+        PMX_H2D(pu->rinfo, sw.rinfo, n, st);
+        PMX_H2D(pu->rank, sw.rank, n, st);
     }
-    PMX_HIP(hipMemcpyAsync(pu->first_ge.p, sw.first_ge.data(), sizeof(uint32_t) * sw.first_ge.size(), hipMemcpyHostToDevice, st));
+    PMX_H2D(pu->first_ge, sw.first_ge, st);
     if (!sw.s_rs.empty()) {
-        PMX_HIP(hipMemcpyAsync(pu->s_rs.p, sw.s_rs.data(), sizeof(int32_t) * sw.s_rs.size(), hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(pu->s_idx.p, sw.s_idx.data(), sizeof(uint32_t) * sw.s_idx.size(), hipMemcpyHostToDevice, st));
+        PMX_H2D(pu->s_rs, sw.s_rs, st);
+        PMX_H2D(pu->s_idx, sw.s_idx, st);
     }
     PileupArgs a;
     memset(&a, 0, sizeof(a));
@@ -182,13 +182,12 @@ int run_core(pmx_ctx* ctx, pmx_pileup* pu, const pmx_aln_record* h_recs, int64_t
     a.min_baseq = pp.min_baseq; a.max_baseq = pp.max_baseq; a.delta_baseq = pp.delta_baseq; a.cap_mapq = pp.cap_mapq;
     const int64_t n_units = paired ? n / 2 : n;
     timer_begin(ctx, "pileup_quals");
-    if (n_units > 0) hipLaunchKernelGGL(k_pileup_quals, dim3(grid_for(n_units, 256, ctx->n_cu * 16)), dim3(256), 0, st, a);
+    if (n_units > 0) PMX_LAUNCH(k_pileup_quals, dim3(grid_for(n_units, 256, ctx->n_cu * 16)), dim3(256), 0, st, a);
     timer_end(ctx, "pileup_quals", 1);
     const int64_t n_windows = (ref_len + PLP_WINDOW - 1) / PLP_WINDOW;
     timer_begin(ctx, "pileup");
-    hipLaunchKernelGGL(k_pileup_window, dim3((unsigned)std::min<int64_t>(n_windows, (int64_t)ctx->n_cu * 64)), dim3(256), 0, st, a);
+    PMX_LAUNCH(k_pileup_window, dim3((unsigned)std::min<int64_t>(n_windows, (int64_t)ctx->n_cu * 64)), dim3(256), 0, st, a);
     timer_end(ctx, "pileup", 1);
-    PMX_HIP(hipGetLastError());
     PMX_HIP(hipStreamSynchronize(st));
     pu->h_rinfo.swap(sw.rinfo);
     pu->h_rank.swap(sw.rank);
@@ -233,9 +232,8 @@ int pmx_pileup_run(pmx_ctx* ctx, pmx_pileup* pu, pmx_aligner* al, const pmx_read
     if (words < 0) return (int)words;
     std::vector<pmx_aln_record> recs((size_t)std::max<int64_t>(n, 1));
     std::vector<int64_t> off((size_t)n + 1);
-    if (n > 0) PMX_HIP(hipMemcpyAsync(recs.data(), pmx_align_device_records(al), sizeof(pmx_aln_record) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(off.data(), rs->off.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H(recs, pmx_align_device_records(al), n, ctx->stream);
+    PMX_D2H_SYNC(off, rs->off, (size_t)n + 1, ctx->stream);
     if (rs->has_qual && rs->off0 != 0) return fail(PMX_ERR_ARG, "pileup: qualities need a read set whose offsets start at 0");
     return run_core(ctx, pu, recs.data(), n, words, off.data(), (const pmx_aln_record*)pmx_align_device_records(al),
                     (const uint32_t*)pmx_align_device_cigars(al), rs->ascii.p, rs->has_qual ? rs->qual.p : nullptr, rs->off.p, ref_len, paired,
@@ -258,13 +256,13 @@ int pmx_pileup_run_records(pmx_ctx* ctx, pmx_pileup* pu, const pmx_aln_record* r
     pu->ascii.ensure((size_t)total + 1);
     pu->off.ensure((size_t)n + 1);
     hipStream_t st = ctx->stream;
-    if (n > 0) PMX_HIP(hipMemcpyAsync(pu->recs.p, records, sizeof(pmx_aln_record) * (size_t)n, hipMemcpyHostToDevice, st));
-    if (n_words > 0) PMX_HIP(hipMemcpyAsync(pu->cigars.p, cigar_arena, sizeof(uint32_t) * (size_t)n_words, hipMemcpyHostToDevice, st));
-    if (total > 0) PMX_HIP(hipMemcpyAsync(pu->ascii.p, concat, (size_t)total, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(pu->off.p, offsets, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, st));
+    PMX_H2D(pu->recs, records, n, st);
+    PMX_H2D(pu->cigars, cigar_arena, n_words, st);
+    PMX_H2D(pu->ascii, concat, total, st);
+    PMX_H2D(pu->off, offsets, (size_t)n + 1, st);
     if (qual_concat) {
         pu->qual.ensure((size_t)total + 1);
-        if (total > 0) PMX_HIP(hipMemcpyAsync(pu->qual.p, qual_concat, (size_t)total, hipMemcpyHostToDevice, st));
+        PMX_H2D(pu->qual, qual_concat, total, st);
     }
     return run_core(ctx, pu, records, n, n_words, offsets, pu->recs.p, pu->cigars.p, pu->ascii.p, qual_concat ? pu->qual.p : nullptr, pu->off.p, ref_len,
                     paired, revcomp_mate2, names_concat, name_offsets, pp);
@@ -276,8 +274,8 @@ int pmx_pileup_fetch(pmx_ctx* ctx, pmx_pileup* pu, uint32_t* hist, uint32_t* aux
     if (pu->ref_len <= 0) return fail(PMX_ERR_ARG, "pileup: nothing has been run");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    if (hist) PMX_HIP(hipMemcpyAsync(hist, pu->hist.p, sizeof(uint32_t) * (size_t)pu->ref_len * PLP_HIST, hipMemcpyDeviceToHost, ctx->stream));
-    if (aux) PMX_HIP(hipMemcpyAsync(aux, pu->aux.p, sizeof(uint32_t) * (size_t)pu->ref_len * PLP_AUX, hipMemcpyDeviceToHost, ctx->stream));
+    if (hist) PMX_D2H(hist, pu->hist, (size_t)pu->ref_len * PLP_HIST, ctx->stream);
+    if (aux) PMX_D2H(aux, pu->aux, (size_t)pu->ref_len * PLP_AUX, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
     PMX_CATCH
@@ -300,17 +298,15 @@ int pmx_pileup_bias(pmx_ctx* ctx, pmx_pileup* pu, const int32_t* positions, cons
     pu->b_ref.ensure((size_t)n_sites);
     pu->b_out.ensure((size_t)n_sites * PLB_CELLS);
     hipStream_t st = ctx->stream;
-    PMX_HIP(hipMemcpyAsync(pu->b_sites.p, positions, sizeof(int32_t) * (size_t)n_sites, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(pu->b_ref.p, ref_bases, (size_t)n_sites, hipMemcpyHostToDevice, st));
+    PMX_H2D(pu->b_sites, positions, n_sites, st);
+    PMX_H2D(pu->b_ref, ref_bases, n_sites, st);
     PileupBiasArgs b;
     b.run = pu->last;
     b.sites = pu->b_sites.p; b.ref_bases = pu->b_ref.p; b.n_sites = n_sites; b.out = pu->b_out.p;
     timer_begin(ctx, "pileup_bias");
-    hipLaunchKernelGGL(k_pileup_bias, dim3((unsigned)std::min<int64_t>(n_sites, (int64_t)ctx->n_cu * 16)), dim3(256), 0, st, b);
+    PMX_LAUNCH(k_pileup_bias, dim3((unsigned)std::min<int64_t>(n_sites, (int64_t)ctx->n_cu * 16)), dim3(256), 0, st, b);
     timer_end(ctx, "pileup_bias", 1);
-    PMX_HIP(hipGetLastError());
-    PMX_HIP(hipMemcpyAsync(out, pu->b_out.p, sizeof(uint32_t) * (size_t)n_sites * PLB_CELLS, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(out, pu->b_out, (size_t)n_sites * PLB_CELLS, st);
     return PMX_OK;
     PMX_CATCH
 }

@@ -406,10 +406,9 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
     d_mine.alloc(mx);
     d_all.alloc(mx * (size_t)world);
     std::vector<char> all(mx * (size_t)world);
-    PMX_HIP(hipMemcpyAsync(d_mine.p, mine.data(), mx, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(d_mine, mine, mx, ctx->stream);
     dist_all_gather(m->dist, d_mine.p, mx, d_all.p);
-    PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(all, d_all, ctx->stream);
     struct Run { const int64_t *len, *mult; const uint64_t* h; const uint8_t* v; const int32_t* amp; int64_t n, i, at; };
     std::vector<Run> runs;
     for (int r = 0; r < world; ++r) {
@@ -459,10 +458,9 @@ void score_rows(pmx_ctx* ctx, pmx_meta* m, int64_t first, int64_t count, uint16_
     const int64_t threads = count * (int64_t)words;
     const dim3 grid(grid_for(threads, 256, ctx->n_cu * 16)), block(256);
     meta_with_planes(m->longest, [&](auto planes) {
-        hipLaunchKernelGGL(k_meta_scores<decltype(planes)::value>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count,
-                           m->mask_fwd.p, m->mask_rev.p, words, n_cand, out);
+        PMX_LAUNCH(k_meta_scores<decltype(planes)::value>, grid, block, 0, ctx->stream, m->d_read_off.p + first, m->d_seed_uid.p, m->d_seed_rev.p, count,
+                   m->mask_fwd.p, m->mask_rev.p, words, n_cand, out);
     });
-    PMX_HIP(hipGetLastError());
 }
 
 // a read set made inside a step: released when the step ends, on every way out of it (the step's caller has set the device)
@@ -592,7 +590,7 @@ int MetaReads::seedmer_lists() {
     if (lds > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_seed_histogram, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     r_off.assign((size_t)n_reads + 1, 0);
     lc.d_ctr.alloc(PMX_CTR_N);
-    PMX_HIP(hipMemsetAsync(lc.d_ctr.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
+    PMX_ZERO(lc.d_ctr, PMX_CTR_N, ctx->stream);
     for (int64_t c0 = 0; c0 < n_reads; c0 += kListChunk) {
         const int rc = seedmer_lists_chunk(lc, c0, std::min(n_reads, c0 + kListChunk) - c0);
         if (rc != PMX_OK) return rc;
@@ -612,14 +610,12 @@ int MetaReads::seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc) {
     if (rc != PMX_OK) return rc;
     const size_t slots = (size_t)std::max<int64_t>(rs->n_words, 1) * 32;
     lc.d_lh.ensure(slots); lc.d_lr.ensure(slots); lc.d_ln.ensure((size_t)nc);
-    PMX_HIP(hipMemsetAsync(lc.d_ln.p, 0, sizeof(uint32_t) * (size_t)nc, ctx->stream));
-    hipLaunchKernelGGL(k_seed_histogram, dim3(grid_for(nc, PMX_SEED_BLOCK, ctx->n_cu * 16)), dim3(PMX_SEED_BLOCK), lc.lds, ctx->stream, rs->words.p, rs->amb.p,
-                       rs->woff.p, rs->off.p, (int64_t)0, nc, lc.sp, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0, lc.d_ctr.p,
-                       (const uint8_t*)nullptr, (const uint8_t*)nullptr, 0, lc.d_lh.p, lc.d_lr.p, lc.d_ln.p);
-    PMX_HIP(hipGetLastError());
+    PMX_ZERO(lc.d_ln, nc, ctx->stream);
+    PMX_LAUNCH(k_seed_histogram, dim3(grid_for(nc, PMX_SEED_BLOCK, ctx->n_cu * 16)), dim3(PMX_SEED_BLOCK), lc.lds, ctx->stream, rs->words.p, rs->amb.p,
+               rs->woff.p, rs->off.p, (int64_t)0, nc, lc.sp, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0, lc.d_ctr.p,
+               (const uint8_t*)nullptr, (const uint8_t*)nullptr, 0, lc.d_lh.p, lc.d_lr.p, lc.d_ln.p);
     std::vector<uint32_t> h_n((size_t)nc);
-    PMX_HIP(hipMemcpyAsync(h_n.data(), lc.d_ln.p, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(h_n, lc.d_ln, nc, ctx->stream);
     std::vector<int64_t> o_off((size_t)nc + 1, 0);
     for (int64_t i = 0; i < nc; ++i) o_off[(size_t)i + 1] = o_off[(size_t)i] + (int64_t)h_n[(size_t)i];
     const int64_t tot = o_off[(size_t)nc];
@@ -628,13 +624,11 @@ int MetaReads::seedmer_lists_chunk(ListChunks& lc, int64_t c0, int64_t nc) {
     r_rev.resize(base + (size_t)tot);
     if (tot > 0) {
         lc.d_ooff.ensure((size_t)nc + 1); lc.d_oh.ensure((size_t)tot); lc.d_or.ensure((size_t)tot);
-        PMX_HIP(hipMemcpyAsync(lc.d_ooff.p, o_off.data(), sizeof(int64_t) * ((size_t)nc + 1), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_meta_gather_lists, dim3(grid_for(nc * 8, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, lc.d_lh.p, lc.d_lr.p, rs->woff.p,
-                           lc.d_ooff.p, nc, lc.d_oh.p, lc.d_or.p);
-        PMX_HIP(hipGetLastError());
-        PMX_HIP(hipMemcpyAsync(r_hash.data() + base, lc.d_oh.p, sizeof(uint64_t) * (size_t)tot, hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(r_rev.data() + base, lc.d_or.p, (size_t)tot, hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
+        PMX_H2D(lc.d_ooff, o_off, (size_t)nc + 1, ctx->stream);
+        PMX_LAUNCH(k_meta_gather_lists, dim3(grid_for(nc * 8, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, lc.d_lh.p, lc.d_lr.p, rs->woff.p,
+                   lc.d_ooff.p, nc, lc.d_oh.p, lc.d_or.p);
+        PMX_D2H(r_hash.data() + base, lc.d_oh, tot, ctx->stream);
+        PMX_D2H_SYNC(r_rev.data() + base, lc.d_or, tot, ctx->stream);
     }
     for (int64_t i = 0; i < nc; ++i) r_off[(size_t)(c0 + i) + 1] = (int64_t)base + o_off[(size_t)i + 1];
     return PMX_OK;
@@ -740,11 +734,11 @@ void MetaReads::upload_lists() {
     m->d_seed_uid.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
     m->d_seed_rev.ensure((size_t)std::max<int64_t>(m->n_seedmers, 1));
     m->d_uniq.ensure(std::max<size_t>(m->h_uniq.size(), 1));
-    PMX_HIP(hipMemcpyAsync(m->d_read_off.p, m->h_read_off.data(), sizeof(int64_t) * ((size_t)m->n_reads + 1), hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(m->d_read_off, m->h_read_off, (size_t)m->n_reads + 1, ctx->stream);
     if (m->n_seedmers > 0) {
-        PMX_HIP(hipMemcpyAsync(m->d_seed_uid.p, uid.data(), sizeof(uint32_t) * (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->d_seed_rev.p, m->h_seed_rev.data(), (size_t)m->n_seedmers, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->d_uniq.p, m->h_uniq.data(), sizeof(uint64_t) * m->h_uniq.size(), hipMemcpyHostToDevice, ctx->stream));
+        PMX_H2D(m->d_seed_uid, uid, m->n_seedmers, ctx->stream);
+        PMX_H2D(m->d_seed_rev, m->h_seed_rev, m->n_seedmers, ctx->stream);
+        PMX_H2D(m->d_uniq, m->h_uniq, ctx->stream);
     }
     PMX_HIP(hipStreamSynchronize(ctx->stream));
 }
@@ -814,16 +808,16 @@ void own_row_slice(pmx_meta* m) {
 void build_masks(pmx_ctx* ctx, pmx_meta* m) {
     const int n_cand = (int)m->cand.size(), words = (n_cand + 63) / 64;
     m->d_cand.ensure((size_t)n_cand);
-    PMX_HIP(hipMemcpyAsync(m->d_cand.p, m->cand.data(), sizeof(uint32_t) * (size_t)n_cand, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(m->d_cand, m->cand, n_cand, ctx->stream);
     const size_t mask_words = m->h_uniq.size() * (size_t)words;
     m->mask_fwd.ensure(std::max<size_t>(mask_words, 1));
     m->mask_rev.ensure(std::max<size_t>(mask_words, 1));
-    PMX_HIP(hipMemsetAsync(m->mask_fwd.p, 0, sizeof(unsigned long long) * std::max<size_t>(mask_words, 1), ctx->stream));
-    PMX_HIP(hipMemsetAsync(m->mask_rev.p, 0, sizeof(unsigned long long) * std::max<size_t>(mask_words, 1), ctx->stream));
+    PMX_ZERO(m->mask_fwd, std::max<size_t>(mask_words, 1), ctx->stream);
+    PMX_ZERO(m->mask_rev, std::max<size_t>(mask_words, 1), ctx->stream);
     if (m->n_changes > 0)
-        hipLaunchKernelGGL(k_meta_mask_events, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, m->ch_key.p, m->ch_pc.p,
-                           m->ch_cc.p, m->ch_node.p, m->n_changes, m->subtree_end.p, m->d_uniq.p, (int64_t)m->h_uniq.size(), m->d_cand.p, n_cand, words,
-                           m->mask_fwd.p, m->mask_rev.p);
+        PMX_LAUNCH(k_meta_mask_events, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, m->ch_key.p, m->ch_pc.p,
+                   m->ch_cc.p, m->ch_node.p, m->n_changes, m->subtree_end.p, m->d_uniq.p, (int64_t)m->h_uniq.size(), m->d_cand.p, n_cand, words,
+                   m->mask_fwd.p, m->mask_rev.p);
 }
 
 // ---- pmx_meta_em's steps
@@ -897,14 +891,12 @@ void EmStage::group_columns(const std::vector<uint64_t>& digests, int n_ranks) {
 // Reads: m->score.  Leaves: the columns and `rows`, the reads that score somewhere (the others carry no weight,
 // src/mgsr.cpp:8170-8173) and that --discard keeps.
 void EmStage::kept_rows_one_rank() {
-    hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, n_reads, n_cand, d_dig.p);
+    PMX_LAUNCH(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, n_reads, n_cand, d_dig.p);
     std::vector<uint64_t> dig(2 * (size_t)n_cand);
-    PMX_HIP(hipMemcpyAsync(dig.data(), d_dig.p, sizeof(uint64_t) * dig.size(), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(dig, d_dig, st);
     group_columns(dig, 1);
     std::vector<uint16_t> h_score((size_t)n_reads * (size_t)n_cand);
-    PMX_HIP(hipMemcpyAsync(h_score.data(), m->score.p, sizeof(uint16_t) * h_score.size(), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(h_score, m->score, st);
     for (int64_t r = 0; r < n_reads; ++r) {
         int mx = 0;
         for (int c = 0; c < n_cand; ++c) mx = std::max<int>(mx, h_score[(size_t)r * (size_t)n_cand + (size_t)c]);
@@ -926,16 +918,14 @@ void EmStage::kept_rows_dist() {
     DevBuf<char> d_mine, d_all;
     d_mine.alloc(part_bytes);
     d_all.alloc(part_bytes * (size_t)world);
-    PMX_HIP(hipMemsetAsync(d_mine.p, 0, part_bytes, st));
-    hipLaunchKernelGGL(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, m->row_count, n_cand, (uint64_t*)d_mine.p);
+    PMX_ZERO(d_mine, part_bytes, st);
+    PMX_LAUNCH(k_meta_column_digest, dim3((n_cand + 63) / 64), dim3(64), 0, st, m->score.p, m->row_count, n_cand, (uint64_t*)d_mine.p);
     if (m->row_count > 0)
-        hipLaunchKernelGGL(k_meta_row_keep, dim3(grid_for(m->row_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->score.p, m->row_count, n_cand,
-                           m->d_read_off.p + m->row_first, mp->discard, (uint8_t*)(d_mine.p + dig_bytes));
-    PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_meta_row_keep, dim3(grid_for(m->row_count * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->score.p, m->row_count, n_cand,
+                   m->d_read_off.p + m->row_first, mp->discard, (uint8_t*)(d_mine.p + dig_bytes));
     dist_all_gather(m->dist, d_mine.p, part_bytes, d_all.p);
     std::vector<char> all(part_bytes * (size_t)world);
-    PMX_HIP(hipMemcpyAsync(all.data(), d_all.p, all.size(), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(all, d_all, st);
     std::vector<uint64_t> dig(2 * (size_t)n_cand * (size_t)world);
     for (int r = 0; r < world; ++r) memcpy(&dig[2 * (size_t)n_cand * (size_t)r], all.data() + (size_t)r * part_bytes, dig_bytes);
     group_columns(dig, world);
@@ -1006,11 +996,11 @@ void EmStage::upload_rows() {
     d_rows.alloc((size_t)e_count); d_tab_off.alloc((size_t)e_count); d_tab.alloc(tab.size()); d_weight.alloc((size_t)e_count);
     d_denom.alloc((size_t)e_count); d_llh.alloc((size_t)e_count);
     if (e_count > 0) {
-        PMX_HIP(hipMemcpyAsync(d_rows.p, loc_rows.data(), sizeof(int64_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_tab_off.p, tab_off.data() + e_first, sizeof(uint32_t) * (size_t)e_count, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_weight.p, weight.data() + e_first, sizeof(double) * (size_t)e_count, hipMemcpyHostToDevice, st));
+        PMX_H2D(d_rows, loc_rows, e_count, st);
+        PMX_H2D(d_tab_off, tab_off.data() + e_first, e_count, st);
+        PMX_H2D(d_weight, weight.data() + e_first, e_count, st);
     }
-    PMX_HIP(hipMemcpyAsync(d_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    PMX_H2D(d_tab, tab, st);
     d_bsum.alloc((size_t)slot_bsum);
     if (m->dist) d_gbsum.alloc((size_t)slot_bsum * (size_t)world);
     bsum_all = m->dist ? d_gbsum.p : d_bsum.p;
@@ -1062,11 +1052,11 @@ EmRound::EmRound(EmStage* stage, const std::vector<int>& cols) : S(stage), m(sta
     S->d_cols.ensure((size_t)n_cols); S->d_props.ensure((size_t)n_cols); S->d_out.ensure((size_t)n_cols); S->d_part.ensure((size_t)S->slot_chunks * (size_t)n_cols);
     if (m->dist) S->d_gpart.ensure((size_t)S->slot_chunks * (size_t)n_cols * (size_t)S->world);
     part_all = m->dist ? S->d_gpart.p : S->d_part.p;
-    PMX_HIP(hipMemcpyAsync(S->d_cols.p, cols.data(), sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    PMX_H2D(S->d_cols, cols, n_cols, st);
     d_p0.alloc((size_t)n_cols); d_p1.alloc((size_t)n_cols); d_p2.alloc((size_t)n_cols); d_sq.alloc((size_t)n_cols);
     d_ctl.alloc(1);
     memset(&h_ctl, 0, sizeof(h_ctl));
-    PMX_HIP(hipMemcpyAsync(d_ctl.p, &h_ctl, sizeof(h_ctl), hipMemcpyHostToDevice, st));
+    PMX_H2D(d_ctl, &h_ctl, 1, st);
     d_done = &d_ctl.p->done;
     // the in-order sums of the small kernels read a copy of the vector in LDS (2 x n_cols doubles at most); beyond 160 KB a
     // scratch vector in global memory stands in.  The 160 KB of a workgroup hold the kernels' static __shared__ words too
@@ -1085,30 +1075,30 @@ EmRound::EmRound(EmStage* stage, const std::vector<int>& cols) : S(stage), m(sta
 }
 
 void EmRound::denoms(const double* pr) {
-    hipLaunchKernelGGL(k_meta_denoms, dim3(grid_for(S->e_count * 64, 256, S->ctx->n_cu * 8)), dim3(256), 0, st, S->score_p, S->n_cand, S->d_cols.p, n_cols, pr,
-                       S->d_rows.p, S->e_count, S->d_tab_off.p, S->d_tab.p, S->d_weight.p, S->d_denom.p, S->d_llh.p, d_done);
+    PMX_LAUNCH(k_meta_denoms, dim3(grid_for(S->e_count * 64, 256, S->ctx->n_cu * 8)), dim3(256), 0, st, S->score_p, S->n_cand, S->d_cols.p, n_cols, pr,
+               S->d_rows.p, S->e_count, S->d_tab_off.p, S->d_tab.p, S->d_weight.p, S->d_denom.p, S->d_llh.p, d_done);
 }
 
 // updateProps (src/mgsr.cpp:4341-4372) + normalizeProps
 void EmRound::em_step(const double* from, double* to) {
     if (S->e_count > 0) {
         denoms(from);
-        hipLaunchKernelGGL(k_meta_colsum, dim3((n_cols + 63) / 64, S->loc_chunks), dim3(64), 0, st, S->score_p, S->n_cand, S->d_cols.p, n_cols, from, S->d_rows.p,
-                           S->e_count, kColsumChunk, S->d_tab_off.p, S->d_tab.p, S->d_weight.p, S->d_denom.p, S->d_part.p, d_done);
+        PMX_LAUNCH(k_meta_colsum, dim3((n_cols + 63) / 64, S->loc_chunks), dim3(64), 0, st, S->score_p, S->n_cand, S->d_cols.p, n_cols, from, S->d_rows.p,
+                   S->e_count, kColsumChunk, S->d_tab_off.p, S->d_tab.p, S->d_weight.p, S->d_denom.p, S->d_part.p, d_done);
     }
     if (m->dist) dist_all_gather(m->dist, S->d_part.p, sizeof(double) * (size_t)S->slot_chunks * (size_t)n_cols, S->d_gpart.p);
-    hipLaunchKernelGGL(k_meta_fold, dim3((n_cols + 63) / 64), dim3(64), 0, st, part_all, S->n_chunks, n_cols, S->inv_total, S->d_out.p, d_done);
-    hipLaunchKernelGGL(k_em_normalize, dim3(1), dim3(256), em_work ? 0 : sizeof(double) * (size_t)n_cols, st, S->d_out.p, to, n_cols, d_ctl.p, em_work);
+    PMX_LAUNCH(k_meta_fold, dim3((n_cols + 63) / 64), dim3(64), 0, st, part_all, S->n_chunks, n_cols, S->inv_total, S->d_out.p, d_done);
+    PMX_LAUNCH(k_em_normalize, dim3(1), dim3(256), em_work ? 0 : sizeof(double) * (size_t)n_cols, st, S->d_out.p, to, n_cols, d_ctl.p, em_work);
 }
 
 // getExp (src/mgsr.cpp:4385-4388)
 void EmRound::log_likelihood(const double* pr, int which) {
     if (S->e_count > 0) {
         denoms(pr);
-        hipLaunchKernelGGL(k_meta_sum_blocks, dim3((unsigned)((S->loc_bsum + 3) / 4)), dim3(256), 0, st, S->d_llh.p, S->e_count, S->d_bsum.p, d_done);
+        PMX_LAUNCH(k_meta_sum_blocks, dim3((unsigned)((S->loc_bsum + 3) / 4)), dim3(256), 0, st, S->d_llh.p, S->e_count, S->d_bsum.p, d_done);
     }
     if (m->dist) dist_all_gather(m->dist, S->d_bsum.p, sizeof(double) * (size_t)S->slot_bsum, S->d_gbsum.p);
-    hipLaunchKernelGGL(k_em_store_llh, dim3(1), dim3(64), 0, st, S->bsum_all, S->n_bsum, d_ctl.p, which);
+    PMX_LAUNCH(k_em_store_llh, dim3(1), dim3(64), 0, st, S->bsum_all, S->n_bsum, d_ctl.p, which);
 }
 
 // runSquareEM (src/mgsr.cpp:4394-4443) from uniform proportions, in batches of 16 iterations between two looks at the convergence flag.
@@ -1116,28 +1106,25 @@ void EmRound::log_likelihood(const double* pr, int which) {
 void EmRound::run(std::vector<double>& props) {
     const pmx_meta_params* mp = S->mp;
     props.assign((size_t)n_cols, 1.0 / (double)n_cols);
-    PMX_HIP(hipMemcpyAsync(S->d_props.p, props.data(), sizeof(double) * (size_t)n_cols, hipMemcpyHostToDevice, st));
+    PMX_H2D(S->d_props, props, n_cols, st);
     const int look_every = 16;
     for (int iter = 0; iter < mp->em_max_iterations;) {
         const int batch = std::min(look_every, mp->em_max_iterations - iter);
         for (int b = 0; b < batch; ++b) {
-            hipLaunchKernelGGL(k_em_copy, dim3(1), dim3(256), 0, st, S->d_props.p, d_p0.p, n_cols, d_ctl.p);
+            PMX_LAUNCH(k_em_copy, dim3(1), dim3(256), 0, st, S->d_props.p, d_p0.p, n_cols, d_ctl.p);
             em_step(d_p0.p, d_p1.p);
             em_step(d_p1.p, d_p2.p);
-            hipLaunchKernelGGL(k_em_extrapolate, dim3(1), dim3(256), em_work ? 0 : 2 * sizeof(double) * (size_t)n_cols, st, d_p0.p, d_p1.p, d_p2.p, d_sq.p, n_cols, d_ctl.p, em_work);
+            PMX_LAUNCH(k_em_extrapolate, dim3(1), dim3(256), em_work ? 0 : 2 * sizeof(double) * (size_t)n_cols, st, d_p0.p, d_p1.p, d_p2.p, d_sq.p, n_cols, d_ctl.p, em_work);
             log_likelihood(d_p2.p, 0);
             log_likelihood(d_sq.p, 1);
-            hipLaunchKernelGGL(k_em_choose, dim3(1), dim3(256), 0, st, d_p0.p, d_p2.p, d_sq.p, S->d_props.p, n_cols, d_ctl.p, mp->em_convergence,
-                               mp->em_delta_threshold);
+            PMX_LAUNCH(k_em_choose, dim3(1), dim3(256), 0, st, d_p0.p, d_p2.p, d_sq.p, S->d_props.p, n_cols, d_ctl.p, mp->em_convergence,
+                       mp->em_delta_threshold);
         }
-        PMX_HIP(hipGetLastError());
-        PMX_HIP(hipMemcpyAsync(&h_ctl, d_ctl.p, sizeof(h_ctl), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
+        PMX_D2H_SYNC(&h_ctl, d_ctl, 1, st);
         iter += batch;
         if (h_ctl.done) break;
     }
-    PMX_HIP(hipMemcpyAsync(props.data(), S->d_props.p, sizeof(double) * (size_t)n_cols, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(props, S->d_props, n_cols, st);
 }
 
 // removeLowPropNodes (src/mgsr.cpp:4445-4490), called after EVERY round including the last allowed one (src/main.cpp:1263-1271):
@@ -1204,14 +1191,14 @@ int pmx_meta_create(pmx_ctx* ctx, const pmx_index* idx_std, const pmx_index* idx
         for (uint64_t q = O->offsets[v]; q < O->offsets[v + 1]; ++q) node[q] = (uint32_t)v;
     m->ch_key.alloc((size_t)c); m->ch_pc.alloc((size_t)c); m->ch_cc.alloc((size_t)c); m->ch_node.alloc((size_t)c); m->subtree_end.alloc((size_t)n);
     if (c > 0) {
-        PMX_HIP(hipMemcpyAsync(m->ch_key.p, O->hash.data(), sizeof(uint64_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->ch_pc.p, O->parent_count.data(), sizeof(int16_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->ch_cc.p, O->child_count.data(), sizeof(int16_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(m->ch_node.p, node.data(), sizeof(uint32_t) * (size_t)c, hipMemcpyHostToDevice, ctx->stream));
+        PMX_H2D(m->ch_key, O->hash, c, ctx->stream);
+        PMX_H2D(m->ch_pc, O->parent_count, c, ctx->stream);
+        PMX_H2D(m->ch_cc, O->child_count, c, ctx->stream);
+        PMX_H2D(m->ch_node, node, c, ctx->stream);
     }
     // (copies on the context's stream: synchronous null-stream copies against its blocking CU-masked queue are a suspect of
     //  the unexplained stalls)
-    PMX_HIP(hipMemcpyAsync(m->subtree_end.p, end.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(m->subtree_end, end, n, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     const int rc = pmx_place_create(ctx, idx_std, &m->placer);
     if (rc != PMX_OK) return rc;
@@ -1333,8 +1320,7 @@ int pmx_meta_scores(pmx_ctx* ctx, pmx_meta* m, uint16_t* out, int64_t cap) {
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     if (n > 0) {
-        PMX_HIP(hipMemcpyAsync(out, m->score.p, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
+        PMX_D2H_SYNC(out, m->score, n, ctx->stream);
     }
     return PMX_OK;
     PMX_CATCH

@@ -114,10 +114,27 @@ struct PlaceSwitches {
     }
 };
 
+// The host reaches the device counters through these two alone.  counters_zero clears [first, first + n) and drops the
+// host's snapshot of them; with n == 0 it only drops it, which is what a caller does before it launches kernels that count
+// into them.  Zeroing PMX_CTR_COMPACT alone keeps the snapshot: that counter is k_table_compact's cursor, and the host never
+// reads it.
+void counters_zero(pmx_ctx* ctx, pmx_place* pl, int first, int n) {
+    PMX_ZERO(pmx::at(pl->counters, first), n, ctx->stream);
+    if (!(first == PMX_CTR_COMPACT && n == 1)) pl->h_ctr_valid = false;
+}
+// the counters as of the last kernel that wrote them: read back (and waited for) only when the snapshot was dropped
+const unsigned long long* counters_read(pmx_ctx* ctx, pmx_place* pl) {
+    if (!pl->h_ctr_valid) {
+        PMX_D2H_SYNC(pl->h_ctr, pl->counters, ctx->stream);
+        pl->h_ctr_valid = true;
+    }
+    return pl->h_ctr;
+}
+
 // every slot of the seed table empty: the keys PMX_EMPTY_KEY, the counts zero
 void table_clear(pmx_ctx* ctx, pmx_place* pl) {
-    hipLaunchKernelGGL(k_fill_u64, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, PMX_EMPTY_KEY, pl->cap);
-    PMX_HIP(hipMemsetAsync(pl->vals.p, 0, pl->cap * sizeof(unsigned long long), ctx->stream));
+    PMX_LAUNCH(k_fill_u64, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, PMX_EMPTY_KEY, pl->cap);
+    PMX_ZERO(pl->vals, pl->cap, ctx->stream);
 }
 
 // (the device memory stays at its high-water mark: a batch whose ranges want a small, then a large table would otherwise
@@ -146,9 +163,7 @@ void table_reserve(pmx_ctx* ctx, pmx_place* pl, uint64_t bound_new) {
         else table_clear(ctx, pl);
         return;
     }
-    unsigned long long h_ctr[PMX_CTR_N];
-    PMX_HIP(hipMemcpyAsync(h_ctr, pl->counters.p, sizeof(h_ctr), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    const unsigned long long* h_ctr = counters_read(ctx, pl);
     uint64_t entries = 0;
     for (int i = 0; i < PMX_CTR_NSHARD; ++i) entries += h_ctr[PMX_CTR_SHARD0 + i];
     uint64_t need = next_pow2((uint64_t)((double)(entries + bound_new) / 0.7) + 1024);
@@ -165,21 +180,15 @@ void table_reserve(pmx_ctx* ctx, pmx_place* pl, uint64_t bound_new) {
     ovals.swap(pl->vals);
     const uint64_t ocap = pl->cap;
     table_alloc(ctx, pl, need);
-    PMX_HIP(hipMemsetAsync(pl->counters.p + PMX_CTR_SHARD0, 0, sizeof(unsigned long long) * PMX_CTR_NSHARD, ctx->stream));
-    hipLaunchKernelGGL(k_table_rehash, dim3(grid_for((int64_t)ocap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, okeys.p, ovals.p, ocap,
-                       pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p);
-    PMX_HIP(hipGetLastError());
+    counters_zero(ctx, pl, PMX_CTR_SHARD0, PMX_CTR_NSHARD);
+    PMX_LAUNCH(k_table_rehash, dim3(grid_for((int64_t)ocap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, okeys.p, ovals.p, ocap,
+               pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p);
 }
 
 // table -> hash-sorted (hash,count) arrays
 void finalize_histogram(pmx_ctx* ctx, pmx_place* pl) {
     if (pl->hist_sorted) return;
-    unsigned long long* h_ctr = pl->h_ctr;
-    if (!pl->h_ctr_valid) {   // (the overflow check that ends an optimistic seeding pass has read them already)
-        PMX_HIP(hipMemcpyAsync(h_ctr, pl->counters.p, sizeof(pl->h_ctr), hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
-        pl->h_ctr_valid = true;
-    }
+    const unsigned long long* h_ctr = counters_read(ctx, pl);   // (the overflow check that ends an optimistic seeding pass has read them already)
     if (h_ctr[PMX_CTR_OVERFLOW]) throw std::runtime_error("seed table overflow (internal sizing error)");
     int64_t n = 0;
     for (int i = 0; i < PMX_CTR_NSHARD; ++i) n += (int64_t)h_ctr[PMX_CTR_SHARD0 + i];
@@ -190,9 +199,9 @@ void finalize_histogram(pmx_ctx* ctx, pmx_place* pl) {
     pl->hist_hash_tmp.ensure(n);
     pl->hist_count_tmp.ensure(n);
     if (n > 0) {
-        PMX_HIP(hipMemsetAsync(pl->counters.p + PMX_CTR_COMPACT, 0, sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(k_table_compact, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p,
-                           pl->vals.p, pl->cap, pl->hist_hash_tmp.p, pl->hist_count_tmp.p, pl->counters.p + PMX_CTR_COMPACT);
+        counters_zero(ctx, pl, PMX_CTR_COMPACT, 1);
+        PMX_LAUNCH(k_table_compact, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p,
+                   pl->vals.p, pl->cap, pl->hist_hash_tmp.p, pl->hist_count_tmp.p, pl->counters.p + PMX_CTR_COMPACT);
         PMX_ROCPRIM(pl->tmp, radix_sort_pairs, pl->hist_hash_tmp.p, pl->hist_hash.p, pl->hist_count_tmp.p, pl->hist_count.p, (size_t)n, 0, 64, ctx->stream);
     }
     pl->hist_sorted = true;
@@ -288,8 +297,8 @@ static void order_range(pmx_ctx* ctx, const pmx_readset* rs, int64_t r0, int64_t
     const int64_t n = rs->n, m = r1 - r0;
     rs->loc_key.ensure((size_t)n); rs->loc_key2.ensure((size_t)n); rs->loc_idx.ensure((size_t)n); rs->loc_perm.ensure((size_t)n);
     if (m <= 0) return;
-    hipLaunchKernelGGL(k_read_prefix_keys, dim3(grid_for(m, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rs->words.p, rs->woff.p, r0, r1, rs->loc_key.p,
-                       rs->loc_idx.p);
+    PMX_LAUNCH(k_read_prefix_keys, dim3(grid_for(m, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rs->words.p, rs->woff.p, r0, r1, rs->loc_key.p,
+               rs->loc_idx.p);
     // (sorting on the key's top 20 bits alone -- three radix passes instead of four -- returned index arrays that were no
     //  permutation on this rocprim: measured, not understood; the full key it is)
     const unsigned lo_bit = 0u;
@@ -398,7 +407,7 @@ static int readset_finish(pmx_ctx* ctx, pmx_readset* rs, const int64_t* h_off) {
     rs->max_len = maxlen;
     rs->total = total;
     rs->woff.alloc((size_t)rs->n + 1);
-    PMX_HIP(hipMemcpyAsync(rs->woff.p, woff.data(), sizeof(int64_t) * ((size_t)rs->n + 1), hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(rs->woff, woff, (size_t)rs->n + 1, ctx->stream);
     rs->words.alloc((size_t)w);
     rs->amb.alloc((size_t)w);
     rs->has_recs = rs->n > 0 && maxlen <= 160;
@@ -416,10 +425,10 @@ int pmx_readset_upload(pmx_ctx* ctx, const char* concat, const int64_t* offsets,
     const int64_t total = offsets[n_reads] - offsets[0];
     rs->ascii.alloc((size_t)total + 32);
     rs->off.alloc((size_t)n_reads + 1);
-    if (total > 0) PMX_HIP(hipMemcpyAsync(rs->ascii.p, concat + offsets[0], (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(rs->ascii, concat + offsets[0], total, ctx->stream);
     std::vector<int64_t> rel((size_t)n_reads + 1);
     for (int64_t i = 0; i <= n_reads; ++i) rel[i] = offsets[i] - offsets[0];
-    PMX_HIP(hipMemcpyAsync(rs->off.p, rel.data(), sizeof(int64_t) * ((size_t)n_reads + 1), hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(rs->off, rel, (size_t)n_reads + 1, ctx->stream);
     readset_finish(ctx, rs.get(), rel.data());
     *out = rs.release();
     return PMX_OK;
@@ -436,7 +445,7 @@ int pmx_readset_wrap_device(pmx_ctx* ctx, const void* d_concat, const void* d_of
     rs->ascii.wrap((uint8_t*)d_concat, (size_t)total_bytes);
     rs->off.wrap((int64_t*)d_offsets, (size_t)n_reads + 1);
     std::vector<int64_t> h_off((size_t)n_reads + 1);
-    PMX_HIP(hipMemcpy(h_off.data(), d_offsets, sizeof(int64_t) * ((size_t)n_reads + 1), hipMemcpyDeviceToHost));
+    PMX_D2H_BLOCKING(h_off.data(), rs->off, h_off.size());
     // the kernels trust these offsets: they must lie inside the wrapped buffer, in order.  (offsets need not start at 0:
     // a slice [r0, r1] of a larger offsets array addresses its reads in the same buffer.)
     if (h_off[0] < 0 || h_off[n_reads] > total_bytes) return fail(PMX_ERR_ARG, "device offsets run outside the wrapped buffer");
@@ -475,17 +484,16 @@ int pmx_readset_rewrap_device(pmx_ctx* ctx, pmx_readset* rs, const void* d_conca
     rs->nw_tmp.ensure((size_t)n_reads + 1);
     rs->woff.ensure((size_t)n_reads + 1);
     rs->stats.ensure(2);
-    PMX_HIP(hipMemsetAsync(rs->stats.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_read_word_counts, dim3(grid_for(n_reads + 1, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rs->off.p, n_reads, total_bytes,
-                       rs->nw_tmp.p, rs->stats.p);
+    PMX_ZERO(rs->stats, 2, ctx->stream);
+    PMX_LAUNCH(k_read_word_counts, dim3(grid_for(n_reads + 1, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rs->off.p, n_reads, total_bytes,
+               rs->nw_tmp.p, rs->stats.p);
     PMX_ROCPRIM(rs->scan_tmp, exclusive_scan, rs->nw_tmp.p, rs->woff.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), ctx->stream);
     struct { int64_t n_words; unsigned long long st[2]; } h = {0, {0, 0}};
-    PMX_HIP(hipMemcpyAsync(&h.n_words, rs->woff.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(h.st, rs->stats.p, sizeof(h.st), hipMemcpyDeviceToHost, ctx->stream));
+    PMX_D2H(&h.n_words, pmx::at(rs->woff, n_reads), 1, ctx->stream);
+    PMX_D2H(h.st, rs->stats, ctx->stream);
     int64_t first = 0, last = 0;
-    PMX_HIP(hipMemcpyAsync(&first, rs->off.p, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(&last, rs->off.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H(&first, rs->off, 1, ctx->stream);
+    PMX_D2H_SYNC(&last, pmx::at(rs->off, n_reads), 1, ctx->stream);
     if (h.st[1]) return fail(PMX_ERR_ARG, "device offsets are not monotone or run outside the wrapped buffer");
     if (max_read_len > 0 && (int64_t)h.st[0] > max_read_len) return fail(PMX_ERR_ARG, "a read is longer than max_read_len");
     rs->n_words = h.n_words;
@@ -506,7 +514,7 @@ int pmx_readset_set_qualities(pmx_ctx* ctx, pmx_readset* rs, const char* qual_co
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     rs->qual.ensure((size_t)rs->total + 32);
-    if (rs->total > 0) PMX_HIP(hipMemcpyAsync(rs->qual.p, qual_concat, (size_t)rs->total, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(rs->qual, qual_concat, rs->total, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     rs->has_qual = true;
     return PMX_OK;
@@ -522,14 +530,13 @@ int pmx_readset_pack(pmx_ctx* ctx, pmx_readset* rs) {
     const bool fixed = rs->n > 0 && rs->max_len > 0 && rs->total == rs->n * rs->max_len;
     uint8_t* recs = rs->has_recs ? rs->recs.p : nullptr;
     // (ragged sets: a read without a word gets no record written -- cleared first, so that it reads as length 0)
-    if (recs && !fixed) PMX_HIP(hipMemsetAsync(recs, 0, (size_t)rs->n * 64, ctx->stream));
+    if (recs && !fixed) PMX_ZERO(recs, (size_t)rs->n * 64, ctx->stream);
     if (rs->n_words > 0 && fixed)
-        hipLaunchKernelGGL(k_pack_reads_fixed, dim3(grid_for(rs->n_words, 256, 1 << 30)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off0, (int)rs->max_len,
-                           (int64_t)0, rs->n_words, rs->words.p, rs->amb.p, recs);
+        PMX_LAUNCH(k_pack_reads_fixed, dim3(grid_for(rs->n_words, 256, 1 << 30)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off0, (int)rs->max_len,
+                   (int64_t)0, rs->n_words, rs->words.p, rs->amb.p, recs);
     else if (rs->n_words > 0)
-        hipLaunchKernelGGL(k_pack_reads, dim3(grid_for(rs->n_words, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p,
-                           rs->woff.p, rs->n, rs->n_words, rs->words.p, rs->amb.p, (int64_t)0, (int64_t)-1, recs);
-    PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_pack_reads, dim3(grid_for(rs->n_words, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p,
+                   rs->woff.p, rs->n, rs->n_words, rs->words.p, rs->amb.p, (int64_t)0, (int64_t)-1, recs);
     timer_end(ctx, "pack", 1);
     rs->packed = true;
     rs->has_order = false;   // (the buffer behind a wrapped read set may hold new reads)
@@ -552,10 +559,9 @@ int pmx_readset_pack_range(pmx_ctx* ctx, pmx_readset* rs, int64_t r0, int64_t r1
         // grid sized by the range's share of the words (exact for reads of one length; any grid is correct: the kernel strides)
         const int64_t est = (int64_t)((double)rs->n_words * (double)(r1 - r0) / (double)std::max<int64_t>(rs->n, 1)) + 1;
         // (a read without a word gets no record written: the range's records are cleared first)
-        if (rs->has_recs) PMX_HIP(hipMemsetAsync(rs->recs.p + (size_t)r0 * 64, 0, (size_t)(r1 - r0) * 64, ctx->stream));
-        hipLaunchKernelGGL(k_pack_reads, dim3(grid_for(est, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p,
-                           rs->woff.p, rs->n, rs->n_words, rs->words.p, rs->amb.p, r0, r1, rs->has_recs ? rs->recs.p : nullptr);
-        PMX_HIP(hipGetLastError());
+        if (rs->has_recs) PMX_ZERO(pmx::at(rs->recs, (size_t)r0 * 64), (size_t)(r1 - r0) * 64, ctx->stream);
+        PMX_LAUNCH(k_pack_reads, dim3(grid_for(est, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p,
+                   rs->woff.p, rs->n, rs->n_words, rs->words.p, rs->amb.p, r0, r1, rs->has_recs ? rs->recs.p : nullptr);
     }
     if (rs->packed) {   // re-packing part of a packed set: the order of those reads may have changed
         rs->has_order = false;
@@ -599,24 +605,21 @@ void hpc_compress_into(pmx_ctx* ctx, const pmx_readset* src, int64_t r0, int64_t
     dst->nw_tmp.ensure((size_t)m + 1);
     dst->woff.ensure((size_t)m + 1);
     dst->stats.ensure(2);
-    PMX_HIP(hipMemsetAsync(dst->stats.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    PMX_ZERO(dst->stats, 2, ctx->stream);
     const int grid = grid_for(m, 4, ctx->n_cu * 32);   // four waves per block, one read per wave and step
     timer_begin(ctx, "hpc");
-    hipLaunchKernelGGL(k_hpc_count, dim3(grid), dim3(256), 0, ctx->stream, src->ascii.p, src->off.p + r0, m, dst->len_tmp.p, dst->nw_tmp.p, dst->stats.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_hpc_count, dim3(grid), dim3(256), 0, ctx->stream, src->ascii.p, src->off.p + r0, m, dst->len_tmp.p, dst->nw_tmp.p, dst->stats.p);
     PMX_ROCPRIM(dst->scan_tmp, exclusive_scan, dst->len_tmp.p, dst->off.p, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), ctx->stream);
     PMX_ROCPRIM(dst->scan_tmp, exclusive_scan, dst->nw_tmp.p, dst->woff.p, (int64_t)0, (size_t)m + 1, rocprim::plus<int64_t>(), ctx->stream);
     if (m > 0) {
-        hipLaunchKernelGGL(k_hpc_write, dim3(grid), dim3(256), 0, ctx->stream, src->ascii.p, src->off.p + r0, src->has_qual ? src->qual.p : (const uint8_t*)nullptr, m,
-                           dst->off.p, dst->ascii.p, src->has_qual ? dst->qual.p : (uint8_t*)nullptr);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_hpc_write, dim3(grid), dim3(256), 0, ctx->stream, src->ascii.p, src->off.p + r0, src->has_qual ? src->qual.p : (const uint8_t*)nullptr, m,
+                   dst->off.p, dst->ascii.p, src->has_qual ? dst->qual.p : (uint8_t*)nullptr);
     }
     timer_end(ctx, "hpc", 1);
     struct { int64_t total, n_words; unsigned long long st[2]; } h = {0, 0, {0, 0}};
-    PMX_HIP(hipMemcpyAsync(&h.total, dst->off.p + m, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(&h.n_words, dst->woff.p + m, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(h.st, dst->stats.p, sizeof(h.st), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H(&h.total, pmx::at(dst->off, m), 1, ctx->stream);
+    PMX_D2H(&h.n_words, pmx::at(dst->woff, m), 1, ctx->stream);
+    PMX_D2H_SYNC(h.st, dst->stats, ctx->stream);
     dst->total = h.total;
     dst->n_words = h.n_words;
     dst->max_len = (int64_t)h.st[0];
@@ -653,9 +656,9 @@ int64_t pmx_readset_export(pmx_ctx* ctx, const pmx_readset* rs, char* concat, in
     if (cap < rs->total || (rs->total > 0 && !concat) || !offsets) return rs->total;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    if (rs->total > 0) PMX_HIP(hipMemcpyAsync(concat, rs->ascii.p + rs->off0, (size_t)rs->total, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(offsets, rs->off.p, sizeof(int64_t) * ((size_t)rs->n + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if (qual && rs->has_qual && rs->total > 0) PMX_HIP(hipMemcpyAsync(qual, rs->qual.p + rs->off0, (size_t)rs->total, hipMemcpyDeviceToHost, ctx->stream));
+    PMX_D2H(concat, pmx::at(rs->ascii, rs->off0), rs->total, ctx->stream);
+    PMX_D2H(offsets, rs->off, (size_t)rs->n + 1, ctx->stream);
+    if (qual && rs->has_qual) PMX_D2H(qual, pmx::at(rs->qual, rs->off0), rs->total, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     for (int64_t i = rs->n; i >= 0; --i) offsets[i] -= offsets[0];
     return rs->total;
@@ -683,12 +686,12 @@ int pmx_place_create(pmx_ctx* ctx, const pmx_index* idx, pmx_place** out) {
     pl->params = L->params;
     pl->hpc = L->hpc;
     pl->parent.alloc(n); pl->offsets.alloc(n + 1); pl->ch_hash.alloc(m); pl->ch_par.alloc(m); pl->ch_child.alloc(m);
-    PMX_HIP(hipMemcpyAsync(pl->parent.p, L->parent.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(pl->offsets.p, L->offsets.data(), sizeof(uint64_t) * (n + 1), hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(pl->parent, L->parent, n, ctx->stream);
+    PMX_H2D(pl->offsets, L->offsets, n + 1, ctx->stream);
     if (m > 0) {
-        PMX_HIP(hipMemcpyAsync(pl->ch_hash.p, L->hash.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(pl->ch_par.p, L->parent_count.data(), sizeof(int16_t) * m, hipMemcpyHostToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(pl->ch_child.p, L->child_count.data(), sizeof(int16_t) * m, hipMemcpyHostToDevice, ctx->stream));
+        PMX_H2D(pl->ch_hash, L->hash, m, ctx->stream);
+        PMX_H2D(pl->ch_par, L->parent_count, m, ctx->stream);
+        PMX_H2D(pl->ch_child, L->child_count, m, ctx->stream);
     }
     pl->root_beg = L->offsets[0];
     pl->root_end = L->offsets[1];
@@ -711,7 +714,7 @@ int pmx_place_create(pmx_ctx* ctx, const pmx_index* idx, pmx_place** out) {
         for (int64_t i = 0; i < n; ++i) pl->h_order[fill[depth[i]]++] = (uint32_t)i;
     }
     pl->level_nodes.alloc(n);
-    PMX_HIP(hipMemcpyAsync(pl->level_nodes.p, pl->h_order.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(pl->level_nodes, pl->h_order, n, ctx->stream);
     // heavy-path chains for k_score_chains: weight of a node = its change count (the serial adds it costs) plus a
     // constant; a chain = head (the root or a non-heaviest child), then heaviest child after heaviest child
     std::vector<uint32_t> h_chain_off, h_chain_nodes;
@@ -743,12 +746,12 @@ int pmx_place_create(pmx_ctx* ctx, const pmx_index* idx, pmx_place** out) {
     pl->n_chains = (int64_t)h_chain_off.size() - 1;
     for (int64_t c = 0; c < pl->n_chains; ++c) pl->max_chain_len = std::max<int64_t>(pl->max_chain_len, (int64_t)h_chain_off[c + 1] - h_chain_off[c]);
     pl->chain_off.alloc(h_chain_off.size()); pl->chain_nodes.alloc((size_t)n); pl->chain_beg.alloc((size_t)n); pl->chain_end.alloc((size_t)n);
-    PMX_HIP(hipMemcpyAsync(pl->chain_off.p, h_chain_off.data(), sizeof(uint32_t) * h_chain_off.size(), hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(pl->chain_nodes.p, h_chain_nodes.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(pl->chain_beg.p, h_chain_beg.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(pl->chain_end.p, h_chain_end.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    PMX_H2D(pl->chain_off, h_chain_off, ctx->stream);
+    PMX_H2D(pl->chain_nodes, h_chain_nodes, n, ctx->stream);
+    PMX_H2D(pl->chain_beg, h_chain_beg, n, ctx->stream);
+    PMX_H2D(pl->chain_end, h_chain_end, n, ctx->stream);
     pl->counters.alloc(PMX_CTR_N);
-    PMX_HIP(hipMemsetAsync(pl->counters.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
+    counters_zero(ctx, pl, 0, PMX_CTR_N);
     pl->scalars.alloc(8);
     pl->stats.alloc(8);
     pl->metrics5.alloc(5 * (size_t)n);
@@ -772,8 +775,7 @@ int pmx_place_reset(pmx_ctx* ctx, pmx_place* pl) {
     if (!ctx || !pl) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    PMX_HIP(hipMemsetAsync(pl->counters.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
-    pl->h_ctr_valid = false;
+    counters_zero(ctx, pl, 0, PMX_CTR_N);
     pl->needs_clear = pl->cap != 0;   // the slots are cleared by the next reservation, which may also pick a better size
     pl->bases_added = 0;
     pl->n_reads_added = 0;
@@ -792,13 +794,12 @@ static void dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs) {
     pl->dd_h1.ensure((size_t)n); pl->dd_h2.ensure((size_t)n); pl->dd_h1s.ensure((size_t)n); pl->dd_key.ensure((size_t)n);
     pl->dd_idx.ensure((size_t)n); pl->dd_idx2.ensure((size_t)n); pl->dd_keep.ensure((size_t)n);
     if (n == 0) { pl->dd_for = rs; return; }
-    hipLaunchKernelGGL(k_read_hashes, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p, n, pl->dd_h1.p, pl->dd_h2.p, pl->dd_idx.p);
+    PMX_LAUNCH(k_read_hashes, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p, n, pl->dd_h1.p, pl->dd_h2.p, pl->dd_idx.p);
     PMX_ROCPRIM(pl->tmp, radix_sort_pairs, pl->dd_h2.p, pl->dd_key.p, pl->dd_idx.p, pl->dd_idx2.p, (size_t)n, 0, 64, ctx->stream);
-    hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_idx2.p, n, pl->dd_key.p);
+    PMX_LAUNCH(k_gather_u64, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_idx2.p, n, pl->dd_key.p);
     PMX_ROCPRIM(pl->tmp, radix_sort_pairs, pl->dd_key.p, pl->dd_h1s.p, pl->dd_idx2.p, pl->dd_idx.p, (size_t)n, 0, 64, ctx->stream);
-    hipLaunchKernelGGL(k_mark_first_of_run, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p, pl->dd_h1s.p, pl->dd_h2.p, pl->dd_idx.p, n,
-                       pl->dd_keep.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_mark_first_of_run, dim3(grid_for(n, 256, G)), dim3(256), 0, ctx->stream, rs->ascii.p, rs->off.p, pl->dd_h1s.p, pl->dd_h2.p, pl->dd_idx.p, n,
+               pl->dd_keep.p);
     pl->dd_for = rs;
 }
 
@@ -944,23 +945,21 @@ void SeedStage::launch_chunk(int j, int64_t r0, int64_t r1, hipStream_t st) {
         const int64_t n_c = r1 - r0, n_tiles = (n_c + 63) / 64;
         pl->t_words[j].ensure((size_t)n_tiles * 5 * 64); pl->t_amb[j].ensure((size_t)n_tiles * 5 * 64);
         pl->t_len[j].ensure((size_t)n_tiles * 64); pl->t_mult[j].ensure((size_t)n_tiles * 64);
-        PMX_HIP(hipMemsetAsync(pl->t_count.p + j, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_collapse_reads, dim3((unsigned)((n_c + PMX_DEDUP_BLOCK - 1) / PMX_DEDUP_BLOCK)), dim3(PMX_DEDUP_BLOCK), PMX_DEDUP_LDS_BYTES, st,
-                           rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, keep, perm, sp.k, fixed_len, rs->has_recs ? rs->recs.p : (const uint8_t*)nullptr, pl->t_words[j].p, pl->t_amb[j].p, pl->t_len[j].p,
-                           pl->t_mult[j].p, pl->t_count.p + j);
-        PMX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ks, grid, block, lds_ks, st, pl->t_words[j].p, pl->t_amb[j].p,
-                           (const int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, n_c, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p,
-                           (const uint8_t*)nullptr, (const uint32_t*)nullptr, pl->t_len[j].p, pl->t_mult[j].p, pl->t_count.p + j);
+        PMX_ZERO(pmx::at(pl->t_count, j), 1, st);
+        PMX_LAUNCH(k_collapse_reads, dim3((unsigned)((n_c + PMX_DEDUP_BLOCK - 1) / PMX_DEDUP_BLOCK)), dim3(PMX_DEDUP_BLOCK), PMX_DEDUP_LDS_BYTES, st,
+                   rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, keep, perm, sp.k, fixed_len, rs->has_recs ? rs->recs.p : (const uint8_t*)nullptr, pl->t_words[j].p, pl->t_amb[j].p, pl->t_len[j].p,
+                   pl->t_mult[j].p, pl->t_count.p + j);
+        PMX_LAUNCH(ks, grid, block, lds_ks, st, pl->t_words[j].p, pl->t_amb[j].p,
+                   (const int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, n_c, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p,
+                   (const uint8_t*)nullptr, (const uint32_t*)nullptr, pl->t_len[j].p, pl->t_mult[j].p, pl->t_count.p + j);
     } else if (ks_path)
-        hipLaunchKernelGGL(ks, grid, block, lds_ks, st, rs->words.p, rs->amb.p,
-                           rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p, keep, perm,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const unsigned long long*)nullptr);
+        PMX_LAUNCH(ks, grid, block, lds_ks, st, rs->words.p, rs->amb.p,
+                   rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p, keep, perm,
+                   (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const unsigned long long*)nullptr);
     else
-        hipLaunchKernelGGL(k_seed_histogram, grid, block, lds, st, rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p,
-                           pl->vals.p, pl->cap - 1, pl->counters.p, keep, quality_mode ? rs->qual.p : nullptr,
-                           quality_mode ? pp->min_seed_quality : 0, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr);
-    PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_seed_histogram, grid, block, lds, st, rs->words.p, rs->amb.p, rs->woff.p, rs->off.p, r0, r1, sp, pl->keys.p,
+                   pl->vals.p, pl->cap - 1, pl->counters.p, keep, quality_mode ? rs->qual.p : nullptr,
+                   quality_mode ? pp->min_seed_quality : 0, (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr);
 }
 
 // One pass over the range: groups of n_par chunks, one table reservation per group.  The bound on the distinct keys a group
@@ -974,6 +973,7 @@ void SeedStage::pass(bool optimistic) {
         const double safe_bound = (double)(g1 - g0) * (double)rs->max_len;
         const double bound = !optimistic ? safe_bound : bound_frac > 0 ? safe_bound * bound_frac : safe_bound / (double)bound_div;
         table_reserve(ctx, pl, (uint64_t)bound + 1);
+        counters_zero(ctx, pl, 0, 0);   // the chunks count their inserts
         if (n_par > 1) PMX_HIP(hipEventRecord(ctx->seed_go, ctx->stream));
         int j = 0;
         for (int64_t r0 = g0; r0 < g1; r0 += chunk_reads, ++j) {
@@ -989,12 +989,10 @@ void SeedStage::pass(bool optimistic) {
     }
 }
 
-// the inserts of an optimistic pass that found no slot (the counters read here serve finalize_histogram too)
+// the inserts of an optimistic pass that found no slot (the counters read here serve finalize_histogram too, unless the
+// pass is redone)
 unsigned long long SeedStage::failed_inserts() {
-    PMX_HIP(hipMemcpyAsync(pl->h_ctr, pl->counters.p, sizeof(pl->h_ctr), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
-    pl->h_ctr_valid = true;
-    const unsigned long long h_ovf = pl->h_ctr[PMX_CTR_OVERFLOW];
+    const unsigned long long h_ovf = counters_read(ctx, pl)[PMX_CTR_OVERFLOW];
     if (sw.prof) fprintf(stderr, "[pmx place] seeding with bound 1/%lld: table %llu slots, %llu failed inserts\n", (long long)bound_div, (unsigned long long)pl->cap, h_ovf);
     return h_ovf;
 }
@@ -1026,7 +1024,6 @@ static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, in
         rr0 = 0;
         rr1 = rs->n;
     }
-    pl->h_ctr_valid = false;
     SeedStage S(ctx, pl, rs, pp, rr0, rr1);
     if (S.lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
     if (S.lds > 64 * 1024)
@@ -1041,7 +1038,7 @@ static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, in
         S.pass(optimistic);
         if (optimistic && S.failed_inserts() != 0) {
             // the optimistic table overflowed: start over with the safe bound
-            PMX_HIP(hipMemsetAsync(pl->counters.p, 0, sizeof(unsigned long long) * PMX_CTR_N, ctx->stream));
+            counters_zero(ctx, pl, 0, PMX_CTR_N);
             table_clear(ctx, pl);
             S.pass(false);
         }
@@ -1058,8 +1055,7 @@ static int add_reads_impl(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs, in
 // host count of the reads the --dedup mask keeps
 static int64_t dedup_mask_count(pmx_ctx* ctx, pmx_place* pl, int64_t n) {
     std::vector<uint8_t> h((size_t)n);
-    if (n > 0) PMX_HIP(hipMemcpyAsync(h.data(), pl->dd_keep.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(h, pl->dd_keep, n, ctx->stream);
     int64_t kept = 0;
     for (uint8_t v : h) kept += v;
     return kept;
@@ -1075,15 +1071,14 @@ int64_t pmx_place_dedup_local(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs
     PMX_HIP(hipSetDevice(ctx->device));
     dedup_local(ctx, pl, rs);
     pl->dd_count.ensure(1);
-    PMX_HIP(hipMemsetAsync(pl->dd_count.p, 0, sizeof(unsigned long long), ctx->stream));
+    PMX_ZERO(pl->dd_count, 1, ctx->stream);
     if (!d_h1 || !d_h2) return dedup_mask_count(ctx, pl, rs->n);   // count only: a reduction of the mask through the same kernel into scratch is not worth a variant
     if (cap < rs->n) return fail(PMX_ERR_CAPACITY, "dedup export buffers must hold one pair per read");
     if (rs->n > 0)
-        hipLaunchKernelGGL(k_kept_read_hashes, dim3(grid_for(rs->n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_h2.p, pl->dd_keep.p, rs->n,
-                           (uint64_t*)d_h1, (uint64_t*)d_h2, pl->dd_count.p);
+        PMX_LAUNCH(k_kept_read_hashes, dim3(grid_for(rs->n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_h2.p, pl->dd_keep.p, rs->n,
+                   (uint64_t*)d_h1, (uint64_t*)d_h2, pl->dd_count.p);
     unsigned long long kept = 0;
-    PMX_HIP(hipMemcpyAsync(&kept, pl->dd_count.p, sizeof(kept), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    PMX_D2H_SYNC(&kept, pl->dd_count, 1, ctx->stream);
     return (int64_t)kept;
     PMX_CATCH
 }
@@ -1109,9 +1104,8 @@ int pmx_place_dedup_drop_seen(pmx_ctx* ctx, pmx_place* pl, const pmx_readset* rs
     DevBuf<uint64_t> s1, s2;
     s1.alloc((size_t)n_seen); s2.alloc((size_t)n_seen);
     PMX_ROCPRIM(pl->tmp, radix_sort_pairs, (uint64_t*)d_seen_h1, s1.p, (uint64_t*)d_seen_h2, s2.p, (size_t)n_seen, 0, 64, ctx->stream);
-    hipLaunchKernelGGL(k_drop_seen_reads, dim3(grid_for(rs->n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_h2.p, rs->n, s1.p, s2.p, n_seen,
-                       pl->dd_keep.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_drop_seen_reads, dim3(grid_for(rs->n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->dd_h1.p, pl->dd_h2.p, rs->n, s1.p, s2.p, n_seen,
+               pl->dd_keep.p);
     PMX_HIP(hipStreamSynchronize(ctx->stream));   // (s1 / s2 go out of scope)
     return PMX_OK;
     PMX_CATCH
@@ -1142,8 +1136,8 @@ int pmx_place_histogram_export(pmx_ctx* ctx, pmx_place* pl, uint64_t* hash, int6
     finalize_histogram(ctx, pl);
     if (cap < pl->n_hist) return fail(PMX_ERR_CAPACITY, "histogram export buffer too small");
     if (pl->n_hist > 0) {
-        PMX_HIP(hipMemcpyAsync(hash, pl->hist_hash.p, sizeof(uint64_t) * pl->n_hist, hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(count, pl->hist_count.p, sizeof(int64_t) * pl->n_hist, hipMemcpyDeviceToHost, ctx->stream));
+        PMX_D2H(hash, pl->hist_hash, pl->n_hist, ctx->stream);
+        PMX_D2H(count, pl->hist_count, pl->n_hist, ctx->stream);
     }
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
@@ -1157,8 +1151,8 @@ int pmx_place_histogram_export_device(pmx_ctx* ctx, pmx_place* pl, void* d_hash,
     finalize_histogram(ctx, pl);
     if (cap < pl->n_hist) return fail(PMX_ERR_CAPACITY, "histogram export buffer too small");
     if (pl->n_hist > 0) {
-        PMX_HIP(hipMemcpyAsync(d_hash, pl->hist_hash.p, sizeof(uint64_t) * pl->n_hist, hipMemcpyDeviceToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(d_count, pl->hist_count.p, sizeof(int64_t) * pl->n_hist, hipMemcpyDeviceToDevice, ctx->stream));
+        PMX_D2D(d_hash, pl->hist_hash, pl->n_hist, ctx->stream);
+        PMX_D2D(d_count, pl->hist_count, pl->n_hist, ctx->stream);
     }
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
@@ -1173,14 +1167,10 @@ int64_t pmx_place_histogram_entries(pmx_ctx* ctx, pmx_place* pl) {
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     if (pl->hist_sorted) return pl->n_hist;
-    if (!pl->h_ctr_valid) {
-        PMX_HIP(hipMemcpyAsync(pl->h_ctr, pl->counters.p, sizeof(pl->h_ctr), hipMemcpyDeviceToHost, ctx->stream));
-        PMX_HIP(hipStreamSynchronize(ctx->stream));
-        pl->h_ctr_valid = true;
-    }
-    if (pl->h_ctr[PMX_CTR_OVERFLOW]) throw std::runtime_error("seed table overflow (internal sizing error)");
+    const unsigned long long* h_ctr = counters_read(ctx, pl);
+    if (h_ctr[PMX_CTR_OVERFLOW]) throw std::runtime_error("seed table overflow (internal sizing error)");
     int64_t n = 0;
-    for (int i = 0; i < PMX_CTR_NSHARD; ++i) n += (int64_t)pl->h_ctr[PMX_CTR_SHARD0 + i];
+    for (int i = 0; i < PMX_CTR_NSHARD; ++i) n += (int64_t)h_ctr[PMX_CTR_SHARD0 + i];
     return n;
     PMX_CATCH
 }
@@ -1194,14 +1184,13 @@ int pmx_place_histogram_export_device_unsorted(pmx_ctx* ctx, pmx_place* pl, void
     if (cap < n) return fail(PMX_ERR_CAPACITY, "histogram export buffer too small");
     if (n == 0) return PMX_OK;
     if (pl->hist_sorted) {   // already finalized: the sorted arrays are as good
-        PMX_HIP(hipMemcpyAsync(d_hash, pl->hist_hash.p, sizeof(uint64_t) * n, hipMemcpyDeviceToDevice, ctx->stream));
-        PMX_HIP(hipMemcpyAsync(d_count, pl->hist_count.p, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, ctx->stream));
+        PMX_D2D(d_hash, pl->hist_hash, n, ctx->stream);
+        PMX_D2D(d_count, pl->hist_count, n, ctx->stream);
         return PMX_OK;
     }
-    PMX_HIP(hipMemsetAsync(pl->counters.p + PMX_CTR_COMPACT, 0, sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_table_compact, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, pl->vals.p, pl->cap,
-                       (uint64_t*)d_hash, (int64_t*)d_count, pl->counters.p + PMX_CTR_COMPACT);
-    PMX_HIP(hipGetLastError());
+    counters_zero(ctx, pl, PMX_CTR_COMPACT, 1);
+    PMX_LAUNCH(k_table_compact, dim3(grid_for((int64_t)pl->cap, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, pl->keys.p, pl->vals.p, pl->cap,
+               (uint64_t*)d_hash, (int64_t*)d_count, pl->counters.p + PMX_CTR_COMPACT);
     return PMX_OK;   // (stream-ordered: the caller synchronizes before another stream reads the buffers)
     PMX_CATCH
 }
@@ -1212,12 +1201,12 @@ int pmx_place_histogram_merge_device(pmx_ctx* ctx, pmx_place* pl, const void* d_
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     table_reserve(ctx, pl, (uint64_t)n);
-    hipLaunchKernelGGL(k_table_merge, dim3(grid_for(n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, (const uint64_t*)d_hash,
-                       (const int64_t*)d_count, n, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p);
+    counters_zero(ctx, pl, 0, 0);   // the merge counts its inserts
+    PMX_LAUNCH(k_table_merge, dim3(grid_for(n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, (const uint64_t*)d_hash,
+               (const int64_t*)d_count, n, pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     pl->hist_sorted = false;
     pl->table_dirty = true;
-    pl->h_ctr_valid = false;
     return PMX_OK;
     PMX_CATCH
 }
@@ -1235,17 +1224,16 @@ int pmx_place_histogram_merge_device_parts(pmx_ctx* ctx, pmx_place* pl, const vo
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     table_reserve(ctx, pl, (uint64_t)total);   // one capacity check for every part, then the merges run back to back
+    counters_zero(ctx, pl, 0, 0);   // the merges count their inserts
     for (int p = 0; p < n_parts; ++p) {
         if (p == skip_part || sizes[p] == 0) continue;
-        hipLaunchKernelGGL(k_table_merge, dim3(grid_for(sizes[p], 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
-                           (const uint64_t*)d_hash + (size_t)p * (size_t)part_stride, (const int64_t*)d_count + (size_t)p * (size_t)part_stride, sizes[p],
-                           pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p);
+        PMX_LAUNCH(k_table_merge, dim3(grid_for(sizes[p], 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream,
+                   (const uint64_t*)d_hash + (size_t)p * (size_t)part_stride, (const int64_t*)d_count + (size_t)p * (size_t)part_stride, sizes[p],
+                   pl->keys.p, pl->vals.p, pl->cap - 1, pl->counters.p);
     }
-    PMX_HIP(hipGetLastError());
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     pl->hist_sorted = false;
     pl->table_dirty = true;
-    pl->h_ctr_valid = false;
     return PMX_OK;
     PMX_CATCH
 }
@@ -1256,17 +1244,17 @@ int pmx_place_histogram_merge(pmx_ctx* ctx, pmx_place* pl, const uint64_t* hash,
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     table_reserve(ctx, pl, (uint64_t)n);
+    counters_zero(ctx, pl, 0, 0);   // the merge counts its inserts
     DevBuf<uint64_t> dh;
     DevBuf<int64_t> dc;
     dh.alloc(n); dc.alloc(n);
-    PMX_HIP(hipMemcpyAsync(dh.p, hash, sizeof(uint64_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(dc.p, count, sizeof(int64_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_table_merge, dim3(grid_for(n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, dh.p, dc.p, n, pl->keys.p, pl->vals.p,
-                       pl->cap - 1, pl->counters.p);
+    PMX_H2D(dh, hash, n, ctx->stream);
+    PMX_H2D(dc, count, n, ctx->stream);
+    PMX_LAUNCH(k_table_merge, dim3(grid_for(n, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, dh.p, dc.p, n, pl->keys.p, pl->vals.p,
+               pl->cap - 1, pl->counters.p);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     pl->hist_sorted = false;
     pl->table_dirty = true;
-    pl->h_ctr_valid = false;
     return PMX_OK;
     PMX_CATCH
 }
@@ -1325,19 +1313,18 @@ struct ScoreStage {
 // after the homopolymer erase.
 void ScoreStage::mask_top_fraction(int64_t n) {
     // unique seeds after homopolymer erase
-    PMX_HIP(hipMemsetAsync(pl->stats.p, 0, 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
-    PMX_HIP(hipMemcpyAsync(h_stats, pl->stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_ZERO(pl->stats, 4, st);
+    PMX_LAUNCH(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
+    PMX_D2H_SYNC(h_stats, pl->stats, st);
     const int64_t n_mask = (int64_t)(pp->seed_mask_fraction * (double)h_stats[3]);   // :1775
     if (n_mask <= 0) return;
     DevBuf<uint64_t> key, key2;
     DevBuf<uint32_t> idx, idx2;
     key.alloc(n); key2.alloc(n); idx.alloc(n); idx2.alloc(n);
-    hipLaunchKernelGGL(k_mask_keys, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, key.p, idx.p);
+    PMX_LAUNCH(k_mask_keys, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, key.p, idx.p);
     PMX_ROCPRIM(pl->tmp, radix_sort_pairs, key.p, key2.p, idx.p, idx2.p, (size_t)n, 0, 64, st);
     const int64_t nm = std::min<int64_t>(n_mask, (int64_t)h_stats[3]);
-    hipLaunchKernelGGL(k_mask_apply, dim3(grid_for(nm, 256, G)), dim3(256), 0, st, idx2.p, nm, pl->dead.p);
+    PMX_LAUNCH(k_mask_apply, dim3(grid_for(nm, 256, G)), dim3(256), 0, st, idx2.p, nm, pl->dead.p);
     PMX_HIP(hipStreamSynchronize(st));   // (the four local buffers go out of scope)
 }
 
@@ -1352,26 +1339,24 @@ void ScoreStage::read_filters() {
     pl->kept_log.ensure(n);
     min_support = pp->min_read_support;
     if (n > 0) {
-        hipLaunchKernelGGL(k_mark_homopolymer, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_hash.p, n, homopolymer_hash(0, pl->params.k),
-                           homopolymer_hash(1, pl->params.k), homopolymer_hash(2, pl->params.k), homopolymer_hash(3, pl->params.k), pl->dead.p);
+        PMX_LAUNCH(k_mark_homopolymer, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_hash.p, n, homopolymer_hash(0, pl->params.k),
+                   homopolymer_hash(1, pl->params.k), homopolymer_hash(2, pl->params.k), homopolymer_hash(3, pl->params.k), pl->dead.p);
         if (pp->seed_mask_fraction > 0.0) mask_top_fraction(n);
-        PMX_HIP(hipMemsetAsync(pl->stats.p, 0, 4 * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
-        PMX_HIP(hipMemcpyAsync(h_stats, pl->stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
+        PMX_ZERO(pl->stats, 4, st);
+        PMX_LAUNCH(k_hist_stats, dim3(grid_for(n, 256, ctx->n_cu)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, pl->stats.p);
+        PMX_D2H_SYNC(h_stats, pl->stats, st);
         if (min_support < 0) {   // resolveMinReadSupport, src/placement.cpp:931-955
             const double est = h_stats[1] > 0 ? (double)h_stats[0] / (double)h_stats[1] : 0.0;
             min_support = est > 3.0 ? 2 : 1;
         }
-        hipLaunchKernelGGL(k_keep_flags, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, min_support, pl->flag.p);
+        PMX_LAUNCH(k_keep_flags, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_count.p, pl->dead.p, n, min_support, pl->flag.p);
         PMX_ROCPRIM(pl->tmp, exclusive_scan, pl->flag.p, pl->pos.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
         uint32_t last_pos = 0, last_flag = 0;
-        PMX_HIP(hipMemcpyAsync(&last_pos, pl->pos.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(&last_flag, pl->flag.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipStreamSynchronize(st));
+        PMX_D2H(&last_pos, pmx::at(pl->pos, n - 1), 1, st);
+        PMX_D2H_SYNC(&last_flag, pmx::at(pl->flag, n - 1), 1, st);
         n_kept = (int64_t)last_pos + last_flag;
-        hipLaunchKernelGGL(k_keep_scatter, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_hash.p, pl->hist_count.p, pl->flag.p, pl->pos.p, n,
-                           pl->kept_hash.p, pl->kept_log.p);
+        PMX_LAUNCH(k_keep_scatter, dim3(grid_for(n, 256, G)), dim3(256), 0, st, pl->hist_hash.p, pl->hist_count.p, pl->flag.p, pl->pos.p, n,
+                   pl->kept_hash.p, pl->kept_log.p);
     } else if (min_support < 0) min_support = 1;
     pl->n_kept = n_kept;
 }
@@ -1381,17 +1366,17 @@ void ScoreStage::read_filters() {
 void ScoreStage::sums_and_probe_table() {
     const int64_t nb = (n_kept + PMX_SUM_BLOCK - 1) / PMX_SUM_BLOCK;
     pl->partial.ensure((size_t)(2 * nb + 2));
-    if (nb > 0) hipLaunchKernelGGL(k_block_sums, dim3((unsigned)std::min<int64_t>(nb, (int64_t)G * 4)), dim3(64), 0, st, pl->kept_log.p, n_kept, pl->partial.p);
-    hipLaunchKernelGGL(k_sequential_sums, dim3(1), dim3(64), 0, st, pl->partial.p, nb, pl->scalars.p);
+    if (nb > 0) PMX_LAUNCH(k_block_sums, dim3((unsigned)std::min<int64_t>(nb, (int64_t)G * 4)), dim3(64), 0, st, pl->kept_log.p, n_kept, pl->partial.p);
+    PMX_LAUNCH(k_sequential_sums, dim3(1), dim3(64), 0, st, pl->partial.p, nb, pl->scalars.p);
     pl->tcap = next_pow2((uint64_t)std::max<int64_t>(n_kept, 1) * 2 + 64);
     pl->tkeys.ensure(pl->tcap);
     pl->tvals.ensure(pl->tcap);
-    hipLaunchKernelGGL(k_fill_u64, dim3(grid_for((int64_t)pl->tcap, 256, G)), dim3(256), 0, st, pl->tkeys.p, PMX_EMPTY_KEY, pl->tcap);
+    PMX_LAUNCH(k_fill_u64, dim3(grid_for((int64_t)pl->tcap, 256, G)), dim3(256), 0, st, pl->tkeys.p, PMX_EMPTY_KEY, pl->tcap);
     if (n_kept > 0)
-        hipLaunchKernelGGL(k_kept_table_build, dim3(grid_for(n_kept, 256, G)), dim3(256), 0, st, pl->kept_hash.p, pl->kept_log.p, n_kept, pl->tkeys.p,
-                           pl->tvals.p, pl->tcap - 1);
-    hipLaunchKernelGGL(k_wc_denominator, dim3(1), dim3(1024), 0, st, pl->ch_hash.p, pl->ch_child.p, pl->root_beg, pl->root_end, pl->tkeys.p, pl->tvals.p,
-                       pl->tcap - 1, n_kept > 0 ? 1 : 0, pl->scalars.p + 2);
+        PMX_LAUNCH(k_kept_table_build, dim3(grid_for(n_kept, 256, G)), dim3(256), 0, st, pl->kept_hash.p, pl->kept_log.p, n_kept, pl->tkeys.p,
+                   pl->tvals.p, pl->tcap - 1);
+    PMX_LAUNCH(k_wc_denominator, dim3(1), dim3(1024), 0, st, pl->ch_hash.p, pl->ch_child.p, pl->root_beg, pl->root_end, pl->tkeys.p, pl->tvals.p,
+               pl->tcap - 1, n_kept > 0 ? 1 : 0, pl->scalars.p + 2);
 }
 
 // the five terms of every change of the index (k_score_terms) -> pl->terms, pl->term_meta
@@ -1402,20 +1387,20 @@ void ScoreStage::score_terms() {
     double* const t = pl->terms.p;
     ta = {t, t + n_ch, t + 2 * n_ch, t + 3 * n_ch, t + 4 * n_ch, pl->term_meta.p};
     if (n_ch > 0)
-        hipLaunchKernelGGL(k_score_terms, dim3(grid_for(n_ch, 256, G)), dim3(256), 0, st, pl->ch_hash.p, pl->ch_par.p, pl->ch_child.p, n_ch,
-                           pl->tkeys.p, pl->tvals.p, pl->tcap - 1, n_kept > 0 ? 1 : 0, t, t + n_ch, t + 2 * n_ch, t + 3 * n_ch, t + 4 * n_ch,
-                           pl->term_meta.p);
+        PMX_LAUNCH(k_score_terms, dim3(grid_for(n_ch, 256, G)), dim3(256), 0, st, pl->ch_hash.p, pl->ch_par.p, pl->ch_child.p, n_ch,
+                   pl->tkeys.p, pl->tvals.p, pl->tcap - 1, n_kept > 0 ? 1 : 0, t, t + n_ch, t + 2 * n_ch, t + 3 * n_ch, t + 4 * n_ch,
+                   pl->term_meta.p);
 }
 
 // the per-node flags of the persistent kernels: a node is done when its flag holds the epoch of this call
 void ScoreStage::begin_persistent() {
     if (!pl->tree_done.p) {
         pl->tree_done.alloc((size_t)pl->n_nodes + 1);
-        PMX_HIP(hipMemsetAsync(pl->tree_done.p, 0, sizeof(uint32_t) * ((size_t)pl->n_nodes + 1), st));
+        PMX_ZERO(pl->tree_done, (size_t)pl->n_nodes + 1, st);
         pl->tree_epoch = 0;
     }
     if (++pl->tree_epoch == 0) {   // wrapped: start over
-        PMX_HIP(hipMemsetAsync(pl->tree_done.p, 0, sizeof(uint32_t) * ((size_t)pl->n_nodes + 1), st));
+        PMX_ZERO(pl->tree_done, (size_t)pl->n_nodes + 1, st);
         pl->tree_epoch = 1;
     }
 }
@@ -1425,17 +1410,17 @@ void ScoreStage::begin_persistent() {
 void ScoreStage::launch_chains() {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_chains + 3) / 4));
     pl->last_grid_waves = (int64_t)grid * 4;
-    hipLaunchKernelGGL(k_score_chains, dim3(grid), dim3(256), 0, st, pl->chain_off.p, pl->n_chains, pl->chain_nodes.p, pl->chain_beg.p,
-                       pl->chain_end.p, pl->parent.p, ta, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
-                       pl->tree_done.p + pl->n_nodes);
+    PMX_LAUNCH(k_score_chains, dim3(grid), dim3(256), 0, st, pl->chain_off.p, pl->n_chains, pl->chain_nodes.p, pl->chain_beg.p,
+               pl->chain_end.p, pl->parent.p, ta, pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch,
+               pl->tree_done.p + pl->n_nodes);
 }
 
 // per-node flags in BFS order (k_score_tree; kept for comparison), resident like the chains kernel
 void ScoreStage::launch_tree() {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ctx->n_cu, (pl->n_nodes + 3) / 4));
     pl->last_grid_waves = (int64_t)grid * 4;
-    hipLaunchKernelGGL(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, ta,
-                       pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
+    PMX_LAUNCH(k_score_tree, dim3(grid), dim3(256), 0, st, pl->level_nodes.p, pl->n_nodes, pl->parent.p, pl->offsets.p, ta,
+               pl->metrics5.p, pl->counts2.p, pl->tree_done.p, pl->tree_epoch, pl->tree_done.p + pl->n_nodes);
 }
 
 // one launch per BFS level (k_score_level); needs no co-residency
@@ -1444,8 +1429,8 @@ void ScoreStage::launch_levels() {
     for (int lv = 0; lv < n_levels; ++lv) {
         const int64_t beg = pl->level_off[lv], cnt = pl->level_off[lv + 1] - beg;
         if (cnt <= 0) continue;
-        hipLaunchKernelGGL(k_score_level, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, pl->level_nodes.p + beg, cnt, pl->parent.p,
-                           pl->offsets.p, ta, pl->metrics5.p, pl->counts2.p);
+        PMX_LAUNCH(k_score_level, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, pl->level_nodes.p + beg, cnt, pl->parent.p,
+                   pl->offsets.p, ta, pl->metrics5.p, pl->counts2.p);
     }
 }
 
@@ -1457,7 +1442,13 @@ void ScoreStage::launch_levels_graph() {
         if (pl->level_graph_exec) { (void)hipGraphExecDestroy(pl->level_graph_exec); pl->level_graph_exec = nullptr; }
         hipGraph_t graph = nullptr;
         PMX_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-        launch_levels();
+        try {
+            launch_levels();
+        } catch (...) {   // a refused launch: the stream must not stay capturing, and the partial graph goes
+            (void)hipStreamEndCapture(st, &graph);
+            if (graph) (void)hipGraphDestroy(graph);
+            throw;
+        }
         PMX_HIP(hipStreamEndCapture(st, &graph));
         PMX_HIP(hipGraphInstantiate(&pl->level_graph_exec, graph, nullptr, nullptr, 0));
         (void)hipGraphDestroy(graph);
@@ -1478,7 +1469,7 @@ void ScoreStage::score_nodes() {
         else launch_chains();
         if (sw.test_starved) {   // tests: pretend a wave gave up, so that the level-kernel redo runs
             const uint32_t one = 1;
-            PMX_HIP(hipMemcpyAsync(pl->tree_done.p + pl->n_nodes, &one, sizeof(one), hipMemcpyHostToDevice, st));
+            PMX_H2D(pmx::at(pl->tree_done, pl->n_nodes), &one, 1, st);
         }
     } else if (sw.no_graph) {
         pl->last_form = PMX_SCORE_FORM_LEVELS;
@@ -1491,14 +1482,13 @@ void ScoreStage::score_nodes() {
 
 // node scores from the accumulators, everything the host needs back in one synchronisation -> pl->h_scores, h_scal, tree_status
 void ScoreStage::fetch() {
-    hipLaunchKernelGGL(k_score_getters, dim3(grid_for(pl->n_nodes, 256, G)), dim3(256), 0, st, pl->metrics5.p, pl->counts2.p, pl->n_nodes, pl->scalars.p,
-                       n_kept, pl->scores5.p, pl->level_nodes.p, pl->scores_bfs.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_score_getters, dim3(grid_for(pl->n_nodes, 256, G)), dim3(256), 0, st, pl->metrics5.p, pl->counts2.p, pl->n_nodes, pl->scalars.p,
+               n_kept, pl->scores5.p, pl->level_nodes.p, pl->scores_bfs.p);
     pl->h_scores.resize(5 * (size_t)pl->n_nodes);
-    PMX_HIP(hipMemcpyAsync(pl->h_scores.data(), pl->scores_bfs.p, sizeof(double) * 5 * (size_t)pl->n_nodes, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(h_scal, pl->scalars.p, sizeof(h_scal), hipMemcpyDeviceToHost, st));
+    PMX_D2H(pl->h_scores, pl->scores_bfs, 5 * (size_t)pl->n_nodes, st);
+    PMX_D2H(h_scal, pl->scalars, st);
     tree_status = 0;
-    if (persistent) PMX_HIP(hipMemcpyAsync(&tree_status, pl->tree_done.p + pl->n_nodes, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (persistent) PMX_D2H(&tree_status, pmx::at(pl->tree_done, pl->n_nodes), 1, st);
     PMX_HIP(hipStreamSynchronize(st));
 }
 
@@ -1506,11 +1496,10 @@ void ScoreStage::fetch() {
 // without seeing its parent's flag gave up (the GPU is shared with another process, or with collectives in
 // flight).  The level kernels need no co-residency and add the same terms in the same order: redo with them.
 void ScoreStage::redo_by_levels() {
-    PMX_HIP(hipMemsetAsync(pl->tree_done.p + pl->n_nodes, 0, sizeof(uint32_t), st));
+    PMX_ZERO(pmx::at(pl->tree_done, pl->n_nodes), 1, st);
     persistent = false;
     pl->last_redone = 1;
     launch_levels();
-    PMX_HIP(hipGetLastError());
     fetch();
 }
 
@@ -1585,9 +1574,9 @@ int pmx_place_node_outputs(pmx_ctx* ctx, pmx_place* pl, double* scores5, double*
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     const size_t n = (size_t)pl->n_nodes;
-    if (scores5) PMX_HIP(hipMemcpyAsync(scores5, pl->scores5.p, sizeof(double) * 5 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (metrics5) PMX_HIP(hipMemcpyAsync(metrics5, pl->metrics5.p, sizeof(double) * 5 * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (counts2) PMX_HIP(hipMemcpyAsync(counts2, pl->counts2.p, sizeof(int64_t) * 2 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (scores5) PMX_D2H(scores5, pl->scores5, 5 * n, ctx->stream);
+    if (metrics5) PMX_D2H(metrics5, pl->metrics5, 5 * n, ctx->stream);
+    if (counts2) PMX_D2H(counts2, pl->counts2, 2 * n, ctx->stream);
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return PMX_OK;
     PMX_CATCH
@@ -1599,8 +1588,8 @@ int64_t pmx_place_kept_seeds(pmx_ctx* ctx, pmx_place* pl, uint64_t* hash, double
     PMX_HIP(hipSetDevice(ctx->device));
     if (cap < pl->n_kept) return pl->n_kept;
     if (pl->n_kept > 0) {
-        if (hash) PMX_HIP(hipMemcpyAsync(hash, pl->kept_hash.p, sizeof(uint64_t) * pl->n_kept, hipMemcpyDeviceToHost, ctx->stream));
-        if (logc) PMX_HIP(hipMemcpyAsync(logc, pl->kept_log.p, sizeof(double) * pl->n_kept, hipMemcpyDeviceToHost, ctx->stream));
+        if (hash) PMX_D2H(hash, pl->kept_hash, pl->n_kept, ctx->stream);
+        if (logc) PMX_D2H(logc, pl->kept_log, pl->n_kept, ctx->stream);
     }
     PMX_HIP(hipStreamSynchronize(ctx->stream));
     return pl->n_kept;

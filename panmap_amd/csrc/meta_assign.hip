@@ -653,7 +653,7 @@ void AssignStage::begin() {
     d_state.alloc(n + (breadth ? 3 : 0));   // (k_meta_breadth_rows reads the states by whole words)
     if (max_taxa > 0) {
         d_ntax.alloc(n); d_tax.alloc(n * (size_t)max_taxa);
-        PMX_HIP(hipMemsetAsync(d_tax.p, 0, sizeof(uint32_t) * n * (size_t)max_taxa, st));
+        PMX_ZERO(d_tax, n * (size_t)max_taxa, st);
         timer_sum_reset(ctx, "meta_assign_taxa");
     }
     timer_sum_reset(ctx, "meta_assign");
@@ -663,7 +663,7 @@ void AssignStage::begin() {
         timer_sum_reset(ctx, "meta_breadth");
         breadth_begin();
     }
-    PMX_HIP(hipMemsetAsync(d_count.p, 0, sizeof(uint32_t) * (n + 1), st));
+    PMX_ZERO(d_count, n + 1, st);
 }
 
 // Merged reads [r0, r1): their distinct seedmers' rows, the reads' maxima and assigned nodes.
@@ -685,8 +685,8 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     d_wmask.ensure((size_t)n * (size_t)words); d_wmax.ensure((size_t)n * (size_t)words); d_off.ensure((size_t)n + 1);
     if (touch) d_touch.ensure(mat);
     if (near) d_near.ensure((size_t)n * (size_t)words);
-    PMX_HIP(hipMemcpyAsync(d_uniq.p, uniq.data(), sizeof(uint64_t) * (size_t)n_rows, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(d_uid.p, uid.data(), sizeof(uint32_t) * uid.size(), hipMemcpyHostToDevice, st));
+    PMX_H2D(d_uniq, uniq, n_rows, st);
+    PMX_H2D(d_uid, uid, st);
     std::vector<int64_t> car_off;   // breadth: the chunk's inverted list, alive until the synchronize below
     std::vector<uint32_t> car;
     if (breadth) {
@@ -711,36 +711,34 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
             }
         }
         d_car_off.ensure(car_off.size()); d_car.ensure(car.size()); d_row_id.ensure((size_t)n_rows);
-        PMX_HIP(hipMemcpyAsync(d_car_off.p, car_off.data(), sizeof(int64_t) * car_off.size(), hipMemcpyHostToDevice, st));
-        if (!car.empty()) PMX_HIP(hipMemcpyAsync(d_car.p, car.data(), sizeof(uint32_t) * car.size(), hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_row_id.p, ids.data(), sizeof(uint32_t) * (size_t)n_rows, hipMemcpyHostToDevice, st));
+        PMX_H2D(d_car_off, car_off, st);
+        if (!car.empty()) PMX_H2D(d_car, car, st);
+        PMX_H2D(d_row_id, ids, n_rows, st);
     }
     timer_begin(ctx, "meta_assign");
-    PMX_HIP(hipMemsetAsync(d_fwd.p, 0, sizeof(unsigned long long) * mat, st));
-    PMX_HIP(hipMemsetAsync(d_rev.p, 0, sizeof(unsigned long long) * mat, st));
-    if (touch) PMX_HIP(hipMemsetAsync(d_touch.p, 0, sizeof(unsigned long long) * mat, st));
+    PMX_ZERO(d_fwd, mat, st);
+    PMX_ZERO(d_rev, mat, st);
+    if (touch) PMX_ZERO(d_touch, mat, st);
     if (m->n_changes > 0)
-        hipLaunchKernelGGL(k_assign_mark_ends, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->ch_key.p, m->ch_pc.p, m->ch_cc.p,
-                           m->ch_node.p, m->n_changes, m->subtree_end.p, m->n_nodes, d_uniq.p, n_rows, words, d_fwd.p, d_rev.p,
-                           touch ? d_touch.p : nullptr);
-    hipLaunchKernelGGL(k_assign_prefix_xor, dim3(grid_for(2 * n_rows * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words);
+        PMX_LAUNCH(k_assign_mark_ends, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->ch_key.p, m->ch_pc.p, m->ch_cc.p,
+                   m->ch_node.p, m->n_changes, m->subtree_end.p, m->n_nodes, d_uniq.p, n_rows, words, d_fwd.p, d_rev.p,
+                   touch ? d_touch.p : nullptr);
+    PMX_LAUNCH(k_assign_prefix_xor, dim3(grid_for(2 * n_rows * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words);
     const dim3 grid(grid_for(n * 64, 256, ctx->n_cu * 16)), block(256);
     meta_with_planes(m->longest, [&](auto planes) {
-        hipLaunchKernelGGL(k_meta_assign_max<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
-                           words, m->n_nodes, discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
+        PMX_LAUNCH(k_meta_assign_max<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
+                   words, m->n_nodes, discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
     });
-    PMX_HIP(hipGetLastError());
     if (max_taxa > 0) {   // its own span: "meta_assign" then ends here, the scan below belongs to "meta_assign_taxa"
         timer_end(ctx, "meta_assign", 1);
         timer_begin(ctx, "meta_assign_taxa");
         if (near)
             meta_with_planes(m->longest, [&](auto planes) {
-                hipLaunchKernelGGL(k_meta_assign_near<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p,
-                                   d_rev.p, touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
+                PMX_LAUNCH(k_meta_assign_near<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p,
+                           d_rev.p, touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
             });
-        hipLaunchKernelGGL(k_meta_assign_taxa, grid, block, 0, st, near ? d_near.p : d_wmask.p, words, n, m->tx_over.p, m->tx_count.p, m->tx_ids.p, max_taxa,
-                           d_state.p + r0, d_count.p + r0, d_ntax.p + r0, d_tax.p + (size_t)r0 * (size_t)max_taxa);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_meta_assign_taxa, grid, block, 0, st, near ? d_near.p : d_wmask.p, words, n, m->tx_over.p, m->tx_count.p, m->tx_ids.p, max_taxa,
+                   d_state.p + r0, d_count.p + r0, d_ntax.p + r0, d_tax.p + (size_t)r0 * (size_t)max_taxa);
     }
     // (d_count has one entry past the last read, zero: the scan's entry n is the chunk's total; the entry it reads past the
     //  chunk's own counts plays no part in any output)
@@ -750,14 +748,12 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
         timer_begin(ctx, "meta_breadth");
         const int rpb = breadth_rows_per_block(n_rows);
         const int64_t items = ((n_rows + rpb - 1) / rpb) * (int64_t)((words + 63) / 64);
-        hipLaunchKernelGGL(k_meta_breadth_rows, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words, d_row_id.p,
-                           d_car_off.p, d_car.p, reinterpret_cast<const uint32_t*>(d_state.p), r0, d_mult.p + r0, d_wmask.p, rpb, breadth_cap, d_hit.p, d_depth.p);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_meta_breadth_rows, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words, d_row_id.p,
+                   d_car_off.p, d_car.p, reinterpret_cast<const uint32_t*>(d_state.p), r0, d_mult.p + r0, d_wmask.p, rpb, breadth_cap, d_hit.p, d_depth.p);
         timer_end(ctx, "meta_breadth", 1);
     }
     h_off.resize((size_t)n + 1);
-    PMX_HIP(hipMemcpyAsync(h_off.data(), d_off.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));   // (uniq / uid go out of scope; the total sizes the list)
+    PMX_D2H_SYNC(h_off, d_off, (size_t)n + 1, st);   // (uniq / uid go out of scope; the total sizes the list)
     timer_sum_add(ctx, "meta_assign");
     if (max_taxa > 0) timer_sum_add(ctx, "meta_assign_taxa");
     if (breadth) timer_sum_add(ctx, "meta_breadth");
@@ -766,12 +762,10 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     if (total == 0) return;
     d_nodes.ensure((size_t)total);
     timer_begin(ctx, "meta_assign_emit");
-    hipLaunchKernelGGL(k_meta_assign_emit, grid, block, 0, st, d_count.p + r0, d_off.p, n, d_wmask.p, words, d_nodes.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_meta_assign_emit, grid, block, 0, st, d_count.p + r0, d_off.p, n, d_wmask.p, words, d_nodes.p);
     timer_end(ctx, "meta_assign_emit", 1);
     m->as_nodes.resize((size_t)(base + total));
-    PMX_HIP(hipMemcpyAsync(m->as_nodes.data() + base, d_nodes.p, sizeof(uint32_t) * (size_t)total, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(m->as_nodes.data() + base, d_nodes, total, st);
     timer_sum_add(ctx, "meta_assign_emit");
 }
 
@@ -779,14 +773,14 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
 // set is the lowest ancestor a of its first node with subtree_end[a] >= its last node.
 void AssignStage::finish() {
     std::vector<uint32_t> first((size_t)n_reads), last((size_t)n_reads);
-    PMX_HIP(hipMemcpyAsync(m->as_max.data(), d_max.p, sizeof(uint16_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(m->as_count.data(), d_count.p, sizeof(uint32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(m->as_state.data(), d_state.p, (size_t)n_reads, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(first.data(), d_first.p, sizeof(uint32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(last.data(), d_last.p, sizeof(uint32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st));
+    PMX_D2H(m->as_max, d_max, n_reads, st);
+    PMX_D2H(m->as_count, d_count, n_reads, st);
+    PMX_D2H(m->as_state, d_state, n_reads, st);
+    PMX_D2H(first, d_first, n_reads, st);
+    PMX_D2H(last, d_last, n_reads, st);
     if (max_taxa > 0) {
-        PMX_HIP(hipMemcpyAsync(m->as_ntax.data(), d_ntax.p, (size_t)n_reads, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(m->as_tax.data(), d_tax.p, sizeof(uint32_t) * (size_t)n_reads * (size_t)max_taxa, hipMemcpyDeviceToHost, st));
+        PMX_D2H(m->as_ntax, d_ntax, n_reads, st);
+        PMX_D2H(m->as_tax, d_tax, (size_t)n_reads * (size_t)max_taxa, st);
     }
     PMX_HIP(hipStreamSynchronize(st));
     for (int64_t r = 0; r < n_reads; ++r) {
@@ -802,13 +796,11 @@ void AssignStage::finish() {
     const int64_t items = ((n_uniq + rpb - 1) / rpb) * (int64_t)((words + 63) / 64);
     timer_begin(ctx, "meta_breadth");
     timer_begin(ctx, "meta_breadth_count");   // (the count kernel alone; "meta_breadth" holds it too)
-    hipLaunchKernelGGL(k_meta_breadth_count, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_hit.p, n_uniq, words, rpb, breadth_cap, d_observed.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_meta_breadth_count, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_hit.p, n_uniq, words, rpb, breadth_cap, d_observed.p);
     timer_end(ctx, "meta_breadth_count", 1);
     timer_end(ctx, "meta_breadth", 1);
-    PMX_HIP(hipMemcpyAsync(m->br_observed.data(), d_observed.p, sizeof(uint64_t) * (size_t)m->n_nodes, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(m->br_depth.data(), d_depth.p, sizeof(uint64_t) * (size_t)m->n_nodes, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H(m->br_observed, d_observed, m->n_nodes, st);
+    PMX_D2H_SYNC(m->br_depth, d_depth, m->n_nodes, st);
     timer_sum_add(ctx, "meta_breadth");
 }
 
@@ -822,10 +814,10 @@ int AssignStage::breadth_rows_per_block(int64_t n_rows) const {
 void AssignStage::breadth_begin() {
     const size_t mat = m->h_uniq.size() * (size_t)words, cols = (size_t)words * 64;
     d_hit.alloc(mat); d_depth.alloc(cols); d_observed.alloc(cols); d_mult.alloc((size_t)n_reads);
-    PMX_HIP(hipMemsetAsync(d_hit.p, 0, sizeof(unsigned long long) * mat, st));
-    PMX_HIP(hipMemsetAsync(d_depth.p, 0, sizeof(unsigned long long) * cols, st));
-    PMX_HIP(hipMemsetAsync(d_observed.p, 0, sizeof(unsigned long long) * cols, st));
-    PMX_HIP(hipMemcpyAsync(d_mult.p, m->h_mult.data(), sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    PMX_ZERO(d_hit, mat, st);
+    PMX_ZERO(d_depth, cols, st);
+    PMX_ZERO(d_observed, cols, st);
+    PMX_H2D(d_mult, m->h_mult, n_reads, st);
     if (const char* f = opt_str(O_META_BREADTH_FLUSH)) breadth_cap = (uint32_t)std::min<long long>(breadth_cap, std::max<long long>(1, atoll(f)));
 }
 
@@ -995,9 +987,9 @@ int pmx_meta_set_taxonomy(pmx_meta* m, const int32_t* node_taxon, int64_t n_node
     }
     const hipStream_t st = m->ctx->stream;
     m->tx_count.ensure(n); m->tx_ids.ensure(n * M); m->tx_over.ensure(words);
-    PMX_HIP(hipMemcpyAsync(m->tx_count.p, m->h_tx_count.data(), n, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(m->tx_ids.p, m->h_tx_ids.data(), sizeof(uint32_t) * n * M, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemcpyAsync(m->tx_over.p, m->h_tx_over.data(), sizeof(unsigned long long) * words, hipMemcpyHostToDevice, st));
+    PMX_H2D(m->tx_count, m->h_tx_count, n, st);
+    PMX_H2D(m->tx_ids, m->h_tx_ids, n * M, st);
+    PMX_H2D(m->tx_over, m->h_tx_over, words, st);
     PMX_HIP(hipStreamSynchronize(st));
     m->max_taxa = max_taxa;
     m->n_taxa = n_taxa;

@@ -384,46 +384,45 @@ void MaskStage::upload() {
         d_read_amp.alloc((size_t)n_reads); d_thr.alloc(thr.size()); d_pair_count.alloc((size_t)n_seedmers); d_pair_key.alloc((size_t)n_seedmers);
         d_akey.alloc((size_t)n_seedmers); d_akey_sorted.alloc((size_t)n_seedmers); d_aval.alloc((size_t)n_seedmers); d_aval_sorted.alloc((size_t)n_seedmers);
         d_head.alloc((size_t)n_seedmers + 1); d_before.alloc((size_t)n_seedmers + 1); d_seed_pid.alloc((size_t)n_seedmers);
-        PMX_HIP(hipMemcpyAsync(d_read_amp.p, m->h_read_amp.data(), sizeof(int32_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_thr.p, thr.data(), sizeof(unsigned long long) * thr.size(), hipMemcpyHostToDevice, st));
+        PMX_H2D(d_read_amp, m->h_read_amp, n_reads, st);
+        PMX_H2D(d_thr, thr, st);
     }
     count_id = grouped ? d_seed_pid.p : m->d_seed_uid.p;
     counters = grouped ? d_pair_count.p : d_count.p;
-    PMX_HIP(hipMemcpyAsync(d_mult.p, m->h_mult.data(), sizeof(int64_t) * (size_t)n_reads, hipMemcpyHostToDevice, st));
+    PMX_H2D(d_mult, m->h_mult, n_reads, st);
     if (n_long > 0) {
         d_long_read.alloc((size_t)n_long); d_long_off.alloc((size_t)n_long + 1); d_key.alloc((size_t)n_keys); d_key_sorted.alloc((size_t)n_keys);
-        PMX_HIP(hipMemcpyAsync(d_long_read.p, long_read.data(), sizeof(uint32_t) * (size_t)n_long, hipMemcpyHostToDevice, st));
-        PMX_HIP(hipMemcpyAsync(d_long_off.p, long_off.data(), sizeof(int64_t) * ((size_t)n_long + 1), hipMemcpyHostToDevice, st));
+        PMX_H2D(d_long_read, long_read, n_long, st);
+        PMX_H2D(d_long_off, long_off, (size_t)n_long + 1, st);
     }
 }
 
 // Leaves: zero in the counters of every hash (and pair), in used[], in the two counters of k_meta_mask_flag and in the entry
 // past the last read of new_len[] / alive[] (the scans run over one entry more: their totals).
 void MaskStage::clear_counters() {
-    PMX_HIP(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long) * (size_t)n_uniq, st));
-    PMX_HIP(hipMemsetAsync(d_used.p, 0, sizeof(uint32_t) * ((size_t)n_uniq + 1), st));
-    PMX_HIP(hipMemsetAsync(d_ctr.p, 0, sizeof(unsigned long long) * 2, st));
-    PMX_HIP(hipMemsetAsync(d_new_len.p + n_reads, 0, sizeof(int64_t), st));
-    PMX_HIP(hipMemsetAsync(d_alive.p + n_reads, 0, sizeof(uint32_t), st));
-    if (grouped) PMX_HIP(hipMemsetAsync(d_pair_count.p, 0, sizeof(unsigned long long) * (size_t)n_seedmers, st));
+    PMX_ZERO(d_count, n_uniq, st);
+    PMX_ZERO(d_used, (size_t)n_uniq + 1, st);
+    PMX_ZERO(d_ctr, 2, st);
+    PMX_ZERO(pmx::at(d_new_len, n_reads), 1, st);
+    PMX_ZERO(pmx::at(d_alive, n_reads), 1, st);
+    if (grouped) PMX_ZERO(d_pair_count, n_seedmers, st);
 }
 
 // Amplicons only: the (amplicon, hash) pairs ranked.  Reads: the merged lists on the device, d_read_amp.  Leaves: d_seed_pid
 // (per entry the rank of its pair, ascending by (amplicon, hash)), d_pair_key (per pair its key), d_before[n_seedmers] (the
 // number of distinct pairs); the "meta_mask_sort" span around the key sort.
 void MaskStage::rank_pairs() {
-    hipLaunchKernelGGL(k_meta_amp_keys, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_read_amp.p, n_reads,
-                       d_akey.p, d_aval.p);
+    PMX_LAUNCH(k_meta_amp_keys, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p, d_read_amp.p, n_reads,
+               d_akey.p, d_aval.p);
     unsigned end_bit = 32;   // (the uid, and the bits of the greatest amplicon)
     while (end_bit < 64 && ((uint64_t)(m->n_amp - 1) >> (end_bit - 32)) != 0) ++end_bit;
     timer_begin(ctx, "meta_mask_sort");   // (a span of its own inside "meta_mask": the share the key sort takes)
     PMX_ROCPRIM(tmp, radix_sort_pairs, d_akey.p, d_akey_sorted.p, d_aval.p, d_aval_sorted.p, (size_t)n_seedmers, 0u, end_bit, st);
     timer_end(ctx, "meta_mask_sort", 1);
-    hipLaunchKernelGGL(k_meta_amp_heads, dim3(grid_for(n_seedmers + 1, 256, G)), dim3(256), 0, st, d_akey_sorted.p, n_seedmers, d_head.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_meta_amp_heads, dim3(grid_for(n_seedmers + 1, 256, G)), dim3(256), 0, st, d_akey_sorted.p, n_seedmers, d_head.p);
     PMX_ROCPRIM(tmp, exclusive_scan, d_head.p, d_before.p, 0u, (size_t)n_seedmers + 1, rocprim::plus<uint32_t>(), st);
-    hipLaunchKernelGGL(k_meta_amp_scatter, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_akey_sorted.p, d_aval_sorted.p, d_head.p, d_before.p,
-                       n_seedmers, d_seed_pid.p, d_pair_key.p);
+    PMX_LAUNCH(k_meta_amp_scatter, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_akey_sorted.p, d_aval_sorted.p, d_head.p, d_before.p,
+               n_seedmers, d_seed_pid.p, d_pair_key.p);
 }
 
 // Reads: count_id (uids, or pids), the multiplicities, the plan.  Leaves: counters[] = per hash (per pair) the sum of the
@@ -431,19 +430,19 @@ void MaskStage::rank_pairs() {
 // longer ones.  With amplicons also d_count[] = every hash's total over its pairs.
 void MaskStage::count() {
     if (n_long < n_reads)
-        hipLaunchKernelGGL(k_meta_mask_count, dim3(grid_for(n_reads * 64, 64 * kMaskWaves, G)), dim3(64 * kMaskWaves), 0, st, m->d_read_off.p, count_id,
-                           d_mult.p, n_reads, bound, counters);
+        PMX_LAUNCH(k_meta_mask_count, dim3(grid_for(n_reads * 64, 64 * kMaskWaves, G)), dim3(64 * kMaskWaves), 0, st, m->d_read_off.p, count_id,
+                   d_mult.p, n_reads, bound, counters);
     if (n_long > 0) {
-        hipLaunchKernelGGL(k_meta_mask_long_keys, dim3(grid_for(n_long * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, count_id, d_long_read.p,
-                           d_long_off.p, n_long, d_key.p);
+        PMX_LAUNCH(k_meta_mask_long_keys, dim3(grid_for(n_long * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, count_id, d_long_read.p,
+                   d_long_off.p, n_long, d_key.p);
         unsigned end_bit = 33;   // (the uid, and the bits of the greatest ordinal)
         while (end_bit < 64 && ((uint64_t)(n_long - 1) >> (end_bit - 32)) != 0) ++end_bit;
         PMX_ROCPRIM(tmp, radix_sort_keys, d_key.p, d_key_sorted.p, (size_t)n_keys, 0u, end_bit, st);
-        hipLaunchKernelGGL(k_meta_mask_long_add, dim3(grid_for(n_keys, 256, G)), dim3(256), 0, st, d_key_sorted.p, n_keys, d_long_read.p, d_mult.p, counters);
+        PMX_LAUNCH(k_meta_mask_long_add, dim3(grid_for(n_keys, 256, G)), dim3(256), 0, st, d_key_sorted.p, n_keys, d_long_read.p, d_mult.p, counters);
     }
     if (grouped)
-        hipLaunchKernelGGL(k_meta_amp_totals, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_pair_key.p, d_pair_count.p, d_before.p + n_seedmers,
-                           d_count.p);
+        PMX_LAUNCH(k_meta_amp_totals, dim3(grid_for(n_seedmers, 256, G)), dim3(256), 0, st, d_pair_key.p, d_pair_count.p, d_before.p + n_seedmers,
+                   d_count.p);
 }
 
 // Reads: counters[], the thresholds.  Leaves: per read its new length and alive[], per hash used[], their exclusive scans
@@ -451,18 +450,17 @@ void MaskStage::count() {
 // left_seedmers / left_reads / left_uniq, h_ctr[] and n_pairs on the host.
 void MaskStage::flag_and_size() {
     with_grouped(grouped, [&](auto g) {
-        hipLaunchKernelGGL(k_meta_mask_flag<decltype(g)::value>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p,
-                           n_reads, counters, threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, d_seed_pid.p, d_read_amp.p, d_thr.p);
+        PMX_LAUNCH(k_meta_mask_flag<decltype(g)::value>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p,
+                   n_reads, counters, threshold, whole_reads ? 1 : 0, d_new_len.p, d_alive.p, d_used.p, d_ctr.p, d_seed_pid.p, d_read_amp.p, d_thr.p);
     });
-    PMX_HIP(hipGetLastError());
     PMX_ROCPRIM(tmp, exclusive_scan, d_new_len.p, d_new_off.p, (int64_t)0, (size_t)n_reads + 1, rocprim::plus<int64_t>(), st);
     PMX_ROCPRIM(tmp, exclusive_scan, d_alive.p, d_read_pos.p, 0u, (size_t)n_reads + 1, rocprim::plus<uint32_t>(), st);
     PMX_ROCPRIM(tmp, exclusive_scan, d_used.p, d_uid_pos.p, 0u, (size_t)n_uniq + 1, rocprim::plus<uint32_t>(), st);
-    PMX_HIP(hipMemcpyAsync(&left_seedmers, d_new_off.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(&left_reads, d_read_pos.p + n_reads, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(&left_uniq, d_uid_pos.p + n_uniq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(h_ctr, d_ctr.p, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
-    if (grouped) PMX_HIP(hipMemcpyAsync(&n_pairs, d_before.p + n_seedmers, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PMX_D2H(&left_seedmers, pmx::at(d_new_off, n_reads), 1, st);
+    PMX_D2H(&left_reads, pmx::at(d_read_pos, n_reads), 1, st);
+    PMX_D2H(&left_uniq, pmx::at(d_uid_pos, n_uniq), 1, st);
+    PMX_D2H(h_ctr, d_ctr, st);
+    if (grouped) PMX_D2H(&n_pairs, pmx::at(d_before, n_seedmers), 1, st);
     PMX_HIP(hipStreamSynchronize(st));
 }
 
@@ -473,13 +471,12 @@ void MaskStage::compact() {
     o_hash.alloc((size_t)left_seedmers); o_uid.alloc((size_t)left_seedmers); o_rev.alloc((size_t)left_seedmers); o_uniq.alloc((size_t)left_uniq);
     if (grouped) o_amp.alloc((size_t)left_reads);
     with_grouped(grouped, [&](auto g) {
-        hipLaunchKernelGGL(k_meta_mask_compact<decltype(g)::value>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p,
-                           m->d_seed_rev.p, m->d_uniq.p, d_mult.p, n_reads, counters, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p,
-                           o_hash.p, o_uid.p, o_rev.p, o_mult.p, d_seed_pid.p, d_read_amp.p, d_thr.p, o_amp.p);
+        PMX_LAUNCH(k_meta_mask_compact<decltype(g)::value>, dim3(grid_for(n_reads * 64, 256, G)), dim3(256), 0, st, m->d_read_off.p, m->d_seed_uid.p,
+                   m->d_seed_rev.p, m->d_uniq.p, d_mult.p, n_reads, counters, threshold, d_new_len.p, d_new_off.p, d_read_pos.p, d_uid_pos.p, o_off.p,
+                   o_hash.p, o_uid.p, o_rev.p, o_mult.p, d_seed_pid.p, d_read_amp.p, d_thr.p, o_amp.p);
     });
-    hipLaunchKernelGGL(k_meta_mask_compact_uniq, dim3(grid_for(n_uniq, 256, G)), dim3(256), 0, st, m->d_uniq.p, d_count.p, d_used.p, d_uid_pos.p, n_uniq,
-                       o_uniq.p, o_count.p);
-    PMX_HIP(hipGetLastError());
+    PMX_LAUNCH(k_meta_mask_compact_uniq, dim3(grid_for(n_uniq, 256, G)), dim3(256), 0, st, m->d_uniq.p, d_count.p, d_used.p, d_uid_pos.p, n_uniq,
+               o_uniq.p, o_count.p);
 }
 
 // Reads: o_*, d_count / d_read_pos, the pair table.  Leaves: the sample as its survivors -- the host's copies, which
@@ -488,27 +485,27 @@ void MaskStage::compact() {
 // (group, hash, count) triples before masking in pair order, the survivors' amplicons and amp_left.
 void MaskStage::publish() {
     std::vector<uint32_t> read_pos((size_t)n_reads + 1);
-    PMX_HIP(hipMemcpyAsync(m->lowcov_count.data(), d_count.p, sizeof(int64_t) * (size_t)n_uniq, hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipMemcpyAsync(read_pos.data(), d_read_pos.p, sizeof(uint32_t) * ((size_t)n_reads + 1), hipMemcpyDeviceToHost, st));
+    PMX_D2H(m->lowcov_count, d_count, n_uniq, st);
+    PMX_D2H(read_pos, d_read_pos, (size_t)n_reads + 1, st);
     m->h_read_off.assign((size_t)left_reads + 1, 0);
     m->h_mult.resize((size_t)left_reads);
     m->h_seed_hash.resize((size_t)left_seedmers); m->h_seed_uid.resize((size_t)left_seedmers); m->h_seed_rev.resize((size_t)left_seedmers);
     m->h_uniq.resize((size_t)left_uniq);
-    PMX_HIP(hipMemcpyAsync(m->h_read_off.data(), o_off.p, sizeof(int64_t) * ((size_t)left_reads + 1), hipMemcpyDeviceToHost, st));
+    PMX_D2H(m->h_read_off, o_off, (size_t)left_reads + 1, st);
     if (left_reads > 0) {
-        PMX_HIP(hipMemcpyAsync(m->h_mult.data(), o_mult.p, sizeof(int64_t) * (size_t)left_reads, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(m->h_seed_hash.data(), o_hash.p, sizeof(uint64_t) * (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(m->h_seed_uid.data(), o_uid.p, sizeof(uint32_t) * (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(m->h_seed_rev.data(), o_rev.p, (size_t)left_seedmers, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(m->h_uniq.data(), o_uniq.p, sizeof(uint64_t) * (size_t)left_uniq, hipMemcpyDeviceToHost, st));
+        PMX_D2H(m->h_mult, o_mult, left_reads, st);
+        PMX_D2H(m->h_seed_hash, o_hash, left_seedmers, st);
+        PMX_D2H(m->h_seed_uid, o_uid, left_seedmers, st);
+        PMX_D2H(m->h_seed_rev, o_rev, left_seedmers, st);
+        PMX_D2H(m->h_uniq, o_uniq, left_uniq, st);
     }
     std::vector<uint64_t> pair_key((size_t)n_pairs);
     if (grouped) {
         m->ampc_count.resize((size_t)n_pairs);
         m->h_read_amp.resize((size_t)left_reads);
-        PMX_HIP(hipMemcpyAsync(pair_key.data(), d_pair_key.p, sizeof(uint64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
-        PMX_HIP(hipMemcpyAsync(m->ampc_count.data(), d_pair_count.p, sizeof(int64_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, st));
-        if (left_reads > 0) PMX_HIP(hipMemcpyAsync(m->h_read_amp.data(), o_amp.p, sizeof(int32_t) * (size_t)left_reads, hipMemcpyDeviceToHost, st));
+        PMX_D2H(pair_key, d_pair_key, n_pairs, st);
+        PMX_D2H(m->ampc_count, d_pair_count, n_pairs, st);
+        PMX_D2H(m->h_read_amp, o_amp, left_reads, st);
     }
     PMX_HIP(hipStreamSynchronize(st));
     if (grouped) {

@@ -132,18 +132,16 @@ extern "C" int pmx_readset_select(pmx_ctx* ctx, const pmx_readset* src, const in
     dst->nw_tmp.ensure((size_t)n + 1);
     dst->woff.ensure((size_t)n + 1);
     dst->stats.ensure(2);
-    PMX_HIP(hipMemsetAsync(dst->stats.p, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    if (n > 0) PMX_HIP(hipMemcpyAsync(dst->sel_idx.p, idx, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_select_lengths, dim3(grid_for(n + 1, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, src->off.p, dst->sel_idx.p, n, dst->len_tmp.p,
-                       dst->nw_tmp.p, dst->stats.p);
-    PMX_HIP(hipGetLastError());
+    PMX_ZERO(dst->stats, 2, ctx->stream);
+    PMX_H2D(dst->sel_idx, idx, n, ctx->stream);
+    PMX_LAUNCH(k_select_lengths, dim3(grid_for(n + 1, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, src->off.p, dst->sel_idx.p, n, dst->len_tmp.p,
+               dst->nw_tmp.p, dst->stats.p);
     PMX_ROCPRIM(dst->scan_tmp, exclusive_scan, dst->len_tmp.p, dst->off.p, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), ctx->stream);
     PMX_ROCPRIM(dst->scan_tmp, exclusive_scan, dst->nw_tmp.p, dst->woff.p, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), ctx->stream);
     struct { int64_t total, n_words; unsigned long long st[2]; } h = {0, 0, {0, 0}};
-    PMX_HIP(hipMemcpyAsync(&h.total, dst->off.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(&h.n_words, dst->woff.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipMemcpyAsync(h.st, dst->stats.p, sizeof(h.st), hipMemcpyDeviceToHost, ctx->stream));
-    PMX_HIP(hipStreamSynchronize(ctx->stream));   // (sizes the output; `idx` has been read by now)
+    PMX_D2H(&h.total, pmx::at(dst->off, n), 1, ctx->stream);
+    PMX_D2H(&h.n_words, pmx::at(dst->woff, n), 1, ctx->stream);
+    PMX_D2H_SYNC(h.st, dst->stats, ctx->stream);   // (sizes the output; `idx` has been read by now)
     own_ensure(dst->ascii, (size_t)h.total + 32);
     if (src->has_qual) dst->qual.ensure((size_t)h.total + 32);
     dst->words.ensure((size_t)std::max<int64_t>(h.n_words, 1));
@@ -152,9 +150,8 @@ extern "C" int pmx_readset_select(pmx_ctx* ctx, const pmx_readset* src, const in
     if (recs) dst->recs.ensure((size_t)n * 64);
     if (h.total > 0) {
         timer_begin(ctx, "select");
-        hipLaunchKernelGGL(k_select_copy, dim3(grid_for(n, 4, ctx->n_cu * 32)), dim3(256), 0, ctx->stream, src->ascii.p, src->has_qual ? src->qual.p : (const uint8_t*)nullptr,
-                           src->off.p, dst->sel_idx.p, n, dst->off.p, dst->ascii.p, src->has_qual ? dst->qual.p : (uint8_t*)nullptr);
-        PMX_HIP(hipGetLastError());
+        PMX_LAUNCH(k_select_copy, dim3(grid_for(n, 4, ctx->n_cu * 32)), dim3(256), 0, ctx->stream, src->ascii.p, src->has_qual ? src->qual.p : (const uint8_t*)nullptr,
+                   src->off.p, dst->sel_idx.p, n, dst->off.p, dst->ascii.p, src->has_qual ? dst->qual.p : (uint8_t*)nullptr);
         timer_end(ctx, "select", 1);
     } else {
         timer_cancel(ctx, "select");

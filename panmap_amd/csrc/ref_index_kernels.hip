@@ -127,20 +127,19 @@ bool build_ref_index_device(hipStream_t st, const char* reference, int64_t ref_l
     d.keys2.ensure(cap);
     d.pos.ensure(cap);
     d.ctr.ensure(4);
-    PMX_HIP(hipMemcpyAsync(d.ascii.p, reference, (size_t)len, hipMemcpyHostToDevice, st));
-    PMX_HIP(hipMemsetAsync(d.ctr.p, 0, 4 * sizeof(unsigned long long), st));
-    PMX_HIP(hipMemsetAsync(d.keys.p, 0xff, cap * sizeof(uint64_t), st));
-    hipLaunchKernelGGL(k_ref_encode, dim3((unsigned)((n_words + 127) / 128)), dim3(128), 0, st, d.ascii.p, len, d.seq.p, d.pk.p, d.pk_amb.p, n_words);
+    PMX_H2D(d.ascii, reference, len, st);
+    PMX_ZERO(d.ctr, 4, st);
+    PMX_FILL(d.keys, 0xff, cap, st);
+    PMX_LAUNCH(k_ref_encode, dim3((unsigned)((n_words + 127) / 128)), dim3(128), 0, st, d.ascii.p, len, d.seq.p, d.pk.p, d.pk_amb.p, n_words);
     const int n_slices = (len + kSlice - 1) / kSlice;
-    hipLaunchKernelGGL(k_ref_sketch, dim3((unsigned)((n_slices + 63) / 64)), dim3(64), 0, st, d.seq.p, len, o.w, o.k, d.keys.p, cap, d.ctr.p);
+    PMX_LAUNCH(k_ref_sketch, dim3((unsigned)((n_slices + 63) / 64)), dim3(64), 0, st, d.seq.p, len, o.w, o.k, d.keys.p, cap, d.ctr.p);
     const unsigned end_bit = (unsigned)(2 * o.k + kPosBits);
     PMX_ROCPRIM(d.tmp, radix_sort_keys, d.keys.p, d.keys2.p, (size_t)cap, 0, end_bit, st);
     // the unused tail of the key buffer is all ones: the largest value in the sorted bits, and no minimizer has every
     // position bit set (ref_index_device_supported), so the sentinels sort behind the minimizers and k_ref_runs skips them
-    hipLaunchKernelGGL(k_ref_runs, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, d.keys2.p, (int64_t)cap, d.pos.p, d.ctr.p);
+    PMX_LAUNCH(k_ref_runs, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, d.keys2.p, (int64_t)cap, d.pos.p, d.ctr.p);
     unsigned long long h[4] = {0, 0, 0, 0};
-    PMX_HIP(hipMemcpyAsync(h, d.ctr.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    PMX_HIP(hipStreamSynchronize(st));
+    PMX_D2H_SYNC(h, d.ctr, 3, st);
     const int64_t n_mv = (int64_t)h[0];
     if ((uint64_t)n_mv > cap) throw std::runtime_error("reference sketch emitted more minimizers than positions");
     const size_t n_keys = (size_t)h[1], n_ge10 = (size_t)h[2];
@@ -154,10 +153,9 @@ bool build_ref_index_device(hipStream_t st, const char* reference, int64_t ref_l
     while (tcap < n_keys * 2 + 2) tcap <<= 1;
     d.ht.ensure(tcap);
     d.ht_pv.ensure(tcap);
-    PMX_HIP(hipMemsetAsync(d.ht.p, 0xff, tcap * sizeof(HtEnt), st));
-    PMX_HIP(hipMemsetAsync(d.ht_pv.p, 0xff, tcap * sizeof(uint32_t), st));
-    if (n_mv > 0) hipLaunchKernelGGL(k_ref_table, dim3((unsigned)((n_mv + 255) / 256)), dim3(256), 0, st, d.keys2.p, n_mv, d.ht.p, d.ht_pv.p, (uint32_t)(tcap - 1));
-    PMX_HIP(hipGetLastError());
+    PMX_FILL(d.ht, 0xff, tcap, st);
+    PMX_FILL(d.ht_pv, 0xff, tcap, st);
+    if (n_mv > 0) PMX_LAUNCH(k_ref_table, dim3((unsigned)((n_mv + 255) / 256)), dim3(256), 0, st, d.keys2.p, n_mv, d.ht.p, d.ht_pv.p, (uint32_t)(tcap - 1));
     d.ht_mask = (uint32_t)(tcap - 1);
     d.n_mv = n_mv;
     d.n_keys = (int64_t)n_keys;

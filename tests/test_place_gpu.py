@@ -406,3 +406,41 @@ def test_read_collapse_keeps_the_histogram(pmx, oracle, ctx, sars, sars_index):
     fixed = [r for r in reads if len(r) == 150]
     assert len(fixed) > 4096
     _check_place(pmx, oracle, ctx, sars_index, fixed)
+
+
+def test_seeding_redone_after_the_optimistic_table_overflows(pmx, oracle, ctx, sars, sars_index, monkeypatch, capfd):
+    """PMX_SEED_BOUND_DIV=1048576 sizes the optimistic pass's table at its floor of 65,536 slots; 60,000 simulated reads carry
+    115,522 distinct seeds, so inserts fail, the counters and the table are cleared and the pass is redone with the safe bound.
+    The redo ran (the profile line reports failed inserts), the result equals the oracle's, and after reset() the same placer
+    gives the same histogram and best nodes without the switch: nothing of the first pass's counters survives."""
+    import re
+    concat, off = pmx.simulate_paired_reads(sars.genome("node_7618"), 60000, seed=1)
+    reads = _as_reads(concat, off)
+    monkeypatch.setenv("PMX_SEED_BOUND_DIV", "1048576")
+    monkeypatch.setenv("PMX_PLACE_PROF", "1")
+    pmx.reload_options()
+    capfd.readouterr()
+    want = _check_place(pmx, oracle, ctx, sars_index, reads)
+    lines = re.findall(r"\[pmx place\] seeding with bound 1/1048576: table (\d+) slots, (\d+) failed inserts", capfd.readouterr().err)
+    assert lines and int(lines[0][1]) > 0, lines
+    params = pmx.TraversalParams()
+    placer = pmx.Placer(ctx, sars_index)
+    placer.reset()
+    rs = pmx.ReadSet(ctx, reads)
+    placer.add_reads(rs, params)
+    forced = placer.score(params, len(reads))
+    forced_hist = placer.histogram()
+    monkeypatch.delenv("PMX_SEED_BOUND_DIV")
+    monkeypatch.delenv("PMX_PLACE_PROF")
+    pmx.reload_options()
+    placer.reset()
+    placer.add_reads(rs, params)
+    plain = placer.score(params, len(reads))
+    plain_hist = placer.histogram()
+    assert len(plain_hist[0]) > 65536
+    for a, b in zip(forced_hist, plain_hist):
+        assert np.array_equal(a, b)
+    for res in (forced, plain):
+        assert list(res.best_index) == list(want.best_index) and list(res.best_score) == list(want.best_score)
+    rs.close()
+    placer.close()
