@@ -166,6 +166,13 @@ int pmx_readset_has_qualities(const pmx_readset *rs);
 /* download a read set's ASCII bases, offsets (n+1, starting at 0) and, if present and qual != NULL, qualities:
    returns the number of bases; copies only when cap suffices */
 int64_t pmx_readset_export(pmx_ctx *ctx, const pmx_readset *rs, char *concat, int64_t cap, int64_t *offsets, char *qual);
+/* TEST ACCESSOR: download the packed form of a packed read set as the pack kernels wrote it: words[n_words] (2 bits per base),
+   amb[n_words] (1 bit per base), woff[n+1] (word offsets) and, when the set has read records (no read longer than 160 bases;
+   *has_recs says so), the n x 64 record bytes.  Returns n_words and copies only when cap_words suffices and the pointers the
+   set needs are there (recs may be NULL for a set without records), so a first call with cap_words = -1 asks for the sizes.
+   An unpacked set is PMX_ERR_ARG.  Copies on the context's stream and a wait for it; no kernel. */
+int64_t pmx_readset_export_packed(pmx_ctx *ctx, const pmx_readset *rs, uint64_t *words, uint32_t *amb, int64_t cap_words,
+                                  int64_t *woff, uint8_t *recs, int *has_recs);
 void pmx_readset_free(pmx_ctx *ctx, pmx_readset *rs);
 int64_t pmx_readset_num_reads(const pmx_readset *rs);
 

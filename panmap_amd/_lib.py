@@ -136,6 +136,7 @@ SIGNATURES = {
     "pmx_readset_is_hpc": (_i32, [_vp]),
     "pmx_readset_has_qualities": (_i32, [_vp]),
     "pmx_readset_export": (_i64, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    "pmx_readset_export_packed": (_i64, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "pmx_readset_free": (None, [_vp, _vp]),
     "pmx_readset_num_reads": (_i64, [_vp]),
     "pmx_place_create": (_i32, [_vp, _vp, _PP]),

@@ -488,6 +488,23 @@ class ReadSet:
             raise _lib.PmxError(got if got < 0 else -5, "pmx_readset_export")
         return concat[:total].tobytes(), off, (qual[:total].tobytes() if has_qual else None)
 
+    def export_packed(self):
+        """(words, amb, woff, records | None): the packed form as the pack kernels wrote it (a test accessor): uint64 2-bit
+        words, uint32 ambiguity words, the n+1 int64 word offsets and, when no read is longer than 160 bases, the (n, 64)
+        uint8 read records"""
+        has = C.c_int(0)
+        n_words = int(lib.pmx_readset_export_packed(self.ctx._h, self._h, None, None, -1, None, None, C.byref(has)))
+        if n_words < 0:
+            raise _lib.PmxError(n_words, "pmx_readset_export_packed")
+        words, amb = np.zeros(max(n_words, 1), np.uint64), np.zeros(max(n_words, 1), np.uint32)
+        woff = np.zeros(self.n_reads + 1, np.int64)
+        recs = np.zeros((self.n_reads, 64), np.uint8) if has.value else None
+        got = int(lib.pmx_readset_export_packed(self.ctx._h, self._h, words.ctypes.data, amb.ctypes.data, n_words, woff.ctypes.data,
+                                                recs.ctypes.data if recs is not None else None, None))
+        if got != n_words:
+            raise _lib.PmxError(got if got < 0 else -5, "pmx_readset_export_packed")
+        return words[:n_words], amb[:n_words], woff, recs
+
     def close(self):
         if self._h:
             lib.pmx_readset_free(self.ctx._h, self._h)

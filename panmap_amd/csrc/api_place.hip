@@ -665,6 +665,23 @@ int64_t pmx_readset_export(pmx_ctx* ctx, const pmx_readset* rs, char* concat, in
     PMX_CATCH
 }
 
+// test accessor: the packed form as the pack kernels left it.  Copies alone, on the context's stream; no kernel.
+int64_t pmx_readset_export_packed(pmx_ctx* ctx, const pmx_readset* rs, uint64_t* words, uint32_t* amb, int64_t cap_words, int64_t* woff,
+                                  uint8_t* recs, int* has_recs) {
+    if (!ctx || !rs) return PMX_ERR_ARG;
+    if (!rs->packed) return fail(PMX_ERR_ARG, "read set is not packed (call pmx_readset_pack / pmx_readset_pack_range first)");
+    if (has_recs) *has_recs = rs->has_recs ? 1 : 0;
+    if (cap_words < rs->n_words || (rs->n_words > 0 && (!words || !amb)) || !woff || (rs->has_recs && !recs)) return rs->n_words;
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    PMX_D2H(words, rs->words, (size_t)rs->n_words, ctx->stream);
+    PMX_D2H(amb, rs->amb, (size_t)rs->n_words, ctx->stream);
+    if (rs->has_recs) PMX_D2H(recs, rs->recs, (size_t)rs->n * 64, ctx->stream);
+    PMX_D2H_SYNC(woff, rs->woff, (size_t)rs->n + 1, ctx->stream);
+    return rs->n_words;
+    PMX_CATCH
+}
+
 void pmx_readset_free(pmx_ctx* ctx, pmx_readset* rs) {
     if (ctx) (void)hipSetDevice(ctx->device);
     delete rs;
