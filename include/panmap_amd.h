@@ -456,6 +456,45 @@ int pmx_align_dp_probe(pmx_ctx *ctx, pmx_aligner *al, int path, int max_read_len
                        const uint8_t *seqs, const int64_t *q_off, const int64_t *t_off, int64_t n, const int32_t *w,
                        const int32_t *zdrop, const int32_t *end_bonus, const int32_t *flag, pmx_dp_probe_result *out,
                        uint32_t *cigar_arena, int64_t arena_cap, pmx_dp_probe_caps caps[2]);
+/* TEST ACCESSOR (not on the product path): one operation of the align tiers' anchor sort / chaining code on a batch of anchor lists,
+ * exactly as map_frag calls it -- the entry point of the parity tests against the reference's radix_sort_128x / radix_sort_64 /
+ * mg_lchain_dp / mg_lchain_rmq.
+ *   path  WAVE_LONG / WAVE_GENERAL: one list per wave on the layout of the long-read launch / the general layout of the wave tiers
+ *         (the wave forms: rank sort, chain_fill_wave, chain_fill_wide_wave, the ballot backtrack);
+ *         LANE: one list per lane on the interleaved arena of the thread-per-pair kernel (the scalar forms, 64 different lists per wave).
+ *   op    SORT128 radix_sort_128x, SORT64 radix_sort_64 (the x words; y is ignored and comes back 0), CHAIN_DP chain_dp,
+ *         CHAIN_RMQ chain_rmq with the arguments of the long-join pass.  A path that does not compile an operation: PMX_ERR_UNSUPPORTED.
+ * par: the chaining parameters; a field set to PMX_CHAIN_PROBE_DEFAULT (floats: NaN) takes the value of the aligner's preset
+ * (max_dist_x / max_dist_y: max_gap; n_seg: 1), and the values in force are written back.  anchors: (x, y) word pairs in the
+ * reference's packing, list i at [a_off[i], a_off[i + 1]); qlen: two read lengths per list (NULL: 0).  out_anchors / out_u: list i's
+ * resulting anchors (out[i].n_a of them) and chains (out[i].n_u words score << 32 | count) from a_off[i] on.  out[i].status: the
+ * PMX_ST_* bits the operation left (1 overflow, 2 unsupported).  A list longer than caps->max_anchor is not served (served = 0,
+ * nothing written).  caps receives the capacities of the layout also when n == 0. */
+#define PMX_CHAIN_PROBE_WAVE_LONG 0
+#define PMX_CHAIN_PROBE_WAVE_GENERAL 1
+#define PMX_CHAIN_PROBE_LANE 2
+#define PMX_CHAIN_PROBE_SORT128 0
+#define PMX_CHAIN_PROBE_SORT64 1
+#define PMX_CHAIN_PROBE_CHAIN_DP 2
+#define PMX_CHAIN_PROBE_CHAIN_RMQ 3
+#define PMX_CHAIN_PROBE_DEFAULT INT32_MIN
+typedef struct {
+    int32_t bw, bw_long, max_gap, max_chain_skip, max_chain_iter, min_cnt, min_chain_score;
+    float chn_pen_gap, chn_pen_skip;
+    int32_t rmq_inner_dist, rmq_size_cap, max_dist_x, max_dist_y, n_seg;
+} pmx_chain_probe_params;
+typedef struct {
+    int32_t served;
+    uint32_t status;
+    int64_t n_a;
+    int32_t n_u, reserved;
+} pmx_chain_probe_result;
+typedef struct {
+    int32_t max_anchor, max_reg, max_qlen, reserved;
+} pmx_chain_probe_caps;
+int pmx_align_chain_probe(pmx_ctx *ctx, pmx_aligner *al, int path, int op, int max_read_len, int n_segs, pmx_chain_probe_params *par,
+                          const uint64_t *anchors, const int64_t *a_off, const int32_t *qlen, int64_t n, pmx_chain_probe_result *out,
+                          uint64_t *out_anchors, uint64_t *out_u, pmx_chain_probe_caps *caps);
 int64_t pmx_align_num_records(const pmx_aligner *al);
 int64_t pmx_align_cigar_words(pmx_ctx *ctx, pmx_aligner *al);
 int pmx_align_fetch(pmx_ctx *ctx, pmx_aligner *al, pmx_aln_record *records, int64_t n_records, uint32_t *cigar_arena,

@@ -353,3 +353,81 @@ def ref_ksw_ll(query, target, mat, gapo, gape):
     score = L.ksw_ll_i16(qp, len(tb), tb, gapo, gape, C.byref(qe), C.byref(te))
     _libc.free(qp)      # (kmalloc of a NULL pool is malloc)
     return int(score), int(qe.value), int(te.value)
+
+
+# ------------------------------------------------------------------ the reference's sort and chaining on their own
+class _Mm128(C.Structure):   # mm128_t (src/3rdparty/minimap2/minimap.h)
+    _fields_ = [("x", C.c_uint64), ("y", C.c_uint64)]
+
+
+_libc.malloc.restype = C.c_void_p
+_libc.malloc.argtypes = [C.c_size_t]
+
+
+def ref_radix_sort_128x(x, y):
+    """radix_sort_128x of the compiled reference (KRADIX_SORT_INIT(128x, ...), src/3rdparty/minimap2/misc.c) on (x, y) pairs:
+    sorted by x, the unstable order of equal keys as the reference leaves it.  -> (x, y) as uint64 arrays"""
+    fn = rlib().radix_sort_128x
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_void_p]
+    a = np.empty((len(x), 2), np.uint64)
+    a[:, 0] = x
+    a[:, 1] = y
+    fn(a.ctypes.data, a.ctypes.data + 16 * len(a))
+    return a[:, 0].copy(), a[:, 1].copy()
+
+
+def ref_radix_sort_64(v):
+    """radix_sort_64 of the compiled reference on uint64 values"""
+    fn = rlib().radix_sort_64
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_void_p]
+    a = np.array(v, np.uint64)
+    fn(a.ctypes.data, a.ctypes.data + 8 * len(a))
+    return a
+
+
+def _ref_chain_call(call, x, y):
+    """the calling convention mg_lchain_dp and mg_lchain_rmq share: the input array is handed over (libc malloc: the callee
+    frees it), the returned anchors and u[] are the caller's to free.  -> (x, y, u) as uint64 arrays"""
+    n = len(x)
+    a = None
+    if n:
+        a = _libc.malloc(16 * n)
+        src = np.empty((n, 2), np.uint64)
+        src[:, 0] = x
+        src[:, 1] = y
+        C.memmove(a, src.ctypes.data, 16 * n)
+    n_u = C.c_int(0)
+    u = C.POINTER(C.c_uint64)()
+    b = call(n, a, C.byref(n_u), C.byref(u))
+    uu = np.array([u[i] for i in range(n_u.value)], np.uint64)
+    n_b = int(np.sum(uu & np.uint64(0xffffffff))) if n_u.value else 0
+    out = np.zeros((n_b, 2), np.uint64)
+    if b and n_b:
+        C.memmove(out.ctypes.data, b, 16 * n_b)
+    if b:
+        _libc.free(b)
+    if u:
+        _libc.free(C.cast(u, C.c_void_p))
+    return out[:, 0].copy(), out[:, 1].copy(), uu
+
+
+def ref_lchain_dp(x, y, max_dist_x, max_dist_y, bw, max_skip, max_iter, min_cnt, min_sc, chn_pen_gap, chn_pen_skip, n_seg):
+    """mg_lchain_dp of the compiled reference (src/3rdparty/minimap2/lchain.c:148-217; is_cdna = 0, km = NULL) on anchors sorted
+    by x.  -> (x, y, u): the chained anchors grouped by chain, u[i] = score << 32 | count"""
+    fn = rlib().mg_lchain_dp
+    fn.restype = C.c_void_p
+    fn.argtypes = [C.c_int] * 7 + [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.POINTER(C.c_int),
+                                   C.POINTER(C.POINTER(C.c_uint64)), C.c_void_p]
+    return _ref_chain_call(lambda n, a, n_u, u: fn(max_dist_x, max_dist_y, bw, max_skip, max_iter, min_cnt, min_sc, chn_pen_gap, chn_pen_skip,
+                                                   0, n_seg, n, a, n_u, u, None), x, y)
+
+
+def ref_lchain_rmq(x, y, max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, min_cnt, min_sc, chn_pen_gap, chn_pen_skip):
+    """mg_lchain_rmq of the compiled reference (src/3rdparty/minimap2/lchain.c:250-369; km = NULL).  -> as ref_lchain_dp"""
+    fn = rlib().mg_lchain_rmq
+    fn.restype = C.c_void_p
+    fn.argtypes = [C.c_int] * 7 + [C.c_float, C.c_float, C.c_int64, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_uint64)), C.c_void_p]
+    return _ref_chain_call(lambda n, a, n_u, u: fn(max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, min_cnt, min_sc, chn_pen_gap,
+                                                   chn_pen_skip, n, a, n_u, u, None), x, y)

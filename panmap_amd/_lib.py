@@ -163,6 +163,7 @@ SIGNATURES = {
     "pmx_align_scoring": (_i32, [_vp, C.POINTER(C.c_int32)]),
     "pmx_align_dp_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(C.c_double)]),
     "pmx_align_dp_probe": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "pmx_align_chain_probe": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     "pmx_place_score": (_i32, [_vp, _vp, C.POINTER(PlaceParams), _i64, C.POINTER(PlaceResult)]),
     "pmx_place_score_info": (_i32, [_vp, C.POINTER(ScoreInfo)]),
     "pmx_place_tied": (_i32, [_vp, _i32, _vp, _i64]),

@@ -818,6 +818,14 @@ DP_PROBE_PATHS = {"SERVE": 0, "SERVE_ONE_CLASS": 1, "WAVE_LONG": 2, "WAVE_GENERA
 # path_taken (PMX_DP_PATH_* of include/panmap_amd.h)
 DP_PATH_REG, DP_PATH_ROWS, DP_PATH_DIAG, DP_PATH_KIND = 0x100, 0x200, 0x300, 0x300
 DP_PATH_EXACT, DP_PATH_FAST, DP_PATH_TB_LDS, DP_PATH_ALL_LDS = 0x20, 0x40, 0x80, 0x1000
+CHAIN_PROBE_PATHS = {"WAVE_LONG": 0, "WAVE_GENERAL": 1, "LANE": 2}
+CHAIN_PROBE_OPS = {"SORT128": 0, "SORT64": 1, "CHAIN_DP": 2, "CHAIN_RMQ": 3}
+CHAIN_PROBE_DEFAULT = -(1 << 31)
+CHAIN_PROBE_PARAMS_DTYPE = np.dtype([(k, "<f4" if k.startswith("chn_pen") else "<i4") for k in
+                                     ("bw", "bw_long", "max_gap", "max_chain_skip", "max_chain_iter", "min_cnt", "min_chain_score", "chn_pen_gap", "chn_pen_skip",
+                                      "rmq_inner_dist", "rmq_size_cap", "max_dist_x", "max_dist_y", "n_seg")])
+CHAIN_PROBE_RESULT_DTYPE = np.dtype([("served", "<i4"), ("status", "<u4"), ("n_a", "<i8"), ("n_u", "<i4"), ("reserved", "<i4")])
+CHAIN_PROBE_CAPS_DTYPE = np.dtype([("max_anchor", "<i4"), ("max_reg", "<i4"), ("max_qlen", "<i4"), ("reserved", "<i4")])
 REC_DTYPE = np.dtype([("rs", "<i4"), ("re", "<i4"), ("qs", "<i4"), ("qe", "<i4"), ("mapq", "u1"), ("rev", "u1"),
                       ("proper_frag", "u1"), ("mapped", "u1"), ("n_cigar", "<u2"), ("flags", "<u2"), ("cigar_off", "<u4"),
                       ("score", "<i4")])
@@ -935,6 +943,25 @@ class Aligner:
             check(lib.pmx_align_dp_probe(*args, seqs.ctypes.data, qs.ctypes.data, ts.ctypes.data, n, w_.ctypes.data, z_.ctypes.data, e_.ctypes.data,
                                          f_.ctypes.data, out.ctypes.data, arena.ctypes.data, len(arena), caps.ctypes.data), "pmx_align_dp_probe")
         return out, arena, caps
+
+    def chain_probe(self, path, op, anchors, offsets, qlen, params, max_read_len: int, n_segs: int = 1):
+        """TEST ACCESSOR: one operation of the anchor sort / chaining code on a batch of anchor lists (pmx_align_chain_probe); path: a key
+        of CHAIN_PROBE_PATHS, op: of CHAIN_PROBE_OPS.  anchors: uint64 [total][2] (x, y), offsets: int64 [n + 1], qlen: int32 [n][2] or
+        None, params: one record of CHAIN_PROBE_PARAMS_DTYPE (CHAIN_PROBE_DEFAULT / NaN = the preset's value; the values in force are
+        written back).  -> (CHAIN_PROBE_RESULT_DTYPE [n], anchors out [total][2], u out [total], capacities: a CHAIN_PROBE_CAPS_DTYPE record)"""
+        anchors = np.ascontiguousarray(anchors, np.uint64).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n = len(offsets) - 1
+        assert params.dtype == CHAIN_PROBE_PARAMS_DTYPE and params.shape == (1,) and int(offsets[-1]) <= len(anchors)
+        ql = None if qlen is None else np.ascontiguousarray(qlen, np.int32).reshape(n, 2)
+        caps = np.zeros(1, CHAIN_PROBE_CAPS_DTYPE)
+        out = np.zeros(max(n, 1), CHAIN_PROBE_RESULT_DTYPE)
+        oa = np.zeros((max(len(anchors), 1), 2), np.uint64)
+        ou = np.zeros(max(len(anchors), 1), np.uint64)
+        check(lib.pmx_align_chain_probe(self.ctx._h, self._h, CHAIN_PROBE_PATHS[path], CHAIN_PROBE_OPS[op], int(max_read_len), int(n_segs), params.ctypes.data,
+                                        anchors.ctypes.data if n else None, offsets.ctypes.data if n else None, None if ql is None or not n else ql.ctypes.data, n,
+                                        out.ctypes.data, oa.ctypes.data, ou.ctypes.data, caps.ctypes.data), "pmx_align_chain_probe")
+        return out[:n], oa, ou, caps[0]
 
     def stats(self) -> dict:
         """work statistics of the last align_readset call (DP cells = q * min(t, 2w+1) per ksw2 call)"""

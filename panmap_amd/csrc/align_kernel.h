@@ -1,6 +1,7 @@
 // Launch interface of the ALIGN kernel (align_kernel.hip), shared with align_stage.hip.
 #pragma once
 #include "align/aln_host.hpp"
+#include "align/aln_chain_probe.hpp"
 
 #define PMX_ALIGN_WORK_BYTES 1280   // LDS bytes reserved for the Work descriptor
 
@@ -107,6 +108,26 @@ struct DpProbeArgs {
     size_t slow_stride;
 };
 
+// pmx_align_chain_probe (k_align_chain_probe in align_kernel.hip: one list per wave on a wave-per-read layout;
+// k_align_chain_probe_lane in align_kernel_tpp.hip: one list per lane on the thread-per-pair arena)
+struct ChainProbeArgs {
+    TppArena tpp;               // MUST stay first (IPtr::phys reads it from the kernarg segment); zero for the wave kernel
+    const A128* anchors;        // list i: anchors[a_off[i] .. a_off[i+1])
+    const int64_t* a_off;
+    const int32_t* qlen;        // two per list
+    int64_t n;
+    ChainProbeOut* out;         // zeroed by the host: a list beyond caps.max_anchor is left alone
+    A128* out_anchors;          // list i from a_off[i] on
+    uint64_t* out_u;
+    int op, n_segs, max_dist_x, max_dist_y, n_seg;
+    Opt opt;
+    Layout layout;
+    uint8_t* slow_base;         // wave kernel: the waves' slabs; lane kernel: the waves' strided Reg regions
+    size_t slow_stride;
+};
+
+__global__ void k_align_chain_probe(ChainProbeArgs A);
+__global__ void k_align_chain_probe_lane(ChainProbeArgs A);
 __global__ void k_align_reads(AlignArgs A);
 __global__ void k_align_reads_w4(AlignArgs A);
 __global__ void k_align_reads_t1(AlignArgs A);

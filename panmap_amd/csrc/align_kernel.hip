@@ -70,5 +70,59 @@ __global__ void __launch_bounds__(64, 2) k_align_dp_probe(DpProbeArgs A) {
     }
 }
 
+// pmx_align_chain_probe: one anchor list per wave on a layout of the wave-per-read kernels -- the list copied to where map_frag
+// keeps its anchors (W.a; LDS or the wave's slab, by the layout), then one operation of the sort / chaining code exactly as
+// map_frag calls it (aln_chain_probe.hpp).  A list beyond the layout's anchor capacity is left unserved before anything is copied.
+__global__ void __launch_bounds__(64, 2) k_align_chain_probe(ChainProbeArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    Work& W = *reinterpret_cast<Work*>(lds);
+    uint8_t* fast = lds + PMX_ALIGN_WORK_BYTES;
+    uint8_t* slow = A.slow_base + (size_t)blockIdx.x * A.slow_stride;
+    const int lane = (int)(threadIdx.x & 63u);
+    for (int64_t it = blockIdx.x; it < A.n; it += gridDim.x) {
+        __syncthreads();
+        bind_work(W, A.layout, fast, slow);
+        W.n_segs = A.n_segs;
+        W.prof = nullptr;
+        W.no_rows_dp = 0;
+        W.mv_ready = 0;
+        W.dp_path = 0;
+        const int64_t a0 = A.a_off[it], na = A.a_off[it + 1] - a0;
+        W.qlen[0] = A.qlen ? A.qlen[2 * it] : 0;
+        W.qlen[1] = A.qlen ? A.qlen[2 * it + 1] : 0;
+        W.n_a = na;
+        W.n_u = 0;
+        __syncthreads();
+        if (na < 0 || na > A.layout.caps.max_anchor) continue;
+        A128* a = W.a;
+        if (A.op == PMX_CP_SORT64) {
+            uint64_t* v = reinterpret_cast<uint64_t*>(a);
+            for (int64_t i = lane; i < na; i += 64) v[i] = A.anchors[a0 + i].x;
+        } else {
+            for (int64_t i = lane; i < na; i += 64) a[i] = A.anchors[a0 + i];
+        }
+        __syncthreads();
+        chain_probe_run(W, A.opt, A.op, A.max_dist_x, A.max_dist_y, A.n_seg);
+        __syncthreads();
+        ChainProbeOut o;
+        o.served = 1;
+        o.status = W.status;
+        o.n_a = W.n_a;
+        o.n_u = W.n_u;
+        o.pad = 0;
+        // (what the operation may leave: at most the anchors it was given, at most one chain per anchor)
+        const int64_t n_out = o.n_a < 0 ? 0 : (o.n_a > na ? na : o.n_a), u_out = o.n_u < 0 ? 0 : ((int64_t)o.n_u > na ? na : (int64_t)o.n_u);
+        if (A.op == PMX_CP_SORT64) {
+            const uint64_t* v = reinterpret_cast<const uint64_t*>(a);
+            for (int64_t i = lane; i < n_out; i += 64) { A128 e; e.x = v[i]; e.y = 0; A.out_anchors[a0 + i] = e; }
+        } else {
+            for (int64_t i = lane; i < n_out; i += 64) A.out_anchors[a0 + i] = a[i];
+        }
+        const uint64_t* u = W.u;
+        for (int64_t i = lane; i < u_out; i += 64) A.out_u[a0 + i] = u[i];
+        if (lane == 0) A.out[it] = o;
+    }
+}
+
 }  // namespace aln
 }  // namespace pmx

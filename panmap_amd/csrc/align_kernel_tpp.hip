@@ -233,5 +233,49 @@ k_align_reads_tpp(AlignArgs A) {
     }
 }
 
+// pmx_align_chain_probe, LANE path: one anchor list per lane, the arena bound as k_align_reads_tpp binds it -- the 64 lanes of a
+// wave run 64 different lists through the scalar forms of the sort / chaining code (PMX_W = 1 in this unit), diverging wherever the
+// lists differ.  Nothing in those forms is a wave-wide operation, so a lane without a list simply sits out.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PMX_TPP_OCC)))
+k_align_chain_probe_lane(ChainProbeArgs A) {   // (the register budget of k_align_reads_tpp: the two share the pipeline's out-of-line functions)
+    static_assert(offsetof(ChainProbeArgs, tpp) == 0, "IPtr::phys reads the arena from the start of the kernarg segment");
+    const int lane = (int)(threadIdx.x & 63u);
+    uint8_t* raw = A.slow_base + (size_t)blockIdx.x * A.slow_stride + ((threadIdx.x & 63u) << 2);
+    for (int64_t it0 = (int64_t)blockIdx.x * 64; it0 < A.n; it0 += (int64_t)gridDim.x * 64) {
+        const int64_t it = it0 + lane;
+        if (it >= A.n) continue;
+        const int64_t a0 = A.a_off[it], na = A.a_off[it + 1] - a0;
+        if (na < 0 || na > A.layout.caps.max_anchor) continue;
+        Work W;
+        bind_work(W, A.layout, nullptr, nullptr, raw);
+        W.n_segs = A.n_segs;
+        W.prof = nullptr;
+        W.no_rows_dp = 0;
+        W.mv_ready = 0;
+        W.dp_path = 0;
+        W.qlen[0] = A.qlen ? A.qlen[2 * it] : 0;
+        W.qlen[1] = A.qlen ? A.qlen[2 * it + 1] : 0;
+        W.n_a = na;
+        W.n_u = 0;
+        Ptr<A128> a = W.a;
+        Ptr<uint64_t> v = ptr_cast<uint64_t>(a);
+        if (A.op == PMX_CP_SORT64) for (int64_t i = 0; i < na; ++i) v[i] = A.anchors[a0 + i].x;
+        else for (int64_t i = 0; i < na; ++i) a[i] = A.anchors[a0 + i];
+        chain_probe_run(W, A.opt, A.op, A.max_dist_x, A.max_dist_y, A.n_seg);
+        ChainProbeOut o;
+        o.served = 1;
+        o.status = W.status;
+        o.n_a = W.n_a;
+        o.n_u = W.n_u;
+        o.pad = 0;
+        const int64_t n_out = o.n_a < 0 ? 0 : (o.n_a > na ? na : o.n_a), u_out = o.n_u < 0 ? 0 : ((int64_t)o.n_u > na ? na : (int64_t)o.n_u);
+        if (A.op == PMX_CP_SORT64) for (int64_t i = 0; i < n_out; ++i) { A128 e; e.x = v[i]; e.y = 0; A.out_anchors[a0 + i] = e; }
+        else for (int64_t i = 0; i < n_out; ++i) A.out_anchors[a0 + i] = a[i];
+        Ptr<uint64_t> u = W.u;
+        for (int64_t i = 0; i < u_out; ++i) A.out_u[a0 + i] = u[i];
+        A.out[it] = o;
+    }
+}
+
 }  // namespace aln
 }  // namespace pmx

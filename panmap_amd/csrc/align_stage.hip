@@ -894,4 +894,91 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
     }
     return PMX_OK;
 }
+
+// pmx_align_chain_probe (include/panmap_amd.h): one operation of the sort / chaining code on the caller's anchor lists
+static_assert(sizeof(pmx_chain_probe_params) == sizeof(ChainProbeParams) && sizeof(pmx_chain_probe_result) == sizeof(ChainProbeOut) &&
+                  offsetof(pmx_chain_probe_params, n_seg) == offsetof(ChainProbeParams, n_seg) && sizeof(A128) == 16 &&
+                  PMX_CHAIN_PROBE_SORT128 == PMX_CP_SORT128 && PMX_CHAIN_PROBE_SORT64 == PMX_CP_SORT64 && PMX_CHAIN_PROBE_CHAIN_DP == PMX_CP_CHAIN_DP &&
+                  PMX_CHAIN_PROBE_CHAIN_RMQ == PMX_CP_CHAIN_RMQ && PMX_CHAIN_PROBE_DEFAULT == PMX_CP_DEFAULT,
+              "the chain probe's records of the public header");
+int align_chain_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int op, int max_read_len, int n_segs, pmx_chain_probe_params* par, const uint64_t* anchors,
+                      const int64_t* a_off, const int32_t* qlen, int64_t n, pmx_chain_probe_result* out, uint64_t* out_anchors, uint64_t* out_u,
+                      pmx_chain_probe_caps* caps) {
+    const hipStream_t stream = ctx->stream;
+    ChainProbeParams P;
+    memcpy(&P, par, sizeof(P));
+    const Opt o = chain_probe_resolve(P, al->opt);
+    memcpy(par, &P, sizeof(P));
+    const bool lane = path == PMX_CHAIN_PROBE_LANE;
+    const AlignSwitches sw;
+    const Layout L = lane ? plan_layout_tpp(max_read_len, n_segs, o, sw.tpp_tb)
+                          : path == PMX_CHAIN_PROBE_WAVE_GENERAL ? plan_general_layout(max_read_len, n_segs, o) : plan_long_reads_layout(max_read_len, n_segs, o, false);
+    memset(caps, 0, sizeof(*caps));
+    caps->max_anchor = L.caps.max_anchor; caps->max_reg = L.caps.max_reg; caps->max_qlen = L.caps.max_qlen;
+    if (n == 0) return PMX_OK;
+    for (int64_t i = 0; i < n; ++i) {
+        memset(&out[i], 0, sizeof(out[i]));
+        if (a_off[i + 1] < a_off[i] || a_off[i] < 0) return fail(PMX_ERR_ARG, "pmx_align_chain_probe: descending offsets");
+    }
+    const int64_t total = a_off[n];
+    ChainProbeArgs A{};
+    DevBuf<A128> d_in, d_out_a;
+    DevBuf<int64_t> d_off;
+    DevBuf<int32_t> d_qlen;
+    DevBuf<ChainProbeOut> d_out;
+    DevBuf<uint64_t> d_u;
+    DevBuf<uint8_t> slab, arena;
+    d_in.alloc((size_t)std::max<int64_t>(total, 1));
+    d_out_a.alloc((size_t)std::max<int64_t>(total, 1));
+    d_u.alloc((size_t)std::max<int64_t>(total, 1));
+    d_off.alloc((size_t)(n + 1));
+    d_out.alloc((size_t)n);
+    if (total > 0) PMX_H2D(pmx::as<uint64_t>(d_in), anchors, 2 * total, stream);
+    PMX_H2D(d_off, a_off, n + 1, stream);
+    if (qlen) {
+        d_qlen.alloc((size_t)(2 * n));
+        PMX_H2D(d_qlen, qlen, 2 * n, stream);
+    }
+    PMX_ZERO(d_out, n, stream);
+    PMX_ZERO(d_out_a, std::max<int64_t>(total, 1), stream);
+    PMX_ZERO(d_u, std::max<int64_t>(total, 1), stream);
+    A.anchors = d_in.p; A.a_off = d_off.p; A.qlen = qlen ? d_qlen.p : nullptr;
+    A.n = n;
+    A.out = d_out.p; A.out_anchors = d_out_a.p; A.out_u = d_u.p;
+    A.op = op; A.n_segs = n_segs; A.max_dist_x = P.max_dist_x; A.max_dist_y = P.max_dist_y; A.n_seg = P.n_seg;
+    A.opt = o;
+    A.layout = L;
+    if (lane) {
+        const int64_t grid = std::min<int64_t>((n + 63) / 64, 256);
+        const size_t wave_stride = tpp_arena_bytes(L) * 64;
+        if (wave_stride > UINT32_MAX) return fail(PMX_ERR_CAPACITY, "pmx_align_chain_probe: thread-per-pair arena stride exceeds 32 bits");
+        A.slow_stride = (L.raw_bytes + 255) & ~(size_t)255;
+        arena.alloc(wave_stride * (size_t)grid);
+        slab.alloc(A.slow_stride * (size_t)grid);
+        A.tpp.base = arena.p;
+        A.tpp.wave_stride = (uint32_t)wave_stride;
+        A.slow_base = slab.p;
+        PMX_LAUNCH(k_align_chain_probe_lane, dim3((unsigned)grid), dim3(64), 0, stream, A);
+    } else {
+        const size_t lds_bytes = PMX_ALIGN_WORK_BYTES + L.fast_bytes + 16;
+        if (lds_bytes > 160 * 1024) return fail(PMX_ERR_CAPACITY, "pmx_align_chain_probe: reads too long for the LDS work arena");
+        if (lds_bytes > 64 * 1024) PMX_HIP(hipFuncSetAttribute((const void*)k_align_chain_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        const int64_t grid = std::min<int64_t>(n, 128);   // (as the DP probe: a long-read slab is ~8 MB per wave)
+        A.slow_stride = (L.slow_bytes + 255) & ~(size_t)255;
+        slab.alloc(A.slow_stride * (size_t)grid);
+        A.slow_base = slab.p;
+        PMX_LAUNCH(k_align_chain_probe, dim3((unsigned)grid), dim3(64), lds_bytes, stream, A);
+    }
+    std::vector<ChainProbeOut> res((size_t)n);
+    PMX_D2H(res, d_out, n, stream);
+    if (total > 0) {
+        PMX_D2H(out_anchors, pmx::as<uint64_t>(d_out_a), 2 * total, stream);
+        PMX_D2H(out_u, d_u, total, stream);
+    }
+    PMX_HIP(hipStreamSynchronize(stream));
+    for (int64_t i = 0; i < n; ++i) {
+        out[i].served = res[(size_t)i].served; out[i].status = res[(size_t)i].status; out[i].n_a = res[(size_t)i].n_a; out[i].n_u = res[(size_t)i].n_u;
+    }
+    return PMX_OK;
+}
 }  // namespace pmx

@@ -98,6 +98,11 @@ int align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len, in
                    const int64_t* q_off, const int64_t* t_off, int64_t n, const int32_t* w, const int32_t* zdrop, const int32_t* end_bonus,
                    const int32_t* flag, pmx_dp_probe_result* out, uint32_t* cigar_arena, int64_t arena_cap, pmx_dp_probe_caps* caps);
 
+// align_stage.hip: pmx_align_chain_probe behind its argument checks (include/panmap_amd.h)
+int align_chain_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int op, int max_read_len, int n_segs, pmx_chain_probe_params* par, const uint64_t* anchors,
+                      const int64_t* a_off, const int32_t* qlen, int64_t n, pmx_chain_probe_result* out, uint64_t* out_anchors, uint64_t* out_u,
+                      pmx_chain_probe_caps* caps);
+
 // align_pairs.hip (readset_pair_order / readset_pair_map: readset.hpp)
 // the representatives of the distinct-pair map in launch order (`order`, nullptr = input order) -> al->dd_list; their number
 int64_t pair_select_reps(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, const uint32_t* order, int64_t n_pairs);

@@ -434,6 +434,19 @@ int pmx_align_dp_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int max_read_len
     PMX_CATCH
 }
 
+int pmx_align_chain_probe(pmx_ctx* ctx, pmx_aligner* al, int path, int op, int max_read_len, int n_segs, pmx_chain_probe_params* par, const uint64_t* anchors,
+                          const int64_t* a_off, const int32_t* qlen, int64_t n, pmx_chain_probe_result* out, uint64_t* out_anchors, uint64_t* out_u,
+                          pmx_chain_probe_caps* caps) {
+    if (!ctx || !al || !par || !caps || n < 0 || path < PMX_CHAIN_PROBE_WAVE_LONG || path > PMX_CHAIN_PROBE_LANE || op < PMX_CHAIN_PROBE_SORT128 ||
+        op > PMX_CHAIN_PROBE_CHAIN_RMQ || max_read_len < 1 || max_read_len > (1 << 20) || n_segs < 1 || n_segs > 2)
+        return PMX_ERR_ARG;
+    if (n > 0 && (!anchors || !a_off || !out || !out_anchors || !out_u)) return PMX_ERR_ARG;
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    return align_chain_probe(ctx, al, path, op, max_read_len, n_segs, par, anchors, a_off, qlen, n, out, out_anchors, out_u, caps);
+    PMX_CATCH
+}
+
 // The download of pmx_align_fetch on a stream of the caller's choice, without waiting for it: the copies start when the
 // results are complete (event on the context's stream) and the next pmx_align_readset on this aligner waits for them
 // before it overwrites the buffers.  The caller synchronises `stream` before it reads the host buffers (pinned memory, or

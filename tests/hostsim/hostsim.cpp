@@ -15,6 +15,7 @@ static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long 
 static long long pmx_us_cnt[8];
 #define PMX_UNSUPPORTED_AT(site) (++pmx_us_cnt[site])
 #include "align/aln_host.hpp"
+#include "align/aln_chain_probe.hpp"
 extern "C" void hs_unsupported_counts(long long* out, int reset) { for (int i = 0; i < PMX_US_SITES; ++i) { out[i] = pmx_us_cnt[i]; if (reset) pmx_us_cnt[i] = 0; } }
 #ifndef PMX_HOSTSIM_TPP
 // work counters of the compact tier (0: anchors, 1: anchor pairs the chain fill evaluated, 2: run skips, 3: pairs whose seeds the two-way merge ordered)
@@ -370,6 +371,57 @@ extern "C" int hs_shortcut_fuzz(uint64_t seed, int64_t n_cases, int64_t* counts 
     return 0;
 }
 #endif
+
+// pmx_align_chain_probe on the host (PMX_W = 1): one operation of the sort / chaining code per anchor list, exactly as map_frag calls
+// it (align/aln_chain_probe.hpp).  This build: the layout of the wave tiers (its capacities; the scalar packed fill, the scalar
+// backtrack, the insertion sort); the PMX_HOSTSIM_TPP build: the capacities of the thread-per-pair layout.  mean_read_len picks
+// the preset the defaults come from.  anchors: (x, y) pairs, list i at [a_off[i], a_off[i + 1]); qlen: two per list (NULL: 0).
+// out_anchors / out_u: list i's results from a_off[i] on.  caps: max_anchor, max_reg, max_qlen, 0 (also when n == 0).
+extern "C" int hs_chain_probe(int mean_read_len, int op, int max_read_len, int n_segs, ChainProbeParams* par, const uint64_t* anchors, const int64_t* a_off,
+                              const int32_t* qlen, int64_t n, ChainProbeOut* out, uint64_t* out_anchors, uint64_t* out_u, int32_t* caps) {
+    if (!par || !caps || op < PMX_CP_SORT128 || op > PMX_CP_CHAIN_RMQ || n_segs < 1 || n_segs > 2 || max_read_len < 1) return -1;
+    Opt preset = make_opt(mean_read_len);
+    HostRefIndex none;
+    finish_ref_opt(preset, 0, none);   // the chain penalties of the preset
+    const Opt o = chain_probe_resolve(*par, preset);
+#ifdef PMX_HOSTSIM_TPP
+    const Layout L = plan_layout_compact(max_read_len, n_segs, o);
+#else
+    const Layout L = plan_layout(max_read_len, n_segs, o, (size_t)1 << 30);
+#endif
+    caps[0] = L.caps.max_anchor; caps[1] = L.caps.max_reg; caps[2] = L.caps.max_qlen; caps[3] = 0;
+    if (n == 0) return 0;
+    if (!anchors || !a_off || !out || !out_anchors || !out_u) return -1;
+    std::vector<uint8_t> fast(L.fast_bytes + 64), slow(L.slow_bytes + 64);
+    Work W;
+    memset(&W, 0, sizeof(W));
+    for (int64_t it = 0; it < n; ++it) {
+        ChainProbeOut& r = out[it];
+        memset(&r, 0, sizeof(r));
+        const int64_t na = a_off[it + 1] - a_off[it];
+        if (na < 0) return -1;
+        if (na > L.caps.max_anchor) continue;
+        memset(fast.data(), 0xa5, fast.size());   // results must not depend on what the arrays held
+        memset(slow.data(), 0xa5, slow.size());
+        bind_work(W, L, fast.data(), slow.data());
+        W.n_segs = n_segs;
+        W.qlen[0] = qlen ? qlen[2 * it] : 0;
+        W.qlen[1] = qlen ? qlen[2 * it + 1] : 0;
+        W.n_a = na;
+        if (op == PMX_CP_SORT64) for (int64_t i = 0; i < na; ++i) reinterpret_cast<uint64_t*>(W.a)[i] = anchors[2 * (a_off[it] + i)];
+        else for (int64_t i = 0; i < na; ++i) { W.a[i].x = anchors[2 * (a_off[it] + i)]; W.a[i].y = anchors[2 * (a_off[it] + i) + 1]; }
+        chain_probe_run(W, o, op, par->max_dist_x, par->max_dist_y, par->n_seg);
+        r.served = 1;
+        r.status = W.status;
+        r.n_a = W.n_a;
+        r.n_u = W.n_u;
+        uint64_t* oa = out_anchors + 2 * a_off[it];
+        if (op == PMX_CP_SORT64) for (int64_t i = 0; i < W.n_a; ++i) { oa[2 * i] = reinterpret_cast<uint64_t*>(W.a)[i]; oa[2 * i + 1] = 0; }
+        else for (int64_t i = 0; i < W.n_a; ++i) { oa[2 * i] = W.a[i].x; oa[2 * i + 1] = W.a[i].y; }
+        for (int i = 0; i < W.n_u; ++i) out_u[a_off[it] + i] = W.u[i];
+    }
+    return 0;
+}
 
 // The reference sketch: slice == 0 -> the sequential sketch_segment_t (what build_ref_index runs); slice > 0 -> the
 // concatenation of sketch_slice over consecutive slices of that many bases (what the device index build runs).
