@@ -89,6 +89,9 @@ int pmx_index_build_ex(const pmx_panman *pm, int k, int s, int t, int l, int ope
 int pmx_index_from_arrays(const pmx_index_info *info, const uint32_t *parent, const uint64_t *offsets,
                           const uint64_t *hash, const int16_t *parent_count, const int16_t *child_count,
                           pmx_index **out);
+/* the node ids of an index adopted from arrays (copied; ids[v] for DFS index v, n = the index's nodes, else PMX_ERR_ARG):
+ * what pmx_index_node_id returns from then on, and what --em-leaves-only reads */
+int pmx_index_set_node_ids(pmx_index *idx, const char *const *ids, int64_t n);
 /* The `.idx` container the reference's place stage loads and its index stage writes (32-byte PMI1 header + Cap'n Proto
  * LiteIndex message, raw or as concatenated zstd frames; src/index_single_mode.cpp:1561-1640, src/placement.cpp:1009-1092,
  * src/index_lite.capnp:36-70).  Load rejects a stale format version / missing struct-of-arrays fields / short offsets with
@@ -626,6 +629,24 @@ int pmx_meta_em_info(const pmx_meta *m, int32_t *rounds, int32_t *iterations, do
  * greater than T (src/mgsr.cpp:1593-1594, 1833-1834).  pmx_read_dust = mgsr::getDust (src/mgsr.cpp:1505-1568; host, no
  * device): Prinseq-scaled score over base triplets in a sliding window of `window` triplets (the reference uses 64). */
 int pmx_meta_set_dust(pmx_meta *m, double threshold);
+/* --mask-read-ends N (src/main.cpp:2065; extractReadSequences, src/mgsr.cpp:1274-1280, 1304-1310), 0 = off, kept for the
+ * pmx_meta_set_reads calls that follow: a read of length L becomes read[N : L - N] when L > 2N and the empty read otherwise,
+ * before anything else looks at it.  The DUST score is the trimmed read's (an empty one scores 0 and stays), the seedmer
+ * lists and the overlap coefficients are seeded from the trimmed read (the seeding kernels' per-end trim: no copy of the
+ * reads), and a read trimmed to nothing counts wherever a read without seedmers counts: in the kept reads behind the overlap
+ * coefficients, in its amplicon group's N, -1 in pmx_meta_raw_to_merged.  When every read ends empty there are no merged
+ * reads, every overlap coefficient is 0 and pmx_meta_em leaves no haplotype.  n < 0 or n > INT32_MAX: PMX_ERR_ARG.
+ * --gpus N: the same value on every rank, each trims its shard.  pmx_meta_assign on reads set with N > 0 is
+ * PMX_ERR_UNSUPPORTED: the reference's reader for --filter-and-assign takes the value and ignores it (src/mgsr.cpp:1575). */
+int pmx_meta_set_mask_read_ends(pmx_meta *m, int64_t n);
+/* --em-leaves-only (src/main.cpp:2053; squareEM::squareEM, src/mgsr.cpp:8018-8037), for the pmx_meta_score calls that follow
+ * without a candidate override (an override stays "exactly these nodes").  A node is a SAMPLE when its id in the plain index
+ * does not begin with `node_`, and ELIGIBLE when it, or a node that pmx_index_node_heads folds onto the same head, is a
+ * sample.  The candidates are then chosen by walking the nodes by falling overlap coefficient (ascending DFS index within a
+ * value), passing over the nodes that are not eligible BEFORE a rank is counted, up to top_oc distinct values among the
+ * eligible ones.  Every node is ranked by its own coefficient, as without the switch, and equal score columns are merged
+ * after scoring.  No eligible node: PMX_ERR_ARG. */
+int pmx_meta_set_em_leaves_only(pmx_meta *m, int on);
 /* --mask-reads N / --mask-seeds N (src/main.cpp:2026-2030; initializeQueryData, src/mgsr.cpp:2049-2139), both 0 = off, for the
  * pmx_meta_set_reads calls that follow.  On the merged reads, count[h] = the sum of the multiplicities of the merged reads whose
  * list holds hash h (once per read, either orientation).  mask_reads T > 0: a merged read with an entry of count <= T is

@@ -114,6 +114,7 @@ SIGNATURES = {
     "pmx_index_build": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _PP]),
     "pmx_index_build_ex": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _PP]),
     "pmx_index_from_arrays": (_i32, [C.POINTER(IndexInfo), _vp, _vp, _vp, _vp, _vp, _PP]),
+    "pmx_index_set_node_ids": (_i32, [_vp, _vp, _i64]),
     "pmx_index_close": (None, [_vp]),
     "pmx_index_get_info": (_i32, [_vp, C.POINTER(IndexInfo)]),
     "pmx_index_parents": (_vp, [_vp]),
@@ -213,6 +214,8 @@ SIGNATURES = {
     "pmx_meta_haplotype": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64]),
     "pmx_meta_em_info": (_i32, [_vp, _vp, _vp, _vp]),
     "pmx_meta_set_dust": (_i32, [_vp, C.c_double]),
+    "pmx_meta_set_mask_read_ends": (_i32, [_vp, _i64]),
+    "pmx_meta_set_em_leaves_only": (_i32, [_vp, _i32]),
     "pmx_meta_set_masks": (_i32, [_vp, _i64, _i64]),
     "pmx_meta_mask_info": (_i32, [_vp, _vp, _vp, _vp]),
     "pmx_meta_mask_num_counts": (_i64, [_vp]),

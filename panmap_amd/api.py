@@ -96,8 +96,10 @@ class Index:
         return cls(h)
 
     @classmethod
-    def from_arrays(cls, k, s, t, l, open_syncmer, parent, offsets, hashes, parent_counts, child_counts, flank_mask=0, hpc=False, oriented=False):
-        """oriented: the arrays are an oriented (--meta) index, keys as Index.build(mode=ORIENTED) makes them"""
+    def from_arrays(cls, k, s, t, l, open_syncmer, parent, offsets, hashes, parent_counts, child_counts, flank_mask=0, hpc=False, oriented=False,
+                    node_ids=None):
+        """oriented: the arrays are an oriented (--meta) index, keys as Index.build(mode=ORIENTED) makes them; node_ids: the id
+        of every node by DFS index (without them every node_id is "")"""
         parent = np.ascontiguousarray(parent, np.uint32)
         offsets = np.ascontiguousarray(offsets, np.uint64)
         hashes = np.ascontiguousarray(hashes, np.uint64)
@@ -107,7 +109,11 @@ class Index:
         h = C.c_void_p()
         check(lib.pmx_index_from_arrays(C.byref(info), parent.ctypes.data, offsets.ctypes.data, hashes.ctypes.data,
                                         pc.ctypes.data, cc.ctypes.data, C.byref(h)), "pmx_index_from_arrays")
-        return cls(h)
+        out = cls(h)
+        if node_ids is not None:
+            ids = (C.c_char_p * len(node_ids))(*[x.encode() if isinstance(x, str) else bytes(x) for x in node_ids])
+            check(lib.pmx_index_set_node_ids(h, ids, len(node_ids)), "pmx_index_set_node_ids")
+        return out
 
     @classmethod
     def load(cls, path: str) -> "Index":

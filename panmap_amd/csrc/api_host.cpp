@@ -169,6 +169,14 @@ int pmx_index_from_arrays(const pmx_index_info* info, const uint32_t* parent, co
     return PMX_OK;
 }
 
+int pmx_index_set_node_ids(pmx_index* idx, const char* const* ids, int64_t n) {
+    if (!idx || !ids || n != (int64_t)idx->ix.n_nodes()) return PMX_ERR_ARG;
+    for (int64_t v = 0; v < n; ++v)
+        if (!ids[v]) return PMX_ERR_ARG;
+    for (int64_t v = 0; v < n; ++v) idx->ix.node_id[(size_t)v] = ids[v];
+    return PMX_OK;
+}
+
 // ---- .idx container (host/idx_file.cpp)
 int pmx_index_save(const pmx_index* idx, const char* path, int zstd_level, int uncompressed) {
     if (!idx || !path) return PMX_ERR_ARG;

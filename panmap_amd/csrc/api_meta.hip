@@ -28,6 +28,8 @@
 //     chunk order).  HBM-bound: 2 B per (read, candidate) per pass, six passes per SQUAREM iteration.
 // --filter-and-assign (every read against EVERY node, no score matrix) is meta_assign.hip, on the state of meta_state.hpp;
 // --mask-reads / --mask-seeds (merged reads or list entries with low-coverage k-min-mers leave the sample) is meta_mask.hip.
+// --mask-read-ends is the seeding kernels' per-end trim (seedmer_lists, overlap_place_params; DUST scores the same slice);
+// --em-leaves-only is a filter in select_candidates.
 // Read-side seedmer extraction is host C++ here (threads; the k-min-mer definitions of host/seed_host.hpp); moving it into
 // the seeding kernel is the next step.  parity: the reference's own MGSR index and EM cannot be built here (panman / TBB /
 // Eigen / abseil are absent): scores and EM are checked by the test suite against a direct restatement (per-node seed
@@ -43,6 +45,7 @@
 #include <map>
 #include <memory>
 #include <numeric>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -466,11 +469,12 @@ void score_rows(pmx_ctx* ctx, pmx_meta* m, int64_t first, int64_t count, uint16_
 // a read set made inside a step: released when the step ends, on every way out of it (the step's caller has set the device)
 using ReadSetGuard = std::unique_ptr<pmx_readset>;
 
-// the place stage's parameters for the overlap coefficients: every read seed kept
-pmx_place_params overlap_place_params() {
+// the place stage's parameters for the overlap coefficients: every read seed kept, of the reads without their masked ends
+pmx_place_params overlap_place_params(const pmx_meta* m) {
     pmx_place_params pp;
     memset(&pp, 0, sizeof(pp));
     pp.min_read_support = 1;
+    pp.trim_start = pp.trim_end = meta_read_end_trim(m);
     return pp;
 }
 
@@ -541,12 +545,14 @@ int MetaReads::check_settings() const {
     return PMX_OK;
 }
 
-// --dust.  Reads: the caller's reads, m->dust_threshold.  Leaves: concat / offsets / n_reads describe the kept reads only
+// --dust.  Reads: the caller's reads, m->dust_threshold, m->mask_read_ends.  Leaves: concat / offsets / n_reads describe the kept reads only
 // (re-concatenated when any was dropped), n_dusty, n_kept_all.  Nothing below knows about DUST.
 void MetaReads::drop_dusty() {
     const double dust_thr = m->dust_threshold;
     if (!(dust_thr < 100.0)) return;
     // src/mgsr.cpp:1593-1594: a read with a non-zero score above the threshold is left out
+    // --mask-read-ends: the score is the trimmed read's, a slice of the caller's bytes; a read trimmed to nothing scores 0 and stays
+    const int64_t ends = m->mask_read_ends;
     std::vector<uint8_t> dusty((size_t)n_reads, 0);
     unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     if (n_reads < 4096) n_thr = 1;
@@ -554,7 +560,8 @@ void MetaReads::drop_dusty() {
     for (unsigned t = 0; t < n_thr; ++t)
         pool.emplace_back([&, t]() {
             for (int64_t r = (int64_t)t; r < n_reads; r += n_thr) {
-                const double d = pmx_read_dust(concat + offsets[r], offsets[r + 1] - offsets[r], 64);
+                const int64_t len = offsets[r + 1] - offsets[r];
+                const double d = ends > 0 && len <= 2 * ends ? 0.0 : pmx_read_dust(concat + offsets[r] + ends, len - 2 * ends, 64);
                 if (d != 0 && d > dust_thr) dusty[(size_t)r] = 1;
             }
         });
@@ -583,7 +590,9 @@ int MetaReads::seedmer_lists() {
     const SyncmerParams& p = m->params;
     ListChunks lc;
     SeedParams& sp = lc.sp;
-    sp.k = p.k; sp.s = p.s; sp.t = p.t; sp.l = p.l; sp.open = p.open ? 1 : 0; sp.trim_start = 0; sp.trim_end = 0;
+    // --mask-read-ends: the kernel's per-end trim keeps the k-mers inside read[n : len - n] -- the trimmed string's -- and its
+    // k-min-mer windows run over those alone; the reads themselves are uploaded whole
+    sp.k = p.k; sp.s = p.s; sp.t = p.t; sp.l = p.l; sp.open = p.open ? 1 : 0; sp.trim_start = sp.trim_end = meta_read_end_trim(m);
     const int w = sp.k - sp.s + 1;
     const size_t lds = lc.lds = (size_t)(2 * w + p.l) * PMX_SEED_BLOCK * sizeof(uint64_t) + (size_t)(PMX_SEED_BLOCK / 64) * (PMX_SEED_QCAP * sizeof(uint64_t) + 8);
     if (lds > 160 * 1024) return fail(PMX_ERR_UNSUPPORTED, "k-s+1 too large for the LDS ring");
@@ -754,7 +763,7 @@ int MetaReads::overlap_coefficients() {
     int rc = pmx_readset_upload(ctx, concat, offsets, n_reads, &rs);
     if (rc != PMX_OK) return rc;
     ReadSetGuard rs_guard(rs);
-    const pmx_place_params pp = overlap_place_params();
+    const pmx_place_params pp = overlap_place_params(m);
     rc = pmx_readset_pack(ctx, rs);
     if (rc == PMX_OK) rc = pmx_place_reset(ctx, m->placer);
     if (rc == PMX_OK) rc = pmx_place_add_reads(ctx, m->placer, rs, &pp);
@@ -764,10 +773,29 @@ int MetaReads::overlap_coefficients() {
 
 // ---- pmx_meta_score's steps
 
+// --em-leaves-only (no HIP), one flag per node: the node is a sampled genome -- its id does not begin with `node_`
+// (src/mgsr.cpp:8023) -- or pmx_index_node_heads folds it onto the same head as one, which stands for the reference's "or one
+// of its identicalNodeIdentifiers" (:8024-8026).  The ids are the plain index's (what the abundance file prints); an index
+// adopted from arrays without ids names every node "", a sample.
+std::vector<uint8_t> sampled_or_folded_with_one(const pmx_meta* m) {
+    const size_t n = (size_t)m->n_nodes;
+    std::vector<uint32_t> head(n);
+    if (pmx_index_node_heads(m->idx_oriented, head.data()) != PMX_OK) throw std::runtime_error(pmx_last_error());
+    std::vector<uint8_t> group_sampled(n, 0), eligible(n, 0);
+    for (size_t v = 0; v < n; ++v) {
+        const char* id = pmx_index_node_id(m->idx_std, (int64_t)v);
+        if (!id || strncmp(id, "node_", 5) != 0) group_sampled[head[v]] = 1;
+    }
+    for (size_t v = 0; v < n; ++v) eligible[v] = group_sampled[head[v]];
+    return eligible;
+}
+
 // The candidates (no HIP): the nodes of the `top_oc` best distinct overlap coefficients, or exactly the nodes of the
-// override; ascending DFS indices, each once.  False: an override node out of range.
+// override; ascending DFS indices, each once.  False: an override node out of range.  `eligible` (--em-leaves-only, one flag
+// per node; null: every node): a node that is not eligible is passed over BEFORE a new rank is counted, so the ranks are those
+// of the eligible nodes' coefficients (squareEM::squareEM, src/mgsr.cpp:8021-8037); an override is taken as it is.
 bool select_candidates(const std::vector<double>& oc, int64_t n_nodes, int64_t top_oc, const uint32_t* cand_override, int64_t n_override,
-                       std::vector<uint32_t>& cand) {
+                       const uint8_t* eligible, std::vector<uint32_t>& cand) {
     cand.clear();
     if (n_override > 0) {
         cand.assign(cand_override, cand_override + n_override);
@@ -780,6 +808,7 @@ bool select_candidates(const std::vector<double>& oc, int64_t n_nodes, int64_t t
         int64_t ranks = 0;
         double cur = -1.0;
         for (uint32_t v : by_oc) {
+            if (eligible && !eligible[v]) continue;
             if (oc[v] != cur) {
                 cur = oc[v];
                 if (++ranks > top_oc) break;
@@ -1147,7 +1176,7 @@ bool drop_low_proportions(std::vector<int>& cols, std::vector<std::vector<uint32
 
 // (declared in meta_state.hpp: MetaReads::overlap_coefficients and meta_mask.hip's path end here)
 int meta_overlap_from_histogram(pmx_ctx* ctx, pmx_meta* m, int rc, int64_t n_kept, ReadSetGuard* seeded) {
-    const pmx_place_params pp = overlap_place_params();
+    const pmx_place_params pp = overlap_place_params(m);
     pmx_place_result res;
     if (rc == PMX_OK) rc = pmx_place_score(ctx, m->placer, &pp, n_kept, &res);
     if (seeded) seeded->reset();
@@ -1257,6 +1286,7 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     m->assigned = false;
     m->row_first = 0;
     m->row_count = m->dist ? 0 : m->n_reads;
+    m->read_ends_masked = m->mask_read_ends;
     m->reads_set = true;
     return PMX_OK;
     PMX_CATCH
@@ -1268,7 +1298,14 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
     if (!ctx || !m || (n_override > 0 && !cand_override)) return PMX_ERR_ARG;
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
-    if (!select_candidates(m->oc, m->n_nodes, top_oc, cand_override, n_override, m->cand)) return fail(PMX_ERR_ARG, "candidate node out of range");
+    std::vector<uint8_t> eligible;
+    if (m->em_leaves_only && n_override <= 0) {
+        eligible = sampled_or_folded_with_one(m);
+        if (std::find(eligible.begin(), eligible.end(), (uint8_t)1) == eligible.end())
+            return fail(PMX_ERR_ARG, "pmx_meta_score: --em-leaves-only, and every node of the tree is named node_...: no sampled genome to choose the candidates among");
+    }
+    if (!select_candidates(m->oc, m->n_nodes, top_oc, cand_override, n_override, eligible.empty() ? nullptr : eligible.data(), m->cand))
+        return fail(PMX_ERR_ARG, "candidate node out of range");
     m->groups.clear();
     own_row_slice(m);
     if (m->cand.empty() || m->n_reads == 0) return PMX_OK;
@@ -1361,6 +1398,20 @@ int pmx_meta_em(pmx_ctx* ctx, pmx_meta* m, const pmx_meta_params* mp) {
 int pmx_meta_set_dust(pmx_meta* m, double threshold) {
     if (!m || !(threshold <= 100.0)) return PMX_ERR_ARG;      // src/main.cpp:1353-1356: --dust must be <= 100
     m->dust_threshold = threshold;
+    return PMX_OK;
+}
+
+// --mask-read-ends N (src/main.cpp:2065): kept for the next pmx_meta_set_reads, like the DUST threshold
+int pmx_meta_set_mask_read_ends(pmx_meta* m, int64_t n) {
+    if (!m || n < 0 || n > INT32_MAX) return PMX_ERR_ARG;
+    m->mask_read_ends = n;
+    return PMX_OK;
+}
+
+// --em-leaves-only (src/main.cpp:2053): for the pmx_meta_score calls that follow
+int pmx_meta_set_em_leaves_only(pmx_meta* m, int on) {
+    if (!m) return PMX_ERR_ARG;
+    m->em_leaves_only = on != 0;
     return PMX_OK;
 }
 

@@ -7,7 +7,7 @@
 //   genotype   device pileup of the alignments -> substitution calls -> `<prefix>.vcf` (runGenotyping, src/main.cpp:1828-1875)
 //   consensus  the placed genome with the calls applied -> `<prefix>.consensus.fa` (runConsensus, src/main.cpp:1877-1900)
 // `--stop index|place|align|genotype|consensus` ends after that stage (default: consensus).  --meta ->
-// `<prefix>.mgsr.abundance.out`; --meta --filter-and-assign --align-reads [--min-num-align N] -> `<prefix>_mgsr_aligned/`: one
+// `<prefix>.mgsr.abundance.out` (with --write-ocranks also `<prefix>.overlapCoefficients.tsv`); --meta --filter-and-assign --align-reads [--min-num-align N] -> `<prefix>_mgsr_aligned/`: one
 // BAM (+ .bai) per node with at least N assigned reads, and their genomes in reference.fa.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
 // parts of panmap this build leaves out (--impute, ...), BUILDING a homopolymer-compressed index (one
 // given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta.
@@ -33,8 +33,10 @@
 #include <algorithm>
 #include <chrono>
 #include <fstream>
+#include <iomanip>
 #include <memory>
 #include <new>
+#include <numeric>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -71,6 +73,13 @@ struct Config {
     // (src/main.cpp:2032-2040, src/mgsr.cpp:1216-1342, 2062-2075); they are listed in mask_options too
     std::string amplicon_depth;
     double mask_reads_rf = 0.0, mask_seeds_rf = 0.0;
+    // --mask-read-ends N: bases cut from both ends of every read of --meta (src/main.cpp:2065, src/mgsr.cpp:1274-1280); listed
+    // in mask_options too
+    int64_t mask_read_ends = 0;
+    // --em-leaves-only (src/main.cpp:2053) and --write-ocranks (:2115), switches of the abundance mode; `em_options`: the ones
+    // given, in order
+    bool em_leaves_only = false, write_ocranks = false;
+    std::vector<std::string> em_options;
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
     int em_max_iterations = 1000, em_max_rounds = 5;
@@ -124,6 +133,11 @@ void usage() {
           "                             of a primer (amplicon), the reads that are not listed forming one more group\n"
           "      --mask-reads-relative-frequency F / --mask-seeds-relative-frequency F   as --mask-reads / --mask-seeds with the threshold\n"
           "                             int(F x the reads of the amplicon); needs --amplicon-depth; unlisted reads stay unmasked (one of the four)\n"
+          "      --mask-read-ends N     --meta: cut N bases from both ends of every read before anything else looks at it (a read of 2N\n"
+          "                             bases or fewer stays in the sample, empty; also with --gpus N and --batch; not with --filter-and-assign)\n"
+          "      --em-leaves-only       --meta: take the EM's candidates among the sampled genomes only (ids that do not begin with node_, and\n"
+          "                             nodes identical to one); the --top-oc ranks are counted among those (a switch)\n"
+          "      --write-ocranks        --meta: write <prefix>.overlapCoefficients.tsv, every node's id, overlap coefficient and rank (a switch)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange (with --batch:\n"
           "                             whole samples dealt instead, nothing exchanged; also for --meta --filter-and-assign)\n"
@@ -205,8 +219,18 @@ Config parse(int argc, char** argv) {
         else if (a == "--amplicon-depth") { c.amplicon_depth = v(); c.mask_options.push_back(a); }
         else if (a == "--mask-reads-relative-frequency") { c.mask_reads_rf = atof(v().c_str()); c.mask_options.push_back(a); }
         else if (a == "--mask-seeds-relative-frequency") { c.mask_seeds_rf = atof(v().c_str()); c.mask_options.push_back(a); }
-        else if (a == "--jplace" || a == "--mask-read-ends")
-            die("option " + a + " is not accepted: --filter-and-assign is built without jplace output and read-end masking");
+        else if (a == "--mask-read-ends") {
+            const std::string n = v();
+            char* end = nullptr;
+            errno = 0;
+            c.mask_read_ends = strtoll(n.c_str(), &end, 10);
+            if (n.empty() || *end != '\0' || errno != 0 || c.mask_read_ends < 0 || c.mask_read_ends > INT32_MAX)
+                die("option --mask-read-ends is not accepted with the value '" + n + "': it takes a number of bases, 0 or more");
+            c.mask_options.push_back(a);
+        }
+        else if (a == "--em-leaves-only") { c.em_leaves_only = true; c.em_options.push_back(a); }
+        else if (a == "--write-ocranks") { c.write_ocranks = true; c.em_options.push_back(a); }
+        else if (a == "--jplace") die("option " + a + " is not accepted: this build writes no jplace output");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
         else if (a == "--em-convergence-threshold") c.em_convergence = atof(v().c_str());
         else if (a == "--em-delta-threshold") c.em_delta = atof(v().c_str());
@@ -983,7 +1007,10 @@ struct MetaRun {
         if (c.dust > 100.0) die("--dust must be <= 100");                                    // src/main.cpp:1353-1356
         if (c.l < 2) die("--meta needs l >= 2 in this build (the orientation of a lone syncmer is not indexed)");
         if (!c.mask_options.empty() && c.filter_and_assign)   // (initializeQueryDataBatch, src/mgsr.cpp:1575, never masks)
-            die("option " + c.mask_options[0] + " is not accepted with --filter-and-assign: the reference's reader for that mode never masks");
+            die("option " + c.mask_options[0] + " is not accepted with --filter-and-assign: the reference's reader for that mode " +
+                (c.mask_options[0] == "--mask-read-ends" ? "takes the value and ignores it" : "never masks"));
+        if (!c.em_options.empty() && c.filter_and_assign)
+            die("option " + c.em_options[0] + " is not accepted with --filter-and-assign: that mode ranks no candidates and runs no EM");
         if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
         if (c.mask_reads_rf < 0.0 || c.mask_seeds_rf < 0.0)
             die("--mask-reads-relative-frequency and --mask-seeds-relative-frequency must not be negative");
@@ -1060,6 +1087,11 @@ struct MetaRun {
         check(pmx_meta_create(run.ctx, run.idx, run.oidx, &m), "uploading the indexes");
         if (run.dist) check(pmx_meta_attach_dist(m, run.dist), "attaching the ranks");
         check(pmx_meta_set_dust(m, c.dust), "--dust");
+        check(pmx_meta_set_mask_read_ends(m, c.mask_read_ends), "--mask-read-ends");
+        if (c.mask_read_ends > 0)
+            say(c, "meta", "Mask-read-ends " + std::to_string(c.mask_read_ends) + " turned on: " + std::to_string(c.mask_read_ends) +
+                               " bases are cut from both ends of every read before seeding");
+        check(pmx_meta_set_em_leaves_only(m, c.em_leaves_only ? 1 : 0), "--em-leaves-only");
         check(pmx_meta_set_masks(m, c.mask_reads, c.mask_seeds), "--mask-reads / --mask-seeds");
         check(pmx_meta_set_relative_masks(m, c.mask_reads_rf, c.mask_seeds_rf), "--mask-reads-relative-frequency / --mask-seeds-relative-frequency");
         if (!c.filter_and_assign) return;
@@ -1469,6 +1501,33 @@ struct MetaSample {
                            (taxonomy.t ? ", " + std::to_string(n_over) + " spanning more than " + std::to_string(c.maximum_taxon_number) + " taxa" : std::string()) + ")");
     }
 
+    // --write-ocranks (writeOCRanks, src/main.cpp:430-444): `<prefix>.overlapCoefficients.tsv`, one line per node of the index,
+    // id <TAB> coefficient with six decimals <TAB> rank; by falling coefficient, ascending DFS index within a value; the rank
+    // starts at 0 and goes up by one whenever the coefficient differs from the line before.  Every node, also under
+    // --em-leaves-only.  Reads: the overlap coefficients set_reads left (--gpus N: the same on every rank).
+    void write_ocranks() const {
+        pmx_index_info info;
+        check(pmx_index_get_info(run.idx, &info), "the index's size");
+        std::vector<double> oc((size_t)info.n_nodes);
+        check(pmx_meta_overlap_coefficients(run.meta, oc.data(), info.n_nodes), "the overlap coefficients");
+        std::vector<uint32_t> by_oc(oc.size());
+        std::iota(by_oc.begin(), by_oc.end(), 0u);
+        std::stable_sort(by_oc.begin(), by_oc.end(), [&](uint32_t a, uint32_t b) { return oc[a] > oc[b]; });
+        const std::string path = c.output + ".overlapCoefficients.tsv";
+        std::ofstream out(path);
+        if (!out.is_open()) die("cannot write " + path);
+        out << std::fixed << std::setprecision(6);
+        uint32_t rank = 0;
+        double cur = oc.empty() ? 0.0 : oc[by_oc[0]];
+        for (uint32_t v : by_oc) {
+            if (oc[v] != cur) { cur = oc[v]; ++rank; }
+            out << pmx_index_node_id(run.idx, v) << '\t' << oc[v] << '\t' << rank << '\n';
+        }
+        out.close();
+        if (!out) die("cannot write " + path);
+        say(c, "meta", path + " (" + std::to_string(oc.size()) + " nodes, " + std::to_string(oc.empty() ? 0 : rank + 1) + " ranks)");
+    }
+
     // ---- the abundances.  Reads: the merged reads.  Leaves: the candidates scored and the EM's haplotypes in run.meta, on every rank.
     void estimate() {
         pmx_meta* m = run.meta;
@@ -1517,6 +1576,7 @@ void meta_steps(MetaSample& s, bool writer) {
         if (s.c.breadth_ratio) s.write_breadths();
         s.report_assigned();
     } else {
+        if (writer && s.c.write_ocranks) s.write_ocranks();
         s.estimate();
         if (writer) s.write_abundance();
     }
@@ -1586,6 +1646,7 @@ int real_main(int argc, char** argv) {
     if (!c.align_options.empty() && !c.align_reads) die("option --min-num-align is not accepted without --align-reads");
     if (c.filter_and_assign && !c.meta) die("--filter-and-assign needs --meta");
     if (!c.mask_options.empty() && !c.meta) die("option " + c.mask_options[0] + " is not accepted without --meta");
+    if (!c.em_options.empty() && !c.meta) die("option " + c.em_options[0] + " is not accepted without --meta");
     if (c.meta) {   // the reference's --meta has no HPC
         pmx_index_info h;
         if (c.hpc) die("--meta has no homopolymer-compressed form: drop --hpc");

@@ -883,6 +883,9 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     if (m->masked)   // (the reference's reader for this mode, initializeQueryDataBatch, never masks: src/mgsr.cpp:1575)
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with a low-coverage mask (pmx_meta_set_masks), which --filter-and-assign "
                                          "does not have: clear the masks and set the reads again");
+    if (m->read_ends_masked > 0)   // (that reader takes the value and ignores it: `uint32_t /*maskReadsEnds*/`, src/mgsr.cpp:1575)
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with masked read ends (pmx_meta_set_mask_read_ends), which --filter-and-assign "
+                                         "does not have: set the masked ends to 0 and set the reads again");
     if (m->amp_on)   // (that reader takes no amplicon file either)
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with amplicons (pmx_meta_set_amplicons), which --filter-and-assign does not "
                                          "have: clear the amplicons and set the reads again");

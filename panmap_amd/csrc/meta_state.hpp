@@ -79,6 +79,10 @@ struct pmx_meta {
     double llh = 0.0;
     double dust_threshold = 100.0;          // --dust: 100 = no filter
     int64_t n_dust_dropped = 0;
+    // --mask-read-ends (pmx_meta_set_mask_read_ends; extractReadSequences, src/mgsr.cpp:1274-1280): bases the next set_reads
+    // cuts from both ends of every read, and what the last one cut
+    int64_t mask_read_ends = 0, read_ends_masked = 0;
+    bool em_leaves_only = false;            // --em-leaves-only (pmx_meta_set_em_leaves_only): pmx_meta_score's candidates
     int64_t longest = 0;                    // seedmers of the longest merged read
     // --gpus N (pmx_meta_attach_dist): `score` holds merged reads [row_first, row_first + row_count) only (pass A), score_em
     // the EM rows this rank owns (pass B)
@@ -143,6 +147,11 @@ struct pmx_meta {
 inline int meta_masks_above_zero(int64_t reads, int64_t seeds, double reads_rf, double seeds_rf) {
     return (reads > 0) + (seeds > 0) + (reads_rf > 0) + (seeds_rf > 0);
 }
+
+// The per-end trim the seeding kernels get for --mask-read-ends: a k-mer counts when it lies inside read[n : len - n], which
+// is seeding the trimmed string.  The kernels' positions are 32-bit, so a read has fewer than 2^31 bases: a cut of 2^30 bases
+// or more leaves nothing of any read, as 2^30 itself does, and len - trim - k stays inside an int.
+inline int meta_read_end_trim(const pmx_meta* m) { return (int)std::min<int64_t>(m->mask_read_ends, (int64_t)1 << 30); }
 
 // The plane count of the bit-sliced scoring kernels for a sample whose longest merged read has `longest` seedmers: launch is
 // called with it as a compile-time constant, std::integral_constant<int, 7> (counts below 128) or <int, 16>.

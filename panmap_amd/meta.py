@@ -115,6 +115,17 @@ class Meta:
         """--dust: the next set_reads drops reads whose DUST score is non-zero and above `threshold` (100 = off)"""
         check(lib.pmx_meta_set_dust(self._h, float(threshold)), "pmx_meta_set_dust")
 
+    def set_mask_read_ends(self, n: int):
+        """--mask-read-ends: the next set_reads sees every read as read[n:len(read) - n] (empty when len(read) <= 2 * n) -- DUST,
+        seedmer lists, overlap coefficients and all that follows; a read trimmed to nothing stays in the sample like any read
+        without seedmers (raw_to_merged -1).  0 = off.  assign() refuses a read set made with n > 0.  --gpus N: the same n on every rank."""
+        check(lib.pmx_meta_set_mask_read_ends(self._h, int(n)), "pmx_meta_set_mask_read_ends")
+
+    def set_em_leaves_only(self, on: bool = True):
+        """--em-leaves-only: score() without `candidates` chooses among the sampled genomes only -- nodes whose id does not begin
+        with `node_`, or that Index.node_heads folds onto the same head as one -- and counts the top_oc ranks among those"""
+        check(lib.pmx_meta_set_em_leaves_only(self._h, int(bool(on))), "pmx_meta_set_em_leaves_only")
+
     def set_masks(self, reads: int = 0, seeds: int = 0):
         """--mask-reads / --mask-seeds (src/mgsr.cpp:2049-2139) for the set_reads calls that follow; at most one above 0.  With
         count[h] = the summed multiplicities of the merged reads that carry hash h: `reads` = T drops every merged read with a
