@@ -525,7 +525,9 @@ typedef struct pmx_align_stats {
     int64_t huge_tier_items;     /* wave-tier items re-run once more with 16x the anchors (what overflowed the general capacities) */
     int64_t simple_chain_items;  /* ... of the compact tier's, the distinct pairs its register-only chain kernel finished (mates that
                                     do not overlap on the reference) */
-    int64_t reserved[6];
+    int64_t near_chain_items;    /* ... and the ones it finished whose mates' extents overlap while their seeds do not (the near class);
+                                    not part of simple_chain_items */
+    int64_t reserved[5];
 } pmx_align_stats;
 int pmx_align_get_stats(pmx_ctx *ctx, pmx_aligner *al, pmx_align_stats *out);
 /* device pointers of the last result (for RCCL gathers without a host bounce) */

@@ -85,7 +85,7 @@ class AlignStats(C.Structure):
     _fields_ = [("n_items", C.c_int64), ("dp_pairs", C.c_int64), ("dp_calls", C.c_int64), ("dp_cells", C.c_int64),
                 ("dp_rounds", C.c_int64), ("wave_tier_items", C.c_int64), ("general_tier_items", C.c_int64),
                 ("compact_tier_items", C.c_int64), ("huge_tier_items", C.c_int64), ("simple_chain_items", C.c_int64),
-                ("reserved", C.c_int64 * 6)]
+                ("near_chain_items", C.c_int64), ("reserved", C.c_int64 * 5)]
 
 
 class AlnRecord(C.Structure):

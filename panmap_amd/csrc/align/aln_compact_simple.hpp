@@ -63,6 +63,36 @@
 // is 0, and c_align1 reads only the list's first and last anchor and whether it has more than one: it is called on a list
 // of those two.  c_reg_set_coor's outputs are all overwritten by c_align1 and read by nothing before it but
 // mm_fix_bad_ends' loops, which do not run here.  From there on (filter, mapq, pairing, record) the code is shared.
+//
+// RANGES, NOT EXTENTS.  (d) is about the mates' position ranges: the reference positions of their SEEDS.  The mates'
+// extents -- where the reads themselves lie, each projected from its first seed -- may overlap: mates that overlap by at
+// most k - 1 bases cannot share a k-mer, so they share no minimizer, and every seed of the lower mate still lies below
+// every seed of the upper one; the same holds for a longer overlap as far as neither mate has a seed inside it.  No step
+// above reads an extent:
+//   * SORT needs the position words distinct and the runs in order: (c) and (d).
+//   * FILL, across the mates: comput_sc on a pair of anchors of different mates tests dq and dr against 0 and max_dist_x
+//     and nothing else.  dr > 0 by (d), dq > 0 because the mates' query intervals are disjoint whatever the reference
+//     says; a dr below k (the runs' ends closer than a seed: the seeds themselves overlap on the reference) only makes
+//     dg = min(dr, dq) small, and (1), (2) are statements about min(dg, k) for any dg > 0.  The penalty is the one number
+//     pen for dd = |dr - dq|: with extents that overlap by v bases dr - dq = -v at every cross pair.
+//   * the junction is c_chain_score_tab on those two anchors -- the function compact_chain_pair's fill calls; a chain
+//     linked across overlapping extents is the chain the first form finds.
+//   * REGIONS: one region per mate from its own run's two ends; c_align1's end extensions run along the mate's own
+//     diagonal to the read's ends and take no notice of the other mate's region.  Pairing and the record are shared code.
+//
+// CLASSES.  Two sets of pairs come here, both on the simple list:
+//   * marked by the seeding (compact_seed_pair's `simple`, PMX_C_NSEED_SIMPLE in the hand-over count): the extents lie
+//     apart.  Extents are all the seeds kernel has in registers; its code does not change.
+//   * the near class, decided in k_compact_classes_near16/32 (registers to spare) by compact_near_class below for a pair
+//     without the mark: both mates have a seed, n <= PMX_C_CAP1, and the junction seeds -- mate 0's last, mate 1's first --
+//     have one strand relation and lie in the order (d) implies for it: rel = 0: pos(seed n0 - 1) < pos(seed n0); rel = 1:
+//     pos(seed n0) < pos(seed n0 - 1).  For a pair that satisfies (b) and (c) that IS (d), since each mate's positions are
+//     monotone; for any other pair it is a guess, and the pass over the words finds (b), (c) violated and returns
+//     PMX_C_BAIL.  A wrong class costs a detour through the second form, never a record.
+//     Third condition: the junction's link gains, min(dg, k) > pen.  Junction seeds of overlapping extents lie a few bases
+//     apart (dr small) while dd is the overlap, so the link often gains nothing: fJ <= fA, which BACKTRACK above does not
+//     follow -- in the host model every bail of a near pair that the first form finishes was this one (4 % of the class).
+// The kernel counts what it finishes of the two in separate counters (simple_chain_items, near_chain_items).
 #pragma once
 #include "aln_compact.hpp"
 
@@ -76,6 +106,37 @@ struct CEnds {
     PMX_HD int32_t y(int i) const { return i ? yl : y0; }
     PMX_HD uint32_t rev(int) const { return 0u; }   // (read by c_align1<MULTI>'s fence scan only, which this list never reaches)
 };
+
+// The near class (see CLASSES above): the junction seeds of a pair the seeding did not mark -- mate 0's last seed and mate
+// 1's first, adjacent hand-over words -- have one strand relation, lie in the order (d) asks of them, and the link between
+// them would raise the score.  `out`: the pair's hand-over words (CSeedOutT<PT>::out).  Not complete and not meant to be:
+// compact_chain_simple checks (a) - (e) itself.
+template <class PT>
+PMX_HD bool compact_near_class(const c_g32* out, int n_s, int n_s0, const Opt& o) {
+    const int n0 = n_s0, n1 = n_s - n_s0;
+    if (n0 < 1 || n1 < 1 || n_s > PMX_C_CAP1) return false;
+    uint32_t xa, ya, xb, yb;   // a: seed n0 - 1, b: seed n0
+    if (sizeof(PT) == 2) {
+        const uint32_t a = out[n0 - 1], b = out[n0];
+        xa = a & 0xffffu; ya = a >> 16; xb = b & 0xffffu; yb = b >> 16;
+    } else {
+        xa = out[2 * n0 - 2]; ya = out[2 * n0 - 1]; xb = out[2 * n0]; yb = out[2 * n0 + 1];
+    }
+    const uint32_t rel = (xa ^ ya) & 1u;
+    if (((xb ^ yb) & 1u) != rel) return false;
+    // the junction as compact_chain_simple sees it: the anchors' dq is the seeds' on either strand (both query positions
+    // are mirrored), dr their distance on the reference in the order of (d)
+    const int32_t dr = rel ? (int32_t)(xa >> 1) - (int32_t)(xb >> 1) : (int32_t)(xb >> 1) - (int32_t)(xa >> 1);
+    const int32_t dq = (int32_t)((yb & 0x3ffu) >> 1) - (int32_t)((ya & 0x3ffu) >> 1);
+    if (dr <= 0 || dq <= 0) return false;
+    // min(dg, k) - pen > 0 (comput_sc for anchors of different mates, the values the penalty table holds): with seeds this
+    // close the link often gains nothing, and a linked junction with fJ <= fA is one the path does not follow
+    const int32_t dd = dr > dq ? dr - dq : dq - dr, dg = dr < dq ? dr : dq;
+    if (dd >= PMX_C_PEN_DIFF) return false;
+    int ps, pd;
+    c_pen_values(o.chn_pen_gap, dd, &ps, &pd);
+    return (dg < o.k ? dg : o.k) > (pd < 255 ? pd : 255);
+}
 
 template <class PT>
 PMX_HD int compact_chain_simple(const CSeedOutT<PT>& so, const Opt& o, const RefIndex& ri, const CRead* rd, int n_s, int n_s0, CResult& out,

@@ -57,13 +57,15 @@ struct AlignArgs {
     // where they are) to multi_list, the second form runs over the list and appends what it cannot finish to retry_list.
     // NULL = every bail goes to retry_list at once.
     uint32_t* multi_list;
-    unsigned long long* multi_count;   // [0] length of multi_list, [1] pairs the second form finished, [2] .. [4]: see simple_list
+    unsigned long long* multi_count;   // [0] length of multi_list, [1] pairs the second form finished, [2] .. [5]: see simple_list
     uint32_t* multi_ws;                // region records of the second form: PMX_CM_WS_WORDS * 64 words per wave of its grid
     // Pairs whose mates do not overlap on the reference (k_align_simple*, align/aln_compact_simple.hpp): k_compact_seeds
     // marks them in cseed_n, k_compact_classes appends every launch position to one of two lists, the simple pairs from simple_list[0] on (length multi_count[2]),
     // all others from simple_list[n_items rounded up to 64] on (length multi_count[3]); k_align_simple* runs the first
     // list and counts the pairs it finishes in multi_count[4], k_align_compact* runs the second.  NULL = no classes:
     // k_align_compact* runs every launch position (PMX_ALIGN_NO_SIMPLE).
+    // k_compact_classes_near16/32 put on the first list, beside the marked pairs, those whose junction seeds lie in order
+    // (compact_near_class; PMX_ALIGN_NO_NEAR: k_compact_classes); k_align_simple* counts the ones it finishes in multi_count[5].
     uint32_t* simple_list;
 
     // CIGAR arena (output).  Here and not behind `records`: with these three at the end of the struct the wave kernels'
@@ -145,6 +147,8 @@ __global__ void k_align_simple16(AlignArgs A);    // over the simple list: chain
 __global__ void k_align_simple32(AlignArgs A);
 __global__ void k_compact_seeds16(AlignArgs A);   // sketch + index probes of every pair -> cseeds / cseed_n
 __global__ void k_compact_classes(AlignArgs A);   // cseed_n -> the two class lists (simple_list)
+__global__ void k_compact_classes_near16(AlignArgs A);   // ... and the near class, from the junction seeds in cseeds
+__global__ void k_compact_classes_near32(AlignArgs A);
 __global__ void k_compact_seeds32(AlignArgs A);
 
 // bytes of the traceback matrix ksw_extd2 needs for a request (same n_col as ksw2_extd2_sse.c:95-98)

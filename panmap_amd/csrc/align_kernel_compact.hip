@@ -82,9 +82,21 @@ __device__ __forceinline__ void compact_seeds_body(const AlignArgs& A) {
 // SIMD (132 VGPRs).  A workgroup takes PMX_C_CLASS_BLOCK consecutive positions and claims its stretch of each list with
 // ONE atomic: with one per wave of 64 positions, as multi_list is filled, the 78,000 waves of a 5M-pair launch queue on
 // two addresses and the kernel takes 1.24 ms instead of 0.1.  Inside the stretch: wave by wave, pass by pass, lane by lane.
+// NEAR (the hand-over's position type, or void = off: PMX_ALIGN_NO_NEAR): a position the seeding did not mark goes to the
+// first list too when its junction seeds say so (compact_near_class: one scattered 8-byte read of the pair's hand-over
+// words).  Decided here and not in the seeds kernel for the same reason: this kernel has the registers to spare.
 #define PMX_C_CLASS_PASSES 8
 #define PMX_C_CLASS_BLOCK (256 * PMX_C_CLASS_PASSES)
-__global__ void __launch_bounds__(256) k_compact_classes(AlignArgs A) {
+template <class NEAR> struct CNearOf {
+    static __device__ __forceinline__ bool get(const AlignArgs& A, int64_t it, unsigned int c) {
+        return compact_near_class<NEAR>((const c_g32*)(A.cseeds + (size_t)it * CSeedOutT<NEAR>::kPairWords), PMX_C_NSEED_N(c), PMX_C_NSEED_N0(c), A.opt);
+    }
+};
+template <> struct CNearOf<void> {
+    static __device__ __forceinline__ bool get(const AlignArgs&, int64_t, unsigned int) { return false; }
+};
+template <class NEAR>
+__device__ __forceinline__ void compact_classes_body(const AlignArgs& A) {
     __shared__ unsigned int w_s[4], w_r[4];
     __shared__ unsigned long long b_s, b_r;
     const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
@@ -97,7 +109,8 @@ __global__ void __launch_bounds__(256) k_compact_classes(AlignArgs A) {
         const int64_t it = base + p * 64 + lane;
         const bool in = it < A.n_items;
         const unsigned int c = in ? (unsigned int)A.cseed_n[it] : PMX_C_NSEED_BAIL;
-        const bool simple = c != PMX_C_NSEED_BAIL && (c & PMX_C_NSEED_SIMPLE) != 0u;
+        bool simple = c != PMX_C_NSEED_BAIL && (c & PMX_C_NSEED_SIMPLE) != 0u;
+        if (c != PMX_C_NSEED_BAIL && !simple) simple = CNearOf<NEAR>::get(A, it, c);
         smask[p] = __ballot(simple);
         rmask[p] = __ballot(in && !simple);
         n_s += (unsigned int)__popcll(smask[p]);
@@ -123,6 +136,9 @@ __global__ void __launch_bounds__(256) k_compact_classes(AlignArgs A) {
         at_r += (unsigned long long)__popcll(rmask[p]);
     }
 }
+__global__ void __launch_bounds__(256) k_compact_classes(AlignArgs A) { compact_classes_body<void>(A); }
+__global__ void __launch_bounds__(256) k_compact_classes_near16(AlignArgs A) { compact_classes_body<uint16_t>(A); }
+__global__ void __launch_bounds__(256) k_compact_classes_near32(AlignArgs A) { compact_classes_body<uint32_t>(A); }
 __global__ void __launch_bounds__(64) k_compact_seeds16(AlignArgs A) { compact_seeds_body<uint16_t>(A); }
 __global__ void __launch_bounds__(64) k_compact_seeds32(AlignArgs A) { compact_seeds_body<uint32_t>(A); }
 
@@ -312,7 +328,8 @@ __device__ __forceinline__ void align_compact_multi_body(const AlignArgs& A) {
     }
 }
 
-// The pairs of the simple list (launch positions; mates that do not overlap on the reference): thread per pair, chained
+// The pairs of the simple list (launch positions; mates that do not overlap on the reference, counted in multi_count[4]
+// when finished, and mates whose junction seeds lie in order -- the near class -- in multi_count[5]): thread per pair, chained
 // from the hand-over words in registers (align/aln_compact_simple.hpp).  The only LDS is the penalty tables.  A pair the
 // path does not finish goes where the first form sends a pair it leaves after the seeds: to the second form's list (which
 // finishes a superset of the first form's pairs), or, without a second form, to the bail list.  One workgroup per 64
@@ -341,6 +358,9 @@ __device__ __forceinline__ void align_simple_body(const AlignArgs& A) {
         int rc = PMX_C_DONE;
         CResult res;
         res.mapped = 0;
+        // the lanes whose pair the seeding marked (the others: the near class); a wave-wide mask, so that no lane carries
+        // its class across the chain
+        const unsigned long long cmask = __ballot(e < n_list && (A.cseed_n[A.simple_list[e]] & PMX_C_NSEED_SIMPLE) != 0u);
         if (e < n_list) {
             it = (int64_t)A.simple_list[e];
             CRead rd[2];
@@ -354,8 +374,9 @@ __device__ __forceinline__ void align_simple_body(const AlignArgs& A) {
         }
         const bool done = item >= 0 && rc == PMX_C_DONE;
         bool bail = item >= 0 && rc != PMX_C_DONE;
-        const unsigned long long dmask = __ballot(done);
+        const unsigned long long fmask = __ballot(done), dmask = fmask & cmask, nmask = fmask & ~cmask;
         if (dmask && lane == 0) atomicAdd(A.multi_count + 4, (unsigned long long)__popcll(dmask));
+        if (nmask && lane == 0) atomicAdd(A.multi_count + 5, (unsigned long long)__popcll(nmask));
         if (A.multi_list) {
             const unsigned long long mmask = __ballot(bail);
             if (mmask) {

@@ -100,7 +100,7 @@ namespace {
 struct AlignSwitches {
     static bool on(OptId id) { return pmx::opt_str(id) != nullptr; }
     const bool no_tpp = on(O_ALIGN_NO_TPP), no_compact = on(O_ALIGN_NO_COMPACT), no_dedup = on(O_ALIGN_NO_DEDUP);
-    const bool compact_pos32 = on(O_ALIGN_COMPACT_POS32), compact_fused = on(O_ALIGN_COMPACT_FUSED), no_multi = on(O_ALIGN_NO_MULTI), no_simple = on(O_ALIGN_NO_SIMPLE);
+    const bool compact_pos32 = on(O_ALIGN_COMPACT_POS32), compact_fused = on(O_ALIGN_COMPACT_FUSED), no_multi = on(O_ALIGN_NO_MULTI), no_simple = on(O_ALIGN_NO_SIMPLE), no_near = on(O_ALIGN_NO_NEAR);
     const bool prof = on(O_ALIGN_PROF), verbose = on(O_ALIGN_VERBOSE);                                                    // diagnostics
     const bool dp_hist = on(O_DP_HIST), dpg_prof = on(O_DPG_PROF);
     int waves_per_simd = 4;
@@ -111,7 +111,7 @@ struct AlignSwitches {
                                         // the boundary's handling of invalid records can be exercised (tests/test_align_gpu.py)
     size_t lds_budget = 24 * 1024, lr_lds_budget = 8900;   // wave tiers: short reads / long reads (one switch sets both)
     size_t slab_budget = 0;             // tests: force a small grid; 0 = a third of the device memory
-    size_t tpp_tb = 0;                  // in-lane DPs measured slower than request + replay (divergence): off
+    const size_t tpp_tb = 0;            // in-lane DPs measured slower than request + replay (divergence): off, and no switch for it any more
     size_t tb_small = (size_t)8 << 20;  // long reads: traceback per wave of the first launch
     int64_t small_rounds = 8192, bail_tpp_min = 4096, dpg_left_few = 256;
     double dedup_depth = 64.0;
@@ -121,7 +121,6 @@ struct AlignSwitches {
         if (const char* e = pmx::opt_str(pmx::O_ALIGN_SLAB_MB)) slab_budget = (size_t)std::max<long long>(atoll(e), 1) << 20;
         if (const char* e = pmx::opt_str(pmx::O_ALIGN_TEST_MAX_CIGAR)) test_max_cigar = atoi(e);
         if (const char* e = pmx::opt_str(pmx::O_ALIGN_TPP_WAVES)) tpp_waves = atoi(e);
-        if (const char* e = pmx::opt_str(pmx::O_ALIGN_TPP_TB)) tpp_tb = (size_t)atoll(e);
         if (const char* e = pmx::opt_str(pmx::O_ALIGN_TPP_MIN)) small_rounds = atoll(e);
         if (const char* e = pmx::opt_str(pmx::O_ALIGN_DPG_WAVES)) dpg_waves = std::max(1, atoi(e));
         if (const char* e = pmx::opt_str(pmx::O_ALIGN_BAIL_TPP_MIN)) bail_tpp_min = atoll(e);
@@ -221,7 +220,7 @@ bool AlignStage::setup(int revcomp_mate2, uint64_t cigar_cap) {
     PMX_ZERO(al->stats, 4, stream);
     al->dd_count.ensure(4);   // distinct-pair map: [0] representatives, [1] copies of an arena-overflowed representative, [2] copies of bails
     PMX_ZERO(al->dd_count, 4, stream);
-    al->last_dp_slots = 0; al->last_compact = 0; al->last_simple = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_huge = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
+    al->last_dp_slots = 0; al->last_compact = 0; al->last_simple = 0; al->last_near = 0; al->last_tpp_retry = 0; al->last_retry = 0; al->last_huge = 0; al->last_dp_rounds = 0; al->last_dp_requests = 0;
     memset(&al->last_stats, 0, sizeof(al->last_stats));
     if (n_items <= 0) return false;
     al->last_stats.n_items = n_items;
@@ -439,10 +438,12 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
     // registers allow instead of seven waves per CU; the seeds cross in HBM (224 bytes per pair with 16-bit
     // position words).  PMX_ALIGN_COMPACT_FUSED keeps everything in k_align_compact.
     // PMX_ALIGN_NO_SIMPLE: no class lists, the chain kernel runs every launch position.
+    // PMX_ALIGN_NO_NEAR: only the pairs the seeding marked (extents apart) on the simple list, not the near class.
     const bool c_simple = !c_fused && !sw.no_simple;
     if (!c_fused) {
         const size_t blocks = (size_t)((n_launch + 63) / 64);
-        // [0] length of multi_list, [1] pairs the second form finished, [2] / [3] lengths of the two class lists, [4] pairs k_align_simple finished
+        // [0] length of multi_list, [1] pairs the second form finished, [2] / [3] lengths of the two class lists,
+        // [4] / [5] pairs k_align_simple finished: marked by the seeding / of the near class
         al->multi_count.ensure(8);
         PMX_ZERO(al->multi_count, 8, stream);
         if (c_simple) {
@@ -464,7 +465,7 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         PMX_LAUNCH(s_kern, dim3((unsigned)s_grid), dim3(64), ((size_t)PMX_C_SEEDQ * 2 + 8) * 64 * sizeof(uint32_t),   // queues + eight staging words per lane
                    stream, A);
         if (c_simple) {
-            PMX_LAUNCH(k_compact_classes, dim3((unsigned)((n_launch + 2047) / 2048)), dim3(256), 0, stream, A);   // PMX_C_CLASS_BLOCK positions each
+            PMX_LAUNCH(sw.no_near ? k_compact_classes : pos16 ? k_compact_classes_near16 : k_compact_classes_near32, dim3((unsigned)((n_launch + 2047) / 2048)), dim3(256), 0, stream, A);   // PMX_C_CLASS_BLOCK positions each
         }
         timer_end(ctx, "align_cseeds", 1);
     }
@@ -484,6 +485,7 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
     // registers allow; the chain kernel below then runs the other list.  Both lists' lengths stay on the device: one
     // workgroup per 64 positions of the launch, those beyond a list's end leave at once (a resident grid striding over
     // the lists -- PMX_ALIGN_COMPACT_WAVES -- is the slower form here as it is for the chain kernel alone).
+    // The near class (mates that overlap by less than a seed, another 29 % of that library) is on the same list.
     if (c_simple) {
         PMX_LAUNCH(pos16 ? k_align_simple16 : k_align_simple32, dim3((unsigned)c_grid), dim3(64), (size_t)PMX_C_SIMPLE_LDS_PAD + PMX_C_PEN_BYTES, stream, A);
     }
@@ -504,14 +506,15 @@ int64_t AlignStage::compact_tier(const uint32_t* order) {
         pair_count_copies(ctx, al, al->bail_list.p, al->retry_count.p + 2, rs->pd_mult.p, n_launch);
         PMX_D2H(&h_dups, pmx::at(al->dd_count, 2), 1, stream);
     }
-    unsigned long long h_cnt[5] = {0, 0, 0, 0, 0};   // multi_count[0 .. 4]
+    unsigned long long h_cnt[6] = {0, 0, 0, 0, 0, 0};   // multi_count[0 .. 5]
     PMX_D2H(&h_bail, pmx::at(al->retry_count, 2), 1, stream);
     if (!c_fused) PMX_D2H(h_cnt, al->multi_count, stream);
     PMX_HIP(hipStreamSynchronize(stream));
     if (sw.verbose && !c_fused)
-        fprintf(stderr, "align: compact tier, %lld launch positions: simple list %llu (k_align_simple finished %llu), other list %llu; second form: %llu listed, %llu finished; %llu bails\n",
-                (long long)n_launch, h_cnt[2], h_cnt[4], h_cnt[3], h_cnt[0], h_cnt[1], h_bail);
+        fprintf(stderr, "align: compact tier, %lld launch positions: simple list %llu (k_align_simple finished %llu marked by the seeding, %llu of the near class), other list %llu; second form: %llu listed, %llu finished; %llu bails\n",
+                (long long)n_launch, h_cnt[2], h_cnt[4], h_cnt[5], h_cnt[3], h_cnt[0], h_cnt[1], h_bail);
     al->last_simple = (int64_t)h_cnt[4];
+    al->last_near = (int64_t)h_cnt[5];
     al->last_compact = n_items - (int64_t)h_bail - (int64_t)h_dups;
     return (int64_t)h_bail;
 }

@@ -58,7 +58,7 @@ struct pmx_aligner {
     pmx::DevBuf<int32_t> edits;              // AlignArgs::edits while pmx_align_score_reads runs
     bool want_edits = false;
     pmx_align_stats last_stats;
-    int64_t last_dp_slots = 0, last_compact = 0, last_simple = 0;
+    int64_t last_dp_slots = 0, last_compact = 0, last_simple = 0, last_near = 0;
     int64_t n_records = 0;
     uint64_t cigar_cap = 0;
     size_t dev_total_mem = 0;            // hipMemGetInfo total, asked once

@@ -189,6 +189,7 @@ int pmx_align_readset(pmx_ctx* ctx, pmx_aligner* al, const pmx_readset* rs, int 
         al->last_stats.general_tier_items = al->last_retry;
         al->last_stats.compact_tier_items = al->last_compact;
         al->last_stats.simple_chain_items = al->last_simple;
+        al->last_stats.near_chain_items = al->last_near;
         al->last_stats.huge_tier_items = al->last_huge;
         if (rs->total > 0) al->cigar_words_per_kbase = std::max(al->cigar_words_per_kbase * 0.5, (double)used * 1000.0 / (double)rs->total);
         if (used <= cap) return PMX_OK;

@@ -40,6 +40,7 @@
     X(ALIGN_DEDUP_DEPTH, "tune", "align: distinct-pair map from this many pairs per reference base (default 64; 0 = always)")                  \
     X(ALIGN_NO_MULTI, "ab", "align: compact tier without its second form (several regions per mate): every bail to the thread-per-pair tier")  \
     X(ALIGN_NO_SIMPLE, "ab", "align: compact tier without the register-only chain kernel for mates that do not overlap: every pair through k_align_compact") \
+    X(ALIGN_NO_NEAR, "ab", "align: only pairs whose mates' extents lie apart on the register-only chain kernel's list, not those whose junction seeds lie in order") \
     X(ALIGN_COMPACT_WAVES, "tune", "align: compact chain kernel on a resident grid of N waves per CU (default: one workgroup per 64 pairs)")    \
     X(ALIGN_CSEED_WAVES, "tune", "align: compact seeds kernel on a resident grid of N waves per CU")                                           \
     X(ALIGN_NO_TPP, "ab", "align: no thread-per-pair tier (bails straight to the wave tiers)")                                                 \
@@ -47,7 +48,6 @@
     X(ALIGN_BAIL_TPP_MIN, "tune", "align: fewer compact-tier bails than this go straight to the wave tier (default 4096)")                     \
     X(ALIGN_TPP_MIN, "tune", "align: fewer DP requests than this end the service rounds (default 8192)")                                       \
     X(ALIGN_TPP_WAVES, "tune", "align: thread-per-pair waves per CU (default 16)")                                                             \
-    X(ALIGN_TPP_TB, "tune", "align: thread-per-pair in-lane traceback bytes (default 0: DPs are requests)")                                    \
     X(ALIGN_DPG_WAVES, "tune", "align: grouped DP service waves per CU (default 8)")                                                           \
     X(ALIGN_WAVES, "tune", "align: wave tiers' target waves per SIMD (default 4)")                                                             \
     X(ALIGN_LDS_KB, "tune", "align: LDS budget of a wave-tier wave, KB")                                                                       \

@@ -105,3 +105,13 @@ cls, forms = cs.host_chain_simple(tempfile.mkdtemp(prefix="chain_simple_"), g, [
 d1 = forms[1][1]
 print("---- simple path: classed simple %.4f of the pairs, finished %.4f, bailed %.4f; first form finishes %.4f; finished by the first form but not by the path, among the classed: %.4f"
       % ((cls >= 2).mean(), (cls == 2).mean(), (cls == 3).mean(), d1.mean(), ((cls == 3) & (d1 == 1)).mean()))
+# ---- the near class (compact_near_class: the junction seeds lie in order) against the rule that needs no read of the hand-over
+# words (extents overlap by at most k - 1), among the pairs the seeding did not mark -- the decision rule of profiles/r18
+import chain_near_cases as cn
+cls, bound, forms = cn.host_chain_near(tempfile.mkdtemp(prefix="chain_near_"), g, [r if i % 2 == 0 else pmx.reverse_complement(r) for i, r in enumerate(reads)])
+d1 = forms[1][1]
+near = cls >= 4
+print("---- near class: junction rule classes %.4f of the pairs, finishes %.4f, bails on %.4f (of which the first form finishes %.4f); "
+      "extent bound classes %.4f, of which the path finishes %.4f; classed by the bound but not by the junction rule %.4f; marked by the seeding %.4f (finished %.4f)"
+      % (near.mean(), (cls == 4).mean(), (cls == 5).mean(), ((cls == 5) & (d1 == 1)).mean(),
+         (bound == 1).mean(), ((bound == 1) & (cls == 4)).mean(), ((bound == 1) & ~near).mean(), ((cls == 2) | (cls == 3)).mean(), (cls == 2).mean()))
