@@ -787,6 +787,23 @@ int64_t pmx_taxonomy_lookup(const pmx_taxonomy *t, const char *identifier);
  * 8 GiB: nothing is approximated. */
 int pmx_meta_set_breadth(pmx_meta *m, int on);
 int pmx_meta_breadth(const pmx_meta *m, uint64_t *total_ref_seeds, uint64_t *observed, uint64_t *depth, int64_t cap_nodes);
+/* The per-read scores behind --write-meta-read-scores-unfiltered / -filtered of the abundance mode (scoreReads, src/mgsr.cpp:
+ * 7325-7420: maxScore and epp of every read; collapseIdenticalScoringNodes, :794-847; writeMetaReadScores, src/main.cpp:446-466).
+ * pmx_meta_read_best scores every merged read of the last pmx_meta_set_reads against EVERY node, score = max(f, r) as above,
+ * and keeps two numbers a read: max_score, its best score over all nodes, and n_best, the number of ACTIVE nodes that reach
+ * it (0 when max_score is 0).  A node is active when it is the root or one of its changes in the oriented index has a hash, in
+ * either orientation, among the distinct seedmer hashes of the merged reads (after --dust and the masks): the nodes the
+ * reference keeps when it collapses the tree for a sample.  An inactive node scores as its nearest active ancestor, so the
+ * maximum is the same over either set.  It needs no pmx_meta_score, builds no read -> node list, and runs on reads set with a
+ * mask, with amplicons or with masked ends.  PMX_ERR_ARG before pmx_meta_set_reads; PMX_ERR_UNSUPPORTED with an attached dist
+ * (a sharded sample has no raw -> merged map to report against).  What pmx_meta_assign left on the handle stays, and the other
+ * way round; pmx_meta_set_reads empties all of it.
+ * pmx_meta_read_best_get: per merged read (cap >= pmx_meta_num_reads; either pointer may be NULL); pmx_meta_active_nodes: one
+ * byte per DFS index, 1 = active (cap_nodes >= the index's nodes).  Both PMX_ERR_ARG until pmx_meta_read_best has run since the
+ * last pmx_meta_set_reads. */
+int pmx_meta_read_best(pmx_ctx *ctx, pmx_meta *m);
+int pmx_meta_read_best_get(const pmx_meta *m, uint16_t *max_score, uint32_t *n_best, int64_t cap);
+int pmx_meta_active_nodes(const pmx_meta *m, uint8_t *active, int64_t cap_nodes);
 /* the reads of the last pmx_meta_set_reads in input order -> their merged read, -1 for a read dropped by --dust or without
  * seedmers (PMX_ERR_UNSUPPORTED with an attached dist: the merged reads are then the whole sample's) */
 int64_t pmx_meta_num_raw_reads(const pmx_meta *m);
@@ -949,7 +966,7 @@ int64_t pmx_options_describe(char *buf, int64_t cap);
    pmx_meta_score; "meta_assign" = the device work of pmx_meta_assign up to the scan of the node counts, "meta_assign_emit" = its
    list kernel, both summed over the call's chunks; with a taxonomy "meta_assign" ends before the taxonomy kernels and
    "meta_assign_taxa" holds them and that scan; with pmx_meta_set_breadth "meta_breadth" = the breadth kernels, summed likewise, and "meta_breadth_count" = the column
-   count kernel among them; "meta_mask" = the mask step of pmx_meta_set_reads, and with amplicons "meta_mask_sort" = the sort
+   count kernel among them; "meta_read_best" = the device work of pmx_meta_read_best, summed over its chunks; "meta_mask" = the mask step of pmx_meta_set_reads, and with amplicons "meta_mask_sort" = the sort
    of its (amplicon, hash) keys inside it); < 0: no such span in the last call */
 double pmx_last_kernel_ms(pmx_ctx *ctx, const char *name);
 

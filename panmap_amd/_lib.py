@@ -251,6 +251,9 @@ SIGNATURES = {
     "pmx_taxonomy_num_taxa": (_i64, [_vp]),
     "pmx_taxonomy_taxon_name": (_cp, [_vp, _i64]),
     "pmx_taxonomy_lookup": (_i64, [_vp, _cp]),
+    "pmx_meta_read_best": (_i32, [_vp, _vp]),
+    "pmx_meta_read_best_get": (_i32, [_vp, _vp, _vp, _i64]),
+    "pmx_meta_active_nodes": (_i32, [_vp, _vp, _i64]),
     "pmx_meta_num_raw_reads": (_i64, [_vp]),
     "pmx_meta_raw_to_merged": (_i32, [_vp, _vp, _i64]),
     "pmx_index_node_heads": (_i32, [_vp, _vp]),

@@ -1284,6 +1284,7 @@ int pmx_meta_set_reads(pmx_ctx* ctx, pmx_meta* m, const char* concat, const int6
     m->cand.clear();
     m->groups.clear();
     m->assigned = false;
+    m->best_done = m->active_built = false;
     m->row_first = 0;
     m->row_count = m->dist ? 0 : m->n_reads;
     m->read_ends_masked = m->mask_read_ends;

@@ -7,7 +7,8 @@
 //   genotype   device pileup of the alignments -> substitution calls -> `<prefix>.vcf` (runGenotyping, src/main.cpp:1828-1875)
 //   consensus  the placed genome with the calls applied -> `<prefix>.consensus.fa` (runConsensus, src/main.cpp:1877-1900)
 // `--stop index|place|align|genotype|consensus` ends after that stage (default: consensus).  --meta ->
-// `<prefix>.mgsr.abundance.out` (with --write-ocranks also `<prefix>.overlapCoefficients.tsv`); --meta --filter-and-assign --align-reads [--min-num-align N] -> `<prefix>_mgsr_aligned/`: one
+// `<prefix>.mgsr.abundance.out` (with --write-ocranks also `<prefix>.overlapCoefficients.tsv`, with --write-meta-read-scores-unfiltered / -filtered
+// `<prefix>.read_scores_info.unfiltered.tsv` / `.filtered.tsv`); --meta --filter-and-assign --align-reads [--min-num-align N] -> `<prefix>_mgsr_aligned/`: one
 // BAM (+ .bai) per node with at least N assigned reads, and their genomes in reference.fa.  Refused with an error, never a silent no-op: the bwa backend (-a), --baq, the options of the
 // parts of panmap this build leaves out (--impute, ...), BUILDING a homopolymer-compressed index (one
 // given with -i or found at <panman>.idx is placed against as it is), --hpc or such an index with --meta.
@@ -76,9 +77,9 @@ struct Config {
     // --mask-read-ends N: bases cut from both ends of every read of --meta (src/main.cpp:2065, src/mgsr.cpp:1274-1280); listed
     // in mask_options too
     int64_t mask_read_ends = 0;
-    // --em-leaves-only (src/main.cpp:2053) and --write-ocranks (:2115), switches of the abundance mode; `em_options`: the ones
-    // given, in order
-    bool em_leaves_only = false, write_ocranks = false;
+    // --em-leaves-only (src/main.cpp:2053), --write-ocranks (:2115) and the two read-score reports, --write-meta-read-scores-
+    // unfiltered / -filtered (src/main.cpp:1225-1227, 1308-1310), switches of the abundance mode; `em_options`: the ones given, in order
+    bool em_leaves_only = false, write_ocranks = false, read_scores_unfiltered = false, read_scores_filtered = false;
     std::vector<std::string> em_options;
     int64_t top_oc = 1000;
     double em_convergence = 0.00001, em_delta = 0.0, discard = 0.0, dust = 100.0;
@@ -138,6 +139,10 @@ void usage() {
           "      --em-leaves-only       --meta: take the EM's candidates among the sampled genomes only (ids that do not begin with node_, and\n"
           "                             nodes identical to one); the --top-oc ranks are counted among those (a switch)\n"
           "      --write-ocranks        --meta: write <prefix>.overlapCoefficients.tsv, every node's id, overlap coefficient and rank (a switch)\n"
+          "      --write-meta-read-scores-unfiltered / --write-meta-read-scores-filtered   --meta: write <prefix>.read_scores_info.unfiltered.tsv /\n"
+          "                             .filtered.tsv, one line per distinct read that maps: its copies, seedmers, best score over ALL nodes, the\n"
+          "                             number of nodes that reach it, and the input positions of its copies; the filtered file lacks the reads\n"
+          "                             below --discard (switches; one GPU a sample: with --batch also --gpus N)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange (with --batch:\n"
           "                             whole samples dealt instead, nothing exchanged; also for --meta --filter-and-assign)\n"
@@ -230,6 +235,8 @@ Config parse(int argc, char** argv) {
         }
         else if (a == "--em-leaves-only") { c.em_leaves_only = true; c.em_options.push_back(a); }
         else if (a == "--write-ocranks") { c.write_ocranks = true; c.em_options.push_back(a); }
+        else if (a == "--write-meta-read-scores-unfiltered") { c.read_scores_unfiltered = true; c.em_options.push_back(a); }
+        else if (a == "--write-meta-read-scores-filtered") { c.read_scores_filtered = true; c.em_options.push_back(a); }
         else if (a == "--jplace") die("option " + a + " is not accepted: this build writes no jplace output");
         else if (a == "--top-oc") c.top_oc = atoll(v().c_str());
         else if (a == "--em-convergence-threshold") c.em_convergence = atof(v().c_str());
@@ -1011,6 +1018,9 @@ struct MetaRun {
                 (c.mask_options[0] == "--mask-read-ends" ? "takes the value and ignores it" : "never masks"));
         if (!c.em_options.empty() && c.filter_and_assign)
             die("option " + c.em_options[0] + " is not accepted with --filter-and-assign: that mode ranks no candidates and runs no EM");
+        if ((c.read_scores_unfiltered || c.read_scores_filtered) && c.gpus > 1 && c.batch.empty())
+            die(std::string("option ") + (c.read_scores_unfiltered ? "--write-meta-read-scores-unfiltered" : "--write-meta-read-scores-filtered") +
+                " is not accepted with one sample over --gpus " + std::to_string(c.gpus) + ": the reads of a sharded sample have no common numbering; drop --gpus");
         if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
         if (c.mask_reads_rf < 0.0 || c.mask_seeds_rf < 0.0)
             die("--mask-reads-relative-frequency and --mask-seeds-relative-frequency must not be negative");
@@ -1131,6 +1141,11 @@ struct MetaSample {
     // positions of its reads (ascending)
     std::vector<int64_t> fq_read;
     std::vector<std::vector<int64_t>> by_node;
+    // the read-score reports, what score_all_nodes() leaves for the two writers (and `merged`, n_merged)
+    std::vector<uint16_t> rs_max;
+    std::vector<uint32_t> rs_nbest;
+    std::vector<int64_t> rs_seedmers, rs_mult;
+    std::vector<std::vector<int64_t>> rs_copies;
 
     MetaSample(MetaRun& mr, const Config& c_) : c(c_), run(mr.run), amplicons(mr.amplicons), taxonomy(mr.taxonomy) {}
     ~MetaSample() {                              // (a sample that failed inside --align-reads)
@@ -1528,6 +1543,63 @@ struct MetaSample {
         say(c, "meta", path + " (" + std::to_string(oc.size()) + " nodes, " + std::to_string(oc.empty() ? 0 : rank + 1) + " ranks)");
     }
 
+    // ---- the read-score reports of the abundance mode (writeMetaReadScores, src/main.cpp:446-466; the discard loop, :1229-1243).
+    // One line per merged read that maps, by ascending merged index: index, copies, seedmers, best score over ALL nodes, the
+    // number of active nodes that reach it, (filtered file only: OvermaximumTaxonNumber, always 0 in this mode,) the positions of
+    // its copies in the input, ascending and comma-joined.  The filtered file lacks the reads whose best score is below
+    // (int)(seedmers * --discard): the all-node maximum, as in the reference; which reads the EM keeps is pmx_meta_em's matter
+    // (DESIGN.md section 4.3).
+
+    // Leaves: rs_max / rs_nbest / rs_seedmers / rs_mult per merged read and rs_copies, the input positions of every merged read's copies.
+    void score_all_nodes() {
+        pmx_meta* m = run.meta;
+        check(pmx_meta_read_best(run.ctx, m), "scoring the reads against every node");
+        n_merged = pmx_meta_num_reads(m);
+        const size_t n = (size_t)std::max<int64_t>(n_merged, 1);
+        rs_max.resize(n); rs_nbest.resize(n); rs_seedmers.resize(n); rs_mult.resize(n);
+        check(pmx_meta_read_best_get(m, rs_max.data(), rs_nbest.data(), n_merged), "the reads' best scores");
+        check(pmx_meta_read_info(m, rs_seedmers.data(), rs_mult.data(), n_merged), "the reads' seedmers");
+        const int64_t n_raw = pmx_meta_num_raw_reads(m);
+        merged.resize((size_t)std::max<int64_t>(n_raw, 1));
+        check(pmx_meta_raw_to_merged(m, merged.data(), n_raw), "the reads' merged reads");
+        rs_copies.assign((size_t)n_merged, std::vector<int64_t>());
+        for (int64_t r = 0; r < n_raw; ++r)
+            if (merged[(size_t)r] >= 0) rs_copies[(size_t)merged[(size_t)r]].push_back(r);
+    }
+    bool below_discard(int64_t r) const { return (int)rs_max[(size_t)r] < (int)((double)rs_seedmers[(size_t)r] * c.discard); }
+
+    void write_read_scores(bool filtered) const {
+        const std::string path = c.output + (filtered ? ".read_scores_info.filtered.tsv" : ".read_scores_info.unfiltered.tsv");
+        std::ofstream out(path);
+        if (!out.is_open()) die("cannot write " + path);
+        out << "ReadIndex\tNumDuplicates\tTotalScore\tMaxScore\tNumMaxScoreNodes\t" << (filtered ? "OvermaximumTaxonNumber\t" : "") << "RawReadsIndices\n";
+        int64_t n_lines = 0;
+        for (int64_t r = 0; r < n_merged; ++r) {
+            if (rs_max[(size_t)r] == 0 || (filtered && below_discard(r))) continue;
+            const std::vector<int64_t>& copies = rs_copies[(size_t)r];
+            out << r << '\t' << copies.size() << '\t' << rs_seedmers[(size_t)r] << '\t' << rs_max[(size_t)r] << '\t' << rs_nbest[(size_t)r] << '\t';
+            if (filtered) out << "0\t";
+            for (size_t j = 0; j < copies.size(); ++j) out << (j ? "," : "") << copies[j];
+            out << '\n';
+            ++n_lines;
+        }
+        out.close();
+        if (!out) die("cannot write " + path);
+        say(c, "meta", path + " (" + std::to_string(n_lines) + " reads)");
+    }
+
+    // the reference's three tallies over the merged reads (src/main.cpp:1240-1243)
+    void report_read_scores() const {
+        int64_t unmapped = 0, discarded = 0;
+        for (int64_t r = 0; r < n_merged; ++r) {
+            if (rs_max[(size_t)r] == 0) ++unmapped;
+            else if (below_discard(r)) ++discarded;
+        }
+        say(c, "meta", std::to_string(unmapped) + " reads unmapped... ");
+        say(c, "meta", std::to_string(discarded) + " reads discarded due to low parsimony score... ");
+        say(c, "meta", std::to_string(n_merged - unmapped - discarded) + " reads mapped to nodes...");
+    }
+
     // ---- the abundances.  Reads: the merged reads.  Leaves: the candidates scored and the EM's haplotypes in run.meta, on every rank.
     void estimate() {
         pmx_meta* m = run.meta;
@@ -1576,9 +1648,14 @@ void meta_steps(MetaSample& s, bool writer) {
         if (s.c.breadth_ratio) s.write_breadths();
         s.report_assigned();
     } else {
+        const bool read_scores = s.c.read_scores_unfiltered || s.c.read_scores_filtered;   // (one GPU a sample: refuse_options)
         if (writer && s.c.write_ocranks) s.write_ocranks();
+        if (read_scores) s.score_all_nodes();
+        if (s.c.read_scores_unfiltered) s.write_read_scores(false);
+        if (read_scores) s.report_read_scores();
         s.estimate();
         if (writer) s.write_abundance();
+        if (s.c.read_scores_filtered) s.write_read_scores(true);
     }
 }
 

@@ -30,7 +30,7 @@
     X(PLACE_TREE_KERNEL, "ab", "node scoring: the flag-per-node persistent kernel instead of the chains kernel")                               \
     X(PLACE_NO_GRAPH, "ab", "node scoring by levels: plain launches instead of the captured HIP graph")                                        \
     X(PLACE_TEST_STARVED, "test", "node scoring: make the persistent kernel report a starved grid (exercises the level-kernel fall-back)")     \
-    X(META_ASSIGN_CHUNK, "test", "--meta --filter-and-assign: merged reads per chunk of pmx_meta_assign (default: what the bit-matrix budget holds)")           \
+    X(META_ASSIGN_CHUNK, "test", "--meta --filter-and-assign: merged reads per chunk of pmx_meta_assign and pmx_meta_read_best (default: what the bit-matrix budget holds)")           \
     X(META_BREADTH_FLUSH, "test", "--meta --filter-and-assign --breadth-ratio: the weight the bit-sliced counters take before they are expanded (default 2^20 - 1)") \
     X(META_MASK_LONG, "test", "--meta --mask-reads / --mask-seeds: seedmers of a read above which its hashes are counted by the sorted path (default and maximum 1024)") \
     X(ALIGN_NO_COMPACT, "ab", "align: skip the compact tier (every pair through the general tiers)")                                           \

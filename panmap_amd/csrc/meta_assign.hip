@@ -43,6 +43,9 @@
 //   * with a taxonomy, k_meta_assign_near<PLANES> (only with an ambiguity option) and k_meta_assign_taxa: see there;
 //   * k_meta_assign_emit: after an exclusive scan of the node counts, a wave per read expands its set bits into the CSR list
 //     read -> DFS indices, ascending.
+//   * for the read-score reports of the abundance mode (pmx_meta_read_best), instead of all that follows the prefix XOR:
+//     k_meta_active_nodes once per read set and k_meta_read_best<PLANES>, which keeps a read's maximum and the number of
+//     active columns that reach it and stores nothing per word: see there.
 // The merged reads are processed in chunks, each with the rows of ITS distinct seedmers, so that the two bit matrices stay
 // under kAssignMatrixBytes and the per-read word masks under kAssignReadRowBytes; no result depends on the chunking.
 // The host derives the LCA from (first, last) assigned node: in pre-order it is the lowest ancestor a of `first` with
@@ -223,6 +226,65 @@ __global__ void __launch_bounds__(256) k_meta_assign_max(const int64_t* __restri
             }
         }
         if (lane == 0) { out_max[r] = (uint16_t)best; out_count[r] = count; out_first[r] = first; out_last[r] = last; out_state[r] = (uint8_t)state; }
+    }
+}
+
+// ---- The read-score reports of the abundance mode (--write-meta-read-scores-*; scoreReads, src/mgsr.cpp:7325-7420: maxScore and
+// epp of every read over the whole collapsed tree; collapseIdenticalScoringNodes, :794-847).
+// The active nodes of a read set as one row of `words` words: the root, and every node with a change whose hash, in either
+// orientation, is among the distinct seedmers of the whole sample (uniq, ascending).  A thread per change of the oriented
+// index; `active` comes in zeroed.  An inactive node holds none of the reads' seedmers differently from its parent, scores
+// as its nearest active ancestor for every read, and is what the reference folds away before it counts.
+__global__ void k_meta_active_nodes(const uint64_t* __restrict__ ch_key, const uint32_t* __restrict__ ch_node, int64_t n_changes,
+                                    const uint64_t* __restrict__ uniq, int64_t n_uniq, unsigned long long* active) {
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t0 == 0) atomicOr(&active[0], 1ULL);   // the root
+    for (int64_t c = t0; c < n_changes; c += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t key = ch_key[c];
+        if (find_sorted(uniq, n_uniq, key) < 0 && find_sorted(uniq, n_uniq, key ^ PMX_ORIENT_XOR) < 0) continue;
+        const uint32_t v = ch_node[c];
+        atomicOr(&active[v >> 6], 1ULL << (v & 63));
+    }
+}
+
+// a word's maximum x and its active best columns taken into a lane's running (best, cnt)
+__device__ __forceinline__ void best_take(uint32_t x, unsigned long long cols, uint32_t& best, uint32_t& cnt) {
+    const uint32_t c = (uint32_t)__popcll(cols);
+    if (x > best) { best = x; cnt = c; }
+    else if (x == best) cnt += c;
+}
+
+// A wave per merged read of the chunk, a lane per pair of words, the loads and the word maxima of k_meta_assign_max; nothing
+// is stored per word.  out_max: the read's maximum over all columns < N; out_nbest: the ACTIVE columns that reach it (0 when
+// the maximum is 0).  active: one row of `words` words.
+template <int PLANES>
+__global__ void __launch_bounds__(256) k_meta_read_best(const int64_t* __restrict__ read_off, int64_t seed_base, const uint32_t* __restrict__ seed_uid,
+                                                       const uint8_t* __restrict__ seed_rev, int64_t n_reads, const unsigned long long* __restrict__ mask_fwd,
+                                                       const unsigned long long* __restrict__ mask_rev, int words, int64_t n_nodes,
+                                                       const unsigned long long* __restrict__ active, uint16_t* out_max, uint32_t* out_nbest) {
+    const int lane = threadIdx.x & 63;
+    const int pairs = words >> 1;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = wave; r < n_reads; r += n_waves) {
+        const int64_t i0 = read_off[r], i1 = read_off[r + 1];
+        uint32_t best = 0, cnt = 0;
+        for (int q = lane; q < pairs; q += 64) {
+            unsigned long long same0[PLANES], other0[PLANES], same1[PLANES], other1[PLANES];
+            read_planes<PLANES>(mask_fwd, mask_rev, seed_uid, seed_rev, i0, i1, seed_base, words, q, same0, other0, same1, other1);
+            const unsigned long long v0 = valid_columns(n_nodes, (int64_t)q * 128), v1 = valid_columns(n_nodes, (int64_t)q * 128 + 64);
+            const ulonglong2 act = *reinterpret_cast<const ulonglong2*>(active + 2 * q);
+            unsigned long long m0, m1;
+            uint32_t x0, x1;
+            word_max<PLANES>(same0, other0, v0, &m0, &x0);
+            word_max<PLANES>(same1, other1, v1, &m1, &x1);
+            best_take(x0, m0 & act.x, best, cnt);
+            best_take(x1, m1 & act.y, best, cnt);
+        }
+        uint32_t top = best;
+        for (int o = 32; o > 0; o >>= 1) top = max(top, (uint32_t)__shfl_xor((int)top, o));
+        if (best != top || top == 0) cnt = 0;
+        for (int o = 32; o > 0; o >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, o);
+        if (lane == 0) { out_max[r] = (uint16_t)top; out_nbest[r] = cnt; }
     }
 }
 
@@ -619,16 +681,13 @@ struct AssignStage {
     int breadth_rows_per_block(int64_t n_rows) const;
 };
 
-// Chunks of consecutive merged reads whose distinct seedmers fit kAssignMatrixBytes and whose word masks fit
-// kAssignReadRowBytes (a read that alone exceeds them is a chunk of its own); PMX_META_ASSIGN_CHUNK forces a size in reads.
-void AssignStage::plan_chunks() {
-    const int64_t cap_rows = std::max<int64_t>(1, (int64_t)(kAssignMatrixBytes / ((touch ? 24 : 16) * (size_t)words)));
-    int64_t cap_reads = std::max<int64_t>(1, (int64_t)(kAssignReadRowBytes / ((near ? 18 : 10) * (size_t)words)));
-    if (const char* f = opt_str(O_META_ASSIGN_CHUNK)) cap_reads = std::max<int64_t>(1, atoll(f));
+// Chunks of consecutive merged reads whose distinct seedmers number at most cap_rows, at most cap_reads reads each (a read that
+// alone exceeds them is a chunk of its own): the first merged read of every chunk, then n_reads.
+std::vector<int64_t> plan_read_chunks(const pmx_meta* m, int64_t cap_rows, int64_t cap_reads) {
     std::vector<int64_t> seen(m->h_uniq.size(), -1);   // the chunk (by its first read) that last counted the seedmer
-    chunk_first.assign(1, 0);
+    std::vector<int64_t> chunk_first(1, 0);
     int64_t r0 = 0, rows = 0;
-    for (int64_t r = 0; r < n_reads; ++r) {
+    for (int64_t r = 0; r < m->n_reads; ++r) {
         int64_t fresh = 0;
         for (int64_t i = m->h_read_off[(size_t)r]; i < m->h_read_off[(size_t)r + 1]; ++i) fresh += seen[m->h_seed_uid[(size_t)i]] != r0;
         if (r > r0 && (r - r0 >= cap_reads || rows + fresh > cap_rows)) {
@@ -641,7 +700,37 @@ void AssignStage::plan_chunks() {
             if (s != r0) { s = r0; ++rows; }
         }
     }
-    chunk_first.push_back(n_reads);
+    chunk_first.push_back(m->n_reads);
+    return chunk_first;
+}
+
+// Chunks whose distinct seedmers fit kAssignMatrixBytes and whose word masks fit kAssignReadRowBytes; PMX_META_ASSIGN_CHUNK
+// forces a size in reads.
+void AssignStage::plan_chunks() {
+    const int64_t cap_rows = std::max<int64_t>(1, (int64_t)(kAssignMatrixBytes / ((touch ? 24 : 16) * (size_t)words)));
+    int64_t cap_reads = std::max<int64_t>(1, (int64_t)(kAssignReadRowBytes / ((near ? 18 : 10) * (size_t)words)));
+    if (const char* f = opt_str(O_META_ASSIGN_CHUNK)) cap_reads = std::max<int64_t>(1, atoll(f));
+    chunk_first = plan_read_chunks(m, cap_rows, cap_reads);
+}
+
+// The rows of a chunk, merged reads [r0, r1): its distinct seedmers as indices into h_uniq (ids, ascending, as h_uniq is) and
+// as hashes (uniq), and every seedmer of those reads as its row (uid).
+struct ChunkRows {
+    std::vector<uint32_t> ids, uid;
+    std::vector<uint64_t> uniq;
+};
+ChunkRows chunk_rows(const pmx_meta* m, int64_t r0, int64_t r1) {
+    const int64_t s0 = m->h_read_off[(size_t)r0], s1 = m->h_read_off[(size_t)r1];
+    ChunkRows C;
+    C.ids.assign(m->h_seed_uid.begin() + s0, m->h_seed_uid.begin() + s1);
+    std::sort(C.ids.begin(), C.ids.end());
+    C.ids.erase(std::unique(C.ids.begin(), C.ids.end()), C.ids.end());
+    C.uniq.resize(C.ids.size());
+    for (size_t i = 0; i < C.ids.size(); ++i) C.uniq[i] = m->h_uniq[C.ids[i]];
+    C.uid.resize((size_t)(s1 - s0));
+    for (int64_t i = s0; i < s1; ++i)
+        C.uid[(size_t)(i - s0)] = (uint32_t)(std::lower_bound(C.ids.begin(), C.ids.end(), m->h_seed_uid[(size_t)i]) - C.ids.begin());
+    return C;
 }
 
 // Leaves: the per-read device buffers of the call (d_tax and d_count zeroed: a read fills its first ids only, the scans read
@@ -670,16 +759,12 @@ void AssignStage::begin() {
 // With a taxonomy the reads spanning too many taxa become PMX_META_OVER_TAXA before the scan (d_ntax, d_tax: the others' taxa).
 // Leaves: d_max .. d_state of the reads, m->as_off (r0, r1] and m->as_nodes grown by the chunk's lists.
 void AssignStage::run_chunk(int64_t r0, int64_t r1) {
-    const int64_t n = r1 - r0, s0 = m->h_read_off[(size_t)r0], s1 = m->h_read_off[(size_t)r1];
-    // the chunk's distinct seedmers (ascending, as h_uniq is) and every seedmer as its row
-    std::vector<uint32_t> ids(m->h_seed_uid.begin() + s0, m->h_seed_uid.begin() + s1);
-    std::sort(ids.begin(), ids.end());
-    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const int64_t n = r1 - r0, s0 = m->h_read_off[(size_t)r0];
+    const ChunkRows C = chunk_rows(m, r0, r1);
+    const std::vector<uint32_t>& ids = C.ids;
+    const std::vector<uint32_t>& uid = C.uid;
+    const std::vector<uint64_t>& uniq = C.uniq;
     const int64_t n_rows = (int64_t)ids.size();
-    std::vector<uint64_t> uniq((size_t)n_rows);
-    for (int64_t i = 0; i < n_rows; ++i) uniq[(size_t)i] = m->h_uniq[ids[(size_t)i]];
-    std::vector<uint32_t> uid((size_t)(s1 - s0));
-    for (int64_t i = s0; i < s1; ++i) uid[(size_t)(i - s0)] = (uint32_t)(std::lower_bound(ids.begin(), ids.end(), m->h_seed_uid[(size_t)i]) - ids.begin());
     const size_t mat = (size_t)n_rows * (size_t)words;
     d_uniq.ensure((size_t)n_rows); d_uid.ensure(uid.size()); d_fwd.ensure(mat); d_rev.ensure(mat);
     d_wmask.ensure((size_t)n * (size_t)words); d_wmax.ensure((size_t)n * (size_t)words); d_off.ensure((size_t)n + 1);
@@ -872,6 +957,65 @@ void reset_assign_results(pmx_ctx* ctx, pmx_meta* m) {
     timer_cancel(ctx, "meta_breadth");
     timer_cancel(ctx, "meta_breadth_count");
 }
+
+// One call of pmx_meta_read_best: the chunks of AssignStage without its word masks (nothing is kept per read and word, so
+// kAssignReadRowBytes does not bound a chunk), per chunk the two matrices and k_meta_read_best.
+struct BestStage {
+    pmx_ctx* const ctx;
+    pmx_meta* const m;
+    const hipStream_t st;
+    const int words;
+    DevBuf<uint16_t> d_max;
+    DevBuf<uint32_t> d_nbest, d_uid;
+    DevBuf<uint64_t> d_uniq;
+    DevBuf<unsigned long long> d_fwd, d_rev;
+
+    BestStage(pmx_ctx* c, pmx_meta* mm) : ctx(c), m(mm), st(c->stream), words(assign_words(mm->n_nodes)) {}
+    void active_nodes();
+    void run_chunk(int64_t r0, int64_t r1);
+};
+
+// Leaves: m->d_active and m->h_active for the reads of the last set_reads (built by the first call after it).
+void BestStage::active_nodes() {
+    if (m->active_built) return;
+    m->d_active.ensure((size_t)words);
+    std::vector<unsigned long long> row((size_t)words);
+    timer_begin(ctx, "meta_read_best");
+    PMX_ZERO(m->d_active, (size_t)words, st);
+    PMX_LAUNCH(k_meta_active_nodes, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->ch_key.p, m->ch_node.p, m->n_changes, m->d_uniq.p,
+               (int64_t)m->h_uniq.size(), m->d_active.p);
+    timer_end(ctx, "meta_read_best", 1);
+    PMX_D2H_SYNC(row, m->d_active, (size_t)words, st);
+    timer_sum_add(ctx, "meta_read_best");
+    m->h_active.resize((size_t)m->n_nodes);
+    for (int64_t v = 0; v < m->n_nodes; ++v) m->h_active[(size_t)v] = (uint8_t)((row[(size_t)v >> 6] >> (v & 63)) & 1ULL);
+    m->active_built = true;
+}
+
+// Merged reads [r0, r1): their distinct seedmers' rows, then d_max / d_nbest of the reads.
+void BestStage::run_chunk(int64_t r0, int64_t r1) {
+    const int64_t n = r1 - r0, s0 = m->h_read_off[(size_t)r0];
+    const ChunkRows C = chunk_rows(m, r0, r1);
+    const int64_t n_rows = (int64_t)C.ids.size();
+    const size_t mat = (size_t)n_rows * (size_t)words;
+    d_uniq.ensure((size_t)n_rows); d_uid.ensure(C.uid.size()); d_fwd.ensure(mat); d_rev.ensure(mat);
+    PMX_H2D(d_uniq, C.uniq, n_rows, st);
+    PMX_H2D(d_uid, C.uid, st);
+    timer_begin(ctx, "meta_read_best");
+    PMX_ZERO(d_fwd, mat, st);
+    PMX_ZERO(d_rev, mat, st);
+    if (m->n_changes > 0)
+        PMX_LAUNCH(k_assign_mark_ends, dim3(grid_for(m->n_changes, 256, ctx->n_cu * 8)), dim3(256), 0, st, m->ch_key.p, m->ch_pc.p, m->ch_cc.p,
+                   m->ch_node.p, m->n_changes, m->subtree_end.p, m->n_nodes, d_uniq.p, n_rows, words, d_fwd.p, d_rev.p, nullptr);
+    PMX_LAUNCH(k_assign_prefix_xor, dim3(grid_for(2 * n_rows * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words);
+    meta_with_planes(m->longest, [&](auto planes) {
+        PMX_LAUNCH(k_meta_read_best<decltype(planes)::value>, dim3(grid_for(n * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, m->d_read_off.p + r0, s0, d_uid.p,
+                   m->d_seed_rev.p, n, d_fwd.p, d_rev.p, words, m->n_nodes, m->d_active.p, d_max.p + r0, d_nbest.p + r0);
+    });
+    timer_end(ctx, "meta_read_best", 1);
+    PMX_HIP(hipStreamSynchronize(st));   // (the chunk's host lists go out of scope)
+    timer_sum_add(ctx, "meta_read_best");
+}
 }  // namespace
 
 extern "C" {
@@ -916,6 +1060,50 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     m->as_breadth = m->breadth_on;
     return PMX_OK;
     PMX_CATCH
+}
+
+int pmx_meta_read_best(pmx_ctx* ctx, pmx_meta* m) {
+    if (!ctx || !m) return PMX_ERR_ARG;
+    if (m->dist) return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_read_best runs on one GPU: not with an attached dist (no raw -> merged map of a sharded sample)");
+    if (!m->reads_set) return fail(PMX_ERR_ARG, "pmx_meta_read_best: call pmx_meta_set_reads first");
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    m->best_done = false;
+    const int rc = meta_longest_read(m);
+    if (rc != PMX_OK) return rc;
+    BestStage S(ctx, m);
+    const size_t n = (size_t)m->n_reads;
+    timer_sum_reset(ctx, "meta_read_best");
+    timer_cancel(ctx, "meta_read_best");   // (no span when nothing below runs: the active nodes are built, no reads)
+    S.active_nodes();
+    m->rb_max.assign(n, 0);
+    m->rb_nbest.assign(n, 0);
+    if (n > 0) {
+        S.d_max.alloc(n); S.d_nbest.alloc(n);
+        const int64_t cap_rows = std::max<int64_t>(1, (int64_t)(kAssignMatrixBytes / (16 * (size_t)S.words)));
+        int64_t cap_reads = INT64_MAX;
+        if (const char* f = opt_str(O_META_ASSIGN_CHUNK)) cap_reads = std::max<int64_t>(1, atoll(f));
+        const std::vector<int64_t> chunk_first = plan_read_chunks(m, cap_rows, cap_reads);
+        for (size_t c = 0; c + 1 < chunk_first.size(); ++c) S.run_chunk(chunk_first[c], chunk_first[c + 1]);
+        PMX_D2H(m->rb_max, S.d_max, n, S.st);
+        PMX_D2H_SYNC(m->rb_nbest, S.d_nbest, n, S.st);
+    }
+    m->best_done = true;
+    return PMX_OK;
+    PMX_CATCH
+}
+
+int pmx_meta_read_best_get(const pmx_meta* m, uint16_t* max_score, uint32_t* n_best, int64_t cap) {
+    if (!m || !m->best_done || cap < m->n_reads) return PMX_ERR_ARG;
+    if (max_score) std::copy(m->rb_max.begin(), m->rb_max.end(), max_score);
+    if (n_best) std::copy(m->rb_nbest.begin(), m->rb_nbest.end(), n_best);
+    return PMX_OK;
+}
+
+int pmx_meta_active_nodes(const pmx_meta* m, uint8_t* active, int64_t cap_nodes) {
+    if (!m || !m->active_built || !active || cap_nodes < m->n_nodes) return PMX_ERR_ARG;
+    std::copy(m->h_active.begin(), m->h_active.end(), active);
+    return PMX_OK;
 }
 
 int pmx_meta_set_breadth(pmx_meta* m, int on) {

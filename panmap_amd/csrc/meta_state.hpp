@@ -104,6 +104,14 @@ struct pmx_meta {
     // br_observed / br_depth of the last pmx_meta_assign when as_breadth
     bool breadth_on = false, as_breadth = false;
     std::vector<uint64_t> total_ref_seeds, br_observed, br_depth;
+    // pmx_meta_read_best (meta_assign.hip): per merged read its best score over ALL nodes and the number of ACTIVE nodes that
+    // reach it; the active nodes of the read set as a row of assign_words(n_nodes) words, on the device and one byte a node on
+    // the host (built by the first call after a set_reads).  All emptied by set_reads
+    bool best_done = false, active_built = false;
+    std::vector<uint16_t> rb_max;
+    std::vector<uint32_t> rb_nbest;
+    pmx::DevBuf<unsigned long long> d_active;
+    std::vector<uint8_t> h_active;
     // low-coverage masks (pmx_meta_set_masks; meta_mask.hip; src/mgsr.cpp:2049-2139): the thresholds the next set_reads applies
     // (at most one above 0), and of the last set_reads: whether it masked, the reference's three numbers, the distinct hashes
     // of the merged reads BEFORE masking (ascending) with their occurrence counts, and on the device the counts of the

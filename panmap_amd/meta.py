@@ -246,6 +246,23 @@ class Meta:
             numbers = tuple(x.astype(np.int64) for x in u)
         return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads(), read_taxa, node_sets, numbers)
 
+    def read_best(self):
+        """per merged read of the last set_reads: (max, n_best), its best score over ALL nodes and the number of active
+        nodes (active_nodes) that reach it, 0 where max is 0 (pmx_meta_read_best; the numbers of the abundance mode's
+        read-score reports).  Runs on masked reads too; needs no score()."""
+        check(lib.pmx_meta_read_best(self.ctx._h, self._h), "pmx_meta_read_best")
+        n = self.n_reads
+        mx, nb = np.zeros(n, np.uint16), np.zeros(n, np.uint32)
+        check(lib.pmx_meta_read_best_get(self._h, mx.ctypes.data, nb.ctypes.data, n), "pmx_meta_read_best_get")
+        return mx, nb
+
+    def active_nodes(self) -> np.ndarray:
+        """one flag per DFS index: the root and the nodes with a change whose hash the merged reads carry, as built by the
+        last read_best()"""
+        out = np.zeros(self.index_oriented.info.n_nodes, np.uint8)
+        check(lib.pmx_meta_active_nodes(self._h, out.ctypes.data, len(out)), "pmx_meta_active_nodes")
+        return out.astype(bool)
+
     def raw_to_merged(self) -> np.ndarray:
         """per read of the last set_reads (input order): its merged read, -1 when --dust dropped it or it has no seedmers"""
         out = np.zeros(int(lib.pmx_meta_num_raw_reads(self._h)), np.int64)

@@ -9,6 +9,10 @@ calls, each run twice: without a taxonomy, with it, and with it and --ambiguous-
 the taxonomy pass (its kernels and the scan of the node counts, which "meta_assign" holds without a taxonomy).
 With `breadth` as the last argument instead: --breadth-ratio.  Two calls, each run twice: without breadth and with it; "meta_breadth" is
 the breadth pass (k_meta_breadth_rows per chunk and k_meta_breadth_count once), hit_matrix_bytes the matrix it keeps across the chunks.
+With `best` as the last argument instead: the all-node pass of the read-score reports, pmx_meta_read_best, beside its yardstick
+pmx_meta_assign on the same reads.  Three rounds, each two calls of assign and two of read_best; of every round the second call's
+span ("meta_assign", "meta_read_best") and wall time; the three observations and their median.  A library without
+pmx_meta_read_best (PMX_LIB_PATH pointing at an earlier build) gives the yardstick alone.
   meta_assign_timing.py rsv  [n_reads]   rsv_4K, reads at step 1 over two of its genomes (default 20,000)
   meta_assign_timing.py sars [n_reads]   SARS-CoV-2 20k tree, the 5-haplotype mixture of test_config5_sars_five_haplotypes (default 200,000)"""
 import json
@@ -84,11 +88,38 @@ def breadth_mode(meta, ms, out):
     out["nodes_with_hits"], out["observed_sum"], out["depth_sum"] = int((observed > 0).sum()), int(observed.sum()), int(depth.sum())
 
 
+def best_mode(pmx, meta, ms, out):
+    have = "pmx_meta_read_best" not in pmx._lib.MISSING
+    seen = dict(assign_ms=[], assign_wall_s=[], read_best_ms=[], read_best_wall_s=[])
+    for rnd in range(3):
+        for rep in range(2):
+            t0 = time.perf_counter()
+            res = meta.assign(0.0)
+            wall, span = time.perf_counter() - t0, ms("meta_assign")
+        seen["assign_ms"].append(span)
+        seen["assign_wall_s"].append(wall)
+        for rep in range(2 if have else 0):
+            t0 = time.perf_counter()
+            mx, nb = meta.read_best()
+            wall, span = time.perf_counter() - t0, ms("meta_read_best")
+        if have:
+            seen["read_best_ms"].append(span)
+            seen["read_best_wall_s"].append(wall)
+    for name, obs in seen.items():
+        if obs:
+            out[name], out[name + "_median"] = obs, float(np.median(obs))
+    if have:
+        merged_max = np.zeros(meta.n_reads, np.int64)
+        merged_max[res.merged[res.merged >= 0]] = res.max[res.merged >= 0]
+        out["max_equal"] = bool(np.array_equal(mx.astype(np.int64), merged_max))
+        out["mapped_reads"], out["n_best_sum"], out["active_nodes"] = int((mx > 0).sum()), int(nb.sum()), int(meta.active_nodes().sum())
+
+
 def main():
     import panmap_amd as pmx
     from panmap_amd._lib import lib
-    taxonomy, breadth = sys.argv[-1] == "taxonomy", sys.argv[-1] == "breadth"
-    if taxonomy or breadth:
+    taxonomy, breadth, best = sys.argv[-1] == "taxonomy", sys.argv[-1] == "breadth", sys.argv[-1] == "best"
+    if taxonomy or breadth or best:
         sys.argv.pop()
     which = sys.argv[1] if len(sys.argv) > 1 else "rsv"
     n = int(sys.argv[2]) if len(sys.argv) > 2 else (20000 if which == "rsv" else 200000)
@@ -104,8 +135,8 @@ def main():
     words = ((n_nodes + 63) // 64 + 1) & ~1
     out["distinct_seedmers"] = int(len(np.unique(h)))
     out["bit_matrix_bytes"] = 2 * out["distinct_seedmers"] * words * 8     # (of all reads: split over chunks of at most 2 GiB)
-    if taxonomy or breadth:
-        taxonomy_mode(meta, ms, out) if taxonomy else breadth_mode(meta, ms, out)
+    if taxonomy or breadth or best:
+        taxonomy_mode(meta, ms, out) if taxonomy else breadth_mode(meta, ms, out) if breadth else best_mode(pmx, meta, ms, out)
         print(json.dumps(out))
         return
     for rep in range(2):
