@@ -114,6 +114,8 @@ const int16_t *pmx_index_child_counts(const pmx_index *idx);  /* n_changes */
  * ------------------------------------------------------------------------------------------ */
 typedef struct pmx_ctx pmx_ctx;
 int pmx_ctx_create(int device_ordinal, pmx_ctx **out);
+/* the HIP devices this process can open (0: none).  It initialises the runtime: a process that forks ranks asks in a child. */
+int pmx_device_count(void);
 void pmx_ctx_destroy(pmx_ctx *ctx);
 int pmx_ctx_synchronize(pmx_ctx *ctx);
 /* the HIP stream all kernels of this context are launched on (hipStream_t as void*).  Every context owns a hardware queue
@@ -717,7 +719,26 @@ int32_t pmx_amplicons_lookup(const pmx_amplicons *a, const char *read_name);
  * From then on set_reads, score and em are COLLECTIVE: every rank calls them in the same order, set_reads with its own shard of
  * the raw reads.  The merged reads, overlap coefficients, candidates, haplotypes and em_info are then those of one rank over the
  * whole sample, bit for bit, on every rank.  pmx_meta_scores returns only this rank's rows: merged reads [first, first + count)
- * (pmx_meta_row_range; without a dist: 0 and num_reads). */
+ * (pmx_meta_row_range; without a dist: 0 and num_reads).
+ * pmx_meta_assign and pmx_meta_read_best are collective too, for a dist of two ranks or more (a dist of ONE rank stays
+ * PMX_ERR_UNSUPPORTED for both, as every dist was before: one GPU runs them without a dist): each sets the row range by the rule of pmx_meta_score (it is 0
+ * rows between set_reads and the first of the three) and works on its rank's rows only.  Their per-read getters
+ * (pmx_meta_assign_reads / _nodes / _taxa, pmx_meta_assign_num_nodes, pmx_meta_read_best_get) then report this rank's rows, index
+ * 0 = `first`, cap >= count; pmx_meta_breadth and pmx_meta_active_nodes are the whole sample's on every rank.  The rules that
+ * keep these collectives from hanging (csrc/meta_assign.hip has them in full): every refusal follows from settings that are the
+ * same on every rank; pmx_meta_assign begins by exchanging a digest of its settings (discard, breadth on / off, max_taxa, the
+ * ambiguity pair, a hash of the taxonomy's node table) and ranks that disagree ALL return PMX_ERR_ARG before any other exchange;
+ * no exchange depends on a rank's own number of rows or chunks, and a rank with an empty shard or no rows takes part in all.
+ * pmx_meta_assign_gather / pmx_meta_read_best_gather (collective; PMX_ERR_ARG without a dist, before the matching compute call,
+ * or a second time after it): every rank's rows to `root`, whose getters then cover all pmx_meta_num_reads merged reads and equal
+ * one rank's over the whole sample bit for bit (the CSR offsets rebased, the node lists in row order); the other ranks keep
+ * their rows.  pmx_meta_row_range stays the rank's own on every rank.  No run on more than one physical GPU exists: the tests
+ * run the ranks as processes on one device. */
+int pmx_meta_assign_gather(pmx_ctx *ctx, pmx_meta *m, int root);
+/* rows of the breadth hit matrix per exchange of its merge over the ranks (0 = default: what a 1 GiB buffer of world x slab holds);
+ * the same value on every rank; the tests force slab edges with it.  rows < 0: PMX_ERR_ARG */
+int pmx_meta_set_breadth_slab(pmx_meta *m, int64_t rows);
+int pmx_meta_read_best_gather(pmx_ctx *ctx, pmx_meta *m, int root);
 int pmx_meta_attach_dist(pmx_meta *m, pmx_dist *d);
 int pmx_meta_row_range(const pmx_meta *m, int64_t *first, int64_t *count);
 double pmx_read_dust(const char *seq, int64_t len, int32_t window);
@@ -728,7 +749,7 @@ double pmx_read_dust(const char *seq, int64_t len, int32_t window);
  * n its seedmers (pmx_meta_read_info): max == 0 -> PMX_META_UNMAPPED; 0 < max < (int32)(discard * n) -> PMX_META_DISCARDED
  * (the cast truncates, src/mgsr.cpp:1693); else PMX_META_ASSIGNED, and the read's nodes are ALL nodes with score == max, its LCA
  * node their lowest common ancestor (UINT32_MAX for a read that is not assigned).  Nodes are DFS indices; identical nodes are
- * NOT folded here (pmx_index_node_heads folds at output time).  One GPU: PMX_ERR_UNSUPPORTED with an attached dist.
+ * NOT folded here (pmx_index_node_heads folds at output time).  With an attached dist: collective, see pmx_meta_attach_dist.
  * With a taxonomy (pmx_meta_set_taxonomy, below) an assigned read whose best-scoring or near-best-scoring nodes span more than
  * max_taxa taxa becomes PMX_META_OVER_TAXA instead: no nodes, no LCA.  PMX_ERR_UNSUPPORTED then for discard > 0 together with
  * a non-zero ambiguity threshold.  Without a taxonomy nothing of it runs.
@@ -795,8 +816,8 @@ int pmx_meta_breadth(const pmx_meta *m, uint64_t *total_ref_seeds, uint64_t *obs
  * either orientation, among the distinct seedmer hashes of the merged reads (after --dust and the masks): the nodes the
  * reference keeps when it collapses the tree for a sample.  An inactive node scores as its nearest active ancestor, so the
  * maximum is the same over either set.  It needs no pmx_meta_score, builds no read -> node list, and runs on reads set with a
- * mask, with amplicons or with masked ends.  PMX_ERR_ARG before pmx_meta_set_reads; PMX_ERR_UNSUPPORTED with an attached dist
- * (a sharded sample has no raw -> merged map to report against).  What pmx_meta_assign left on the handle stays, and the other
+ * mask, with amplicons or with masked ends.  PMX_ERR_ARG before pmx_meta_set_reads; with an attached dist it is collective
+ * (pmx_meta_attach_dist).  What pmx_meta_assign left on the handle stays, and the other
  * way round; pmx_meta_set_reads empties all of it.
  * pmx_meta_read_best_get: per merged read (cap >= pmx_meta_num_reads; either pointer may be NULL); pmx_meta_active_nodes: one
  * byte per DFS index, 1 = active (cap_nodes >= the index's nodes).  Both PMX_ERR_ARG until pmx_meta_read_best has run since the
@@ -804,8 +825,10 @@ int pmx_meta_breadth(const pmx_meta *m, uint64_t *total_ref_seeds, uint64_t *obs
 int pmx_meta_read_best(pmx_ctx *ctx, pmx_meta *m);
 int pmx_meta_read_best_get(const pmx_meta *m, uint16_t *max_score, uint32_t *n_best, int64_t cap);
 int pmx_meta_active_nodes(const pmx_meta *m, uint8_t *active, int64_t cap_nodes);
-/* the reads of the last pmx_meta_set_reads in input order -> their merged read, -1 for a read dropped by --dust or without
- * seedmers (PMX_ERR_UNSUPPORTED with an attached dist: the merged reads are then the whole sample's) */
+/* the reads of the last pmx_meta_set_reads in input order -> their merged read, -1 for a read dropped by --dust, without
+ * seedmers or dropped by a low-coverage mask.  With an attached dist: pmx_meta_num_raw_reads is the shard's raw count and the
+ * map names, for this rank's raw reads in shard order, their merged read in the WHOLE sample's numbering -- the slice of the
+ * one-rank map that the shard covers */
 int64_t pmx_meta_num_raw_reads(const pmx_meta *m);
 int pmx_meta_raw_to_merged(const pmx_meta *m, int64_t *map, int64_t cap);
 /* Host only, no device.  head[v] of an ORIENTED index: v itself when v is the root or carries changes, else the nearest
@@ -966,7 +989,8 @@ int64_t pmx_options_describe(char *buf, int64_t cap);
    pmx_meta_score; "meta_assign" = the device work of pmx_meta_assign up to the scan of the node counts, "meta_assign_emit" = its
    list kernel, both summed over the call's chunks; with a taxonomy "meta_assign" ends before the taxonomy kernels and
    "meta_assign_taxa" holds them and that scan; with pmx_meta_set_breadth "meta_breadth" = the breadth kernels, summed likewise, and "meta_breadth_count" = the column
-   count kernel among them; "meta_read_best" = the device work of pmx_meta_read_best, summed over its chunks; "meta_mask" = the mask step of pmx_meta_set_reads, and with amplicons "meta_mask_sort" = the sort
+   count kernel among them, and with an attached dist "meta_breadth_merge" = the kernels that OR the ranks' hit matrices into the local one, summed over
+   the slabs of the exchange (the exchange itself is not in it); "meta_read_best" = the device work of pmx_meta_read_best, summed over its chunks; "meta_mask" = the mask step of pmx_meta_set_reads, and with amplicons "meta_mask_sort" = the sort
    of its (amplicon, hash) keys inside it); < 0: no such span in the last call */
 double pmx_last_kernel_ms(pmx_ctx *ctx, const char *name);
 

@@ -123,6 +123,7 @@ SIGNATURES = {
     "pmx_index_parent_counts": (_vp, [_vp]),
     "pmx_index_child_counts": (_vp, [_vp]),
     "pmx_ctx_create": (_i32, [_i32, _PP]),
+    "pmx_device_count": (_i32, []),
     "pmx_ctx_destroy": (None, [_vp]),
     "pmx_ctx_synchronize": (_i32, [_vp]),
     "pmx_ctx_stream": (_vp, [_vp]),
@@ -254,6 +255,9 @@ SIGNATURES = {
     "pmx_meta_read_best": (_i32, [_vp, _vp]),
     "pmx_meta_read_best_get": (_i32, [_vp, _vp, _vp, _i64]),
     "pmx_meta_active_nodes": (_i32, [_vp, _vp, _i64]),
+    "pmx_meta_assign_gather": (_i32, [_vp, _vp, _i32]),
+    "pmx_meta_set_breadth_slab": (_i32, [_vp, _i64]),
+    "pmx_meta_read_best_gather": (_i32, [_vp, _vp, _i32]),
     "pmx_meta_num_raw_reads": (_i64, [_vp]),
     "pmx_meta_raw_to_merged": (_i32, [_vp, _vp, _i64]),
     "pmx_index_node_heads": (_i32, [_vp, _vp]),

@@ -218,6 +218,10 @@ void dist_all_gather(pmx_dist* d, const void* d_mine, size_t bytes, void* d_all)
     PMX_HIP(hipSetDevice(d->ctx->device));
     d->tp->all_gather(d->ctx->stream, d_mine, bytes, d_all);
 }
+void dist_gather_v(pmx_dist* d, const void* d_mine, const std::vector<size_t>& sizes, const std::vector<size_t>& offs, void* d_all, int root) {
+    PMX_HIP(hipSetDevice(d->ctx->device));
+    d->tp->gather_v(d->ctx->stream, d_mine, sizes, offs, d_all, root);
+}
 std::vector<int64_t> dist_exchange_counts(pmx_dist* d, const int64_t* mine, int k) {
     PMX_HIP(hipSetDevice(d->ctx->device));
     return d->exchange_counts(mine, k);

@@ -383,8 +383,9 @@ int cmp_lists(const uint64_t* xh, const uint8_t* xv, int64_t xn, const uint64_t*
 
 // --gpus N: every rank's merged run (sorted, distinct lists with multiplicities) to every rank -- the counts first, then one
 // max-padded all-gather of the bytes -- and a k-way merge into the whole sample's run, multiplicities added.  Equal to what
-// one rank makes of all the reads: a sort of the union with equal lists merged.
-void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int k) {
+// one rank makes of all the reads: a sort of the union with equal lists merged.  to_whole: for every merged read of THIS rank's
+// run (before the merge) the index of the whole sample's merged read that took it.
+void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int k, std::vector<int64_t>& to_whole) {
     pmx_ctx* ctx = m->ctx;
     const int world = (int)(counts.size() / (size_t)k);
     const bool amps = m->amp_on;   // (the same on every rank: merge_over_ranks checked); then the amplicon of every read ends the run
@@ -394,6 +395,8 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
     for (int r = 0; r < world; ++r) mx = std::max(mx, run_bytes(counts[(size_t)r * k + 3], counts[(size_t)r * k + 4]));
     // this rank's run: lengths, multiplicities (int64), hashes (uint64), orientations (bytes)
     const int64_t nr = m->n_reads, ns = m->n_seedmers;
+    const int rank = pmx_dist_rank(m->dist);
+    to_whole.assign((size_t)nr, -1);
     std::vector<char> mine(mx, 0);
     for (int64_t i = 0; i < nr; ++i) {
         const int64_t len = m->h_read_off[(size_t)i + 1] - m->h_read_off[(size_t)i];
@@ -443,6 +446,7 @@ void merge_runs_over_ranks(pmx_meta* m, const std::vector<int64_t>& counts, int 
             Run& x = runs[r];
             if (x.i < x.n && (r == lo || cmp_heads(x, head) == 0)) {
                 mult += x.mult[x.i];
+                if (r == rank) to_whole[(size_t)x.i] = (int64_t)m->h_mult.size();   // (the merged read made by this turn of the loop)
                 x.at += x.len[x.i];
                 ++x.i;
             }
@@ -723,9 +727,12 @@ int MetaReads::merge_over_ranks() {
         for (size_t r = 0; r < world; ++r)
             for (int32_t g = 0; g < m->n_amp; ++g) m->amp_raw[(size_t)g] += raw[r * (size_t)m->n_amp + (size_t)g];
     }
-    merge_runs_over_ranks(m, counts, k);
+    std::vector<int64_t> to_whole;
+    merge_runs_over_ranks(m, counts, k, to_whole);
     amplicon_tallies();
-    m->h_raw_to_merged.clear();   // (the merged reads are the whole sample's now: this rank's map no longer names them)
+    // (the merged reads are the whole sample's now: this rank's raw reads, in shard order, name them through the merge)
+    for (int64_t& to : m->h_raw_to_merged)
+        if (to >= 0) to = to_whole[(size_t)to];
     return PMX_OK;
 }
 
@@ -821,16 +828,6 @@ bool select_candidates(const std::vector<double>& oc, int64_t n_nodes, int64_t t
     return true;
 }
 
-// this rank's rows of the score matrix: all merged reads, or (--gpus N, pass A) a balanced contiguous slice of them
-void own_row_slice(pmx_meta* m) {
-    m->row_first = 0;
-    m->row_count = m->n_reads;
-    if (m->dist) {
-        const int64_t rank = pmx_dist_rank(m->dist), world = pmx_dist_world(m->dist);
-        m->row_first = m->n_reads * rank / world;
-        m->row_count = m->n_reads * (rank + 1) / world - m->row_first;
-    }
-}
 
 // Reads: m->cand, the oriented index, m->d_uniq.  Leaves: m->d_cand and the two (seedmer x candidate) bit matrices,
 // enqueued on the context's stream.
@@ -1308,7 +1305,7 @@ int pmx_meta_score(pmx_ctx* ctx, pmx_meta* m, int64_t top_oc, const uint32_t* ca
     if (!select_candidates(m->oc, m->n_nodes, top_oc, cand_override, n_override, eligible.empty() ? nullptr : eligible.data(), m->cand))
         return fail(PMX_ERR_ARG, "candidate node out of range");
     m->groups.clear();
-    own_row_slice(m);
+    meta_own_row_slice(m);
     if (m->cand.empty() || m->n_reads == 0) return PMX_OK;
     m->score.ensure((size_t)m->row_count * m->cand.size());
     const int rc = meta_longest_read(m);

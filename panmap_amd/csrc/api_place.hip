@@ -333,6 +333,11 @@ const uint32_t* readset_locality_order_range(pmx_ctx* ctx, const pmx_readset* rs
 extern "C" {
 
 // ---------------------------------------------------------------------------------- context
+int pmx_device_count(void) {
+    int n = 0;
+    return hipGetDeviceCount(&n) == hipSuccess && n > 0 ? n : 0;
+}
+
 int pmx_ctx_create(int device_ordinal, pmx_ctx** out) {
     if (!out) return PMX_ERR_ARG;
     int n = 0;

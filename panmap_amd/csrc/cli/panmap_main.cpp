@@ -118,7 +118,8 @@ void usage() {
           "                             are dealt to N processes, one per GPU, each sample whole on one GPU: the files of the one-GPU run\n"
           "      --meta                 estimate haplotype abundances of a mixed sample -> <prefix>.mgsr.abundance.out\n"
           "      --meta --filter-and-assign   assign every read to the nodes it scores best on -> <prefix>.mgsr.assignedReads.fastq,\n"
-          "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; one GPU)\n"
+          "                             .mgsr.assignedReads.out, .mgsr.assignedReadsLCANode.out (--discard F, --dust F; also with --gpus N:\n"
+          "                             every rank assigns its share of the distinct reads, rank 0 gathers and writes the one-GPU files)\n"
           "      --breadth-ratio        ... and write <prefix>.mgsr.breadths.out: per node the distinct seeds of its genome, how many of them\n"
           "                             the reads assigned to it hit, their depth, and the observed / expected breadth ratios (a switch)\n"
           "      --align-reads          ... and align the reads of every node that has at least --min-num-align N (default 10) of them to that\n"
@@ -142,10 +143,11 @@ void usage() {
           "      --write-meta-read-scores-unfiltered / --write-meta-read-scores-filtered   --meta: write <prefix>.read_scores_info.unfiltered.tsv /\n"
           "                             .filtered.tsv, one line per distinct read that maps: its copies, seedmers, best score over ALL nodes, the\n"
           "                             number of nodes that reach it, and the input positions of its copies; the filtered file lacks the reads\n"
-          "                             below --discard (switches; one GPU a sample: with --batch also --gpus N)\n"
+          "                             below --discard (switches; also with --gpus N, with or without --batch)\n"
           "      --top-oc N --em-convergence-threshold F --em-delta-threshold F --em-maximum-iterations N --em-maximum-rounds N --discard F --dust F\n"
           "      --gpus N               N processes, one per GPU: reads sharded, seed index replicated, RCCL exchange (with --batch:\n"
-          "                             whole samples dealt instead, nothing exchanged; also for --meta --filter-and-assign)\n"
+          "                             whole samples dealt instead, nothing exchanged).  With --meta, --filter-and-assign included, one sample is\n"
+          "                             sharded over the N ranks and rank 0 writes the files of the one-GPU run\n"
           "      --refine               re-rank the top candidates by aligning the reads against them\n"
           "      --refine-top-pct F / --refine-max-top-n N / --refine-neighbor-radius N / --refine-max-neighbor-n N\n"
           "  -i, --index PATH           load a pre-built index       --index-out PATH   write the built index here\n"
@@ -897,6 +899,26 @@ bool fork_ranks(int n, Ranks& rk, int* code, bool rendezvous = true) {
     return false;
 }
 
+// The GPUs a rank of this run could open, counted in a child of its own: the parent must not touch the GPU before it forks
+// the ranks (each rank opens its own device in a fresh process state).
+int visible_gpus() {
+    fflush(stdout); fflush(stderr);
+    const pid_t pid = fork();
+    if (pid < 0) return 0;
+    if (pid == 0) _exit(std::min(pmx_device_count(), 255));
+    int st = 0;
+    while (waitpid(pid, &st, 0) < 0 && errno == EINTR) {}
+    return WIFEXITED(st) ? WEXITSTATUS(st) : 0;
+}
+
+// one sample sharded over --gpus N needs a GPU per rank (PMX_DEVICE names the first; PMX_DIST_SAME_DEVICE: the ranks share it)
+bool gpus_for_every_rank(int n, int* have) {
+    if (getenv("PMX_DIST_SAME_DEVICE")) return true;
+    *have = visible_gpus();
+    const char* e = getenv("PMX_DEVICE");
+    return (e ? atoi(e) : 0) + n <= *have;
+}
+
 int rank_device(const Ranks& rk) {
     int dev = 0;
     if (const char* e = getenv("PMX_DEVICE")) dev = atoi(e);
@@ -1007,7 +1029,12 @@ struct MetaRun {
     // the refusals that need no file
     void refuse_options() const {
         if (c.reads1.empty() && c.batch.empty()) die("--meta needs reads");
-        if (c.filter_and_assign && c.gpus > 1 && c.batch.empty()) die("--filter-and-assign runs on one GPU: drop --gpus");
+        // one sample of --filter-and-assign, or with the read-score reports, over --gpus N is sharded over N ranks that gather
+        // to rank 0; decided here, before anything is built, when the machine cannot give every rank a GPU
+        int have = 0;
+        if (c.filter_and_assign && c.gpus > 1 && c.batch.empty() && !gpus_for_every_rank(c.gpus, &have))
+            die("--filter-and-assign over --gpus " + std::to_string(c.gpus) + " shards the sample over " + std::to_string(c.gpus) +
+                " ranks and needs one GPU per rank: this machine shows " + std::to_string(have) + "; lower --gpus");
         if (!c.batch.empty() && !c.amplicon_depth.empty())
             die("option --amplicon-depth is not accepted with --batch: one table cannot name the reads of several samples");
         if (c.discard < 0.0 || c.discard > 1.0) die("--discard must be between 0 and 1");   // src/main.cpp:1358-1361
@@ -1018,9 +1045,10 @@ struct MetaRun {
                 (c.mask_options[0] == "--mask-read-ends" ? "takes the value and ignores it" : "never masks"));
         if (!c.em_options.empty() && c.filter_and_assign)
             die("option " + c.em_options[0] + " is not accepted with --filter-and-assign: that mode ranks no candidates and runs no EM");
-        if ((c.read_scores_unfiltered || c.read_scores_filtered) && c.gpus > 1 && c.batch.empty())
+        if ((c.read_scores_unfiltered || c.read_scores_filtered) && !c.filter_and_assign && c.gpus > 1 && c.batch.empty() && !gpus_for_every_rank(c.gpus, &have))
             die(std::string("option ") + (c.read_scores_unfiltered ? "--write-meta-read-scores-unfiltered" : "--write-meta-read-scores-filtered") +
-                " is not accepted with one sample over --gpus " + std::to_string(c.gpus) + ": the reads of a sharded sample have no common numbering; drop --gpus");
+                " is not accepted with one sample over --gpus " + std::to_string(c.gpus) + " on this machine: the ranks gather their rows of the reads to rank 0 and need a GPU each, it shows " +
+                std::to_string(have) + "; lower --gpus");
         if (c.mask_reads < 0 || c.mask_seeds < 0) die("--mask-reads and --mask-seeds must not be negative");
         if (c.mask_reads_rf < 0.0 || c.mask_seeds_rf < 0.0)
             die("--mask-reads-relative-frequency and --mask-seeds-relative-frequency must not be negative");
@@ -1208,19 +1236,43 @@ struct MetaSample {
     // --maximum-taxon-number taxa are in none of the files, and the second column holds the taxon names of the head's subtree by
     // ascending taxon index, `.` when there are none or too many.
 
+    // Leaves: `merged`, per read of the WHOLE input its merged read.  One sample over --gpus N (collective): every rank holds the
+    // slice of its shard, in the whole sample's numbering; the shards are contiguous in input order, so the map is their
+    // concatenation -- a zero-filled array with the slice (+ 1) at the shard's place, summed over the ranks.
+    void whole_raw_to_merged() {
+        pmx_meta* m = run.meta;
+        merged.assign((size_t)std::max<int64_t>(reads().n_reads, 1), 0);
+        if (!run.dist) {
+            check(pmx_meta_raw_to_merged(m, merged.data(), reads().n_reads), "the reads' merged reads");
+            return;
+        }
+        if (pmx_meta_num_raw_reads(m) != hi - lo) die("the shard's raw -> merged map does not cover the shard");
+        std::vector<int64_t> mine((size_t)std::max<int64_t>(hi - lo, 1));
+        check(pmx_meta_raw_to_merged(m, mine.data(), hi - lo), "the shard's merged reads");
+        for (int64_t r = lo; r < hi; ++r) merged[(size_t)r] = mine[(size_t)(r - lo)] + 1;
+        check(pmx_dist_sum_i64(run.dist, merged.data(), reads().n_reads), "assembling the reads' merged reads over the ranks");
+        for (int64_t& x : merged) --x;
+    }
+
     // Leaves: the assignment on the device's side done and downloaded: state / lca / off / nodes / merged, head / folded.
+    // One sample over --gpus N: every rank assigns its rows of the merged reads, rank 0 gathers them (the other ranks return
+    // after the collective calls, with nothing to write).
     void assign() {
         pmx_meta* m = run.meta;
         check(pmx_meta_assign(run.ctx, m, c.discard), "assigning the reads to nodes");
+        if (run.dist) {
+            check(pmx_meta_assign_gather(run.ctx, m, 0), "gathering the ranks' assignments");
+            whole_raw_to_merged();
+            if (pmx_dist_rank(run.dist) != 0) return;
+        }
         n_merged = pmx_meta_num_reads(m);
         state.resize((size_t)std::max<int64_t>(n_merged, 1));
         lca.resize(state.size());
         nodes.resize((size_t)std::max<int64_t>(pmx_meta_assign_num_nodes(m), 1));
         off.resize((size_t)n_merged + 1);
-        merged.resize((size_t)std::max<int64_t>(reads().n_reads, 1));
         check(pmx_meta_assign_reads(m, state.data(), nullptr, lca.data(), nullptr, n_merged), "the reads' states");
         check(pmx_meta_assign_nodes(m, off.data(), nodes.data(), (int64_t)nodes.size()), "the reads' nodes");
-        check(pmx_meta_raw_to_merged(m, merged.data(), reads().n_reads), "the reads' merged reads");
+        if (!run.dist) whole_raw_to_merged();
         pmx_index_info info;
         check(pmx_index_get_info(run.oidx, &info), "index info");
         n_nodes = info.n_nodes;
@@ -1551,17 +1603,22 @@ struct MetaSample {
     // (DESIGN.md section 4.3).
 
     // Leaves: rs_max / rs_nbest / rs_seedmers / rs_mult per merged read and rs_copies, the input positions of every merged read's copies.
+    // One sample over --gpus N: every rank scores its rows, rank 0 gathers them and holds what the writers need.
     void score_all_nodes() {
         pmx_meta* m = run.meta;
         check(pmx_meta_read_best(run.ctx, m), "scoring the reads against every node");
+        if (run.dist) {
+            check(pmx_meta_read_best_gather(run.ctx, m, 0), "gathering the ranks' read scores");
+            whole_raw_to_merged();
+            if (pmx_dist_rank(run.dist) != 0) return;
+        }
         n_merged = pmx_meta_num_reads(m);
         const size_t n = (size_t)std::max<int64_t>(n_merged, 1);
         rs_max.resize(n); rs_nbest.resize(n); rs_seedmers.resize(n); rs_mult.resize(n);
         check(pmx_meta_read_best_get(m, rs_max.data(), rs_nbest.data(), n_merged), "the reads' best scores");
         check(pmx_meta_read_info(m, rs_seedmers.data(), rs_mult.data(), n_merged), "the reads' seedmers");
-        const int64_t n_raw = pmx_meta_num_raw_reads(m);
-        merged.resize((size_t)std::max<int64_t>(n_raw, 1));
-        check(pmx_meta_raw_to_merged(m, merged.data(), n_raw), "the reads' merged reads");
+        const int64_t n_raw = reads().n_reads;
+        if (!run.dist) whole_raw_to_merged();
         rs_copies.assign((size_t)n_merged, std::vector<int64_t>());
         for (int64_t r = 0; r < n_raw; ++r)
             if (merged[(size_t)r] >= 0) rs_copies[(size_t)merged[(size_t)r]].push_back(r);
@@ -1642,20 +1699,21 @@ void meta_steps(MetaSample& s, bool writer) {
     s.report_masks();
     if (s.c.filter_and_assign) {
         s.assign();
+        if (!writer) return;   // (one sample over --gpus N: rank 0 gathered, writes and aligns alone; the others wait at the run's last barrier)
         s.write_fastq();
         s.write_node_lists();
         if (s.c.align_reads) s.align_reads();
         if (s.c.breadth_ratio) s.write_breadths();
         s.report_assigned();
     } else {
-        const bool read_scores = s.c.read_scores_unfiltered || s.c.read_scores_filtered;   // (one GPU a sample: refuse_options)
+        const bool read_scores = s.c.read_scores_unfiltered || s.c.read_scores_filtered;
         if (writer && s.c.write_ocranks) s.write_ocranks();
         if (read_scores) s.score_all_nodes();
-        if (s.c.read_scores_unfiltered) s.write_read_scores(false);
-        if (read_scores) s.report_read_scores();
+        if (writer && s.c.read_scores_unfiltered) s.write_read_scores(false);
+        if (writer && read_scores) s.report_read_scores();
         s.estimate();
         if (writer) s.write_abundance();
-        if (s.c.read_scores_filtered) s.write_read_scores(true);
+        if (writer && s.c.read_scores_filtered) s.write_read_scores(true);
     }
 }
 

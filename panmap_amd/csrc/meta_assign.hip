@@ -528,7 +528,7 @@ __device__ __forceinline__ void planes_flush(unsigned long long (&plane)[PLANES]
 
 // One chunk's part of hit[] and depth[] (see "Breadth").  Rows [0, n_rows) of the chunk's fwd / rev matrices; row_id: the row
 // of `hit` (the seedmer's index among the read set's distinct seedmers); car_off / car: the chunk's reads (indices into mult /
-// wmask, which point at the chunk's first read, read0; state_words: the states of ALL reads, four to a word, padded to whole
+// wmask, which point at the chunk's first read, read0; state_words: the states of ALL reads of the call, four to a word, padded to whole
 // words) that carry the row's seedmer.  The carriers are taken four at a time,
 // their states, multiplicities and mask words loaded before any is used (a read that is not ASSIGNED is loaded too and masked
 // out): one load after the other left the kernel waiting on latency.
@@ -630,6 +630,35 @@ __global__ void __launch_bounds__(256) k_meta_breadth_count(const unsigned long 
     }
 }
 
+// --gpus N: the ranks' copies of one slab of `hit` (world x slab), the buffer of AssignStage::breadth_merge; it counts against
+// nothing else: the chunks' matrices are released only with the stage, `hit` itself is under kBreadthHitBytes
+constexpr size_t kBreadthSlabBytes = (size_t)1 << 30;
+
+// dst[i] |= all[r * stride + i] for every rank r < world and word i < n: the ranks' copies of a slab of `hit` folded into the
+// local rows.  Pure streaming: (world + 1) reads and one write of the slab.  Two words a lane and step (16-byte loads and stores)
+// in a grid-stride loop while dst, all and the copies' stride are 16-byte aligned, the words left over (n odd, or no alignment)
+// one at a time.  One thread owns a word: no atomics.
+__global__ void __launch_bounds__(256) k_meta_breadth_or(unsigned long long* __restrict__ dst, const unsigned long long* __restrict__ all, int64_t n,
+                                                         int64_t stride, int world) {
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, n_thr = (int64_t)gridDim.x * blockDim.x;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(all)) & 15) == 0 && (stride & 1) == 0;
+    const int64_t n_vec = aligned ? n >> 1 : 0;
+    for (int64_t i = t0; i < n_vec; i += n_thr) {
+        ulonglong2 a = reinterpret_cast<const ulonglong2*>(dst)[i];
+        for (int r = 0; r < world; ++r) {
+            const ulonglong2 b = reinterpret_cast<const ulonglong2*>(all + (size_t)r * (size_t)stride)[i];
+            a.x |= b.x;
+            a.y |= b.y;
+        }
+        reinterpret_cast<ulonglong2*>(dst)[i] = a;
+    }
+    for (int64_t i = 2 * n_vec + t0; i < n; i += n_thr) {
+        unsigned long long a = dst[i];
+        for (int r = 0; r < world; ++r) a |= all[(size_t)r * (size_t)stride + (size_t)i];
+        dst[i] = a;
+    }
+}
+
 // One call of pmx_meta_assign: the plan of the chunks, then one function per chunk step.
 int assign_words(int64_t n_nodes) { return (int)(((n_nodes + 63) / 64 + 1) & ~(int64_t)1); }
 
@@ -638,7 +667,7 @@ struct AssignStage {
     pmx_meta* const m;
     const hipStream_t st;
     const double discard;
-    const int64_t n_reads;
+    const int64_t row0, n_reads;   // this rank's rows of the merged reads (all of them without a dist): the per-read buffers hold these
     const int words;   // 64-bit words of a row: one bit per node, padded to an even count
     // taxonomy (pmx_meta_set_taxonomy / pmx_meta_set_ambiguous): none, the best columns, or k_meta_assign_near's rows
     const int max_taxa;
@@ -662,12 +691,12 @@ struct AssignStage {
     // (row -> the chunk's reads that carry it) and the rows' places in `hit` are per chunk
     const bool breadth;
     uint32_t breadth_cap = (1u << kBreadthPlanes) - 1u;
-    DevBuf<unsigned long long> d_hit, d_depth, d_observed;
+    DevBuf<unsigned long long> d_hit, d_depth, d_observed, d_slabs;   // (d_slabs: --gpus N, the ranks' copies of a slab of d_hit)
     DevBuf<int64_t> d_mult, d_car_off;
     DevBuf<uint32_t> d_car, d_row_id;
 
     AssignStage(pmx_ctx* c, pmx_meta* mm, double d)
-        : ctx(c), m(mm), st(c->stream), discard(d), n_reads(mm->n_reads), words(assign_words(mm->n_nodes)), max_taxa(mm->max_taxa),
+        : ctx(c), m(mm), st(c->stream), discard(d), row0(mm->row_first), n_reads(mm->row_count), words(assign_words(mm->n_nodes)), max_taxa(mm->max_taxa),
           near(mm->max_taxa > 0 && (mm->amb_abs > 0 || mm->amb_ratio > 0.0)), breadth(mm->breadth_on) {
         // lo = max(0, max - max(abs, (int)(max * ratio))) == 0 for some maximum a read of this set can have
         for (int64_t mx = 1; near && !touch && mx <= mm->longest; ++mx)
@@ -678,16 +707,19 @@ struct AssignStage {
     void run_chunk(int64_t r0, int64_t r1);
     void finish();
     void breadth_begin();
+    void breadth_merge();
     int breadth_rows_per_block(int64_t n_rows) const;
 };
 
-// Chunks of consecutive merged reads whose distinct seedmers number at most cap_rows, at most cap_reads reads each (a read that
-// alone exceeds them is a chunk of its own): the first merged read of every chunk, then n_reads.
+// Chunks of consecutive merged reads of this rank's rows [row_first, row_first + row_count) whose distinct seedmers number at
+// most cap_rows, at most cap_reads reads each (a read that alone exceeds them is a chunk of its own): the first merged read of
+// every chunk, then the end of the rows (a rank without rows: the first row alone, no chunk).
 std::vector<int64_t> plan_read_chunks(const pmx_meta* m, int64_t cap_rows, int64_t cap_reads) {
     std::vector<int64_t> seen(m->h_uniq.size(), -1);   // the chunk (by its first read) that last counted the seedmer
-    std::vector<int64_t> chunk_first(1, 0);
-    int64_t r0 = 0, rows = 0;
-    for (int64_t r = 0; r < m->n_reads; ++r) {
+    const int64_t row_end = m->row_first + m->row_count;
+    std::vector<int64_t> chunk_first(1, m->row_first);
+    int64_t r0 = m->row_first, rows = 0;
+    for (int64_t r = m->row_first; r < row_end; ++r) {
         int64_t fresh = 0;
         for (int64_t i = m->h_read_off[(size_t)r]; i < m->h_read_off[(size_t)r + 1]; ++i) fresh += seen[m->h_seed_uid[(size_t)i]] != r0;
         if (r > r0 && (r - r0 >= cap_reads || rows + fresh > cap_rows)) {
@@ -700,7 +732,7 @@ std::vector<int64_t> plan_read_chunks(const pmx_meta* m, int64_t cap_rows, int64
             if (s != r0) { s = r0; ++rows; }
         }
     }
-    chunk_first.push_back(m->n_reads);
+    if (m->row_count > 0) chunk_first.push_back(row_end);   // (a rank without rows: no chunk)
     return chunk_first;
 }
 
@@ -759,7 +791,7 @@ void AssignStage::begin() {
 // With a taxonomy the reads spanning too many taxa become PMX_META_OVER_TAXA before the scan (d_ntax, d_tax: the others' taxa).
 // Leaves: d_max .. d_state of the reads, m->as_off (r0, r1] and m->as_nodes grown by the chunk's lists.
 void AssignStage::run_chunk(int64_t r0, int64_t r1) {
-    const int64_t n = r1 - r0, s0 = m->h_read_off[(size_t)r0];
+    const int64_t n = r1 - r0, s0 = m->h_read_off[(size_t)r0], l0 = r0 - row0;   // l0: the chunk's first read among this rank's rows
     const ChunkRows C = chunk_rows(m, r0, r1);
     const std::vector<uint32_t>& ids = C.ids;
     const std::vector<uint32_t>& uid = C.uid;
@@ -812,7 +844,7 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     const dim3 grid(grid_for(n * 64, 256, ctx->n_cu * 16)), block(256);
     meta_with_planes(m->longest, [&](auto planes) {
         PMX_LAUNCH(k_meta_assign_max<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p, d_rev.p,
-                   words, m->n_nodes, discard, d_wmask.p, d_wmax.p, d_max.p + r0, d_count.p + r0, d_first.p + r0, d_last.p + r0, d_state.p + r0);
+                   words, m->n_nodes, discard, d_wmask.p, d_wmax.p, d_max.p + l0, d_count.p + l0, d_first.p + l0, d_last.p + l0, d_state.p + l0);
     });
     if (max_taxa > 0) {   // its own span: "meta_assign" then ends here, the scan below belongs to "meta_assign_taxa"
         timer_end(ctx, "meta_assign", 1);
@@ -820,21 +852,21 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
         if (near)
             meta_with_planes(m->longest, [&](auto planes) {
                 PMX_LAUNCH(k_meta_assign_near<decltype(planes)::value>, grid, block, 0, st, m->d_read_off.p + r0, s0, d_uid.p, m->d_seed_rev.p, n, d_fwd.p,
-                           d_rev.p, touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + r0, d_state.p + r0, d_near.p);
+                           d_rev.p, touch ? d_touch.p : nullptr, words, m->n_nodes, (int)m->amb_abs, m->amb_ratio, d_max.p + l0, d_state.p + l0, d_near.p);
             });
         PMX_LAUNCH(k_meta_assign_taxa, grid, block, 0, st, near ? d_near.p : d_wmask.p, words, n, m->tx_over.p, m->tx_count.p, m->tx_ids.p, max_taxa,
-                   d_state.p + r0, d_count.p + r0, d_ntax.p + r0, d_tax.p + (size_t)r0 * (size_t)max_taxa);
+                   d_state.p + l0, d_count.p + l0, d_ntax.p + l0, d_tax.p + (size_t)l0 * (size_t)max_taxa);
     }
     // (d_count has one entry past the last read, zero: the scan's entry n is the chunk's total; the entry it reads past the
     //  chunk's own counts plays no part in any output)
-    PMX_ROCPRIM(tmp, exclusive_scan, d_count.p + r0, d_off.p, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
+    PMX_ROCPRIM(tmp, exclusive_scan, d_count.p + l0, d_off.p, (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), st);
     timer_end(ctx, max_taxa > 0 ? "meta_assign_taxa" : "meta_assign", 1);
     if (breadth) {   // the states are final
         timer_begin(ctx, "meta_breadth");
         const int rpb = breadth_rows_per_block(n_rows);
         const int64_t items = ((n_rows + rpb - 1) / rpb) * (int64_t)((words + 63) / 64);
         PMX_LAUNCH(k_meta_breadth_rows, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words, d_row_id.p,
-                   d_car_off.p, d_car.p, reinterpret_cast<const uint32_t*>(d_state.p), r0, d_mult.p + r0, d_wmask.p, rpb, breadth_cap, d_hit.p, d_depth.p);
+                   d_car_off.p, d_car.p, reinterpret_cast<const uint32_t*>(d_state.p), l0, d_mult.p + l0, d_wmask.p, rpb, breadth_cap, d_hit.p, d_depth.p);
         timer_end(ctx, "meta_breadth", 1);
     }
     h_off.resize((size_t)n + 1);
@@ -843,11 +875,11 @@ void AssignStage::run_chunk(int64_t r0, int64_t r1) {
     if (max_taxa > 0) timer_sum_add(ctx, "meta_assign_taxa");
     if (breadth) timer_sum_add(ctx, "meta_breadth");
     const int64_t total = h_off[(size_t)n], base = (int64_t)m->as_nodes.size();
-    for (int64_t i = 1; i <= n; ++i) m->as_off[(size_t)(r0 + i)] = base + h_off[(size_t)i];
+    for (int64_t i = 1; i <= n; ++i) m->as_off[(size_t)(l0 + i)] = base + h_off[(size_t)i];
     if (total == 0) return;
     d_nodes.ensure((size_t)total);
     timer_begin(ctx, "meta_assign_emit");
-    PMX_LAUNCH(k_meta_assign_emit, grid, block, 0, st, d_count.p + r0, d_off.p, n, d_wmask.p, words, d_nodes.p);
+    PMX_LAUNCH(k_meta_assign_emit, grid, block, 0, st, d_count.p + l0, d_off.p, n, d_wmask.p, words, d_nodes.p);
     timer_end(ctx, "meta_assign_emit", 1);
     m->as_nodes.resize((size_t)(base + total));
     PMX_D2H_SYNC(m->as_nodes.data() + base, d_nodes, total, st);
@@ -879,6 +911,7 @@ void AssignStage::finish() {
     const int64_t n_uniq = (int64_t)m->h_uniq.size();
     const int rpb = breadth_rows_per_block(n_uniq);
     const int64_t items = ((n_uniq + rpb - 1) / rpb) * (int64_t)((words + 63) / 64);
+    if (m->dist) breadth_merge();   // the whole sample's hit matrix on every rank
     timer_begin(ctx, "meta_breadth");
     timer_begin(ctx, "meta_breadth_count");   // (the count kernel alone; "meta_breadth" holds it too)
     PMX_LAUNCH(k_meta_breadth_count, dim3(grid_for(items * 64, 256, ctx->n_cu * 8)), dim3(256), 0, st, d_hit.p, n_uniq, words, rpb, breadth_cap, d_observed.p);
@@ -887,6 +920,34 @@ void AssignStage::finish() {
     PMX_D2H(m->br_observed, d_observed, m->n_nodes, st);
     PMX_D2H_SYNC(m->br_depth, d_depth, m->n_nodes, st);
     timer_sum_add(ctx, "meta_breadth");
+    // (the depths are 64-bit sums over the reads of a node: the ranks' sums add up)
+    if (m->dist && pmx_dist_sum_i64(m->dist, reinterpret_cast<int64_t*>(m->br_depth.data()), m->n_nodes) != PMX_OK) throw HipError{pmx_last_error()};
+}
+
+// --gpus N, after the last chunk: every rank's `hit` holds the (seedmer, node) pairs its own rows hit; the whole sample's
+// matrix is their bitwise OR (a pair hit on two ranks counts once).  The matrices have one shape (rows: h_uniq, the same on every
+// rank), so whole rows are exchanged in slabs through the dist's device all-gather -- world x slab words in d_slabs, at most
+// kBreadthSlabBytes, pmx_meta_set_breadth_slab forces the rows of a slab -- and k_meta_breadth_or folds the copies into the local rows.
+// The number of exchanges is a function of h_uniq, the words of a row and the world: the same on every rank, a rank without rows
+// included.  "meta_breadth_merge": the OR kernels, summed over the slabs.
+void AssignStage::breadth_merge() {
+    const int world = pmx_dist_world(m->dist);
+    const int64_t n_uniq = (int64_t)m->h_uniq.size();
+    int64_t slab_rows = std::max<int64_t>(1, (int64_t)(kBreadthSlabBytes / ((size_t)world * (size_t)words * sizeof(unsigned long long))));
+    if (m->breadth_slab_rows > 0) slab_rows = m->breadth_slab_rows;
+    slab_rows = std::min(slab_rows, std::max<int64_t>(n_uniq, 1));
+    d_slabs.alloc((size_t)world * (size_t)slab_rows * (size_t)words);
+    timer_sum_reset(ctx, "meta_breadth_merge");
+    for (int64_t row0 = 0; row0 < n_uniq; row0 += slab_rows) {
+        const int64_t n = std::min(slab_rows, n_uniq - row0) * (int64_t)words;   // words of this slab, and from one copy to the next
+        unsigned long long* mine = d_hit.p + (size_t)row0 * (size_t)words;
+        dist_all_gather(m->dist, mine, (size_t)n * sizeof(unsigned long long), d_slabs.p);
+        timer_begin(ctx, "meta_breadth_merge");
+        PMX_LAUNCH(k_meta_breadth_or, dim3(grid_for((n + 1) / 2, 256, ctx->n_cu * 8)), dim3(256), 0, st, mine, d_slabs.p, n, n, world);
+        timer_end(ctx, "meta_breadth_merge", 1);
+        PMX_HIP(hipStreamSynchronize(st));   // (the next exchange writes d_slabs)
+        timer_sum_add(ctx, "meta_breadth_merge");
+    }
 }
 
 // Rows a wave walks before it expands its counters: enough (block, span) items for 32 waves a CU, 16 to 512 rows.
@@ -902,7 +963,7 @@ void AssignStage::breadth_begin() {
     PMX_ZERO(d_hit, mat, st);
     PMX_ZERO(d_depth, cols, st);
     PMX_ZERO(d_observed, cols, st);
-    PMX_H2D(d_mult, m->h_mult, n_reads, st);
+    PMX_H2D(d_mult, m->h_mult.data() + row0, (size_t)n_reads, st);
     if (const char* f = opt_str(O_META_BREADTH_FLUSH)) breadth_cap = (uint32_t)std::min<long long>(breadth_cap, std::max<long long>(1, atoll(f)));
 }
 
@@ -939,7 +1000,9 @@ std::vector<uint64_t> total_ref_seeds(const pmx_meta* m) {
 // The results of a call that assigns nothing, sized for the merged reads: every read unmapped, no nodes, no taxa; with breadth
 // zero counts per node and TotalRefSeeds, computed on the first such call.  No "meta_breadth" spans are left from an earlier call.
 void reset_assign_results(pmx_ctx* ctx, pmx_meta* m) {
-    const size_t n = (size_t)m->n_reads;
+    const size_t n = (size_t)m->row_count;   // (--gpus N: this rank's rows)
+    m->as_rows = m->row_count;
+    m->as_gathered = false;
     m->as_state.assign(n, PMX_META_UNMAPPED);
     m->as_max.assign(n, 0);
     m->as_count.assign(n, 0);
@@ -956,6 +1019,7 @@ void reset_assign_results(pmx_ctx* ctx, pmx_meta* m) {
     }
     timer_cancel(ctx, "meta_breadth");
     timer_cancel(ctx, "meta_breadth_count");
+    timer_cancel(ctx, "meta_breadth_merge");
 }
 
 // One call of pmx_meta_read_best: the chunks of AssignStage without its word masks (nothing is kept per read and word, so
@@ -970,7 +1034,7 @@ struct BestStage {
     DevBuf<uint64_t> d_uniq;
     DevBuf<unsigned long long> d_fwd, d_rev;
 
-    BestStage(pmx_ctx* c, pmx_meta* mm) : ctx(c), m(mm), st(c->stream), words(assign_words(mm->n_nodes)) {}
+    BestStage(pmx_ctx* c, pmx_meta* mm) : ctx(c), m(mm), st(c->stream), words(assign_words(mm->n_nodes)) {}   // (d_max / d_nbest: this rank's rows)
     void active_nodes();
     void run_chunk(int64_t r0, int64_t r1);
 };
@@ -1010,11 +1074,75 @@ void BestStage::run_chunk(int64_t r0, int64_t r1) {
     PMX_LAUNCH(k_assign_prefix_xor, dim3(grid_for(2 * n_rows * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, d_fwd.p, d_rev.p, n_rows, words);
     meta_with_planes(m->longest, [&](auto planes) {
         PMX_LAUNCH(k_meta_read_best<decltype(planes)::value>, dim3(grid_for(n * 64, 256, ctx->n_cu * 16)), dim3(256), 0, st, m->d_read_off.p + r0, s0, d_uid.p,
-                   m->d_seed_rev.p, n, d_fwd.p, d_rev.p, words, m->n_nodes, m->d_active.p, d_max.p + r0, d_nbest.p + r0);
+                   m->d_seed_rev.p, n, d_fwd.p, d_rev.p, words, m->n_nodes, m->d_active.p, d_max.p + (r0 - m->row_first), d_nbest.p + (r0 - m->row_first));
     });
     timer_end(ctx, "meta_read_best", 1);
     PMX_HIP(hipStreamSynchronize(st));   // (the chunk's host lists go out of scope)
     timer_sum_add(ctx, "meta_read_best");
+}
+
+// ---- --gpus N (pmx_meta_attach_dist): pmx_meta_assign and pmx_meta_read_best as collectives.
+// A merged read's results depend on its own list and the index only, and after a collective set_reads every rank holds the whole
+// sample's merged reads, h_uniq and the index: a rank runs its chunk loop over ITS rows [row_first, row_first + row_count) (the
+// rule of pmx_meta_score) and nothing in the per-read kernels changes.  Only breadth is not per read (AssignStage::breadth_merge
+// and the sum of the depths).  What keeps a collective from hanging:
+//   * every refusal is decided from settings, identically on every rank, and before any exchange but the digest's: the masks,
+//     the amplicons and the masked ends of the last set_reads (itself collective) before it; after it, when the ranks are known
+//     to be set alike, discard together with an ambiguity threshold and the kBreadthHitBytes bound, a function of h_uniq and the
+//     node count;
+//   * pmx_meta_assign starts by exchanging a digest of its settings -- the bits of discard, breadth on / off, max_taxa, the
+//     ambiguity pair, a hash of the node table of pmx_meta_set_taxonomy -- and ranks that disagree ALL return PMX_ERR_ARG after that
+//     exchange and before any other (the rule of MetaReads::merge_over_ranks for the amplicon groups);
+//   * no exchange sits inside the per-chunk loop: ranks have different numbers of chunks.  Exchanges happen only at points
+//     whose number depends on global quantities (h_uniq.size(), the words of a row, the world);
+//   * a rank with an empty shard, or with zero rows, takes part in every exchange.
+// A dist of ONE rank stays PMX_ERR_UNSUPPORTED for both calls, as every dist was before they became collective: one GPU has no
+// use for the exchanges and runs the calls without a dist.
+// pmx_meta_read_best exchanges nothing: the active nodes are a function of h_uniq.
+
+uint64_t fnv1a(uint64_t h, const void* p, size_t n) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 0x100000001b3ULL;
+    return h;
+}
+
+// the settings of a pmx_meta_assign call as six numbers: equal on ranks that were configured alike
+void assign_digest(const pmx_meta* m, double discard, int64_t (&d)[6]) {
+    uint64_t tx = 0xcbf29ce484222325ULL;
+    if (m->max_taxa > 0) {
+        tx = fnv1a(tx, m->h_tx_count.data(), m->h_tx_count.size());
+        tx = fnv1a(tx, m->h_tx_ids.data(), m->h_tx_ids.size() * sizeof(uint32_t));
+        tx = fnv1a(tx, m->h_tx_over.data(), m->h_tx_over.size() * sizeof(unsigned long long));
+    }
+    memcpy(&d[0], &discard, 8);
+    d[1] = m->breadth_on ? 1 : 0;
+    d[2] = m->max_taxa;
+    d[3] = m->amb_abs;
+    memcpy(&d[4], &m->amb_ratio, 8);
+    memcpy(&d[5], &tx, 8);
+}
+
+// Every rank's part of a per-row array to `root`, in rank order: elems[r] elements of rank r.  The root returns the whole
+// array, the others an empty one.  The dist's gather (send / receive, exact sizes); every rank calls it, whatever its part.
+template <class T>
+std::vector<T> gather_rows(pmx_meta* m, const T* mine, const std::vector<int64_t>& elems, int root) {
+    pmx_ctx* ctx = m->ctx;
+    const int world = pmx_dist_world(m->dist), rank = pmx_dist_rank(m->dist);
+    std::vector<size_t> sizes((size_t)world), offs((size_t)world);
+    size_t total = 0;
+    for (int r = 0; r < world; ++r) { offs[(size_t)r] = total; sizes[(size_t)r] = (size_t)elems[(size_t)r] * sizeof(T); total += sizes[(size_t)r]; }
+    DevBuf<char> d_mine, d_all;
+    d_mine.alloc(sizes[(size_t)rank]);
+    if (rank == root) d_all.alloc(total);
+    PMX_H2D(d_mine, reinterpret_cast<const char*>(mine), sizes[(size_t)rank], ctx->stream);
+    dist_gather_v(m->dist, d_mine.p, sizes, offs, d_all.p, root);
+    std::vector<T> all;
+    if (rank == root) {
+        all.resize(total / sizeof(T));
+        PMX_D2H(reinterpret_cast<char*>(all.data()), d_all, total, ctx->stream);
+    }
+    PMX_HIP(hipStreamSynchronize(ctx->stream));
+    return all;
 }
 }  // namespace
 
@@ -1022,7 +1150,8 @@ extern "C" {
 
 int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     if (!ctx || !m || !(discard >= 0.0 && discard <= 1.0)) return PMX_ERR_ARG;   // src/main.cpp:1358-1361
-    if (m->dist) return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign runs on one GPU: not with an attached dist");
+    if (m->dist && pmx_dist_world(m->dist) < 2)   // (as before the call was collective; the same on every rank)
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign with an attached dist of one rank: the collective needs two ranks or more, one GPU runs it without a dist");
     if (!m->reads_set) return fail(PMX_ERR_ARG, "pmx_meta_assign: call pmx_meta_set_reads first");
     if (m->masked)   // (the reference's reader for this mode, initializeQueryDataBatch, never masks: src/mgsr.cpp:1575)
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with a low-coverage mask (pmx_meta_set_masks), which --filter-and-assign "
@@ -1033,6 +1162,18 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
     if (m->amp_on)   // (that reader takes no amplicon file either)
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: the reads were set with amplicons (pmx_meta_set_amplicons), which --filter-and-assign does not "
                                          "have: clear the amplicons and set the reads again");
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    if (m->dist) {   // the first exchange: the ranks' settings
+        int64_t mine[6];
+        assign_digest(m, discard, mine);
+        const std::vector<int64_t> all = dist_exchange_counts(m->dist, mine, 6);
+        for (size_t i = 0; i < all.size(); ++i)
+            if (all[i] != all[i % 6])
+                return fail(PMX_ERR_ARG, "pmx_meta_assign: the ranks disagree on the settings of the call (discard, breadth, max_taxa, the ambiguity "
+                                         "thresholds or the taxonomy): rank " + std::to_string(i / 6) + " differs from rank 0");
+    }
+    // (the refusals that depend on the call's own settings: after the digest, so that ranks set differently have all left above)
     if (m->max_taxa > 0 && discard > 0.0 && (m->amb_abs > 0 || m->amb_ratio > 0.0))
         return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign: a discard threshold together with an ambiguity threshold (the reference's records then depend "
                                          "on the order of a node's seed changes)");
@@ -1042,14 +1183,13 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
             return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_assign with breadth: the hit matrix (distinct seedmers of the reads x nodes, one bit each) needs " +
                                                  std::to_string(bytes) + " bytes, the budget is " + std::to_string(kBreadthHitBytes));
     }
-    PMX_TRY
-    PMX_HIP(hipSetDevice(ctx->device));
     m->assigned = false;
     m->as_breadth = false;
-    const int rc = meta_longest_read(m);
+    const int rc = meta_longest_read(m);   // (of the whole sample's merged reads: the same on every rank)
     if (rc != PMX_OK) return rc;
+    meta_own_row_slice(m);
     reset_assign_results(ctx, m);
-    if (m->n_reads > 0) {
+    if (m->n_reads > 0) {   // (the whole sample's: a rank without rows runs no chunk and takes part in the breadth merge)
         AssignStage S(ctx, m, discard);
         S.plan_chunks();
         S.begin();
@@ -1064,15 +1204,19 @@ int pmx_meta_assign(pmx_ctx* ctx, pmx_meta* m, double discard) {
 
 int pmx_meta_read_best(pmx_ctx* ctx, pmx_meta* m) {
     if (!ctx || !m) return PMX_ERR_ARG;
-    if (m->dist) return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_read_best runs on one GPU: not with an attached dist (no raw -> merged map of a sharded sample)");
+    if (m->dist && pmx_dist_world(m->dist) < 2)   // (as before the call was collective)
+        return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_read_best with an attached dist of one rank: the collective needs two ranks or more, one GPU runs it without a dist");
     if (!m->reads_set) return fail(PMX_ERR_ARG, "pmx_meta_read_best: call pmx_meta_set_reads first");
     PMX_TRY
     PMX_HIP(hipSetDevice(ctx->device));
     m->best_done = false;
     const int rc = meta_longest_read(m);
     if (rc != PMX_OK) return rc;
+    meta_own_row_slice(m);
     BestStage S(ctx, m);
-    const size_t n = (size_t)m->n_reads;
+    const size_t n = (size_t)m->row_count;   // (--gpus N: this rank's rows; nothing is exchanged)
+    m->rb_rows = m->row_count;
+    m->rb_gathered = false;
     timer_sum_reset(ctx, "meta_read_best");
     timer_cancel(ctx, "meta_read_best");   // (no span when nothing below runs: the active nodes are built, no reads)
     S.active_nodes();
@@ -1094,7 +1238,7 @@ int pmx_meta_read_best(pmx_ctx* ctx, pmx_meta* m) {
 }
 
 int pmx_meta_read_best_get(const pmx_meta* m, uint16_t* max_score, uint32_t* n_best, int64_t cap) {
-    if (!m || !m->best_done || cap < m->n_reads) return PMX_ERR_ARG;
+    if (!m || !m->best_done || cap < m->rb_rows) return PMX_ERR_ARG;
     if (max_score) std::copy(m->rb_max.begin(), m->rb_max.end(), max_score);
     if (n_best) std::copy(m->rb_nbest.begin(), m->rb_nbest.end(), n_best);
     return PMX_OK;
@@ -1112,6 +1256,12 @@ int pmx_meta_set_breadth(pmx_meta* m, int on) {
     return PMX_OK;
 }
 
+int pmx_meta_set_breadth_slab(pmx_meta* m, int64_t rows) {
+    if (!m || rows < 0) return PMX_ERR_ARG;
+    m->breadth_slab_rows = rows;
+    return PMX_OK;
+}
+
 int pmx_meta_breadth(const pmx_meta* m, uint64_t* total_ref_seeds, uint64_t* observed, uint64_t* depth, int64_t cap_nodes) {
     if (!m || !m->assigned || !m->as_breadth || cap_nodes < m->n_nodes) return PMX_ERR_ARG;
     if (total_ref_seeds) std::copy(m->total_ref_seeds.begin(), m->total_ref_seeds.end(), total_ref_seeds);
@@ -1121,7 +1271,7 @@ int pmx_meta_breadth(const pmx_meta* m, uint64_t* total_ref_seeds, uint64_t* obs
 }
 
 int pmx_meta_assign_reads(const pmx_meta* m, uint8_t* state, uint16_t* max_score, uint32_t* lca, uint32_t* n_nodes, int64_t cap) {
-    if (!m || !m->assigned || cap < m->n_reads) return PMX_ERR_ARG;
+    if (!m || !m->assigned || cap < m->as_rows) return PMX_ERR_ARG;
     if (state) std::copy(m->as_state.begin(), m->as_state.end(), state);
     if (max_score) std::copy(m->as_max.begin(), m->as_max.end(), max_score);
     if (lca) std::copy(m->as_lca.begin(), m->as_lca.end(), lca);
@@ -1196,7 +1346,7 @@ int pmx_meta_set_ambiguous(pmx_meta* m, int32_t abs, double ratio) {
 }
 
 int pmx_meta_assign_taxa(const pmx_meta* m, uint32_t* n_taxa, uint32_t* taxa, int64_t cap) {
-    if (!m || !m->assigned || cap < m->n_reads) return PMX_ERR_ARG;
+    if (!m || !m->assigned || cap < m->as_rows) return PMX_ERR_ARG;
     if (n_taxa) std::copy(m->as_ntax.begin(), m->as_ntax.end(), n_taxa);
     if (taxa) std::copy(m->as_tax.begin(), m->as_tax.end(), taxa);
     return PMX_OK;
@@ -1215,11 +1365,59 @@ int64_t pmx_meta_node_taxa(const pmx_meta* m, int64_t v, uint32_t* ids, int64_t 
     return c;
 }
 
-int64_t pmx_meta_num_raw_reads(const pmx_meta* m) { return m ? m->n_raw_reads : 0; }
+// (--gpus N: n_raw_reads counts the whole sample's reads, the map covers the shard's)
+// The rows of every rank to `root`: afterwards its getters cover all merged reads, as one rank's would -- the per-read arrays in
+// row order (the ranks' rows tile the merged reads in rank order), the node lists back to back, the offsets rebased (a read's
+// stretch of the list is its node count, on one rank as here).  The other ranks keep their rows.
+int pmx_meta_assign_gather(pmx_ctx* ctx, pmx_meta* m, int root) {
+    if (!ctx || !m || !m->dist || root < 0 || root >= pmx_dist_world(m->dist)) return PMX_ERR_ARG;
+    if (!m->assigned || m->as_gathered) return fail(PMX_ERR_ARG, "pmx_meta_assign_gather: call pmx_meta_assign first, and gather its results once");
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    const int world = pmx_dist_world(m->dist);
+    const int64_t mine[2] = {m->as_rows, (int64_t)m->as_nodes.size()};
+    const std::vector<int64_t> counts = dist_exchange_counts(m->dist, mine, 2);
+    std::vector<int64_t> rows((size_t)world), lists((size_t)world), taxa((size_t)world);
+    for (int r = 0; r < world; ++r) {
+        rows[(size_t)r] = counts[2 * (size_t)r];
+        lists[(size_t)r] = counts[2 * (size_t)r + 1];
+        taxa[(size_t)r] = rows[(size_t)r] * m->as_max_taxa;
+    }
+    std::vector<uint8_t> state = gather_rows(m, m->as_state.data(), rows, root), ntax = gather_rows(m, m->as_ntax.data(), rows, root);
+    std::vector<uint16_t> mx = gather_rows(m, m->as_max.data(), rows, root);
+    std::vector<uint32_t> lca = gather_rows(m, m->as_lca.data(), rows, root), count = gather_rows(m, m->as_count.data(), rows, root);
+    std::vector<uint32_t> tax = gather_rows(m, m->as_tax.data(), taxa, root), nodes = gather_rows(m, m->as_nodes.data(), lists, root);
+    m->as_gathered = true;
+    if (pmx_dist_rank(m->dist) != root) return PMX_OK;
+    m->as_state.swap(state); m->as_ntax.swap(ntax); m->as_max.swap(mx); m->as_lca.swap(lca); m->as_count.swap(count); m->as_tax.swap(tax);
+    m->as_nodes.swap(nodes);
+    m->as_rows = (int64_t)m->as_state.size();
+    m->as_off.assign((size_t)m->as_rows + 1, 0);
+    for (int64_t r = 0; r < m->as_rows; ++r) m->as_off[(size_t)r + 1] = m->as_off[(size_t)r] + (int64_t)m->as_count[(size_t)r];
+    return PMX_OK;
+    PMX_CATCH
+}
+
+int pmx_meta_read_best_gather(pmx_ctx* ctx, pmx_meta* m, int root) {
+    if (!ctx || !m || !m->dist || root < 0 || root >= pmx_dist_world(m->dist)) return PMX_ERR_ARG;
+    if (!m->best_done || m->rb_gathered) return fail(PMX_ERR_ARG, "pmx_meta_read_best_gather: call pmx_meta_read_best first, and gather its results once");
+    PMX_TRY
+    PMX_HIP(hipSetDevice(ctx->device));
+    const std::vector<int64_t> rows = dist_exchange_counts(m->dist, &m->rb_rows, 1);
+    std::vector<uint16_t> mx = gather_rows(m, m->rb_max.data(), rows, root);
+    std::vector<uint32_t> nbest = gather_rows(m, m->rb_nbest.data(), rows, root);
+    m->rb_gathered = true;
+    if (pmx_dist_rank(m->dist) != root) return PMX_OK;
+    m->rb_max.swap(mx); m->rb_nbest.swap(nbest);
+    m->rb_rows = (int64_t)m->rb_max.size();
+    return PMX_OK;
+    PMX_CATCH
+}
+
+int64_t pmx_meta_num_raw_reads(const pmx_meta* m) { return !m ? 0 : m->dist ? (int64_t)m->h_raw_to_merged.size() : m->n_raw_reads; }
 
 int pmx_meta_raw_to_merged(const pmx_meta* m, int64_t* map, int64_t cap) {
     if (!m || !map || !m->reads_set) return PMX_ERR_ARG;
-    if (m->dist) return fail(PMX_ERR_UNSUPPORTED, "pmx_meta_raw_to_merged: the merged reads of an attached dist are the whole sample's");
     if (cap < (int64_t)m->h_raw_to_merged.size()) return PMX_ERR_ARG;
     std::copy(m->h_raw_to_merged.begin(), m->h_raw_to_merged.end(), map);
     return PMX_OK;

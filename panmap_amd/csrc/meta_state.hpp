@@ -62,7 +62,7 @@ struct pmx_meta {
     std::vector<int64_t> h_mult;
     std::vector<uint64_t> h_uniq;
     std::vector<uint32_t> h_seed_uid;       // every seedmer as its index into h_uniq
-    std::vector<int64_t> h_raw_to_merged;   // per raw read of the last set_reads: its merged read, -1 = dropped (DUST, no seedmers); one rank only
+    std::vector<int64_t> h_raw_to_merged;   // per raw read of the last set_reads: its merged read, -1 = dropped (DUST, no seedmers, a mask); --gpus N: this rank's shard -> the whole sample's merged reads
     pmx::DevBuf<int64_t> d_read_off;
     pmx::DevBuf<uint32_t> d_seed_uid;
     pmx::DevBuf<uint8_t> d_seed_rev;
@@ -90,8 +90,10 @@ struct pmx_meta {
     bool reads_set = false;
     int64_t row_first = 0, row_count = 0;
     pmx::DevBuf<uint16_t> score_em;
-    // pmx_meta_assign (meta_assign.hip), per merged read of the last call; emptied by set_reads
-    bool assigned = false;
+    // pmx_meta_assign (meta_assign.hip), per merged read of the last call; emptied by set_reads.  --gpus N: per merged read of
+    // this rank's rows, as_rows of them from row_first on; after pmx_meta_assign_gather (as_gathered) the root holds all n_reads
+    bool assigned = false, as_gathered = false;
+    int64_t as_rows = 0;
     std::vector<uint8_t> as_state;
     std::vector<uint16_t> as_max;
     std::vector<uint32_t> as_lca, as_count;
@@ -103,11 +105,13 @@ struct pmx_meta {
     // breadth (pmx_meta_set_breadth; calculateBreadthRatio, src/mgsr.cpp:6518-6584), per node: total_ref_seeds once per pmx_meta,
     // br_observed / br_depth of the last pmx_meta_assign when as_breadth
     bool breadth_on = false, as_breadth = false;
+    int64_t breadth_slab_rows = 0;   // pmx_meta_set_breadth_slab: rows of the hit matrix per exchange of its merge over the ranks, 0 = what the slab buffer holds
     std::vector<uint64_t> total_ref_seeds, br_observed, br_depth;
     // pmx_meta_read_best (meta_assign.hip): per merged read its best score over ALL nodes and the number of ACTIVE nodes that
     // reach it; the active nodes of the read set as a row of assign_words(n_nodes) words, on the device and one byte a node on
     // the host (built by the first call after a set_reads).  All emptied by set_reads
-    bool best_done = false, active_built = false;
+    bool best_done = false, active_built = false, rb_gathered = false;   // (rb_rows / rb_gathered: as as_rows / as_gathered)
+    int64_t rb_rows = 0;
     std::vector<uint16_t> rb_max;
     std::vector<uint32_t> rb_nbest;
     pmx::DevBuf<unsigned long long> d_active;
@@ -167,6 +171,18 @@ template <class F>
 inline void meta_with_planes(int64_t longest, F&& launch) {
     if (longest < 128) launch(std::integral_constant<int, 7>());
     else launch(std::integral_constant<int, 16>());
+}
+
+// This rank's rows of the merged reads: all of them, or (--gpus N) a balanced contiguous slice.  The rule of pmx_meta_score,
+// which pmx_meta_assign and pmx_meta_read_best follow.  Leaves: m->row_first / row_count.
+inline void meta_own_row_slice(pmx_meta* m) {
+    m->row_first = 0;
+    m->row_count = m->n_reads;
+    if (m->dist) {
+        const int64_t rank = pmx_dist_rank(m->dist), world = pmx_dist_world(m->dist);
+        m->row_first = m->n_reads * rank / world;
+        m->row_count = m->n_reads * (rank + 1) / world - m->row_first;
+    }
 }
 
 // m->longest = the seedmers of the longest merged read; refused from 65,535 on (the scores are 16-bit)

@@ -93,12 +93,14 @@ class Meta:
     def attach_dist(self, dist):
         """--gpus N: `dist` (a Dist on this Meta's context) makes set_reads / score / em collective -- every rank calls them in
         the same order, set_reads with its own shard of the reads -- and every rank ends with the whole sample's result.
+        assign() and read_best() are collective too and work on this rank's rows of the merged reads (row_range()).
         Call before set_reads; keep `dist` alive as long as this Meta."""
         check(lib.pmx_meta_attach_dist(self._h, dist._h), "pmx_meta_attach_dist")
         self._dist = dist
 
     def row_range(self):
-        """(first, count): the merged reads whose rows scores() returns (all of them without a dist)"""
+        """(first, count): the merged reads whose rows scores() returns (all of them without a dist); with a dist valid after
+        score(), assign() or read_best()"""
         first, count = C.c_int64(0), C.c_int64(0)
         check(lib.pmx_meta_row_range(self._h, C.byref(first), C.byref(count)), "pmx_meta_row_range")
         return int(first.value), int(count.value)
@@ -216,15 +218,51 @@ class Meta:
             raise ValueError("node_taxa: no taxonomy is set, or no such node")
         return None if n < 0 else ids[:n].copy()
 
-    def assign(self, discard: float = 0.0, ambiguous: int = 0, ambiguous_ratio: float = 0.0, breadth: bool = False) -> AssignResult:
+    def set_breadth_slab(self, rows: int = 0):
+        """with a dist: rows of the breadth hit matrix per exchange of its merge over the ranks (0 = what the slab buffer holds);
+        the same value on every rank"""
+        check(lib.pmx_meta_set_breadth_slab(self._h, int(rows)), "pmx_meta_set_breadth_slab")
+
+    def _whole_raw_to_merged(self) -> np.ndarray:
+        """with a dist, collective: the whole sample's raw -> merged map on every rank, assembled from the shards' slices.  The
+        shards are contiguous in input order, rank by rank, so it is their concatenation; a zero-filled array with this rank's
+        slice (+ 1) at its place, summed over the ranks, moves it."""
+        d = self._dist
+        mine = self.raw_to_merged()
+        counts = np.zeros(d.world, np.int64)
+        counts[d.rank] = len(mine)
+        check(lib.pmx_dist_sum_i64(d._h, counts.ctypes.data, len(counts)), "pmx_dist_sum_i64")
+        whole = np.zeros(max(int(counts.sum()), 1), np.int64)
+        at = int(counts[:d.rank].sum())
+        whole[at:at + len(mine)] = mine + 1
+        check(lib.pmx_dist_sum_i64(d._h, whole.ctypes.data, len(whole)), "pmx_dist_sum_i64")
+        return whole[:int(counts.sum())] - 1
+
+    def assign(self, discard: float = 0.0, ambiguous: int = 0, ambiguous_ratio: float = 0.0, breadth: bool = False, gather: bool = False):
         """--filter-and-assign on the reads of the last set_reads: every read against every node (pmx_meta_assign).
         `ambiguous` / `ambiguous_ratio` (--ambiguous-score-threshold, -ratio) widen the nodes whose taxa count for a read from
         its best ones to those within max(ambiguous, int(max * ratio)) of its best score; they act through a taxonomy only.
-        `breadth` (--breadth-ratio): also the per-node seed breadth of the assignment, in AssignResult.breadth."""
+        `breadth` (--breadth-ratio): also the per-node seed breadth of the assignment, in AssignResult.breadth.
+        With an attached dist the call is collective and the result is of THIS RANK'S ROWS, one entry per merged read of
+        row_range() instead of per raw read (`merged` is then 0 .. count - 1; the breadth is the whole sample's on every rank).
+        `gather=True` (collective, to rank 0): rank 0 gets the whole sample's AssignResult, per raw read of the whole input and
+        equal to what one rank makes of it -- the shards must be contiguous in input order, rank by rank -- the others None."""
+        dist = getattr(self, "_dist", None)
         check(lib.pmx_meta_set_breadth(self._h, int(bool(breadth))), "pmx_meta_set_breadth")
         check(lib.pmx_meta_set_ambiguous(self._h, int(ambiguous), float(ambiguous_ratio)), "pmx_meta_set_ambiguous")
         check(lib.pmx_meta_assign(self.ctx._h, self._h, float(discard)), "pmx_meta_assign")
-        n = self.n_reads
+        n = self.n_reads if dist is None else self.row_range()[1]
+        merged = None
+        if gather:
+            if dist is None:
+                raise ValueError("assign(gather=True) needs an attached dist")
+            merged = self._whole_raw_to_merged()
+            check(lib.pmx_meta_assign_gather(self.ctx._h, self._h, 0), "pmx_meta_assign_gather")
+            if dist.rank != 0:
+                return None
+            n = self.n_reads
+        elif dist is not None:
+            merged = np.arange(n, dtype=np.int64)
         state, mx = np.zeros(n, np.uint8), np.zeros(n, np.uint16)
         lca, cnt = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         check(lib.pmx_meta_assign_reads(self._h, state.ctypes.data, mx.ctypes.data, lca.ctypes.data, cnt.ctypes.data, n), "pmx_meta_assign_reads")
@@ -244,14 +282,23 @@ class Meta:
             u = [np.zeros(n_nodes, np.uint64) for _ in range(3)]
             check(lib.pmx_meta_breadth(self._h, u[0].ctypes.data, u[1].ctypes.data, u[2].ctypes.data, n_nodes), "pmx_meta_breadth")
             numbers = tuple(x.astype(np.int64) for x in u)
-        return AssignResult(self.raw_to_merged(), state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads(), read_taxa, node_sets, numbers)
+        return AssignResult(self.raw_to_merged() if merged is None else merged, state, mx, lca, off, nodes[:off[-1]], self.index_oriented.node_heads(), read_taxa, node_sets, numbers)
 
-    def read_best(self):
+    def read_best(self, gather: bool = False):
         """per merged read of the last set_reads: (max, n_best), its best score over ALL nodes and the number of active
         nodes (active_nodes) that reach it, 0 where max is 0 (pmx_meta_read_best; the numbers of the abundance mode's
-        read-score reports).  Runs on masked reads too; needs no score()."""
+        read-score reports).  Runs on masked reads too; needs no score().  With an attached dist: collective, and the arrays
+        are of this rank's rows (row_range()); `gather=True` (collective, to rank 0): the whole sample's on rank 0, None elsewhere."""
+        dist = getattr(self, "_dist", None)
         check(lib.pmx_meta_read_best(self.ctx._h, self._h), "pmx_meta_read_best")
-        n = self.n_reads
+        n = self.n_reads if dist is None else self.row_range()[1]
+        if gather:
+            if dist is None:
+                raise ValueError("read_best(gather=True) needs an attached dist")
+            check(lib.pmx_meta_read_best_gather(self.ctx._h, self._h, 0), "pmx_meta_read_best_gather")
+            if dist.rank != 0:
+                return None
+            n = self.n_reads
         mx, nb = np.zeros(n, np.uint16), np.zeros(n, np.uint32)
         check(lib.pmx_meta_read_best_get(self._h, mx.ctypes.data, nb.ctypes.data, n), "pmx_meta_read_best_get")
         return mx, nb
@@ -264,7 +311,8 @@ class Meta:
         return out.astype(bool)
 
     def raw_to_merged(self) -> np.ndarray:
-        """per read of the last set_reads (input order): its merged read, -1 when --dust dropped it or it has no seedmers"""
+        """per read of the last set_reads (input order): its merged read, -1 when --dust dropped it, it has no seedmers or a mask
+        dropped it.  With an attached dist: per read of this rank's shard, its merged read in the whole sample's numbering"""
         out = np.zeros(int(lib.pmx_meta_num_raw_reads(self._h)), np.int64)
         check(lib.pmx_meta_raw_to_merged(self._h, out.ctypes.data, len(out)), "pmx_meta_raw_to_merged")
         return out
